@@ -3,6 +3,14 @@
 (B=8, H=16, S=4096, D=64) bf16, n=1, non-causal, on N replicated GPUs (no sharding, no RCCL on the data path).
 
   python bench.py --gpus N --steps K --warmup W [--workload m0|c1|c2|c3|c4|c5|d256|t32] [--pass fwd|bwd|fwdbwd]
+                  [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up (W steps, continued until the GPU has run the step for SETTLE_S), times exactly K steps and
+prints the line. `--full` adds everything else this script measures (the roofline loop, clock / power under load, the
+backward / fwdbwd objects of the default forward run and the CPU baseline with its accuracy figures), as described below.
+`--dump-outputs DIR` writes, after the timed steps, what the timed path's last step returned (the forward's output, the
+backward's dQ / dK / dV) as DIR/<name>.npy in float32; an output larger than its share of 60 MB is written as a fixed,
+seeded sample of its rows (dump_outputs).
 
 N > 1: bench.py launches its own N replica processes (one per GPU, gloo control plane over 127.0.0.1) when it is started
 without WORLD_SIZE; started under `python -m torch.distributed.run --nproc-per-node N ...` it joins that world instead.
@@ -13,7 +21,7 @@ A step = one pass of the hot path over the whole batch, inputs resident in HBM:
   --pass fwdbwd  forward + backward through autograd (fasn_fwd, then fasn_bwd = [delta +] dQ + dK/dV kernels)
   --pass bwd     the backward alone: one fasn_bwd call on saved (o, lse) with preallocated gradients
 Rank 0 prints ONE JSON line; `value` = whole-job steps/s = N * K / max-over-ranks(wall time of K steps).
-In the line: `roofline` (dominant kernel(s) vs the dense MFMA peak, duration from events on the launch stream, HBM traffic
+With --full, in the line: `roofline` (dominant kernel(s) vs the dense MFMA peak, duration from events on the launch stream, HBM traffic
 from the committed PMC pass of THIS libfasn.so build or null), at N=1 `cpu_baseline` (the oracle's restatement of
 slow_attention_n on the host cores, bounded sample) and `max_abs_err` against that oracle; the default forward run also
 carries `backward` / `fwdbwd` objects (same K and W, measured after the headline's timed region).
@@ -197,25 +205,35 @@ class Control:
             self.dist.destroy_process_group()
 
 
-MIN_TIMED_S = 0.05   # a timed region shorter than this is mostly launch / sync jitter (20 steps of the M0 forward are 10 ms)
+MIN_TIMED_S = 0.05   # --full: the extra passes' timed regions last at least this long (20 steps of the M0 forward are 10 ms)
+SETTLE_S = 0.2       # the headline's warm-up keeps the device busy with the step at least this long: a cold GPU runs its first launches
+                     # ~5 % slower while its clocks ramp (a few ms of warm-up steps measure the ramp, not the steady state)
 
 
-def timed(ctl, step, sync, steps, warmup, info=None):
-    """W untimed warm-up steps, then the timed region between barrier + device sync on both sides; MAX over ranks. The region is K
-    steps, repeated in whole blocks of K until it lasts at least MIN_TIMED_S (the block count comes from one untimed pilot block and
-    is agreed across ranks); the returned time is that of ONE block of K steps, `info` gets the block count and this rank's own time."""
+def timed(ctl, step, sync, steps, warmup, info=None, min_s=0.0, settle_s=0.0):
+    """W untimed warm-up steps (followed by more, in growing chunks, for at least settle_s), then the timed region between barrier +
+    device sync on both sides; MAX over ranks. The region is exactly K steps. With min_s > 0 it is repeated in whole blocks of K until
+    it lasts at least min_s (the block count comes from one untimed pilot block and is agreed across ranks); the returned time is that
+    of ONE block of K steps, `info` gets the number of timed steps and this rank's own time per step."""
     for _ in range(warmup):
         step()
     sync()
-    t0 = time.perf_counter()
-    for _ in range(steps):   # pilot block (untimed in the result): how long do K steps take here?
-        step()
-    sync()
-    pilot = max(time.perf_counter() - t0, 1e-6)
-    blocks = int(ctl.max(float(max(1, -(-1.25 * MIN_TIMED_S // pilot)))))   # 25 % margin: the pilot block is often the slowest one
-    if MIN_TIMED_S <= 0.0:
-        blocks = 1
-    blocks = min(blocks, 10000)
+    t0 = time.perf_counter()   # (after the W steps: their first launches load code objects, which is not device work)
+    chunk = 1
+    while time.perf_counter() - t0 < settle_s:
+        for _ in range(chunk):
+            step()
+        sync()
+        chunk = min(2 * chunk, 1024)
+    blocks = 1
+    if min_s > 0.0:
+        t0 = time.perf_counter()
+        for _ in range(steps):   # pilot block (untimed in the result): how long do K steps take here?
+            step()
+        sync()
+        pilot = max(time.perf_counter() - t0, 1e-6)
+        blocks = int(ctl.max(float(max(1, -(-1.25 * min_s // pilot)))))   # 25 % margin: the pilot block is often the slowest one
+        blocks = min(blocks, 10000)
     ctl.barrier()
     sync()
     t0 = time.perf_counter()
@@ -230,6 +248,32 @@ def timed(ctl, step, sync, steps, warmup, info=None):
     return ctl.max(dt)
 
 
+DUMP_BYTES = 60_000_000   # all .npy files of one --dump-outputs together stay below 64 MB
+DUMP_SEED = 20240917
+
+
+def dump_outputs(outputs, path):
+    """Write each tensor of `outputs` ({name: tensor}) as path/<name>.npy in float32. A tensor larger than its share of DUMP_BYTES
+    is written as a sample of its rows (the last dimension kept whole): a sorted set of row indices drawn without replacement by a
+    generator seeded with DUMP_SEED, so the same shape always gives the same rows. Returns {name: shape written}."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(outputs))
+    written = {}
+    for name, t in outputs.items():
+        t = t.detach()
+        if t.numel() * 4 > share:
+            rows = t.reshape(-1, t.shape[-1])
+            keep = max(1, share // (4 * rows.shape[1]))
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(rows.shape[0], size=keep, replace=False))
+            t = rows.index_select(0, torch.from_numpy(idx).to(rows.device))
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -237,16 +281,22 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="m0", choices=sorted(WORKLOADS))
     ap.add_argument("--pass", dest="which", default="fwd", choices=["fwd", "bwd", "fwdbwd"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline loop, clock / power under load, backward / fwdbwd objects, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path's last step returned as DIR/<name>.npy (float32, < 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--roofline-launches", type=int, default=0,
-                    help="back-to-back launches of the roofline loop (default: 200 forward / 60 backward; counter passes of the profile scripts use fewer)")
-    ap.add_argument("--no-extra-passes", action="store_true", help="default forward run: skip the backward / fwdbwd objects")
-    ap.add_argument("--min-timed-ms", type=float, default=50.0,
-                    help="shortest timed region (default 50 ms; the counter passes of the profile scripts pass 0: exactly K timed steps, counters serialise the launches)")
+                    help="--full: back-to-back launches of the roofline loop (default: 200 forward / 60 backward; counter passes of the profile scripts use fewer)")
+    ap.add_argument("--no-extra-passes", action="store_true", help="--full, default forward run: skip the backward / fwdbwd objects")
+    ap.add_argument("--min-timed-ms", type=float, default=None,
+                    help="repeat the K timed steps in whole blocks until the region lasts this long (default: exactly K timed steps; "
+                         "the extra passes of --full default to 50 ms)")
     ap.add_argument("--stub-step-ms", type=float, default=None,
                     help="testing only: replace the GPU step by a sleep of this many ms (exercises launch + aggregation on CPU)")
     args = ap.parse_args()
-    globals()["MIN_TIMED_S"] = args.min_timed_ms * 1e-3
+    head_min_s = (args.min_timed_ms or 0.0) * 1e-3
+    extra_min_s = MIN_TIMED_S if args.min_timed_ms is None else args.min_timed_ms * 1e-3
     if args.gpus < 1:
         sys.exit("--gpus must be >= 1")
 
@@ -270,7 +320,7 @@ def main():
         def step():
             time.sleep(args.stub_step_ms * 1e-3 * (1 + rank))   # rank-dependent: the MAX over ranks is rank N-1's time
         tinfo = {}
-        dt = timed(ctl, step, lambda: None, args.steps, args.warmup, tinfo)
+        dt = timed(ctl, step, lambda: None, args.steps, args.warmup, tinfo, min_s=head_min_s)
     else:
         import ctypes  # noqa: F401
         import torch
@@ -298,37 +348,49 @@ def main():
             with torch.no_grad():
                 out_holder["o"] = pkg.flash_attention_n(q, k, v, softmax_n_param=n, is_causal=causal, attn_mask=mask, attn_bias=bias)
 
-        qg, kg, vg = (t.detach().clone().requires_grad_() for t in (q, k, v))
+        if args.which == "fwdbwd" or args.full:
+            qg, kg, vg = (t.detach().clone().requires_grad_() for t in (q, k, v))
 
         def step_fwdbwd():
             qg.grad = kg.grad = vg.grad = None
             o = pkg.flash_attention_n(qg, kg, vg, softmax_n_param=n, is_causal=causal, attn_mask=mask, attn_bias=bias)
             o.backward(do)
+            if args.dump_outputs:
+                out_holder["o_fwdbwd"] = o
 
-        # the backward alone: one fasn_bwd ([delta +] dQ + dK/dV) on the saved forward state, gradients preallocated
-        o_s = torch.empty_like(q)
-        lse = torch.empty(B, H, S, dtype=torch.float32, device=dev)
-        m8 = None if mask is None else mask.expand(B, H, S, S).view(torch.uint8)
-        b4 = None if bias is None else bias.unsqueeze(0).expand(B, H, S, S)
-        fargs = pkg._lib.FwdArgs()
-        fa._fill_fwd(fargs, q, k, v, o_s, lse, m8, b4, n, 1.0 / D ** 0.5, causal)
-        pkg._lib.check(lib.fasn_fwd(fargs, stream), "fasn_fwd")
-        dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
-        delta = torch.empty_like(lse)
-        bargs = pkg._lib.BwdArgs()
-        fa._fill_fwd(bargs.fwd, q, k, v, o_s, lse, m8, b4, n, 1.0 / D ** 0.5, causal)
-        bargs.dout, bargs.dq, bargs.dk, bargs.dv = (fa._view4(t) for t in (do, dq, dk, dv))
-        bargs.delta = delta.data_ptr()
-        bargs.flags = 0
-        ws_bytes = lib.fasn_bwd_workspace_bytes(bargs)   # (0 with libfasn.so: the backward needs no scratch beyond delta)
-        if ws_bytes:
-            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            bargs.workspace, bargs.workspace_bytes = ws.data_ptr(), ws_bytes
+        if args.which == "bwd" or args.full:
+            # the backward alone: one fasn_bwd ([delta +] dQ + dK/dV) on the saved forward state, gradients preallocated
+            o_s = torch.empty_like(q)
+            lse = torch.empty(B, H, S, dtype=torch.float32, device=dev)
+            m8 = None if mask is None else mask.expand(B, H, S, S).view(torch.uint8)
+            b4 = None if bias is None else bias.unsqueeze(0).expand(B, H, S, S)
+            fargs = pkg._lib.FwdArgs()
+            fa._fill_fwd(fargs, q, k, v, o_s, lse, m8, b4, n, 1.0 / D ** 0.5, causal)
+            pkg._lib.check(lib.fasn_fwd(fargs, stream), "fasn_fwd")
+            dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+            delta = torch.empty_like(lse)
+            bargs = pkg._lib.BwdArgs()
+            fa._fill_fwd(bargs.fwd, q, k, v, o_s, lse, m8, b4, n, 1.0 / D ** 0.5, causal)
+            bargs.dout, bargs.dq, bargs.dk, bargs.dv = (fa._view4(t) for t in (do, dq, dk, dv))
+            bargs.delta = delta.data_ptr()
+            bargs.flags = 0
+            ws_bytes = lib.fasn_bwd_workspace_bytes(bargs)   # (0 with libfasn.so: the backward needs no scratch beyond delta)
+            if ws_bytes:
+                ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+                bargs.workspace, bargs.workspace_bytes = ws.data_ptr(), ws_bytes
 
         def step_bwd():
             pkg._lib.check(lib.fasn_bwd(bargs, stream), "fasn_bwd")
 
         steps_of = {"fwd": step_fwd, "bwd": step_bwd, "fwdbwd": step_fwdbwd}
+
+        def last_outputs():
+            """what the caller of the timed path received from its last step"""
+            if args.which == "fwd":
+                return {"out": out_holder["o"]}
+            if args.which == "bwd":
+                return {"dq": dq, "dk": dk, "dv": dv}
+            return {"out": out_holder["o_fwdbwd"], "dq": qg.grad, "dk": kg.grad, "dv": vg.grad}
 
         sensors = []
 
@@ -345,22 +407,25 @@ def main():
             e1.synchronize()
             return e0.elapsed_time(e1) / iters
 
-        # The roofline measurement (dominant kernels, back to back) runs FIRST: it is part of what this script reports anyway,
-        # and it leaves the device at its sustained clocks, so that the W warm-up + K timed steps below measure the steady
-        # state a long-running job sees rather than the power ramp of a cold GPU (+5 % on the first ~20 launches).
-        # (the forward goes through fasn_fwd_ws with the workspace it asks for, like the front end does: split-K partials or the
-        # work counters of the persistent bias launches)
-        fws_bytes = lib.fasn_fwd_workspace_bytes(fargs)
-        fws = torch.empty(max(fws_bytes, 16), dtype=torch.uint8, device=dev)
-        raw = {"fwd": (lambda: lib.fasn_fwd_ws(fargs, fws.data_ptr(), fws_bytes, stream)) if fws_bytes else (lambda: lib.fasn_fwd(fargs, stream)),
-               "bwd": lambda: lib.fasn_bwd(bargs, stream)}
-        if args.which in raw:
-            kernel_ms = kernel_time(raw[args.which], args.roofline_launches or max(200 if args.which == "fwd" else 60, args.steps))
-        else:
-            kernel_ms = kernel_time(raw["fwd"], 100) + kernel_time(raw["bwd"], 60)
+        if args.full:
+            # The roofline measurement (dominant kernels, back to back) runs FIRST: it leaves the device at its sustained clocks, so
+            # that the W warm-up + K timed steps below measure the steady state a long-running job sees rather than the power ramp
+            # of a cold GPU (+5 % on the first ~20 launches). A plain run leaves that to its W warm-up steps.
+            # (the forward goes through fasn_fwd_ws with the workspace it asks for, like the front end does: split-K partials or the
+            # work counters of the persistent bias launches)
+            fws_bytes = lib.fasn_fwd_workspace_bytes(fargs)
+            fws = torch.empty(max(fws_bytes, 16), dtype=torch.uint8, device=dev)
+            raw = {"fwd": (lambda: lib.fasn_fwd_ws(fargs, fws.data_ptr(), fws_bytes, stream)) if fws_bytes else (lambda: lib.fasn_fwd(fargs, stream)),
+                   "bwd": lambda: lib.fasn_bwd(bargs, stream)}
+            if args.which in raw:
+                kernel_ms = kernel_time(raw[args.which], args.roofline_launches or max(200 if args.which == "fwd" else 60, args.steps))
+            else:
+                kernel_ms = kernel_time(raw["fwd"], 100) + kernel_time(raw["bwd"], 60)
 
         tinfo = {}
-        dt = timed(ctl, steps_of[args.which], sync, args.steps, args.warmup, tinfo)
+        dt = timed(ctl, steps_of[args.which], sync, args.steps, args.warmup, tinfo, min_s=head_min_s, settle_s=SETTLE_S)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(last_outputs(), args.dump_outputs)
 
         def sample_under_load(fn, ms):
             """Clock / power under THIS load, AFTER everything that is timed: about 0.4 s of back-to-back launches, the amdgpu
@@ -384,11 +449,11 @@ def main():
             if last is not None:
                 sensors.append((last, pmax))
 
-        if args.which == "fwd" and args.workload == "m0" and world == 1 and not args.no_extra_passes:
+        if args.full and args.which == "fwd" and args.workload == "m0" and world == 1 and not args.no_extra_passes:
             # driver-visible backward numbers next to the headline (same K and W, measured after the headline's timed region)
             for w in ("bwd", "fwdbwd"):
                 winfo = {}
-                dtw = timed(ctl, steps_of[w], sync, args.steps, args.warmup, winfo)
+                dtw = timed(ctl, steps_of[w], sync, args.steps, args.warmup, winfo, min_s=extra_min_s)
                 kms = kernel_time(raw["bwd"], 60) if w == "bwd" else None
                 alg, exe = pass_flops(w, B, H, S, D, causal, vis)
                 extra["backward" if w == "bwd" else "fwdbwd"] = {
@@ -400,8 +465,9 @@ def main():
 
         # every rank samples ITS GPU while all of them run the same loop: a bent 1 -> N curve can then be attributed from this one
         # record (a shared power budget shows as lower clocks on all ranks, host launch contention as equal clocks and longer steps)
-        ctl.barrier()
-        sample_under_load(raw[args.which] if args.which in raw else raw["bwd"], kernel_ms)
+        if args.full:
+            ctl.barrier()
+            sample_under_load(raw[args.which] if args.which in raw else raw["bwd"], kernel_ms)
 
     mine = {"rank": rank, "ms_per_step": tinfo.get("local_ms_per_step")}
     if not stub and sensors and sensors[0][0]:
@@ -417,7 +483,7 @@ def main():
     line = {
         "metric": f"attn-ops/sec (flash_attention_n {names[args.which]})", "value": ops_per_s, "unit": "attn-ops/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
-        "timed_steps": tinfo.get("timed_steps", args.steps),   # the timed region: whole blocks of `steps` steps, at least 50 ms of work
+        "timed_steps": tinfo.get("timed_steps", args.steps),   # the timed region: `steps` steps (whole blocks of them with --min-timed-ms)
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": dname, "data": "synthetic",
         "config": {"workload": f"{args.workload}: flash_attention_n {args.which} (B={B},H={H},S={S},D={D}) n={n} causal={causal}"
                                + (" + ALiBi bias [H,L,S] + key-padding mask [B,1,1,S]" if args.workload == "c4" else ""),
@@ -429,7 +495,7 @@ def main():
         line["per_rank"] = per_rank   # each rank's own time per step and its GPU's clock / power under the common load
     if stub:
         line["data"] = "stub (no GPU work: launch + aggregation test)"
-    else:
+    elif args.full:
         # the kernels behind the timed call, as the library's own launch tables name them (fasn_launch_plan: the host side of the call run
         # with recording launch sites - the names are those of the code objects a rocprofv3 kernel trace of this command shows)
         plans = {"fwd": [pkg._lib.FASN_PLAN_FWD_WS if fws_bytes else pkg._lib.FASN_PLAN_FWD], "bwd": [pkg._lib.FASN_PLAN_BWD]}
@@ -457,7 +523,7 @@ def main():
                                               "frac_of_clock_adjusted_peak": achieved / (peak * mhz / 2400.0)}
         line.update(extra)
 
-    if not stub and world == 1 and not args.no_cpu_baseline:
+    if args.full and not stub and world == 1 and not args.no_cpu_baseline:
         # CPU baseline + accuracy on a bounded sample: batch 0, a few heads, through the oracle's eager restatement of
         # slow_attention_n in the native dtype (exactly what the reference runs on CPU), all host threads.
         import platform

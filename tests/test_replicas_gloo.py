@@ -57,7 +57,8 @@ def _bench_line(cmd, env=None):
 def test_bench_py_launches_its_own_two_replicas():
     """bench.py's REAL N=2 path (self-spawn, gloo rendezvous on 127.0.0.1, barrier, MAX over ranks, whole-job value) with the
     GPU step replaced by a rank-dependent sleep: rank r sleeps (r+1)*10 ms per step."""
-    r, lines = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--stub-step-ms", "10"],
+    r, lines = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--stub-step-ms", "10",
+                            "--min-timed-ms", "50"],
                            env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr
     assert len(lines) == 1                      # rank 0 prints ONE line
@@ -81,9 +82,9 @@ def test_bench_py_counter_pass_mode_runs_exactly_k_steps():
 
 
 def test_bench_py_times_at_least_50_ms():
-    """K steps of 1 ms would be a 3 ms timed region: the region is repeated in whole blocks of K until it lasts >= 50 ms, `steps` stays K"""
-    r, lines = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--stub-step-ms", "1"],
-                           env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
+    """--min-timed-ms 50: K steps of 1 ms would be a 3 ms timed region: the region is repeated in whole blocks of K until it lasts >= 50 ms, `steps` stays K"""
+    r, lines = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--stub-step-ms", "1",
+                            "--min-timed-ms", "50"], env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr
     line = lines[0]
     assert line["steps"] == 3 and line["timed_steps"] % 3 == 0 and line["timed_steps"] >= 30

@@ -7,6 +7,6 @@ timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -5 | tee $O/pytest_
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2 | tee $O/smoke.log
 (cd tools && timeout 600 ./fasn_harness test 0 1 2>&1 | tail -4) | tee $O/harness_test.log
 {
-echo "=== c4 fwd: in-tree vs prio8"; bash tools/ab_libs.sh "bench.py --workload c4 --pass fwd --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes" . prio8
-echo "=== c4 bwd: in-tree vs wsb vs wsa"; bash tools/ab_libs.sh "bench.py --workload c4 --pass bwd --steps 10 --warmup 3 --no-cpu-baseline --no-extra-passes" . wsb wsa
+echo "=== c4 fwd: in-tree vs prio8"; bash tools/ab_libs.sh "bench.py --full --workload c4 --pass fwd --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes" . prio8
+echo "=== c4 bwd: in-tree vs wsb vs wsa"; bash tools/ab_libs.sh "bench.py --full --workload c4 --pass bwd --steps 10 --warmup 3 --no-cpu-baseline --no-extra-passes" . wsb wsa
 } 2>&1 | tee $O/prio_ab.log

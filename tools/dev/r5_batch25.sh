@@ -6,5 +6,5 @@ cd $R
 timeout 2400 python -m pytest tests -m gpu -x -q 2>&1 | tail -3 | tee $O/pytest_gpu_tail.log
 for wp in "c5 fwd" "m0 fwd" "c3 fwd"; do
   set -- $wp
-  echo "=== $1 $2"; bash tools/ab_libs.sh "bench.py --workload $1 --pass $2 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes" . staticdeal . staticdeal . staticdeal
+  echo "=== $1 $2"; bash tools/ab_libs.sh "bench.py --full --workload $1 --pass $2 --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes" . staticdeal . staticdeal . staticdeal
 done 2>&1 | tee $O/dynamic_deal_product_ab.log

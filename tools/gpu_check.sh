@@ -4,10 +4,10 @@ R=${GRAFT_REPO_ROOT:-/root/repo}; T=$1; shift; O=$R/gpurun_out/$T; mkdir -p $O
 cd $R
 timeout 2400 python -m pytest tests -m gpu -q -x --durations=15 "$@" > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
 tail -25 $O/pytest.log
-python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; cut -c1-1800 $O/bench_default.json
+python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err; cut -c1-1800 $O/bench_default.json
 : > $O/bench_all.jsonl
 for w in m0 c2 c3 c5 c4; do for p in fwd bwd fwdbwd; do
-  python bench.py --workload $w --pass $p --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes >> $O/bench_all.jsonl 2>> $O/bench_all.err
+  python bench.py --full --workload $w --pass $p --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes >> $O/bench_all.jsonl 2>> $O/bench_all.err
 done; done
 python - <<PY
 import json

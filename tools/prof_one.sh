@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=$1; W=$2; P=$3; O=$R/gpurun_out/$T; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 SQ1="SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_LDS"
-n=${W}_$P; B="python $R/bench.py --workload $W --pass $P --steps 3 --warmup 1 --no-cpu-baseline --no-extra-passes"; D=$O/$n; mkdir -p $D
+n=${W}_$P; B="python $R/bench.py --full --workload $W --pass $P --steps 3 --warmup 1 --no-cpu-baseline --no-extra-passes"; D=$O/$n; mkdir -p $D
 timeout 600 rocprofv3 --kernel-trace --stats -d $D/kt -o kt -- $B > $D/kt.log 2>&1
 for set in FETCH_SIZE WRITE_SIZE "$SQ1"; do
   c=$(echo $set | cut -d" " -f1); timeout 600 rocprofv3 --pmc $set -d $D/pmc_$c -o pmc -- $B --roofline-launches 40 > $D/pmc_$c.log 2>&1

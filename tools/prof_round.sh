@@ -10,7 +10,7 @@ SQ1="SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE
 SQ2="SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 run() {   # run WORKLOAD PASS counter-set...
   w=$1; p=$2; shift 2; D=$O/${w}_${p}; mkdir -p $D
-  B="python $R/bench.py --workload $w --pass $p --steps 3 --warmup 1 --no-cpu-baseline --no-extra-passes"
+  B="python $R/bench.py --full --workload $w --pass $p --steps 3 --warmup 1 --no-cpu-baseline --no-extra-passes"
   timeout 300 rocprofv3 --kernel-trace --stats -d $D/kt -o kt -- $B > $D/kt.log 2>&1
   for set in "$@"; do
     n=$(echo $set | cut -d" " -f1); timeout 300 rocprofv3 --pmc $set -d $D/pmc_$n -o pmc -- $B > $D/pmc_$n.log 2>&1

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 SQ1="SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_INSTS_LDS GRBM_GUI_ACTIVE"
 SQ2="SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE"
 run() {   # run NAME "bench args" LAUNCHES counter-set...   (NAME = workload_pass)
-  n=$1; B="python $R/bench.py $2 --steps 3 --warmup 1 --no-cpu-baseline --no-extra-passes"; L=$3; shift 3; D=$O/$n; mkdir -p $D
+  n=$1; B="python $R/bench.py --full $2 --steps 3 --warmup 1 --no-cpu-baseline --no-extra-passes"; L=$3; shift 3; D=$O/$n; mkdir -p $D
   timeout 300 rocprofv3 --kernel-trace --stats -d $D/kt -o kt -- $B > $D/kt.log 2>&1
   for set in "$@"; do
     c=$(echo $set | cut -d" " -f1)
@@ -47,12 +47,12 @@ if [ "$PART" = "b" ] || [ "$PART" = "all" ]; then
   done
   fi
   cd $R
-  python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+  python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
   : > $O/bench_all.jsonl
   for w in m0 c2 c3 c5 c4 d256; do for p in fwd bwd fwdbwd; do
-    python bench.py --workload $w --pass $p --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes >> $O/bench_all.jsonl 2>> $O/bench_all.err
+    python bench.py --full --workload $w --pass $p --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes >> $O/bench_all.jsonl 2>> $O/bench_all.err
   done; done
-  python bench.py --workload c1 --steps 50 --warmup 5 >> $O/bench_all.jsonl 2>> $O/bench_all.err
+  python bench.py --full --workload c1 --steps 50 --warmup 5 >> $O/bench_all.jsonl 2>> $O/bench_all.err
   python - <<PY
 import json
 for l in open("$O/bench_all.jsonl"):
