@@ -22,6 +22,7 @@ FASN_PLAN_FWD, FASN_PLAN_BWD, FASN_PLAN_FWD_WS = 0, 1, 2
 EXPORTS = (
     "fasn_abi_version", "fasn_strerror", "fasn_supported", "fasn_fwd", "fasn_fwd_path", "fasn_bwd_path", "fasn_fwd_workspace_bytes", "fasn_fwd_ws",
     "fasn_bwd_workspace_bytes", "fasn_bwd", "fasn_rng_advance", "fasn_launch_plan",
+    "fasn_fwd_n", "fasn_bwd_dn_workspace_bytes", "fasn_bwd_dn",
     "fasn_softmax_n_fwd", "fasn_softmax_n_bwd", "fasn_moments",
 )
 
@@ -92,6 +93,12 @@ def load():
     lib.fasn_fwd_ws.argtypes = [POINTER(FwdArgs), c_void_p, c_size_t, c_void_p]
     lib.fasn_bwd.restype = c_int32
     lib.fasn_bwd.argtypes = [POINTER(BwdArgs), c_void_p]
+    lib.fasn_fwd_n.restype = c_int32
+    lib.fasn_fwd_n.argtypes = [POINTER(FwdArgs), c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]
+    lib.fasn_bwd_dn_workspace_bytes.restype = c_size_t
+    lib.fasn_bwd_dn_workspace_bytes.argtypes = [POINTER(BwdArgs)]
+    lib.fasn_bwd_dn.restype = c_int32
+    lib.fasn_bwd_dn.argtypes = [POINTER(BwdArgs), c_void_p, c_int64, c_int64, c_void_p, c_size_t, c_void_p]
     lib.fasn_rng_advance.restype = c_int32
     lib.fasn_rng_advance.argtypes = [c_void_p, c_void_p, c_uint64, c_void_p]
     lib.fasn_bwd_workspace_bytes.restype = c_size_t

@@ -9,6 +9,7 @@
 #include "fasn.h"
 #include "fasn_launch.h"
 #include "fasn_bwd_launch.h"
+#include "fasn_bwd_dn.h"
 
 using namespace fasn;
 
@@ -245,6 +246,8 @@ int build_fwd(const fasn_fwd_args* a, FwdParams& p, FwdLaunch& l, int pass = 0) 
         p.vbytes = (unsigned)vb;
     }
     p.n = a->softmax_n;
+    p.nt = nullptr;   // per-(batch, head) n: set by fasn_fwd_n only
+    p.nsb = p.nsh = 0;
 
     l.dtype = a->dtype;
     l.D = a->D;
@@ -422,11 +425,15 @@ size_t fasn_fwd_workspace_bytes(const fasn_fwd_args* args) {
     return xq_wanted(p, l) ? kXqBytes : 0;
 }
 
-int fasn_fwd_ws(const fasn_fwd_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+// fasn_fwd_ws, and fasn_fwd_n with its per-(batch, head) n (nt != nullptr): the same plan, the kernels only read n elsewhere
+static int fwd_ws(const fasn_fwd_args* args, void* workspace, size_t workspace_bytes, hipStream_t stream, const float* nt, int nsb, int nsh) {
     FwdParams p;
     FwdLaunch l;
     const int rc = build_fwd(args, p, l);
     if (rc) return rc;
+    p.nt = nt;
+    p.nsb = nsb;
+    p.nsh = nsh;
     int tps;
     const int nsplit = plan_splitk(args, p, l, tps);
     if (nsplit > 1 && workspace != nullptr && workspace_bytes >= splitk_bytes(args, nsplit)) {
@@ -435,13 +442,31 @@ int fasn_fwd_ws(const fasn_fwd_args* args, void* workspace, size_t workspace_byt
         p.tps = tps;
         p.part_o = static_cast<float*>(workspace);
         p.part_ml = p.part_o + (size_t)args->B * args->H * nsplit * args->Sq * args->D;
-        return launch_fwd_splitk(p, l, (hipStream_t)stream);
+        return launch_fwd_splitk(p, l, stream);
     }
     if (nsplit <= 1 && workspace != nullptr && workspace_bytes >= kXqBytes && xq_wanted(p, l)) {
         if (reinterpret_cast<uintptr_t>(workspace) % 4) return FASN_EALIGN;
         p.xq = static_cast<int*>(workspace);
     }
-    return dispatch_fwd(p, l, (hipStream_t)stream);
+    return dispatch_fwd(p, l, stream);
+}
+
+int fasn_fwd_ws(const fasn_fwd_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return fwd_ws(args, workspace, workspace_bytes, (hipStream_t)stream, nullptr, 0, 0);
+}
+
+int fasn_fwd_n(const fasn_fwd_args* args, const float* n, int64_t n_stride_b, int64_t n_stride_h, void* workspace, size_t workspace_bytes,
+               fasn_stream_t stream) {
+    if (n == nullptr) return fasn_fwd_ws(args, workspace, workspace_bytes, stream);
+    if (args == nullptr) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(n) % 4) return FASN_EALIGN;
+    // the kernels index n with 32-bit offsets: every (b, h) must address an element below 2^31
+    if (n_stride_b < 0 || n_stride_h < 0 || (args->B > 0 && args->H > 0 &&
+        (int64_t)(args->B - 1) * n_stride_b + (int64_t)(args->H - 1) * n_stride_h >= (1ll << 31)))
+        return FASN_EINVAL;
+    fasn_fwd_args a = *args;
+    a.softmax_n = 0.f;   // ignored: the value check of the scalar does not apply
+    return fwd_ws(&a, workspace, workspace_bytes, (hipStream_t)stream, n, (int)n_stride_b, (int)n_stride_h);
 }
 
 #ifdef FASN_DEV_VARIANTS
@@ -557,6 +582,58 @@ int fasn_bwd(const fasn_bwd_args* a, fasn_stream_t stream) {
         return launch_bwd_dbias(p, l, a->dbias.stride[0] == 0 ? 1 : a->fwd.B, a->dbias.stride[1] == 0 ? 1 : a->fwd.H, dbias_f32, (hipStream_t)stream);
     }
     return launch_bwd(p, l, (hipStream_t)stream);
+}
+
+// dn: the stage-1 plan of fasn_bwd_dn (rows per workgroup from the row size of O); FASN_OK or the FASN_E* code of the call
+static int bwd_dn_plan(const fasn_bwd_args* a, DnParams& d) {
+    if (a == nullptr) return FASN_EINVAL;
+    fasn_fwd_args f = a->fwd;
+    f.softmax_n = 0.f;   // (a forward through fasn_fwd_n ignored the scalar; so does its gradient)
+    FwdParams fp;
+    FwdLaunch l;
+    int rc = build_fwd(&f, fp, l);
+    if (rc) return rc;
+    if (f.lse == nullptr) return FASN_EINVAL;
+    const int esize = f.dtype == FASN_DTYPE_F32 ? 4 : 2;
+    if ((rc = check_view(a->dout, true, esize))) return rc;
+    d.o = (const char*)f.o.ptr;
+    d.dout = (const char*)a->dout.ptr;
+    d.lse = f.lse;
+    for (int i = 0; i < 3; ++i) {
+        d.os[i] = f.o.stride[i];
+        d.dos[i] = a->dout.stride[i];
+    }
+    d.B = f.B;
+    d.H = f.H;
+    d.Sq = f.Sq;
+    d.cpr = f.Dv * esize / 16;   // 4 .. 32 for the supported head dims
+    d.rpw = dn_rows_per_workgroup(d.cpr);
+    d.nchunk = (f.Sq + d.rpw - 1) / d.rpw;
+    return FASN_OK;
+}
+
+size_t fasn_bwd_dn_workspace_bytes(const fasn_bwd_args* args) {
+    DnParams d;
+    if (bwd_dn_plan(args, d)) return 0;
+    return (size_t)d.B * d.H * d.nchunk * sizeof(float);
+}
+
+int fasn_bwd_dn(const fasn_bwd_args* args, float* dn, int64_t dn_stride_b, int64_t dn_stride_h, void* workspace, size_t workspace_bytes,
+                fasn_stream_t stream) {
+    DnParams d;
+    const int rc = bwd_dn_plan(args, d);
+    if (rc) return rc;
+    if (dn == nullptr || dn_stride_b < 0 || dn_stride_h < 0) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(dn) % 4) return FASN_EALIGN;
+    if (workspace == nullptr || workspace_bytes < (size_t)d.B * d.H * d.nchunk * sizeof(float)) return FASN_EWORKSPACE;
+    if (reinterpret_cast<uintptr_t>(workspace) % 16) return FASN_EALIGN;
+    d.part = static_cast<float*>(workspace);
+    d.dn = dn;
+    d.dsb = dn_stride_b;
+    d.dsh = dn_stride_h;
+    d.Bo = dn_stride_b == 0 ? 1 : d.B;   // a zero stride: the sum over that dimension
+    d.Ho = dn_stride_h == 0 ? 1 : d.H;
+    return launch_bwd_dn(d, args->fwd.dtype, (hipStream_t)stream);
 }
 
 int fasn_launch_plan(const fasn_bwd_args* args, int32_t which, char* buf, size_t cap) {

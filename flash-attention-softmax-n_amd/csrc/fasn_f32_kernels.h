@@ -128,8 +128,9 @@ __global__ void __launch_bounds__(256) fasn_f32_fwd_kernel(const FwdParams p) {
     sK.init(tid, p.ks[2]);
     sV.init(tid, p.vs[2]);
     u32x4 stg[St::NLD];   // one staging set: the next tile's K rows travel during the first S chain, its V rows during the second
-    const bool sink = p.n > 0.f;
-    float m_run = sink ? 0.f : -INFINITY, l_run = (sink && hi == 0) ? p.n : 0.f;
+    const float n_p = item_n(p, b, h);
+    const bool sink = n_p > 0.f;
+    float m_run = sink ? 0.f : -INFINITY, l_run = (sink && hi == 0) ? n_p : 0.f;
     f32x16 oacc[DB];
 #pragma unroll
     for (int d = 0; d < DB; ++d)

@@ -89,10 +89,20 @@ struct FwdParams {
     float* part_o;   // [B*H][nsplit][Sq][D]
     float* part_ml;  // [B*H][nsplit][Sq][2]
     int* xq;         // eight zeroed item counters (caller's workspace, fasn_fwd_ws): dynamic deal of the (head, query block) items across XCDs; nullptr = static deal
+    const float* nt; // per-(batch, head) softmax_n (fasn_fwd_n): item (b, h) reads nt[b * nsb + h * nsh] instead of `n`; nullptr = `n` for every item
+    int nsb, nsh;
 #ifdef FASN_DEV_VARIANTS
     unsigned long long* timeline;   // developer library: per workgroup {t_entry, t_loop, t_epilogue, t_end, hw_id, xcc_id, ntiles, 0} (100 MHz clock)
 #endif
 };
+// softmax_n of the work item (b, h): the caller's per-(batch, head) tensor (fasn_fwd_n) or the call's scalar. Wave-uniform: one load per item,
+// the value is moved to an SGPR (a run-time select rather than a template flag: the scalar-n kernels keep their instantiations)
+FASN_DEV float item_n(const FwdParams& p, int b, int h) {
+    if (p.nt == nullptr) return p.n;
+    const int i = __builtin_amdgcn_readfirstlane(b * p.nsb + h * p.nsh);
+    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.nt[i])));
+}
+
 #ifdef FASN_DEV_VARIANTS
 #define FASN_STAMP(slot) do { if (p.timeline != nullptr && threadIdx.x == 0) p.timeline[(size_t)blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
 #else
@@ -338,6 +348,10 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     // always walk nqblk + 1 tiles: every workgroup of a paired launch costs the same. Used when the launch is many rounds long
     // (equal workgroups quantise the last round).
     const int npass = ((PAIRABLE && p.pair && qi != p.nqblk - 1 - qi) || (KPAIR && bh2 >= 0)) ? 2 : 1;
+    // softmax_n of the items (fasn_fwd_n: per (b, h)), read once before the walk: a paired second pass is the same head, a length-paired
+    // one head bh2. (Reading it inside the pass loop kept the pointer and its strides live across the first pass: SGPR spills.)
+    const float n_item0 = item_n(p, bh / p.H, bh % p.H);
+    const float n_item1 = (KPAIR && bh2 >= 0) ? item_n(p, bh2 / p.H, bh2 % p.H) : n_item0;
     for (int pass = 0; pass < npass; ++pass) {
     if ((PAIRABLE || KPAIR) && pass) __syncthreads();
     if (KPAIR && pass) bh = bh2;
@@ -482,13 +496,13 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     // SEED: -m (0 while m is still -inf) in all 16 registers of an accumulator-shaped tuple = the C operand of the first QK^T MFMA
     // of every key block; rewritten only when the exact path moves the max. `unseeded`: some row has no finite max yet.
     f32x16 mseed[(SEED && !VEC) ? QB : 1];   // the vector general modes build their start values per element from -m
-    bool unseeded = !(p.n > 0.f && split == 0);
+    float n_p = (KPAIR && pass) ? n_item1 : n_item0;
+    bool unseeded = !(n_p > 0.f && split == 0);
 #pragma unroll
     for (int qb = 0; qb < ((SEED && !VEC) ? QB : 1); ++qb)
 #pragma unroll
         for (int r = 0; r < 16; ++r) mseed[qb][r] = 0.f;
     const int hi_p = FOLD ? (fresh_lane_id() >> 5) : hi;
-    float n_p = p.n;
     if constexpr (FOLD) asm volatile("" : "+s"(n_p));   // (per pass: not hoisted in front of the pass loop and parked in scratch)
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) {

@@ -145,8 +145,9 @@ __global__ void __launch_bounds__(512, 2) fasn_fwd_ws256_kernel(const FwdParams 
     }
     // softmax_n state of the lane's row: the sink column (logit 0, weight n) is the start value; each half-wave sums its own 16 keys
     // per block and the halves are merged at the end (the maximum is shared every block, so both halves scale alike)
-    float m_run = p.n > 0.f ? 0.f : -INFINITY;
-    float l_run = (p.n > 0.f && hi == 0) ? p.n : 0.f;
+    const float n_p = item_n(p, b, h);
+    float m_run = n_p > 0.f ? 0.f : -INFINITY;
+    float l_run = (n_p > 0.f && hi == 0) ? n_p : 0.f;
     const int wave_first_vis = qw0 + coff, wave_last_vis = qw0 + 31 + coff;
     // wave-uniform classification of (this wave's 32 rows) x (key block u): identical for the A and the B wave of a row block
     auto classify = [&](int u, bool& skip, bool& need_mask, uint32_t& kpb) {

@@ -156,13 +156,26 @@ def _cache():
 
 
 class _Plan:
-    __slots__ = ("fwd", "fwd_ws", "bwd", "bwd_ws", "path", "bwd_path")
+    __slots__ = ("fwd", "fwd_ws", "bwd", "bwd_ws", "path", "bwd_path", "dn_ws")
+
+
+# n given as a tensor (per batch element / head): its values travel as a pointer per call (fasn_fwd_n), never in the cached argument block,
+# whose softmax_n is then 0 - so a cached plan can never replay another call's n
+_N_TENSOR = "tensor"
+
+
+def _n_strides(nt: Tensor):
+    """(batch, head) element strides of a [1 or B, 1 or H] fp32 n for fasn_fwd_n / fasn_bwd_dn: 0 over a size-1 dimension (broadcast on the way
+    in, the sum over that dimension on the way out)."""
+    return (nt.stride(0) if nt.shape[0] > 1 else 0), (nt.stride(1) if nt.shape[1] > 1 else 0)
 
 
 _WARNED_SLOW = set()
 
 
 def _plan_for(q, k, v, mask, bias, n, scale, causal, dropout_p):
+    if isinstance(n, Tensor) or n is _N_TENSOR:
+        n = _N_TENSOR
     key = (_sig(q), _sig(k), _sig(v), _sig(mask), _sig(bias), n, scale, causal, dropout_p, q.device.index)
     c = _cache()
     pl = c.get(key)
@@ -174,10 +187,12 @@ def _plan_for(q, k, v, mask, bias, n, scale, causal, dropout_p):
         o = torch.empty((B, H, L, v.shape[3]), dtype=q.dtype, device=q.device)
         lse = torch.empty((B, H, L), dtype=torch.float32, device=q.device)
         pl = _Plan()
+        n_val = 0.0 if n is _N_TENSOR else n
         pl.fwd = FwdArgs()
-        _fill_fwd(pl.fwd, q, k, v, o, lse, mask, bias, n, scale, causal, dropout_p)
+        _fill_fwd(pl.fwd, q, k, v, o, lse, mask, bias, n_val, scale, causal, dropout_p)
         pl.bwd = BwdArgs()
-        _fill_fwd(pl.bwd.fwd, q, k, v, o, lse, mask, bias, n, scale, causal, dropout_p)
+        _fill_fwd(pl.bwd.fwd, q, k, v, o, lse, mask, bias, n_val, scale, causal, dropout_p)
+        pl.dn_ws = None   # asked at the first backward that wants the gradient of a tensor n
         dk = torch.empty((B, k.shape[1], k.shape[2], k.shape[3]), dtype=q.dtype, device=q.device)   # contiguous outputs: only the strides matter here
         pl.bwd.dout, pl.bwd.dq, pl.bwd.dk, pl.bwd.dv = _view4(o), _view4(o), _view4(dk), _view4(dk)
         pl.bwd.flags = 0
@@ -225,7 +240,11 @@ def _launch_fwd(q, k, v, mask, bias, n, scale, causal, dropout_p, rng):
     dev = q.device
 
     def launch():
-        if pl.fwd_ws:
+        if isinstance(n, Tensor):   # per-(batch, head) n: same plan as fasn_fwd_ws, n read per work item
+            ws = torch.empty(pl.fwd_ws, dtype=torch.uint8, device=dev) if pl.fwd_ws else None
+            nsb, nsh = _n_strides(n)
+            _lib.check(lib.fasn_fwd_n(a, n.data_ptr(), nsb, nsh, None if ws is None else ws.data_ptr(), pl.fwd_ws, _stream_ptr(dev)), "fasn_fwd_n")
+        elif pl.fwd_ws:
             ws = torch.empty(pl.fwd_ws, dtype=torch.uint8, device=dev)
             _lib.check(lib.fasn_fwd_ws(a, ws.data_ptr(), pl.fwd_ws, _stream_ptr(dev)), "fasn_fwd_ws")
         else:
@@ -248,12 +267,16 @@ class _FlashAttentionSoftmaxN(torch.autograd.Function):
     """autograd glue; same role as _FlashAttentionN (flash_attn_triton.py:241-336)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, mask, bias, n: float, scale: float, causal: bool, dropout_p: float = 0.0, rng=None, bias_small: bool = False):
+    def forward(ctx, q, k, v, mask, bias, n, scale: float, causal: bool, dropout_p: float = 0.0, rng=None, bias_small: bool = False):
         # bias_small: `bias` is the caller's [1 or B, 1 or H, L, S] tensor, not yet expanded - its gradient then comes back in that
         # shape, summed over the broadcast batch / head dimensions inside the dbias kernel (no [B,H,L,S] buffer)
+        # n: a float, or a [1 or B, 1 or H] fp32 tensor (per batch element / head; its gradient comes back in that shape, fasn_bwd_dn)
         bias_k = bias.expand(q.shape[0], q.shape[1], q.shape[2], k.shape[2]) if bias_small else bias
         o, lse = _launch_fwd(q, k, v, mask, bias_k, n, scale, causal, dropout_p, rng)
         ctx.save_for_backward(q, k, v, o, lse, mask, bias)
+        ctx.n_shape = tuple(n.shape) if isinstance(n, Tensor) else None
+        if isinstance(n, Tensor):
+            n = _N_TENSOR
         ctx.n, ctx.scale, ctx.causal, ctx.dropout_p, ctx.rng, ctx.bias_small = n, scale, causal, dropout_p, rng, bias_small
         return o
 
@@ -315,6 +338,10 @@ class _FlashAttentionSoftmaxN(torch.autograd.Function):
                     warnings.warn("flash_attention_n backward: dQ / dK / dV of this call take the element-load kernels (3-5x slower) although its forward "
                                   "is on the vector path. See fasn_bwd_path in include/fasn.h.", RuntimeWarning, stacklevel=2)
 
+        dn = None
+        if ctx.n_shape is not None and ctx.needs_input_grad[5]:
+            dn = torch.empty(ctx.n_shape, dtype=torch.float32, device=dev)
+
         def launch():
             if pl.bwd_ws:
                 ws = torch.empty(pl.bwd_ws, dtype=torch.uint8, device=dev)
@@ -322,6 +349,12 @@ class _FlashAttentionSoftmaxN(torch.autograd.Function):
             rc = lib.fasn_bwd(a, _stream_ptr(dev))
             if rc:
                 _lib.check(rc, "fasn_bwd")
+            if dn is not None:   # dL/dn = -sum_i delta_i exp(-lse_i), summed over the dimensions n broadcasts over
+                if pl.dn_ws is None:
+                    pl.dn_ws = lib.fasn_bwd_dn_workspace_bytes(a)
+                wsn = torch.empty(pl.dn_ws, dtype=torch.uint8, device=dev)
+                dsb, dsh = _n_strides(dn)
+                _lib.check(lib.fasn_bwd_dn(a, dn.data_ptr(), dsb, dsh, wsn.data_ptr(), pl.dn_ws, _stream_ptr(dev)), "fasn_bwd_dn")
 
         try:
             if _current_device() == dev.index:   # the usual case: no device-guard object (about 10 us of host time per step)
@@ -335,11 +368,28 @@ class _FlashAttentionSoftmaxN(torch.autograd.Function):
             a.dbias.ptr = None
         if dbias is not None and dbias.dtype != bias.dtype:
             dbias = dbias.to(bias.dtype)
-        return dq, dk, dv, None, dbias, None, None, None, None, None, None
+        return dq, dk, dv, None, dbias, dn, None, None, None, None, None
 
 
 def _pad_feature(t: Tensor, d: int) -> Tensor:
     return t if t.shape[-1] == d else torch.nn.functional.pad(t, (0, d - t.shape[-1]))
+
+
+def _n_tensor(n: Tensor, query: Tensor) -> Tensor:
+    """softmax_n given as a tensor that broadcasts to [B, H] ([H], [1, H], [B, 1], [B, H] or 0-d; H = query heads): the fp32 [1 or B,
+    1 or H] view the kernels read per (batch, head). `.float()` and the reshape are autograd ops, so the gradient reaches the caller's
+    tensor in its own shape and dtype. The values are not looked at (no host round trip: capturable)."""
+    B, H = query.shape[0], query.shape[1]
+    if not n.is_floating_point():
+        raise TypeError(f"softmax_n_param as a tensor must be floating point; got {n.dtype}")
+    if n.device != query.device:
+        raise ValueError(f"softmax_n_param is on {n.device}, query on {query.device}: pass n on the query's device")
+    if n.dim() > 2:
+        raise ValueError(f"softmax_n_param must broadcast to [B, H] = [{B}, {H}] ([H], [1, H], [B, 1], [B, H] or 0-d); got {tuple(n.shape)}")
+    nt = n.float().reshape((1,) * (2 - n.dim()) + tuple(n.shape))
+    if nt.shape[0] not in (1, B) or nt.shape[1] not in (1, H):
+        raise ValueError(f"softmax_n_param must broadcast to [B, H] = [{B}, {H}] ([H], [1, H], [B, 1], [B, H] or 0-d); got {tuple(n.shape)}")
+    return nt
 
 
 def _prepare(query, key, value, n, scale, dropout_p, mask, bias):
@@ -357,10 +407,13 @@ def _prepare(query, key, value, n, scale, dropout_p, mask, bias):
         raise ValueError("dropout_p must be in [0, 1)")
     if query.dim() != 4:
         raise ValueError("query must be [B, H, L, E]")
-    n = 0.0 if n is None else float(n)
-    if n < 0:
-        raise ValueError("softmax_n_param must be >= 0")
     B, H, L, E = query.shape
+    if isinstance(n, Tensor):
+        n = _n_tensor(n, query)
+    else:
+        n = 0.0 if n is None else float(n)
+        if n < 0:
+            raise ValueError("softmax_n_param must be >= 0")
 
     # 3-D key/value [B, S, E] = one K/V shared by all heads: a stride-0 head dimension, no copy
     if key.dim() == 3:
@@ -456,13 +509,15 @@ def _attention(query, key, value, n, scale, dropout_p, mask, bias, is_causal) ->
     # (seed, offset, b, h, row, key) - dropout.py is the host mirror
     rng = _next_rng_state(query.device) if dropout_p > 0.0 else None
     _TLS.last_rng_state = rng   # per thread: what last_dropout_state() / last_rng_state() report
-    rg = _regroup_decode(q, k, mask, bias, dropout_p)
+    tensor_n = isinstance(n, Tensor)
+    rg = None if tensor_n else _regroup_decode(q, k, mask, bias, dropout_p)   # (per-row n in the regrouped problem: not built)
     if rg is not None:
         q_g, mask_g, bias_g = rg
         out = _FlashAttentionSoftmaxN.apply(q_g, k, v, mask_g, bias_g, n, scale, False, 0.0, None)
         out = out.view(B, H, 1, dpad)
         return out if Ev == dpad else out[..., :Ev]
-    if not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (bias is not None and bias.requires_grad))):
+    if not (torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (bias is not None and bias.requires_grad)
+                                         or (tensor_n and n.requires_grad))):
         out = _launch_fwd(q, k, v, mask, bias, n, scale, bool(is_causal), dropout_p, rng)[0]   # nothing to differentiate: no autograd node
     else:
         out = _FlashAttentionSoftmaxN.apply(q, k, v, mask, bias, n, scale, bool(is_causal), dropout_p, rng, bias_small)
@@ -470,17 +525,21 @@ def _attention(query, key, value, n, scale, dropout_p, mask, bias, is_causal) ->
 
 
 def kernel_path(query: Tensor, key: Tensor, value: Tensor, attn_mask: Optional[Tensor] = None, attn_bias: Optional[Tensor] = None,
-                is_causal: bool = False, dropout_p: float = 0.0, scale: Optional[float] = None) -> str:
+                is_causal: bool = False, dropout_p: float = 0.0, scale: Optional[float] = None, softmax_n_param=None) -> str:
     """Name of the kernel family a flash_attention_n call with these arguments is routed to (fasn_fwd_path): "plain", "key-padding",
     "vector mask/bias", "vector bias + key-padding", "element-load (slow)" or "fp32". Launches no attention kernel and leaves the
     per-thread plan cache alone: it runs the argument normalisation of the real call (which may issue its small device ops - a feature
     pad, the copy of a misaligned operand, a bias cast) and asks fasn_fwd_path about a throw-away argument block built from the
-    canonical tensors, including the regrouping of a grouped-query decode call. fasn_fwd_path looks at layouts and modes only."""
+    canonical tensors, including the regrouping of a grouped-query decode call. fasn_fwd_path looks at layouts and modes only. A tensor
+    softmax_n_param (per batch element / head) takes the same kernels, and keeps a grouped-query decode call on the per-head launch."""
+    tensor_n = isinstance(softmax_n_param, Tensor)
+    if tensor_n:
+        _n_tensor(softmax_n_param, query)   # (validation only)
     q, k, v, mask, bias, n, sc, dp, _, _, bias_small = _prepare(query, key, value, 1.0, scale, dropout_p, attn_mask, attn_bias)
     if bias_small:
         bias = bias.expand(q.shape[0], q.shape[1], q.shape[2], k.shape[2])
     causal = bool(is_causal)
-    rg = _regroup_decode(q, k, mask, bias, dp)
+    rg = None if tensor_n else _regroup_decode(q, k, mask, bias, dp)
     if rg is not None:
         (q, mask, bias), causal = rg, False
     a = FwdArgs()
@@ -524,7 +583,12 @@ def flash_attention_n(
                   rate, E <= 128).
     :param key: [B, H, S, E] (or [B, S, E], shared by all heads).
     :param value: [B, H, S, Ev].
-    :param softmax_n_param: n >= 0; real values allowed (the reference's SDPA path takes integers only).
+    :param softmax_n_param: n >= 0; real values allowed (the reference's SDPA path takes integers only). Or a floating tensor on the
+                            query's device that broadcasts to [B, H] ([H], [1, H], [B, 1], [B, H] or 0-d; H = query heads, also under
+                            grouped K/V): one n per batch element and head (learned attention sinks: n_h = exp(s_h)), read as fp32 and
+                            differentiated (dL/dn = -sum_i delta_i exp(-lse_i), summed over the dimensions n broadcasts over) when it
+                            requires grad. Its values are not checked (no host synchronisation; capturable): an entry that is not > 0
+                            (negative, NaN) acts as n = 0. A tensor filled with c gives the results of the float c bit for bit.
     :param scale: multiplies q.k^T; default 1/sqrt(E).
     :param dropout_p: attention-weight dropout, realised in 1/65536 steps (dropout.effective_p); the mask is a pure function of
                       the call's (seed, offset) - drawn from a per-device stream seeded by torch's CUDA generator, advanced on the

@@ -126,9 +126,20 @@ def apply_attention_softmax_n(model: Module, softmax_n_param: float,
 def _hf_attention(module: Module, query: torch.Tensor, key: torch.Tensor, value: torch.Tensor,
                   attention_mask: Optional[torch.Tensor], scaling: Optional[float] = None, dropout: float = 0.0, **kwargs):
     """`transformers` attention-interface function: [B,H,L,E] in, ([B,L,H,Ev], None) out. The additive float mask HF builds
-    ([B,1,L,S], finfo.min where hidden) is passed as `attn_bias` through its broadcast strides."""
+    ([B,1,L,S], finfo.min where hidden) is passed as `attn_bias` through its broadcast strides.
+    Attention sinks (`s_aux`, GPT-OSS: one learned logit s_h per query head, a softmax column that is dropped after the softmax) are
+    softmax_n with n_h = exp(s_h): they add to a surgery n (n_h = softmax_n_param + exp(s_h)) and their gradient reaches the sink
+    parameter. Causality follows transformers' SDPA integration: the `is_causal` kwarg, else the module's `is_causal` attribute, and
+    only for more than one query row and no mask (a mask, when given, already holds the causal pattern)."""
     from .flash_attn import flash_attention_n
     n = float(getattr(module, "softmax_n_param", 0.0))
+    s_aux = kwargs.get("s_aux")
+    if s_aux is not None:
+        n = torch.exp(s_aux.float()) + n   # [H]: one n per query head
+    is_causal = kwargs.get("is_causal")
+    if is_causal is None:
+        is_causal = getattr(module, "is_causal", False)
+    is_causal = bool(is_causal) and query.shape[2] > 1 and attention_mask is None
     if kwargs.get("head_mask") is not None:
         raise NotImplementedError("head_mask multiplies the attention probabilities, which the fused kernel never materialises")
     bias = mask = None
@@ -145,7 +156,7 @@ def _hf_attention(module: Module, query: torch.Tensor, key: torch.Tensor, value:
                 mask = keymask
                 bias = torch.where(keymask, bias[..., :1, :], torch.zeros((), dtype=bias.dtype, device=bias.device)) if ADDITIVE_KEY_MASKS_MAY_BE_SOFT else None
     out = flash_attention_n(query, key, value, softmax_n_param=n, scale=scaling, dropout_p=dropout if module.training else 0.0,
-                            attn_mask=mask, attn_bias=bias, is_causal=bool(kwargs.get("is_causal", False)) and query.shape[2] > 1)
+                            attn_mask=mask, attn_bias=bias, is_causal=is_causal)
     return out.transpose(1, 2).contiguous(), None
 
 

@@ -166,6 +166,33 @@ size_t fasn_fwd_workspace_bytes(const fasn_fwd_args* args);
 int fasn_fwd_ws(const fasn_fwd_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
 
 /*
+ * Forward with a per-(batch, head) softmax_n (learned attention sinks: n_h = exp(s_h) is the weight of a per-head sink logit s_h, as
+ * in GPT-OSS; the reference takes one n per call). Replaces fasn_fwd_ws when n is a tensor: `n` is a DEVICE pointer to fp32 values,
+ * work item (b, h) reads n[b * n_stride_b + h * n_stride_h] (element strides >= 0, 0 = broadcast; h is the QUERY head, also under
+ * kv_group) and args->softmax_n is ignored. The values are not checked (that would be a host round trip and break graph capture):
+ * an entry that is not > 0 (0, negative, NaN) acts as n = 0. Same validation codes, workspace rule and kernel plan as fasn_fwd_ws
+ * with the same args; a tensor filled with c gives bit for bit the results of softmax_n = c. n == NULL: exactly fasn_fwd_ws.
+ * `n` must be 4-byte aligned (FASN_EALIGN) and (B-1) n_stride_b + (H-1) n_stride_h < 2^31 (FASN_EINVAL).
+ */
+int fasn_fwd_n(const fasn_fwd_args* args, const float* n, int64_t n_stride_b, int64_t n_stride_h, void* workspace,
+               size_t workspace_bytes, fasn_stream_t stream);
+
+/*
+ * Gradient of that n (no counterpart in the reference, whose n carries none). With lse_i = log(n + sum_j exp(x_ij)) and
+ * delta_i = sum_d dO_id O_id:
+ *     dL/dn_(b,h) = - sum_i delta_i exp(-lse_i)        (rows with lse = -inf add 0; unchanged under dropout: O is the dropped output)
+ * Reads args->fwd.o, args->fwd.lse and args->dout (the views of the fasn_bwd call; nothing else of args is read beyond validation,
+ * args->fwd.softmax_n is ignored), WRITES dn[b * dn_stride_b + h * dn_stride_h] as fp32. A stride of 0 asks for the sum over that
+ * dimension (dn_stride_b = 0: sum over the batch, e.g. an n of shape [H]). Deterministic: a fixed-order two-stage reduction through
+ * the caller's workspace (fasn_bwd_dn_workspace_bytes(args) bytes, 16-byte aligned; FASN_EWORKSPACE when missing or too small), no
+ * atomics - the same inputs give the same bits. fasn_bwd needs no change for a tensor n: its kernels see n only through lse.
+ * Two small kernels on `stream`; call it after (or before) fasn_bwd with the same args.
+ */
+size_t fasn_bwd_dn_workspace_bytes(const fasn_bwd_args* args);
+int fasn_bwd_dn(const fasn_bwd_args* args, float* dn, int64_t dn_stride_b, int64_t dn_stride_h, void* workspace,
+                size_t workspace_bytes, fasn_stream_t stream);
+
+/*
  * Dropout stream position in device memory (replaces the host-side philox seed / offset bookkeeping behind
  * flash_attention_softmax_n/core/flash_attn.py:122 and functional.py:92): copies state[0..1] = {seed, offset} to out[0..1]
  * (out may be NULL) and advances state[1] by `increment`, as one tiny kernel on `stream` - capturable, no host round trip.
