@@ -24,6 +24,7 @@ EXPORTS = (
     "fasn_bwd_workspace_bytes", "fasn_bwd", "fasn_rng_advance", "fasn_launch_plan",
     "fasn_fwd_n", "fasn_bwd_dn_workspace_bytes", "fasn_bwd_dn",
     "fasn_softmax_n_fwd", "fasn_softmax_n_bwd", "fasn_moments",
+    "fasn_fwd_kvcache_workspace_bytes", "fasn_fwd_kvcache", "fasn_kvcache_append", "fasn_kvcache_plan",
 )
 
 
@@ -53,6 +54,22 @@ class BwdArgs(Structure):
         ("dbias", View4),
         ("flags", c_int32),
         ("dbias_dtype", c_int32),
+    ]
+
+
+class KvCacheArgs(Structure):
+    """fasn_kvcache_args (include/fasn.h): forward over a paged or dense K/V cache whose lengths live in device memory"""
+    _fields_ = [
+        ("q", View4), ("o", View4),
+        ("lse", c_void_p),
+        ("k_cache", c_void_p), ("v_cache", c_void_p),
+        ("k_stride", c_int64 * 3), ("v_stride", c_int64 * 3),
+        ("block_table", c_void_p), ("block_table_stride", c_int64), ("max_pages", c_int32),
+        ("seqlens", c_void_p), ("seqlen_add", c_int32), ("page_size", c_int32),
+        ("B", c_int32), ("H", c_int32), ("kv_group", c_int32), ("Sq", c_int32), ("D", c_int32),
+        ("dtype", c_int32),
+        ("scale", c_float), ("softmax_n", c_float), ("causal", c_int32),
+        ("n", c_void_p), ("n_stride_b", c_int64), ("n_stride_h", c_int64),
     ]
 
 
@@ -111,6 +128,14 @@ def load():
     lib.fasn_softmax_n_bwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int32, c_void_p]
     lib.fasn_moments.restype = c_int32
     lib.fasn_moments.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p]
+    lib.fasn_fwd_kvcache_workspace_bytes.restype = c_size_t
+    lib.fasn_fwd_kvcache_workspace_bytes.argtypes = [POINTER(KvCacheArgs)]
+    lib.fasn_fwd_kvcache.restype = c_int32
+    lib.fasn_fwd_kvcache.argtypes = [POINTER(KvCacheArgs), c_void_p, c_size_t, c_void_p]
+    lib.fasn_kvcache_append.restype = c_int32
+    lib.fasn_kvcache_append.argtypes = [POINTER(KvCacheArgs), POINTER(View4), POINTER(View4), c_void_p]
+    lib.fasn_kvcache_plan.restype = c_int32
+    lib.fasn_kvcache_plan.argtypes = [POINTER(KvCacheArgs), c_char_p, c_size_t]
     ver = lib.fasn_abi_version()
     if ver != FASN_ABI_VERSION:
         raise ImportError(f"libfasn ABI version {ver} != expected {FASN_ABI_VERSION}; rebuild csrc/")
@@ -147,6 +172,19 @@ def launch_plan_described(args, which):
         cfg = cfg.split("=", 1)[1]
         shown = name if cfg == "-" else f"{name.split('<', 1)[0]}<{cfg}>"
         out.append((shown, int(g.split("=")[1]), int(b.split("=")[1]), int(l.split("=")[1])))
+    return out
+
+
+def kvcache_plan(args):
+    """The kernels fasn_fwd_kvcache would launch for `args` (a KvCacheArgs), as launch_plan returns them. Nothing is launched."""
+    buf = ctypes.create_string_buffer(4096)
+    rc = load().fasn_kvcache_plan(args, buf, len(buf))
+    if rc < 0:
+        check(rc, "fasn_kvcache_plan")
+    out = []
+    for line in buf.value.decode().splitlines():
+        name, g, b, l, _cfg = line.rsplit(" ", 4)
+        out.append((name, int(g.split("=")[1]), int(b.split("=")[1]), int(l.split("=")[1])))
     return out
 
 

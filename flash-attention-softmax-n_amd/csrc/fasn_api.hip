@@ -49,6 +49,9 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
         {"fasn_f32_dq_kernel", "D M"},
         {"fasn_f32_dkdv_kernel", "D M"},
         {"fasn_f32_delta_kernel", "D"},
+        {"fasn_kvcache_fwd_kernel", "T D"},
+        {"fasn_kvcache_combine_kernel", "T D"},
+        {"fasn_kvcache_append_kernel", "D"},
     };
     static const char* const modes[] = {"plain", "causal", "bias+mask", "element-load", "bias", "mask", "keypad", "bias+keypad"};
     if (cap == 0) return 0;

@@ -1,0 +1,179 @@
+"""Attention over a K/V cache (inference): paged or dense cache, lengths in device memory, grouped-query heads as rows of one problem.
+
+Host side of fasn_fwd_kvcache / fasn_kvcache_append (include/fasn.h). Nothing about the lengths or the block table is read on the
+host - no `.item()`, no synchronisation, the launches depend on shapes and capacity only - so a call can be captured once in a
+torch.cuda.graph and replayed while `cache_seqlens`, `block_table`, the cache and `query` change in place. Forward only: the training
+and prefill entry point is flash_attention_n.
+"""
+from math import sqrt
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from ._lib import KvCacheArgs
+from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
+
+_KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
+_KV_HEAD_DIMS = (64, 128)
+_MAX_ROWS = 128   # query heads per K/V head x query positions: the rows of one workgroup
+
+
+def _check_cache(name: str, t: Tensor, paged: bool, D: int) -> None:
+    if t.stride(3) != 1:
+        raise ValueError(f"{name}: feature stride must be 1 (got {t.stride(3)}); a cache is never copied, so it cannot be made contiguous here")
+    if t.data_ptr() % 16 != 0 or any(t.stride(i) % 8 != 0 for i in range(3) if t.size(i) > 1):
+        raise ValueError(f"{name}: rows must be 16-byte aligned (base pointer % 16 == 0, page / row / head strides % 8 elements); "
+                         f"got strides {tuple(t.stride())}")
+    if t.size(1) > 1 and t.stride(1) < D:
+        raise ValueError(f"{name}: rows overlap (row stride {t.stride(1)} < head dim {D})")
+
+
+def flash_attention_n_kvcache(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """softmax_n attention of a few new query positions against a K/V cache, on MI355X.
+
+    :param query: [B, H, Sq, D] fp16 / bf16 device tensor, D in {64, 128}; Sq = 1 is decode, a few positions speculative / chunked decode.
+    :param k_cache, v_cache: paged [num_pages, page_size, Hkv, D] with `block_table` (page_size a multiple of 64), or dense
+                  [B, capacity, Hkv, D] with block_table=None. Any strided view whose rows are 16-byte aligned with feature stride 1
+                  (e.g. sliced out of a fused K/V buffer); never copied. H % Hkv == 0 and (H // Hkv) * Sq <= 128: the query heads of a
+                  K/V head times the positions are the rows of one problem, so the cache is read once per K/V head.
+    :param cache_seqlens: int32 [B] ON THE DEVICE: valid keys per batch element before this call. Not modified (the caller advances it).
+    :param block_table: int32 [B, max_pages] on the device: page ids of each batch element, in order. Entries beyond the pages a batch
+                  element needs are never read; cache rows at or beyond its length may hold anything (NaN included).
+    :param k_new, v_new: optional [B, Hkv, Sq, D]: written to the cache positions cache_seqlens[b] .. + Sq - 1 first (positions at or
+                  beyond the capacity are dropped) and then attended to: batch element b sees len_b = cache_seqlens[b] + Sq keys.
+    :param softmax_n_param: n >= 0, or a floating tensor that broadcasts to [B, H] as in flash_attention_n (one n per batch element and
+                  query head: attention sinks, n_h = exp(s_h)); no gradient here.
+    :param scale: multiplies q.k^T; default 1/sqrt(D).
+    :param is_causal: bottom-right aligned per batch element: position i sees key j iff j <= i + len_b - Sq. False: every position sees
+                  all len_b keys.
+    :param return_lse: also return lse [B, H, Sq] fp32 = log(n + sum_j exp(x_ij)).
+    :return: [B, H, Sq, D] in query's dtype (and lse). Rows that see no key give exactly 0 and lse = log n (-inf for n = 0).
+    """
+    if query.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError("query must be [B, H, Sq, D] and the caches [num_pages, page_size, Hkv, D] (paged) or [B, capacity, Hkv, D] (dense)")
+    if query.dtype not in _KV_DTYPES:
+        raise ValueError(f"flash_attention_n_kvcache: dtype {query.dtype} is not supported (fp16 and bf16 caches only)")
+    B, H, Sq, D = query.shape
+    dev = query.device
+    tensors = {"k_cache": k_cache, "v_cache": v_cache, "cache_seqlens": cache_seqlens, "block_table": block_table, "k_new": k_new, "v_new": v_new}
+    for name, t in tensors.items():
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}, query on {dev}: every operand must live on the query's device "
+                               "(the lengths and the block table are read by the kernels, never on the host)")
+    if k_cache.dtype != query.dtype or v_cache.dtype != query.dtype:
+        raise TypeError("query, k_cache and v_cache must share one dtype")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (query, k_cache, v_cache, k_new, v_new)) or (
+            torch.is_grad_enabled() and isinstance(softmax_n_param, Tensor) and softmax_n_param.requires_grad):
+        raise RuntimeError("flash_attention_n_kvcache is forward only (inference): an input requires grad. Call it under torch.no_grad(), "
+                           "or use flash_attention_n, which differentiates q, k, v and a tensor n")
+    if D not in _KV_HEAD_DIMS:
+        raise ValueError(f"flash_attention_n_kvcache: head dim {D} is not supported (supported: {_KV_HEAD_DIMS}); a cache is never "
+                         "zero-padded on the host")
+    if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
+        raise ValueError(f"k_cache and v_cache must have one shape [*, *, Hkv, {D}]; got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+    page_size, Hkv = k_cache.shape[1], k_cache.shape[2]
+    if Hkv < 1 or H % Hkv != 0:
+        raise ValueError(f"the cache has {Hkv} K/V heads: must divide the {H} query heads (grouped-query attention)")
+    G = H // Hkv
+    if G * Sq > _MAX_ROWS:
+        raise ValueError(f"(query heads per K/V head) x (query positions) = {G} x {Sq} = {G * Sq} rows exceed the {_MAX_ROWS} of one pass; "
+                         "split the query positions over several calls")
+    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B or not cache_seqlens.is_contiguous():
+        raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
+    paged = block_table is not None
+    if paged:
+        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.stride(1) != 1:
+            raise ValueError(f"block_table must be an int32 tensor [B, max_pages] with unit column stride; got {block_table.dtype} {tuple(block_table.shape)}")
+        if block_table.shape[0] != B:
+            raise ValueError(f"block_table has {block_table.shape[0]} rows but the batch is {B}: one row of page ids per batch element")
+        if block_table.shape[1] < 1:
+            raise ValueError("block_table must name at least one page per batch element")
+        if page_size % 64 != 0:
+            raise ValueError(f"page_size {page_size} is not supported: a paged cache needs page_size % 64 == 0 (a 64-key tile never straddles a page)")
+    elif k_cache.shape[0] != B:
+        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, Hkv, D] with B = {B}; got {tuple(k_cache.shape)}")
+    _check_cache("k_cache", k_cache, paged, D)
+    _check_cache("v_cache", v_cache, paged, D)
+    if (k_new is None) != (v_new is None):
+        raise ValueError("k_new and v_new come together")
+    if k_new is not None:
+        for name, t in (("k_new", k_new), ("v_new", v_new)):
+            if t.dtype != query.dtype or tuple(t.shape) != (B, Hkv, Sq, D):
+                raise ValueError(f"{name} must be [B, Hkv, Sq, D] = [{B}, {Hkv}, {Sq}, {D}] in {query.dtype}; got {tuple(t.shape)} {t.dtype}")
+        k_new, v_new = _rows(k_new), _rows(v_new)
+    query = _rows(query)
+    if isinstance(softmax_n_param, Tensor):
+        nt = _n_tensor(softmax_n_param.detach(), query).contiguous()
+        n = 0.0
+    else:
+        nt = None
+        n = 0.0 if softmax_n_param is None else float(softmax_n_param)
+        if n < 0:
+            raise ValueError("softmax_n_param must be >= 0")
+    scale = (1.0 / sqrt(D)) if scale is None else float(scale)
+    # (the argument checks above need no device; everything below does)
+    if not query.is_cuda:
+        raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
+                           "(there is deliberately no CPU fallback)")
+
+    lib = _lib.load()
+    out = torch.empty((B, H, Sq, D), dtype=query.dtype, device=dev)
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+    a = KvCacheArgs()
+    a.q, a.o = _view4(query), _view4(out)
+    a.lse = None if lse is None else lse.data_ptr()
+    a.k_cache, a.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+    for i in range(3):
+        a.k_stride[i] = k_cache.stride(i) if k_cache.size(i) > 1 else 0
+        a.v_stride[i] = v_cache.stride(i) if v_cache.size(i) > 1 else 0
+    if k_cache.size(1) == 1:   # (a one-row page still needs a row stride that covers the row)
+        a.k_stride[1] = a.v_stride[1] = D
+    if paged:
+        a.block_table, a.block_table_stride, a.max_pages = block_table.data_ptr(), block_table.stride(0) if B > 1 else block_table.shape[1], block_table.shape[1]
+    else:
+        a.block_table, a.block_table_stride, a.max_pages = None, 0, 1
+    a.seqlens = cache_seqlens.data_ptr()
+    a.seqlen_add = Sq if k_new is not None else 0
+    a.page_size = page_size
+    a.B, a.H, a.kv_group, a.Sq, a.D = B, H, G, Sq, D
+    a.dtype = _KV_DTYPES[query.dtype]
+    a.scale, a.softmax_n, a.causal = scale, n, 1 if is_causal else 0
+    if nt is not None:
+        a.n = nt.data_ptr()
+        a.n_stride_b, a.n_stride_h = _n_strides(nt)
+    else:
+        a.n, a.n_stride_b, a.n_stride_h = None, 0, 0
+
+    def launch():
+        stream = _stream_ptr(dev)
+        if k_new is not None:
+            _lib.check(lib.fasn_kvcache_append(a, _view4(k_new), _view4(v_new), stream), "fasn_kvcache_append")
+        ws_bytes = lib.fasn_fwd_kvcache_workspace_bytes(a)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (torch's caching allocator: capturable, as _launch_fwd's)
+        _lib.check(lib.fasn_fwd_kvcache(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache")
+
+    if _current_device() == dev.index:
+        launch()
+    else:
+        with torch.cuda.device(dev):
+            launch()
+    return (out, lse) if return_lse else out
+
+
+def _rows(t: Tensor) -> Tensor:
+    """query / k_new / v_new: small per-step tensors, made contiguous when their rows are not 16-byte aligned (the cache never is)"""
+    ok = t.stride(3) == 1 and t.data_ptr() % 16 == 0 and all(t.stride(i) % 8 == 0 or t.size(i) == 1 for i in range(3))
+    return t if ok else t.contiguous()

@@ -230,6 +230,60 @@ int fasn_launch_plan(const fasn_bwd_args* args, int32_t which, char* buf, size_t
 int fasn_bwd_path(const fasn_bwd_args* args);
 
 /*
+ * Forward over a K/V CACHE (inference; additions within ABI 6, no counterpart in the reference, which has no cache): attention of a few new
+ * query positions per batch element (Sq = 1: decode) against keys that live in a paged or dense cache whose valid LENGTHS ARE IN DEVICE
+ * MEMORY. Nothing about the lengths or the block table is read on the host: the launches depend on shapes and capacity only, so one
+ * captured HIP graph serves every step of a generation while the sequences grow. Forward only; no mask, bias or dropout.
+ *
+ *   cache     key j of batch element b is row j % page_size of page block_table[b * block_table_stride + j / page_size]; element
+ *             (page, row, K/V head hk, feature d) of K sits at k_cache + (page * k_stride[0] + row * k_stride[1] + hk * k_stride[2] + d)
+ *             elements (feature stride 1, every stride % 8, base 16-byte aligned). block_table == NULL is the dense cache: batch element b
+ *             is one page of page_size (= its capacity) rows, page stride = batch stride; max_pages is ignored.
+ *   lengths   len_b = clamp(seqlens[b] + seqlen_add, 0, capacity), capacity = max_pages * page_size (dense: page_size). Rows at or beyond
+ *             len_b and pages beyond ceil(len_b / page_size) may hold anything (NaN bit patterns included) and never reach the result;
+ *             block-table entries that are not needed are not read.
+ *   rows      H % kv_group == 0; the kv_group query heads of a K/V head times the Sq positions are the rows of one problem (kv_group * Sq
+ *             <= 128, else FASN_EUNSUPPORTED), so the cache is read once per K/V head; each row uses the softmax_n of its own query head:
+ *             `n` / n_stride_b / n_stride_h with the meaning fasn_fwd_n gives them, n == NULL = the scalar softmax_n.
+ *   causal    bottom-right aligned per batch element: position i sees key j iff j <= i + len_b - Sq. Rows that see no key give 0 and
+ *             lse = log n (-inf for n = 0).
+ *   supported D in {64, 128} (FASN_EHEADDIM otherwise), fp16 / bf16 (FASN_EDTYPE), paged: page_size % 64 == 0 (FASN_EUNSUPPORTED).
+ *
+ * fasn_fwd_kvcache needs fasn_fwd_kvcache_workspace_bytes(args) bytes of 16-byte aligned device memory (split partials; FASN_EWORKSPACE
+ * when missing or too small) and launches two kernels. fasn_kvcache_append writes the Sq rows of k_new / v_new ([B, H / kv_group, Sq, D]
+ * views) to the cache positions seqlens[b] .. seqlens[b] + Sq - 1 (seqlen_add is not used; positions at or beyond the capacity are dropped
+ * inside the kernel; `seqlens` is not modified - the caller advances it); a forward that is to see them passes seqlen_add = Sq.
+ * fasn_kvcache_plan writes the launches of fasn_fwd_kvcache as text, in the line format of fasn_launch_plan, without touching a device.
+ */
+typedef struct fasn_kvcache_args {
+    fasn_view4 q;          /* [B,H,Sq,D] */
+    fasn_view4 o;          /* [B,H,Sq,D] out */
+    float* lse;            /* [B,H,Sq] fp32 contiguous, out; may be NULL */
+    void* k_cache;
+    void* v_cache;
+    int64_t k_stride[3];   /* element strides (page, row, K/V head) */
+    int64_t v_stride[3];
+    const int32_t* block_table;  /* DEVICE [B, max_pages] page ids, or NULL (dense cache) */
+    int64_t block_table_stride;  /* elements between the rows of two batch elements */
+    int32_t max_pages;
+    const int32_t* seqlens;      /* DEVICE [B] */
+    int32_t seqlen_add;
+    int32_t page_size;
+    int32_t B, H, kv_group, Sq, D;
+    int32_t dtype;         /* FASN_DTYPE_F16 / FASN_DTYPE_BF16 */
+    float scale;
+    float softmax_n;
+    int32_t causal;
+    const float* n;        /* DEVICE per-(batch, query head) softmax_n, or NULL */
+    int64_t n_stride_b, n_stride_h;
+} fasn_kvcache_args;
+
+size_t fasn_fwd_kvcache_workspace_bytes(const fasn_kvcache_args* args);
+int fasn_fwd_kvcache(const fasn_kvcache_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).
