@@ -14,14 +14,6 @@
 using namespace fasn;
 
 namespace fasn {
-#ifdef FASN_DEV_VARIANTS
-int g_bwd_variant = 0;
-unsigned long long* g_timeline = nullptr;
-int* g_xq = nullptr;      // developer experiment: dynamic deal of the forward's items across XCDs (fasn_fwd_kernel.h)
-int g_xq_extra = 0;       // surplus workgroups per XCD of such a launch
-int g_pair_mode = -1;
-int g_kprot = 1;
-#endif
 thread_local LaunchLog* t_launch_log = nullptr;
 // one line per launch: the kernel with its template arguments (demangled from the type name kernel_pretty_name<&kernel<...>> hands over:
 // "fasn::KernelTag<&(void fasn::kernel<arguments>(fasn::Params))>"), grid, block, LDS
@@ -154,7 +146,7 @@ int check_view(const fasn_view4& v, bool required, int esize = 2) {
 // mask, fp16 scale overflow) still takes the element-load kernels, forward (launch_gen) and backward (launch_bwd_mode).
 bool f32_bias_vector(int D) { return D == 32 || D == 64 || D == 128; }
 
-int build_fwd(const fasn_fwd_args* a, FwdParams& p, FwdLaunch& l, int pass = 0) {
+int build_fwd(const fasn_fwd_args* a, FwdParams& p, FwdLaunch& l) {
     if (a == nullptr) return FASN_EINVAL;
     if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->Sk <= 0 || a->D <= 0 || a->Dv <= 0) return FASN_EINVAL;
     if (a->dtype != FASN_DTYPE_F16 && a->dtype != FASN_DTYPE_BF16 && a->dtype != FASN_DTYPE_F32) return FASN_EDTYPE;
@@ -273,18 +265,9 @@ int build_fwd(const fasn_fwd_args* a, FwdParams& p, FwdLaunch& l, int pass = 0) 
     // The vector kernels multiply Q (or K) by c = scale*log2e in the operand type before the MFMAs. In fp16 a large scale could
     // push an otherwise representable operand past 65504 there: such calls take the element-load kernels, which scale in fp32.
     if (a->dtype == FASN_DTYPE_F16 && fabsf(p.c) > 8.f) l.mode = MODE_GENERAL_SLOW;
-    l.variant = 0;
     p.xq = nullptr;   // static deal of the items unless fasn_fwd_ws hands over counters (below)
-#ifdef FASN_DEV_VARIANTS
-    p.timeline = g_timeline;
-    if (g_xq != nullptr && pass == 0) p.xq = g_xq;   // (developer harness, env FASN_XQ: forces the dynamic deal of the FORWARD with its own counters and surplus)
-#endif
     p.pair = 0;   // set per launch (paired causal blocks, fasn_launch.h)
-#ifdef FASN_DEV_VARIANTS
-    p.kprot = g_kprot;
-#else
     p.kprot = 1;
-#endif
     p.nsplit = 1;
     p.tps = 0;
     p.part_o = nullptr;
@@ -405,11 +388,7 @@ int fasn_fwd_path(const fasn_fwd_args* args) {
 
 // Long plain / causal launches at D = 64 deal their items dynamically across XCDs when the caller hands over 32 bytes of workspace for the eight
 // counters (fasn_fwd_kernel.h: draw_item): from 8 rounds of workgroups (M0's four rounds lose 0.6 % to the memset and the atomics, 16 rounds gain 2 %).
-#ifndef FASN_XQ_RULE
-#define FASN_XQ_RULE 1   // (A/B: 0 = never ask for the counters: static deal everywhere, as before)
-#endif
 static bool xq_wanted(const FwdParams& p, const FwdLaunch& l) {
-    if (!FASN_XQ_RULE) return false;
     if (l.D != 64 || l.dtype == FASN_DTYPE_F32 || p.drop_thr || ((p.B * p.H) & 7) || p.Sq < 256) return false;
     const long blocks = (long)((p.Sq + 255) / 256) * p.B * p.H;
     if (l.mode == MODE_PLAIN) return blocks >= 8 * 512;
@@ -472,53 +451,18 @@ int fasn_fwd_n(const fasn_fwd_args* args, const float* n, int64_t n_stride_b, in
     return fwd_ws(&a, workspace, workspace_bytes, (hipStream_t)stream, n, (int)n_stride_b, (int)n_stride_h);
 }
 
-#ifdef FASN_DEV_VARIANTS
-// developer library only (tools/libfasn_dev.so): backward A/B switch (see fasn_bwd_launch.h)
-void fasn_dev_set_bwd_variant(int v) { fasn::g_bwd_variant = v; }
-void fasn_dev_set_timeline(unsigned long long* buf) { fasn::g_timeline = buf; }
-void fasn_dev_set_pair_mode(int v) { fasn::g_pair_mode = v; }
-void fasn_dev_set_kprot(int v) { fasn::g_kprot = v; }
-void fasn_dev_set_xq(int* counters, int extra) { fasn::g_xq = counters; fasn::g_xq_extra = extra; }
-// developer library only (tools/libfasn_dev.so): forward with an explicit tuning variant, used by tools/fasn_harness
-int fasn_fwd_variant(const fasn_fwd_args* args, fasn_stream_t stream, int variant) {
-    FwdParams p;
-    FwdLaunch l;
-    const int rc = build_fwd(args, p, l);
-    if (rc) return rc;
-    l.variant = variant;
-    return dispatch_fwd(p, l, (hipStream_t)stream);
-}
-#endif
-
-// One-pass backward (tools/dev/fasn_bwd_fused.h): a measured loser on MI355X, kept in the DEVELOPER library only
-// (tools/libfasn_dev.so, FASN_DEV_VARIANTS) for A/B work; libfasn.so ignores FASN_BWD_ONE_PASS and never asks for a workspace.
-static bool bwd_fused_applies(const fasn_bwd_args* a, const FwdParams& p, const FwdLaunch& l) {
-#ifndef FASN_DEV_VARIANTS
-    (void)a; (void)p; (void)l;
-    return false;
-#else
-    if (!(a->flags & FASN_BWD_ONE_PASS)) return false;
-    if (l.dtype == FASN_DTYPE_F32 || l.D != 64) return false;
-    if (l.mode != MODE_PLAIN && l.mode != MODE_CAUSAL) return false;
-    if (p.drop_thr != 0 || p.kvg > 1) return false;
-    return true;
-#endif
-}
-static size_t bwd_fused_bytes(const fasn_bwd_args* a) { return (size_t)a->fwd.B * a->fwd.H * a->fwd.Sq * a->fwd.D * sizeof(float); }
-
+// The backward needs no workspace: FASN_BWD_ONE_PASS is accepted and ignored (the one-pass backward it once asked for was a measured loser on
+// MI355X).
 size_t fasn_bwd_workspace_bytes(const fasn_bwd_args* args) {
-    if (args == nullptr) return 0;
-    FwdParams p;
-    FwdLaunch l;
-    if (build_fwd(&args->fwd, p, l)) return 0;
-    return bwd_fused_applies(args, p, l) ? bwd_fused_bytes(args) : 0;
+    (void)args;
+    return 0;
 }
 
 int fasn_bwd(const fasn_bwd_args* a, fasn_stream_t stream) {
     if (a == nullptr) return FASN_EINVAL;
     FwdParams fp;
     FwdLaunch l;
-    int rc = build_fwd(&a->fwd, fp, l, 1);
+    int rc = build_fwd(&a->fwd, fp, l);
     if (rc) return rc;
     if (a->fwd.lse == nullptr || a->delta == nullptr) return FASN_EINVAL;
     if (l.mode == MODE_KEYPAD && l.dtype == FASN_DTYPE_F32) l.mode = MODE_GENERAL_SLOW;   // (the fp32 kernels have the element-load mask path only)
@@ -542,12 +486,8 @@ int fasn_bwd(const fasn_bwd_args* a, fasn_stream_t stream) {
         p.qbytes = (unsigned)qb;
         p.dobytes = (unsigned)db;
     }
-    p.dqacc = nullptr;
+    p.dqacc = nullptr;   // unused
     p.skip = 0;
-    if (bwd_fused_applies(a, fp, l) && a->workspace != nullptr && a->workspace_bytes >= bwd_fused_bytes(a)) {
-        if (reinterpret_cast<uintptr_t>(a->workspace) % 16) return FASN_EALIGN;
-        p.dqacc = static_cast<float*>(a->workspace);
-    }
     p.dbias = nullptr;
     p.dbias_vec = 0;
     for (int i = 0; i < 3; ++i) p.dbs[i] = 0;

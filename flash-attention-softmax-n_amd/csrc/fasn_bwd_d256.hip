@@ -5,12 +5,6 @@
 // kernels (round 6), operands whose rows do not move as vectors the element-load kernels.
 #include "fasn_bwd_launch.h"
 #include "fasn_bwd_ws256.h"
-#ifndef FASN_D256_VEC_DH
-#define FASN_D256_VEC_DH 2   // feature halves of the one-wave vector dK/dV kernels (1: whole rows, 94 - 124 spilled registers; A/B in LABNOTES)
-#endif
-#ifndef FASN_D256_GEN_WS
-#define FASN_D256_GEN_WS 1
-#endif
 namespace fasn {
 // plain / causal without dropout or grouped K/V: the two-wave kernels of fasn_bwd_ws256.h (round 4): delta, dQ, dK/dV
 // MODE = the dQ kernel's; MODE_KEYPAD (a boolean mask over (batch, head, key), p.f.causal as it comes): the dK/dV kernel then is the
@@ -64,23 +58,17 @@ static int go(const BwdParams& p, int mode, hipStream_t s) {
     if (p.f.drop_thr) {   // dropout (round 6): ONE vector instantiation for every mode whose mask / bias rows move as vectors - no operand at all included
         const int md = mode == MODE_KEYPAD ? p.f.keypad_fallback : mode;
         if (md == MODE_GENERAL_SLOW) return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL_SLOW, 1, 1, 1, 0, 2>(p, s);
-        return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL, 1, 1, 1, 0, FASN_D256_VEC_DH>(p, s);
+        return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL, 1, 1, 1, 0, 2>(p, s);   // (DH = 2, feature halves: whole rows spilled 94 - 124 registers, LABNOTES.md)
     }
-    if (!(FASN_BWD_VARIANT & 1)) {   // (developer library: bwd_variant bit 0 = the round-3 feature-half kernels, for A/B)
-        if (mode == MODE_PLAIN) return launch_ws256<Tag, MODE_PLAIN>(p, s);      // (grouped K/V included since round 5)
-        if (mode == MODE_CAUSAL) return launch_ws256<Tag, MODE_CAUSAL>(p, s);
-        if (p.f.kvg == 1 && mode == MODE_KEYPAD && p.f.ms[3] == 1 && (p.f.Sk + 63) / 64 <= kDq256KpTiles) return launch_ws256<Tag, MODE_KEYPAD>(p, s);
-    }
+    if (mode == MODE_PLAIN) return launch_ws256<Tag, MODE_PLAIN>(p, s);      // (grouped K/V included since round 5)
+    if (mode == MODE_CAUSAL) return launch_ws256<Tag, MODE_CAUSAL>(p, s);
+    if (p.f.kvg == 1 && mode == MODE_KEYPAD && p.f.ms[3] == 1 && (p.f.Sk + 63) / 64 <= kDq256KpTiles) return launch_ws256<Tag, MODE_KEYPAD>(p, s);
     switch (mode) {
-#ifdef FASN_DEV_VARIANTS   // (plain and causal calls always take the two-wave kernels above: the one-wave causal instantiation is reachable from the A/B switch only)
-        case MODE_CAUSAL: return launch_bwd_one<Tag, 256, 1, 1, MODE_CAUSAL, 1, 1, 0, 0, 2>(p, s);
-#endif
-        case MODE_PLAIN:   // the key-padding instantiation without a mask (every key visible): the plain one spills at this head dim
         case MODE_KEYPAD: return launch_bwd_one<Tag, 256, 1, 1, MODE_KEYPAD, 1, 1, 0, 0, 2>(p, s);
         // dense masks / 16-bit bias with vector-movable rows (round 6): the one-wave vector kernels - the dK/dV kernel with ONE additive tile
         // (two of them next to four 32 KiB Q / dO buffers would need 161 KiB of LDS; round 5 sent these calls to the element-load kernels, 3 x slower)
         case MODE_GENERAL: case MODE_GENERAL_B: case MODE_GENERAL_M:
-            if (FASN_D256_GEN_WS && p.dbias == nullptr) {   // dQ by the two-wave kernel with per-wave images (no dense dS store there); dK / dV by the one-wave vector kernel
+            if (p.dbias == nullptr) {   // dQ by the two-wave kernel with per-wave images (no dense dS store there); dK / dV by the one-wave vector kernel
                 const int nbh = p.f.B * p.f.H;
                 constexpr int RPB = 256 / (256 / 8);
                 const int64_t rows = (int64_t)nbh * p.f.Sq;
@@ -94,9 +82,9 @@ static int go(const BwdParams& p, int mode, hipStream_t s) {
                 FASN_LAUNCH(kern, dim3((unsigned)(q.nblk * nbh)), dim3(512), smem, s, q);
                 BwdParams r = p;
                 r.skip |= 2 | 4;   // dQ and delta are launched
-                return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL, 1, 1, 0, 0, FASN_D256_VEC_DH>(r, s);
+                return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL, 1, 1, 0, 0, 2>(r, s);
             }
-            return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL, 1, 1, 0, 0, FASN_D256_VEC_DH>(p, s);
+            return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL, 1, 1, 0, 0, 2>(p, s);
         default: return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL_SLOW, 1, 1, 0, 0, 2>(p, s);
     }
 }

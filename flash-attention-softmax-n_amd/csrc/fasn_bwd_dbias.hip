@@ -44,7 +44,7 @@ static int launch_ws(const DbiasParams& dp, hipStream_t s) {
     const int grid = (int)(tiles < n ? tiles : n);
     w.dk = grid % dp.nkb, w.dq = (grid / dp.nkb) % dp.nqb, w.dh = (grid / (dp.nkb * dp.nqb)) % dp.Hb, w.db = grid / (dp.nkb * dp.nqb * dp.Hb);
     // XCD-local tile order: written for 8 XCDs of 32 CUs with workgroup i on XCD i % 8 (a whole MI355X); any other device keeps the plain order
-    w.xorder = (n == 256 && grid == 256 && dp.Hb % 8 == 0 && dp.nkb % 8 == 0 && dp.nqb % 4 == 0 && !(FASN_BWD_VARIANT & 4096)) ? 1 : 0;   // (developer library: bit 12 = plain tile order)
+    w.xorder = (n == 256 && grid == 256 && dp.Hb % 8 == 0 && dp.nkb % 8 == 0 && dp.nqb % 4 == 0) ? 1 : 0;
     FASN_LAUNCH(kern, dim3((unsigned)grid), dim3(512), smem, s, w);
     return launch_rc();
 }
@@ -53,8 +53,7 @@ static int launch_one(const DbiasParams& dp, hipStream_t s) {
     const FwdParams& f = dp.b.f;
     if constexpr (D == 64 || D == 128) {
         // 16-bit bias and gradient whose rows move in 16-byte pieces; no mask, or one without a row dimension (key padding) and unit key stride
-        const bool ws = f.bias_vec && !f.bias_f32 && f.bs[3] == 1 && !dp.out_f32 && dp.b.dbias_vec && (f.mask == nullptr || (f.ms[2] == 0 && f.ms[3] == 1)) && f.kvg == 1 &&
-                        !(FASN_BWD_VARIANT & 2048);   // (developer library: bwd_variant bit 11 = the round-3 kernel, for A/B)
+        const bool ws = f.bias_vec && !f.bias_f32 && f.bs[3] == 1 && !dp.out_f32 && dp.b.dbias_vec && (f.mask == nullptr || (f.ms[2] == 0 && f.ms[3] == 1)) && f.kvg == 1;
         if (ws) return launch_ws<Tag, D>(dp, s);
     }
     // the instantiation without per-element global access: 16-bit bias and gradient whose rows move in 16-byte pieces, a mask (if

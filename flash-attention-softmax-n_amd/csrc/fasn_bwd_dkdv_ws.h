@@ -25,22 +25,13 @@
 
 namespace fasn {
 
-#ifndef FASN_EXP_BIASHOT
-#ifndef FASN_WS_FRESH_DV
-#define FASN_WS_FRESH_DV 1
-#endif
-#define FASN_EXP_BIASHOT 0   // experiment: every bias request reads the first rows (always an L2 hit): separates fetch latency from issue cost
-#endif
-#ifndef FASN_WS_ATTR
-#define FASN_WS_ATTR
-#endif
 // DROP = 1 (round 4): attention-weight dropout. Wave A draws the keep bits and publishes P with the sign bit set for a dropped weight
 // (see fasn_bwd_dq_ws.h); its own dV GEMM takes the kept weights only and the 1/(1-p) goes on the dV accumulator at the end. A lane
 // owns a KEY here and its registers are rows, so the (row, key quad) state the forward computes once per 4 weights would be needed once
 // per weight - but the four lanes of a key quad hold the same 16 rows: each computes the state of ONE row of a 4-row register group and
 // the quad exchanges them with DPP quad_perm moves (4 states instead of 16 per block and lane, the same bits as everywhere else).
 template <typename Tag, int D, int MODE, int GQA = 0, int DROP = 0>   // GQA = 1: the loop over the query heads of a K/V group is compiled in
-__global__ void __launch_bounds__(512, 2) FASN_WS_ATTR fasn_bwd_dkdv_ws_kernel(const BwdParams bp) {
+__global__ void __launch_bounds__(512, 2) fasn_bwd_dkdv_ws_kernel(const BwdParams bp) {
     using E = ET<Tag>;
     using vec8 = typename E::vec8;
     const FwdParams& p = bp.f;
@@ -70,9 +61,6 @@ __global__ void __launch_bounds__(512, 2) FASN_WS_ATTR fasn_bwd_dkdv_ws_kernel(c
     const int l31 = lane & 31;
     const int hi = lane >> 5;
     const int role = wave >> 2;    // 0 = A (S, P, dV), 1 = B (dP, dS, dK)
-#if FASN_PRIO_WS   // (round 5 A/B: static wave priority for one role of a SIMD's pair: 1 = wave B, 2 = wave A)
-    if (role == (FASN_PRIO_WS == 1 ? 1 : 0)) __builtin_amdgcn_s_setprio(1);
-#endif
     const int kbw = wave & 3;      // key block of this wave inside the workgroup's 128 keys
     const DropSeed dsd = DROP ? drop_seed(p.seed_lo, p.seed_hi, p.rng) : DropSeed{0u, 0u};
     static_assert(!(DROP && GQA), "dropout with grouped K/V stays on the one-wave kernel");
@@ -88,18 +76,14 @@ __global__ void __launch_bounds__(512, 2) FASN_WS_ATTR fasn_bwd_dkdv_ws_kernel(c
         const int xcd = blockIdx.x & 7;
         int j = blockIdx.x >> 3;
         // Key-padded batch: a workgroup whose 128 keys are all padding has nothing to do, but under the in-order dispatcher its CU
-        // still waits a whole round for its next turn (tools/fasn_harness timeline) - skipping 22 % of C4's key blocks bought nothing.
+        // still waits a whole round for its next turn (per-workgroup time stamps, LABNOTES.md) - skipping 22 % of C4's key blocks bought nothing.
         // Every workgroup therefore reads the whole key-padding mask once (B x Sk bytes from L2, a few microseconds against its
         // milliseconds of work), marks the (batch, key block) pairs with a visible key, and takes the j-th VISIBLE pair of its
         // XCD's list (same order, batch fastest): the workgroups without work are the LAST ids of the launch and leave in whole rounds.
         constexpr int kCompactBytes = 64 * 1024, kCompactBlocks = 2048;
-#ifdef FASN_NO_COMPACT
-        const bool compact = false;
-#else
         const bool compact = KPD && !GQA && p.mask != nullptr && p.ms[1] == 0 && (int64_t)p.B * p.Sk <= kCompactBytes &&
                              p.B * bp.nblk <= kCompactBlocks && (p.Sk & 15) == 0 && (p.ms[0] & 15) == 0 &&
                              (reinterpret_cast<uintptr_t>(p.mask) & 15) == 0;
-#endif
         if (compact) {
             uint8_t* const vis = reinterpret_cast<uint8_t*>(smem);   // [B][nblk] (the Q buffers are not in use yet)
             for (int i = threadIdx.x; i < p.B * bp.nblk; i += 512) vis[i] = 0;
@@ -143,7 +127,7 @@ __global__ void __launch_bounds__(512, 2) FASN_WS_ATTR fasn_bwd_dkdv_ws_kernel(c
         bhk = bb * Hkv + (rest / bp.nblk) * 8 + xcd;
     } else {
         const bool causal0 = (MODE == MODE_CAUSAL) || (MODE >= MODE_GENERAL && p.causal);   // (key block 0 is the heaviest: ascending order = heaviest first)
-        block_to_work_grouped(blockIdx.x, p.B * Hkv, bp.nblk, (FASN_CAUSAL_GROUPS && causal0) ? causal_head_group(p.B * Hkv, p.Sq * kvg, D) : 1, bhk, kblk);
+        block_to_work_grouped(blockIdx.x, p.B * Hkv, bp.nblk, causal0 ? causal_head_group(p.B * Hkv, p.Sq * kvg, D) : 1, bhk, kblk);
     }
     const bool causal = (MODE == MODE_CAUSAL) || (MODE >= MODE_GENERAL && p.causal);
     const int b = bhk / Hkv, hk = bhk % Hkv;
@@ -261,14 +245,14 @@ __global__ void __launch_bounds__(512, 2) FASN_WS_ATTR fasn_bwd_dkdv_ws_kernel(c
     auto bias_request = [&](int row0, int slot) {   // kBiasPieces vector-memory requests
 #pragma unroll
         for (int i = 0; i < kBiasPieces; ++i)
-            lds_dma16(brw, __builtin_amdgcn_readfirstlane(ring_a + slot * 2048 + i * 1024), bvo, (FASN_EXP_BIASHOT ? 16 * i : row0 + 16 * i) * (int)p.bs[2] * 2);
+            lds_dma16(brw, __builtin_amdgcn_readfirstlane(ring_a + slot * 2048 + i * 1024), bvo, (row0 + 16 * i) * (int)p.bs[2] * 2);
     };
     // A lane owns a key column: its 16 rows of a block come out of the row-major ring through four transposing reads (lane i of a
     // 16-lane group addresses row 4hi + i/4, keys 4(i%4).. of its half and receives rows 4hi + {0..3} of key i), as packed pairs.
     const char* const ring_rd = ldsBias + kbw * (3 * 2048) + (4 * hi + ((lane & 15) >> 2)) * 64 + (((lane >> 4) & 1) * 16 + 4 * (lane & 3)) * 2;
     // (Measured and rejected: wave B touching the rows of a later tile as an L2 prefetch - one dword per row is 64 cache lines per
     // request and costs the texture addresser more than the hidden latency is worth: C4 backward 15.5 -> 16.8 ms. With every bias
-    // request forced to hit L2 (FASN_EXP_BIASHOT) the same launch takes 14.7 ms: that is all the fetch latency is worth.)
+    // request forced to hit L2 (an experiment build) the same launch takes 14.7 ms: that is all the fetch latency is worth.)
     auto bias_read = [&](int slot, u32x2 (&br)[4]) {
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
@@ -433,7 +417,7 @@ __global__ void __launch_bounds__(512, 2) FASN_WS_ATTR fasn_bwd_dkdv_ws_kernel(c
             // The addresses of the transposed dO reads from a fresh lane id (round 6) in the instantiations that otherwise keep 1 - 14 of them in scratch
             // across the tile loop (dropout, grouped K/V, fp16 bias + key padding); the others have the registers, and recomputing the addresses per
             // block costs them 2 % (config 4 backward 13.68 -> 13.97 ms)
-            constexpr bool FRESH = FASN_WS_FRESH_DV && (DROP || GQA || (MODE == MODE_BIAS_KEYPAD && std::is_same<Tag, f16_tag>::value));
+            constexpr bool FRESH = DROP || GQA || (MODE == MODE_BIAS_KEYPAD && std::is_same<Tag, f16_tag>::value);
             const int lane = FRESH ? fresh_lane_id() : (int)(threadIdx.x & 63);
 #pragma unroll
             for (int t2 = 0; t2 < 2; ++t2)

@@ -56,9 +56,6 @@ __global__ void __launch_bounds__(512, 2) fasn_bwd_dq_ws_kernel(const BwdParams 
     const int hi = lane >> 5;
     const int role = wave >> 2;   // 0 = A, 1 = B
     const int rbw = wave & 3;     // 32-row block of this wave inside the workgroup's 128 rows
-#if FASN_PRIO_WS   // (round 5 A/B: static wave priority for one role of a SIMD's pair: 1 = wave B (two of the three GEMMs), 2 = wave A (exponentials, bias))
-    if (role == (FASN_PRIO_WS == 1 ? 1 : 0)) __builtin_amdgcn_s_setprio(1);
-#endif
     const DropSeed dsd = DROP ? drop_seed(p.seed_lo, p.seed_hi, p.rng) : DropSeed{0u, 0u};
 
     // Ragged key-padded batch under a batch-broadcast bias (config 4): like the forward (fasn_fwd_kernel.h, kpair_plan) a workgroup takes
@@ -84,7 +81,7 @@ __global__ void __launch_bounds__(512, 2) fasn_bwd_dq_ws_kernel(const BwdParams 
         bh0 = bb * p.H + (rest / bp.nblk) * 8 + xcd;
     } else {
         const bool causal0 = (MODE == MODE_CAUSAL) || (MODE >= MODE_GENERAL && p.causal);
-        block_to_work_grouped(blockIdx.x, p.B * p.H, bp.nblk, (FASN_CAUSAL_GROUPS && causal0) ? causal_head_group(p.B * p.H, p.Sk, D) : 1, bh0, qi0);
+        block_to_work_grouped(blockIdx.x, p.B * p.H, bp.nblk, causal0 ? causal_head_group(p.B * p.H, p.Sk, D) : 1, bh0, qi0);
     }
     auto item = [&](const int bh, const int qi, auto SECOND_) __attribute__((always_inline)) {
     constexpr bool ROT = KPAIR && decltype(SECOND_)::value;   // second element of a length pair: rotated key walk (fasn_fwd_kernel.h, kpair_plan)

@@ -20,9 +20,6 @@
 #include "fasn_common.h"
 #include "fasn_fwd_kernel.h"
 
-#ifndef FASN_DKDV256_FRESH
-#define FASN_DKDV256_FRESH 1
-#endif
 namespace fasn {
 
 struct BwdParams {
@@ -39,8 +36,8 @@ struct BwdParams {
     char* dbias;       // optional: dS written densely [B,H,Sq,Sk] (element type of q), key stride 1; nullptr = not wanted
     int64_t dbs[3];
     int dbias_vec;     // rows 16-byte aligned: 8 keys per store on the vector path
-    float* dqacc;      // fused backward (developer library, tools/dev/fasn_bwd_fused.h): fp32 dQ accumulator [B,H,Sq,D] in the caller's workspace; nullptr = split kernels
-    int skip;          // host side only (launch_bwd_one): bit 0 = dK/dV, bit 1 = dQ are launched by the caller (fasn_bwd_pipe.h kernels)
+    float* dqacc;      // unused, always nullptr: kept so that the kernel arguments do not move (it was the one-pass backward's dQ accumulator)
+    int skip;          // host side only (launch_bwd_one): bit 1 = dQ, bit 2 = delta are launched by the caller (fasn_bwd_d256.hip)
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -102,10 +99,7 @@ FASN_DEV float row_delta(const u32x4 (&o)[KS], const u32x4 (&d)[KS]) {
 }
 // (D = 128 / 256: the one-wave dQ kernels are at their register limit, and so is the causal D = 32 instantiation with 64 rows per wave - 2 -> 6 spilled
 // registers with the O chunks live in its prologue: delta keeps its launch there)
-#ifndef FASN_DQ_FUSED_DELTA
-#define FASN_DQ_FUSED_DELTA 1   // (A/B: 0 = the one-wave dQ kernels read delta from the delta kernel's launch, as before round 5)
-#endif
-constexpr bool dq_computes_delta(int D, int QB, int MODE) { return FASN_DQ_FUSED_DELTA && (D == 64 || D == 32); }
+constexpr bool dq_computes_delta(int D) { return D == 64 || D == 32; }
 
 // shared helpers: stage a [64][D] tile (rows row0..row0+63 of one (b,h) matrix) global -> registers -> swizzled LDS image.
 // Buffer loads through a per-(b,h) descriptor: fixed per-thread byte offset, tile offset in an SGPR, rows past the end of
@@ -162,17 +156,9 @@ struct TileDma {
 
 // ---------------------------------------------------------------------------------------------
 // dQ: workgroup = 4 waves x QB x 32 query rows, loop over 64-key tiles.
-#ifndef FASN_BWD_UNROLL2
-#define FASN_BWD_UNROLL2 1
-#endif
-#ifndef FASN_DQ_SEED_D128
-#define FASN_DQ_SEED_D128 2
-#endif
-#ifndef FASN_DQ_SEED_D32
-#define FASN_DQ_SEED_D32 2
-#endif
+constexpr int dq_seed(int D) { return D == 64 ? 3 : 2; }   // DQ_SEED of the shipped instantiations (bit 0 = S, bit 1 = dP seeded; measurements: LABNOTES.md)
 // BF32 (round 5): fp32 bias image next to 16-bit q / k / v, as in the forward (fasn_fwd_kernel.h)
-template <typename Tag, int D, int QB, int MODE, int OCC, int DROP = 0, int DQ_SEED = (D >= 128 ? FASN_DQ_SEED_D128 : D == 32 ? FASN_DQ_SEED_D32 : 3), int BF32 = 0>
+template <typename Tag, int D, int QB, int MODE, int OCC, int DROP = 0, int DQ_SEED = dq_seed(D), int BF32 = 0>
 __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams bp) {
     static_assert(!BF32 || mode_has_vbias(MODE), "fp32 bias image: the vector bias modes");
     constexpr int IMGB = BF32 ? 8192 : 4096, IMGM = mode_has_vmask(MODE) ? 2048 : 0, BPC = BF32 ? 16 : 8, BW = BF32 ? 16 : 8;   // (fasn_fwd_kernel.h)
@@ -201,10 +187,10 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams b
     int bh, qi;
     const bool causal = (MODE == MODE_CAUSAL) || (MODE >= MODE_GENERAL && p.causal);
     // paired causal launch (see fasn_fwd_kernel.h): query block nblk-1-r, then block r, so that every workgroup walks the same number of tiles
-    constexpr bool PAIRABLE = (MODE == MODE_CAUSAL || (FASN_VEC_PAIR && D <= 128 && mode_is_vector(MODE) && !mode_has_keypad(MODE))) && (!DROP || (FASN_DROP_PAIR && MODE == MODE_CAUSAL));   // (round 6: also the vector modes under the causal flag, and the causal dropout kernels)
+    constexpr bool PAIRABLE = (MODE == MODE_CAUSAL || (D <= 128 && mode_is_vector(MODE) && !mode_has_keypad(MODE))) && (!DROP || MODE == MODE_CAUSAL);   // (round 6: also the vector modes under the causal flag, and the causal dropout kernels)
     // (a causal launch that does not pair - small, or grouped K/V in the dK/dV kernel below - takes its heads in groups, blocks heaviest first across a group: fasn_common.h)
     block_to_work_grouped(blockIdx.x, p.B * p.H, (PAIRABLE && p.pair) ? (bp.nblk + 1) / 2 : bp.nblk,
-                          (FASN_CAUSAL_GROUPS && causal && !(PAIRABLE && p.pair)) ? causal_head_group(p.B * p.H, p.Sk, D) : 1, bh, qi);
+                          (causal && !(PAIRABLE && p.pair)) ? causal_head_group(p.B * p.H, p.Sk, D) : 1, bh, qi);
     const int npass = (PAIRABLE && p.pair && qi != bp.nblk - 1 - qi) ? 2 : 1;
     for (int pass = 0; pass < npass; ++pass) {
     if (pass) __syncthreads();   // the first block's last tile has been read by every wave before the buffers are refilled
@@ -229,7 +215,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams b
         ntiles = min(ntiles, kmax < 0 ? 0 : (kmax / KT + 1));
     }
 
-    constexpr bool FUSE_DELTA = dq_computes_delta(D, QB, MODE);   // delta = rowsum(O o dO) of the lane's rows computed here and published (row_delta above)
+    constexpr bool FUSE_DELTA = dq_computes_delta(D);   // delta = rowsum(O o dO) of the lane's rows computed here and published (row_delta above)
     vec8 qf[QB][KS], dof[QB][KS];
     u32x4 ofr[FUSE_DELTA ? QB : 1][KS];
     float lse2[QB], dlt[QB];
@@ -412,11 +398,11 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams b
     }
 
     // the loop is unrolled by its two LDS buffers: the buffer offset is a compile-time constant and folds into the ds_read
-    // immediates instead of costing VALU adds per LDS address (FASN_BWD_UNROLL2 = 0: dynamic buffer index, for A/B)
+    // immediates instead of costing VALU adds per LDS address
     using Buf0 = std::integral_constant<int, 0>;
-    using Buf1 = std::integral_constant<int, FASN_BWD_UNROLL2 ? 1 : 0>;
+    using Buf1 = std::integral_constant<int, 1>;
     auto ktile_body = [&](const int t, auto BUF_) {
-        const int buf = FASN_BWD_UNROLL2 ? decltype(BUF_)::value : (t & 1);
+        constexpr int buf = decltype(BUF_)::value;
         const int k0 = t * KT;
         uint64_t kp_bits = ~0ull;
         if (KP && !VEC) {
@@ -586,7 +572,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams b
             }
             // dQ^T[d][q] += K^T[d][key] dS^T[key][q]
             // (D = 256 element-load mode: the addresses of the transposed reads from a fresh lane id, see the dK/dV kernel)
-            const int lane_t = (D == 256 && MODE == MODE_GENERAL_SLOW && FASN_DKDV256_FRESH) ? fresh_lane_id() : lane;
+            const int lane_t = (D == 256 && MODE == MODE_GENERAL_SLOW) ? fresh_lane_id() : lane;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -606,13 +592,9 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams b
         }
         __syncthreads();
     };
-    if constexpr (FASN_BWD_UNROLL2 != 0) {
-        for (int t = 0; t < ntiles; t += 2) {
-            ktile_body(t, Buf0{});
-            if (t + 1 < ntiles) ktile_body(t + 1, Buf1{});
-        }
-    } else {
-        for (int t = 0; t < ntiles; ++t) ktile_body(t, Buf0{});
+    for (int t = 0; t < ntiles; t += 2) {
+        ktile_body(t, Buf0{});
+        if (t + 1 < ntiles) ktile_body(t + 1, Buf1{});
     }
 
     if (VEC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the image requested for the tile past the end has landed
@@ -677,10 +659,10 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
     int bhk, kblk0;
     const int d0 = DH > 1 ? (int)(blockIdx.x % DH) * DB : 0;   // first feature block of this workgroup
     // paired causal launch (see fasn_fwd_kernel.h): key block r (seen by the most query rows), then block nblk-1-r
-    constexpr bool PAIRABLE = (MODE == MODE_CAUSAL || (FASN_VEC_PAIR && mode_is_vector(MODE) && !mode_has_keypad(MODE))) && (!DROP || (FASN_DROP_PAIR && MODE == MODE_CAUSAL)) && !GQA && DH == 1;
+    constexpr bool PAIRABLE = (MODE == MODE_CAUSAL || (mode_is_vector(MODE) && !mode_has_keypad(MODE))) && (!DROP || MODE == MODE_CAUSAL) && !GQA && DH == 1;
     const bool causal_l = (MODE == MODE_CAUSAL) || (MODE >= MODE_GENERAL && p.causal);
     block_to_work_grouped(DH > 1 ? (int)(blockIdx.x / DH) : (int)blockIdx.x, p.B * Hkv, (PAIRABLE && p.pair) ? (bp.nblk + 1) / 2 : bp.nblk,
-                          (FASN_CAUSAL_GROUPS && causal_l && !(PAIRABLE && p.pair)) ? causal_head_group(p.B * Hkv, p.Sq * kvg, D) : 1, bhk, kblk0);
+                          (causal_l && !(PAIRABLE && p.pair)) ? causal_head_group(p.B * Hkv, p.Sq * kvg, D) : 1, bhk, kblk0);
     const int npass = (PAIRABLE && p.pair && kblk0 != bp.nblk - 1 - kblk0) ? 2 : 1;
     for (int pass = 0; pass < npass; ++pass) {
     if (pass) __syncthreads();   // the first block's last tile has been read by every wave before the buffers are refilled
@@ -907,11 +889,11 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
         kp_none = !__any(any);
     }
     // the loop is unrolled by its two LDS buffers: the buffer offset is a compile-time constant and folds into the ds_read
-    // immediates instead of costing VALU adds per LDS address (FASN_BWD_UNROLL2 = 0: dynamic buffer index, for A/B)
+    // immediates instead of costing VALU adds per LDS address
     using Buf0 = std::integral_constant<int, 0>;
-    using Buf1 = std::integral_constant<int, FASN_BWD_UNROLL2 ? 1 : 0>;
+    using Buf1 = std::integral_constant<int, 1>;
     auto qtile_body = [&](const int tq, auto BUF_) {
-        const int buf = FASN_BWD_UNROLL2 ? decltype(BUF_)::value : ((tq - tq0) & 1);
+        constexpr int buf = decltype(BUF_)::value;
         const int r0 = tq * QT;
         if (tq + 1 < ntq) {
             if (DIRECT) {   // buffer buf^1 was released by the barrier that ended the previous tile
@@ -990,7 +972,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
 #pragma unroll
                     for (int r = 0; r < 16; ++r) pacc[kb][r] = SEED_P ? xr[r] : 0.f;
                 }
-                const int lane_s = (D == 256 && MODE == MODE_GENERAL_SLOW && FASN_DKDV256_FRESH) ? fresh_lane_id() : lane;   // (likewise the row fragments' addresses)
+                const int lane_s = (D == 256 && MODE == MODE_GENERAL_SLOW) ? fresh_lane_id() : lane;   // (likewise the row fragments' addresses)
 #pragma unroll
                 for (int s = 0; s < KS; ++s) {
                     vec8 qa = lds_read_rowfrag<E, D>(tQ, qb * 32 + (lane_s & 31), s, lane_s >> 5);
@@ -1061,7 +1043,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
                 }
                 // dV^T[d][key] += dO^T[d][q] P[q][key];  dK^T[d][key] += Q^T[d][q] dS[q][key]
                 // (D = 256 vector modes: the addresses of the transposed reads from a fresh lane id - kept across the tile loop, 43 - 59 of them went to scratch)
-                const int lane_t = (D == 256 && (VEC || MODE == MODE_GENERAL_SLOW) && FASN_DKDV256_FRESH) ? fresh_lane_id() : lane;
+                const int lane_t = (D == 256 && (VEC || MODE == MODE_GENERAL_SLOW)) ? fresh_lane_id() : lane;
 #pragma unroll
                 for (int t2 = 0; t2 < 2; ++t2)
 #pragma unroll
@@ -1090,13 +1072,9 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
         if (DIRECT) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the next Q / dO tiles have landed
         __syncthreads();
     };
-    if constexpr (FASN_BWD_UNROLL2 != 0) {
-        for (int tq = tq0; tq < ntq; tq += 2) {
-            qtile_body(tq, Buf0{});
-            if (tq + 1 < ntq) qtile_body(tq + 1, Buf1{});
-        }
-    } else {
-        for (int tq = tq0; tq < ntq; ++tq) qtile_body(tq, Buf0{});
+    for (int tq = tq0; tq < ntq; tq += 2) {
+        qtile_body(tq, Buf0{});
+        if (tq + 1 < ntq) qtile_body(tq + 1, Buf1{});
     }
 
     }   // query heads of the group

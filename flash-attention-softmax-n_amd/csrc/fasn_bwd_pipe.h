@@ -363,375 +363,6 @@ __global__ void __launch_bounds__(256, 2) fasn_bwd_dkdv_pipe_kernel(const BwdPar
     }   // pass
 }
 
-// MFMA with its C / D operands in ARCHITECTURAL registers and its B operand in the accumulator half, as inline assembly: with 512
-// registers per lane hipcc selects the accumulator form for EVERY builtin MFMA and copies each S / dP tile out with 16 v_accvgpr_read
-// (272 moves per 64 MFMAs in the first build of the kernel below). The builtin (accumulator) form stays for dK / dV, which only
-// MFMAs touch. The hazard recogniser does not look inside an asm statement: results of these MFMAs are consumed one phase (>= 8
-// MFMAs) later, and mfma_guard() stands where a phase could be scheduled too close.
-template <typename Tag> struct MfmaV;
-template <> struct MfmaV<bf16_tag> {
-    template <typename V> static FASN_DEV void first(f32x16& d, const V& a, const V& b, const f32x16& c) {
-        asm("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-    }
-    template <typename V> static FASN_DEV void next(f32x16& d, const V& a, const V& b) {
-        asm("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    }
-};
-template <> struct MfmaV<f16_tag> {
-    template <typename V> static FASN_DEV void first(f32x16& d, const V& a, const V& b, const f32x16& c) {
-        asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(d) : "v"(a), "a"(b), "v"(c));
-    }
-    template <typename V> static FASN_DEV void next(f32x16& d, const V& a, const V& b) {
-        asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(d) : "v"(a), "a"(b));
-    }
-};
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The same pipeline with KB 32-key blocks per wave and ONE wave per SIMD (512 registers: the dK / dV accumulators and the K / V
-// fragments, which only MFMAs touch, can live in the accumulator half of the file). Every Q / dO fragment and every row-statistics
-// read from LDS then feeds KB blocks: LDS instructions per MFMA fall by KB. The row statistics are read into their own registers
-// and enter as the untied C operand of the first MFMA of each chain; the causal diagonal zeroes hidden P / dS behind the element pass.
-template <typename Tag, int MODE, int KB>
-__global__ void __launch_bounds__(256, 1) fasn_bwd_dkdv_pipe2_kernel(const BwdParams bp) {
-    static_assert(MODE == MODE_PLAIN || MODE == MODE_CAUSAL, "pipelined dK/dV: plain and causal");
-    using E = ET<Tag>;
-    using vec8 = typename E::vec8;
-    const FwdParams& p = bp.f;
-    constexpr int D = 64, KS = 4, DB = 2, BN = 4 * KB * 32;
-    constexpr int TILEB = PQT * D * 2;   // 8 KiB
-    constexpr bool causal = MODE == MODE_CAUSAL;
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* const ldsQ = smem;                                                    // [PNB][TILEB]
-    char* const ldsDO = smem + PNB * TILEB;                                     // [PNB][TILEB]
-    float* const ldsLse = reinterpret_cast<float*>(smem + 2 * PNB * TILEB);     // [PNB][PQT]  -lse*log2e
-    float* const ldsDlt = ldsLse + PNB * PQT;                                   // [PNB][PQT]  -delta
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int l31 = lane & 31;
-    const int hi = lane >> 5;
-
-    int bh, kblk0;
-    block_to_work((int)blockIdx.x, p.B * p.H, (causal && p.pair) ? (bp.nblk + 1) / 2 : bp.nblk, bh, kblk0);
-    const int npass = (causal && p.pair && kblk0 != bp.nblk - 1 - kblk0) ? 2 : 1;
-    const int b = bh / p.H, h = bh % p.H;
-    const int coff = p.Sk - p.Sq;
-    const char* qbase = p.q + (b * p.qs[0] + h * p.qs[1]) * 2;
-    const char* kbase = p.k + (b * p.ks[0] + h * p.ks[1]) * 2;
-    const char* vbase = p.v + (b * p.vs[0] + h * p.vs[1]) * 2;
-    const char* dobase = bp.dout + (b * bp.dos[0] + h * bp.dos[1]) * 2;
-    const float* lsebase = p.lse + (int64_t)bh * p.Sq;
-    const float* dltbase = bp.delta + (int64_t)bh * p.Sq;
-
-    TileDma<D, 2> tdQ, tdD;
-    tdQ.init(tid, p.qs[2]);
-    tdD.init(tid, bp.dos[2]);
-    const u32x4 qrw = make_rsrc_words(qbase, bp.qbytes), drw = make_rsrc_words(dobase, bp.dobytes);
-    const uint32_t ldsQ_w = lds_addr(smem) + wave * 1024, ldsDO_w = ldsQ_w + PNB * TILEB;
-
-    for (int pass = 0; pass < npass; ++pass) {
-    if (pass) __syncthreads();   // every wave has read the last tile of the first key block before the buffers are refilled
-    const int kblk = pass == 0 ? kblk0 : bp.nblk - 1 - kblk0;
-    const int kw0 = kblk * BN + wave * (KB * 32);   // first key of this wave
-
-    const int ntq = (p.Sq + PQT - 1) / PQT;
-    int tq0 = 0;
-    if (causal) {
-        const int first_row = kblk * BN - coff;
-        tq0 = first_row <= 0 ? 0 : first_row / PQT;
-    }
-    const int nt = ntq - tq0;
-
-    f32x16 dkacc[KB][DB], dvacc[KB][DB];
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int d = 0; d < DB; ++d)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                dkacc[kb][d][r] = 0.f;
-                dvacc[kb][d][r] = 0.f;
-            }
-
-    if (nt > 0) {
-    vec8 kf[KB][KS], vf[KB][KS];
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-        const int key = kw0 + kb * 32 + l31;
-        const bool ok = key < p.Sk;
-        const char* rk = kbase + (int64_t)key * p.ks[2] * 2 + hi * 16;
-        const char* rv = vbase + (int64_t)key * p.vs[2] * 2 + hi * 16;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            u32x4 a = {0u, 0u, 0u, 0u}, c = {0u, 0u, 0u, 0u};
-            if (ok) {
-                a = gload16(rk + s * 32);
-                c = gload16(rv + s * 32);
-            }
-            __builtin_memcpy(&kf[kb][s], &a, 16);
-            __builtin_memcpy(&vf[kb][s], &c, 16);
-        }
-    }
-
-    float stL = 0.f, stX = 0.f;
-    auto stats_gload = [&](int row0) {
-        if (tid < PQT) {
-            const int gr = row0 + tid;
-            float l = INFINITY, x = 0.f;
-            if (gr < p.Sq) {
-                l = lsebase[gr];
-                x = dltbase[gr];
-            }
-            stL = (l == -INFINITY || l == INFINITY) ? -INFINITY : -l * kLog2e;   // a row without weights: every P = exp2(-inf) = 0
-            stX = -x;
-        }
-    };
-    auto stats_lstore = [&](int buf) {
-        if (tid < PQT) {
-            ldsLse[buf * PQT + tid] = stL;
-            ldsDlt[buf * PQT + tid] = stX;
-        }
-    };
-    auto tile_dma = [&](int t, int buf) {   // tile t (local index) -> buffer buf
-        tdQ.dma(qrw, ldsQ_w + buf * TILEB, (tq0 + t) * PQT, p.qs[2]);
-        tdD.dma(drw, ldsDO_w + buf * TILEB, (tq0 + t) * PQT, bp.dos[2]);
-    };
-
-    tile_dma(0, 0);
-    stats_gload(tq0 * PQT);
-    stats_lstore(0);
-    if (nt > 1) {
-        tile_dma(1, 1);
-        stats_gload((tq0 + 1) * PQT);
-    }
-    if (nt > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");   // tile 0 has landed (the four pieces of tile 1 may still fly)
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            retire_loads(kf[kb][s]);
-            retire_loads(vf[kb][s]);
-            uint16_t hk[8];
-            __builtin_memcpy(hk, &kf[kb][s], 16);
-            f32x8 f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = E::to_f32(hk[e]) * p.c;
-            kf[kb][s] = E::cvt8(f);
-        }
-
-    f32x16 sX[KB], pX[KB], sY[KB], pY[KB];   // S' / dP' (then P / dS) of the even and the odd row block in flight
-    f32x16 lr, xr;                 // row statistics of the block whose S MFMAs come next (C operand of the first MFMA of each chain)
-    vec8 qa[KS], da[KS];           // row fragments of that block
-    vec8 dot[2][DB], qt[2][DB];    // transposed fragments of the block whose G MFMAs come next
-    vec8 pk[KB][2], dsk[KB][2];    // 16-bit P, dS of that block
-#define FASN_SB() __builtin_amdgcn_sched_barrier(0)
-    auto pin = [](auto& x) __attribute__((always_inline)) { asm volatile("" : "+v"(x)); };
-    auto pin_a = [](auto& x) __attribute__((always_inline)) { asm volatile("" : "+a"(x)); };   // the value lives in the accumulator half of the file HERE
-    auto pin_acc = [&]() __attribute__((always_inline)) {
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int d = 0; d < DB; ++d) pin_a(dkacc[kb][d]), pin_a(dvacc[kb][d]);
-    };
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-        for (int s = 0; s < KS; ++s) pin_a(kf[kb][s]), pin_a(vf[kb][s]);
-    pin_acc();
-
-    auto load_rf_q = [&](int bo, int qb) __attribute__((always_inline)) {
-        const char* tQ = ldsQ + bo;
-        const float* tL = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ldsLse) + (bo >> 5));
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) qa[ks] = lds_read_rowfrag<E, D>(tQ, qb * 32 + l31, ks, hi);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 a = *LDS_PTR(const f32x4, tL + qb * 32 + 8 * g + 4 * hi);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) lr[4 * g + e] = a[e];
-        }
-    };
-    auto load_rf_d = [&](int bo, int qb) __attribute__((always_inline)) {
-        const char* tD = ldsDO + bo;
-        const float* tX = reinterpret_cast<const float*>(reinterpret_cast<const char*>(ldsDlt) + (bo >> 5));
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) da[ks] = lds_read_rowfrag<E, D>(tD, qb * 32 + l31, ks, hi);
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 c = *LDS_PTR(const f32x4, tX + qb * 32 + 8 * g + 4 * hi);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) xr[4 * g + e] = c[e];
-        }
-    };
-    auto mfma_S1 = [&](f32x16 (&s)[KB]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) MfmaV<Tag>::first(s[kb], qa[0], kf[kb][0], lr);
-#pragma unroll
-        for (int ks = 1; ks < KS; ++ks)
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) MfmaV<Tag>::next(s[kb], qa[ks], kf[kb][ks]);
-    };
-    auto mfma_S2 = [&](f32x16 (&pp)[KB]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) MfmaV<Tag>::first(pp[kb], da[0], vf[kb][0], xr);
-#pragma unroll
-        for (int ks = 1; ks < KS; ++ks)
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) MfmaV<Tag>::next(pp[kb], da[ks], vf[kb][ks]);
-    };
-    auto load_tr = [&](int bo, int qb, int t2) __attribute__((always_inline)) {
-        const char* tQ = ldsQ + bo;
-        const char* tD = ldsDO + bo;
-#pragma unroll
-        for (int d = 0; d < DB; ++d) {
-            dot[t2][d] = lds_read_trfrag<E, D>(tD, qb * 32 + 16 * t2, d, lane);
-            qt[t2][d] = lds_read_trfrag<E, D>(tQ, qb * 32 + 16 * t2, d, lane);
-        }
-    };
-    auto mfma_G = [&](int t2) __attribute__((always_inline)) {
-#pragma unroll
-        for (int d = 0; d < DB; ++d)
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) {
-                dvacc[kb][d] = E::mfma(dot[t2][d], pk[kb][t2], dvacc[kb][d]);
-                dkacc[kb][d] = E::mfma(qt[t2][d], dsk[kb][t2], dkacc[kb][d]);
-            }
-    };
-    auto elem_half = [&](f32x16 (&s)[KB], f32x16 (&pp)[KB], int half) __attribute__((always_inline)) {
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-#pragma unroll
-            for (int rr = 0; rr < 8; ++rr) s[kb][8 * half + rr] = fast_exp2(s[kb][8 * half + rr]);
-            // dP' comes from an asm MFMA (no hazard bookkeeping by the compiler): its first reader stands behind the eight exponentials
-            asm volatile("s_nop 3" : "+v"(s[kb]), "+v"(pp[kb]));
-#pragma unroll
-            for (int rr = 0; rr < 8; ++rr) pp[kb][8 * half + rr] *= s[kb][8 * half + rr];
-        }
-    };
-    auto pack = [&](const f32x16 (&s)[KB], const f32x16 (&pp)[KB]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb)
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) {
-                f32x8 x, y;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    x[e] = s[kb][8 * t2 + e];
-                    y[e] = pp[kb][8 * t2 + e];
-                }
-                pk[kb][t2] = E::cvt8(x);
-                dsk[kb][t2] = E::cvt8(y);
-                pin(pk[kb][t2]), pin(dsk[kb][t2]);
-            }
-    };
-    // causal diagonal: zero the hidden P and dS of the block (rows r0 ..) in a small wave-uniform branch between the phases
-    auto diag_mask = [&](f32x16 (&s)[KB], f32x16 (&pp)[KB], int r0) __attribute__((always_inline)) {
-        if (causal && (r0 + coff) < (kw0 + KB * 32 - 1)) {
-#pragma unroll
-            for (int kb = 0; kb < KB; ++kb) {
-                const int key = kw0 + kb * 32 + l31;
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = r0 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                    const bool show = key <= row + coff;
-                    s[kb][r] = show ? s[kb][r] : 0.f;
-                    pp[kb][r] = show ? pp[kb][r] : 0.f;
-                }
-            }
-        }
-    };
-    using TrueT = std::true_type;
-    using FalseT = std::false_type;
-    auto phase_a = [&](auto HAVE_PREV, f32x16 (&s)[KB], f32x16 (&pp)[KB], const f32x16 (&ps)[KB], const f32x16 (&ppp)[KB], int pbo, int pqb) __attribute__((always_inline)) {
-        constexpr bool hp = decltype(HAVE_PREV)::value;
-        mfma_S1(s);
-        if (hp) pack(ps, ppp);
-        FASN_SB();
-        if (hp) load_tr(pbo, pqb, 0);
-        mfma_S2(pp);
-        FASN_SB();
-        if (hp) load_tr(pbo, pqb, 1);
-        // the row statistics are the untied C operand of asm MFMAs, read over the MFMA's passes: their registers stay allocated until
-        // here (the compiler believes an asm statement is done when it has issued and would hand them to the next VALU result)
-        asm volatile("" ::"v"(lr), "v"(xr));
-        FASN_SB();
-    };
-    auto phase_b = [&](auto HAVE_PREV, f32x16 (&s)[KB], f32x16 (&pp)[KB], int r0, int nbo, int nqb) __attribute__((always_inline)) {
-        constexpr bool hp = decltype(HAVE_PREV)::value;
-        if (hp) mfma_G(0);
-        elem_half(s, pp, 0);
-        FASN_SB();
-        load_rf_q(nbo, nqb);
-        if (hp) mfma_G(1);
-        elem_half(s, pp, 1);
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) pin(s[kb]), pin(pp[kb]);
-        FASN_SB();
-        load_rf_d(nbo, nqb);
-        FASN_SB();
-        diag_mask(s, pp, r0);
-        FASN_SB();
-    };
-
-    int bo = 0;
-    load_rf_q(0, 0);
-    load_rf_d(0, 0);
-    auto tile_body = [&](const int t, auto FIRST) __attribute__((always_inline)) {
-        constexpr bool first = decltype(FIRST)::value;
-        const int r0 = (tq0 + t) * PQT;
-        const int bo_prev = bo == 0 ? (PNB - 1) * TILEB : bo - TILEB;
-        const int bo_next = bo == (PNB - 1) * TILEB ? 0 : bo + TILEB;
-        phase_a(std::integral_constant<bool, !first>{}, sX, pX, sY, pY, bo_prev, 1);
-        phase_b(std::integral_constant<bool, !first>{}, sX, pX, r0, bo, 1);
-        phase_a(TrueT{}, sY, pY, sX, pX, bo, 0);
-        if (t + 1 < nt) {
-            stats_lstore(bo_next == 0 ? 0 : (bo_next == TILEB ? 1 : 2));
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (t + 2 < nt) {
-                tile_dma(t + 2, bo_prev == 0 ? 0 : (bo_prev == TILEB ? 1 : 2));
-                stats_gload((tq0 + t + 2) * PQT);
-            }
-        }
-        phase_b(TrueT{}, sY, pY, r0 + 32, bo_next, 0);
-        pin_acc();
-        bo = bo_next;
-    };
-    tile_body(0, TrueT{});
-    for (int t = 1; t < nt; ++t) tile_body(t, FalseT{});
-    {
-        const int bo_last = bo == 0 ? (PNB - 1) * TILEB : bo - TILEB;
-        pack(sY, pY);
-        load_tr(bo_last, 1, 0);
-        load_tr(bo_last, 1, 1);
-        mfma_G(0);
-        mfma_G(1);
-    }
-#undef FASN_SB
-    }   // nt > 0
-
-    char* dkbase = bp.dk + (b * bp.dks[0] + h * bp.dks[1]) * 2;
-    char* dvbase = bp.dv + (b * bp.dvs[0] + h * bp.dvs[1]) * 2;
-#pragma unroll
-    for (int kb = 0; kb < KB; ++kb) {
-        const int key = kw0 + kb * 32 + l31;
-        if (key < p.Sk) {
-            char* rk = dkbase + (int64_t)key * bp.dks[2] * 2;
-            char* rv = dvbase + (int64_t)key * bp.dvs[2] * 2;
-#pragma unroll
-            for (int d = 0; d < DB; ++d) {
-                store_block_wide<E>(rk + d * 64, dkacc[kb][d], bp.scale, hi);
-                store_block_wide<E>(rv + d * 64, dvacc[kb][d], 1.0f, hi);
-            }
-        }
-    }
-    }   // pass
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
 // dQ: workgroup = 4 waves x 32 query rows, walks 64-key K / V tiles; a lane owns a query row (S^T, dP^T, dS^T are [key][row]
 // accumulator tiles, dS^T feeds dQ^T[d][q] += K^T[d][key] dS^T[key][q] straight from registers), as fasn_bwd_dq_kernel.

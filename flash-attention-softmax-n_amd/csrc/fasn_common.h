@@ -4,13 +4,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifndef FASN_PRIO8
-#define FASN_PRIO8 0   // (round 5 A/B: static s_setprio 1 for the second-dispatched half of the 8-wave forward workgroups, cdna_hip_programming.md T5 static form)
-#endif
-#ifndef FASN_PRIO_WS
-#define FASN_PRIO_WS 0   // (round 5 A/B, two-wave backward kernels: static s_setprio 1 for wave B (1) or wave A (2) of every SIMD's pair)
-#endif
-
 namespace fasn {
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -451,9 +444,6 @@ FASN_DEV void block_to_work(int bid, int nbh, int nblk_per_head, int& bh, int& b
 // (4,16,2048,128), measured 0.69 of the non-causal time where 0.53 is the work). Heads are therefore taken in GROUPS of G per XCD and the blocks of a
 // group handed out block index by block index (heaviest first, see the callers): a decreasing sequence per group, which list scheduling packs tightly.
 // G = as many heads as share the XCD's 4 MiB L2 with their K / V (or Q / dO) - at most 4, a power of two that divides the XCD's heads.
-#ifndef FASN_CAUSAL_GROUPS
-#define FASN_CAUSAL_GROUPS 1
-#endif
 FASN_DEV int causal_head_group(int nbh, int rows, int D) {
     if ((nbh & 7) != 0) return 1;
     const int hx = nbh >> 3;

@@ -81,11 +81,7 @@ struct F32Drop {
     DropSeed dsd;
     uint32_t thr;
     FASN_DEV explicit F32Drop(const FwdParams& p) : dsd(p.drop_thr ? drop_seed(p.seed_lo, p.seed_hi, p.rng) : DropSeed{0u, 0u}), thr(p.drop_thr ? p.drop_thr : 1u) {}
-#ifdef FASN_F32_NODROP
-    FASN_DEV bool keep(int, int, int) const { return true; }
-#else
     FASN_DEV bool keep(int bh, int row, int key) const { return drop_keep_at(dsd, (uint32_t)bh, (uint32_t)row, (uint32_t)key, thr); }
-#endif
 };
 
 // ------------------------------------------------------------------------------------------------ forward

@@ -6,9 +6,6 @@
 // zero-range descriptor / an all-ones word), key padding rides the plain kernel, everything else the element-load kernel.
 #include "fasn_launch.h"
 #include "fasn_fwd_ws256.h"
-#ifndef FASN_D256_GEN_WS
-#define FASN_D256_GEN_WS 1
-#endif
 namespace fasn {
 // plain / causal: the two-wave kernel (fasn_fwd_ws256.h, round 4): 128-row workgroups of 8 waves, no score computed twice
 template <typename Tag, int MODE, int DROP = 0>
@@ -26,24 +23,15 @@ static int go(const FwdParams& p, const FwdLaunch& l, hipStream_t s) {
     if (p.drop_thr) {   // dropout (round 6): the vector general instantiation whenever the call's mask / bias rows move as vectors (or there is no operand)
         const int md = (l.mode == MODE_BIAS_KEYPAD || l.mode == MODE_KEYPAD) ? p.keypad_fallback : l.mode;
         if (md == MODE_GENERAL_SLOW) return launch_fwd_one<Tag, 256, 1, MODE_GENERAL_SLOW, 1, 4, 0, 0, 1, 2>(p, s);   // the element-load kernel
-        if (FASN_D256_GEN_WS) return launch_ws256<Tag, MODE_GENERAL, 1>(p, s);   // the two-wave kernel (per-wave images; keep bits on the packed weights)
-        return launch_fwd_one<Tag, 256, 1, MODE_GENERAL, 1, 4, 0, 2, 1, 2>(p, s);
+        return launch_ws256<Tag, MODE_GENERAL, 1>(p, s);   // the two-wave kernel (per-wave images; keep bits on the packed weights)
     }
     const int mode = l.mode == MODE_BIAS_KEYPAD ? p.keypad_fallback : l.mode;   // bias + key padding: the dense-mask view of the same mask
-#ifdef FASN_DEV_VARIANTS
-    if (l.variant == 1) {   // A/B: the round-3 feature-half kernels
-        if (mode == MODE_PLAIN) return launch_fwd_one<Tag, 256, 1, MODE_PLAIN, 1, 4, 0, 2, 0, 2>(p, s);
-        if (mode == MODE_CAUSAL) return launch_fwd_one<Tag, 256, 1, MODE_CAUSAL, 1, 4, 0, 2, 0, 2>(p, s);
-        if (mode == MODE_KEYPAD) return launch_fwd_one<Tag, 256, 1, MODE_KEYPAD, 1, 4, 0, 2, 0, 2>(p, s);
-    }
-#endif
     switch (mode) {
         case MODE_PLAIN: return launch_ws256<Tag, MODE_PLAIN>(p, s);
         case MODE_CAUSAL: return launch_ws256<Tag, MODE_CAUSAL>(p, s);
         case MODE_KEYPAD: return launch_ws256<Tag, MODE_KEYPAD>(p, s);
-        case MODE_GENERAL: case MODE_GENERAL_B: case MODE_GENERAL_M:   // dense mask and / or 16-bit bias: the two-wave kernel with per-wave images (round 6; FASN_D256_GEN_WS=0: the feature-half kernel)
-            if (FASN_D256_GEN_WS) return launch_ws256<Tag, MODE_GENERAL>(p, s);
-            return launch_fwd_one<Tag, 256, 1, MODE_GENERAL, 1, 4, 0, 2, 0, 2>(p, s);
+        case MODE_GENERAL: case MODE_GENERAL_B: case MODE_GENERAL_M:   // dense mask and / or 16-bit bias: the two-wave kernel with per-wave images (round 6; the feature-half kernel it replaced: LABNOTES.md)
+            return launch_ws256<Tag, MODE_GENERAL>(p, s);
         default: return launch_fwd_one<Tag, 256, 1, MODE_GENERAL_SLOW, 1, 4, 0, 0, 0, 2>(p, s);
     }
 }

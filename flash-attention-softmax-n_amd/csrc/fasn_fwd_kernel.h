@@ -23,21 +23,6 @@
 #include <type_traits>
 #include "fasn_common.h"
 
-#ifndef FASN_UNR3_D128
-#define FASN_UNR3_D128 1
-#endif
-#ifndef FASN_SEED_KEEPALIVE
-#define FASN_SEED_KEEPALIVE 1
-#endif
-#ifndef FASN_FWD_UNR2
-#define FASN_FWD_UNR2 1
-#endif
-#ifndef FASN_VEC_PAIR
-#define FASN_VEC_PAIR 1
-#endif
-#ifndef FASN_DROP_PAIR
-#define FASN_DROP_PAIR 1   // paired blocks in the causal dropout forward too (round 6)
-#endif
 namespace fasn {
 
 // MODE_GENERAL: mask and/or bias through 4-key vector (buffer) loads - needs key stride 1 and aligned rows (bias_vec /
@@ -85,15 +70,12 @@ struct FwdParams {
     int keypad_fallback;   // MODE_KEYPAD launches: the general mode (vector or element-load) the same mask would otherwise take
     int nsplit, tps;
     int pair;       // causal (MODE_CAUSAL kernels): one workgroup takes query block r AND block nqblk-1-r of its head, one after the other
-    int kprot;      // length-paired batch elements: rotate the key walk of the second element (kpair_plan's `lead`); 0 = developer A/B
+    int kprot;      // length-paired batch elements: rotate the key walk of the second element (kpair_plan's `lead`); always 1
     float* part_o;   // [B*H][nsplit][Sq][D]
     float* part_ml;  // [B*H][nsplit][Sq][2]
     int* xq;         // eight zeroed item counters (caller's workspace, fasn_fwd_ws): dynamic deal of the (head, query block) items across XCDs; nullptr = static deal
     const float* nt; // per-(batch, head) softmax_n (fasn_fwd_n): item (b, h) reads nt[b * nsb + h * nsh] instead of `n`; nullptr = `n` for every item
     int nsb, nsh;
-#ifdef FASN_DEV_VARIANTS
-    unsigned long long* timeline;   // developer library: per workgroup {t_entry, t_loop, t_epilogue, t_end, hw_id, xcc_id, ntiles, 0} (100 MHz clock)
-#endif
 };
 // softmax_n of the work item (b, h): the caller's per-(batch, head) tensor (fasn_fwd_n) or the call's scalar. Wave-uniform: one load per item,
 // the value is moved to an SGPR (a run-time select rather than a template flag: the scalar-n kernels keep their instantiations)
@@ -103,15 +85,6 @@ FASN_DEV float item_n(const FwdParams& p, int b, int h) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.nt[i])));
 }
 
-#ifdef FASN_DEV_VARIANTS
-#define FASN_STAMP(slot) do { if (p.timeline != nullptr && threadIdx.x == 0) p.timeline[(size_t)blockIdx.x * 8 + (slot)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define FASN_STAMP(slot) do { } while (0)
-#endif
-
-#ifndef FASN_XADDR
-#define FASN_XADDR 1
-#endif
 constexpr int KT = 64;  // keys per tile
 // key-padding modes: visibility words (one per K/V tile) kept in LDS by the forward kernels: 4 KiB, Sk <= 32768. Longer key
 // sequences take the dense-mask general mode of the same mask (fasn_api.hip).
@@ -164,7 +137,7 @@ constexpr int kPairMaxBatch = 64, kPairMaxBytes = 64 * 1024;
 FASN_DEV bool kpair_plan(const FwdParams& p, char* scratch, int tid, int slot, int& b0, int& b1, int& lead) {
     lead = 0;
     if (p.mask == nullptr || p.ms[1] != 0 || p.B < 2 || p.B > kPairMaxBatch || (int64_t)p.B * p.Sk > kPairMaxBytes || (p.Sk & 15) != 0 ||
-        (p.ms[0] & 15) != 0 || (reinterpret_cast<uintptr_t>(p.mask) & 15) != 0 || p.pair == 2)   // (pair 2 / 3: developer override)
+        (p.ms[0] & 15) != 0 || (reinterpret_cast<uintptr_t>(p.mask) & 15) != 0 || p.pair == 2)   // (pair 2 = never / 3 = whatever the lengths: values of a retired A/B switch that no launch sets; removing them changes the kernels' code)
         return false;
     int* const len = reinterpret_cast<int*>(scratch);
     const int nthreads = (int)blockDim.x;
@@ -238,8 +211,8 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     using E = ET<Tag>;
     using vec8 = typename E::vec8;
     constexpr bool PSUM = SEED >= 2;   // fast-path row sums from the packed weights (dropout masks the packed weights AFTER the sum)
-    constexpr bool UNR3 = RING == 2 && (D <= 64 || (FASN_UNR3_D128 && NW == 8 && !mode_is_vector(MODE) && !DROP));  // direct-to-LDS loop unrolled by its three buffers
-    constexpr bool UNR2 = RING == 0 && FASN_FWD_UNR2;   // single-set staging: loop unrolled by its two LDS buffers
+    constexpr bool UNR3 = RING == 2 && (D <= 64 || (NW == 8 && !mode_is_vector(MODE) && !DROP));  // direct-to-LDS loop unrolled by its three buffers
+    constexpr bool UNR2 = RING == 0;   // single-set staging: loop unrolled by its two LDS buffers
     constexpr int NT = NW * 64;
     constexpr int BM = NW * QB * 32;
     constexpr int ROWB = D * 2;
@@ -261,7 +234,6 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     const int l31 = lane & 31;
     const int hi = lane >> 5;
 
-    FASN_STAMP(0);
     int bh, qi, split = 0;
     // Dynamic deal of the work items across XCDs (round 5, long plain / causal launches through fasn_fwd_ws): the XCDs
     // of a part differ by up to 4 % and the dispatcher deals each exactly 1/8 of the workgroups. With p.xq set the ITEMS are dealt dynamically
@@ -303,7 +275,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     // a ballot turns the 64 bytes into a wave-uniform bit word; tiles with all keys visible run as plain tiles, tiles with none
     // are skipped, only the boundary tiles start their hidden scores at -inf. Key-padded batches cost what unpadded ones do.
     constexpr bool KP = mode_has_keypad(MODE);
-    constexpr bool PAIRABLE = (MODE == MODE_CAUSAL || (FASN_VEC_PAIR && mode_is_vector(MODE) && !mode_has_keypad(MODE))) && !SPLIT && VH == 1 && (!DROP || (FASN_DROP_PAIR && MODE == MODE_CAUSAL));   // (round 6: also the vector mask / bias modes under the causal flag)
+    constexpr bool PAIRABLE = (MODE == MODE_CAUSAL || (mode_is_vector(MODE) && !mode_has_keypad(MODE))) && !SPLIT && VH == 1 && (!DROP || MODE == MODE_CAUSAL);   // (round 6: also the vector mask / bias modes under the causal flag)
     constexpr bool KPAIR = KP && VBIAS && !SPLIT && VH == 1 && !DROP;   // length-paired batch elements (see below)
     int bh2 = -1;   // KPAIR: the (b,h) of the second pass
     int kp_lead = 0;   // KPAIR: tile steps by which this workgroup starts its second pass before the group's last one (kpair_plan)
@@ -342,8 +314,8 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
         block_to_work(wgid, p.B * p.H, p.nqblk, bh, qi);
         if (fwd_xq_kernel(D, MODE, SPLIT, VH, DROP) && p.xq != nullptr && !draw_item(p.nqblk)) return;
     }
-    // Paired causal launch: the workgroup dispatcher hands workgroups out IN ORDER and waits for the CU whose turn it is (tools/
-    // fasn_harness timeline: with 80..128-tile workgroups next to each other a CU idles until the longest of its round is done), so
+    // Paired causal launch: the workgroup dispatcher hands workgroups out IN ORDER and waits for the CU whose turn it is (per-workgroup
+    // time stamps, LABNOTES.md: with 80..128-tile workgroups next to each other a CU idles until the longest of its round is done), so
     // unequal causal blocks leave 7 % of the workgroup slots empty even when sorted by weight. Block r and block nqblk-1-r together
     // always walk nqblk + 1 tiles: every workgroup of a paired launch costs the same. Used when the launch is many rounds long
     // (equal workgroups quantise the last round).
@@ -459,7 +431,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     // the row size (the dynamic LDS starts at 0 and every tile is a multiple of ROWB): ONE live address per operand and one v_xor
     // per distinct (s | d) instead of a precomputed offset register per step plus two VALU per read to add the buffer offset
     // (bias + key-padding kernel at D = 128: 228 -> 192 VGPRs, 63 VALU fewer per tile, C4 forward 4.26 -> 4.13 ms).
-    constexpr bool XADDR = RING == 2 && !UNR3 && D >= 128 && FASN_XADDR;
+    constexpr bool XADDR = RING == 2 && !UNR3 && D >= 128;
     const uint32_t xk0 = lds_addr(ldsK) + l31 * ROWB + ((hi ^ swz_f<D>(l31)) << 4);
     const uint32_t xv0 = lds_addr(ldsV) + (4 * hi + ((lane & 15) >> 2)) * ROWB +
                          (((((lane >> 4) & 1) * 2 + ((lane & 3) >> 1)) ^ swz_f<D>(4 * hi + ((lane & 15) >> 2))) << 4) + (lane & 1) * 8;
@@ -625,7 +597,6 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     // PRIO 3 = raised priority while a wave issues its QK^T MFMAs
     if (PRIO == 2 && NW == 4 && ((blockIdx.x >> 8) & 1)) __builtin_amdgcn_s_setprio(1);
 
-    FASN_STAMP(1);
     // rows of this wave: [qw0, qw0 + QB*32)
     const int wave_first_vis = qw0 + coff;                 // last visible key of the wave's first row
     const int wave_last_vis = qw0 + QB * 32 - 1 + coff;    // last visible key of the wave's last row
@@ -680,7 +651,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
             // PRIO 4 (round 5, launches of ONE round): the wave's priority falls with its progress through the key walk, so the two workgroups
             // that share a CU stay within a quarter of the walk of each other. With the arbiter's oldest-first rule alone the first-dispatched
             // workgroup of a CU runs ahead and finishes at ~70 % of the span; its partner then runs the last 30 % alone, at half the CU's
-            // throughput (tools/fasn_harness timeline, config 2). Launches of several rounds WANT that stagger (a fresh workgroup's prologue
+            // throughput (per-workgroup time stamps, config 2). Launches of several rounds WANT that stagger (a fresh workgroup's prologue
             // overlaps the older one's loop) and keep PRIO 0.
             const int done4 = (t - t_begin) * 4, span = ntiles - t_begin;
             if (done4 < span) __builtin_amdgcn_s_setprio(3);
@@ -847,7 +818,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
             // keep the -m tuple visibly alive past the QK^T MFMAs: the compiler then uses it as an UNTIED C operand for every key
             // block's first MFMA instead of copying it into the second block's accumulator (16 v_mov_b64 per 64-row tile)
 #if defined(__HIP_DEVICE_COMPILE__)   // (the host pass cannot take a 16-register tuple as an asm operand)
-            if (SEED && !VEC && FASN_SEED_KEEPALIVE) {
+            if (SEED && !VEC) {
 #pragma unroll
                 for (int qb = QLO; qb < QHI; ++qb) asm volatile("" ::"v"(mseed[qb]));
             }
@@ -1106,7 +1077,6 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     }
     // direct-to-LDS requests issued for tiles past the end must land before this workgroup's LDS can be handed to another one
     if (RING == 2 || VEC) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    FASN_STAMP(2);
 
     if (SPLIT) {   // ---- partial result of this key range: un-normalised accumulator + (m, l) per row
         float* po = p.part_o + ((int64_t)bh * p.nsplit + split) * p.Sq * D;
@@ -1159,14 +1129,6 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
             }
         }
     }
-#ifdef FASN_DEV_VARIANTS
-    if (p.timeline != nullptr && threadIdx.x == 0) {
-        p.timeline[(size_t)blockIdx.x * 8 + 3] = __builtin_amdgcn_s_memrealtime();
-        p.timeline[(size_t)blockIdx.x * 8 + 4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_ID
-        p.timeline[(size_t)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // XCC_ID
-        p.timeline[(size_t)blockIdx.x * 8 + 6] = (pass ? p.timeline[(size_t)blockIdx.x * 8 + 6] : 0ull) + (unsigned long long)ntiles;
-    }
-#endif
     }   // pass
 }
 

@@ -105,10 +105,10 @@ typedef struct fasn_fwd_args {
  * Plan: a dQ kernel and a dK/dV kernel that each recompute S and dP (7 GEMMs for the 5 of the algorithm, deterministic, no
  * workspace). The single 5-GEMM kernel of the reference (flash_attn_triton.py:199-226; dQ by load-add-store, here fp32 atomics
  * into a caller-provided accumulator) was built in round 3 and measured slower on MI355X in every form:
- * since round 4 only the developer library carries it. libfasn.so ignores FASN_BWD_ONE_PASS, fasn_bwd_workspace_bytes() returns 0
+ * it is no longer part of the sources. The library ignores FASN_BWD_ONE_PASS, fasn_bwd_workspace_bytes() returns 0
  * and `workspace` may be NULL; the fields stay in the struct so that the ABI version does not change.
  */
-#define FASN_BWD_ONE_PASS 1 /* fasn_bwd_args.flags: reserved (one-pass backward: developer library only); ignored by libfasn.so */
+#define FASN_BWD_ONE_PASS 1 /* fasn_bwd_args.flags: reserved (the one-pass backward, no longer built); ignored by libfasn.so */
 typedef struct fasn_bwd_args {
     fasn_fwd_args fwd; /* same views as forward; o and lse are inputs here */
     fasn_view4 dout;   /* [B,H,Sq,Dv] */

@@ -74,7 +74,7 @@ def test_bench_py_launches_its_own_two_replicas():
 
 
 def test_bench_py_counter_pass_mode_runs_exactly_k_steps():
-    """--min-timed-ms 0 (the counter passes of tools/prof_round4.sh: hardware counters serialise the launches) switches the 50 ms rule off"""
+    """--min-timed-ms 0 (the counter passes of tools/prof_workloads.sh: hardware counters serialise the launches) switches the 50 ms rule off"""
     r, lines = _bench_line([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--stub-step-ms", "1",
                             "--min-timed-ms", "0"], env={k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")})
     assert r.returncode == 0, r.stderr

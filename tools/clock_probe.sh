@@ -1,7 +1,7 @@
 #!/bin/bash
 # samples sclk / socket power (rocm-smi) while a harness bench line loops: tools/clock_probe.sh <harness bench args...>
 # (waits until the socket draws more than 500 W - the harness builds its inputs on the host first - then takes six samples)
-R=${GRAFT_REPO_ROOT:-/root/repo}; export LD_LIBRARY_PATH=$R/tools:$LD_LIBRARY_PATH
+R=$(cd "$(dirname "$0")/.." && pwd)
 $R/tools/fasn_harness bench "$@" > /tmp/probe_bench.log 2>&1 &
 BP=$!
 smp() { /opt/rocm/bin/rocm-smi -d 0 --showclocks --showpower 2>/dev/null | grep -E "sclk|Package Power" | sed -E 's/.*sclk clock level: [^(]*\(([0-9]+)Mhz\).*/sclk \1 MHz/; s/.*Power \(W\): ([0-9.]+)/\1 W/' | tr '\n' ' '; echo; }

@@ -1,5 +1,5 @@
 #!/bin/bash
-# tools/collect_profiles.sh TAG PREFIX: copy what a tools/prof_round6.sh call left under gpurun_out/TAG into profiles/ under the names profiles/INDEX.md uses
+# tools/collect_profiles.sh TAG PREFIX: copy what a tools/prof_workloads.sh call left in its output directory for TAG into profiles/ under the names profiles/INDEX.md uses
 # (PREFIX_<workload>_<pass>_rocprofv3_summary.txt, PREFIX_bench_all_workloads.jsonl, PREFIX_bench_default.json, PREFIX_clocks_and_power_under_load.log, pmc_latest.json)
 R=/root/repo; T=$1; P=$2; O=$R/gpurun_out/$T
 for d in $O/*_fwd $O/*_bwd; do

@@ -3,7 +3,8 @@
 // Test infrastructure only; not part of the product path.
 //   fasn_harness probe                      ds_read_b64_tr_b16 / MFMA layout probes
 //   fasn_harness test                       correctness battery (fwd + bwd)
-//   fasn_harness bench B H Sq Sk D dtype causal [variant] [iters] [bwd]
+//   fasn_harness bench B H Sq Sk D dtype causal [iters] [bwd] [n] [mask_kind] [bias_kind]
+// Everything goes through the public C ABI of include/fasn.h and links libfasn.so.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -12,16 +13,8 @@
 #include <string.h>
 #include <algorithm>
 #include <string>
-#include <map>
 #include <vector>
 #include "fasn.h"
-
-extern "C" int fasn_fwd_variant(const fasn_fwd_args* args, fasn_stream_t stream, int variant);
-extern "C" void fasn_dev_set_xq(int* counters, int extra);   // experiment: dynamic deal of the forward's items across XCDs, `extra` surplus workgroups per XCD (env FASN_XQ)
-extern "C" void fasn_dev_set_kprot(int v);       // length pairs: rotated key walk of the second element, 1 shipped / 0 off (env FASN_KPROT)
-extern "C" void fasn_dev_set_pair_mode(int v);   // causal block pairing: -1 shipped rule, 0 off, 1 on (env FASN_PAIR)
-extern "C" void fasn_dev_set_timeline(unsigned long long* buf);   // per-workgroup time stamps of the forward kernels (developer library)
-extern "C" void fasn_dev_set_bwd_variant(int v);   // 1 = one-wave dK/dV kernel where the two-wave kernel is the default
 
 #define HIP_CHECK(x)                                                                         \
     do {                                                                                     \
@@ -255,7 +248,6 @@ static fasn_view4 view(void* p, int H, int S, int D) {
     v.stride[3] = 1;
     return v;
 }
-static int g_one_pass = 0;   // harness switch: request the one-pass backward (`test ... onepass`, bench bwd_variant bit 3)
 static void fill_args(const Problem& P, const Host& h, Dev& d, fasn_bwd_args& a) {
     memset(&a, 0, sizeof(a));
     fasn_fwd_args& f = a.fwd;
@@ -283,8 +275,7 @@ static void fill_args(const Problem& P, const Host& h, Dev& d, fasn_bwd_args& a)
     a.dk = view(d.dk, P.H, P.Sk, P.D);
     a.dv = view(d.dv, P.H, P.Sk, P.D);
     a.delta = d.delta;
-    // one-pass backward (opt-in; g_one_pass): the fp32 dQ accumulator is the caller's (poisoned here: the library must clear it itself)
-    a.flags = g_one_pass ? FASN_BWD_ONE_PASS : 0;
+    a.flags = 0;
     const size_t wb = fasn_bwd_workspace_bytes(&a);
     if (wb && d.ws == nullptr) {
         HIP_CHECK(hipMalloc(&d.ws, wb));
@@ -306,14 +297,14 @@ static double cmp16(const std::vector<uint16_t>& got, size_t off, const std::vec
     return e;
 }
 
-static bool run_case(const char* name, Problem P, bool bwd, int variant, uint64_t seed = 1) {
+static bool run_case(const char* name, Problem P, bool bwd, uint64_t seed = 1) {
     Host h;
     make_inputs(P, h, seed);
     Dev d;
     dev_alloc(P, h, d);
     fasn_bwd_args a;
     fill_args(P, h, d, a);
-    int rc = fasn_fwd_variant(&a.fwd, nullptr, variant);
+    int rc = fasn_fwd(&a.fwd, nullptr);
     if (rc) {
         printf("[FAIL] %-34s fwd rc=%d (%s)\n", name, rc, fasn_strerror(rc));
         dev_free(d);
@@ -445,7 +436,7 @@ static Problem mk(int B, int H, int Sq, int Sk, int D, int dtype, int causal, fl
     return P;
 }
 
-static int do_test(int variant, bool quick) {
+static int do_test(bool quick) {
     int fails = 0;
     const int BF = FASN_DTYPE_BF16, HF = FASN_DTYPE_F16;
     struct C { const char* name; Problem P; bool bwd; };
@@ -496,13 +487,13 @@ static int do_test(int variant, bool quick) {
         cases.push_back({"d64 bf16 (8,16,4096) n1", mk(8, 16, 4096, 4096, 64, BF, 0, 1.f), false});
         cases.push_back({"d128 bf16 (1,4,2048) n.5", mk(1, 4, 2048, 2048, 128, BF, 0, 0.5f), true});
     }
-    for (auto& c : cases) fails += !run_case(c.name, c.P, c.bwd, variant);
+    for (auto& c : cases) fails += !run_case(c.name, c.P, c.bwd);
     // spike test: one query/key pair with a huge score late in the sequence forces a rescale
     {
         Problem P = mk(1, 1, 256, 512, 64, BF, 0, 1.f);
         P.std = 0.5f;
         // handled through seed variation only (random data); explicit spike below
-        fails += !run_case("d64 bf16 seed7", P, true, variant, 7);
+        fails += !run_case("d64 bf16 seed7", P, true, 7);
     }
     printf("%s: %d failing case(s)\n", fails ? "TESTS FAILED" : "ALL TESTS PASSED", fails);
     return fails ? 1 : 0;
@@ -510,20 +501,15 @@ static int do_test(int variant, bool quick) {
 
 static int do_bench(int argc, char** argv) {
     if (argc < 9) {
-        fprintf(stderr, "bench B H Sq Sk D dtype(0=f16,1=bf16) causal [variant] [iters] [bwd] [n] [mask_kind] [bias_kind] [bwd_variant]\n");
+        fprintf(stderr, "bench B H Sq Sk D dtype(0=f16,1=bf16) causal [iters] [bwd] [n] [mask_kind] [bias_kind]\n");
         return 2;
     }
     Problem P = mk(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoi(argv[6]), atoi(argv[7]), atoi(argv[8]), 1.f);
-    const int variant = argc > 9 ? atoi(argv[9]) : 0;
-    const int iters = argc > 10 ? atoi(argv[10]) : 20;
-    const bool bwd = argc > 11 ? atoi(argv[11]) != 0 : false;
-    if (argc > 12) P.n = (float)atof(argv[12]);
-    if (argc > 13) P.mask_kind = atoi(argv[13]);
-    if (argc > 14) P.bias_kind = atoi(argv[14]);
-    if (argc > 15) {   // bit 3 (8): request the one-pass backward
-        fasn_dev_set_bwd_variant(atoi(argv[15]));
-        g_one_pass = (atoi(argv[15]) >> 3) & 1;
-    }
+    const int iters = argc > 9 ? atoi(argv[9]) : 20;
+    const bool bwd = argc > 10 ? atoi(argv[10]) != 0 : false;
+    if (argc > 11) P.n = (float)atof(argv[11]);
+    if (argc > 12) P.mask_kind = atoi(argv[12]);
+    if (argc > 13) P.bias_kind = atoi(argv[13]);
     Host h;
     make_inputs(P, h, 3);
     Dev d;
@@ -534,12 +520,12 @@ static int do_bench(int argc, char** argv) {
     HIP_CHECK(hipEventCreate(&e0));
     HIP_CHECK(hipEventCreate(&e1));
     for (int i = 0; i < 5; ++i) {
-        int rc = fasn_fwd_variant(&a.fwd, nullptr, variant);
+        int rc = fasn_fwd(&a.fwd, nullptr);
         if (rc) { printf("fwd rc=%d\n", rc); return 1; }
     }
     HIP_CHECK(hipDeviceSynchronize());
     HIP_CHECK(hipEventRecord(e0, 0));
-    for (int i = 0; i < iters; ++i) fasn_fwd_variant(&a.fwd, nullptr, variant);
+    for (int i = 0; i < iters; ++i) fasn_fwd(&a.fwd, nullptr);
     HIP_CHECK(hipEventRecord(e1, 0));
     HIP_CHECK(hipEventSynchronize(e1));
     float ms = 0;
@@ -547,8 +533,8 @@ static int do_bench(int argc, char** argv) {
     ms /= iters;
     double flops = 4.0 * P.B * P.H * (double)P.Sq * P.Sk * P.D;
     if (P.causal) flops *= 0.5;
-    printf("fwd B%d H%d Sq%d Sk%d D%d %s causal%d variant%d: %.4f ms  %.1f TFLOP/s (%.1f%% of 2500)\n", P.B, P.H, P.Sq, P.Sk, P.D,
-           P.dtype ? "bf16" : "f16", P.causal, variant, ms, flops / ms * 1e-9, flops / ms * 1e-9 / 25.0);
+    printf("fwd B%d H%d Sq%d Sk%d D%d %s causal%d: %.4f ms  %.1f TFLOP/s (%.1f%% of 2500)\n", P.B, P.H, P.Sq, P.Sk, P.D,
+           P.dtype ? "bf16" : "f16", P.causal, ms, flops / ms * 1e-9, flops / ms * 1e-9 / 25.0);
     if (bwd) {
         for (int i = 0; i < 3; ++i) fasn_bwd(&a, nullptr);
         HIP_CHECK(hipDeviceSynchronize());
@@ -565,105 +551,14 @@ static int do_bench(int argc, char** argv) {
     return 0;
 }
 
-// timeline B H Sq Sk D dtype causal [variant]: one forward launch with per-workgroup time stamps (100 MHz clock): where a workgroup's
-// life goes (prologue / tile loop / epilogue), how well the CU slots stay covered, how long the ramp and the tail are
-static int do_timeline(int argc, char** argv) {
-    if (argc < 9) return 2;
-    Problem P = mk(atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), atoi(argv[6]), atoi(argv[7]), atoi(argv[8]), 1.f);
-    const int variant = argc > 9 ? atoi(argv[9]) : 0;
-    if (argc > 10) P.n = (float)atof(argv[10]);
-    if (argc > 11) P.mask_kind = atoi(argv[11]);
-    if (argc > 12) P.bias_kind = atoi(argv[12]);
-    Host h;
-    make_inputs(P, h, 3);
-    Dev d;
-    dev_alloc(P, h, d);
-    fasn_bwd_args a;
-    fill_args(P, h, d, a);
-    const size_t maxwg = (size_t)P.B * P.H * ((P.Sq + 31) / 32) * 2;
-    unsigned long long* tl = nullptr;
-    HIP_CHECK(hipMalloc(&tl, maxwg * 64));
-    for (int i = 0; i < 5; ++i) fasn_fwd_variant(&a.fwd, nullptr, variant);
-    HIP_CHECK(hipDeviceSynchronize());
-    HIP_CHECK(hipMemset(tl, 0, maxwg * 64));
-    fasn_dev_set_timeline(tl);
-    fasn_fwd_variant(&a.fwd, nullptr, variant);
-    fasn_fwd_variant(&a.fwd, nullptr, variant);   // the second of two back-to-back launches is the one kept
-    HIP_CHECK(hipDeviceSynchronize());
-    fasn_dev_set_timeline(nullptr);
-    std::vector<unsigned long long> t(maxwg * 8);
-    HIP_CHECK(hipMemcpy(t.data(), tl, maxwg * 64, hipMemcpyDeviceToHost));
-    size_t n = 0;
-    while (n < maxwg && t[n * 8 + 3] != 0) ++n;
-    if (const char* dump = getenv("FASN_TIMELINE_DUMP")) {   // raw stamps for offline analysis (tools/timeline_gaps.py)
-        FILE* f = fopen(dump, "wb");
-        if (f) { fwrite(t.data(), 64, n, f); fclose(f); }
-    }
-    if (n == 0) { printf("no stamps\n"); return 1; }
-    unsigned long long tmin = ~0ull, tmax = 0;
-    for (size_t i = 0; i < n; ++i) { tmin = std::min(tmin, t[i * 8]); tmax = std::max(tmax, t[i * 8 + 3]); }
-    const double tick = 0.01;   // us
-    std::vector<double> pro(n), epi(n), per(n), life(n);
-    double sum_life = 0, sum_pro = 0, sum_epi = 0, sum_loop = 0, sum_tiles = 0;
-    std::map<unsigned, int> cus;
-    for (size_t i = 0; i < n; ++i) {
-        const unsigned long long* w = &t[i * 8];
-        pro[i] = (w[1] - w[0]) * tick; epi[i] = (w[3] - w[2]) * tick; life[i] = (w[3] - w[0]) * tick;
-        per[i] = w[6] ? (w[2] - w[1]) * tick / (double)w[6] : 0;
-        sum_life += life[i]; sum_pro += pro[i]; sum_epi += epi[i]; sum_loop += (w[2] - w[1]) * tick; sum_tiles += (double)w[6];
-        const unsigned hw = (unsigned)w[4], xcc = (unsigned)w[5] & 15;
-        cus[(xcc << 16) | (hw & 0xff00) | ((hw >> 13) & 7) << 4 | ((hw >> 12) & 1)]++;   // (xcc, cu, se, sh)
-    }
-    auto pct = [&](std::vector<double> v, double q) { std::sort(v.begin(), v.end()); return v[(size_t)(q * (v.size() - 1))]; };
-    const double span = (tmax - tmin) * tick;
-    printf("timeline B%d H%d Sq%d Sk%d D%d causal%d variant%d: %zu workgroups on %zu CUs, span %.1f us\n", P.B, P.H, P.Sq, P.Sk, P.D, P.causal, variant, n, cus.size(), span);
-    printf("  per workgroup: prologue mean %.2f us (p10 %.2f p50 %.2f p90 %.2f)   epilogue mean %.2f (p50 %.2f p90 %.2f)   tile mean %.3f us (p10 %.3f p50 %.3f p90 %.3f)\n",
-           sum_pro / n, pct(pro, .1), pct(pro, .5), pct(pro, .9), sum_epi / n, pct(epi, .5), pct(epi, .9), sum_loop / sum_tiles, pct(per, .1), pct(per, .5), pct(per, .9));
-    printf("  sum of workgroup lifetimes %.0f us = %.2f resident workgroups per CU over the span; prologue %.1f%% loop %.1f%% epilogue %.1f%% of the lifetimes\n",
-           sum_life, sum_life / span / cus.size(), 100 * sum_pro / sum_life, 100 * sum_loop / sum_life, 100 * sum_epi / sum_life);
-    // concurrency profile: resident workgroups in 20 slices of the span
-    printf("  resident workgroups / CU per 5%% slice of the span:");
-    for (int sl = 0; sl < 20; ++sl) {
-        const double a0 = tmin * tick + span * sl / 20, a1 = a0 + span / 20;
-        double acc = 0;
-        for (size_t i = 0; i < n; ++i) {
-            const double s0 = std::max(a0, t[i * 8] * tick), s1 = std::min(a1, t[i * 8 + 3] * tick);
-            if (s1 > s0) acc += s1 - s0;
-        }
-        printf(" %.2f", acc / (span / 20) / cus.size());
-    }
-    printf("\n");
-    // start-to-start: first start of each workgroup relative to the kernel's first stamp
-    std::vector<double> st(n);
-    for (size_t i = 0; i < n; ++i) st[i] = (t[i * 8] - tmin) * tick;
-    std::sort(st.begin(), st.end());
-    const size_t first = std::min(n, cus.size() * 3);
-    printf("  workgroup starts: #%zu at %.1f us, #%zu at %.1f us; last start %.1f us; last end %.1f us\n", cus.size(), st[std::min(n, cus.size()) - 1], first, st[first - 1], st[n - 1], span);
-    fflush(stdout);
-    hipFree(tl);
-    dev_free(d);
-    return 0;
-}
-
 int main(int argc, char** argv) {
     if (argc < 2) {
-        fprintf(stderr, "usage: %s probe | test [variant] [quick] | bench ...\n", argv[0]);
+        fprintf(stderr, "usage: %s probe | test [quick] | bench ...\n", argv[0]);
         return 2;
     }
-    if (const char* pm = getenv("FASN_PAIR")) fasn_dev_set_pair_mode(atoi(pm));
-    if (const char* kr = getenv("FASN_KPROT")) fasn_dev_set_kprot(atoi(kr));
-    if (const char* xq = getenv("FASN_XQ")) {
-        int* ctr = nullptr;
-        if (hipMalloc(&ctr, 64) == hipSuccess) fasn_dev_set_xq(ctr, atoi(xq));
-    }
-    if (const char* bv = getenv("FASN_BWDV")) fasn_dev_set_bwd_variant(atoi(bv));   // backward kernel variant for `test` (bench takes it as an argument)
     std::string cmd = argv[1];
     if (cmd == "probe") return do_probe();
-    if (cmd == "test") {
-        g_one_pass = argc > 4 && atoi(argv[4]) != 0;   // test [variant] [quick] [one_pass]
-        return do_test(argc > 2 ? atoi(argv[2]) : 0, argc > 3 && atoi(argv[3]) != 0);
-    }
+    if (cmd == "test") return do_test(argc > 2 && atoi(argv[2]) != 0);
     if (cmd == "bench") return do_bench(argc, argv);
-    if (cmd == "timeline") return do_timeline(argc, argv);
     return 2;
 }

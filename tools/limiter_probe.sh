@@ -2,8 +2,8 @@
 # Which limiter holds the clock down? amd-smi's throttle accumulators (MI300+: time the SMU spent limiting for socket power (PPT), socket /
 # VR / HBM temperature, PROCHOT) read before and after a load, plus its violation-status monitor while the load runs:
 #   tools/limiter_probe.sh mfma              a launch of nothing but bf16 MFMAs (tools/ubench_mfma_clock: zero and random operands)
-#   tools/limiter_probe.sh <harness bench args...>   a loop of one harness bench line (e.g. 8 16 4096 4096 64 1 0 0 20000)
-R=${GRAFT_REPO_ROOT:-/root/repo}; export LD_LIBRARY_PATH=$R/tools:$LD_LIBRARY_PATH
+#   tools/limiter_probe.sh <harness bench args...>   a loop of one harness bench line (e.g. 8 16 4096 4096 64 1 0 20000)
+R=$(cd "$(dirname "$0")/.." && pwd)
 SMI=/opt/rocm/bin/amd-smi
 acc() { $SMI metric -g 0 -v 2>&1 | grep -vE "^ *$" | tr -s ' ' | tr '\n' ';'; echo; }   # (the per-XCD values follow their labels on lines of their own)
 echo "-- accumulators before:"; acc

@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (via gpurun): tools/prof_one.sh TAG WORKLOAD PASS   - one workload:pass of tools/prof_round3.sh again (kernel trace + FETCH / WRITE / SQ
+# usage (on the GPU box): tools/prof_one.sh TAG WORKLOAD PASS   - one workload:pass of tools/prof_workloads.sh again (kernel trace + FETCH / WRITE / SQ
 # passes) -> gpurun_out/TAG/frag_WORKLOAD_PASS.json, to be merged into pmc_latest.json of the same library
 R=${GRAFT_REPO_ROOT:-/root/repo}; T=$1; W=$2; P=$3; O=$R/gpurun_out/$T; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp

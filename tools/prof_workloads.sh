@@ -1,5 +1,5 @@
 #!/bin/bash
-# usage (via gpurun): tools/prof_round4.sh TAG PART     PART = a (m0 c3 c4 c2 passes) | b (c5 d256, side kernels incl. their PMC pass, bench lines, clocks) | all (a + b without the side kernels: every BASELINE pass, pmc_latest.json and the bench lines from ONE library build)
+# usage (on the GPU box): tools/prof_workloads.sh TAG PART     PART = a (m0 c3 c4 c2 passes) | b (c5 d256, side kernels incl. their PMC pass, bench lines, clocks) | all (a + b without the side kernels: every BASELINE pass, pmc_latest.json and the bench lines from ONE library build)
 # Profiles of the product library as shipped (bench.py -> libfasn.so), one directory per workload:pass under gpurun_out/TAG:
 # rocprofv3 --kernel-trace --stats, then separate --pmc passes (never together with tracing domains other than kernel dispatch):
 # FETCH_SIZE, WRITE_SIZE, two SQ sets (the first one carries GRBM_GUI_ACTIVE: cycles per XCD summed over 8 -> the effective clock of
@@ -32,6 +32,7 @@ fi
 if [ "$PART" = "a" ] || [ "$PART" = "all" ]; then
   for w in m0 c3 c4; do for p in fwd bwd; do run ${w}_$p "--workload $w --pass $p" 40 FETCH_SIZE WRITE_SIZE "$SQ1" "$SQ2"; done; done
   for p in fwd bwd; do run c2_$p "--workload c2 --pass $p" 40 FETCH_SIZE WRITE_SIZE "$SQ1"; done
+  for p in fwd bwd; do run t32_$p "--workload t32 --pass $p" 40 FETCH_SIZE WRITE_SIZE "$SQ1"; done   # (round 6: the shape of the reference's Triton test grid, head dim 32)
 fi
 if [ "$PART" = "b" ] || [ "$PART" = "all" ]; then
   for p in fwd bwd; do run c5_$p "--workload c5 --pass $p" 8 FETCH_SIZE WRITE_SIZE "$SQ1"; done
@@ -49,7 +50,7 @@ if [ "$PART" = "b" ] || [ "$PART" = "all" ]; then
   cd $R
   python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
   : > $O/bench_all.jsonl
-  for w in m0 c2 c3 c5 c4 d256; do for p in fwd bwd fwdbwd; do
+  for w in m0 c2 c3 c5 c4 d256 t32; do for p in fwd bwd fwdbwd; do
     python bench.py --full --workload $w --pass $p --steps 20 --warmup 5 --no-cpu-baseline --no-extra-passes >> $O/bench_all.jsonl 2>> $O/bench_all.err
   done; done
   python bench.py --full --workload c1 --steps 50 --warmup 5 >> $O/bench_all.jsonl 2>> $O/bench_all.err
@@ -60,7 +61,7 @@ for l in open("$O/bench_all.jsonl"):
     print("%-64s %8.3f ms/step kernels %8.3f ms  alg %7.1f TF (%.3f) exec %.3f traffic %s" % (d["config"]["workload"][:64], d["ms_per_step"], r["kernel_ms"], r["achieved"], r["frac"], r["frac_executed"], r["traffic"]))
 PY
   {
-  for a in "8 16 4096 4096 64 1 0 0 20000 0 1.0 0 0" "8 16 4096 4096 64 1 0 0 5000 1 1.0 0 0" "8 16 4096 4096 64 1 1 0 20000 0 1.0 0 0" "4 32 8192 8192 128 1 0 0 2000 0 0.5 4 1" "4 32 8192 8192 128 1 0 0 500 1 0.5 4 1"; do
+  for a in "8 16 4096 4096 64 1 0 20000 0 1.0 0 0" "8 16 4096 4096 64 1 0 5000 1 1.0 0 0" "8 16 4096 4096 64 1 1 20000 0 1.0 0 0" "4 32 8192 8192 128 1 0 2000 0 0.5 4 1" "4 32 8192 8192 128 1 0 500 1 0.5 4 1"; do
     echo "== harness bench $a"; bash $R/tools/clock_probe.sh $a
   done
   } > $O/clocks.log 2>&1

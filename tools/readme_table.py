@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The README's per-workload table from the bench lines of a tools/prof_round6.sh call:  tools/readme_table.py gpurun_out/TAG
+"""The README's per-workload table from the bench lines of a tools/prof_workloads.sh call:  tools/readme_table.py OUTDIR/TAG
 (forward | backward with the executed fraction in brackets | forward + backward | HBM bytes per launch from the PMC passes)."""
 import json
 import sys
