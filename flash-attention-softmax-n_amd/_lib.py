@@ -25,6 +25,7 @@ EXPORTS = (
     "fasn_fwd_n", "fasn_bwd_dn_workspace_bytes", "fasn_bwd_dn",
     "fasn_softmax_n_fwd", "fasn_softmax_n_bwd", "fasn_moments",
     "fasn_fwd_kvcache_workspace_bytes", "fasn_fwd_kvcache", "fasn_kvcache_append", "fasn_kvcache_plan",
+    "fasn_fwd_kvprefill_workspace_bytes", "fasn_fwd_kvprefill", "fasn_kvprefill_append", "fasn_kvprefill_plan",
 )
 
 
@@ -71,6 +72,11 @@ class KvCacheArgs(Structure):
         ("scale", c_float), ("softmax_n", c_float), ("causal", c_int32),
         ("n", c_void_p), ("n_stride_b", c_int64), ("n_stride_h", c_int64),
     ]
+
+
+class KvPrefillArgs(Structure):
+    """fasn_kvprefill_args (include/fasn.h): the K/V-cache arguments plus the per-batch query lengths in device memory"""
+    _fields_ = [("kv", KvCacheArgs), ("q_seqlens", c_void_p)]
 
 
 class FasnError(RuntimeError):
@@ -136,6 +142,14 @@ def load():
     lib.fasn_kvcache_append.argtypes = [POINTER(KvCacheArgs), POINTER(View4), POINTER(View4), c_void_p]
     lib.fasn_kvcache_plan.restype = c_int32
     lib.fasn_kvcache_plan.argtypes = [POINTER(KvCacheArgs), c_char_p, c_size_t]
+    lib.fasn_fwd_kvprefill_workspace_bytes.restype = c_size_t
+    lib.fasn_fwd_kvprefill_workspace_bytes.argtypes = [POINTER(KvPrefillArgs)]
+    lib.fasn_fwd_kvprefill.restype = c_int32
+    lib.fasn_fwd_kvprefill.argtypes = [POINTER(KvPrefillArgs), c_void_p, c_size_t, c_void_p]
+    lib.fasn_kvprefill_append.restype = c_int32
+    lib.fasn_kvprefill_append.argtypes = [POINTER(KvPrefillArgs), POINTER(View4), POINTER(View4), c_void_p]
+    lib.fasn_kvprefill_plan.restype = c_int32
+    lib.fasn_kvprefill_plan.argtypes = [POINTER(KvPrefillArgs), c_char_p, c_size_t]
     ver = lib.fasn_abi_version()
     if ver != FASN_ABI_VERSION:
         raise ImportError(f"libfasn ABI version {ver} != expected {FASN_ABI_VERSION}; rebuild csrc/")
@@ -181,6 +195,19 @@ def kvcache_plan(args):
     rc = load().fasn_kvcache_plan(args, buf, len(buf))
     if rc < 0:
         check(rc, "fasn_kvcache_plan")
+    out = []
+    for line in buf.value.decode().splitlines():
+        name, g, b, l, _cfg = line.rsplit(" ", 4)
+        out.append((name, int(g.split("=")[1]), int(b.split("=")[1]), int(l.split("=")[1])))
+    return out
+
+
+def kvprefill_plan(args):
+    """The kernels fasn_fwd_kvprefill would launch for `args` (a KvPrefillArgs), as launch_plan returns them. Nothing is launched."""
+    buf = ctypes.create_string_buffer(4096)
+    rc = load().fasn_kvprefill_plan(args, buf, len(buf))
+    if rc < 0:
+        check(rc, "fasn_kvprefill_plan")
     out = []
     for line in buf.value.decode().splitlines():
         name, g, b, l, _cfg = line.rsplit(" ", 4)

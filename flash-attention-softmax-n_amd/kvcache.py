@@ -1,9 +1,11 @@
 """Attention over a K/V cache (inference): paged or dense cache, lengths in device memory, grouped-query heads as rows of one problem.
 
-Host side of fasn_fwd_kvcache / fasn_kvcache_append (include/fasn.h). Nothing about the lengths or the block table is read on the
-host - no `.item()`, no synchronisation, the launches depend on shapes and capacity only - so a call can be captured once in a
-torch.cuda.graph and replayed while `cache_seqlens`, `block_table`, the cache and `query` change in place. Forward only: the training
-and prefill entry point is flash_attention_n.
+Host side of fasn_fwd_kvcache / fasn_kvcache_append (decode: flash_attention_n_kvcache, up to 128 rows per K/V head) and of
+fasn_fwd_kvprefill / fasn_kvprefill_append (prefill: flash_attention_n_kvcache_prefill, any number of positions, optional per-batch
+query lengths on the device) in include/fasn.h. Nothing about the lengths or the block table is read on the host - no `.item()`, no
+synchronisation, the launches depend on shapes and capacity only - so a call can be captured once in a torch.cuda.graph and replayed
+while `cache_seqlens`, `query_seqlens`, `block_table`, the cache and `query` change in place. Prompt -> chunked prefill -> decode runs on
+the paged cache alone. Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
 from typing import Optional
@@ -12,7 +14,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import KvCacheArgs
+from ._lib import KvCacheArgs, KvPrefillArgs
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
@@ -30,42 +32,14 @@ def _check_cache(name: str, t: Tensor, paged: bool, D: int) -> None:
         raise ValueError(f"{name}: rows overlap (row stride {t.stride(1)} < head dim {D})")
 
 
-def flash_attention_n_kvcache(
-        query: Tensor,
-        k_cache: Tensor,
-        v_cache: Tensor,
-        cache_seqlens: Tensor,
-        block_table: Optional[Tensor] = None,
-        k_new: Optional[Tensor] = None,
-        v_new: Optional[Tensor] = None,
-        softmax_n_param=1,
-        scale: Optional[float] = None,
-        is_causal: bool = True,
-        return_lse: bool = False):
-    """softmax_n attention of a few new query positions against a K/V cache, on MI355X.
-
-    :param query: [B, H, Sq, D] fp16 / bf16 device tensor, D in {64, 128}; Sq = 1 is decode, a few positions speculative / chunked decode.
-    :param k_cache, v_cache: paged [num_pages, page_size, Hkv, D] with `block_table` (page_size a multiple of 64), or dense
-                  [B, capacity, Hkv, D] with block_table=None. Any strided view whose rows are 16-byte aligned with feature stride 1
-                  (e.g. sliced out of a fused K/V buffer); never copied. H % Hkv == 0 and (H // Hkv) * Sq <= 128: the query heads of a
-                  K/V head times the positions are the rows of one problem, so the cache is read once per K/V head.
-    :param cache_seqlens: int32 [B] ON THE DEVICE: valid keys per batch element before this call. Not modified (the caller advances it).
-    :param block_table: int32 [B, max_pages] on the device: page ids of each batch element, in order. Entries beyond the pages a batch
-                  element needs are never read; cache rows at or beyond its length may hold anything (NaN included).
-    :param k_new, v_new: optional [B, Hkv, Sq, D]: written to the cache positions cache_seqlens[b] .. + Sq - 1 first (positions at or
-                  beyond the capacity are dropped) and then attended to: batch element b sees len_b = cache_seqlens[b] + Sq keys.
-    :param softmax_n_param: n >= 0, or a floating tensor that broadcasts to [B, H] as in flash_attention_n (one n per batch element and
-                  query head: attention sinks, n_h = exp(s_h)); no gradient here.
-    :param scale: multiplies q.k^T; default 1/sqrt(D).
-    :param is_causal: bottom-right aligned per batch element: position i sees key j iff j <= i + len_b - Sq. False: every position sees
-                  all len_b keys.
-    :param return_lse: also return lse [B, H, Sq] fp32 = log(n + sum_j exp(x_ij)).
-    :return: [B, H, Sq, D] in query's dtype (and lse). Rows that see no key give exactly 0 and lse = log n (-inf for n = 0).
-    """
+def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal, return_lse,
+             max_rows=None, args=None):
+    """The argument checks both entry points share (they need no device and come first) and the filled fasn_kvcache_args.
+    Returns (args, out, lse, k_new, v_new, keep): `keep` holds the tensors whose addresses the arguments carry."""
     if query.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("query must be [B, H, Sq, D] and the caches [num_pages, page_size, Hkv, D] (paged) or [B, capacity, Hkv, D] (dense)")
     if query.dtype not in _KV_DTYPES:
-        raise ValueError(f"flash_attention_n_kvcache: dtype {query.dtype} is not supported (fp16 and bf16 caches only)")
+        raise ValueError(f"{fn}: dtype {query.dtype} is not supported (fp16 and bf16 caches only)")
     B, H, Sq, D = query.shape
     dev = query.device
     tensors = {"k_cache": k_cache, "v_cache": v_cache, "cache_seqlens": cache_seqlens, "block_table": block_table, "k_new": k_new, "v_new": v_new}
@@ -77,10 +51,10 @@ def flash_attention_n_kvcache(
         raise TypeError("query, k_cache and v_cache must share one dtype")
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (query, k_cache, v_cache, k_new, v_new)) or (
             torch.is_grad_enabled() and isinstance(softmax_n_param, Tensor) and softmax_n_param.requires_grad):
-        raise RuntimeError("flash_attention_n_kvcache is forward only (inference): an input requires grad. Call it under torch.no_grad(), "
+        raise RuntimeError(f"{fn} is forward only (inference): an input requires grad. Call it under torch.no_grad(), "
                            "or use flash_attention_n, which differentiates q, k, v and a tensor n")
     if D not in _KV_HEAD_DIMS:
-        raise ValueError(f"flash_attention_n_kvcache: head dim {D} is not supported (supported: {_KV_HEAD_DIMS}); a cache is never "
+        raise ValueError(f"{fn}: head dim {D} is not supported (supported: {_KV_HEAD_DIMS}); a cache is never "
                          "zero-padded on the host")
     if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
         raise ValueError(f"k_cache and v_cache must have one shape [*, *, Hkv, {D}]; got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
@@ -88,9 +62,9 @@ def flash_attention_n_kvcache(
     if Hkv < 1 or H % Hkv != 0:
         raise ValueError(f"the cache has {Hkv} K/V heads: must divide the {H} query heads (grouped-query attention)")
     G = H // Hkv
-    if G * Sq > _MAX_ROWS:
-        raise ValueError(f"(query heads per K/V head) x (query positions) = {G} x {Sq} = {G * Sq} rows exceed the {_MAX_ROWS} of one pass; "
-                         "split the query positions over several calls")
+    if max_rows is not None and G * Sq > max_rows:
+        raise ValueError(f"(query heads per K/V head) x (query positions) = {G} x {Sq} = {G * Sq} rows exceed the {max_rows} of one pass; "
+                         "split the query positions over several calls, or use flash_attention_n_kvcache_prefill")
     if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B or not cache_seqlens.is_contiguous():
         raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
     paged = block_table is not None
@@ -129,10 +103,9 @@ def flash_attention_n_kvcache(
         raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
                            "(there is deliberately no CPU fallback)")
 
-    lib = _lib.load()
     out = torch.empty((B, H, Sq, D), dtype=query.dtype, device=dev)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
-    a = KvCacheArgs()
+    a = args if args is not None else KvCacheArgs()
     a.q, a.o = _view4(query), _view4(out)
     a.lse = None if lse is None else lse.data_ptr()
     a.k_cache, a.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
@@ -156,6 +129,45 @@ def flash_attention_n_kvcache(
         a.n_stride_b, a.n_stride_h = _n_strides(nt)
     else:
         a.n, a.n_stride_b, a.n_stride_h = None, 0, 0
+    return a, out, lse, k_new, v_new, (query, nt)
+
+
+def flash_attention_n_kvcache(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """softmax_n attention of a few new query positions against a K/V cache, on MI355X.
+
+    :param query: [B, H, Sq, D] fp16 / bf16 device tensor, D in {64, 128}; Sq = 1 is decode, a few positions speculative / chunked decode.
+    :param k_cache, v_cache: paged [num_pages, page_size, Hkv, D] with `block_table` (page_size a multiple of 64), or dense
+                  [B, capacity, Hkv, D] with block_table=None. Any strided view whose rows are 16-byte aligned with feature stride 1
+                  (e.g. sliced out of a fused K/V buffer); never copied. H % Hkv == 0 and (H // Hkv) * Sq <= 128: the query heads of a
+                  K/V head times the positions are the rows of one problem, so the cache is read once per K/V head.
+    :param cache_seqlens: int32 [B] ON THE DEVICE: valid keys per batch element before this call. Not modified (the caller advances it).
+    :param block_table: int32 [B, max_pages] on the device: page ids of each batch element, in order. Entries beyond the pages a batch
+                  element needs are never read; cache rows at or beyond its length may hold anything (NaN included).
+    :param k_new, v_new: optional [B, Hkv, Sq, D]: written to the cache positions cache_seqlens[b] .. + Sq - 1 first (positions at or
+                  beyond the capacity are dropped) and then attended to: batch element b sees len_b = cache_seqlens[b] + Sq keys.
+    :param softmax_n_param: n >= 0, or a floating tensor that broadcasts to [B, H] as in flash_attention_n (one n per batch element and
+                  query head: attention sinks, n_h = exp(s_h)); no gradient here.
+    :param scale: multiplies q.k^T; default 1/sqrt(D).
+    :param is_causal: bottom-right aligned per batch element: position i sees key j iff j <= i + len_b - Sq. False: every position sees
+                  all len_b keys.
+    :param return_lse: also return lse [B, H, Sq] fp32 = log(n + sum_j exp(x_ij)).
+    :return: [B, H, Sq, D] in query's dtype (and lse). Rows that see no key give exactly 0 and lse = log n (-inf for n = 0).
+    """
+    a, out, lse, k_new, v_new, _keep = _prepare("flash_attention_n_kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                                                softmax_n_param, scale, is_causal, return_lse, max_rows=_MAX_ROWS)
+    lib = _lib.load()
+    dev = query.device
 
     def launch():
         stream = _stream_ptr(dev)
@@ -164,6 +176,72 @@ def flash_attention_n_kvcache(
         ws_bytes = lib.fasn_fwd_kvcache_workspace_bytes(a)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (torch's caching allocator: capturable, as _launch_fwd's)
         _lib.check(lib.fasn_fwd_kvcache(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache")
+
+    if _current_device() == dev.index:
+        launch()
+    else:
+        with torch.cuda.device(dev):
+            launch()
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_n_kvcache_prefill(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        query_seqlens: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """softmax_n attention of ANY number of new query positions against a K/V cache, on MI355X: prefill, chunked prefill, a prefix-cache hit.
+
+    The cache, `block_table`, `cache_seqlens`, `softmax_n_param`, `scale`, dtypes, head dims, alignment rules and refusals are those of
+    flash_attention_n_kvcache. What differs:
+
+    :param query: [B, H, Sq, D], any Sq >= 1 (no row limit: the G = H // Hkv query heads of a K/V head times 128 // G consecutive
+                  positions are the rows of one workgroup, so the cache is still read once per K/V head and row block; G <= 128).
+    :param k_new, v_new: optional [B, Hkv, Sq, D]: rows i < qlen_b are written to the cache positions cache_seqlens[b] + i first (positions
+                  at or beyond the capacity are dropped in the kernel) and then attended to. `cache_seqlens` is not modified.
+    :param query_seqlens: optional contiguous int32 [B] ON THE DEVICE: qlen_b = clamp(query_seqlens[b], 0, Sq); None means Sq. A ragged
+                  batch of prompts or chunks padded to Sq. Never read on the host.
+    :param is_causal: with len_b = clamp(cache_seqlens[b] + (qlen_b if k_new is given else 0), 0, capacity), position i < qlen_b sees key j
+                  iff j < len_b and (causal) j <= i + len_b - qlen_b: bottom-right aligned per batch element.
+    :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32). A position that sees no key gives exactly 0 and lse = log n (-inf
+             for n = 0); padding positions i >= qlen_b give exactly 0 and lse = -inf whatever n is.
+    """
+    fn = "flash_attention_n_kvcache_prefill"
+    pa = KvPrefillArgs()
+    if query_seqlens is not None:
+        B = query.shape[0] if query.dim() == 4 else -1
+        if (not isinstance(query_seqlens, Tensor) or query_seqlens.dtype != torch.int32 or query_seqlens.dim() != 1 or query_seqlens.shape[0] != B
+                or not query_seqlens.is_contiguous()):
+            got = f"{query_seqlens.dtype} {tuple(query_seqlens.shape)}" if isinstance(query_seqlens, Tensor) else type(query_seqlens).__name__
+            raise ValueError(f"query_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {got}")
+        if query_seqlens.device != query.device:
+            raise RuntimeError(f"query_seqlens is on {query_seqlens.device}, query on {query.device}: every operand must live on the query's "
+                               "device (the lengths are read by the kernels, never on the host)")
+    if query.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and query.shape[1] // k_cache.shape[2] > 128 and query.shape[1] % k_cache.shape[2] == 0:
+        raise ValueError(f"{fn}: {query.shape[1] // k_cache.shape[2]} query heads per K/V head are not supported (at most 128: the heads of a "
+                         "K/V head share one workgroup)")
+    _a, out, lse, k_new, v_new, _keep = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                                                 softmax_n_param, scale, is_causal, return_lse, args=pa.kv)
+    pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
+    lib = _lib.load()
+    dev = query.device
+
+    def launch():
+        stream = _stream_ptr(dev)
+        if k_new is not None:
+            _lib.check(lib.fasn_kvprefill_append(pa, _view4(k_new), _view4(v_new), stream), "fasn_kvprefill_append")
+        ws_bytes = lib.fasn_fwd_kvprefill_workspace_bytes(pa)
+        # (one split: no partials, no workspace; otherwise torch's caching allocator: capturable, as _launch_fwd's)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+        _lib.check(lib.fasn_fwd_kvprefill(pa, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill")
 
     if _current_device() == dev.index:
         launch()

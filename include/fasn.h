@@ -284,6 +284,36 @@ int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, 
 int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap);
 
 /*
+ * PREFILL over the same cache (additions within ABI 6): any number of query positions per batch element, Sq >= 1, with an optional
+ * per-batch QUERY LENGTH IN DEVICE MEMORY. `kv` has the meaning fasn_fwd_kvcache gives it, and every rule and error code of that call
+ * holds, except: there is no row limit (only kv_group > 128 is FASN_EUNSUPPORTED), and kv.seqlen_add is 0 (the cache as it is) or kv.Sq
+ * (the cache plus the rows fasn_kvprefill_append wrote), anything else FASN_EINVAL.
+ *
+ *   lengths   qlen_b = clamp(q_seqlens[b], 0, Sq), q_seqlens == NULL = Sq: a ragged batch of prompts or chunks padded to Sq.
+ *             len_b = clamp(seqlens[b] + (seqlen_add ? qlen_b : 0), 0, capacity).
+ *   causal    position i < qlen_b sees key j iff j < len_b and (causal) j <= i + len_b - qlen_b: bottom-right aligned per batch element.
+ *             A position that sees no key gives 0 and lse = log n (-inf for n = 0).
+ *   padding   positions i >= qlen_b give o = 0 and lse = -inf whatever n is; their q / k_new / v_new rows are never read.
+ *   rows      a workgroup owns the kv_group query heads of a K/V head times 128 / kv_group consecutive positions, so the cache is read
+ *             once per K/V head and row block. The grid - (batch element, K/V head, row block, split) - depends on shapes and capacity only.
+ *
+ * fasn_fwd_kvprefill_workspace_bytes is 0 when the plan has one split (the forward kernel then stores o / lse itself, one launch; a NULL
+ * workspace is accepted) and the size of the split partials otherwise (two launches; 16-byte aligned, FASN_EWORKSPACE when missing or too
+ * small). fasn_kvprefill_append writes rows i < qlen_b of k_new / v_new ([B, H / kv_group, Sq, D] views) to the cache positions
+ * seqlens[b] + i, drops positions at or beyond the capacity inside the kernel and does not modify `seqlens`. fasn_kvprefill_plan writes
+ * the launches of fasn_fwd_kvprefill as text, in the line format of fasn_launch_plan, without touching a device.
+ */
+typedef struct fasn_kvprefill_args {
+    fasn_kvcache_args kv;
+    const int32_t* q_seqlens;    /* DEVICE [B] or NULL */
+} fasn_kvprefill_args;
+
+size_t fasn_fwd_kvprefill_workspace_bytes(const fasn_kvprefill_args* args);
+int fasn_fwd_kvprefill(const fasn_kvprefill_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvprefill_append(const fasn_kvprefill_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvprefill_plan(const fasn_kvprefill_args* args, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).
