@@ -26,6 +26,7 @@ EXPORTS = (
     "fasn_softmax_n_fwd", "fasn_softmax_n_bwd", "fasn_moments",
     "fasn_fwd_kvcache_workspace_bytes", "fasn_fwd_kvcache", "fasn_kvcache_append", "fasn_kvcache_plan",
     "fasn_fwd_kvprefill_workspace_bytes", "fasn_fwd_kvprefill", "fasn_kvprefill_append", "fasn_kvprefill_plan",
+    "fasn_fwd_kvcache_alibi", "fasn_fwd_kvprefill_alibi", "fasn_kvcache_alibi_plan", "fasn_kvprefill_alibi_plan",
 )
 
 
@@ -77,6 +78,11 @@ class KvCacheArgs(Structure):
 class KvPrefillArgs(Structure):
     """fasn_kvprefill_args (include/fasn.h): the K/V-cache arguments plus the per-batch query lengths in device memory"""
     _fields_ = [("kv", KvCacheArgs), ("q_seqlens", c_void_p)]
+
+
+class AlibiSlopes(Structure):
+    """fasn_alibi_slopes (include/fasn.h): per-(batch, query head) fp32 ALiBi slopes in device memory, for the *_alibi cache calls"""
+    _fields_ = [("slopes", c_void_p), ("stride_b", c_int64), ("stride_h", c_int64)]
 
 
 class FasnError(RuntimeError):
@@ -150,6 +156,14 @@ def load():
     lib.fasn_kvprefill_append.argtypes = [POINTER(KvPrefillArgs), POINTER(View4), POINTER(View4), c_void_p]
     lib.fasn_kvprefill_plan.restype = c_int32
     lib.fasn_kvprefill_plan.argtypes = [POINTER(KvPrefillArgs), c_char_p, c_size_t]
+    lib.fasn_fwd_kvcache_alibi.restype = c_int32
+    lib.fasn_fwd_kvcache_alibi.argtypes = [POINTER(KvCacheArgs), POINTER(AlibiSlopes), c_void_p, c_size_t, c_void_p]
+    lib.fasn_fwd_kvprefill_alibi.restype = c_int32
+    lib.fasn_fwd_kvprefill_alibi.argtypes = [POINTER(KvPrefillArgs), POINTER(AlibiSlopes), c_void_p, c_size_t, c_void_p]
+    lib.fasn_kvcache_alibi_plan.restype = c_int32
+    lib.fasn_kvcache_alibi_plan.argtypes = [POINTER(KvCacheArgs), POINTER(AlibiSlopes), c_char_p, c_size_t]
+    lib.fasn_kvprefill_alibi_plan.restype = c_int32
+    lib.fasn_kvprefill_alibi_plan.argtypes = [POINTER(KvPrefillArgs), POINTER(AlibiSlopes), c_char_p, c_size_t]
     ver = lib.fasn_abi_version()
     if ver != FASN_ABI_VERSION:
         raise ImportError(f"libfasn ABI version {ver} != expected {FASN_ABI_VERSION}; rebuild csrc/")
@@ -189,12 +203,7 @@ def launch_plan_described(args, which):
     return out
 
 
-def kvcache_plan(args):
-    """The kernels fasn_fwd_kvcache would launch for `args` (a KvCacheArgs), as launch_plan returns them. Nothing is launched."""
-    buf = ctypes.create_string_buffer(4096)
-    rc = load().fasn_kvcache_plan(args, buf, len(buf))
-    if rc < 0:
-        check(rc, "fasn_kvcache_plan")
+def _plan_lines(buf):
     out = []
     for line in buf.value.decode().splitlines():
         name, g, b, l, _cfg = line.rsplit(" ", 4)
@@ -202,17 +211,30 @@ def kvcache_plan(args):
     return out
 
 
-def kvprefill_plan(args):
-    """The kernels fasn_fwd_kvprefill would launch for `args` (a KvPrefillArgs), as launch_plan returns them. Nothing is launched."""
+def kvcache_plan(args, alibi=None):
+    """The kernels fasn_fwd_kvcache would launch for `args` (a KvCacheArgs), as launch_plan returns them; with `alibi` (an AlibiSlopes)
+    those of fasn_fwd_kvcache_alibi. Nothing is launched."""
     buf = ctypes.create_string_buffer(4096)
-    rc = load().fasn_kvprefill_plan(args, buf, len(buf))
+    if alibi is None:
+        rc, what = load().fasn_kvcache_plan(args, buf, len(buf)), "fasn_kvcache_plan"
+    else:
+        rc, what = load().fasn_kvcache_alibi_plan(args, alibi, buf, len(buf)), "fasn_kvcache_alibi_plan"
     if rc < 0:
-        check(rc, "fasn_kvprefill_plan")
-    out = []
-    for line in buf.value.decode().splitlines():
-        name, g, b, l, _cfg = line.rsplit(" ", 4)
-        out.append((name, int(g.split("=")[1]), int(b.split("=")[1]), int(l.split("=")[1])))
-    return out
+        check(rc, what)
+    return _plan_lines(buf)
+
+
+def kvprefill_plan(args, alibi=None):
+    """The kernels fasn_fwd_kvprefill would launch for `args` (a KvPrefillArgs), as launch_plan returns them; with `alibi` (an AlibiSlopes)
+    those of fasn_fwd_kvprefill_alibi. Nothing is launched."""
+    buf = ctypes.create_string_buffer(4096)
+    if alibi is None:
+        rc, what = load().fasn_kvprefill_plan(args, buf, len(buf)), "fasn_kvprefill_plan"
+    else:
+        rc, what = load().fasn_kvprefill_alibi_plan(args, alibi, buf, len(buf)), "fasn_kvprefill_alibi_plan"
+    if rc < 0:
+        check(rc, what)
+    return _plan_lines(buf)
 
 
 def check(rc, what):

@@ -1,4 +1,4 @@
-// K/V-cache forward (include/fasn.h: fasn_fwd_kvcache, fasn_kvcache_append, fasn_kvcache_plan): argument checks, the launch plan -
+// K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi], fasn_kvcache_append, fasn_kvcache[_alibi]_plan): argument checks, the launch plan -
 // which depends on shapes and capacity only, never on the lengths in device memory - and the three launches of fasn_kvcache.h.
 #include <limits.h>
 #include <math.h>
@@ -89,12 +89,28 @@ int kv_build(const fasn_kvcache_args* a, KvParams& p) {
 }
 size_t kv_ws_bytes(const KvParams& p, int D) { return (size_t)p.B * p.Hkv * p.nsplit * p.R * (size_t)(D + 2) * sizeof(float); }
 
+// The ALiBi operand of the *_alibi entry points (checked after the base arguments, before any HIP call): the rules of `n`
+int kv_build_alibi(const fasn_kvcache_args* a, const fasn_alibi_slopes* s, KvAlibi& al) {
+    if (s == nullptr || s->slopes == nullptr) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(s->slopes) % 4) return FASN_EALIGN;
+    if (s->stride_b < 0 || s->stride_h < 0 || (a->B - 1) * s->stride_b + (a->H - 1) * s->stride_h >= (1ll << 31)) return FASN_EINVAL;
+    al = KvAlibi{s->slopes, (int)s->stride_b, (int)s->stride_h};
+    return FASN_OK;
+}
+
+// (al == nullptr: the kernel without a bias; otherwise its ALiBi sibling on the same grid, LDS and workspace)
 template <typename Tag, int D>
-int kv_launch_fwd(const KvParams& p, hipStream_t s) {
+int kv_launch_fwd(const KvParams& p, const KvAlibi* al, hipStream_t s) {
     constexpr int smem = kv_smem(D);
-    constexpr auto kern = &fasn_kvcache_fwd_kernel<Tag, D>;
-    ensure_smem<kern>(smem);
-    FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * p.nsplit)), dim3(256), smem, s, p);
+    if (al == nullptr) {
+        constexpr auto kern = &fasn_kvcache_fwd_kernel<Tag, D>;
+        ensure_smem<kern>(smem);
+        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * p.nsplit)), dim3(256), smem, s, p);
+    } else {
+        constexpr auto kern = &fasn_kvcache_fwd_alibi_kernel<Tag, D>;
+        ensure_smem<kern>(smem);
+        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * p.nsplit)), dim3(256), smem, s, p, *al);
+    }
     const int64_t nthr = (int64_t)p.B * p.Hkv * p.R * (D / 4);
     FASN_LAUNCH((fasn_kvcache_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
@@ -104,6 +120,34 @@ int kv_launch_append(const KvParams& p, hipStream_t s) {
     const int64_t nthr = (int64_t)p.B * p.Hkv * p.Sq * (D / 8);
     FASN_LAUNCH((fasn_kvcache_append_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
+}
+
+int kv_forward(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    KvParams p;
+    int rc = kv_build(args, p);
+    if (rc) return rc;
+    KvAlibi al{};
+    if (with_alibi && (rc = kv_build_alibi(args, alibi, al))) return rc;
+    if (workspace == nullptr || workspace_bytes < kv_ws_bytes(p, args->D)) return FASN_EWORKSPACE;
+    if (!kv_aligned16(workspace)) return FASN_EALIGN;
+    p.part_o = static_cast<float*>(workspace);
+    p.part_ml = p.part_o + (size_t)p.B * p.Hkv * p.nsplit * p.R * args->D;
+    hipStream_t s = (hipStream_t)stream;
+    const KvAlibi* const alp = with_alibi ? &al : nullptr;
+    if (args->dtype == FASN_DTYPE_BF16) return args->D == 64 ? kv_launch_fwd<bf16_tag, 64>(p, alp, s) : kv_launch_fwd<bf16_tag, 128>(p, alp, s);
+    return args->D == 64 ? kv_launch_fwd<f16_tag, 64>(p, alp, s) : kv_launch_fwd<f16_tag, 128>(p, alp, s);
+}
+
+int kv_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, char* buf, size_t cap) {
+    if (args == nullptr || buf == nullptr || cap == 0) return FASN_EINVAL;
+    LaunchLog log{buf, cap, 0};
+    buf[0] = 0;
+    LaunchLog* const outer = t_launch_log;
+    t_launch_log = &log;
+    const int rc = kv_forward(args, alibi, with_alibi, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
+    t_launch_log = outer;
+    if (rc) return rc;
+    return log.len > cap ? FASN_EINVAL : (int)log.len;
 }
 
 }  // namespace
@@ -120,16 +164,11 @@ size_t fasn_fwd_kvcache_workspace_bytes(const fasn_kvcache_args* args) {
 }
 
 int fasn_fwd_kvcache(const fasn_kvcache_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    KvParams p;
-    const int rc = kv_build(args, p);
-    if (rc) return rc;
-    if (workspace == nullptr || workspace_bytes < kv_ws_bytes(p, args->D)) return FASN_EWORKSPACE;
-    if (!kv_aligned16(workspace)) return FASN_EALIGN;
-    p.part_o = static_cast<float*>(workspace);
-    p.part_ml = p.part_o + (size_t)p.B * p.Hkv * p.nsplit * p.R * args->D;
-    hipStream_t s = (hipStream_t)stream;
-    if (args->dtype == FASN_DTYPE_BF16) return args->D == 64 ? kv_launch_fwd<bf16_tag, 64>(p, s) : kv_launch_fwd<bf16_tag, 128>(p, s);
-    return args->D == 64 ? kv_launch_fwd<f16_tag, 64>(p, s) : kv_launch_fwd<f16_tag, 128>(p, s);
+    return kv_forward(args, nullptr, false, workspace, workspace_bytes, stream);
+}
+
+int fasn_fwd_kvcache_alibi(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return kv_forward(args, alibi, true, workspace, workspace_bytes, stream);
 }
 
 int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
@@ -149,16 +188,10 @@ int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, 
     return args->D == 64 ? kv_launch_append<64>(p, s) : kv_launch_append<128>(p, s);
 }
 
-int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) {
-    if (args == nullptr || buf == nullptr || cap == 0) return FASN_EINVAL;
-    LaunchLog log{buf, cap, 0};
-    buf[0] = 0;
-    LaunchLog* const outer = t_launch_log;
-    t_launch_log = &log;
-    const int rc = fasn_fwd_kvcache(args, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
-    t_launch_log = outer;
-    if (rc) return rc;
-    return log.len > cap ? FASN_EINVAL : (int)log.len;
+int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) { return kv_plan(args, nullptr, false, buf, cap); }
+
+int fasn_kvcache_alibi_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap) {
+    return kv_plan(args, alibi, true, buf, cap);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// K/V-cache prefill (include/fasn.h: fasn_fwd_kvprefill, fasn_kvprefill_append, fasn_kvprefill_plan): argument checks, the launch plan -
+// K/V-cache prefill (include/fasn.h: fasn_fwd_kvprefill[_alibi], fasn_kvprefill_append, fasn_kvprefill[_alibi]_plan): argument checks, the launch plan -
 // which depends on shapes and capacity only, never on the lengths in device memory - and the launches of fasn_kvprefill.h.
 #include <limits.h>
 #include <math.h>
@@ -99,13 +99,29 @@ size_t kvp_ws_bytes(const KvPrefillParams& pp, int D) {
     return (size_t)pp.kv.B * pp.kv.Hkv * pp.nrb * pp.kv.nsplit * KVP_ROWS * (size_t)(D + 2) * sizeof(float);
 }
 
+// The ALiBi operand of the *_alibi entry points (checked after the base arguments, before any HIP call): the rules of `n`
+int kvp_build_alibi(const fasn_kvcache_args* a, const fasn_alibi_slopes* s, KvAlibi& al) {
+    if (s == nullptr || s->slopes == nullptr) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(s->slopes) % 4) return FASN_EALIGN;
+    if (s->stride_b < 0 || s->stride_h < 0 || (a->B - 1) * s->stride_b + (a->H - 1) * s->stride_h >= (1ll << 31)) return FASN_EINVAL;
+    al = KvAlibi{s->slopes, (int)s->stride_b, (int)s->stride_h};
+    return FASN_OK;
+}
+
+// (al == nullptr: the kernel without a bias; otherwise its ALiBi sibling on the same grid, LDS and workspace)
 template <typename Tag, int D>
-int kvp_launch_fwd(const KvPrefillParams& pp, hipStream_t s) {
+int kvp_launch_fwd(const KvPrefillParams& pp, const KvAlibi* al, hipStream_t s) {
     const KvParams& p = pp.kv;
     constexpr int smem = kv_smem(D);
-    constexpr auto kern = &fasn_kvprefill_fwd_kernel<Tag, D>;
-    ensure_smem<kern>(smem);
-    FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit)), dim3(256), smem, s, pp);
+    if (al == nullptr) {
+        constexpr auto kern = &fasn_kvprefill_fwd_kernel<Tag, D>;
+        ensure_smem<kern>(smem);
+        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit)), dim3(256), smem, s, pp);
+    } else {
+        constexpr auto kern = &fasn_kvprefill_fwd_alibi_kernel<Tag, D>;
+        ensure_smem<kern>(smem);
+        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit)), dim3(256), smem, s, pp, *al);
+    }
     if (p.nsplit > 1) {
         const int64_t nthr = (int64_t)p.B * p.Hkv * pp.nrb * KVP_ROWS * (D / 4);
         FASN_LAUNCH((fasn_kvprefill_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, pp);
@@ -118,6 +134,38 @@ int kvp_launch_append(const KvPrefillParams& pp, hipStream_t s) {
     if ((nthr + 255) / 256 > INT_MAX) return FASN_EINVAL;
     FASN_LAUNCH((fasn_kvprefill_append_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, pp);
     return launch_rc();
+}
+
+int kvp_forward(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    KvPrefillParams pp;
+    int rc = kvp_build(args, pp);
+    if (rc) return rc;
+    KvAlibi al{};
+    if (with_alibi && (rc = kvp_build_alibi(&args->kv, alibi, al))) return rc;
+    const int D = args->kv.D;
+    const size_t need = kvp_ws_bytes(pp, D);
+    if (need > 0) {   // (one split: nothing is written beside o / lse, a NULL workspace is fine)
+        if (workspace == nullptr || workspace_bytes < need) return FASN_EWORKSPACE;
+        if (!kvp_aligned16(workspace)) return FASN_EALIGN;
+        pp.kv.part_o = static_cast<float*>(workspace);
+        pp.kv.part_ml = pp.kv.part_o + (size_t)pp.kv.B * pp.kv.Hkv * pp.nrb * pp.kv.nsplit * KVP_ROWS * D;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const KvAlibi* const alp = with_alibi ? &al : nullptr;
+    if (args->kv.dtype == FASN_DTYPE_BF16) return D == 64 ? kvp_launch_fwd<bf16_tag, 64>(pp, alp, s) : kvp_launch_fwd<bf16_tag, 128>(pp, alp, s);
+    return D == 64 ? kvp_launch_fwd<f16_tag, 64>(pp, alp, s) : kvp_launch_fwd<f16_tag, 128>(pp, alp, s);
+}
+
+int kvp_plan(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, char* buf, size_t cap) {
+    if (args == nullptr || buf == nullptr || cap == 0) return FASN_EINVAL;
+    LaunchLog log{buf, cap, 0};
+    buf[0] = 0;
+    LaunchLog* const outer = t_launch_log;
+    t_launch_log = &log;
+    const int rc = kvp_forward(args, alibi, with_alibi, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
+    t_launch_log = outer;
+    if (rc) return rc;
+    return log.len > cap ? FASN_EINVAL : (int)log.len;
 }
 
 }  // namespace
@@ -134,20 +182,11 @@ size_t fasn_fwd_kvprefill_workspace_bytes(const fasn_kvprefill_args* args) {
 }
 
 int fasn_fwd_kvprefill(const fasn_kvprefill_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    KvPrefillParams pp;
-    const int rc = kvp_build(args, pp);
-    if (rc) return rc;
-    const int D = args->kv.D;
-    const size_t need = kvp_ws_bytes(pp, D);
-    if (need > 0) {   // (one split: nothing is written beside o / lse, a NULL workspace is fine)
-        if (workspace == nullptr || workspace_bytes < need) return FASN_EWORKSPACE;
-        if (!kvp_aligned16(workspace)) return FASN_EALIGN;
-        pp.kv.part_o = static_cast<float*>(workspace);
-        pp.kv.part_ml = pp.kv.part_o + (size_t)pp.kv.B * pp.kv.Hkv * pp.nrb * pp.kv.nsplit * KVP_ROWS * D;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (args->kv.dtype == FASN_DTYPE_BF16) return D == 64 ? kvp_launch_fwd<bf16_tag, 64>(pp, s) : kvp_launch_fwd<bf16_tag, 128>(pp, s);
-    return D == 64 ? kvp_launch_fwd<f16_tag, 64>(pp, s) : kvp_launch_fwd<f16_tag, 128>(pp, s);
+    return kvp_forward(args, nullptr, false, workspace, workspace_bytes, stream);
+}
+
+int fasn_fwd_kvprefill_alibi(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return kvp_forward(args, alibi, true, workspace, workspace_bytes, stream);
 }
 
 int fasn_kvprefill_append(const fasn_kvprefill_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
@@ -167,16 +206,10 @@ int fasn_kvprefill_append(const fasn_kvprefill_args* args, const fasn_view4* k_n
     return args->kv.D == 64 ? kvp_launch_append<64>(pp, s) : kvp_launch_append<128>(pp, s);
 }
 
-int fasn_kvprefill_plan(const fasn_kvprefill_args* args, char* buf, size_t cap) {
-    if (args == nullptr || buf == nullptr || cap == 0) return FASN_EINVAL;
-    LaunchLog log{buf, cap, 0};
-    buf[0] = 0;
-    LaunchLog* const outer = t_launch_log;
-    t_launch_log = &log;
-    const int rc = fasn_fwd_kvprefill(args, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
-    t_launch_log = outer;
-    if (rc) return rc;
-    return log.len > cap ? FASN_EINVAL : (int)log.len;
+int fasn_kvprefill_plan(const fasn_kvprefill_args* args, char* buf, size_t cap) { return kvp_plan(args, nullptr, false, buf, cap); }
+
+int fasn_kvprefill_alibi_plan(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap) {
+    return kvp_plan(args, alibi, true, buf, cap);
 }
 
 }  // extern "C"

@@ -5,7 +5,9 @@ fasn_fwd_kvprefill / fasn_kvprefill_append (prefill: flash_attention_n_kvcache_p
 query lengths on the device) in include/fasn.h. Nothing about the lengths or the block table is read on the host - no `.item()`, no
 synchronisation, the launches depend on shapes and capacity only - so a call can be captured once in a torch.cuda.graph and replayed
 while `cache_seqlens`, `query_seqlens`, `block_table`, the cache and `query` change in place. Prompt -> chunked prefill -> decode runs on
-the paged cache alone. Forward only: the training entry point is flash_attention_n.
+the paged cache alone. `alibi_slopes` on both calls adds -slope[b, h] * |p_i - j| to the logits inside the kernels (fasn_fwd_kvcache_alibi /
+fasn_fwd_kvprefill_alibi): p_i comes from the lengths in device memory, so no bias tensor exists and the graph stays one graph.
+Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
 from typing import Optional
@@ -14,7 +16,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import KvCacheArgs, KvPrefillArgs
+from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
@@ -32,10 +34,31 @@ def _check_cache(name: str, t: Tensor, paged: bool, D: int) -> None:
         raise ValueError(f"{name}: rows overlap (row stride {t.stride(1)} < head dim {D})")
 
 
+def _slopes_tensor(fn, alibi_slopes, query) -> Tensor:
+    """alibi_slopes as the fp32 [1 or B, 1 or H] tensor the kernels read per (batch, query head): _n_tensor's rules under the argument's
+    own name. The values are not looked at (no host round trip: capturable)."""
+    B, H = query.shape[0], query.shape[1]
+    if not isinstance(alibi_slopes, Tensor) or not alibi_slopes.is_floating_point():
+        got = alibi_slopes.dtype if isinstance(alibi_slopes, Tensor) else type(alibi_slopes).__name__
+        raise TypeError(f"{fn}: alibi_slopes must be a floating-point tensor; got {got}")
+    shape = (1,) * (2 - alibi_slopes.dim()) + tuple(alibi_slopes.shape)
+    if alibi_slopes.dim() > 2 or shape[0] not in (1, B) or shape[1] not in (1, H):
+        raise ValueError(f"{fn}: alibi_slopes must broadcast to [B, H] = [{B}, {H}] ([H], [1, H], [B, 1], [B, H] or 0-d; H = query heads); "
+                         f"got {tuple(alibi_slopes.shape)}")
+    if alibi_slopes.device != query.device:
+        raise RuntimeError(f"alibi_slopes is on {alibi_slopes.device}, query on {query.device}: every operand must live on the query's device "
+                           "(the slopes are read by the kernels, never on the host)")
+    if torch.is_grad_enabled() and alibi_slopes.requires_grad:
+        raise RuntimeError(f"{fn} is forward only (inference): alibi_slopes requires grad and the slopes carry no gradient. Call it under "
+                           "torch.no_grad(), or use flash_attention_n with attn_bias, which differentiates the bias")
+    return _n_tensor(alibi_slopes.detach(), query).contiguous()
+
+
 def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal, return_lse,
-             max_rows=None, args=None):
+             max_rows=None, args=None, alibi_slopes=None):
     """The argument checks both entry points share (they need no device and come first) and the filled fasn_kvcache_args.
-    Returns (args, out, lse, k_new, v_new, keep): `keep` holds the tensors whose addresses the arguments carry."""
+    Returns (args, out, lse, k_new, v_new, keep, alibi): `keep` holds the tensors whose addresses the arguments carry, `alibi` is the
+    filled fasn_alibi_slopes or None."""
     if query.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("query must be [B, H, Sq, D] and the caches [num_pages, page_size, Hkv, D] (paged) or [B, capacity, Hkv, D] (dense)")
     if query.dtype not in _KV_DTYPES:
@@ -97,6 +120,7 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
         n = 0.0 if softmax_n_param is None else float(softmax_n_param)
         if n < 0:
             raise ValueError("softmax_n_param must be >= 0")
+    st = None if alibi_slopes is None else _slopes_tensor(fn, alibi_slopes, query)
     scale = (1.0 / sqrt(D)) if scale is None else float(scale)
     # (the argument checks above need no device; everything below does)
     if not query.is_cuda:
@@ -129,7 +153,12 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
         a.n_stride_b, a.n_stride_h = _n_strides(nt)
     else:
         a.n, a.n_stride_b, a.n_stride_h = None, 0, 0
-    return a, out, lse, k_new, v_new, (query, nt)
+    alibi = None
+    if st is not None:
+        alibi = AlibiSlopes()
+        alibi.slopes = st.data_ptr()
+        alibi.stride_b, alibi.stride_h = _n_strides(st)
+    return a, out, lse, k_new, v_new, (query, nt, st), alibi
 
 
 def flash_attention_n_kvcache(
@@ -143,7 +172,8 @@ def flash_attention_n_kvcache(
         softmax_n_param=1,
         scale: Optional[float] = None,
         is_causal: bool = True,
-        return_lse: bool = False):
+        return_lse: bool = False,
+        alibi_slopes: Optional[Tensor] = None):
     """softmax_n attention of a few new query positions against a K/V cache, on MI355X.
 
     :param query: [B, H, Sq, D] fp16 / bf16 device tensor, D in {64, 128}; Sq = 1 is decode, a few positions speculative / chunked decode.
@@ -162,10 +192,15 @@ def flash_attention_n_kvcache(
     :param is_causal: bottom-right aligned per batch element: position i sees key j iff j <= i + len_b - Sq. False: every position sees
                   all len_b keys.
     :param return_lse: also return lse [B, H, Sq] fp32 = log(n + sum_j exp(x_ij)).
+    :param alibi_slopes: optional floating tensor on the query's device that broadcasts to [B, H] (one slope per query head, or per batch
+                  element and head; e.g. synth.alibi_slopes(H)): the logit becomes x_ij = scale * q_i.k_j - slope[b, h] * |p_i - j| with
+                  p_i = i + len_b - Sq the absolute position of query i - synth.alibi_bias's convention at S = len_b, L = Sq - computed in
+                  the kernel from the length in device memory (no bias tensor; a replayed graph follows cache_seqlens). Converted to fp32,
+                  never read on the host, no gradient. What is visible does not change; lse includes the bias.
     :return: [B, H, Sq, D] in query's dtype (and lse). Rows that see no key give exactly 0 and lse = log n (-inf for n = 0).
     """
-    a, out, lse, k_new, v_new, _keep = _prepare("flash_attention_n_kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
-                                                softmax_n_param, scale, is_causal, return_lse, max_rows=_MAX_ROWS)
+    a, out, lse, k_new, v_new, _keep, alibi = _prepare("flash_attention_n_kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                                                       softmax_n_param, scale, is_causal, return_lse, max_rows=_MAX_ROWS, alibi_slopes=alibi_slopes)
     lib = _lib.load()
     dev = query.device
 
@@ -175,7 +210,10 @@ def flash_attention_n_kvcache(
             _lib.check(lib.fasn_kvcache_append(a, _view4(k_new), _view4(v_new), stream), "fasn_kvcache_append")
         ws_bytes = lib.fasn_fwd_kvcache_workspace_bytes(a)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (torch's caching allocator: capturable, as _launch_fwd's)
-        _lib.check(lib.fasn_fwd_kvcache(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache")
+        if alibi is None:
+            _lib.check(lib.fasn_fwd_kvcache(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache")
+        else:   # (the same launches and workspace; the forward kernel's ALiBi sibling)
+            _lib.check(lib.fasn_fwd_kvcache_alibi(a, alibi, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache_alibi")
 
     if _current_device() == dev.index:
         launch()
@@ -197,7 +235,8 @@ def flash_attention_n_kvcache_prefill(
         softmax_n_param=1,
         scale: Optional[float] = None,
         is_causal: bool = True,
-        return_lse: bool = False):
+        return_lse: bool = False,
+        alibi_slopes: Optional[Tensor] = None):
     """softmax_n attention of ANY number of new query positions against a K/V cache, on MI355X: prefill, chunked prefill, a prefix-cache hit.
 
     The cache, `block_table`, `cache_seqlens`, `softmax_n_param`, `scale`, dtypes, head dims, alignment rules and refusals are those of
@@ -211,6 +250,8 @@ def flash_attention_n_kvcache_prefill(
                   batch of prompts or chunks padded to Sq. Never read on the host.
     :param is_causal: with len_b = clamp(cache_seqlens[b] + (qlen_b if k_new is given else 0), 0, capacity), position i < qlen_b sees key j
                   iff j < len_b and (causal) j <= i + len_b - qlen_b: bottom-right aligned per batch element.
+    :param alibi_slopes: as in flash_attention_n_kvcache, with p_i = i + len_b - qlen_b: the absolute position of query i of batch element
+                  b follows cache_seqlens and query_seqlens in device memory.
     :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32). A position that sees no key gives exactly 0 and lse = log n (-inf
              for n = 0); padding positions i >= qlen_b give exactly 0 and lse = -inf whatever n is.
     """
@@ -228,8 +269,8 @@ def flash_attention_n_kvcache_prefill(
     if query.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and query.shape[1] // k_cache.shape[2] > 128 and query.shape[1] % k_cache.shape[2] == 0:
         raise ValueError(f"{fn}: {query.shape[1] // k_cache.shape[2]} query heads per K/V head are not supported (at most 128: the heads of a "
                          "K/V head share one workgroup)")
-    _a, out, lse, k_new, v_new, _keep = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
-                                                 softmax_n_param, scale, is_causal, return_lse, args=pa.kv)
+    _a, out, lse, k_new, v_new, _keep, alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                                                        softmax_n_param, scale, is_causal, return_lse, args=pa.kv, alibi_slopes=alibi_slopes)
     pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
     lib = _lib.load()
     dev = query.device
@@ -241,7 +282,10 @@ def flash_attention_n_kvcache_prefill(
         ws_bytes = lib.fasn_fwd_kvprefill_workspace_bytes(pa)
         # (one split: no partials, no workspace; otherwise torch's caching allocator: capturable, as _launch_fwd's)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        _lib.check(lib.fasn_fwd_kvprefill(pa, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill")
+        if alibi is None:
+            _lib.check(lib.fasn_fwd_kvprefill(pa, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill")
+        else:   # (the same launches and workspace; the forward kernel's ALiBi sibling)
+            _lib.check(lib.fasn_fwd_kvprefill_alibi(pa, alibi, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill_alibi")
 
     if _current_device() == dev.index:
         launch()

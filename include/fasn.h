@@ -233,7 +233,7 @@ int fasn_bwd_path(const fasn_bwd_args* args);
  * Forward over a K/V CACHE (inference; additions within ABI 6, no counterpart in the reference, which has no cache): attention of a few new
  * query positions per batch element (Sq = 1: decode) against keys that live in a paged or dense cache whose valid LENGTHS ARE IN DEVICE
  * MEMORY. Nothing about the lengths or the block table is read on the host: the launches depend on shapes and capacity only, so one
- * captured HIP graph serves every step of a generation while the sequences grow. Forward only; no mask, bias or dropout.
+ * captured HIP graph serves every step of a generation while the sequences grow. Forward only; no mask, no dropout, no bias other than the ALiBi slopes of the *_alibi calls below.
  *
  *   cache     key j of batch element b is row j % page_size of page block_table[b * block_table_stride + j / page_size]; element
  *             (page, row, K/V head hk, feature d) of K sits at k_cache + (page * k_stride[0] + row * k_stride[1] + hk * k_stride[2] + d)
@@ -312,6 +312,33 @@ size_t fasn_fwd_kvprefill_workspace_bytes(const fasn_kvprefill_args* args);
 int fasn_fwd_kvprefill(const fasn_kvprefill_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
 int fasn_kvprefill_append(const fasn_kvprefill_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
 int fasn_kvprefill_plan(const fasn_kvprefill_args* args, char* buf, size_t cap);
+
+/*
+ * ALiBi SLOPES on the cache calls (additions within ABI 6; the argument blocks above keep their layouts): the logit of query position i
+ * and key j becomes
+ *     scale * q_i . k_j  -  slope[b, h] * | p_i - j |,      p_i = i + len_b - qlen_b      (decode: qlen_b = Sq)
+ * with len_b / qlen_b as the base call defines them, read in device memory - p_i is the absolute position of query i, so a replayed graph
+ * follows `seqlens` and `q_seqlens`. Visibility (causal, lengths, padding positions), the results of rows that see no key, softmax_n and
+ * `n` are those of the base call; lse includes the bias. The bias is computed inside the forward kernels from the two integers and the
+ * slope: no bias tensor exists. slope[b, h] = slopes[b * stride_b + h * stride_h] (fp32, DEVICE, h = query head; stride 0 broadcasts),
+ * never read on the host.
+ *
+ * fasn_fwd_kvcache_alibi / fasn_fwd_kvprefill_alibi are fasn_fwd_kvcache / fasn_fwd_kvprefill with the operand: same launches, grids and
+ * splits (kernels of their own for the forward, the same combine kernel), and the WORKSPACE of the base call -
+ * fasn_fwd_kvcache_workspace_bytes(args) / fasn_fwd_kvprefill_workspace_bytes(args) bytes. The appends are the base calls'. Every rule
+ * and error code of the base call holds and is checked first; then: alibi == NULL or slopes == NULL is FASN_EINVAL, slopes not 4-byte
+ * aligned FASN_EALIGN, a negative stride or (B-1) stride_b + (H-1) stride_h >= 2^31 FASN_EINVAL. The *_alibi_plan calls are
+ * fasn_kvcache_plan / fasn_kvprefill_plan for these launches.
+ */
+typedef struct fasn_alibi_slopes {
+    const float* slopes;         /* DEVICE per-(batch, query head) slope */
+    int64_t stride_b, stride_h;  /* elements */
+} fasn_alibi_slopes;
+
+int fasn_fwd_kvcache_alibi(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_fwd_kvprefill_alibi(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvcache_alibi_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap);
+int fasn_kvprefill_alibi_plan(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap);
 
 /*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
