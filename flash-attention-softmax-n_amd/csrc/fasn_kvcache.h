@@ -57,8 +57,18 @@ struct KvParams {
 };
 
 constexpr int KV_KT = 64;   // keys per tile
-constexpr int kv_nbuf(int D) { return D <= 64 ? 3 : 2; }                        // LDS tile buffers per operand (48 KiB / 64 KiB: three / two workgroups per CU)
+constexpr int kv_nbuf(int D) { return D <= 64 ? 3 : 2; }                        // LDS tile buffers per operand (D = 32 / 64 / 128 / 256: 24 / 48 / 64 / 128 KiB of LDS)
 constexpr int kv_smem(int D) { return 2 * kv_nbuf(D) * KV_KT * D * 2; }
+// Workgroups per CU the forward kernels are compiled for. D = 256: two 32 KiB buffers per operand are 128 KiB of the CU's 160 - one
+// workgroup, whose waves may then use the whole register file (16 accumulator blocks of O^T and the 16 Q fragments do not fit in half).
+// D = 32: three 4 KiB buffers per operand (24 KiB); the registers, not the LDS, set the two workgroups the kernel is compiled for.
+constexpr int kv_wg_per_cu(int D) { return D <= 128 ? 2 : 1; }
+constexpr bool kv_head_dim_ok(int D) { return D == 32 || D == 64 || D == 128 || D == 256; }
+// Workgroups the split rule of both calls aims at. Up to D = 128 the chip holds two to three workgroups per CU and ~1024 are four
+// rounds of them. At D = 256 one workgroup fills a CU: 256 are resident, every further split is a further 128 KiB of LDS to zero, 16
+// more Q fragments to fetch and a partial of D + 2 floats per row that nobody's K/V requests hide - 512 (two rounds, so that a short
+// batch element's workgroups leave their CU to another's) is what the plan aims at there.
+constexpr int kv_split_target(int D) { return D <= 128 ? 1024 : 512; }
 
 FASN_DEV int kv_len(const KvParams& p, int b) {
     const int len = __builtin_amdgcn_readfirstlane(p.seqlens[b]) + p.seqlen_add;

@@ -21,12 +21,13 @@ int kv_check_view(const fasn_view4& v) {
 }
 
 // Validation (no HIP call) + the kernel parameters. The plan: one workgroup per (batch element, K/V head, split); as many splits as
-// bring the grid to ~1024 workgroups (the split-K forward's target), each with enough tiles of a FULL cache to pay for its partial.
+// bring the grid to ~1024 workgroups (the split-K forward's target; ~512 at D = 256, kv_split_target), each with enough tiles of a FULL
+// cache to pay for its partial. Head dims: 32, 64, 128, 256 (kv_head_dim_ok).
 int kv_build(const fasn_kvcache_args* a, KvParams& p) {
     if (a == nullptr) return FASN_EINVAL;
     if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->D <= 0 || a->page_size <= 0) return FASN_EINVAL;
     if (a->dtype != FASN_DTYPE_F16 && a->dtype != FASN_DTYPE_BF16) return FASN_EDTYPE;
-    if (a->D != 64 && a->D != 128) return FASN_EHEADDIM;
+    if (!kv_head_dim_ok(a->D)) return FASN_EHEADDIM;
     const int G = a->kv_group <= 1 ? 1 : a->kv_group;
     if (a->H % G != 0) return FASN_EINVAL;
     if (!(a->softmax_n >= 0.f) || !isfinite(a->scale)) return FASN_EINVAL;
@@ -78,7 +79,7 @@ int kv_build(const fasn_kvcache_args* a, KvParams& p) {
     p.nsb = (int)a->n_stride_b, p.nsh = (int)a->n_stride_h;
     const int64_t base = (int64_t)p.B * p.Hkv;
     const int64_t cap_tiles = (capacity + KV_KT - 1) / KV_KT;
-    int64_t nsplit = (1024 + base - 1) / base;
+    int64_t nsplit = (kv_split_target(a->D) + base - 1) / base;
     // a split costs its partial (R rows of D + 2 floats, written and read back) next to its tiles (64 keys of K and V): at least 4 tiles
     // per split of a full cache, R / 8 when there are many rows (128 rows: the partial moves what 4 tiles do)
     const int64_t min_tps = p.R / 8 > 4 ? p.R / 8 : 4;
@@ -122,6 +123,16 @@ int kv_launch_append(const KvParams& p, hipStream_t s) {
     return launch_rc();
 }
 
+template <typename Tag>
+int kv_launch_fwd_d(int D, const KvParams& p, const KvAlibi* al, hipStream_t s) {   // (kv_build let only these four through)
+    switch (D) {
+        case 32: return kv_launch_fwd<Tag, 32>(p, al, s);
+        case 64: return kv_launch_fwd<Tag, 64>(p, al, s);
+        case 128: return kv_launch_fwd<Tag, 128>(p, al, s);
+        default: return kv_launch_fwd<Tag, 256>(p, al, s);
+    }
+}
+
 int kv_forward(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
     KvParams p;
     int rc = kv_build(args, p);
@@ -134,8 +145,8 @@ int kv_forward(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, bo
     p.part_ml = p.part_o + (size_t)p.B * p.Hkv * p.nsplit * p.R * args->D;
     hipStream_t s = (hipStream_t)stream;
     const KvAlibi* const alp = with_alibi ? &al : nullptr;
-    if (args->dtype == FASN_DTYPE_BF16) return args->D == 64 ? kv_launch_fwd<bf16_tag, 64>(p, alp, s) : kv_launch_fwd<bf16_tag, 128>(p, alp, s);
-    return args->D == 64 ? kv_launch_fwd<f16_tag, 64>(p, alp, s) : kv_launch_fwd<f16_tag, 128>(p, alp, s);
+    if (args->dtype == FASN_DTYPE_BF16) return kv_launch_fwd_d<bf16_tag>(args->D, p, alp, s);
+    return kv_launch_fwd_d<f16_tag>(args->D, p, alp, s);
 }
 
 int kv_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, char* buf, size_t cap) {
@@ -185,7 +196,12 @@ int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, 
         p.vns[i] = v_new->stride[i];
     }
     hipStream_t s = (hipStream_t)stream;
-    return args->D == 64 ? kv_launch_append<64>(p, s) : kv_launch_append<128>(p, s);
+    switch (args->D) {
+        case 32: return kv_launch_append<32>(p, s);
+        case 64: return kv_launch_append<64>(p, s);
+        case 128: return kv_launch_append<128>(p, s);
+        default: return kv_launch_append<256>(p, s);
+    }
 }
 
 int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) { return kv_plan(args, nullptr, false, buf, cap); }

@@ -2,9 +2,9 @@
 // guard). With FASN_KV_ALIBI == 0 the preprocessor leaves fasn_kvcache_fwd_kernel exactly as it was before the ALiBi kernels existed.
 template <typename Tag, int D>
 #if FASN_KV_ALIBI
-__global__ void __launch_bounds__(256, 2) fasn_kvcache_fwd_alibi_kernel(const KvParams p, const KvAlibi al) {
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_alibi_kernel(const KvParams p, const KvAlibi al) {
 #else
-__global__ void __launch_bounds__(256, 2) fasn_kvcache_fwd_kernel(const KvParams p) {
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(const KvParams p) {
 #endif
     using E = ET<Tag>;
     using vec8 = typename E::vec8;

@@ -28,7 +28,7 @@ int kvp_build(const fasn_kvprefill_args* pa, KvPrefillParams& pp) {
     const fasn_kvcache_args* a = &pa->kv;
     if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->D <= 0 || a->page_size <= 0) return FASN_EINVAL;
     if (a->dtype != FASN_DTYPE_F16 && a->dtype != FASN_DTYPE_BF16) return FASN_EDTYPE;
-    if (a->D != 64 && a->D != 128) return FASN_EHEADDIM;
+    if (!kv_head_dim_ok(a->D)) return FASN_EHEADDIM;
     const int G = a->kv_group <= 1 ? 1 : a->kv_group;
     if (a->H % G != 0) return FASN_EINVAL;
     if (!(a->softmax_n >= 0.f) || !isfinite(a->scale)) return FASN_EINVAL;
@@ -85,7 +85,7 @@ int kvp_build(const fasn_kvprefill_args* pa, KvPrefillParams& pp) {
     pp.nrb = (a->Sq + pp.PB - 1) / pp.PB;
     const int64_t base = (int64_t)p.B * p.Hkv * pp.nrb;
     const int64_t cap_tiles = (capacity + KV_KT - 1) / KV_KT;
-    int64_t nsplit = (1024 + base - 1) / base;
+    int64_t nsplit = (kv_split_target(a->D) + base - 1) / base;
     // a split costs its partial (128 row slots of D + 2 floats, written and read back: what 4 tiles move) next to its tiles: at least
     // 16 tiles per split of a full cache (the decode rule at 128 rows)
     const int64_t min_tps = KVP_ROWS / 8;
@@ -136,6 +136,16 @@ int kvp_launch_append(const KvPrefillParams& pp, hipStream_t s) {
     return launch_rc();
 }
 
+template <typename Tag>
+int kvp_launch_fwd_d(int D, const KvPrefillParams& pp, const KvAlibi* al, hipStream_t s) {   // (kvp_build let only these four through)
+    switch (D) {
+        case 32: return kvp_launch_fwd<Tag, 32>(pp, al, s);
+        case 64: return kvp_launch_fwd<Tag, 64>(pp, al, s);
+        case 128: return kvp_launch_fwd<Tag, 128>(pp, al, s);
+        default: return kvp_launch_fwd<Tag, 256>(pp, al, s);
+    }
+}
+
 int kvp_forward(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
     KvPrefillParams pp;
     int rc = kvp_build(args, pp);
@@ -152,8 +162,8 @@ int kvp_forward(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi,
     }
     hipStream_t s = (hipStream_t)stream;
     const KvAlibi* const alp = with_alibi ? &al : nullptr;
-    if (args->kv.dtype == FASN_DTYPE_BF16) return D == 64 ? kvp_launch_fwd<bf16_tag, 64>(pp, alp, s) : kvp_launch_fwd<bf16_tag, 128>(pp, alp, s);
-    return D == 64 ? kvp_launch_fwd<f16_tag, 64>(pp, alp, s) : kvp_launch_fwd<f16_tag, 128>(pp, alp, s);
+    if (args->kv.dtype == FASN_DTYPE_BF16) return kvp_launch_fwd_d<bf16_tag>(D, pp, alp, s);
+    return kvp_launch_fwd_d<f16_tag>(D, pp, alp, s);
 }
 
 int kvp_plan(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, char* buf, size_t cap) {
@@ -203,7 +213,12 @@ int fasn_kvprefill_append(const fasn_kvprefill_args* args, const fasn_view4* k_n
         pp.kv.vns[i] = v_new->stride[i];
     }
     hipStream_t s = (hipStream_t)stream;
-    return args->kv.D == 64 ? kvp_launch_append<64>(pp, s) : kvp_launch_append<128>(pp, s);
+    switch (args->kv.D) {
+        case 32: return kvp_launch_append<32>(pp, s);
+        case 64: return kvp_launch_append<64>(pp, s);
+        case 128: return kvp_launch_append<128>(pp, s);
+        default: return kvp_launch_append<256>(pp, s);
+    }
 }
 
 int fasn_kvprefill_plan(const fasn_kvprefill_args* args, char* buf, size_t cap) { return kvp_plan(args, nullptr, false, buf, cap); }

@@ -2,9 +2,9 @@
 // include guard). With FASN_KV_ALIBI == 0 the preprocessor leaves fasn_kvprefill_fwd_kernel exactly as it was before the ALiBi kernels existed.
 template <typename Tag, int D>
 #if FASN_KV_ALIBI
-__global__ void __launch_bounds__(256, 2) fasn_kvprefill_fwd_alibi_kernel(const KvPrefillParams pp, const KvAlibi al) {
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_alibi_kernel(const KvPrefillParams pp, const KvAlibi al) {
 #else
-__global__ void __launch_bounds__(256, 2) fasn_kvprefill_fwd_kernel(const KvPrefillParams pp) {
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kernel(const KvPrefillParams pp) {
 #endif
     using E = ET<Tag>;
     using vec8 = typename E::vec8;

@@ -20,7 +20,7 @@ from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
-_KV_HEAD_DIMS = (64, 128)
+_KV_HEAD_DIMS = (32, 64, 128, 256)   # the head dims flash_attention_n trains at; any other size is refused (a cache is never padded)
 _MAX_ROWS = 128   # query heads per K/V head x query positions: the rows of one workgroup
 
 
@@ -176,7 +176,7 @@ def flash_attention_n_kvcache(
         alibi_slopes: Optional[Tensor] = None):
     """softmax_n attention of a few new query positions against a K/V cache, on MI355X.
 
-    :param query: [B, H, Sq, D] fp16 / bf16 device tensor, D in {64, 128}; Sq = 1 is decode, a few positions speculative / chunked decode.
+    :param query: [B, H, Sq, D] fp16 / bf16 device tensor, D in {32, 64, 128, 256}; Sq = 1 is decode, a few positions speculative / chunked decode.
     :param k_cache, v_cache: paged [num_pages, page_size, Hkv, D] with `block_table` (page_size a multiple of 64), or dense
                   [B, capacity, Hkv, D] with block_table=None. Any strided view whose rows are 16-byte aligned with feature stride 1
                   (e.g. sliced out of a fused K/V buffer); never copied. H % Hkv == 0 and (H // Hkv) * Sq <= 128: the query heads of a

@@ -247,7 +247,9 @@ int fasn_bwd_path(const fasn_bwd_args* args);
  *             `n` / n_stride_b / n_stride_h with the meaning fasn_fwd_n gives them, n == NULL = the scalar softmax_n.
  *   causal    bottom-right aligned per batch element: position i sees key j iff j <= i + len_b - Sq. Rows that see no key give 0 and
  *             lse = log n (-inf for n = 0).
- *   supported D in {64, 128} (FASN_EHEADDIM otherwise), fp16 / bf16 (FASN_EDTYPE), paged: page_size % 64 == 0 (FASN_EUNSUPPORTED).
+ *   supported D in {32, 64, 128, 256} - the head dims fasn_fwd has kernels for; every other size is FASN_EHEADDIM: a cache is never
+ *             zero-padded - fp16 / bf16 (FASN_EDTYPE), paged: page_size % 64 == 0 at every head dim (FASN_EUNSUPPORTED). D = 256 runs
+ *             one workgroup per CU (128 KiB of LDS) and its plans aim at ~512 workgroups where the other head dims aim at ~1024.
  *
  * fasn_fwd_kvcache needs fasn_fwd_kvcache_workspace_bytes(args) bytes of 16-byte aligned device memory (split partials; FASN_EWORKSPACE
  * when missing or too small) and launches two kernels. fasn_kvcache_append writes the Sq rows of k_new / v_new ([B, H / kv_group, Sq, D]
