@@ -27,6 +27,8 @@ EXPORTS = (
     "fasn_fwd_kvcache_workspace_bytes", "fasn_fwd_kvcache", "fasn_kvcache_append", "fasn_kvcache_plan",
     "fasn_fwd_kvprefill_workspace_bytes", "fasn_fwd_kvprefill", "fasn_kvprefill_append", "fasn_kvprefill_plan",
     "fasn_fwd_kvcache_alibi", "fasn_fwd_kvprefill_alibi", "fasn_kvcache_alibi_plan", "fasn_kvprefill_alibi_plan",
+    "fasn_fwd_kvcache_window_workspace_bytes", "fasn_fwd_kvcache_window", "fasn_kvcache_window_plan",
+    "fasn_fwd_kvprefill_window_workspace_bytes", "fasn_fwd_kvprefill_window", "fasn_kvprefill_window_plan",
 )
 
 
@@ -83,6 +85,11 @@ class KvPrefillArgs(Structure):
 class AlibiSlopes(Structure):
     """fasn_alibi_slopes (include/fasn.h): per-(batch, query head) fp32 ALiBi slopes in device memory, for the *_alibi cache calls"""
     _fields_ = [("slopes", c_void_p), ("stride_b", c_int64), ("stride_h", c_int64)]
+
+
+class KvWindow(Structure):
+    """fasn_kv_window (include/fasn.h): the sliding window of the *_window cache calls, a host integer >= 1; reserved = 0"""
+    _fields_ = [("window", c_int32), ("reserved", c_int32)]
 
 
 class FasnError(RuntimeError):
@@ -164,6 +171,18 @@ def load():
     lib.fasn_kvcache_alibi_plan.argtypes = [POINTER(KvCacheArgs), POINTER(AlibiSlopes), c_char_p, c_size_t]
     lib.fasn_kvprefill_alibi_plan.restype = c_int32
     lib.fasn_kvprefill_alibi_plan.argtypes = [POINTER(KvPrefillArgs), POINTER(AlibiSlopes), c_char_p, c_size_t]
+    lib.fasn_fwd_kvcache_window_workspace_bytes.restype = c_size_t
+    lib.fasn_fwd_kvcache_window_workspace_bytes.argtypes = [POINTER(KvCacheArgs), POINTER(KvWindow)]
+    lib.fasn_fwd_kvcache_window.restype = c_int32
+    lib.fasn_fwd_kvcache_window.argtypes = [POINTER(KvCacheArgs), POINTER(KvWindow), c_void_p, c_size_t, c_void_p]
+    lib.fasn_kvcache_window_plan.restype = c_int32
+    lib.fasn_kvcache_window_plan.argtypes = [POINTER(KvCacheArgs), POINTER(KvWindow), c_char_p, c_size_t]
+    lib.fasn_fwd_kvprefill_window_workspace_bytes.restype = c_size_t
+    lib.fasn_fwd_kvprefill_window_workspace_bytes.argtypes = [POINTER(KvPrefillArgs), POINTER(KvWindow)]
+    lib.fasn_fwd_kvprefill_window.restype = c_int32
+    lib.fasn_fwd_kvprefill_window.argtypes = [POINTER(KvPrefillArgs), POINTER(KvWindow), c_void_p, c_size_t, c_void_p]
+    lib.fasn_kvprefill_window_plan.restype = c_int32
+    lib.fasn_kvprefill_window_plan.argtypes = [POINTER(KvPrefillArgs), POINTER(KvWindow), c_char_p, c_size_t]
     ver = lib.fasn_abi_version()
     if ver != FASN_ABI_VERSION:
         raise ImportError(f"libfasn ABI version {ver} != expected {FASN_ABI_VERSION}; rebuild csrc/")
@@ -234,6 +253,26 @@ def kvprefill_plan(args, alibi=None):
         rc, what = load().fasn_kvprefill_alibi_plan(args, alibi, buf, len(buf)), "fasn_kvprefill_alibi_plan"
     if rc < 0:
         check(rc, what)
+    return _plan_lines(buf)
+
+
+def kvcache_window_plan(args, win):
+    """The kernels fasn_fwd_kvcache_window would launch for `args` (a KvCacheArgs) under `win` (a KvWindow), as launch_plan returns them.
+    Nothing is launched."""
+    buf = ctypes.create_string_buffer(4096)
+    rc = load().fasn_kvcache_window_plan(args, win, buf, len(buf))
+    if rc < 0:
+        check(rc, "fasn_kvcache_window_plan")
+    return _plan_lines(buf)
+
+
+def kvprefill_window_plan(args, win):
+    """The kernels fasn_fwd_kvprefill_window would launch for `args` (a KvPrefillArgs) under `win` (a KvWindow), as launch_plan returns
+    them. Nothing is launched."""
+    buf = ctypes.create_string_buffer(4096)
+    rc = load().fasn_kvprefill_window_plan(args, win, buf, len(buf))
+    if rc < 0:
+        check(rc, "fasn_kvprefill_window_plan")
     return _plan_lines(buf)
 
 

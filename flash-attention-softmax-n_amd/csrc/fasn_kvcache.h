@@ -4,6 +4,7 @@
 //   fasn_kvcache_append_kernel   k_new / v_new rows -> cache rows len_b .. len_b + Sq - 1 (dropped beyond the capacity)
 //   fasn_kvcache_fwd_kernel      split-K walk over the pages of one (batch element, K/V head): un-normalised partials
 //   fasn_kvcache_fwd_alibi_kernel  the same walk with the ALiBi term -slope_h |j - p_i| in the scores (fasn_kvcache_fwd.inc holds both)
+//   fasn_kvcache_fwd_window_kernel  the same walk over the tiles of a sliding window only: key j is visible iff p_i - W < j <= p_i
 //   fasn_kvcache_combine_kernel  merges the partials and scatters the rows back to o[b, h, pos, :] / lse[b, h, pos]
 //
 // Rows. The G = H / Hkv query heads that share a K/V head times the Sq query positions are the rows of ONE problem:
@@ -69,6 +70,19 @@ constexpr bool kv_head_dim_ok(int D) { return D == 32 || D == 64 || D == 128 || 
 // more Q fragments to fetch and a partial of D + 2 floats per row that nobody's K/V requests hide - 512 (two rounds, so that a short
 // batch element's workgroups leave their CU to another's) is what the plan aims at there.
 constexpr int kv_split_target(int D) { return D <= 128 ? 1024 : 512; }
+// The split rule of both calls: as many splits as bring `base` workgroups to the target, each with at least min_tps of the cap_tiles
+// tiles a workgroup can have to walk.
+constexpr int64_t kv_nsplit(int D, int64_t base, int64_t cap_tiles, int64_t min_tps) {
+    int64_t nsplit = (kv_split_target(D) + base - 1) / base;
+    if (nsplit > cap_tiles / min_tps) nsplit = cap_tiles / min_tps;
+    return nsplit < 1 ? 1 : nsplit;
+}
+// ... under a sliding window of W keys: the keys of a workgroup whose rows span `span` positions lie in W + span - 1 positions, which
+// touch one tile more than they fill
+constexpr int64_t kv_window_tiles(int64_t cap_tiles, int64_t W, int64_t span) {
+    const int64_t t = (W + span - 1 + KV_KT - 1) / KV_KT + 1;
+    return t < cap_tiles ? t : cap_tiles;
+}
 
 FASN_DEV int kv_len(const KvParams& p, int b) {
     const int len = __builtin_amdgcn_readfirstlane(p.seqlens[b]) + p.seqlen_add;
@@ -97,15 +111,33 @@ FASN_DEV float kv_alibi_term(float nslope2, float dk0, int kb, int r) {
     return nslope2 * __builtin_fabsf(dk0 + (float)(kb * 32 + (r & 3) + 8 * (r >> 2)));
 }
 
-// fasn_kvcache_fwd_kernel<Tag, D>(KvParams) and fasn_kvcache_fwd_alibi_kernel<Tag, D>(KvParams, KvAlibi): one text, compiled twice.
+// Sliding window (fasn_fwd_kvcache_window / fasn_fwd_kvprefill_window): position p_i = pos_i + len_b - qlen_b sees the W keys
+// p_i - W < j <= p_i (always causal). w = min(W, capacity) on the host: no position is beyond capacity - 1, so the clamp changes nothing
+// and p - w cannot overflow. A workgroup walks the tiles from the one that holds the first key of its FIRST row's window; whatever lies
+// below - cache rows, pages, block-table entries - is never read and may be gone.
+struct KvWindow {
+    int w;
+};
+// which forward kernel a call launches; its operand is nothing, a fasn_alibi_slopes or a fasn_kv_window
+enum KvVariant { KV_BASE, KV_ALIBI, KV_WINDOW };
+
+// fasn_kvcache_fwd_kernel<Tag, D>(KvParams), fasn_kvcache_fwd_alibi_kernel<Tag, D>(KvParams, KvAlibi) and
+// fasn_kvcache_fwd_window_kernel<Tag, D>(KvParams, KvWindow): one text, compiled three times.
 // (A bool-templated device function behind two __global__ wrappers was tried first: the compiler then schedules and allocates the
 // kernel WITHOUT the bias differently - four more VGPRs at D = 64 - and the existing instantiations are to stay byte for byte what
 // they were; tools/kernel_digest.py shows they do.)
+#define FASN_KV_WINDOW 0
 #define FASN_KV_ALIBI 0
 #include "fasn_kvcache_fwd.inc"
 #undef FASN_KV_ALIBI
 #define FASN_KV_ALIBI 1
 #include "fasn_kvcache_fwd.inc"
+#undef FASN_KV_ALIBI
+#undef FASN_KV_WINDOW
+#define FASN_KV_ALIBI 0
+#define FASN_KV_WINDOW 1
+#include "fasn_kvcache_fwd.inc"
+#undef FASN_KV_WINDOW
 #undef FASN_KV_ALIBI
 
 // Merge the partials of a row (the arithmetic of fasn_fwd_combine_kernel: m* = max_s m_s, l = sum_s l_s 2^(m_s - m*),

@@ -1,4 +1,4 @@
-// K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi], fasn_kvcache_append, fasn_kvcache[_alibi]_plan): argument checks, the launch plan -
+// K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi|_window], fasn_kvcache_append, fasn_kvcache[_alibi|_window]_plan): argument checks, the launch plan -
 // which depends on shapes and capacity only, never on the lengths in device memory - and the three launches of fasn_kvcache.h.
 #include <limits.h>
 #include <math.h>
@@ -23,6 +23,10 @@ int kv_check_view(const fasn_view4& v) {
 // Validation (no HIP call) + the kernel parameters. The plan: one workgroup per (batch element, K/V head, split); as many splits as
 // bring the grid to ~1024 workgroups (the split-K forward's target; ~512 at D = 256, kv_split_target), each with enough tiles of a FULL
 // cache to pay for its partial. Head dims: 32, 64, 128, 256 (kv_head_dim_ok).
+// a split costs its partial (R rows of D + 2 floats, written and read back) next to its tiles (64 keys of K and V): at least 4 tiles
+// per split of a full cache, R / 8 when there are many rows (128 rows: the partial moves what 4 tiles do)
+int64_t kv_min_tps(int R) { return R / 8 > 4 ? R / 8 : 4; }
+
 int kv_build(const fasn_kvcache_args* a, KvParams& p) {
     if (a == nullptr) return FASN_EINVAL;
     if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->D <= 0 || a->page_size <= 0) return FASN_EINVAL;
@@ -79,12 +83,7 @@ int kv_build(const fasn_kvcache_args* a, KvParams& p) {
     p.nsb = (int)a->n_stride_b, p.nsh = (int)a->n_stride_h;
     const int64_t base = (int64_t)p.B * p.Hkv;
     const int64_t cap_tiles = (capacity + KV_KT - 1) / KV_KT;
-    int64_t nsplit = (kv_split_target(a->D) + base - 1) / base;
-    // a split costs its partial (R rows of D + 2 floats, written and read back) next to its tiles (64 keys of K and V): at least 4 tiles
-    // per split of a full cache, R / 8 when there are many rows (128 rows: the partial moves what 4 tiles do)
-    const int64_t min_tps = p.R / 8 > 4 ? p.R / 8 : 4;
-    if (nsplit > cap_tiles / min_tps) nsplit = cap_tiles / min_tps;
-    p.nsplit = nsplit < 1 ? 1 : (int)nsplit;
+    p.nsplit = (int)kv_nsplit(a->D, base, cap_tiles, kv_min_tps(p.R));
     if (base * p.nsplit > INT_MAX) return FASN_EINVAL;
     return FASN_OK;
 }
@@ -99,11 +98,26 @@ int kv_build_alibi(const fasn_kvcache_args* a, const fasn_alibi_slopes* s, KvAli
     return FASN_OK;
 }
 
-// (al == nullptr: the kernel without a bias; otherwise its ALiBi sibling on the same grid, LDS and workspace)
+// The window operand of the *_window entry points (checked after the base arguments, before any HIP call), and the plan under it: the
+// base rule over the tiles a workgroup's window can touch, never more splits than the base plan has.
+int kv_build_window(const fasn_kvcache_args* a, const fasn_kv_window* w, KvParams& p, KvWindow& kw) {
+    if (w == nullptr || w->window < 1 || w->reserved != 0) return FASN_EINVAL;
+    if (!a->causal) return FASN_EUNSUPPORTED;
+    kw = KvWindow{w->window < p.capacity ? w->window : p.capacity};
+    const int64_t cap_tiles = ((int64_t)p.capacity + KV_KT - 1) / KV_KT;
+    p.nsplit = (int)kv_nsplit(a->D, (int64_t)p.B * p.Hkv, kv_window_tiles(cap_tiles, w->window, p.Sq), kv_min_tps(p.R));
+    return FASN_OK;
+}
+
+// (al == kw == nullptr: the base kernel; otherwise its ALiBi sibling on the same grid, LDS and workspace, or its window sibling)
 template <typename Tag, int D>
-int kv_launch_fwd(const KvParams& p, const KvAlibi* al, hipStream_t s) {
+int kv_launch_fwd(const KvParams& p, const KvAlibi* al, const KvWindow* kw, hipStream_t s) {
     constexpr int smem = kv_smem(D);
-    if (al == nullptr) {
+    if (kw != nullptr) {
+        constexpr auto kern = &fasn_kvcache_fwd_window_kernel<Tag, D>;
+        ensure_smem<kern>(smem);
+        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * p.nsplit)), dim3(256), smem, s, p, *kw);
+    } else if (al == nullptr) {
         constexpr auto kern = &fasn_kvcache_fwd_kernel<Tag, D>;
         ensure_smem<kern>(smem);
         FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * p.nsplit)), dim3(256), smem, s, p);
@@ -124,38 +138,41 @@ int kv_launch_append(const KvParams& p, hipStream_t s) {
 }
 
 template <typename Tag>
-int kv_launch_fwd_d(int D, const KvParams& p, const KvAlibi* al, hipStream_t s) {   // (kv_build let only these four through)
+int kv_launch_fwd_d(int D, const KvParams& p, const KvAlibi* al, const KvWindow* kw, hipStream_t s) {   // (kv_build let only these four through)
     switch (D) {
-        case 32: return kv_launch_fwd<Tag, 32>(p, al, s);
-        case 64: return kv_launch_fwd<Tag, 64>(p, al, s);
-        case 128: return kv_launch_fwd<Tag, 128>(p, al, s);
-        default: return kv_launch_fwd<Tag, 256>(p, al, s);
+        case 32: return kv_launch_fwd<Tag, 32>(p, al, kw, s);
+        case 64: return kv_launch_fwd<Tag, 64>(p, al, kw, s);
+        case 128: return kv_launch_fwd<Tag, 128>(p, al, kw, s);
+        default: return kv_launch_fwd<Tag, 256>(p, al, kw, s);
     }
 }
 
-int kv_forward(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+int kv_forward(const fasn_kvcache_args* args, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
     KvParams p;
     int rc = kv_build(args, p);
     if (rc) return rc;
     KvAlibi al{};
-    if (with_alibi && (rc = kv_build_alibi(args, alibi, al))) return rc;
+    KvWindow kw{};
+    if (variant == KV_ALIBI && (rc = kv_build_alibi(args, static_cast<const fasn_alibi_slopes*>(operand), al))) return rc;
+    if (variant == KV_WINDOW && (rc = kv_build_window(args, static_cast<const fasn_kv_window*>(operand), p, kw))) return rc;
     if (workspace == nullptr || workspace_bytes < kv_ws_bytes(p, args->D)) return FASN_EWORKSPACE;
     if (!kv_aligned16(workspace)) return FASN_EALIGN;
     p.part_o = static_cast<float*>(workspace);
     p.part_ml = p.part_o + (size_t)p.B * p.Hkv * p.nsplit * p.R * args->D;
     hipStream_t s = (hipStream_t)stream;
-    const KvAlibi* const alp = with_alibi ? &al : nullptr;
-    if (args->dtype == FASN_DTYPE_BF16) return kv_launch_fwd_d<bf16_tag>(args->D, p, alp, s);
-    return kv_launch_fwd_d<f16_tag>(args->D, p, alp, s);
+    const KvAlibi* const alp = variant == KV_ALIBI ? &al : nullptr;
+    const KvWindow* const kwp = variant == KV_WINDOW ? &kw : nullptr;
+    if (args->dtype == FASN_DTYPE_BF16) return kv_launch_fwd_d<bf16_tag>(args->D, p, alp, kwp, s);
+    return kv_launch_fwd_d<f16_tag>(args->D, p, alp, kwp, s);
 }
 
-int kv_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, char* buf, size_t cap) {
+int kv_plan(const fasn_kvcache_args* args, KvVariant variant, const void* operand, char* buf, size_t cap) {
     if (args == nullptr || buf == nullptr || cap == 0) return FASN_EINVAL;
     LaunchLog log{buf, cap, 0};
     buf[0] = 0;
     LaunchLog* const outer = t_launch_log;
     t_launch_log = &log;
-    const int rc = kv_forward(args, alibi, with_alibi, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
+    const int rc = kv_forward(args, variant, operand, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
     t_launch_log = outer;
     if (rc) return rc;
     return log.len > cap ? FASN_EINVAL : (int)log.len;
@@ -175,11 +192,22 @@ size_t fasn_fwd_kvcache_workspace_bytes(const fasn_kvcache_args* args) {
 }
 
 int fasn_fwd_kvcache(const fasn_kvcache_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kv_forward(args, nullptr, false, workspace, workspace_bytes, stream);
+    return kv_forward(args, KV_BASE, nullptr, workspace, workspace_bytes, stream);
 }
 
 int fasn_fwd_kvcache_alibi(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kv_forward(args, alibi, true, workspace, workspace_bytes, stream);
+    return kv_forward(args, KV_ALIBI, alibi, workspace, workspace_bytes, stream);
+}
+
+size_t fasn_fwd_kvcache_window_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_window* window) {
+    KvParams p;
+    KvWindow kw;
+    if (kv_build(args, p) != FASN_OK || kv_build_window(args, window, p, kw) != FASN_OK) return 0;
+    return kv_ws_bytes(p, args->D);
+}
+
+int fasn_fwd_kvcache_window(const fasn_kvcache_args* args, const fasn_kv_window* window, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return kv_forward(args, KV_WINDOW, window, workspace, workspace_bytes, stream);
 }
 
 int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
@@ -204,10 +232,14 @@ int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, 
     }
 }
 
-int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) { return kv_plan(args, nullptr, false, buf, cap); }
+int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) { return kv_plan(args, KV_BASE, nullptr, buf, cap); }
 
 int fasn_kvcache_alibi_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap) {
-    return kv_plan(args, alibi, true, buf, cap);
+    return kv_plan(args, KV_ALIBI, alibi, buf, cap);
+}
+
+int fasn_kvcache_window_plan(const fasn_kvcache_args* args, const fasn_kv_window* window, char* buf, size_t cap) {
+    return kv_plan(args, KV_WINDOW, window, buf, cap);
 }
 
 }  // extern "C"

@@ -1,8 +1,11 @@
-// fasn_kvcache_fwd.inc - the text of the decode forward kernel, included by fasn_kvcache.h once per value of FASN_KV_ALIBI (no include
-// guard). With FASN_KV_ALIBI == 0 the preprocessor leaves fasn_kvcache_fwd_kernel exactly as it was before the ALiBi kernels existed.
+// fasn_kvcache_fwd.inc - the text of the decode forward kernel, included by fasn_kvcache.h once per variant (no include guard):
+// FASN_KV_ALIBI / FASN_KV_WINDOW = 0 / 0, 1 / 0, 0 / 1. With both at 0 the preprocessor leaves fasn_kvcache_fwd_kernel exactly as it was
+// before the variants existed, and with FASN_KV_WINDOW == 0 the ALiBi kernel as it was before the window kernel did.
 template <typename Tag, int D>
 #if FASN_KV_ALIBI
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_alibi_kernel(const KvParams p, const KvAlibi al) {
+#elif FASN_KV_WINDOW
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_window_kernel(const KvParams p, const KvWindow win) {
 #else
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(const KvParams p) {
 #endif
@@ -35,8 +38,16 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     // ---- this split's tile range, from the length in device memory
     const int len = kv_len(p, b);
     const int tiles_b = (len + KV_KT - 1) / KV_KT;
+#if FASN_KV_WINDOW
+    // the walk starts at the tile of the first key that the FIRST row's window holds; the splits share [tlo, tiles_b). Tiles below tlo
+    // get no request and no table read: their pages may be gone
+    const int tlo = min(max(0, len - p.Sq - win.w + 1) / KV_KT, tiles_b);
+    const int tps = (tiles_b - tlo + p.nsplit - 1) / p.nsplit;
+    const int t0 = min(tlo + split * tps, tiles_b);
+#else
     const int tps = (tiles_b + p.nsplit - 1) / p.nsplit;
     const int t0 = min(split * tps, tiles_b);
+#endif
     const int t1 = min(t0 + tps, tiles_b);
 
     // ---- the lane's row: query head of the group, position, softmax_n, causal limit
@@ -166,7 +177,12 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
             // the bias is part of the score before the maximum is taken; k0 is the absolute key index in every split
             const float dk0 = (float)(k0 + 4 * hi - qpos);
 #endif
+#if FASN_KV_WINDOW
+            // ... and not below the window of the LAST row, len - W, either: then every row's window holds the whole tile
+            if (k0 + KV_KT - 1 <= all_vis && k0 >= len - win.w) {
+#else
             if (k0 + KV_KT - 1 <= all_vis) {   // wave-uniform (lanes without a row carry zero queries; their state is never stored)
+#endif
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -179,6 +195,13 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
                         mx = fmaxf(mx, sacc[kb][r]);
                     }
             } else {
+#if FASN_KV_WINDOW
+                // vis - W < key <= vis as ONE unsigned compare of the distance vis - key, which is dvis minus the register's literal (a
+                // lane without a row has vis = -1: its distances wrap beyond every W). dvis is made opaque per tile, or the compiler
+                // hoists the 32 loop-invariant parts of the distances out of the loop and keeps them in registers across it.
+                int dvis = vis - k0 - 4 * hi;
+                asm volatile("" : "+v"(dvis));
+#endif
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -186,6 +209,8 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
                         const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
 #if FASN_KV_ALIBI
                         const float y = key <= vis ? __builtin_fmaf(sacc[kb][r], p.c, kv_alibi_term(nslope2, dk0, kb, r)) : -INFINITY;
+#elif FASN_KV_WINDOW
+                        const float y = (unsigned)(dvis - (kb * 32 + (r & 3) + 8 * (r >> 2))) < (unsigned)win.w ? sacc[kb][r] * p.c : -INFINITY;
 #else
                         const float y = key <= vis ? sacc[kb][r] * p.c : -INFINITY;
 #endif

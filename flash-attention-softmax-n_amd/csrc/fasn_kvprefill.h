@@ -6,6 +6,7 @@
 //   fasn_kvprefill_fwd_kernel      one workgroup per (batch element, K/V head, row block, split); with one split it normalises and stores
 //                                  o / lse itself, with several it writes un-normalised partials
 //   fasn_kvprefill_fwd_alibi_kernel  the same kernel with the ALiBi term -slope_h |j - p_i| in the scores (fasn_kvprefill_fwd.inc holds both)
+//   fasn_kvprefill_fwd_window_kernel  the same kernel over the tiles of a sliding window only (fasn_kvcache.h: KvWindow)
 //   fasn_kvprefill_combine_kernel  (several splits only) merges the partials and scatters the rows of the block map
 //
 // Row blocks. A workgroup owns KVP_ROWS = 128 row slots: the G query heads of one K/V head times PB = 128 / G consecutive positions,
@@ -45,13 +46,20 @@ FASN_DEV int kvp_len(const KvPrefillParams& pp, int b, int qlen) {
     return (int)min(max(len, (int64_t)0), (int64_t)pp.kv.capacity);
 }
 
-// fasn_kvprefill_fwd_kernel<Tag, D>(KvPrefillParams) and fasn_kvprefill_fwd_alibi_kernel<Tag, D>(KvPrefillParams, KvAlibi): one text,
-// compiled twice, for the reason fasn_kvcache.h gives.
+// fasn_kvprefill_fwd_kernel<Tag, D>(KvPrefillParams), fasn_kvprefill_fwd_alibi_kernel<Tag, D>(KvPrefillParams, KvAlibi) and
+// fasn_kvprefill_fwd_window_kernel<Tag, D>(KvPrefillParams, KvWindow): one text, compiled three times, for the reason fasn_kvcache.h gives.
+#define FASN_KV_WINDOW 0
 #define FASN_KV_ALIBI 0
 #include "fasn_kvprefill_fwd.inc"
 #undef FASN_KV_ALIBI
 #define FASN_KV_ALIBI 1
 #include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_ALIBI
+#undef FASN_KV_WINDOW
+#define FASN_KV_ALIBI 0
+#define FASN_KV_WINDOW 1
+#include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_WINDOW
 #undef FASN_KV_ALIBI
 
 // Merge the partials of a row slot (the arithmetic of fasn_kvcache_combine_kernel) and scatter it through the block map: slot r of

@@ -1,4 +1,4 @@
-// K/V-cache prefill (include/fasn.h: fasn_fwd_kvprefill[_alibi], fasn_kvprefill_append, fasn_kvprefill[_alibi]_plan): argument checks, the launch plan -
+// K/V-cache prefill (include/fasn.h: fasn_fwd_kvprefill[_alibi|_window], fasn_kvprefill_append, fasn_kvprefill[_alibi|_window]_plan): argument checks, the launch plan -
 // which depends on shapes and capacity only, never on the lengths in device memory - and the launches of fasn_kvprefill.h.
 #include <limits.h>
 #include <math.h>
@@ -85,12 +85,9 @@ int kvp_build(const fasn_kvprefill_args* pa, KvPrefillParams& pp) {
     pp.nrb = (a->Sq + pp.PB - 1) / pp.PB;
     const int64_t base = (int64_t)p.B * p.Hkv * pp.nrb;
     const int64_t cap_tiles = (capacity + KV_KT - 1) / KV_KT;
-    int64_t nsplit = (kv_split_target(a->D) + base - 1) / base;
     // a split costs its partial (128 row slots of D + 2 floats, written and read back: what 4 tiles move) next to its tiles: at least
     // 16 tiles per split of a full cache (the decode rule at 128 rows)
-    const int64_t min_tps = KVP_ROWS / 8;
-    if (nsplit > cap_tiles / min_tps) nsplit = cap_tiles / min_tps;
-    p.nsplit = nsplit < 1 ? 1 : (int)nsplit;
+    p.nsplit = (int)kv_nsplit(a->D, base, cap_tiles, KVP_ROWS / 8);
     if (base * p.nsplit > INT_MAX / KVP_ROWS) return FASN_EINVAL;
     return FASN_OK;
 }
@@ -108,12 +105,28 @@ int kvp_build_alibi(const fasn_kvcache_args* a, const fasn_alibi_slopes* s, KvAl
     return FASN_OK;
 }
 
-// (al == nullptr: the kernel without a bias; otherwise its ALiBi sibling on the same grid, LDS and workspace)
+// The window operand of the *_window entry points (checked after the base arguments, before any HIP call), and the plan under it: the
+// base rule over the tiles a row block's window can touch, never more splits than the base plan has.
+int kvp_build_window(const fasn_kvcache_args* a, const fasn_kv_window* w, KvPrefillParams& pp, KvWindow& kw) {
+    KvParams& p = pp.kv;
+    if (w == nullptr || w->window < 1 || w->reserved != 0) return FASN_EINVAL;
+    if (!a->causal) return FASN_EUNSUPPORTED;
+    kw = KvWindow{w->window < p.capacity ? w->window : p.capacity};
+    const int64_t cap_tiles = ((int64_t)p.capacity + KV_KT - 1) / KV_KT;
+    p.nsplit = (int)kv_nsplit(a->D, (int64_t)p.B * p.Hkv * pp.nrb, kv_window_tiles(cap_tiles, w->window, pp.PB), KVP_ROWS / 8);
+    return FASN_OK;
+}
+
+// (al == kw == nullptr: the base kernel; otherwise its ALiBi sibling on the same grid, LDS and workspace, or its window sibling)
 template <typename Tag, int D>
-int kvp_launch_fwd(const KvPrefillParams& pp, const KvAlibi* al, hipStream_t s) {
+int kvp_launch_fwd(const KvPrefillParams& pp, const KvAlibi* al, const KvWindow* kw, hipStream_t s) {
     const KvParams& p = pp.kv;
     constexpr int smem = kv_smem(D);
-    if (al == nullptr) {
+    if (kw != nullptr) {
+        constexpr auto kern = &fasn_kvprefill_fwd_window_kernel<Tag, D>;
+        ensure_smem<kern>(smem);
+        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit)), dim3(256), smem, s, pp, *kw);
+    } else if (al == nullptr) {
         constexpr auto kern = &fasn_kvprefill_fwd_kernel<Tag, D>;
         ensure_smem<kern>(smem);
         FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit)), dim3(256), smem, s, pp);
@@ -137,21 +150,23 @@ int kvp_launch_append(const KvPrefillParams& pp, hipStream_t s) {
 }
 
 template <typename Tag>
-int kvp_launch_fwd_d(int D, const KvPrefillParams& pp, const KvAlibi* al, hipStream_t s) {   // (kvp_build let only these four through)
+int kvp_launch_fwd_d(int D, const KvPrefillParams& pp, const KvAlibi* al, const KvWindow* kw, hipStream_t s) {   // (kvp_build let only these four through)
     switch (D) {
-        case 32: return kvp_launch_fwd<Tag, 32>(pp, al, s);
-        case 64: return kvp_launch_fwd<Tag, 64>(pp, al, s);
-        case 128: return kvp_launch_fwd<Tag, 128>(pp, al, s);
-        default: return kvp_launch_fwd<Tag, 256>(pp, al, s);
+        case 32: return kvp_launch_fwd<Tag, 32>(pp, al, kw, s);
+        case 64: return kvp_launch_fwd<Tag, 64>(pp, al, kw, s);
+        case 128: return kvp_launch_fwd<Tag, 128>(pp, al, kw, s);
+        default: return kvp_launch_fwd<Tag, 256>(pp, al, kw, s);
     }
 }
 
-int kvp_forward(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+int kvp_forward(const fasn_kvprefill_args* args, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
     KvPrefillParams pp;
     int rc = kvp_build(args, pp);
     if (rc) return rc;
     KvAlibi al{};
-    if (with_alibi && (rc = kvp_build_alibi(&args->kv, alibi, al))) return rc;
+    KvWindow kw{};
+    if (variant == KV_ALIBI && (rc = kvp_build_alibi(&args->kv, static_cast<const fasn_alibi_slopes*>(operand), al))) return rc;
+    if (variant == KV_WINDOW && (rc = kvp_build_window(&args->kv, static_cast<const fasn_kv_window*>(operand), pp, kw))) return rc;
     const int D = args->kv.D;
     const size_t need = kvp_ws_bytes(pp, D);
     if (need > 0) {   // (one split: nothing is written beside o / lse, a NULL workspace is fine)
@@ -161,18 +176,19 @@ int kvp_forward(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi,
         pp.kv.part_ml = pp.kv.part_o + (size_t)pp.kv.B * pp.kv.Hkv * pp.nrb * pp.kv.nsplit * KVP_ROWS * D;
     }
     hipStream_t s = (hipStream_t)stream;
-    const KvAlibi* const alp = with_alibi ? &al : nullptr;
-    if (args->kv.dtype == FASN_DTYPE_BF16) return kvp_launch_fwd_d<bf16_tag>(D, pp, alp, s);
-    return kvp_launch_fwd_d<f16_tag>(D, pp, alp, s);
+    const KvAlibi* const alp = variant == KV_ALIBI ? &al : nullptr;
+    const KvWindow* const kwp = variant == KV_WINDOW ? &kw : nullptr;
+    if (args->kv.dtype == FASN_DTYPE_BF16) return kvp_launch_fwd_d<bf16_tag>(D, pp, alp, kwp, s);
+    return kvp_launch_fwd_d<f16_tag>(D, pp, alp, kwp, s);
 }
 
-int kvp_plan(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, bool with_alibi, char* buf, size_t cap) {
+int kvp_plan(const fasn_kvprefill_args* args, KvVariant variant, const void* operand, char* buf, size_t cap) {
     if (args == nullptr || buf == nullptr || cap == 0) return FASN_EINVAL;
     LaunchLog log{buf, cap, 0};
     buf[0] = 0;
     LaunchLog* const outer = t_launch_log;
     t_launch_log = &log;
-    const int rc = kvp_forward(args, alibi, with_alibi, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
+    const int rc = kvp_forward(args, variant, operand, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
     t_launch_log = outer;
     if (rc) return rc;
     return log.len > cap ? FASN_EINVAL : (int)log.len;
@@ -192,11 +208,22 @@ size_t fasn_fwd_kvprefill_workspace_bytes(const fasn_kvprefill_args* args) {
 }
 
 int fasn_fwd_kvprefill(const fasn_kvprefill_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kvp_forward(args, nullptr, false, workspace, workspace_bytes, stream);
+    return kvp_forward(args, KV_BASE, nullptr, workspace, workspace_bytes, stream);
 }
 
 int fasn_fwd_kvprefill_alibi(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kvp_forward(args, alibi, true, workspace, workspace_bytes, stream);
+    return kvp_forward(args, KV_ALIBI, alibi, workspace, workspace_bytes, stream);
+}
+
+size_t fasn_fwd_kvprefill_window_workspace_bytes(const fasn_kvprefill_args* args, const fasn_kv_window* window) {
+    KvPrefillParams pp;
+    KvWindow kw;
+    if (kvp_build(args, pp) != FASN_OK || kvp_build_window(&args->kv, window, pp, kw) != FASN_OK) return 0;
+    return kvp_ws_bytes(pp, args->kv.D);
+}
+
+int fasn_fwd_kvprefill_window(const fasn_kvprefill_args* args, const fasn_kv_window* window, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return kvp_forward(args, KV_WINDOW, window, workspace, workspace_bytes, stream);
 }
 
 int fasn_kvprefill_append(const fasn_kvprefill_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
@@ -221,10 +248,14 @@ int fasn_kvprefill_append(const fasn_kvprefill_args* args, const fasn_view4* k_n
     }
 }
 
-int fasn_kvprefill_plan(const fasn_kvprefill_args* args, char* buf, size_t cap) { return kvp_plan(args, nullptr, false, buf, cap); }
+int fasn_kvprefill_plan(const fasn_kvprefill_args* args, char* buf, size_t cap) { return kvp_plan(args, KV_BASE, nullptr, buf, cap); }
 
 int fasn_kvprefill_alibi_plan(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap) {
-    return kvp_plan(args, alibi, true, buf, cap);
+    return kvp_plan(args, KV_ALIBI, alibi, buf, cap);
+}
+
+int fasn_kvprefill_window_plan(const fasn_kvprefill_args* args, const fasn_kv_window* window, char* buf, size_t cap) {
+    return kvp_plan(args, KV_WINDOW, window, buf, cap);
 }
 
 }  // extern "C"

@@ -1,8 +1,11 @@
-// fasn_kvprefill_fwd.inc - the text of the prefill forward kernel, included by fasn_kvprefill.h once per value of FASN_KV_ALIBI (no
-// include guard). With FASN_KV_ALIBI == 0 the preprocessor leaves fasn_kvprefill_fwd_kernel exactly as it was before the ALiBi kernels existed.
+// fasn_kvprefill_fwd.inc - the text of the prefill forward kernel, included by fasn_kvprefill.h once per variant (no include guard):
+// FASN_KV_ALIBI / FASN_KV_WINDOW = 0 / 0, 1 / 0, 0 / 1. With both at 0 the preprocessor leaves fasn_kvprefill_fwd_kernel exactly as it
+// was before the variants existed, and with FASN_KV_WINDOW == 0 the ALiBi kernel as it was before the window kernel did.
 template <typename Tag, int D>
 #if FASN_KV_ALIBI
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_alibi_kernel(const KvPrefillParams pp, const KvAlibi al) {
+#elif FASN_KV_WINDOW
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_window_kernel(const KvPrefillParams pp, const KvWindow win) {
 #else
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kernel(const KvPrefillParams pp) {
 #endif
@@ -65,8 +68,16 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     const int pos_hi = min(pos0 + pp.PB, qlen) - 1;
     const int kend = p.causal ? max(0, min(len, pos_hi + len - qlen + 1)) : len;
     const int tiles_b = (kend + KV_KT - 1) / KV_KT;
+#if FASN_KV_WINDOW
+    // the walk starts at the tile of the first key that the window of the block's FIRST position holds; the splits share
+    // [tlo, tiles_b). Tiles below tlo get no request and no table read: their pages may be gone
+    const int tlo = min(max(0, pos0 + len - qlen - win.w + 1) / KV_KT, tiles_b);
+    const int tps = (tiles_b - tlo + p.nsplit - 1) / p.nsplit;
+    const int t0 = min(tlo + split * tps, tiles_b);
+#else
     const int tps = (tiles_b + p.nsplit - 1) / p.nsplit;
     const int t0 = min(split * tps, tiles_b);
+#endif
     const int t1 = min(t0 + tps, tiles_b);
 
     float n_row = p.n;
@@ -210,18 +221,32 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 #endif
             // raw scores (times ce: log2 domain); hidden keys (beyond the row's limit, which is below len_b) go to -inf
             float mx = -INFINITY;
+#if FASN_KV_WINDOW
+            // ... and not below the window of the block's LAST real position either: then every row's window holds the whole tile
+            if (k0 + KV_KT - 1 <= all_vis && k0 > pos_hi + len - qlen - win.w) {
+#else
             if (k0 + KV_KT - 1 <= all_vis) {   // block-uniform (padding slots carry zero queries; their state is never stored)
+#endif
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
             } else {
+#if FASN_KV_WINDOW
+                // vis - W < key <= vis as one unsigned compare of the distance dvis - literal, dvis opaque per tile (fasn_kvcache_fwd.inc)
+                int dvis = vis - k0 - 4 * hi;
+                asm volatile("" : "+v"(dvis));
+#endif
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
+#if FASN_KV_WINDOW
+                        const float y = (unsigned)(dvis - (kb * 32 + (r & 3) + 8 * (r >> 2))) < (unsigned)win.w ? sacc[kb][r] : -INFINITY;
+#else
                         const float y = key <= vis ? sacc[kb][r] : -INFINITY;
+#endif
                         sacc[kb][r] = y;
                         mx = fmaxf(mx, y);
                     }

@@ -7,6 +7,8 @@ synchronisation, the launches depend on shapes and capacity only - so a call can
 while `cache_seqlens`, `query_seqlens`, `block_table`, the cache and `query` change in place. Prompt -> chunked prefill -> decode runs on
 the paged cache alone. `alibi_slopes` on both calls adds -slope[b, h] * |p_i - j| to the logits inside the kernels (fasn_fwd_kvcache_alibi /
 fasn_fwd_kvprefill_alibi): p_i comes from the lengths in device memory, so no bias tensor exists and the graph stays one graph.
+flash_attention_n_kvcache_window is a sliding-window layer on the same cache (fasn_fwd_kvcache_window / fasn_fwd_kvprefill_window): the
+window is a host integer, the kernels walk the window's tiles only and never touch the pages below it.
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -16,7 +18,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs
+from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs, KvWindow
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
@@ -286,6 +288,91 @@ def flash_attention_n_kvcache_prefill(
             _lib.check(lib.fasn_fwd_kvprefill(pa, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill")
         else:   # (the same launches and workspace; the forward kernel's ALiBi sibling)
             _lib.check(lib.fasn_fwd_kvprefill_alibi(pa, alibi, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill_alibi")
+
+    if _current_device() == dev.index:
+        launch()
+    else:
+        with torch.cuda.device(dev):
+            launch()
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_n_kvcache_window(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        window: int,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        query_seqlens: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        return_lse: bool = False):
+    """softmax_n attention of a SLIDING-WINDOW layer against a K/V cache, on MI355X: decode, chunked prefill or prefill in one call.
+
+    Always causal. With qlen_b = clamp(query_seqlens[b], 0, Sq) (None: Sq), len_b = clamp(cache_seqlens[b] + (qlen_b if k_new is given
+    else 0), 0, capacity) and p_i = i + len_b - qlen_b the absolute position of query i, position i < qlen_b sees key j iff
+    j < len_b and p_i - window < j <= p_i: `window` keys, its own included (Hugging Face `sliding_window`, GPT-OSS, Mistral).
+    The cache, `block_table`, `cache_seqlens`, `k_new` / `v_new`, `query_seqlens`, `softmax_n_param`, `scale`, dtypes, head dims,
+    alignment rules and refusals are those of flash_attention_n_kvcache_prefill. What differs:
+
+    :param window: a Python int >= 1, a constant of the layer: it is part of a captured graph, while the lengths stay on the device. A
+                  window at or beyond the capacity sees what the call without a window sees.
+    :param query_seqlens: as in flash_attention_n_kvcache_prefill. The kernels are chosen by shapes alone (capturable): with
+                  query_seqlens=None and (H // Hkv) * Sq <= 128 the decode kernels run, otherwise the prefill kernels; both give the
+                  same function.
+    :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32 over the visible keys plus n). A position that sees no key
+             (p_i < 0) gives exactly 0 and lse = log n (-inf for n = 0); padding positions i >= qlen_b give exactly 0 and lse = -inf.
+
+    Memory contract. Let first_b = 64 * floor(max(0, len_b - qlen_b - window + 1) / 64). Cache rows j < first_b are never read, and
+    neither are the block-table entries of pages that lie wholly below first_b: both may hold anything (NaN, a freed page, a page that
+    was handed to another sequence), so a server may free every page wholly below the window. Rows first_b .. len_b - 1 are read in
+    tiles of 64 keys and must hold finite values (they are rows an earlier append wrote). Rows at or beyond len_b may hold anything,
+    as in the other cache calls. The work and the K/V traffic follow the window, not the length.
+    """
+    fn = "flash_attention_n_kvcache_window"
+    if isinstance(window, bool) or not isinstance(window, int):
+        raise TypeError(f"{fn}: window must be a Python int (a constant of the layer, part of a captured graph; never a tensor); "
+                        f"got {type(window).__name__}")
+    if window < 1:
+        raise ValueError(f"{fn}: window must be >= 1 (the keys a position sees, its own included); got {window}")
+    if query_seqlens is not None:
+        B = query.shape[0] if query.dim() == 4 else -1
+        if (not isinstance(query_seqlens, Tensor) or query_seqlens.dtype != torch.int32 or query_seqlens.dim() != 1 or query_seqlens.shape[0] != B
+                or not query_seqlens.is_contiguous()):
+            got = f"{query_seqlens.dtype} {tuple(query_seqlens.shape)}" if isinstance(query_seqlens, Tensor) else type(query_seqlens).__name__
+            raise ValueError(f"query_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {got}")
+        if query_seqlens.device != query.device:
+            raise RuntimeError(f"query_seqlens is on {query_seqlens.device}, query on {query.device}: every operand must live on the query's "
+                               "device (the lengths are read by the kernels, never on the host)")
+    if query.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and query.shape[1] // k_cache.shape[2] > 128 and query.shape[1] % k_cache.shape[2] == 0:
+        raise ValueError(f"{fn}: {query.shape[1] // k_cache.shape[2]} query heads per K/V head are not supported (at most 128: the heads of a "
+                         "K/V head share one workgroup)")
+    pa = KvPrefillArgs()   # (its first member is the decode call's argument block)
+    a, out, lse, k_new, v_new, _keep, _alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                                                        softmax_n_param, scale, True, return_lse, args=pa.kv)
+    pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
+    decode = query_seqlens is None and a.kv_group * a.Sq <= _MAX_ROWS
+    win = KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
+    lib = _lib.load()
+    dev = query.device
+
+    def launch():
+        stream = _stream_ptr(dev)
+        if decode:
+            if k_new is not None:
+                _lib.check(lib.fasn_kvcache_append(a, _view4(k_new), _view4(v_new), stream), "fasn_kvcache_append")
+            ws_bytes = lib.fasn_fwd_kvcache_window_workspace_bytes(a, win)
+            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (torch's caching allocator: capturable)
+            _lib.check(lib.fasn_fwd_kvcache_window(a, win, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache_window")
+            return
+        if k_new is not None:
+            _lib.check(lib.fasn_kvprefill_append(pa, _view4(k_new), _view4(v_new), stream), "fasn_kvprefill_append")
+        ws_bytes = lib.fasn_fwd_kvprefill_window_workspace_bytes(pa, win)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None   # (one split: no partials, no workspace)
+        _lib.check(lib.fasn_fwd_kvprefill_window(pa, win, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill_window")
 
     if _current_device() == dev.index:
         launch()

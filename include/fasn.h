@@ -233,7 +233,7 @@ int fasn_bwd_path(const fasn_bwd_args* args);
  * Forward over a K/V CACHE (inference; additions within ABI 6, no counterpart in the reference, which has no cache): attention of a few new
  * query positions per batch element (Sq = 1: decode) against keys that live in a paged or dense cache whose valid LENGTHS ARE IN DEVICE
  * MEMORY. Nothing about the lengths or the block table is read on the host: the launches depend on shapes and capacity only, so one
- * captured HIP graph serves every step of a generation while the sequences grow. Forward only; no mask, no dropout, no bias other than the ALiBi slopes of the *_alibi calls below.
+ * captured HIP graph serves every step of a generation while the sequences grow. Forward only; no mask other than the sliding window of the *_window calls below, no dropout, no bias other than the ALiBi slopes of the *_alibi calls.
  *
  *   cache     key j of batch element b is row j % page_size of page block_table[b * block_table_stride + j / page_size]; element
  *             (page, row, K/V head hk, feature d) of K sits at k_cache + (page * k_stride[0] + row * k_stride[1] + hk * k_stride[2] + d)
@@ -341,6 +341,41 @@ int fasn_fwd_kvcache_alibi(const fasn_kvcache_args* args, const fasn_alibi_slope
 int fasn_fwd_kvprefill_alibi(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
 int fasn_kvcache_alibi_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap);
 int fasn_kvprefill_alibi_plan(const fasn_kvprefill_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap);
+
+/*
+ * SLIDING WINDOW on the cache calls (additions within ABI 6; the argument blocks above keep their layouts): always causal, position
+ *     p_i = i + len_b - qlen_b      (decode: qlen_b = Sq; len_b / qlen_b as the base call defines them, clamps and append included)
+ * sees key j iff j < len_b and p_i - window < j <= p_i: `window` keys, the position's own included (Hugging Face sliding_window,
+ * GPT-OSS, Mistral). `window` is a host integer >= 1 - a per-layer constant, part of a captured graph - while the lengths stay in device
+ * memory. softmax_n, `n`, scale and lse are the base call's: lse covers the visible keys plus n, a position that sees no key (p_i < 0)
+ * gives 0 and lse = log n, padding positions give 0 and -inf.
+ *
+ * MEMORY CONTRACT. With first_b = 64 * floor(max(0, len_b - qlen_b - window + 1) / 64):
+ *   - cache rows j < first_b are never read, and neither are the block-table entries of pages that lie wholly below first_b: both may
+ *     hold anything (NaN, a freed page, a page that serves somebody else) - a server may free every page wholly below the window;
+ *   - rows first_b .. len_b - 1 are read in tiles of 64 keys and must hold finite values (they are rows an earlier append wrote);
+ *   - rows at or beyond len_b keep the base call's rule: out of range for the tile's descriptor, they arrive as zeros.
+ *
+ * fasn_fwd_kvcache_window / fasn_fwd_kvprefill_window are fasn_fwd_kvcache / fasn_fwd_kvprefill with the operand: forward kernels of
+ * their own, the same combine kernels, the appends of the base calls. The plan uses the window - a workgroup walks at most
+ * ceil((window + span - 1) / 64) + 1 tiles (span = Sq, prefill: 128 / kv_group), which takes the place of the capacity's tiles in the
+ * split rule - so the workspace is fasn_fwd_kv{cache,prefill}_window_workspace_bytes(args, window), never more than the base call's
+ * (prefill: 0 with one split). A window >= capacity gives the base plan under the window kernels' names. Every rule and error code of the
+ * base call holds and is checked first; then window == NULL, window->window < 1 or reserved != 0 is FASN_EINVAL and args->causal == 0
+ * FASN_EUNSUPPORTED; any window >= 1 is legal (one beyond the capacity acts as the capacity). There is no window + ALiBi call. The
+ * *_window_plan calls are fasn_kvcache_plan / fasn_kvprefill_plan for these launches.
+ */
+typedef struct fasn_kv_window {
+    int32_t window;              /* keys a position sees, its own included; >= 1 */
+    int32_t reserved;            /* 0 */
+} fasn_kv_window;
+
+size_t fasn_fwd_kvcache_window_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_window* window);
+int fasn_fwd_kvcache_window(const fasn_kvcache_args* args, const fasn_kv_window* window, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvcache_window_plan(const fasn_kvcache_args* args, const fasn_kv_window* window, char* buf, size_t cap);
+size_t fasn_fwd_kvprefill_window_workspace_bytes(const fasn_kvprefill_args* args, const fasn_kv_window* window);
+int fasn_fwd_kvprefill_window(const fasn_kvprefill_args* args, const fasn_kv_window* window, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvprefill_window_plan(const fasn_kvprefill_args* args, const fasn_kv_window* window, char* buf, size_t cap);
 
 /*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
