@@ -29,6 +29,7 @@ EXPORTS = (
     "fasn_fwd_kvcache_alibi", "fasn_fwd_kvprefill_alibi", "fasn_kvcache_alibi_plan", "fasn_kvprefill_alibi_plan",
     "fasn_fwd_kvcache_window_workspace_bytes", "fasn_fwd_kvcache_window", "fasn_kvcache_window_plan",
     "fasn_fwd_kvprefill_window_workspace_bytes", "fasn_fwd_kvprefill_window", "fasn_kvprefill_window_plan",
+    "fasn_kvcache_rope_append", "fasn_kvprefill_rope_append", "fasn_kvcache_rope_append_plan", "fasn_kvprefill_rope_append_plan",
 )
 
 
@@ -90,6 +91,12 @@ class AlibiSlopes(Structure):
 class KvWindow(Structure):
     """fasn_kv_window (include/fasn.h): the sliding window of the *_window cache calls, a host integer >= 1; reserved = 0"""
     _fields_ = [("window", c_int32), ("reserved", c_int32)]
+
+
+class KvRope(Structure):
+    """fasn_kv_rope (include/fasn.h): the cos / sin tables of the rotary rotate-and-append calls, [rows, rotary_dim / 2] in device memory"""
+    _fields_ = [("cos", c_void_p), ("sin", c_void_p), ("row_stride", c_int64), ("rows", c_int32), ("rotary_dim", c_int32),
+                ("table_dtype", c_int32), ("interleaved", c_int32)]
 
 
 class FasnError(RuntimeError):
@@ -183,6 +190,14 @@ def load():
     lib.fasn_fwd_kvprefill_window.argtypes = [POINTER(KvPrefillArgs), POINTER(KvWindow), c_void_p, c_size_t, c_void_p]
     lib.fasn_kvprefill_window_plan.restype = c_int32
     lib.fasn_kvprefill_window_plan.argtypes = [POINTER(KvPrefillArgs), POINTER(KvWindow), c_char_p, c_size_t]
+    lib.fasn_kvcache_rope_append.restype = c_int32
+    lib.fasn_kvcache_rope_append.argtypes = [POINTER(KvCacheArgs), POINTER(KvRope), POINTER(View4), POINTER(View4), POINTER(View4), c_void_p]
+    lib.fasn_kvprefill_rope_append.restype = c_int32
+    lib.fasn_kvprefill_rope_append.argtypes = [POINTER(KvPrefillArgs), POINTER(KvRope), POINTER(View4), POINTER(View4), POINTER(View4), c_void_p]
+    lib.fasn_kvcache_rope_append_plan.restype = c_int32
+    lib.fasn_kvcache_rope_append_plan.argtypes = [POINTER(KvCacheArgs), POINTER(KvRope), POINTER(View4), POINTER(View4), POINTER(View4), c_char_p, c_size_t]
+    lib.fasn_kvprefill_rope_append_plan.restype = c_int32
+    lib.fasn_kvprefill_rope_append_plan.argtypes = [POINTER(KvPrefillArgs), POINTER(KvRope), POINTER(View4), POINTER(View4), POINTER(View4), c_char_p, c_size_t]
     ver = lib.fasn_abi_version()
     if ver != FASN_ABI_VERSION:
         raise ImportError(f"libfasn ABI version {ver} != expected {FASN_ABI_VERSION}; rebuild csrc/")
@@ -273,6 +288,17 @@ def kvprefill_window_plan(args, win):
     rc = load().fasn_kvprefill_window_plan(args, win, buf, len(buf))
     if rc < 0:
         check(rc, "fasn_kvprefill_window_plan")
+    return _plan_lines(buf)
+
+
+def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):
+    """The one launch of fasn_kvcache_rope_append (`args` a KvCacheArgs) or fasn_kvprefill_rope_append (a KvPrefillArgs) under `rope`
+    (a KvRope), as launch_plan returns it. Nothing is launched."""
+    buf = ctypes.create_string_buffer(4096)
+    what = "fasn_kvprefill_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_rope_append_plan"
+    rc = getattr(load(), what)(args, rope, q_out, k_new, v_new, buf, len(buf))
+    if rc < 0:
+        check(rc, what)
     return _plan_lines(buf)
 
 

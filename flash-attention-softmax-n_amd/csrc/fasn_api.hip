@@ -47,6 +47,7 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
         {"fasn_kvprefill_fwd_kernel", "T D"},
         {"fasn_kvprefill_combine_kernel", "T D"},
         {"fasn_kvprefill_append_kernel", "D"},
+        {"fasn_kvrope_kernel", "T D"},
     };
     static const char* const modes[] = {"plain", "causal", "bias+mask", "element-load", "bias", "mask", "keypad", "bias+keypad"};
     if (cap == 0) return 0;

@@ -179,6 +179,10 @@ int kv_plan(const fasn_kvcache_args* args, KvVariant variant, const void* operan
 }
 
 }  // namespace
+
+// the validation and parameter packing above, for the rotary rotate-and-append call (fasn_kvrope.h declares it, fasn_kvrope.hip calls it)
+int kv_build_params(const fasn_kvcache_args* a, KvParams& p) { return kv_build(a, p); }
+
 }  // namespace fasn
 
 using namespace fasn;

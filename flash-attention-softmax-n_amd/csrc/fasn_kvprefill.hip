@@ -195,6 +195,10 @@ int kvp_plan(const fasn_kvprefill_args* args, KvVariant variant, const void* ope
 }
 
 }  // namespace
+
+// the validation and parameter packing above, for the rotary rotate-and-append call (fasn_kvrope.h declares it, fasn_kvrope.hip calls it)
+int kvp_build_params(const fasn_kvprefill_args* pa, KvPrefillParams& pp) { return kvp_build(pa, pp); }
+
 }  // namespace fasn
 
 using namespace fasn;

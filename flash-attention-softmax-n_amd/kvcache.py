@@ -9,6 +9,8 @@ the paged cache alone. `alibi_slopes` on both calls adds -slope[b, h] * |p_i - j
 fasn_fwd_kvprefill_alibi): p_i comes from the lengths in device memory, so no bias tensor exists and the graph stays one graph.
 flash_attention_n_kvcache_window is a sliding-window layer on the same cache (fasn_fwd_kvcache_window / fasn_fwd_kvprefill_window): the
 window is a host integer, the kernels walk the window's tiles only and never touch the pages below it.
+flash_attention_n_kvcache_rope rotates `query` and `k_new` by their absolute positions (RoPE) inside the append launch
+(fasn_kvcache_rope_append / fasn_kvprefill_rope_append): the positions come from the lengths in device memory, so the step stays one graph.
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -18,7 +20,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs, KvWindow
+from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs, KvRope, KvWindow
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
@@ -373,6 +375,152 @@ def flash_attention_n_kvcache_window(
         ws_bytes = lib.fasn_fwd_kvprefill_window_workspace_bytes(pa, win)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None   # (one split: no partials, no workspace)
         _lib.check(lib.fasn_fwd_kvprefill_window(pa, win, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill_window")
+
+    if _current_device() == dev.index:
+        launch()
+    else:
+        with torch.cuda.device(dev):
+            launch()
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_n_kvcache_rope(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        rotary_cos: Tensor,
+        rotary_sin: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        query_seqlens: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False,
+        window: Optional[int] = None,
+        rotary_interleaved: bool = False):
+    """softmax_n attention against a K/V cache with ROTARY POSITION EMBEDDING applied to `query` and `k_new` on the way, on MI355X: one
+    step of a Llama / Mistral / GPT-OSS layer - rotate, append, attend - in the launches of the plain call with `k_new`.
+
+    With qlen_b = clamp(query_seqlens[b], 0, Sq) (None: Sq) and len_b = clamp(cache_seqlens[b] + (qlen_b if k_new is given else 0), 0,
+    capacity), ONE launch rotates row i < qlen_b of k_new[b] at position cache_seqlens[b] + i into the cache (positions at or beyond the
+    capacity are dropped), copies v_new beside it and rotates query position i at p_i = i + len_b - qlen_b - the absolute position the
+    ALiBi and window calls use - into a temporary the forward then reads. The positions come from the lengths in device memory: nothing
+    is read on the host, a captured graph follows `cache_seqlens` / `query_seqlens`. The cache, `block_table`, `cache_seqlens`, `k_new` /
+    `v_new`, `query_seqlens`, `softmax_n_param`, `scale`, dtypes, head dims, alignment rules and refusals are those of
+    flash_attention_n_kvcache_prefill; the kernels are chosen by shapes alone as in flash_attention_n_kvcache_window (query_seqlens=None and
+    (H // Hkv) * Sq <= 128: the decode kernels). What differs:
+
+    :param rotary_cos, rotary_sin: [rows, rotary_dim / 2] on the query's device, fp32 or the dtype of `query`, unit column stride, rows
+                  16-byte aligned (never copied: pass a slice of a longer table as it is); rows >= capacity, 16 <= rotary_dim <= D,
+                  rotary_dim % 16 == 0. Features d >= rotary_dim pass through. The row read is clamp(position, 0, rows - 1): the clamp acts
+                  only on the negative p_i of causal rows that see no key. YaRN / NTK scaling and an attention factor live in the tables.
+    :param k_new, v_new: optional. Without them only `query` is rotated, at p_i = i + len_b - qlen_b over the cache as it is.
+    :param window: None: flash_attention_n_kvcache / _prefill's attention; a Python int >= 1: flash_attention_n_kvcache_window's (needs
+                  is_causal=True).
+    :param rotary_interleaved: False: the half-split layout (GPT-NeoX / Llama / GPT-OSS, Hugging Face rotate_half) - the pair of feature
+                  d < rotary_dim / 2 is (x[d], x[d + rotary_dim / 2]); True: GPT-J - the pair is (x[2 d], x[2 d + 1]). Both use cos[pos, d]:
+                  y1 = x1 cos - x2 sin, y2 = x2 cos + x1 sin.
+    :return: as the call without rotary. `query`, `k_new`, `cache_seqlens` are not modified.
+
+    Arithmetic: operands widened to fp32, every product and the sum rounded to fp32 on their own (no fused multiply-add), one rounding
+    to the 16-bit type - bit for bit (x1.float() * cos.float() - x2.float() * sin.float()).to(dtype) of eager torch. No ALiBi slopes here
+    (a model uses one or the other), no explicit position tensor, no gradient.
+    """
+    fn = "flash_attention_n_kvcache_rope"
+    if window is not None:
+        if isinstance(window, bool) or not isinstance(window, int):
+            raise TypeError(f"{fn}: window must be None or a Python int (a constant of the layer, part of a captured graph; never a tensor); "
+                            f"got {type(window).__name__}")
+        if window < 1:
+            raise ValueError(f"{fn}: window must be >= 1 (the keys a position sees, its own included); got {window}")
+        if not is_causal:
+            raise ValueError(f"{fn}: a sliding window is always causal; window={window} needs is_causal=True")
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if not isinstance(t, Tensor) or t.dim() != 2:
+            got = tuple(t.shape) if isinstance(t, Tensor) else type(t).__name__
+            raise ValueError(f"{fn}: {name} must be a [rows, rotary_dim / 2] tensor; got {got}")
+    if rotary_cos.shape != rotary_sin.shape or rotary_cos.dtype != rotary_sin.dtype or rotary_cos.stride(0) != rotary_sin.stride(0):
+        raise ValueError(f"{fn}: rotary_cos and rotary_sin must have one shape, dtype and row stride; got {tuple(rotary_cos.shape)} "
+                         f"{rotary_cos.dtype} and {tuple(rotary_sin.shape)} {rotary_sin.dtype}")
+    if rotary_cos.dtype != torch.float32 and rotary_cos.dtype != query.dtype:
+        raise ValueError(f"{fn}: rotary_cos / rotary_sin must be float32 or the dtype of query ({query.dtype}); got {rotary_cos.dtype}")
+    if query_seqlens is not None:
+        B = query.shape[0] if query.dim() == 4 else -1
+        if (not isinstance(query_seqlens, Tensor) or query_seqlens.dtype != torch.int32 or query_seqlens.dim() != 1 or query_seqlens.shape[0] != B
+                or not query_seqlens.is_contiguous()):
+            got = f"{query_seqlens.dtype} {tuple(query_seqlens.shape)}" if isinstance(query_seqlens, Tensor) else type(query_seqlens).__name__
+            raise ValueError(f"query_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {got}")
+        if query_seqlens.device != query.device:
+            raise RuntimeError(f"query_seqlens is on {query_seqlens.device}, query on {query.device}: every operand must live on the query's "
+                               "device (the lengths are read by the kernels, never on the host)")
+    if query.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and query.shape[1] // k_cache.shape[2] > 128 and query.shape[1] % k_cache.shape[2] == 0:
+        raise ValueError(f"{fn}: {query.shape[1] // k_cache.shape[2]} query heads per K/V head are not supported (at most 128: the heads of a "
+                         "K/V head share one workgroup)")
+    rows, rd = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
+    esize = rotary_cos.element_size()
+
+    if query.dim() == 4 and k_cache.dim() == 4 and (block_table is None or (isinstance(block_table, Tensor) and block_table.dim() == 2)):
+        # the table checks need no device: here, in front of _prepare and its CPU-tensor refusal (malformed shapes are _prepare's to name)
+        D = query.shape[3]
+        capacity = k_cache.shape[1] * (1 if block_table is None else block_table.shape[1])
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if t.device != query.device:
+                raise RuntimeError(f"{name} is on {t.device}, query on {query.device}: every operand must live on the query's device "
+                                   "(the tables are read by the kernels, never on the host)")
+        if D in _KV_HEAD_DIMS and (rd < 16 or rd > D or rd % 16 != 0):
+            raise ValueError(f"{fn}: rotary_dim = 2 x {rotary_cos.shape[1]} = {rd} is not supported: 16 <= rotary_dim <= head dim {D} and "
+                             "rotary_dim % 16 == 0 (a lane rotates 8 pairs)")
+        if rows < capacity:
+            raise ValueError(f"{fn}: the rotary tables cover {rows} positions but the cache holds up to {capacity}: rows >= capacity, so that "
+                             "no position the lengths in device memory can name lies outside the tables")
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if t.stride(1) != 1 or t.data_ptr() % 16 != 0 or (rows > 1 and ((t.stride(0) * esize) % 16 != 0 or t.stride(0) < rd // 2)):
+                raise ValueError(f"{fn}: {name}: rows must be 16-byte aligned, apart and with unit column stride (base pointer % 16 == 0, row "
+                                 f"stride x {esize} bytes % 16 == 0, row stride >= rotary_dim / 2 = {rd // 2}); got strides {tuple(t.stride())}. "
+                                 "A table is never copied here")
+
+    pa = KvPrefillArgs()   # (its first member is the decode call's argument block)
+    a, out, lse, k_new, v_new, _keep, _alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                                                        softmax_n_param, scale, is_causal, return_lse, args=pa.kv)
+    pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
+    decode = query_seqlens is None and a.kv_group * a.Sq <= _MAX_ROWS
+    win = None if window is None else KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
+    rope = KvRope()
+    rope.cos, rope.sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
+    rope.row_stride = rotary_cos.stride(0) if rows > 1 else rd // 2
+    rope.rows, rope.rotary_dim = min(rows, 2 ** 31 - 1), rd
+    rope.table_dtype = _lib.FASN_DTYPE_F32 if rotary_cos.dtype == torch.float32 else _KV_DTYPES[query.dtype]
+    rope.interleaved = 1 if rotary_interleaved else 0
+    lib = _lib.load()
+    dev = query.device
+    q_rot = torch.empty(tuple(query.shape), dtype=query.dtype, device=dev)   # (torch's caching allocator: a captured graph owns it)
+    kn_view = None if k_new is None else _view4(k_new)
+    vn_view = None if v_new is None else _view4(v_new)
+
+    def launch():
+        stream = _stream_ptr(dev)
+        if decode:
+            _lib.check(lib.fasn_kvcache_rope_append(a, rope, _view4(q_rot), kn_view, vn_view, stream), "fasn_kvcache_rope_append")
+            a.q = _view4(q_rot)   # the forward reads the rotated queries
+            ws_bytes = lib.fasn_fwd_kvcache_workspace_bytes(a) if win is None else lib.fasn_fwd_kvcache_window_workspace_bytes(a, win)
+            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (torch's caching allocator: capturable)
+            if win is None:
+                _lib.check(lib.fasn_fwd_kvcache(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache")
+            else:
+                _lib.check(lib.fasn_fwd_kvcache_window(a, win, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache_window")
+            return
+        _lib.check(lib.fasn_kvprefill_rope_append(pa, rope, _view4(q_rot), kn_view, vn_view, stream), "fasn_kvprefill_rope_append")
+        a.q = _view4(q_rot)
+        ws_bytes = lib.fasn_fwd_kvprefill_workspace_bytes(pa) if win is None else lib.fasn_fwd_kvprefill_window_workspace_bytes(pa, win)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None   # (one split: no partials, no workspace)
+        wsp = None if ws is None else ws.data_ptr()
+        if win is None:
+            _lib.check(lib.fasn_fwd_kvprefill(pa, wsp, ws_bytes, stream), "fasn_fwd_kvprefill")
+        else:
+            _lib.check(lib.fasn_fwd_kvprefill_window(pa, win, wsp, ws_bytes, stream), "fasn_fwd_kvprefill_window")
 
     if _current_device() == dev.index:
         launch()

@@ -378,6 +378,56 @@ int fasn_fwd_kvprefill_window(const fasn_kvprefill_args* args, const fasn_kv_win
 int fasn_kvprefill_window_plan(const fasn_kvprefill_args* args, const fasn_kv_window* window, char* buf, size_t cap);
 
 /*
+ * ROTARY POSITION EMBEDDING on the cache calls (additions within ABI 6; the argument blocks above keep their layouts): one launch that
+ * takes the place of the append in front of a forward. With len_b / qlen_b as the base call defines them (clamps included, read in
+ * device memory - a replayed graph follows `seqlens` and `q_seqlens`):
+ *   k_new   row i < qlen_b of k_new[b, hk] is rotated at position seqlens[b] + i and written to that cache row, addressed as
+ *           fasn_kvcache_append addresses it; rows at a negative position or at / beyond the capacity are dropped inside the kernel
+ *   v_new   row i < qlen_b is copied to the same position, unrotated
+ *   q       row i < qlen_b of args->q[b, h] is rotated at p_i = i + len_b - qlen_b (decode: qlen_b = Sq) - the p_i of the *_alibi and
+ *           *_window calls - and written to q_out[b, h, i]; rows i >= qlen_b are neither read nor written (the forward never reads them)
+ * k_new == v_new == NULL: only the queries are rotated, with args->seqlen_add as given. With k_new / v_new, seqlen_add must be Sq.
+ *
+ *   layouts   features d < rotary_dim are rotated, the others copied. With c = cos[pos, d], s = sin[pos, d], d < rotary_dim / 2:
+ *             interleaved = 0 (GPT-NeoX / Llama / GPT-OSS, Hugging Face rotate_half): x1 = x[d], x2 = x[d + rotary_dim / 2];
+ *             interleaved = 1 (GPT-J): x1 = x[2 d], x2 = x[2 d + 1];   y1 = x1 c - x2 s, y2 = x2 c + x1 s, written where x1 / x2 were.
+ *   tables    cos / sin [rows, rotary_dim / 2], fp32 (FASN_DTYPE_F32, defined below) or the dtype of `args`, DEVICE, column stride 1.
+ *             The row read is clamp(pos, 0, rows - 1); rows >= capacity, so the clamp acts only on the negative p_i of causal rows that
+ *             see no key. Scaling rules (YaRN, NTK, an attention factor) live in the tables.
+ *   rounding  operands widened to fp32; each product rounded to fp32 on its own, the sum / difference rounded to fp32 on its own (no
+ *             fused multiply-add), one rounding to the 16-bit type, to nearest even: bit for bit (x1 c - x2 s) evaluated in fp32 step by step.
+ *
+ * CALL SEQUENCE of one layer step: fasn_kvcache_rope_append(args, rope, &q_out, &k_new, &v_new, stream) with args->seqlen_add = Sq, then
+ * fasn_fwd_kvcache (or fasn_fwd_kvcache_window) on the same args with args->q = q_out; the prefill calls alike. It replaces
+ * fasn_kvcache_append / fasn_kvprefill_append: launches per step do not change. `seqlens` is not modified.
+ *
+ * Every rule and error code of the base call holds and is checked first; then: rope, cos, sin or q_out NULL, k_new and v_new not both
+ * NULL or both given, k_new given with seqlen_add != Sq, rotary_dim outside [16, D] or not a multiple of 16, rows < capacity, interleaved
+ * not 0 or 1, row_stride < rotary_dim / 2 are FASN_EINVAL; table_dtype neither FASN_DTYPE_F32 nor args->dtype is FASN_EDTYPE; a table
+ * base that is not 16-byte aligned or a row stride that is not a multiple of 16 bytes is FASN_EALIGN; q_out, k_new, v_new follow the
+ * rules of q with its codes. The *_plan calls write the one launch as text, in the line format of fasn_launch_plan, without touching a
+ * device: its grid is ceil(((k_new ? B * (H / kv_group) * Sq : 0) + B * H * Sq) * (D / 16) / 256) workgroups - shapes only.
+ */
+typedef struct fasn_kv_rope {
+    const void* cos;             /* DEVICE [rows, rotary_dim / 2], unit column stride */
+    const void* sin;
+    int64_t row_stride;          /* elements */
+    int32_t rows;                /* positions the tables cover; >= capacity */
+    int32_t rotary_dim;          /* 16 <= rotary_dim <= D, % 16 == 0 */
+    int32_t table_dtype;         /* FASN_DTYPE_F32, or the dtype of args */
+    int32_t interleaved;         /* 0 half-split, 1 (2d, 2d+1) pairs */
+} fasn_kv_rope;
+
+int fasn_kvcache_rope_append(const fasn_kvcache_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
+                             const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvprefill_rope_append(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
+                               const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvcache_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
+                                  const fasn_view4* v_new, char* buf, size_t cap);
+int fasn_kvprefill_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                    const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).
