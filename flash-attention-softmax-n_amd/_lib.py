@@ -106,6 +106,29 @@ class FasnError(RuntimeError):
 _lib = None
 
 
+def _kv_bindings():
+    """(name, restype, argtypes) of the 22 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
+    block (fasn_kvprefill_args); `operands` come between the block and the tail"""
+    view, text = POINTER(View4), [c_char_p, c_size_t]
+    launch = [c_void_p]                          # the stream
+    forward = [c_void_p, c_size_t, c_void_p]     # workspace, its bytes, the stream
+    rope = [POINTER(KvRope), view, view, view]
+    for stem, block in (("kvcache", POINTER(KvCacheArgs)), ("kvprefill", POINTER(KvPrefillArgs))):
+        for name, restype, operands, tail in (
+                (f"fasn_fwd_{stem}_workspace_bytes", c_size_t, [], []),
+                (f"fasn_fwd_{stem}_window_workspace_bytes", c_size_t, [POINTER(KvWindow)], []),
+                (f"fasn_fwd_{stem}", c_int32, [], forward),
+                (f"fasn_fwd_{stem}_alibi", c_int32, [POINTER(AlibiSlopes)], forward),
+                (f"fasn_fwd_{stem}_window", c_int32, [POINTER(KvWindow)], forward),
+                (f"fasn_{stem}_append", c_int32, [view, view], launch),
+                (f"fasn_{stem}_rope_append", c_int32, rope, launch),
+                (f"fasn_{stem}_plan", c_int32, [], text),
+                (f"fasn_{stem}_alibi_plan", c_int32, [POINTER(AlibiSlopes)], text),
+                (f"fasn_{stem}_window_plan", c_int32, [POINTER(KvWindow)], text),
+                (f"fasn_{stem}_rope_append_plan", c_int32, rope, text)):
+            yield name, restype, [block] + operands + tail
+
+
 def load():
     """Load libfasn.so once; raise ImportError with the build recipe if it is not there."""
     global _lib
@@ -154,50 +177,9 @@ def load():
     lib.fasn_softmax_n_bwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int32, c_void_p]
     lib.fasn_moments.restype = c_int32
     lib.fasn_moments.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p]
-    lib.fasn_fwd_kvcache_workspace_bytes.restype = c_size_t
-    lib.fasn_fwd_kvcache_workspace_bytes.argtypes = [POINTER(KvCacheArgs)]
-    lib.fasn_fwd_kvcache.restype = c_int32
-    lib.fasn_fwd_kvcache.argtypes = [POINTER(KvCacheArgs), c_void_p, c_size_t, c_void_p]
-    lib.fasn_kvcache_append.restype = c_int32
-    lib.fasn_kvcache_append.argtypes = [POINTER(KvCacheArgs), POINTER(View4), POINTER(View4), c_void_p]
-    lib.fasn_kvcache_plan.restype = c_int32
-    lib.fasn_kvcache_plan.argtypes = [POINTER(KvCacheArgs), c_char_p, c_size_t]
-    lib.fasn_fwd_kvprefill_workspace_bytes.restype = c_size_t
-    lib.fasn_fwd_kvprefill_workspace_bytes.argtypes = [POINTER(KvPrefillArgs)]
-    lib.fasn_fwd_kvprefill.restype = c_int32
-    lib.fasn_fwd_kvprefill.argtypes = [POINTER(KvPrefillArgs), c_void_p, c_size_t, c_void_p]
-    lib.fasn_kvprefill_append.restype = c_int32
-    lib.fasn_kvprefill_append.argtypes = [POINTER(KvPrefillArgs), POINTER(View4), POINTER(View4), c_void_p]
-    lib.fasn_kvprefill_plan.restype = c_int32
-    lib.fasn_kvprefill_plan.argtypes = [POINTER(KvPrefillArgs), c_char_p, c_size_t]
-    lib.fasn_fwd_kvcache_alibi.restype = c_int32
-    lib.fasn_fwd_kvcache_alibi.argtypes = [POINTER(KvCacheArgs), POINTER(AlibiSlopes), c_void_p, c_size_t, c_void_p]
-    lib.fasn_fwd_kvprefill_alibi.restype = c_int32
-    lib.fasn_fwd_kvprefill_alibi.argtypes = [POINTER(KvPrefillArgs), POINTER(AlibiSlopes), c_void_p, c_size_t, c_void_p]
-    lib.fasn_kvcache_alibi_plan.restype = c_int32
-    lib.fasn_kvcache_alibi_plan.argtypes = [POINTER(KvCacheArgs), POINTER(AlibiSlopes), c_char_p, c_size_t]
-    lib.fasn_kvprefill_alibi_plan.restype = c_int32
-    lib.fasn_kvprefill_alibi_plan.argtypes = [POINTER(KvPrefillArgs), POINTER(AlibiSlopes), c_char_p, c_size_t]
-    lib.fasn_fwd_kvcache_window_workspace_bytes.restype = c_size_t
-    lib.fasn_fwd_kvcache_window_workspace_bytes.argtypes = [POINTER(KvCacheArgs), POINTER(KvWindow)]
-    lib.fasn_fwd_kvcache_window.restype = c_int32
-    lib.fasn_fwd_kvcache_window.argtypes = [POINTER(KvCacheArgs), POINTER(KvWindow), c_void_p, c_size_t, c_void_p]
-    lib.fasn_kvcache_window_plan.restype = c_int32
-    lib.fasn_kvcache_window_plan.argtypes = [POINTER(KvCacheArgs), POINTER(KvWindow), c_char_p, c_size_t]
-    lib.fasn_fwd_kvprefill_window_workspace_bytes.restype = c_size_t
-    lib.fasn_fwd_kvprefill_window_workspace_bytes.argtypes = [POINTER(KvPrefillArgs), POINTER(KvWindow)]
-    lib.fasn_fwd_kvprefill_window.restype = c_int32
-    lib.fasn_fwd_kvprefill_window.argtypes = [POINTER(KvPrefillArgs), POINTER(KvWindow), c_void_p, c_size_t, c_void_p]
-    lib.fasn_kvprefill_window_plan.restype = c_int32
-    lib.fasn_kvprefill_window_plan.argtypes = [POINTER(KvPrefillArgs), POINTER(KvWindow), c_char_p, c_size_t]
-    lib.fasn_kvcache_rope_append.restype = c_int32
-    lib.fasn_kvcache_rope_append.argtypes = [POINTER(KvCacheArgs), POINTER(KvRope), POINTER(View4), POINTER(View4), POINTER(View4), c_void_p]
-    lib.fasn_kvprefill_rope_append.restype = c_int32
-    lib.fasn_kvprefill_rope_append.argtypes = [POINTER(KvPrefillArgs), POINTER(KvRope), POINTER(View4), POINTER(View4), POINTER(View4), c_void_p]
-    lib.fasn_kvcache_rope_append_plan.restype = c_int32
-    lib.fasn_kvcache_rope_append_plan.argtypes = [POINTER(KvCacheArgs), POINTER(KvRope), POINTER(View4), POINTER(View4), POINTER(View4), c_char_p, c_size_t]
-    lib.fasn_kvprefill_rope_append_plan.restype = c_int32
-    lib.fasn_kvprefill_rope_append_plan.argtypes = [POINTER(KvPrefillArgs), POINTER(KvRope), POINTER(View4), POINTER(View4), POINTER(View4), c_char_p, c_size_t]
+    for name, restype, argtypes in _kv_bindings():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     ver = lib.fasn_abi_version()
     if ver != FASN_ABI_VERSION:
         raise ImportError(f"libfasn ABI version {ver} != expected {FASN_ABI_VERSION}; rebuild csrc/")
@@ -245,61 +227,43 @@ def _plan_lines(buf):
     return out
 
 
-def kvcache_plan(args, alibi=None):
-    """The kernels fasn_fwd_kvcache would launch for `args` (a KvCacheArgs), as launch_plan returns them; with `alibi` (an AlibiSlopes)
-    those of fasn_fwd_kvcache_alibi. Nothing is launched."""
+def _kv_plan(what, *operands):
     buf = ctypes.create_string_buffer(4096)
-    if alibi is None:
-        rc, what = load().fasn_kvcache_plan(args, buf, len(buf)), "fasn_kvcache_plan"
-    else:
-        rc, what = load().fasn_kvcache_alibi_plan(args, alibi, buf, len(buf)), "fasn_kvcache_alibi_plan"
+    rc = getattr(load(), what)(*operands, buf, len(buf))
     if rc < 0:
         check(rc, what)
     return _plan_lines(buf)
+
+
+def kvcache_plan(args, alibi=None):
+    """The kernels fasn_fwd_kvcache would launch for `args` (a KvCacheArgs), as launch_plan returns them; with `alibi` (an AlibiSlopes)
+    those of fasn_fwd_kvcache_alibi. Nothing is launched."""
+    return _kv_plan("fasn_kvcache_plan", args) if alibi is None else _kv_plan("fasn_kvcache_alibi_plan", args, alibi)
 
 
 def kvprefill_plan(args, alibi=None):
     """The kernels fasn_fwd_kvprefill would launch for `args` (a KvPrefillArgs), as launch_plan returns them; with `alibi` (an AlibiSlopes)
     those of fasn_fwd_kvprefill_alibi. Nothing is launched."""
-    buf = ctypes.create_string_buffer(4096)
-    if alibi is None:
-        rc, what = load().fasn_kvprefill_plan(args, buf, len(buf)), "fasn_kvprefill_plan"
-    else:
-        rc, what = load().fasn_kvprefill_alibi_plan(args, alibi, buf, len(buf)), "fasn_kvprefill_alibi_plan"
-    if rc < 0:
-        check(rc, what)
-    return _plan_lines(buf)
+    return _kv_plan("fasn_kvprefill_plan", args) if alibi is None else _kv_plan("fasn_kvprefill_alibi_plan", args, alibi)
 
 
 def kvcache_window_plan(args, win):
     """The kernels fasn_fwd_kvcache_window would launch for `args` (a KvCacheArgs) under `win` (a KvWindow), as launch_plan returns them.
     Nothing is launched."""
-    buf = ctypes.create_string_buffer(4096)
-    rc = load().fasn_kvcache_window_plan(args, win, buf, len(buf))
-    if rc < 0:
-        check(rc, "fasn_kvcache_window_plan")
-    return _plan_lines(buf)
+    return _kv_plan("fasn_kvcache_window_plan", args, win)
 
 
 def kvprefill_window_plan(args, win):
     """The kernels fasn_fwd_kvprefill_window would launch for `args` (a KvPrefillArgs) under `win` (a KvWindow), as launch_plan returns
     them. Nothing is launched."""
-    buf = ctypes.create_string_buffer(4096)
-    rc = load().fasn_kvprefill_window_plan(args, win, buf, len(buf))
-    if rc < 0:
-        check(rc, "fasn_kvprefill_window_plan")
-    return _plan_lines(buf)
+    return _kv_plan("fasn_kvprefill_window_plan", args, win)
 
 
 def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):
     """The one launch of fasn_kvcache_rope_append (`args` a KvCacheArgs) or fasn_kvprefill_rope_append (a KvPrefillArgs) under `rope`
     (a KvRope), as launch_plan returns it. Nothing is launched."""
-    buf = ctypes.create_string_buffer(4096)
     what = "fasn_kvprefill_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_rope_append_plan"
-    rc = getattr(load(), what)(args, rope, q_out, k_new, v_new, buf, len(buf))
-    if rc < 0:
-        check(rc, what)
-    return _plan_lines(buf)
+    return _kv_plan(what, args, rope, q_out, k_new, v_new)
 
 
 def check(rc, what):

@@ -1,15 +1,13 @@
-// K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi|_window], fasn_kvcache_append, fasn_kvcache[_alibi|_window]_plan): argument checks, the launch plan -
-// which depends on shapes and capacity only, never on the lengths in device memory - and the three launches of fasn_kvcache.h.
+// K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi|_window], fasn_kvcache_append, fasn_kvcache[_alibi|_window]_plan), in two parts:
+//   1. the host layer of the whole K/V-cache family (fasn_kv_host.h declares it; fasn_kvprefill.hip and fasn_kvrope.hip call it): argument
+//      checks, parameter packing, the launch plan - which depends on shapes and capacity only, never on the lengths in device memory -
+//      the operand checks of the ALiBi and window variants and the workspace rule;
+//   2. the decode entry points and the launches of fasn_kvcache.h.
 #include <limits.h>
 #include <math.h>
-#include "fasn.h"
-#include "fasn_kvcache.h"
-#include "fasn_launch.h"
+#include "fasn_kv_host.h"
 
 namespace fasn {
-namespace {
-
-bool kv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int kv_check_view(const fasn_view4& v) {
     if (v.ptr == nullptr) return FASN_EINVAL;
@@ -20,14 +18,20 @@ int kv_check_view(const fasn_view4& v) {
     return FASN_OK;
 }
 
-// Validation (no HIP call) + the kernel parameters. The plan: one workgroup per (batch element, K/V head, split); as many splits as
-// bring the grid to ~1024 workgroups (the split-K forward's target; ~512 at D = 256, kv_split_target), each with enough tiles of a FULL
-// cache to pay for its partial. Head dims: 32, 64, 128, 256 (kv_head_dim_ok).
+namespace {
 // a split costs its partial (R rows of D + 2 floats, written and read back) next to its tiles (64 keys of K and V): at least 4 tiles
-// per split of a full cache, R / 8 when there are many rows (128 rows: the partial moves what 4 tiles do)
+// per split of a full cache, R / 8 when there are many rows (128 rows - every prefill: the partial moves what 4 tiles do, 16 tiles)
 int64_t kv_min_tps(int R) { return R / 8 > 4 ? R / 8 : 4; }
+}  // namespace
 
-int kv_build(const fasn_kvcache_args* a, KvParams& p) {
+// Validation (no HIP call) + the kernel parameters, for decode, prefill and the rotary append. The plan: one workgroup per (batch
+// element, K/V head, row block, split); as many splits as bring the grid to ~1024 workgroups (the split-K forward's target; ~512 at
+// D = 256, kv_split_target), each with enough tiles of a FULL cache to pay for its partial - so a prefill whose row blocks fill the
+// chip has one split, no partials and no combine launch. Head dims: 32, 64, 128, 256 (kv_head_dim_ok).
+// The order of the checks decides which code a block that breaks two rules gets: tests/golden/kvhost_matrix.txt pins it.
+int kv_build(const KvArgs& in, KvPrefillParams& pp) {
+    const fasn_kvcache_args* a = in.a;
+    const bool prefill = in.call == KV_PREFILL;
     if (a == nullptr) return FASN_EINVAL;
     if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->D <= 0 || a->page_size <= 0) return FASN_EINVAL;
     if (a->dtype != FASN_DTYPE_F16 && a->dtype != FASN_DTYPE_BF16) return FASN_EDTYPE;
@@ -36,7 +40,11 @@ int kv_build(const fasn_kvcache_args* a, KvParams& p) {
     if (a->H % G != 0) return FASN_EINVAL;
     if (!(a->softmax_n >= 0.f) || !isfinite(a->scale)) return FASN_EINVAL;
     if (a->seqlens == nullptr || a->k_cache == nullptr || a->v_cache == nullptr) return FASN_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->seqlens) % 4 || reinterpret_cast<uintptr_t>(a->block_table) % 4) return FASN_EALIGN;
+    // (q_seqlens: prefill only, a decode block has none)
+    if (reinterpret_cast<uintptr_t>(a->seqlens) % 4 || reinterpret_cast<uintptr_t>(a->block_table) % 4 || reinterpret_cast<uintptr_t>(in.q_seqlens) % 4) return FASN_EALIGN;
+    // prefill adds qlen_b, which the host does not know: seqlen_add is a flag there (0: the cache as it is; Sq: plus the qlen_b appended
+    // rows). Decode adds the number itself, whatever it is.
+    if (prefill && a->seqlen_add != 0 && a->seqlen_add != a->Sq) return FASN_EINVAL;
     int rc;
     if ((rc = kv_check_view(a->q))) return rc;
     if ((rc = kv_check_view(a->o))) return rc;
@@ -46,9 +54,12 @@ int kv_build(const fasn_kvcache_args* a, KvParams& p) {
     const bool paged = a->block_table != nullptr;
     if (paged && (a->max_pages <= 0 || a->block_table_stride < a->max_pages)) return FASN_EINVAL;
     if (paged && a->page_size % KV_KT != 0) return FASN_EUNSUPPORTED;   // a 64-key tile never straddles a page
-    if ((int64_t)G * a->Sq > 128) return FASN_EUNSUPPORTED;               // the rows of a K/V head are one pass of one workgroup
+    // decode: the rows of a K/V head are one pass of one workgroup; prefill: its query heads share one workgroup
+    if ((prefill ? (int64_t)G : (int64_t)G * a->Sq) > KVP_ROWS) return FASN_EUNSUPPORTED;
     const int64_t capacity = paged ? (int64_t)a->max_pages * a->page_size : (int64_t)a->page_size;
-    if (capacity > INT_MAX - 2 * KV_KT || (int64_t)a->seqlen_add + capacity > INT_MAX) return FASN_EINVAL;
+    // the most a kernel adds to a length: seqlen_add (decode), up to Sq (prefill - bounded so even where seqlen_add is 0: kept as it was)
+    const int64_t added = prefill ? a->Sq : a->seqlen_add;
+    if (capacity > INT_MAX - 2 * KV_KT || added + capacity > INT_MAX) return FASN_EINVAL;
     // a tile's descriptor range and the lanes' offsets into it are 32-bit
     if ((int64_t)KV_KT * a->k_stride[1] * 2 >= (1ll << 31) || (int64_t)KV_KT * a->v_stride[1] * 2 >= (1ll << 31)) return FASN_EUNSUPPORTED;
     if (a->k_stride[1] < a->D || a->v_stride[1] < a->D) return FASN_EINVAL;
@@ -56,7 +67,8 @@ int kv_build(const fasn_kvcache_args* a, KvParams& p) {
         if (reinterpret_cast<uintptr_t>(a->n) % 4) return FASN_EALIGN;
         if (a->n_stride_b < 0 || a->n_stride_h < 0 || (a->B - 1) * a->n_stride_b + (a->H - 1) * a->n_stride_h >= (1ll << 31)) return FASN_EINVAL;
     }
-    p = KvParams{};
+    pp = KvPrefillParams{};
+    KvParams& p = pp.kv;
     p.q = static_cast<const char*>(a->q.ptr);
     p.o = static_cast<char*>(a->o.ptr);
     p.lse = a->lse;
@@ -75,19 +87,44 @@ int kv_build(const fasn_kvcache_args* a, KvParams& p) {
     p.page_size = a->page_size;
     p.tpp = paged ? a->page_size / KV_KT : INT_MAX;
     p.capacity = (int)capacity;
-    p.B = a->B, p.H = a->H, p.G = G, p.Hkv = a->H / G, p.Sq = a->Sq, p.R = G * a->Sq;
+    p.B = a->B, p.H = a->H, p.G = G, p.Hkv = a->H / G, p.Sq = a->Sq;
+    p.R = prefill ? KVP_ROWS : G * a->Sq;
     p.causal = a->causal ? 1 : 0;
     p.c = a->scale * kLog2e;
     p.n = a->softmax_n;
     p.nt = a->n;
     p.nsb = (int)a->n_stride_b, p.nsh = (int)a->n_stride_h;
-    const int64_t base = (int64_t)p.B * p.Hkv;
+    pp.qlens = in.q_seqlens;
+    pp.PB = prefill ? KVP_ROWS / G : a->Sq;
+    pp.nrb = (a->Sq + pp.PB - 1) / pp.PB;   // (decode: 1)
+    const int64_t base = (int64_t)p.B * p.Hkv * pp.nrb;
     const int64_t cap_tiles = (capacity + KV_KT - 1) / KV_KT;
     p.nsplit = (int)kv_nsplit(a->D, base, cap_tiles, kv_min_tps(p.R));
-    if (base * p.nsplit > INT_MAX) return FASN_EINVAL;
+    if (base * p.nsplit > (prefill ? INT_MAX / KVP_ROWS : INT_MAX)) return FASN_EINVAL;   // (prefill: times the row slots of a workgroup)
     return FASN_OK;
 }
-size_t kv_ws_bytes(const KvParams& p, int D) { return (size_t)p.B * p.Hkv * p.nsplit * p.R * (size_t)(D + 2) * sizeof(float); }
+
+int kv_pack_new(const fasn_view4& k_new, const fasn_view4& v_new, KvParams& p) {
+    int rc;
+    if ((rc = kv_check_view(k_new))) return rc;
+    if ((rc = kv_check_view(v_new))) return rc;
+    p.kn = static_cast<const char*>(k_new.ptr);
+    p.vn = static_cast<const char*>(v_new.ptr);
+    for (int i = 0; i < 3; ++i) {
+        p.kns[i] = k_new.stride[i];
+        p.vns[i] = v_new.stride[i];
+    }
+    return FASN_OK;
+}
+
+int kv_build_append(const KvArgs& in, const fasn_view4* k_new, const fasn_view4* v_new, KvPrefillParams& pp) {
+    const int rc = kv_build(in, pp);
+    if (rc) return rc;
+    if (k_new == nullptr || v_new == nullptr) return FASN_EINVAL;
+    return kv_pack_new(*k_new, *v_new, pp.kv);
+}
+
+namespace {
 
 // The ALiBi operand of the *_alibi entry points (checked after the base arguments, before any HIP call): the rules of `n`
 int kv_build_alibi(const fasn_kvcache_args* a, const fasn_alibi_slopes* s, KvAlibi& al) {
@@ -99,101 +136,99 @@ int kv_build_alibi(const fasn_kvcache_args* a, const fasn_alibi_slopes* s, KvAli
 }
 
 // The window operand of the *_window entry points (checked after the base arguments, before any HIP call), and the plan under it: the
-// base rule over the tiles a workgroup's window can touch, never more splits than the base plan has.
-int kv_build_window(const fasn_kvcache_args* a, const fasn_kv_window* w, KvParams& p, KvWindow& kw) {
+// base rule over the tiles the window of a workgroup's rows can touch - they span PB positions - never more splits than the base plan has.
+int kv_build_window(const fasn_kvcache_args* a, const fasn_kv_window* w, KvPrefillParams& pp, KvWindow& kw) {
+    KvParams& p = pp.kv;
     if (w == nullptr || w->window < 1 || w->reserved != 0) return FASN_EINVAL;
     if (!a->causal) return FASN_EUNSUPPORTED;
     kw = KvWindow{w->window < p.capacity ? w->window : p.capacity};
     const int64_t cap_tiles = ((int64_t)p.capacity + KV_KT - 1) / KV_KT;
-    p.nsplit = (int)kv_nsplit(a->D, (int64_t)p.B * p.Hkv, kv_window_tiles(cap_tiles, w->window, p.Sq), kv_min_tps(p.R));
+    p.nsplit = (int)kv_nsplit(a->D, (int64_t)p.B * p.Hkv * pp.nrb, kv_window_tiles(cap_tiles, w->window, pp.PB), kv_min_tps(p.R));
     return FASN_OK;
 }
 
-// (al == kw == nullptr: the base kernel; otherwise its ALiBi sibling on the same grid, LDS and workspace, or its window sibling)
-template <typename Tag, int D>
-int kv_launch_fwd(const KvParams& p, const KvAlibi* al, const KvWindow* kw, hipStream_t s) {
-    constexpr int smem = kv_smem(D);
-    if (kw != nullptr) {
-        constexpr auto kern = &fasn_kvcache_fwd_window_kernel<Tag, D>;
-        ensure_smem<kern>(smem);
-        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * p.nsplit)), dim3(256), smem, s, p, *kw);
-    } else if (al == nullptr) {
-        constexpr auto kern = &fasn_kvcache_fwd_kernel<Tag, D>;
-        ensure_smem<kern>(smem);
-        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * p.nsplit)), dim3(256), smem, s, p);
-    } else {
-        constexpr auto kern = &fasn_kvcache_fwd_alibi_kernel<Tag, D>;
-        ensure_smem<kern>(smem);
-        FASN_LAUNCH(kern, dim3((unsigned)(p.B * p.Hkv * p.nsplit)), dim3(256), smem, s, p, *al);
+int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, KvFwd& f) {
+    int rc = kv_build(in, f.pp);
+    if (rc) return rc;
+    f.variant = variant;
+    f.al = KvAlibi{};
+    f.kw = KvWindow{};
+    if (variant == KV_ALIBI) return kv_build_alibi(in.a, static_cast<const fasn_alibi_slopes*>(operand), f.al);
+    if (variant == KV_WINDOW) return kv_build_window(in.a, static_cast<const fasn_kv_window*>(operand), f.pp, f.kw);
+    return FASN_OK;
+}
+
+// the split partials: [B * Hkv * nrb][nsplit][R][D] and [...][R][2] floats. Decode always writes them and combines; a prefill of one
+// split stores o / lse itself and needs none.
+size_t kv_part_elems(const KvPrefillParams& pp) { return (size_t)pp.kv.B * pp.kv.Hkv * pp.nrb * pp.kv.nsplit * pp.kv.R; }
+size_t kv_ws_bytes(KvCall call, const KvPrefillParams& pp, int D) {
+    if (call == KV_PREFILL && pp.kv.nsplit <= 1) return 0;
+    return kv_part_elems(pp) * (size_t)(D + 2) * sizeof(float);
+}
+
+}  // namespace
+
+size_t kv_workspace_bytes(const KvArgs& in, KvVariant variant, const void* operand) {
+    KvFwd f;
+    if (kv_build_variant(in, variant, operand, f) != FASN_OK) return 0;
+    return kv_ws_bytes(in.call, f.pp, in.a->D);
+}
+
+int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, KvFwd& f) {
+    const int rc = kv_build_variant(in, variant, operand, f);
+    if (rc) return rc;
+    const size_t need = kv_ws_bytes(in.call, f.pp, in.a->D);
+    if (need > 0) {   // (nothing to write beside o / lse: a NULL workspace is fine)
+        if (workspace == nullptr || workspace_bytes < need) return FASN_EWORKSPACE;
+        if (!kv_aligned16(workspace)) return FASN_EALIGN;
+        f.pp.kv.part_o = static_cast<float*>(workspace);
+        f.pp.kv.part_ml = f.pp.kv.part_o + kv_part_elems(f.pp) * in.a->D;
     }
+    return FASN_OK;
+}
+
+namespace {
+
+template <typename Tag, int D>
+int kv_launch_fwd(const KvFwd& f, hipStream_t s) {
+    const KvParams& p = f.pp.kv;
+    kv_launch_variant<&fasn_kvcache_fwd_kernel<Tag, D>, &fasn_kvcache_fwd_alibi_kernel<Tag, D>, &fasn_kvcache_fwd_window_kernel<Tag, D>>(
+        f, p, (unsigned)(p.B * p.Hkv * p.nsplit), kv_smem(D), s);
     const int64_t nthr = (int64_t)p.B * p.Hkv * p.R * (D / 4);
     FASN_LAUNCH((fasn_kvcache_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
 }
 template <int D>
 int kv_launch_append(const KvParams& p, hipStream_t s) {
-    const int64_t nthr = (int64_t)p.B * p.Hkv * p.Sq * (D / 8);
+    const int64_t nthr = (int64_t)p.B * p.Hkv * p.Sq * (D / 8);   // (at most 128 rows per K/V head: the grid fits)
     FASN_LAUNCH((fasn_kvcache_append_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
 }
 
-template <typename Tag>
-int kv_launch_fwd_d(int D, const KvParams& p, const KvAlibi* al, const KvWindow* kw, hipStream_t s) {   // (kv_build let only these four through)
-    switch (D) {
-        case 32: return kv_launch_fwd<Tag, 32>(p, al, kw, s);
-        case 64: return kv_launch_fwd<Tag, 64>(p, al, kw, s);
-        case 128: return kv_launch_fwd<Tag, 128>(p, al, kw, s);
-        default: return kv_launch_fwd<Tag, 256>(p, al, kw, s);
-    }
-}
-
 int kv_forward(const fasn_kvcache_args* args, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    KvParams p;
-    int rc = kv_build(args, p);
+    KvFwd f;
+    const int rc = kv_build_forward(kv_args(args), variant, operand, workspace, workspace_bytes, f);
     if (rc) return rc;
-    KvAlibi al{};
-    KvWindow kw{};
-    if (variant == KV_ALIBI && (rc = kv_build_alibi(args, static_cast<const fasn_alibi_slopes*>(operand), al))) return rc;
-    if (variant == KV_WINDOW && (rc = kv_build_window(args, static_cast<const fasn_kv_window*>(operand), p, kw))) return rc;
-    if (workspace == nullptr || workspace_bytes < kv_ws_bytes(p, args->D)) return FASN_EWORKSPACE;
-    if (!kv_aligned16(workspace)) return FASN_EALIGN;
-    p.part_o = static_cast<float*>(workspace);
-    p.part_ml = p.part_o + (size_t)p.B * p.Hkv * p.nsplit * p.R * args->D;
-    hipStream_t s = (hipStream_t)stream;
-    const KvAlibi* const alp = variant == KV_ALIBI ? &al : nullptr;
-    const KvWindow* const kwp = variant == KV_WINDOW ? &kw : nullptr;
-    if (args->dtype == FASN_DTYPE_BF16) return kv_launch_fwd_d<bf16_tag>(args->D, p, alp, kwp, s);
-    return kv_launch_fwd_d<f16_tag>(args->D, p, alp, kwp, s);
+    return kv_dispatch(args->dtype, args->D, [&](auto tag, auto d) { return kv_launch_fwd<decltype(tag), decltype(d)::value>(f, (hipStream_t)stream); });
 }
-
-int kv_plan(const fasn_kvcache_args* args, KvVariant variant, const void* operand, char* buf, size_t cap) {
-    if (args == nullptr || buf == nullptr || cap == 0) return FASN_EINVAL;
-    LaunchLog log{buf, cap, 0};
-    buf[0] = 0;
-    LaunchLog* const outer = t_launch_log;
-    t_launch_log = &log;
-    const int rc = kv_forward(args, variant, operand, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
-    t_launch_log = outer;
+int kv_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
+    KvPrefillParams pp;
+    const int rc = kv_build_append(kv_args(args), k_new, v_new, pp);
     if (rc) return rc;
-    return log.len > cap ? FASN_EINVAL : (int)log.len;
+    return kv_dispatch_d(args->D, [&](auto d) { return kv_launch_append<decltype(d)::value>(pp.kv, (hipStream_t)stream); });
+}
+int kv_forward_plan(const fasn_kvcache_args* args, KvVariant variant, const void* operand, char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kv_forward(args, variant, operand, kv_plan_workspace(), ~size_t(0), nullptr); });
 }
 
 }  // namespace
-
-// the validation and parameter packing above, for the rotary rotate-and-append call (fasn_kvrope.h declares it, fasn_kvrope.hip calls it)
-int kv_build_params(const fasn_kvcache_args* a, KvParams& p) { return kv_build(a, p); }
-
 }  // namespace fasn
 
 using namespace fasn;
 
 extern "C" {
 
-size_t fasn_fwd_kvcache_workspace_bytes(const fasn_kvcache_args* args) {
-    KvParams p;
-    if (kv_build(args, p) != FASN_OK) return 0;
-    return kv_ws_bytes(p, args->D);
-}
+size_t fasn_fwd_kvcache_workspace_bytes(const fasn_kvcache_args* args) { return kv_workspace_bytes(kv_args(args), KV_BASE, nullptr); }
 
 int fasn_fwd_kvcache(const fasn_kvcache_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
     return kv_forward(args, KV_BASE, nullptr, workspace, workspace_bytes, stream);
@@ -204,10 +239,7 @@ int fasn_fwd_kvcache_alibi(const fasn_kvcache_args* args, const fasn_alibi_slope
 }
 
 size_t fasn_fwd_kvcache_window_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_window* window) {
-    KvParams p;
-    KvWindow kw;
-    if (kv_build(args, p) != FASN_OK || kv_build_window(args, window, p, kw) != FASN_OK) return 0;
-    return kv_ws_bytes(p, args->D);
+    return kv_workspace_bytes(kv_args(args), KV_WINDOW, window);
 }
 
 int fasn_fwd_kvcache_window(const fasn_kvcache_args* args, const fasn_kv_window* window, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
@@ -215,35 +247,17 @@ int fasn_fwd_kvcache_window(const fasn_kvcache_args* args, const fasn_kv_window*
 }
 
 int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
-    KvParams p;
-    int rc = kv_build(args, p);
-    if (rc) return rc;
-    if (k_new == nullptr || v_new == nullptr) return FASN_EINVAL;
-    if ((rc = kv_check_view(*k_new))) return rc;
-    if ((rc = kv_check_view(*v_new))) return rc;
-    p.kn = static_cast<const char*>(k_new->ptr);
-    p.vn = static_cast<const char*>(v_new->ptr);
-    for (int i = 0; i < 3; ++i) {
-        p.kns[i] = k_new->stride[i];
-        p.vns[i] = v_new->stride[i];
-    }
-    hipStream_t s = (hipStream_t)stream;
-    switch (args->D) {
-        case 32: return kv_launch_append<32>(p, s);
-        case 64: return kv_launch_append<64>(p, s);
-        case 128: return kv_launch_append<128>(p, s);
-        default: return kv_launch_append<256>(p, s);
-    }
+    return kv_append(args, k_new, v_new, stream);
 }
 
-int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) { return kv_plan(args, KV_BASE, nullptr, buf, cap); }
+int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) { return kv_forward_plan(args, KV_BASE, nullptr, buf, cap); }
 
 int fasn_kvcache_alibi_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap) {
-    return kv_plan(args, KV_ALIBI, alibi, buf, cap);
+    return kv_forward_plan(args, KV_ALIBI, alibi, buf, cap);
 }
 
 int fasn_kvcache_window_plan(const fasn_kvcache_args* args, const fasn_kv_window* window, char* buf, size_t cap) {
-    return kv_plan(args, KV_WINDOW, window, buf, cap);
+    return kv_forward_plan(args, KV_WINDOW, window, buf, cap);
 }
 
 }  // extern "C"

@@ -47,10 +47,6 @@ struct KvRopeParams {
     int64_t nkv, nq;      // K/V units, query units
 };
 
-// host side (fasn_kvcache.hip / fasn_kvprefill.hip): the base calls' validation and parameter packing, for fasn_kvrope.hip
-int kv_build_params(const fasn_kvcache_args* a, KvParams& p);
-int kvp_build_params(const fasn_kvprefill_args* pa, KvPrefillParams& pp);
-
 template <typename Tag>
 FASN_DEV void kvrope_widen(u32x4 raw, float (&x)[8]) {
     uint16_t h[8];

@@ -58,6 +58,34 @@ def _slopes_tensor(fn, alibi_slopes, query) -> Tensor:
     return _n_tensor(alibi_slopes.detach(), query).contiguous()
 
 
+def _check_window(fn, window, or_none="") -> None:
+    if isinstance(window, bool) or not isinstance(window, int):
+        raise TypeError(f"{fn}: window must be {or_none}a Python int (a constant of the layer, part of a captured graph; never a tensor); "
+                        f"got {type(window).__name__}")
+    if window < 1:
+        raise ValueError(f"{fn}: window must be >= 1 (the keys a position sees, its own included); got {window}")
+
+
+def _check_query_seqlens(fn, query_seqlens, query) -> None:
+    if query_seqlens is None:
+        return
+    B = query.shape[0] if query.dim() == 4 else -1
+    if (not isinstance(query_seqlens, Tensor) or query_seqlens.dtype != torch.int32 or query_seqlens.dim() != 1 or query_seqlens.shape[0] != B
+            or not query_seqlens.is_contiguous()):
+        got = f"{query_seqlens.dtype} {tuple(query_seqlens.shape)}" if isinstance(query_seqlens, Tensor) else type(query_seqlens).__name__
+        raise ValueError(f"query_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {got}")
+    if query_seqlens.device != query.device:
+        raise RuntimeError(f"query_seqlens is on {query_seqlens.device}, query on {query.device}: every operand must live on the query's "
+                           "device (the lengths are read by the kernels, never on the host)")
+
+
+def _check_group_limit(fn, query, k_cache) -> None:
+    """the prefill kernels' limit, in front of _prepare (malformed shapes are _prepare's to name)"""
+    if query.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and query.shape[1] // k_cache.shape[2] > 128 and query.shape[1] % k_cache.shape[2] == 0:
+        raise ValueError(f"{fn}: {query.shape[1] // k_cache.shape[2]} query heads per K/V head are not supported (at most 128: the heads of a "
+                         "K/V head share one workgroup)")
+
+
 def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal, return_lse,
              max_rows=None, args=None, alibi_slopes=None):
     """The argument checks both entry points share (they need no device and come first) and the filled fasn_kvcache_args.
@@ -165,6 +193,40 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
     return a, out, lse, k_new, v_new, (query, nt, st), alibi
 
 
+def _on_device(dev, launch) -> None:
+    """run the launches with `dev` current"""
+    if _current_device() == dev.index:
+        launch()
+    else:
+        with torch.cuda.device(dev):
+            launch()
+
+
+def _append(lib, decode, args, k_new, v_new, stream) -> None:
+    """k_new / v_new -> the cache rows behind the lengths (`args`: the KvCacheArgs of the decode kernels, the KvPrefillArgs of the prefill kernels)"""
+    if k_new is not None:
+        name = "fasn_kvcache_append" if decode else "fasn_kvprefill_append"
+        _lib.check(getattr(lib, name)(args, _view4(k_new), _view4(v_new), stream), name)
+
+
+def _forward(lib, decode, args, dev, stream, alibi=None, win=None) -> None:
+    """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (`alibi`) or of their window siblings (`win`)"""
+    stem = "kvcache" if decode else "kvprefill"
+    name, operand = (f"fasn_fwd_{stem}_alibi", (alibi,)) if alibi is not None else (f"fasn_fwd_{stem}_window", (win,)) if win is not None else (
+        f"fasn_fwd_{stem}", ())
+    if win is None:   # (the ALiBi kernels: the base call's workspace)
+        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_workspace_bytes")(args)
+    else:
+        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_window_workspace_bytes")(args, win)
+    # torch's caching allocator: capturable, as _launch_fwd's. Decode always combines its split partials and always passes a pointer; a
+    # prefill of one split has no partials and takes no workspace
+    if decode:
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+    else:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
+    _lib.check(getattr(lib, name)(args, *operand, None if ws is None else ws.data_ptr(), ws_bytes, stream), name)
+
+
 def flash_attention_n_kvcache(
         query: Tensor,
         k_cache: Tensor,
@@ -210,20 +272,10 @@ def flash_attention_n_kvcache(
 
     def launch():
         stream = _stream_ptr(dev)
-        if k_new is not None:
-            _lib.check(lib.fasn_kvcache_append(a, _view4(k_new), _view4(v_new), stream), "fasn_kvcache_append")
-        ws_bytes = lib.fasn_fwd_kvcache_workspace_bytes(a)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (torch's caching allocator: capturable, as _launch_fwd's)
-        if alibi is None:
-            _lib.check(lib.fasn_fwd_kvcache(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache")
-        else:   # (the same launches and workspace; the forward kernel's ALiBi sibling)
-            _lib.check(lib.fasn_fwd_kvcache_alibi(a, alibi, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache_alibi")
+        _append(lib, True, a, k_new, v_new, stream)
+        _forward(lib, True, a, dev, stream, alibi=alibi)
 
-    if _current_device() == dev.index:
-        launch()
-    else:
-        with torch.cuda.device(dev):
-            launch()
+    _on_device(dev, launch)
     return (out, lse) if return_lse else out
 
 
@@ -261,18 +313,8 @@ def flash_attention_n_kvcache_prefill(
     """
     fn = "flash_attention_n_kvcache_prefill"
     pa = KvPrefillArgs()
-    if query_seqlens is not None:
-        B = query.shape[0] if query.dim() == 4 else -1
-        if (not isinstance(query_seqlens, Tensor) or query_seqlens.dtype != torch.int32 or query_seqlens.dim() != 1 or query_seqlens.shape[0] != B
-                or not query_seqlens.is_contiguous()):
-            got = f"{query_seqlens.dtype} {tuple(query_seqlens.shape)}" if isinstance(query_seqlens, Tensor) else type(query_seqlens).__name__
-            raise ValueError(f"query_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {got}")
-        if query_seqlens.device != query.device:
-            raise RuntimeError(f"query_seqlens is on {query_seqlens.device}, query on {query.device}: every operand must live on the query's "
-                               "device (the lengths are read by the kernels, never on the host)")
-    if query.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and query.shape[1] // k_cache.shape[2] > 128 and query.shape[1] % k_cache.shape[2] == 0:
-        raise ValueError(f"{fn}: {query.shape[1] // k_cache.shape[2]} query heads per K/V head are not supported (at most 128: the heads of a "
-                         "K/V head share one workgroup)")
+    _check_query_seqlens(fn, query_seqlens, query)
+    _check_group_limit(fn, query, k_cache)
     _a, out, lse, k_new, v_new, _keep, alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
                                                         softmax_n_param, scale, is_causal, return_lse, args=pa.kv, alibi_slopes=alibi_slopes)
     pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
@@ -281,21 +323,10 @@ def flash_attention_n_kvcache_prefill(
 
     def launch():
         stream = _stream_ptr(dev)
-        if k_new is not None:
-            _lib.check(lib.fasn_kvprefill_append(pa, _view4(k_new), _view4(v_new), stream), "fasn_kvprefill_append")
-        ws_bytes = lib.fasn_fwd_kvprefill_workspace_bytes(pa)
-        # (one split: no partials, no workspace; otherwise torch's caching allocator: capturable, as _launch_fwd's)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-        if alibi is None:
-            _lib.check(lib.fasn_fwd_kvprefill(pa, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill")
-        else:   # (the same launches and workspace; the forward kernel's ALiBi sibling)
-            _lib.check(lib.fasn_fwd_kvprefill_alibi(pa, alibi, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill_alibi")
+        _append(lib, False, pa, k_new, v_new, stream)
+        _forward(lib, False, pa, dev, stream, alibi=alibi)
 
-    if _current_device() == dev.index:
-        launch()
-    else:
-        with torch.cuda.device(dev):
-            launch()
+    _on_device(dev, launch)
     return (out, lse) if return_lse else out
 
 
@@ -335,23 +366,9 @@ def flash_attention_n_kvcache_window(
     as in the other cache calls. The work and the K/V traffic follow the window, not the length.
     """
     fn = "flash_attention_n_kvcache_window"
-    if isinstance(window, bool) or not isinstance(window, int):
-        raise TypeError(f"{fn}: window must be a Python int (a constant of the layer, part of a captured graph; never a tensor); "
-                        f"got {type(window).__name__}")
-    if window < 1:
-        raise ValueError(f"{fn}: window must be >= 1 (the keys a position sees, its own included); got {window}")
-    if query_seqlens is not None:
-        B = query.shape[0] if query.dim() == 4 else -1
-        if (not isinstance(query_seqlens, Tensor) or query_seqlens.dtype != torch.int32 or query_seqlens.dim() != 1 or query_seqlens.shape[0] != B
-                or not query_seqlens.is_contiguous()):
-            got = f"{query_seqlens.dtype} {tuple(query_seqlens.shape)}" if isinstance(query_seqlens, Tensor) else type(query_seqlens).__name__
-            raise ValueError(f"query_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {got}")
-        if query_seqlens.device != query.device:
-            raise RuntimeError(f"query_seqlens is on {query_seqlens.device}, query on {query.device}: every operand must live on the query's "
-                               "device (the lengths are read by the kernels, never on the host)")
-    if query.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and query.shape[1] // k_cache.shape[2] > 128 and query.shape[1] % k_cache.shape[2] == 0:
-        raise ValueError(f"{fn}: {query.shape[1] // k_cache.shape[2]} query heads per K/V head are not supported (at most 128: the heads of a "
-                         "K/V head share one workgroup)")
+    _check_window(fn, window)
+    _check_query_seqlens(fn, query_seqlens, query)
+    _check_group_limit(fn, query, k_cache)
     pa = KvPrefillArgs()   # (its first member is the decode call's argument block)
     a, out, lse, k_new, v_new, _keep, _alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
                                                         softmax_n_param, scale, True, return_lse, args=pa.kv)
@@ -363,24 +380,11 @@ def flash_attention_n_kvcache_window(
 
     def launch():
         stream = _stream_ptr(dev)
-        if decode:
-            if k_new is not None:
-                _lib.check(lib.fasn_kvcache_append(a, _view4(k_new), _view4(v_new), stream), "fasn_kvcache_append")
-            ws_bytes = lib.fasn_fwd_kvcache_window_workspace_bytes(a, win)
-            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (torch's caching allocator: capturable)
-            _lib.check(lib.fasn_fwd_kvcache_window(a, win, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache_window")
-            return
-        if k_new is not None:
-            _lib.check(lib.fasn_kvprefill_append(pa, _view4(k_new), _view4(v_new), stream), "fasn_kvprefill_append")
-        ws_bytes = lib.fasn_fwd_kvprefill_window_workspace_bytes(pa, win)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None   # (one split: no partials, no workspace)
-        _lib.check(lib.fasn_fwd_kvprefill_window(pa, win, None if ws is None else ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvprefill_window")
+        args = a if decode else pa
+        _append(lib, decode, args, k_new, v_new, stream)
+        _forward(lib, decode, args, dev, stream, win=win)
 
-    if _current_device() == dev.index:
-        launch()
-    else:
-        with torch.cuda.device(dev):
-            launch()
+    _on_device(dev, launch)
     return (out, lse) if return_lse else out
 
 
@@ -431,11 +435,7 @@ def flash_attention_n_kvcache_rope(
     """
     fn = "flash_attention_n_kvcache_rope"
     if window is not None:
-        if isinstance(window, bool) or not isinstance(window, int):
-            raise TypeError(f"{fn}: window must be None or a Python int (a constant of the layer, part of a captured graph; never a tensor); "
-                            f"got {type(window).__name__}")
-        if window < 1:
-            raise ValueError(f"{fn}: window must be >= 1 (the keys a position sees, its own included); got {window}")
+        _check_window(fn, window, or_none="None or ")
         if not is_causal:
             raise ValueError(f"{fn}: a sliding window is always causal; window={window} needs is_causal=True")
     for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
@@ -447,18 +447,8 @@ def flash_attention_n_kvcache_rope(
                          f"{rotary_cos.dtype} and {tuple(rotary_sin.shape)} {rotary_sin.dtype}")
     if rotary_cos.dtype != torch.float32 and rotary_cos.dtype != query.dtype:
         raise ValueError(f"{fn}: rotary_cos / rotary_sin must be float32 or the dtype of query ({query.dtype}); got {rotary_cos.dtype}")
-    if query_seqlens is not None:
-        B = query.shape[0] if query.dim() == 4 else -1
-        if (not isinstance(query_seqlens, Tensor) or query_seqlens.dtype != torch.int32 or query_seqlens.dim() != 1 or query_seqlens.shape[0] != B
-                or not query_seqlens.is_contiguous()):
-            got = f"{query_seqlens.dtype} {tuple(query_seqlens.shape)}" if isinstance(query_seqlens, Tensor) else type(query_seqlens).__name__
-            raise ValueError(f"query_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {got}")
-        if query_seqlens.device != query.device:
-            raise RuntimeError(f"query_seqlens is on {query_seqlens.device}, query on {query.device}: every operand must live on the query's "
-                               "device (the lengths are read by the kernels, never on the host)")
-    if query.dim() == 4 and k_cache.dim() == 4 and k_cache.shape[2] >= 1 and query.shape[1] // k_cache.shape[2] > 128 and query.shape[1] % k_cache.shape[2] == 0:
-        raise ValueError(f"{fn}: {query.shape[1] // k_cache.shape[2]} query heads per K/V head are not supported (at most 128: the heads of a "
-                         "K/V head share one workgroup)")
+    _check_query_seqlens(fn, query_seqlens, query)
+    _check_group_limit(fn, query, k_cache)
     rows, rd = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
     esize = rotary_cos.element_size()
 
@@ -502,31 +492,13 @@ def flash_attention_n_kvcache_rope(
 
     def launch():
         stream = _stream_ptr(dev)
-        if decode:
-            _lib.check(lib.fasn_kvcache_rope_append(a, rope, _view4(q_rot), kn_view, vn_view, stream), "fasn_kvcache_rope_append")
-            a.q = _view4(q_rot)   # the forward reads the rotated queries
-            ws_bytes = lib.fasn_fwd_kvcache_workspace_bytes(a) if win is None else lib.fasn_fwd_kvcache_window_workspace_bytes(a, win)
-            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # (torch's caching allocator: capturable)
-            if win is None:
-                _lib.check(lib.fasn_fwd_kvcache(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache")
-            else:
-                _lib.check(lib.fasn_fwd_kvcache_window(a, win, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvcache_window")
-            return
-        _lib.check(lib.fasn_kvprefill_rope_append(pa, rope, _view4(q_rot), kn_view, vn_view, stream), "fasn_kvprefill_rope_append")
-        a.q = _view4(q_rot)
-        ws_bytes = lib.fasn_fwd_kvprefill_workspace_bytes(pa) if win is None else lib.fasn_fwd_kvprefill_window_workspace_bytes(pa, win)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None   # (one split: no partials, no workspace)
-        wsp = None if ws is None else ws.data_ptr()
-        if win is None:
-            _lib.check(lib.fasn_fwd_kvprefill(pa, wsp, ws_bytes, stream), "fasn_fwd_kvprefill")
-        else:
-            _lib.check(lib.fasn_fwd_kvprefill_window(pa, win, wsp, ws_bytes, stream), "fasn_fwd_kvprefill_window")
+        args = a if decode else pa
+        name = "fasn_kvcache_rope_append" if decode else "fasn_kvprefill_rope_append"
+        _lib.check(getattr(lib, name)(args, rope, _view4(q_rot), kn_view, vn_view, stream), name)
+        a.q = _view4(q_rot)   # the forward reads the rotated queries
+        _forward(lib, decode, args, dev, stream, win=win)
 
-    if _current_device() == dev.index:
-        launch()
-    else:
-        with torch.cuda.device(dev):
-            launch()
+    _on_device(dev, launch)
     return (out, lse) if return_lse else out
 
 
