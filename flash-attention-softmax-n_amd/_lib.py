@@ -30,6 +30,7 @@ EXPORTS = (
     "fasn_fwd_kvcache_window_workspace_bytes", "fasn_fwd_kvcache_window", "fasn_kvcache_window_plan",
     "fasn_fwd_kvprefill_window_workspace_bytes", "fasn_fwd_kvprefill_window", "fasn_kvprefill_window_plan",
     "fasn_kvcache_rope_append", "fasn_kvprefill_rope_append", "fasn_kvcache_rope_append_plan", "fasn_kvprefill_rope_append_plan",
+    "fasn_fwd_kvvarlen_workspace_bytes", "fasn_fwd_kvvarlen", "fasn_kvvarlen_append", "fasn_kvvarlen_plan",
 )
 
 
@@ -83,6 +84,12 @@ class KvPrefillArgs(Structure):
     _fields_ = [("kv", KvCacheArgs), ("q_seqlens", c_void_p)]
 
 
+class KvVarlenArgs(Structure):
+    """fasn_kvvarlen_args (include/fasn.h): the prefill arguments on token-packed queries - B sequences, their token offsets in device
+    memory, the rows of the token buffers"""
+    _fields_ = [("pf", KvPrefillArgs), ("cu_seqlens_q", c_void_p), ("total_tokens", c_int32), ("reserved", c_int32)]
+
+
 class AlibiSlopes(Structure):
     """fasn_alibi_slopes (include/fasn.h): per-(batch, query head) fp32 ALiBi slopes in device memory, for the *_alibi cache calls"""
     _fields_ = [("slopes", c_void_p), ("stride_b", c_int64), ("stride_h", c_int64)]
@@ -107,8 +114,8 @@ _lib = None
 
 
 def _kv_bindings():
-    """(name, restype, argtypes) of the 22 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
-    block (fasn_kvprefill_args); `operands` come between the block and the tail"""
+    """(name, restype, argtypes) of the 26 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
+    block (fasn_kvprefill_args), `operands` come between the block and the tail; then the four of the packed block (fasn_kvvarlen_args)"""
     view, text = POINTER(View4), [c_char_p, c_size_t]
     launch = [c_void_p]                          # the stream
     forward = [c_void_p, c_size_t, c_void_p]     # workspace, its bytes, the stream
@@ -127,6 +134,11 @@ def _kv_bindings():
                 (f"fasn_{stem}_window_plan", c_int32, [POINTER(KvWindow)], text),
                 (f"fasn_{stem}_rope_append_plan", c_int32, rope, text)):
             yield name, restype, [block] + operands + tail
+    packed = [POINTER(KvVarlenArgs)]
+    yield "fasn_fwd_kvvarlen_workspace_bytes", c_size_t, packed
+    yield "fasn_fwd_kvvarlen", c_int32, packed + forward
+    yield "fasn_kvvarlen_append", c_int32, packed + [view, view] + launch
+    yield "fasn_kvvarlen_plan", c_int32, packed + text
 
 
 def load():
@@ -245,6 +257,11 @@ def kvprefill_plan(args, alibi=None):
     """The kernels fasn_fwd_kvprefill would launch for `args` (a KvPrefillArgs), as launch_plan returns them; with `alibi` (an AlibiSlopes)
     those of fasn_fwd_kvprefill_alibi. Nothing is launched."""
     return _kv_plan("fasn_kvprefill_plan", args) if alibi is None else _kv_plan("fasn_kvprefill_alibi_plan", args, alibi)
+
+
+def kvvarlen_plan(args):
+    """The kernels fasn_fwd_kvvarlen would launch for `args` (a KvVarlenArgs), as launch_plan returns them. Nothing is launched."""
+    return _kv_plan("fasn_kvvarlen_plan", args)
 
 
 def kvcache_window_plan(args, win):

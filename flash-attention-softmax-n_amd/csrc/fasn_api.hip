@@ -48,6 +48,10 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
         {"fasn_kvprefill_combine_kernel", "T D"},
         {"fasn_kvprefill_append_kernel", "D"},
         {"fasn_kvrope_kernel", "T D"},
+        {"fasn_kvvarlen_schedule_kernel", "NT"},
+        {"fasn_kvvarlen_fwd_kernel", "T D"},
+        {"fasn_kvvarlen_combine_kernel", "T D"},
+        {"fasn_kvvarlen_append_kernel", "D"},
     };
     static const char* const modes[] = {"plain", "causal", "bias+mask", "element-load", "bias", "mask", "keypad", "bias+keypad"};
     if (cap == 0) return 0;

@@ -1,25 +1,29 @@
-// fasn_kv_host.h — the ONE host layer of the K/V-cache family (decode, prefill, rotary append): argument checks, parameter packing, the
-// launch plan, the workspace rule, the launch recorder and the dtype x head-dim dispatch. fasn_kvcache.hip defines what is declared
-// here; fasn_kvcache.hip, fasn_kvprefill.hip and fasn_kvrope.hip each instantiate and launch the kernels of their own header.
+// fasn_kv_host.h — the ONE host layer of the K/V-cache family (decode, prefill, packed prefill, rotary append): argument checks, parameter
+// packing, the launch plan, the workspace rule, the launch recorder and the dtype x head-dim dispatch. fasn_kvcache.hip defines what is
+// declared here; fasn_kvcache.hip, fasn_kvprefill.hip, fasn_kvvarlen.hip and fasn_kvrope.hip each instantiate and launch the kernels of
+// their own header.
 #pragma once
 #include <type_traits>
 #include "fasn.h"
-#include "fasn_kvprefill.h"
+#include "fasn_kvvarlen.h"
 #include "fasn_launch.h"
 
 namespace fasn {
 
 // Which call an argument block belongs to. Decode is the one-row-block case of prefill - the Sq positions of a K/V head are ONE block
 // (PB = Sq, nrb = 1, R = G * Sq rows) - so both fill a KvPrefillParams and the decode kernels take its .kv. Where the checks differ,
-// kv_build names the call.
-enum KvCall { KV_DECODE, KV_PREFILL };
+// kv_build names the call. The packed call is a prefill whose row blocks come from an item table (fasn_kvvarlen.h): B sequences of up
+// to Sq positions each, `packed` carries the offsets and the size of the token buffer.
+enum KvCall { KV_DECODE, KV_PREFILL, KV_VARLEN };
 struct KvArgs {
     const fasn_kvcache_args* a;   // nullptr: refused first, as a NULL block
     const int32_t* q_seqlens;     // the prefill block's; decode has none
     KvCall call;
+    const fasn_kvvarlen_args* packed;   // KV_VARLEN only
 };
-inline KvArgs kv_args(const fasn_kvcache_args* a) { return {a, nullptr, KV_DECODE}; }
-inline KvArgs kv_args(const fasn_kvprefill_args* pa) { return {pa != nullptr ? &pa->kv : nullptr, pa != nullptr ? pa->q_seqlens : nullptr, KV_PREFILL}; }
+inline KvArgs kv_args(const fasn_kvcache_args* a) { return {a, nullptr, KV_DECODE, nullptr}; }
+inline KvArgs kv_args(const fasn_kvprefill_args* pa) { return {pa != nullptr ? &pa->kv : nullptr, pa != nullptr ? pa->q_seqlens : nullptr, KV_PREFILL, nullptr}; }
+inline KvArgs kv_args(const fasn_kvvarlen_args* va) { return {va != nullptr ? &va->pf.kv : nullptr, va != nullptr ? va->pf.q_seqlens : nullptr, KV_VARLEN, va}; }
 
 // what a forward launches with: the parameters, the variant and its operand
 struct KvFwd {
@@ -27,13 +31,15 @@ struct KvFwd {
     KvVariant variant;
     KvAlibi al;
     KvWindow kw;
+    KvPacked pk;          // KV_VARLEN only
 };
 
 inline bool kv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 int kv_check_view(const fasn_view4& v);                                     // the rules of q: o, q_out, k_new, v_new
-int kv_build(const KvArgs& in, KvPrefillParams& pp);                        // the base checks (no HIP call), the parameters, the plan
+// the base checks (no HIP call), the parameters, the plan; the packed call: then the checks of its own operands, and `pk`
+int kv_build(const KvArgs& in, KvPrefillParams& pp, KvPacked* pk = nullptr);
 int kv_pack_new(const fasn_view4& k_new, const fasn_view4& v_new, KvParams& p);   // the views' checks, then p.kn / vn / kns / vns
-int kv_build_append(const KvArgs& in, const fasn_view4* k_new, const fasn_view4* v_new, KvPrefillParams& pp);
+int kv_build_append(const KvArgs& in, const fasn_view4* k_new, const fasn_view4* v_new, KvPrefillParams& pp, KvPacked* pk = nullptr);
 size_t kv_workspace_bytes(const KvArgs& in, KvVariant variant, const void* operand);
 // everything a forward does before its launches: base checks, the variant's operand (nothing, a fasn_alibi_slopes, a fasn_kv_window),
 // then the workspace

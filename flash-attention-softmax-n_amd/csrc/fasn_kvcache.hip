@@ -1,5 +1,5 @@
 // K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi|_window], fasn_kvcache_append, fasn_kvcache[_alibi|_window]_plan), in two parts:
-//   1. the host layer of the whole K/V-cache family (fasn_kv_host.h declares it; fasn_kvprefill.hip and fasn_kvrope.hip call it): argument
+//   1. the host layer of the whole K/V-cache family (fasn_kv_host.h declares it; fasn_kvprefill.hip, fasn_kvvarlen.hip and fasn_kvrope.hip call it): argument
 //      checks, parameter packing, the launch plan - which depends on shapes and capacity only, never on the lengths in device memory -
 //      the operand checks of the ALiBi and window variants and the workspace rule;
 //   2. the decode entry points and the launches of fasn_kvcache.h.
@@ -29,9 +29,9 @@ int64_t kv_min_tps(int R) { return R / 8 > 4 ? R / 8 : 4; }
 // D = 256, kv_split_target), each with enough tiles of a FULL cache to pay for its partial - so a prefill whose row blocks fill the
 // chip has one split, no partials and no combine launch. Head dims: 32, 64, 128, 256 (kv_head_dim_ok).
 // The order of the checks decides which code a block that breaks two rules gets: tests/golden/kvhost_matrix.txt pins it.
-int kv_build(const KvArgs& in, KvPrefillParams& pp) {
+int kv_build(const KvArgs& in, KvPrefillParams& pp, KvPacked* pk) {
     const fasn_kvcache_args* a = in.a;
-    const bool prefill = in.call == KV_PREFILL;
+    const bool prefill = in.call != KV_DECODE;   // (the packed call is a prefill)
     if (a == nullptr) return FASN_EINVAL;
     if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->D <= 0 || a->page_size <= 0) return FASN_EINVAL;
     if (a->dtype != FASN_DTYPE_F16 && a->dtype != FASN_DTYPE_BF16) return FASN_EDTYPE;
@@ -97,7 +97,18 @@ int kv_build(const KvArgs& in, KvPrefillParams& pp) {
     pp.qlens = in.q_seqlens;
     pp.PB = prefill ? KVP_ROWS / G : a->Sq;
     pp.nrb = (a->Sq + pp.PB - 1) / pp.PB;   // (decode: 1)
-    const int64_t base = (int64_t)p.B * p.Hkv * pp.nrb;
+    int64_t base = (int64_t)p.B * p.Hkv * pp.nrb;
+    if (in.call == KV_VARLEN) {
+        // The packed operands, behind every base rule: B sequences whose lengths come from cu_seqlens_q alone, in a buffer of
+        // total_tokens rows. The grid follows the item table's bound, not B * nrb: one split count for the whole launch.
+        const fasn_kvvarlen_args* va = in.packed;
+        if (va->cu_seqlens_q == nullptr || in.q_seqlens != nullptr || va->total_tokens <= 0 || va->reserved != 0 || pk == nullptr) return FASN_EINVAL;
+        if (reinterpret_cast<uintptr_t>(va->cu_seqlens_q) % 4) return FASN_EALIGN;
+        const int64_t items_max = kvv_items_max(p.B, p.Sq, va->total_tokens, pp.PB);
+        if (items_max * p.Hkv > INT_MAX / KVP_ROWS) return FASN_EINVAL;
+        *pk = KvPacked{va->cu_seqlens_q, nullptr, va->total_tokens, (int)items_max};
+        base = items_max * p.Hkv;
+    }
     const int64_t cap_tiles = (capacity + KV_KT - 1) / KV_KT;
     p.nsplit = (int)kv_nsplit(a->D, base, cap_tiles, kv_min_tps(p.R));
     if (base * p.nsplit > (prefill ? INT_MAX / KVP_ROWS : INT_MAX)) return FASN_EINVAL;   // (prefill: times the row slots of a workgroup)
@@ -117,8 +128,8 @@ int kv_pack_new(const fasn_view4& k_new, const fasn_view4& v_new, KvParams& p) {
     return FASN_OK;
 }
 
-int kv_build_append(const KvArgs& in, const fasn_view4* k_new, const fasn_view4* v_new, KvPrefillParams& pp) {
-    const int rc = kv_build(in, pp);
+int kv_build_append(const KvArgs& in, const fasn_view4* k_new, const fasn_view4* v_new, KvPrefillParams& pp, KvPacked* pk) {
+    const int rc = kv_build(in, pp, pk);
     if (rc) return rc;
     if (k_new == nullptr || v_new == nullptr) return FASN_EINVAL;
     return kv_pack_new(*k_new, *v_new, pp.kv);
@@ -148,7 +159,8 @@ int kv_build_window(const fasn_kvcache_args* a, const fasn_kv_window* w, KvPrefi
 }
 
 int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, KvFwd& f) {
-    int rc = kv_build(in, f.pp);
+    f.pk = KvPacked{};
+    int rc = kv_build(in, f.pp, &f.pk);
     if (rc) return rc;
     f.variant = variant;
     f.al = KvAlibi{};
@@ -159,11 +171,16 @@ int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, K
 }
 
 // the split partials: [B * Hkv * nrb][nsplit][R][D] and [...][R][2] floats. Decode always writes them and combines; a prefill of one
-// split stores o / lse itself and needs none.
-size_t kv_part_elems(const KvPrefillParams& pp) { return (size_t)pp.kv.B * pp.kv.Hkv * pp.nrb * pp.kv.nsplit * pp.kv.R; }
-size_t kv_ws_bytes(KvCall call, const KvPrefillParams& pp, int D) {
-    if (call == KV_PREFILL && pp.kv.nsplit <= 1) return 0;
-    return kv_part_elems(pp) * (size_t)(D + 2) * sizeof(float);
+// split stores o / lse itself and needs none. The packed call: [items_max * Hkv] blocks, behind the item table it always has.
+size_t kv_part_elems(KvCall call, const KvFwd& f) {
+    const KvPrefillParams& pp = f.pp;
+    const size_t blocks = call == KV_VARLEN ? (size_t)f.pk.items_max * pp.kv.Hkv : (size_t)pp.kv.B * pp.kv.Hkv * pp.nrb;
+    return blocks * pp.kv.nsplit * pp.kv.R;
+}
+size_t kv_sched_bytes(KvCall call, const KvFwd& f) { return call == KV_VARLEN ? ((size_t)KVV_HEAD + (size_t)KVV_ITEM * f.pk.items_max) * sizeof(int) : 0; }
+size_t kv_ws_bytes(KvCall call, const KvFwd& f, int D) {
+    if (call != KV_DECODE && f.pp.kv.nsplit <= 1) return kv_sched_bytes(call, f);
+    return kv_sched_bytes(call, f) + kv_part_elems(call, f) * (size_t)(D + 2) * sizeof(float);
 }
 
 }  // namespace
@@ -171,18 +188,20 @@ size_t kv_ws_bytes(KvCall call, const KvPrefillParams& pp, int D) {
 size_t kv_workspace_bytes(const KvArgs& in, KvVariant variant, const void* operand) {
     KvFwd f;
     if (kv_build_variant(in, variant, operand, f) != FASN_OK) return 0;
-    return kv_ws_bytes(in.call, f.pp, in.a->D);
+    return kv_ws_bytes(in.call, f, in.a->D);
 }
 
 int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, KvFwd& f) {
     const int rc = kv_build_variant(in, variant, operand, f);
     if (rc) return rc;
-    const size_t need = kv_ws_bytes(in.call, f.pp, in.a->D);
+    const size_t need = kv_ws_bytes(in.call, f, in.a->D);
     if (need > 0) {   // (nothing to write beside o / lse: a NULL workspace is fine)
         if (workspace == nullptr || workspace_bytes < need) return FASN_EWORKSPACE;
         if (!kv_aligned16(workspace)) return FASN_EALIGN;
-        f.pp.kv.part_o = static_cast<float*>(workspace);
-        f.pp.kv.part_ml = f.pp.kv.part_o + kv_part_elems(f.pp) * in.a->D;
+        const size_t sched = kv_sched_bytes(in.call, f);   // (a multiple of 16 bytes: the partials stay aligned)
+        if (sched > 0) f.pk.sched = static_cast<int*>(workspace);
+        f.pp.kv.part_o = reinterpret_cast<float*>(static_cast<char*>(workspace) + sched);
+        f.pp.kv.part_ml = f.pp.kv.part_o + kv_part_elems(in.call, f) * in.a->D;
     }
     return FASN_OK;
 }

@@ -48,6 +48,8 @@ FASN_DEV int kvp_len(const KvPrefillParams& pp, int b, int qlen) {
 
 // fasn_kvprefill_fwd_kernel<Tag, D>(KvPrefillParams), fasn_kvprefill_fwd_alibi_kernel<Tag, D>(KvPrefillParams, KvAlibi) and
 // fasn_kvprefill_fwd_window_kernel<Tag, D>(KvPrefillParams, KvWindow): one text, compiled three times, for the reason fasn_kvcache.h gives.
+// (FASN_KV_PACKED: the token-packed sibling of fasn_kvvarlen.h, a fourth compilation of the same text.)
+#define FASN_KV_PACKED 0
 #define FASN_KV_WINDOW 0
 #define FASN_KV_ALIBI 0
 #include "fasn_kvprefill_fwd.inc"
@@ -61,6 +63,7 @@ FASN_DEV int kvp_len(const KvPrefillParams& pp, int b, int qlen) {
 #include "fasn_kvprefill_fwd.inc"
 #undef FASN_KV_WINDOW
 #undef FASN_KV_ALIBI
+#undef FASN_KV_PACKED
 
 // Merge the partials of a row slot (the arithmetic of fasn_kvcache_combine_kernel) and scatter it through the block map: slot r of
 // (b, hkv, rb) is o[b, hkv * G + r / PB, rb * PB + r % PB, :]. Padding positions get zeros / -inf here; their partials are never read.

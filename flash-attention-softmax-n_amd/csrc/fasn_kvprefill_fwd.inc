@@ -1,8 +1,14 @@
 // fasn_kvprefill_fwd.inc - the text of the prefill forward kernel, included by fasn_kvprefill.h once per variant (no include guard):
 // FASN_KV_ALIBI / FASN_KV_WINDOW = 0 / 0, 1 / 0, 0 / 1. With both at 0 the preprocessor leaves fasn_kvprefill_fwd_kernel exactly as it
 // was before the variants existed, and with FASN_KV_WINDOW == 0 the ALiBi kernel as it was before the window kernel did.
+// FASN_KV_PACKED = 1 (fasn_kvvarlen.h, with the other two at 0) is the token-packed sibling: its (sequence, row block) comes from the item
+// table of fasn_kvvarlen_schedule_kernel, not from the grid, and its rows are tokens of one [T, H, D] buffer. With FASN_KV_PACKED == 0
+// the three kernels above are what they were. The switch is orthogonal to the other two: packed ALiBi / window siblings are two more
+// inclusions.
 template <typename Tag, int D>
-#if FASN_KV_ALIBI
+#if FASN_KV_PACKED
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvvarlen_fwd_kernel(const KvPrefillParams pp, const KvPacked pk) {
+#elif FASN_KV_ALIBI
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_alibi_kernel(const KvPrefillParams pp, const KvAlibi al) {
 #elif FASN_KV_WINDOW
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_window_kernel(const KvPrefillParams pp, const KvWindow win) {
@@ -31,6 +37,34 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     const int l31 = lane & 31;
     const int hi = lane >> 5;
 
+#if FASN_KV_PACKED
+    // ---- (item, K/V head, split): splits of a block are neighbours, the K/V heads of an item follow each other. The item - sequence,
+    // row block, first token and query length of the sequence, clamped by the schedule kernel - is read wave-uniform, as kvp_qlen is;
+    // a workgroup beyond the item count leaves before it reads anything else
+    const int wg = (int)blockIdx.x;
+    const int split = wg % p.nsplit;
+    const int rest = wg / p.nsplit;
+    const int hkv = rest % p.Hkv;
+    const int item = rest / p.Hkv;
+    if (item >= __builtin_amdgcn_readfirstlane(pk.sched[0])) return;
+    const int* const it = pk.sched + KVV_HEAD + item * KVV_ITEM;
+    const int b = __builtin_amdgcn_readfirstlane(it[0]);
+    const int rb = __builtin_amdgcn_readfirstlane(it[1]);
+    const int token0 = __builtin_amdgcn_readfirstlane(it[2]);
+    const int qlen = __builtin_amdgcn_readfirstlane(it[3]);   // >= 1, rb * PB < qlen, token0 + qlen <= T
+    const int pos0 = rb * pp.PB;
+
+    // ---- the lane's row slot: a packed buffer has no padding rows, a slot beyond qlen_b is a neighbouring sequence's token and is
+    // neither read nor written
+    const int row = wave * 32 + l31;
+    const int g = row / pp.PB;
+    const int pos = pos0 + (row - g * pp.PB);
+    const bool slot_ok = g < p.G && pos < qlen;
+    const int h = hkv * p.G + (slot_ok ? g : 0);
+    const int64_t tok = slot_ok ? token0 + pos : token0;
+    const int64_t lse_at = (int64_t)h * pk.T + tok;
+    char* const orow = p.o + (h * p.os[1] + tok * p.os[2]) * 2;
+#else
     // ---- (batch element, K/V head, row block, split): splits of a block are neighbours, the last row block comes first
     const int wg = (int)blockIdx.x;
     const int split = wg % p.nsplit;
@@ -61,6 +95,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
         }
         return;
     }
+#endif
     const int len = kvp_len(pp, b, qlen);
     const bool row_ok = slot_ok && pos < qlen;    // a real position
 
@@ -89,7 +124,11 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 
     vec8 qf[KS];
     {
+#if FASN_KV_PACKED
+        const char* rp = p.q + (h * p.qs[1] + tok * p.qs[2]) * 2 + hi * 16;
+#else
         const char* rp = p.q + (b * p.qs[0] + h * p.qs[1] + (int64_t)pos * p.qs[2]) * 2 + hi * 16;
+#endif
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
             u32x4 raw = {0u, 0u, 0u, 0u};
@@ -313,7 +352,11 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
         return;
     }
     // ---- several splits: the partial of this key range, un-normalised accumulator + (m, l) per row slot
+#if FASN_KV_PACKED
+    const int64_t part = ((int64_t)item * p.Hkv + hkv) * p.nsplit + split;
+#else
     const int64_t part = ((int64_t)bk * pp.nrb + rb) * p.nsplit + split;
+#endif
     float* po = p.part_o + part * KVP_ROWS * D;
     float* pml = p.part_ml + part * KVP_ROWS * 2;
     if (row_ok) {

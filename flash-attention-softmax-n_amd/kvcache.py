@@ -11,6 +11,8 @@ flash_attention_n_kvcache_window is a sliding-window layer on the same cache (fa
 window is a host integer, the kernels walk the window's tiles only and never touch the pages below it.
 flash_attention_n_kvcache_rope rotates `query` and `k_new` by their absolute positions (RoPE) inside the append launch
 (fasn_kvcache_rope_append / fasn_kvprefill_rope_append): the positions come from the lengths in device memory, so the step stays one graph.
+flash_attention_n_kvcache_varlen is the prefill call on TOKEN-PACKED queries (fasn_fwd_kvvarlen / fasn_kvvarlen_append): one [T, H, D]
+buffer and `cu_seqlens_q` on the device - a continuous-batching step of prompt chunks and decode tokens whose grid follows the tokens.
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -20,7 +22,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs, KvRope, KvWindow
+from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs, KvRope, KvVarlenArgs, KvWindow
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
@@ -87,10 +89,12 @@ def _check_group_limit(fn, query, k_cache) -> None:
 
 
 def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal, return_lse,
-             max_rows=None, args=None, alibi_slopes=None):
+             max_rows=None, args=None, alibi_slopes=None, packed_sq=None):
     """The argument checks both entry points share (they need no device and come first) and the filled fasn_kvcache_args.
     Returns (args, out, lse, k_new, v_new, keep, alibi): `keep` holds the tensors whose addresses the arguments carry, `alibi` is the
-    filled fasn_alibi_slopes or None."""
+    filled fasn_alibi_slopes or None. `packed_sq` (flash_attention_n_kvcache_varlen): `query` is the [B, H, T, D] view of a token-packed
+    buffer - batch stride 0, B sequences - and packed_sq the bound of a sequence's query length: out / lse are token-packed ([T, H, D]
+    behind a [1, H, T, D] view, [H, T]) and the block carries Sq = packed_sq."""
     if query.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("query must be [B, H, Sq, D] and the caches [num_pages, page_size, Hkv, D] (paged) or [B, capacity, Hkv, D] (dense)")
     if query.dtype not in _KV_DTYPES:
@@ -140,8 +144,13 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
         raise ValueError("k_new and v_new come together")
     if k_new is not None:
         for name, t in (("k_new", k_new), ("v_new", v_new)):
-            if t.dtype != query.dtype or tuple(t.shape) != (B, Hkv, Sq, D):
+            if packed_sq is not None:   # (Sq is T here)
+                if t.dtype != query.dtype or tuple(t.shape) != (Sq, Hkv, D):
+                    raise ValueError(f"{name} must be [T, Hkv, D] = [{Sq}, {Hkv}, {D}] in {query.dtype}, token-packed like query; got {tuple(t.shape)} {t.dtype}")
+            elif t.dtype != query.dtype or tuple(t.shape) != (B, Hkv, Sq, D):
                 raise ValueError(f"{name} must be [B, Hkv, Sq, D] = [{B}, {Hkv}, {Sq}, {D}] in {query.dtype}; got {tuple(t.shape)} {t.dtype}")
+        if packed_sq is not None:
+            k_new, v_new = k_new.unsqueeze(0).transpose(1, 2), v_new.unsqueeze(0).transpose(1, 2)   # [1, Hkv, T, D] views
         k_new, v_new = _rows(k_new), _rows(v_new)
     query = _rows(query)
     if isinstance(softmax_n_param, Tensor):
@@ -159,8 +168,13 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
         raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
                            "(there is deliberately no CPU fallback)")
 
-    out = torch.empty((B, H, Sq, D), dtype=query.dtype, device=dev)
-    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+    if packed_sq is None:
+        out = torch.empty((B, H, Sq, D), dtype=query.dtype, device=dev)
+        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+    else:   # Sq is T here: one row per token, whatever B is
+        out = torch.empty((Sq, H, D), dtype=query.dtype, device=dev).unsqueeze(0).transpose(1, 2)
+        lse = torch.empty((H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+        Sq = packed_sq
     a = args if args is not None else KvCacheArgs()
     a.q, a.o = _view4(query), _view4(out)
     a.lse = None if lse is None else lse.data_ptr()
@@ -327,6 +341,102 @@ def flash_attention_n_kvcache_prefill(
         _forward(lib, False, pa, dev, stream, alibi=alibi)
 
     _on_device(dev, launch)
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_n_kvcache_varlen(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        cu_seqlens_q: Tensor,
+        max_seqlen_q: int,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False,
+        alibi_slopes=None,
+        window=None,
+        rotary_cos=None,
+        rotary_sin=None):
+    """softmax_n attention of a CONTINUOUS-BATCHING step against a K/V cache, on MI355X: the query positions of all sequences - prompt
+    chunks of thousands of tokens beside decode sequences of one - token-packed in one buffer (vLLM's flash_attn_varlen_func with a
+    block table). The work, the grid and the memory follow the tokens, not B x the longest chunk.
+
+    The cache, `block_table`, `cache_seqlens`, `softmax_n_param`, `scale`, `is_causal`, dtypes, head dims, alignment rules and refusals
+    are those of flash_attention_n_kvcache_prefill. What differs:
+
+    :param query: [T, H, D], T = the size of the step's token buffer (a shape: part of a captured graph).
+    :param cu_seqlens_q: contiguous int32 [B + 1] ON THE DEVICE: cu[0] = 0, non-decreasing, cu[B] <= T. Token cu[b] + i is position
+                  i < qlen_b of sequence b, qlen_b = clamp(cu[b + 1] - cu[b], 0, max_seqlen_q). B = cu_seqlens_q.shape[0] - 1 must be the
+                  B of `cache_seqlens` (and `block_table`). Never read on the host.
+    :param max_seqlen_q: a Python int >= 1: an upper bound of every qlen_b, a constant of a captured graph (with T it sizes the grid).
+    :param k_new, v_new: optional [T, Hkv, D], token-packed like `query`: token cu[b] + i is written to the cache position
+                  cache_seqlens[b] + i first (positions at or beyond the capacity are dropped in the kernel) and then attended to.
+    :param softmax_n_param: n >= 0, or a tensor that broadcasts to [B, H]: per sequence and query head, not per token.
+    :param alibi_slopes, window, rotary_cos, rotary_sin: not supported on packed queries yet; anything but None is refused.
+    :return: [T, H, D] in query's dtype (and lse [H, T] fp32). With len_b = clamp(cache_seqlens[b] + (qlen_b if k_new is given else 0),
+             0, capacity), position i sees key j iff j < len_b and (causal) j <= i + len_b - qlen_b; a token that sees no key gives
+             exactly 0 and lse = log n (-inf for n = 0).
+
+    Tokens at or beyond cu[B] are never read (the buffer may hold NaN there) and their rows of `out` / `lse` are NOT WRITTEN: they hold
+    whatever the allocation held. Nothing is read on the host: the launches depend on T, B, max_seqlen_q, the head counts, D and the
+    capacity only, so one captured graph serves every step. Whatever values `cu_seqlens_q` holds, no kernel touches memory outside the
+    buffers (token indices are clamped to [0, T), lengths as above): malformed offsets give unspecified values but stay safe. One split
+    count serves the whole launch, so the decode tokens of a mixed step get the launch's, not their own.
+    """
+    fn = "flash_attention_n_kvcache_varlen"
+    for name, value in (("alibi_slopes", alibi_slopes), ("window", window), ("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if value is not None:
+            raise NotImplementedError(f"{fn}: {name} is not supported on token-packed queries (no packed ALiBi, window or rotary kernels yet); "
+                                      "pad the step and use flash_attention_n_kvcache_prefill / _window / _rope with query_seqlens")
+    if not isinstance(query, Tensor) or query.dim() != 3:
+        got = tuple(query.shape) if isinstance(query, Tensor) else type(query).__name__
+        raise ValueError(f"{fn}: query must be token-packed [T, H, D]; got {got}")
+    if (not isinstance(cu_seqlens_q, Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.shape[0] < 2
+            or not cu_seqlens_q.is_contiguous()):
+        got = f"{cu_seqlens_q.dtype} {tuple(cu_seqlens_q.shape)}" if isinstance(cu_seqlens_q, Tensor) else type(cu_seqlens_q).__name__
+        raise ValueError(f"{fn}: cu_seqlens_q must be a contiguous int32 tensor of shape [B + 1] on the device (B >= 1); got {got}")
+    if cu_seqlens_q.device != query.device:
+        raise RuntimeError(f"cu_seqlens_q is on {cu_seqlens_q.device}, query on {query.device}: every operand must live on the query's "
+                           "device (the offsets are read by the kernels, never on the host)")
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int):
+        raise TypeError(f"{fn}: max_seqlen_q must be a Python int (a bound of every query length, part of a captured graph; never a tensor); "
+                        f"got {type(max_seqlen_q).__name__}")
+    if max_seqlen_q < 1:
+        raise ValueError(f"{fn}: max_seqlen_q must be >= 1; got {max_seqlen_q}")
+    B = cu_seqlens_q.shape[0] - 1
+    if isinstance(cache_seqlens, Tensor) and cache_seqlens.dim() == 1 and cache_seqlens.shape[0] != B:
+        raise ValueError(f"{fn}: cu_seqlens_q names {B} sequences but cache_seqlens has {cache_seqlens.shape[0]}: B = cu_seqlens_q.shape[0] - 1 "
+                         "is the batch of cache_seqlens and block_table")
+    T = query.shape[0]
+    if T < 1:
+        raise ValueError(f"{fn}: the token buffer is empty (query is {tuple(query.shape)})")
+    # the [B, H, T, D] view of the buffer (batch stride 0): what _prepare takes as a query of B sequences
+    q4 = _rows(query.unsqueeze(0).transpose(1, 2)).expand(B, -1, -1, -1)
+    _check_group_limit(fn, q4, k_cache)
+    va = KvVarlenArgs()
+    _a, out, lse, k_new, v_new, _keep, _alibi = _prepare(fn, q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                                                         softmax_n_param, scale, is_causal, return_lse, args=va.pf.kv,
+                                                         packed_sq=min(max_seqlen_q, 2 ** 31 - 1))
+    va.pf.q_seqlens = None
+    va.cu_seqlens_q, va.total_tokens, va.reserved = cu_seqlens_q.data_ptr(), T, 0
+    lib = _lib.load()
+    dev = query.device
+
+    def launch():
+        stream = _stream_ptr(dev)
+        if k_new is not None:
+            _lib.check(lib.fasn_kvvarlen_append(va, _view4(k_new), _view4(v_new), stream), "fasn_kvvarlen_append")
+        ws_bytes = lib.fasn_fwd_kvvarlen_workspace_bytes(va)   # the item table (+ the split partials): never 0
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        _lib.check(lib.fasn_fwd_kvvarlen(va, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvvarlen")
+
+    _on_device(dev, launch)
+    out = out.transpose(1, 2).squeeze(0)   # [T, H, D]
     return (out, lse) if return_lse else out
 
 

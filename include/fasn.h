@@ -428,6 +428,44 @@ int fasn_kvprefill_rope_append_plan(const fasn_kvprefill_args* args, const fasn_
                                     const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
 
 /*
+ * PREFILL ON TOKEN-PACKED QUERIES (continuous batching; additions within ABI 6, the argument blocks above keep their layouts): the query
+ * positions of all sequences of a step lie behind each other in one buffer of total_tokens rows, and cu_seqlens_q - B + 1 int32 offsets in
+ * DEVICE memory, cu[0] = 0, non-decreasing, cu[B] <= total_tokens - says where each sequence starts (vLLM's flash_attn_varlen_func with a
+ * block table). A step of many one-token sequences and a few long chunks costs what its tokens cost, not B times the longest chunk.
+ *
+ *   pf.kv     as fasn_fwd_kvprefill takes it, with: B = the number of sequences; Sq = max_seqlen_q >= 1, a host bound of every query
+ *             length (a constant of a captured graph); q / o = views of [1, H, total_tokens, D]: stride[1] between heads, stride[2]
+ *             between tokens, stride[0] unused; lse = [H, total_tokens] fp32 or NULL; seqlen_add = 0 or Sq as in the prefill call.
+ *             pf.q_seqlens must be NULL (FASN_EINVAL): the lengths come from the offsets.
+ *   lengths   qlen_b = clamp(cu[b + 1] - cu[b], 0, Sq); token cu[b] + i is position i < qlen_b of sequence b; len_b, visibility, the
+ *             result of a position that sees no key, `n` ([B, H]: per sequence, not per token) and scale are the prefill call's.
+ *   tokens    at or beyond cu[B] are never read; their o / lse rows are not written.
+ *   safety    nothing is read on the host. Whatever cu_seqlens_q holds, no kernel touches memory outside the buffers: token indices are
+ *             clamped to [0, total_tokens), lengths as above. Malformed offsets give unspecified values in o / lse / the appended rows.
+ *
+ * fasn_fwd_kvvarlen launches a schedule kernel - offsets -> a table of (sequence, row block) items in the workspace - the forward on
+ * items_max * (H / kv_group) * nsplit workgroups, items_max = min(B * ceil(Sq / PB), total_tokens / PB + B), PB = 128 / kv_group, and with
+ * several splits a combine kernel. One split count serves the whole launch, from shapes and capacity: the prefill rule over
+ * items_max * (H / kv_group) blocks. The workspace (fasn_fwd_kvvarlen_workspace_bytes, never 0: the table, then the split partials) is
+ * always needed: 16-byte aligned, FASN_EWORKSPACE when missing or too small. fasn_kvvarlen_append writes token t of k_new / v_new (views
+ * of [1, H / kv_group, total_tokens, D]) to cache row seqlens[b] + t - cu[b] of its sequence under the rules of fasn_kvprefill_append.
+ * fasn_kvvarlen_plan writes the launches of fasn_fwd_kvvarlen as text. Every rule and error code of fasn_fwd_kvprefill holds and is checked
+ * first; then cu_seqlens_q == NULL, pf.q_seqlens != NULL, total_tokens < 1 or reserved != 0 is FASN_EINVAL, offsets that are not 4-byte
+ * aligned FASN_EALIGN, a table beyond 2^31 / 128 / (H / kv_group) items FASN_EINVAL. There is no packed ALiBi, window or rotary call yet.
+ */
+typedef struct fasn_kvvarlen_args {
+    fasn_kvprefill_args pf;
+    const int32_t* cu_seqlens_q; /* DEVICE [B + 1] token offsets */
+    int32_t total_tokens;        /* rows of the token buffers; >= 1 */
+    int32_t reserved;            /* 0 */
+} fasn_kvvarlen_args;
+
+size_t fasn_fwd_kvvarlen_workspace_bytes(const fasn_kvvarlen_args* args);
+int fasn_fwd_kvvarlen(const fasn_kvvarlen_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvvarlen_append(const fasn_kvvarlen_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvvarlen_plan(const fasn_kvvarlen_args* args, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).
