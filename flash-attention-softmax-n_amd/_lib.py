@@ -31,6 +31,8 @@ EXPORTS = (
     "fasn_fwd_kvprefill_window_workspace_bytes", "fasn_fwd_kvprefill_window", "fasn_kvprefill_window_plan",
     "fasn_kvcache_rope_append", "fasn_kvprefill_rope_append", "fasn_kvcache_rope_append_plan", "fasn_kvprefill_rope_append_plan",
     "fasn_fwd_kvvarlen_workspace_bytes", "fasn_fwd_kvvarlen", "fasn_kvvarlen_append", "fasn_kvvarlen_plan",
+    "fasn_fwd_kvvarlen_window_workspace_bytes", "fasn_fwd_kvvarlen_window", "fasn_kvvarlen_window_plan",
+    "fasn_kvvarlen_rope_append", "fasn_kvvarlen_rope_append_plan",
 )
 
 
@@ -114,8 +116,8 @@ _lib = None
 
 
 def _kv_bindings():
-    """(name, restype, argtypes) of the 26 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
-    block (fasn_kvprefill_args), `operands` come between the block and the tail; then the four of the packed block (fasn_kvvarlen_args)"""
+    """(name, restype, argtypes) of the 31 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
+    block (fasn_kvprefill_args), `operands` come between the block and the tail; then the nine of the packed block (fasn_kvvarlen_args)"""
     view, text = POINTER(View4), [c_char_p, c_size_t]
     launch = [c_void_p]                          # the stream
     forward = [c_void_p, c_size_t, c_void_p]     # workspace, its bytes, the stream
@@ -139,6 +141,11 @@ def _kv_bindings():
     yield "fasn_fwd_kvvarlen", c_int32, packed + forward
     yield "fasn_kvvarlen_append", c_int32, packed + [view, view] + launch
     yield "fasn_kvvarlen_plan", c_int32, packed + text
+    yield "fasn_fwd_kvvarlen_window_workspace_bytes", c_size_t, packed + [POINTER(KvWindow)]
+    yield "fasn_fwd_kvvarlen_window", c_int32, packed + [POINTER(KvWindow)] + forward
+    yield "fasn_kvvarlen_window_plan", c_int32, packed + [POINTER(KvWindow)] + text
+    yield "fasn_kvvarlen_rope_append", c_int32, packed + rope + launch
+    yield "fasn_kvvarlen_rope_append_plan", c_int32, packed + rope + text
 
 
 def load():
@@ -264,6 +271,12 @@ def kvvarlen_plan(args):
     return _kv_plan("fasn_kvvarlen_plan", args)
 
 
+def kvvarlen_window_plan(args, win):
+    """The kernels fasn_fwd_kvvarlen_window would launch for `args` (a KvVarlenArgs) under `win` (a KvWindow), as launch_plan returns
+    them. Nothing is launched."""
+    return _kv_plan("fasn_kvvarlen_window_plan", args, win)
+
+
 def kvcache_window_plan(args, win):
     """The kernels fasn_fwd_kvcache_window would launch for `args` (a KvCacheArgs) under `win` (a KvWindow), as launch_plan returns them.
     Nothing is launched."""
@@ -277,9 +290,10 @@ def kvprefill_window_plan(args, win):
 
 
 def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):
-    """The one launch of fasn_kvcache_rope_append (`args` a KvCacheArgs) or fasn_kvprefill_rope_append (a KvPrefillArgs) under `rope`
-    (a KvRope), as launch_plan returns it. Nothing is launched."""
-    what = "fasn_kvprefill_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_rope_append_plan"
+    """The one launch of fasn_kvcache_rope_append (`args` a KvCacheArgs), fasn_kvprefill_rope_append (a KvPrefillArgs) or
+    fasn_kvvarlen_rope_append (a KvVarlenArgs) under `rope` (a KvRope), as launch_plan returns it. Nothing is launched."""
+    what = ("fasn_kvvarlen_rope_append_plan" if isinstance(args, KvVarlenArgs) else
+            "fasn_kvprefill_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_rope_append_plan")
     return _kv_plan(what, args, rope, q_out, k_new, v_new)
 
 

@@ -1,7 +1,7 @@
 // fasn_kv_host.h — the ONE host layer of the K/V-cache family (decode, prefill, packed prefill, rotary append): argument checks, parameter
 // packing, the launch plan, the workspace rule, the launch recorder and the dtype x head-dim dispatch. fasn_kvcache.hip defines what is
 // declared here; fasn_kvcache.hip, fasn_kvprefill.hip, fasn_kvvarlen.hip and fasn_kvrope.hip each instantiate and launch the kernels of
-// their own header.
+// their own header (fasn_kvrope.hip: also the packed rotary append, fasn_kvvarlen.hip: also the packed window forward).
 #pragma once
 #include <type_traits>
 #include "fasn.h"

@@ -148,13 +148,14 @@ int kv_build_alibi(const fasn_kvcache_args* a, const fasn_alibi_slopes* s, KvAli
 
 // The window operand of the *_window entry points (checked after the base arguments, before any HIP call), and the plan under it: the
 // base rule over the tiles the window of a workgroup's rows can touch - they span PB positions - never more splits than the base plan has.
-int kv_build_window(const fasn_kvcache_args* a, const fasn_kv_window* w, KvPrefillParams& pp, KvWindow& kw) {
+// `blocks`: the (K/V head, row block) blocks of the launch, B * Hkv * nrb or, on packed queries, items_max * Hkv.
+int kv_build_window(const fasn_kvcache_args* a, const fasn_kv_window* w, int64_t blocks, KvPrefillParams& pp, KvWindow& kw) {
     KvParams& p = pp.kv;
     if (w == nullptr || w->window < 1 || w->reserved != 0) return FASN_EINVAL;
     if (!a->causal) return FASN_EUNSUPPORTED;
     kw = KvWindow{w->window < p.capacity ? w->window : p.capacity};
     const int64_t cap_tiles = ((int64_t)p.capacity + KV_KT - 1) / KV_KT;
-    p.nsplit = (int)kv_nsplit(a->D, (int64_t)p.B * p.Hkv * pp.nrb, kv_window_tiles(cap_tiles, w->window, pp.PB), kv_min_tps(p.R));
+    p.nsplit = (int)kv_nsplit(a->D, blocks, kv_window_tiles(cap_tiles, w->window, pp.PB), kv_min_tps(p.R));
     return FASN_OK;
 }
 
@@ -166,7 +167,10 @@ int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, K
     f.al = KvAlibi{};
     f.kw = KvWindow{};
     if (variant == KV_ALIBI) return kv_build_alibi(in.a, static_cast<const fasn_alibi_slopes*>(operand), f.al);
-    if (variant == KV_WINDOW) return kv_build_window(in.a, static_cast<const fasn_kv_window*>(operand), f.pp, f.kw);
+    if (variant == KV_WINDOW) {
+        const int64_t blocks = in.call == KV_VARLEN ? (int64_t)f.pk.items_max * f.pp.kv.Hkv : (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb;
+        return kv_build_window(in.a, static_cast<const fasn_kv_window*>(operand), blocks, f.pp, f.kw);
+    }
     return FASN_OK;
 }
 

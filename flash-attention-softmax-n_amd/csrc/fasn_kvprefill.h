@@ -48,7 +48,7 @@ FASN_DEV int kvp_len(const KvPrefillParams& pp, int b, int qlen) {
 
 // fasn_kvprefill_fwd_kernel<Tag, D>(KvPrefillParams), fasn_kvprefill_fwd_alibi_kernel<Tag, D>(KvPrefillParams, KvAlibi) and
 // fasn_kvprefill_fwd_window_kernel<Tag, D>(KvPrefillParams, KvWindow): one text, compiled three times, for the reason fasn_kvcache.h gives.
-// (FASN_KV_PACKED: the token-packed sibling of fasn_kvvarlen.h, a fourth compilation of the same text.)
+// (FASN_KV_PACKED: the token-packed siblings of fasn_kvvarlen.h, a fourth and - under a window - a fifth compilation of the same text.)
 #define FASN_KV_PACKED 0
 #define FASN_KV_WINDOW 0
 #define FASN_KV_ALIBI 0

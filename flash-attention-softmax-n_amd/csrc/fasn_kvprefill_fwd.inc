@@ -3,10 +3,13 @@
 // was before the variants existed, and with FASN_KV_WINDOW == 0 the ALiBi kernel as it was before the window kernel did.
 // FASN_KV_PACKED = 1 (fasn_kvvarlen.h, with the other two at 0) is the token-packed sibling: its (sequence, row block) comes from the item
 // table of fasn_kvvarlen_schedule_kernel, not from the grid, and its rows are tokens of one [T, H, D] buffer. With FASN_KV_PACKED == 0
-// the three kernels above are what they were. The switch is orthogonal to the other two: packed ALiBi / window siblings are two more
-// inclusions.
+// the three kernels above are what they were. The switch is orthogonal to the other two: FASN_KV_PACKED = 1 with FASN_KV_WINDOW = 1
+// (fasn_kvvarlen.h) is the packed window sibling - the body's window blocks read qlen, len, pos0 and pos_hi, which the packed branch
+// defines from the item - and a packed ALiBi sibling would be one more inclusion.
 template <typename Tag, int D>
-#if FASN_KV_PACKED
+#if FASN_KV_PACKED && FASN_KV_WINDOW
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvvarlen_fwd_window_kernel(const KvPrefillParams pp, const KvPacked pk, const KvWindow win) {
+#elif FASN_KV_PACKED
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvvarlen_fwd_kernel(const KvPrefillParams pp, const KvPacked pk) {
 #elif FASN_KV_ALIBI
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_alibi_kernel(const KvPrefillParams pp, const KvAlibi al) {

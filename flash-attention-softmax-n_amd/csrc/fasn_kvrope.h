@@ -26,8 +26,11 @@
 // (16-bit tables) or two (fp32 tables) 16-byte vectors each; the units beyond copy chunks 2 u and 2 u + 1. A K/V unit also copies chunks
 // 2 u and 2 u + 1 of the v_new row. Lanes [0, nkv) are the K/V units (b, hkv, i, u), lanes [nkv, nkv + nq) the query units (b, h, i, u):
 // the grid depends on shapes only. Plain 16-byte vector loads and stores, nothing else.
+//
+// fasn_kvvarlen_rope_kernel is the same launch on token-packed rows (fasn_kvvarlen.h): lanes (t, hkv, u) then (t, h, u) over the T tokens
+// of the buffers, the sequence and position of a token from cu_seqlens_q in device memory.
 #pragma once
-#include "fasn_kvprefill.h"
+#include "fasn_kvvarlen.h"
 
 namespace fasn {
 
@@ -118,46 +121,63 @@ __global__ void __launch_bounds__(256) fasn_kvrope_kernel(const KvRopeParams rp)
         src = p.q + (b * p.qs[0] + h * p.qs[1] + (int64_t)i * p.qs[2]) * 2;
         dst = rp.qo + (b * rp.qos[0] + h * rp.qos[1] + (int64_t)i * rp.qos[2]) * 2;
     }
-    const int ru = rp.rd / 16;   // rotated units
-    const bool rot = u < ru;
-    const int c1 = rot && !rp.interleaved ? u : 2 * u, c2 = rot && !rp.interleaved ? u + ru : 2 * u + 1;
-    const u32x4 a = gload16(src + c1 * 16), bq = gload16(src + c2 * 16);
-    if (!rot) {
-        gstore16(dst + c1 * 16, a);
-        gstore16(dst + c2 * 16, bq);
-        return;
+#include "fasn_kvrope_unit.inc"
+}
+
+// fasn_kvrope_kernel on TOKEN-PACKED rows (fasn_kvvarlen.h): one lane per (token t < T, head, unit), the K/V units first. The token's
+// sequence is found as fasn_kvvarlen_append_kernel finds it - a binary search in cu - and a token of no sequence (at or beyond cu[B])
+// or beyond its sequence's clamped length leaves before it reads a row. qlen_b is the schedule kernel's, the T - token0 clamp included:
+// every row of q_out the forward reads through the item table was written here. len_b: kvp_len's rule, restated per lane as above.
+// Under a malformed cu the search still ends at some index; t < T by the grid, b is a sequence index, the cache row lies below the
+// capacity and the table row inside the tables: unspecified values, never an access outside the buffers.
+template <typename Tag, int D>
+__global__ void __launch_bounds__(256) fasn_kvvarlen_rope_kernel(const KvRopeParams rp, const KvPacked pk) {
+    const KvParams& p = rp.kv;
+    constexpr int UPR = D / 16;   // units per row
+    int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= rp.nkv + rp.nq) return;
+    const bool isq = gid >= rp.nkv;
+    if (isq) gid -= rp.nkv;
+    const int u = (int)(gid % UPR);
+    const int64_t rest = gid / UPR;
+    const int heads = isq ? p.H : p.Hkv;
+    const int h = (int)(rest % heads), t = (int)(rest / heads);   // t < T: nkv / nq count T tokens
+    int lo = 0, hi = p.B + 1;   // the first index of cu[0 .. B] whose offset is beyond t
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pk.cu[mid] <= t) lo = mid + 1;
+        else hi = mid;
     }
-    const int64_t trow = min(max(pos, (int64_t)0), (int64_t)rp.rows - 1);
-    float c[8], s[8], e0[8], e1[8], x1[8], x2[8], y1[8], y2[8];
-    kvrope_table<Tag>(rp.cos, trow * rp.trs + 8 * u, rp.tf32, c);
-    kvrope_table<Tag>(rp.sin, trow * rp.trs + 8 * u, rp.tf32, s);
-    kvrope_widen<Tag>(a, e0);
-    kvrope_widen<Tag>(bq, e1);
-    if (rp.interleaved) {   // the 16 elements are the pairs (2 j, 2 j + 1)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) x1[j] = e0[2 * j], x2[j] = e0[2 * j + 1], x1[4 + j] = e1[2 * j], x2[4 + j] = e1[2 * j + 1];
+    const int b = lo - 1;
+    if (b < 0 || b >= p.B) return;   // a token at or beyond cu[B] (or in front of cu[0])
+    const int64_t c0 = pk.cu[b];
+    const int64_t i = t - c0;        // >= 0: cu[b] <= t
+    const int token0 = (int)min(max(c0, (int64_t)0), (int64_t)pk.T);
+    int qlen = (int)min(max((int64_t)pk.cu[b + 1] - c0, (int64_t)0), (int64_t)p.Sq);
+    qlen = min(qlen, pk.T - token0);
+    if (i >= qlen) return;
+    int64_t pos;
+    const char* src;
+    char* dst;
+    if (!isq) {
+        pos = (int64_t)p.seqlens[b] + i;
+        if (pos < 0 || pos >= p.capacity) return;   // dropped: the host does not know the lengths
+        const int slot = (int)(pos / p.page_size), rip = (int)(pos % p.page_size);
+        const int64_t page = p.bt != nullptr ? p.bt[(int64_t)b * p.bts + slot] : b;
+        src = p.kn + (h * p.kns[1] + (int64_t)t * p.kns[2]) * 2;
+        dst = p.k + (page * p.kps + (int64_t)rip * p.krs + (int64_t)h * p.khs) * 2;
+        const char* const vsrc = p.vn + (h * p.vns[1] + (int64_t)t * p.vns[2]) * 2 + u * 32;
+        char* const vdst = p.v + (page * p.vps + (int64_t)rip * p.vrs + (int64_t)h * p.vhs) * 2 + u * 32;
+        const u32x4 v0 = gload16(vsrc), v1 = gload16(vsrc + 16);
+        gstore16(vdst, v0);
+        gstore16(vdst + 16, v1);
     } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) x1[j] = e0[j], x2[j] = e1[j];
+        const int len = (int)min(max((int64_t)p.seqlens[b] + (rp.add_qlen ? qlen : 0), (int64_t)0), (int64_t)p.capacity);
+        pos = i + len - qlen;
+        src = p.q + (h * p.qs[1] + (int64_t)t * p.qs[2]) * 2;
+        dst = rp.qo + (h * rp.qos[1] + (int64_t)t * rp.qos[2]) * 2;
     }
-    {
-#pragma clang fp contract(off)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float ac = x1[j] * c[j], bs = x2[j] * s[j], bc = x2[j] * c[j], as = x1[j] * s[j];
-            y1[j] = ac - bs;
-            y2[j] = bc + as;
-        }
-    }
-    if (rp.interleaved) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) e0[2 * j] = y1[j], e0[2 * j + 1] = y2[j], e1[2 * j] = y1[4 + j], e1[2 * j + 1] = y2[4 + j];
-    } else {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) e0[j] = y1[j], e1[j] = y2[j];
-    }
-    gstore16(dst + c1 * 16, kvrope_round<Tag>(e0));
-    gstore16(dst + c2 * 16, kvrope_round<Tag>(e1));
+#include "fasn_kvrope_unit.inc"
 }
 
 }  // namespace fasn

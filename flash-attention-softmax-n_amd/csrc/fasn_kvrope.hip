@@ -1,5 +1,5 @@
-// Rotary rotate-and-append on the K/V-cache calls (include/fasn.h: fasn_kvcache_rope_append, fasn_kvprefill_rope_append and their
-// *_plan siblings): the base call's argument checks first (the family's, fasn_kv_host.h), then the operand's, which live here, and the
+// Rotary rotate-and-append on the K/V-cache calls (include/fasn.h: fasn_kvcache_rope_append, fasn_kvprefill_rope_append,
+// fasn_kvvarlen_rope_append and their *_plan siblings): the base call's argument checks first (the family's, fasn_kv_host.h), then the operand's, which live here, and the
 // one launch of fasn_kvrope.h - whose grid depends on shapes only, never on the lengths in device memory.
 #include <limits.h>
 #include "fasn_kv_host.h"
@@ -9,9 +9,9 @@ namespace fasn {
 namespace {
 
 // The operand's checks (after the base arguments, before any HIP call) and the kernel parameters. `rp.kv` / `rp.qlens` are the base
-// call's; `prefill`: the length rule of fasn_fwd_kvprefill.
-int kvr_build(const fasn_kvcache_args* a, bool prefill, const fasn_kv_rope* r, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
-              KvRopeParams& rp) {
+// call's; `prefill`: the length rule of fasn_fwd_kvprefill; `rows`: the rows of a head in q / k_new - B * Sq, packed: total_tokens.
+int kvr_build(const fasn_kvcache_args* a, bool prefill, int64_t rows, const fasn_kv_rope* r, const fasn_view4* q_out, const fasn_view4* k_new,
+              const fasn_view4* v_new, KvRopeParams& rp) {
     KvParams& p = rp.kv;
     if (r == nullptr || r->cos == nullptr || r->sin == nullptr || q_out == nullptr) return FASN_EINVAL;
     if ((k_new == nullptr) != (v_new == nullptr)) return FASN_EINVAL;
@@ -37,8 +37,8 @@ int kvr_build(const fasn_kvcache_args* a, bool prefill, const fasn_kv_rope* r, c
     rp.interleaved = r->interleaved;
     rp.add_qlen = prefill ? (a->seqlen_add != 0 ? 1 : 0) : -1;
     const int64_t upr = a->D / 16;
-    rp.nkv = k_new != nullptr ? (int64_t)p.B * p.Hkv * p.Sq * upr : 0;
-    rp.nq = (int64_t)p.B * p.H * p.Sq * upr;
+    rp.nkv = k_new != nullptr ? rows * p.Hkv * upr : 0;
+    rp.nq = rows * p.H * upr;
     if ((rp.nkv + rp.nq + 255) / 256 > INT_MAX) return FASN_EINVAL;
     return FASN_OK;
 }
@@ -48,15 +48,25 @@ int kvr_launch(const KvRopeParams& rp, hipStream_t s) {
     FASN_LAUNCH((fasn_kvrope_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp);
     return launch_rc();
 }
+template <typename Tag, int D>
+int kvr_launch_packed(const KvRopeParams& rp, const KvPacked& pk, hipStream_t s) {
+    FASN_LAUNCH((fasn_kvvarlen_rope_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, pk);
+    return launch_rc();
+}
 
 int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
     KvPrefillParams pp;
-    int rc = kv_build(in, pp);
+    KvPacked pk{};
+    int rc = kv_build(in, pp, &pk);
     if (rc) return rc;
     KvRopeParams rp{};
     rp.kv = pp.kv;
     rp.qlens = pp.qlens;
-    if ((rc = kvr_build(in.a, in.call == KV_PREFILL, rope, q_out, k_new, v_new, rp))) return rc;
+    const bool packed = in.call == KV_VARLEN;
+    const int64_t rows = packed ? (int64_t)pk.T : (int64_t)pp.kv.B * pp.kv.Sq;
+    if ((rc = kvr_build(in.a, in.call != KV_DECODE, rows, rope, q_out, k_new, v_new, rp))) return rc;
+    if (packed)
+        return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch_packed<decltype(tag), decltype(d)::value>(rp, pk, (hipStream_t)stream); });
     return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch<decltype(tag), decltype(d)::value>(rp, (hipStream_t)stream); });
 }
 
@@ -84,6 +94,16 @@ int fasn_kvcache_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_r
 
 int fasn_kvprefill_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                                     const fasn_view4* v_new, char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kvr_call(kv_args(args), rope, q_out, k_new, v_new, nullptr); });
+}
+
+int fasn_kvvarlen_rope_append(const fasn_kvvarlen_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
+                              const fasn_view4* v_new, fasn_stream_t stream) {
+    return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream);
+}
+
+int fasn_kvvarlen_rope_append_plan(const fasn_kvvarlen_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
+                                   const fasn_view4* v_new, char* buf, size_t cap) {
     return kv_plan(buf, cap, [&] { return kvr_call(kv_args(args), rope, q_out, k_new, v_new, nullptr); });
 }
 

@@ -4,6 +4,7 @@
 //
 //   fasn_kvvarlen_schedule_kernel  cu -> the item table: one item per (sequence, row block) that holds a token
 //   fasn_kvvarlen_fwd_kernel       fasn_kvprefill_fwd.inc under FASN_KV_PACKED: one workgroup per (item, K/V head, split)
+//   fasn_kvvarlen_fwd_window_kernel  the same kernel over the tiles of a sliding window only (FASN_KV_PACKED and FASN_KV_WINDOW)
 //   fasn_kvvarlen_combine_kernel   (several splits only) merges the partials and scatters the rows through the item table
 //   fasn_kvvarlen_append_kernel    k_new / v_new row t -> cache row seqlens[b] + (t - cu[b]) of the token's sequence
 //
@@ -89,6 +90,11 @@ __global__ void __launch_bounds__(NT) fasn_kvvarlen_schedule_kernel(const KvPref
 #define FASN_KV_PACKED 1
 #define FASN_KV_WINDOW 0
 #define FASN_KV_ALIBI 0
+#include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_WINDOW
+// fasn_kvvarlen_fwd_window_kernel<Tag, D>(KvPrefillParams, KvPacked, KvWindow): a fifth time, the item's rows under a sliding window.
+// Schedule and combine kernels are the ones above: the window changes which tiles a workgroup walks, not what an item or a partial is.
+#define FASN_KV_WINDOW 1
 #include "fasn_kvprefill_fwd.inc"
 #undef FASN_KV_ALIBI
 #undef FASN_KV_WINDOW

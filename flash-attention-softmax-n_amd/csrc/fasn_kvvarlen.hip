@@ -1,5 +1,5 @@
-// K/V-cache prefill on token-packed queries (include/fasn.h: fasn_fwd_kvvarlen, fasn_kvvarlen_append, fasn_kvvarlen_plan): the entry
-// points and the launches of fasn_kvvarlen.h. The argument checks, the launch plan and the workspace rule are the family's
+// K/V-cache prefill on token-packed queries (include/fasn.h: fasn_fwd_kvvarlen[_window], fasn_kvvarlen_append, fasn_kvvarlen[_window]_plan):
+// the entry points and the launches of fasn_kvvarlen.h. The argument checks, the launch plan and the workspace rule are the family's
 // (fasn_kv_host.h, defined in fasn_kvcache.hip), called here with a packed block.
 #include <limits.h>
 #include "fasn_kv_host.h"
@@ -12,9 +12,16 @@ int kvv_launch_fwd(const KvFwd& f, hipStream_t s) {
     const KvPrefillParams& pp = f.pp;
     const KvParams& p = pp.kv;
     FASN_LAUNCH(fasn_kvvarlen_schedule_kernel<256>, dim3(1), dim3(256), 0, s, pp, f.pk);
-    constexpr auto fwd = &fasn_kvvarlen_fwd_kernel<Tag, D>;
-    ensure_smem<fwd>(kv_smem(D));
-    FASN_LAUNCH(fwd, dim3((unsigned)(f.pk.items_max * p.Hkv * p.nsplit)), dim3(256), kv_smem(D), s, pp, f.pk);
+    const dim3 grid((unsigned)(f.pk.items_max * p.Hkv * p.nsplit));
+    if (f.variant == KV_WINDOW) {
+        constexpr auto fwd = &fasn_kvvarlen_fwd_window_kernel<Tag, D>;
+        ensure_smem<fwd>(kv_smem(D));
+        FASN_LAUNCH(fwd, grid, dim3(256), kv_smem(D), s, pp, f.pk, f.kw);
+    } else {
+        constexpr auto fwd = &fasn_kvvarlen_fwd_kernel<Tag, D>;
+        ensure_smem<fwd>(kv_smem(D));
+        FASN_LAUNCH(fwd, grid, dim3(256), kv_smem(D), s, pp, f.pk);
+    }
     if (p.nsplit > 1) {
         const int64_t nthr = (int64_t)f.pk.items_max * p.Hkv * KVP_ROWS * (D / 4);
         FASN_LAUNCH((fasn_kvvarlen_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, pp, f.pk);
@@ -29,9 +36,9 @@ int kvv_launch_append(const KvPrefillParams& pp, const KvPacked& pk, hipStream_t
     return launch_rc();
 }
 
-int kvv_forward(const fasn_kvvarlen_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+int kvv_forward(const fasn_kvvarlen_args* args, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
     KvFwd f;
-    const int rc = kv_build_forward(kv_args(args), KV_BASE, nullptr, workspace, workspace_bytes, f);
+    const int rc = kv_build_forward(kv_args(args), variant, operand, workspace, workspace_bytes, f);
     if (rc) return rc;
     const fasn_kvcache_args& a = args->pf.kv;
     return kv_dispatch(a.dtype, a.D, [&](auto tag, auto d) { return kvv_launch_fwd<decltype(tag), decltype(d)::value>(f, (hipStream_t)stream); });
@@ -47,7 +54,15 @@ extern "C" {
 size_t fasn_fwd_kvvarlen_workspace_bytes(const fasn_kvvarlen_args* args) { return kv_workspace_bytes(kv_args(args), KV_BASE, nullptr); }
 
 int fasn_fwd_kvvarlen(const fasn_kvvarlen_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kvv_forward(args, workspace, workspace_bytes, stream);
+    return kvv_forward(args, KV_BASE, nullptr, workspace, workspace_bytes, stream);
+}
+
+size_t fasn_fwd_kvvarlen_window_workspace_bytes(const fasn_kvvarlen_args* args, const fasn_kv_window* window) {
+    return kv_workspace_bytes(kv_args(args), KV_WINDOW, window);
+}
+
+int fasn_fwd_kvvarlen_window(const fasn_kvvarlen_args* args, const fasn_kv_window* window, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return kvv_forward(args, KV_WINDOW, window, workspace, workspace_bytes, stream);
 }
 
 int fasn_kvvarlen_append(const fasn_kvvarlen_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
@@ -59,7 +74,11 @@ int fasn_kvvarlen_append(const fasn_kvvarlen_args* args, const fasn_view4* k_new
 }
 
 int fasn_kvvarlen_plan(const fasn_kvvarlen_args* args, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvv_forward(args, kv_plan_workspace(), ~size_t(0), nullptr); });
+    return kv_plan(buf, cap, [&] { return kvv_forward(args, KV_BASE, nullptr, kv_plan_workspace(), ~size_t(0), nullptr); });
+}
+
+int fasn_kvvarlen_window_plan(const fasn_kvvarlen_args* args, const fasn_kv_window* window, char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kvv_forward(args, KV_WINDOW, window, kv_plan_workspace(), ~size_t(0), nullptr); });
 }
 
 }  // extern "C"

@@ -13,6 +13,8 @@ flash_attention_n_kvcache_rope rotates `query` and `k_new` by their absolute pos
 (fasn_kvcache_rope_append / fasn_kvprefill_rope_append): the positions come from the lengths in device memory, so the step stays one graph.
 flash_attention_n_kvcache_varlen is the prefill call on TOKEN-PACKED queries (fasn_fwd_kvvarlen / fasn_kvvarlen_append): one [T, H, D]
 buffer and `cu_seqlens_q` on the device - a continuous-batching step of prompt chunks and decode tokens whose grid follows the tokens.
+flash_attention_n_kvcache_varlen_window and flash_attention_n_kvcache_varlen_rope are the sliding-window and the rotary call on the same
+packed buffers (fasn_fwd_kvvarlen_window / fasn_kvvarlen_rope_append): a served GPT-OSS or Mistral layer in one token-packed step.
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -241,6 +243,110 @@ def _forward(lib, decode, args, dev, stream, alibi=None, win=None) -> None:
     _lib.check(getattr(lib, name)(args, *operand, None if ws is None else ws.data_ptr(), ws_bytes, stream), name)
 
 
+def _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q):
+    """The checks of a token-packed step that the packed calls share, in front of _prepare: query, cu_seqlens_q, max_seqlen_q, B.
+    Returns (B, T, the [B, H, T, D] view of the buffer - batch stride 0 - that _prepare takes as a query of B sequences)."""
+    if not isinstance(query, Tensor) or query.dim() != 3:
+        got = tuple(query.shape) if isinstance(query, Tensor) else type(query).__name__
+        raise ValueError(f"{fn}: query must be token-packed [T, H, D]; got {got}")
+    if (not isinstance(cu_seqlens_q, Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.shape[0] < 2
+            or not cu_seqlens_q.is_contiguous()):
+        got = f"{cu_seqlens_q.dtype} {tuple(cu_seqlens_q.shape)}" if isinstance(cu_seqlens_q, Tensor) else type(cu_seqlens_q).__name__
+        raise ValueError(f"{fn}: cu_seqlens_q must be a contiguous int32 tensor of shape [B + 1] on the device (B >= 1); got {got}")
+    if cu_seqlens_q.device != query.device:
+        raise RuntimeError(f"cu_seqlens_q is on {cu_seqlens_q.device}, query on {query.device}: every operand must live on the query's "
+                           "device (the offsets are read by the kernels, never on the host)")
+    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int):
+        raise TypeError(f"{fn}: max_seqlen_q must be a Python int (a bound of every query length, part of a captured graph; never a tensor); "
+                        f"got {type(max_seqlen_q).__name__}")
+    if max_seqlen_q < 1:
+        raise ValueError(f"{fn}: max_seqlen_q must be >= 1; got {max_seqlen_q}")
+    B = cu_seqlens_q.shape[0] - 1
+    if isinstance(cache_seqlens, Tensor) and cache_seqlens.dim() == 1 and cache_seqlens.shape[0] != B:
+        raise ValueError(f"{fn}: cu_seqlens_q names {B} sequences but cache_seqlens has {cache_seqlens.shape[0]}: B = cu_seqlens_q.shape[0] - 1 "
+                         "is the batch of cache_seqlens and block_table")
+    T = query.shape[0]
+    if T < 1:
+        raise ValueError(f"{fn}: the token buffer is empty (query is {tuple(query.shape)})")
+    # the [B, H, T, D] view of the buffer (batch stride 0): what _prepare takes as a query of B sequences
+    q4 = _rows(query.unsqueeze(0).transpose(1, 2)).expand(B, -1, -1, -1)
+    _check_group_limit(fn, q4, k_cache)
+    return B, T, q4
+
+
+def _packed_prepare(fn, q4, T, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, k_new, v_new, softmax_n_param, scale,
+                    is_causal, return_lse):
+    """_prepare on the view of _packed_query, and the filled fasn_kvvarlen_args. Returns (va, out, lse, k_new, v_new, keep)."""
+    va = KvVarlenArgs()
+    _a, out, lse, k_new, v_new, keep, _alibi = _prepare(fn, q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                                                        softmax_n_param, scale, is_causal, return_lse, args=va.pf.kv,
+                                                        packed_sq=min(max_seqlen_q, 2 ** 31 - 1))
+    va.pf.q_seqlens = None
+    va.cu_seqlens_q, va.total_tokens, va.reserved = cu_seqlens_q.data_ptr(), T, 0
+    return va, out, lse, k_new, v_new, keep
+
+
+def _packed_forward(lib, va, dev, stream, win=None) -> None:
+    """workspace bytes -> allocate -> the packed forward, or its window sibling (`win`). The item table (+ the split partials): never 0"""
+    if win is None:
+        ws_bytes = lib.fasn_fwd_kvvarlen_workspace_bytes(va)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        _lib.check(lib.fasn_fwd_kvvarlen(va, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvvarlen")
+    else:
+        ws_bytes = lib.fasn_fwd_kvvarlen_window_workspace_bytes(va, win)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+        _lib.check(lib.fasn_fwd_kvvarlen_window(va, win, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvvarlen_window")
+
+
+def _check_rotary_tables(fn, rotary_cos, rotary_sin, query) -> None:
+    """what the rotary tables are, whatever the call's shapes: the first checks of the rope calls"""
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if not isinstance(t, Tensor) or t.dim() != 2:
+            got = tuple(t.shape) if isinstance(t, Tensor) else type(t).__name__
+            raise ValueError(f"{fn}: {name} must be a [rows, rotary_dim / 2] tensor; got {got}")
+    if rotary_cos.shape != rotary_sin.shape or rotary_cos.dtype != rotary_sin.dtype or rotary_cos.stride(0) != rotary_sin.stride(0):
+        raise ValueError(f"{fn}: rotary_cos and rotary_sin must have one shape, dtype and row stride; got {tuple(rotary_cos.shape)} "
+                         f"{rotary_cos.dtype} and {tuple(rotary_sin.shape)} {rotary_sin.dtype}")
+    if rotary_cos.dtype != torch.float32 and rotary_cos.dtype != query.dtype:
+        raise ValueError(f"{fn}: rotary_cos / rotary_sin must be float32 or the dtype of query ({query.dtype}); got {rotary_cos.dtype}")
+
+
+def _check_rotary_fit(fn, rotary_cos, rotary_sin, query, k_cache, block_table) -> None:
+    """the tables against the call's shapes (`query`: [B, H, Sq, D], or the view of _packed_query): device, rotary_dim, rows >= capacity,
+    alignment. They need no device: in front of _prepare and its CPU-tensor refusal (malformed shapes are _prepare's to name)"""
+    rows, rd = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
+    esize = rotary_cos.element_size()
+    if query.dim() == 4 and k_cache.dim() == 4 and (block_table is None or (isinstance(block_table, Tensor) and block_table.dim() == 2)):
+        D = query.shape[3]
+        capacity = k_cache.shape[1] * (1 if block_table is None else block_table.shape[1])
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if t.device != query.device:
+                raise RuntimeError(f"{name} is on {t.device}, query on {query.device}: every operand must live on the query's device "
+                                   "(the tables are read by the kernels, never on the host)")
+        if D in _KV_HEAD_DIMS and (rd < 16 or rd > D or rd % 16 != 0):
+            raise ValueError(f"{fn}: rotary_dim = 2 x {rotary_cos.shape[1]} = {rd} is not supported: 16 <= rotary_dim <= head dim {D} and "
+                             "rotary_dim % 16 == 0 (a lane rotates 8 pairs)")
+        if rows < capacity:
+            raise ValueError(f"{fn}: the rotary tables cover {rows} positions but the cache holds up to {capacity}: rows >= capacity, so that "
+                             "no position the lengths in device memory can name lies outside the tables")
+        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+            if t.stride(1) != 1 or t.data_ptr() % 16 != 0 or (rows > 1 and ((t.stride(0) * esize) % 16 != 0 or t.stride(0) < rd // 2)):
+                raise ValueError(f"{fn}: {name}: rows must be 16-byte aligned, apart and with unit column stride (base pointer % 16 == 0, row "
+                                 f"stride x {esize} bytes % 16 == 0, row stride >= rotary_dim / 2 = {rd // 2}); got strides {tuple(t.stride())}. "
+                                 "A table is never copied here")
+
+
+def _rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query) -> KvRope:
+    rows, rd = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
+    rope = KvRope()
+    rope.cos, rope.sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
+    rope.row_stride = rotary_cos.stride(0) if rows > 1 else rd // 2
+    rope.rows, rope.rotary_dim = min(rows, 2 ** 31 - 1), rd
+    rope.table_dtype = _lib.FASN_DTYPE_F32 if rotary_cos.dtype == torch.float32 else _KV_DTYPES[query.dtype]
+    rope.interleaved = 1 if rotary_interleaved else 0
+    return rope
+
+
 def flash_attention_n_kvcache(
         query: Tensor,
         k_cache: Tensor,
@@ -377,7 +483,8 @@ def flash_attention_n_kvcache_varlen(
     :param k_new, v_new: optional [T, Hkv, D], token-packed like `query`: token cu[b] + i is written to the cache position
                   cache_seqlens[b] + i first (positions at or beyond the capacity are dropped in the kernel) and then attended to.
     :param softmax_n_param: n >= 0, or a tensor that broadcasts to [B, H]: per sequence and query head, not per token.
-    :param alibi_slopes, window, rotary_cos, rotary_sin: not supported on packed queries yet; anything but None is refused.
+    :param alibi_slopes, window, rotary_cos, rotary_sin: anything but None is refused here. A sliding window and rotary embedding on
+                  packed queries are calls of their own: flash_attention_n_kvcache_varlen_window, flash_attention_n_kvcache_varlen_rope.
     :return: [T, H, D] in query's dtype (and lse [H, T] fp32). With len_b = clamp(cache_seqlens[b] + (qlen_b if k_new is given else 0),
              0, capacity), position i sees key j iff j < len_b and (causal) j <= i + len_b - qlen_b; a token that sees no key gives
              exactly 0 and lse = log n (-inf for n = 0).
@@ -393,37 +500,9 @@ def flash_attention_n_kvcache_varlen(
         if value is not None:
             raise NotImplementedError(f"{fn}: {name} is not supported on token-packed queries (no packed ALiBi, window or rotary kernels yet); "
                                       "pad the step and use flash_attention_n_kvcache_prefill / _window / _rope with query_seqlens")
-    if not isinstance(query, Tensor) or query.dim() != 3:
-        got = tuple(query.shape) if isinstance(query, Tensor) else type(query).__name__
-        raise ValueError(f"{fn}: query must be token-packed [T, H, D]; got {got}")
-    if (not isinstance(cu_seqlens_q, Tensor) or cu_seqlens_q.dtype != torch.int32 or cu_seqlens_q.dim() != 1 or cu_seqlens_q.shape[0] < 2
-            or not cu_seqlens_q.is_contiguous()):
-        got = f"{cu_seqlens_q.dtype} {tuple(cu_seqlens_q.shape)}" if isinstance(cu_seqlens_q, Tensor) else type(cu_seqlens_q).__name__
-        raise ValueError(f"{fn}: cu_seqlens_q must be a contiguous int32 tensor of shape [B + 1] on the device (B >= 1); got {got}")
-    if cu_seqlens_q.device != query.device:
-        raise RuntimeError(f"cu_seqlens_q is on {cu_seqlens_q.device}, query on {query.device}: every operand must live on the query's "
-                           "device (the offsets are read by the kernels, never on the host)")
-    if isinstance(max_seqlen_q, bool) or not isinstance(max_seqlen_q, int):
-        raise TypeError(f"{fn}: max_seqlen_q must be a Python int (a bound of every query length, part of a captured graph; never a tensor); "
-                        f"got {type(max_seqlen_q).__name__}")
-    if max_seqlen_q < 1:
-        raise ValueError(f"{fn}: max_seqlen_q must be >= 1; got {max_seqlen_q}")
-    B = cu_seqlens_q.shape[0] - 1
-    if isinstance(cache_seqlens, Tensor) and cache_seqlens.dim() == 1 and cache_seqlens.shape[0] != B:
-        raise ValueError(f"{fn}: cu_seqlens_q names {B} sequences but cache_seqlens has {cache_seqlens.shape[0]}: B = cu_seqlens_q.shape[0] - 1 "
-                         "is the batch of cache_seqlens and block_table")
-    T = query.shape[0]
-    if T < 1:
-        raise ValueError(f"{fn}: the token buffer is empty (query is {tuple(query.shape)})")
-    # the [B, H, T, D] view of the buffer (batch stride 0): what _prepare takes as a query of B sequences
-    q4 = _rows(query.unsqueeze(0).transpose(1, 2)).expand(B, -1, -1, -1)
-    _check_group_limit(fn, q4, k_cache)
-    va = KvVarlenArgs()
-    _a, out, lse, k_new, v_new, _keep, _alibi = _prepare(fn, q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
-                                                         softmax_n_param, scale, is_causal, return_lse, args=va.pf.kv,
-                                                         packed_sq=min(max_seqlen_q, 2 ** 31 - 1))
-    va.pf.q_seqlens = None
-    va.cu_seqlens_q, va.total_tokens, va.reserved = cu_seqlens_q.data_ptr(), T, 0
+    _B, T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    va, out, lse, k_new, v_new, _keep = _packed_prepare(fn, q4, T, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
+                                                        k_new, v_new, softmax_n_param, scale, is_causal, return_lse)
     lib = _lib.load()
     dev = query.device
 
@@ -431,9 +510,124 @@ def flash_attention_n_kvcache_varlen(
         stream = _stream_ptr(dev)
         if k_new is not None:
             _lib.check(lib.fasn_kvvarlen_append(va, _view4(k_new), _view4(v_new), stream), "fasn_kvvarlen_append")
-        ws_bytes = lib.fasn_fwd_kvvarlen_workspace_bytes(va)   # the item table (+ the split partials): never 0
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        _lib.check(lib.fasn_fwd_kvvarlen(va, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvvarlen")
+        _packed_forward(lib, va, dev, stream)
+
+    _on_device(dev, launch)
+    out = out.transpose(1, 2).squeeze(0)   # [T, H, D]
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_n_kvcache_varlen_window(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        cu_seqlens_q: Tensor,
+        max_seqlen_q: int,
+        window: int,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        return_lse: bool = False):
+    """softmax_n attention of a SLIDING-WINDOW layer on a CONTINUOUS-BATCHING step, on MI355X: flash_attention_n_kvcache_window on the
+    token-packed buffers of flash_attention_n_kvcache_varlen (every other layer of GPT-OSS, Mistral).
+
+    Always causal. With qlen_b = clamp(cu[b + 1] - cu[b], 0, max_seqlen_q), len_b = clamp(cache_seqlens[b] + (qlen_b if k_new is given
+    else 0), 0, capacity) and p_i = i + len_b - qlen_b, token cu[b] + i sees key j iff j < len_b and p_i - window < j <= p_i. `query`,
+    `cu_seqlens_q`, `max_seqlen_q`, `k_new` / `v_new`, the cache, `softmax_n_param`, `scale`, the outputs ([T, H, D], lse [H, T]; rows at or
+    beyond cu[B] are not written) and the refusals are those of flash_attention_n_kvcache_varlen. What differs:
+
+    :param window: a Python int >= 1, a constant of the layer and part of a captured graph. A window at or beyond the capacity sees what
+                  flash_attention_n_kvcache_varlen sees.
+
+    Memory contract, per sequence: flash_attention_n_kvcache_window's. Let first_b = 64 * floor(max(0, len_b - qlen_b - window + 1) / 64).
+    Cache rows j < first_b are never read and neither are the block-table entries of pages wholly below first_b: a server may free them.
+    Nothing is read on the host: the launches depend on T, B, max_seqlen_q, the head counts, D, the capacity and `window` only. One split
+    count serves the launch, from the tiles a window can touch: never more splits than flash_attention_n_kvcache_varlen has.
+    """
+    fn = "flash_attention_n_kvcache_varlen_window"
+    _check_window(fn, window)
+    _B, T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    va, out, lse, k_new, v_new, _keep = _packed_prepare(fn, q4, T, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
+                                                        k_new, v_new, softmax_n_param, scale, True, return_lse)
+    win = KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
+    lib = _lib.load()
+    dev = query.device
+
+    def launch():
+        stream = _stream_ptr(dev)
+        if k_new is not None:
+            _lib.check(lib.fasn_kvvarlen_append(va, _view4(k_new), _view4(v_new), stream), "fasn_kvvarlen_append")
+        _packed_forward(lib, va, dev, stream, win=win)
+
+    _on_device(dev, launch)
+    out = out.transpose(1, 2).squeeze(0)   # [T, H, D]
+    return (out, lse) if return_lse else out
+
+
+def flash_attention_n_kvcache_varlen_rope(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        cu_seqlens_q: Tensor,
+        max_seqlen_q: int,
+        rotary_cos: Tensor,
+        rotary_sin: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False,
+        window: Optional[int] = None,
+        rotary_interleaved: bool = False):
+    """softmax_n attention of a CONTINUOUS-BATCHING step with ROTARY POSITION EMBEDDING applied to `query` and `k_new` on the way, on
+    MI355X: flash_attention_n_kvcache_rope on the token-packed buffers of flash_attention_n_kvcache_varlen - one layer step of a served
+    Llama / Mistral / GPT-OSS: rotate, append, attend.
+
+    With qlen_b, len_b and p_i = i + len_b - qlen_b as in flash_attention_n_kvcache_varlen, ONE launch rotates token cu[b] + i of k_new at
+    position cache_seqlens[b] + i into the cache (positions < 0 or >= the capacity are dropped), copies v_new beside it and rotates the
+    query token at p_i into a [T, H, D] temporary the forward then reads. Tokens at or beyond cu[B] are neither read nor written.
+    `query`, `cu_seqlens_q`, `max_seqlen_q`, `k_new` / `v_new`, the cache, `softmax_n_param`, `scale`, `is_causal`, the outputs and the
+    refusals are those of flash_attention_n_kvcache_varlen; `rotary_cos` / `rotary_sin` (layouts, rotary_dim, the table row
+    clamp(position, 0, rows - 1), rows >= capacity) and `rotary_interleaved` those of flash_attention_n_kvcache_rope, as is the arithmetic:
+    bit for bit (x1.float() * cos.float() - x2.float() * sin.float()).to(dtype) of eager torch.
+
+    :param k_new, v_new: optional [T, Hkv, D]. Without them only `query` is rotated, at p_i over the cache as it is.
+    :param window: None: flash_attention_n_kvcache_varlen's attention; a Python int >= 1: flash_attention_n_kvcache_varlen_window's
+                  (needs is_causal=True).
+    :return: [T, H, D] (and lse [H, T]). `query`, `k_new`, `cache_seqlens` are not modified.
+
+    Nothing is read on the host: the launches depend on T, B, max_seqlen_q, the head counts, D, the capacity and `window` only, so one
+    captured graph serves every step. No ALiBi slopes here (a model uses one or the other).
+    """
+    fn = "flash_attention_n_kvcache_varlen_rope"
+    if window is not None:
+        _check_window(fn, window, or_none="None or ")
+        if not is_causal:
+            raise ValueError(f"{fn}: a sliding window is always causal; window={window} needs is_causal=True")
+    _B, T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    _check_rotary_tables(fn, rotary_cos, rotary_sin, query)
+    _check_rotary_fit(fn, rotary_cos, rotary_sin, q4, k_cache, block_table)
+    va, out, lse, k_new, v_new, _keep = _packed_prepare(fn, q4, T, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
+                                                        k_new, v_new, softmax_n_param, scale, is_causal, return_lse)
+    win = None if window is None else KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
+    rope = _rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query)
+    lib = _lib.load()
+    dev = query.device
+    q_rot = torch.empty(tuple(query.shape), dtype=query.dtype, device=dev).unsqueeze(0).transpose(1, 2)   # [1, H, T, D] view of [T, H, D]
+    kn_view = None if k_new is None else _view4(k_new)
+    vn_view = None if v_new is None else _view4(v_new)
+
+    def launch():
+        stream = _stream_ptr(dev)
+        _lib.check(lib.fasn_kvvarlen_rope_append(va, rope, _view4(q_rot), kn_view, vn_view, stream), "fasn_kvvarlen_rope_append")
+        va.pf.kv.q = _view4(q_rot)   # the forward reads the rotated queries
+        _packed_forward(lib, va, dev, stream, win=win)
 
     _on_device(dev, launch)
     out = out.transpose(1, 2).squeeze(0)   # [T, H, D]
@@ -548,52 +742,17 @@ def flash_attention_n_kvcache_rope(
         _check_window(fn, window, or_none="None or ")
         if not is_causal:
             raise ValueError(f"{fn}: a sliding window is always causal; window={window} needs is_causal=True")
-    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-        if not isinstance(t, Tensor) or t.dim() != 2:
-            got = tuple(t.shape) if isinstance(t, Tensor) else type(t).__name__
-            raise ValueError(f"{fn}: {name} must be a [rows, rotary_dim / 2] tensor; got {got}")
-    if rotary_cos.shape != rotary_sin.shape or rotary_cos.dtype != rotary_sin.dtype or rotary_cos.stride(0) != rotary_sin.stride(0):
-        raise ValueError(f"{fn}: rotary_cos and rotary_sin must have one shape, dtype and row stride; got {tuple(rotary_cos.shape)} "
-                         f"{rotary_cos.dtype} and {tuple(rotary_sin.shape)} {rotary_sin.dtype}")
-    if rotary_cos.dtype != torch.float32 and rotary_cos.dtype != query.dtype:
-        raise ValueError(f"{fn}: rotary_cos / rotary_sin must be float32 or the dtype of query ({query.dtype}); got {rotary_cos.dtype}")
+    _check_rotary_tables(fn, rotary_cos, rotary_sin, query)
     _check_query_seqlens(fn, query_seqlens, query)
     _check_group_limit(fn, query, k_cache)
-    rows, rd = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
-    esize = rotary_cos.element_size()
-
-    if query.dim() == 4 and k_cache.dim() == 4 and (block_table is None or (isinstance(block_table, Tensor) and block_table.dim() == 2)):
-        # the table checks need no device: here, in front of _prepare and its CPU-tensor refusal (malformed shapes are _prepare's to name)
-        D = query.shape[3]
-        capacity = k_cache.shape[1] * (1 if block_table is None else block_table.shape[1])
-        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-            if t.device != query.device:
-                raise RuntimeError(f"{name} is on {t.device}, query on {query.device}: every operand must live on the query's device "
-                                   "(the tables are read by the kernels, never on the host)")
-        if D in _KV_HEAD_DIMS and (rd < 16 or rd > D or rd % 16 != 0):
-            raise ValueError(f"{fn}: rotary_dim = 2 x {rotary_cos.shape[1]} = {rd} is not supported: 16 <= rotary_dim <= head dim {D} and "
-                             "rotary_dim % 16 == 0 (a lane rotates 8 pairs)")
-        if rows < capacity:
-            raise ValueError(f"{fn}: the rotary tables cover {rows} positions but the cache holds up to {capacity}: rows >= capacity, so that "
-                             "no position the lengths in device memory can name lies outside the tables")
-        for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
-            if t.stride(1) != 1 or t.data_ptr() % 16 != 0 or (rows > 1 and ((t.stride(0) * esize) % 16 != 0 or t.stride(0) < rd // 2)):
-                raise ValueError(f"{fn}: {name}: rows must be 16-byte aligned, apart and with unit column stride (base pointer % 16 == 0, row "
-                                 f"stride x {esize} bytes % 16 == 0, row stride >= rotary_dim / 2 = {rd // 2}); got strides {tuple(t.stride())}. "
-                                 "A table is never copied here")
-
+    _check_rotary_fit(fn, rotary_cos, rotary_sin, query, k_cache, block_table)
     pa = KvPrefillArgs()   # (its first member is the decode call's argument block)
     a, out, lse, k_new, v_new, _keep, _alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
                                                         softmax_n_param, scale, is_causal, return_lse, args=pa.kv)
     pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
     decode = query_seqlens is None and a.kv_group * a.Sq <= _MAX_ROWS
     win = None if window is None else KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
-    rope = KvRope()
-    rope.cos, rope.sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
-    rope.row_stride = rotary_cos.stride(0) if rows > 1 else rd // 2
-    rope.rows, rope.rotary_dim = min(rows, 2 ** 31 - 1), rd
-    rope.table_dtype = _lib.FASN_DTYPE_F32 if rotary_cos.dtype == torch.float32 else _KV_DTYPES[query.dtype]
-    rope.interleaved = 1 if rotary_interleaved else 0
+    rope = _rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query)
     lib = _lib.load()
     dev = query.device
     q_rot = torch.empty(tuple(query.shape), dtype=query.dtype, device=dev)   # (torch's caching allocator: a captured graph owns it)

@@ -451,7 +451,23 @@ int fasn_kvprefill_rope_append_plan(const fasn_kvprefill_args* args, const fasn_
  * of [1, H / kv_group, total_tokens, D]) to cache row seqlens[b] + t - cu[b] of its sequence under the rules of fasn_kvprefill_append.
  * fasn_kvvarlen_plan writes the launches of fasn_fwd_kvvarlen as text. Every rule and error code of fasn_fwd_kvprefill holds and is checked
  * first; then cu_seqlens_q == NULL, pf.q_seqlens != NULL, total_tokens < 1 or reserved != 0 is FASN_EINVAL, offsets that are not 4-byte
- * aligned FASN_EALIGN, a table beyond 2^31 / 128 / (H / kv_group) items FASN_EINVAL. There is no packed ALiBi, window or rotary call yet.
+ * aligned FASN_EALIGN, a table beyond 2^31 / 128 / (H / kv_group) items FASN_EINVAL.
+ *
+ * SLIDING WINDOW AND ROTARY EMBEDDING ON PACKED QUERIES (additions within ABI 6): the packed siblings of the *_window and *_rope_append
+ * calls above, with their operands, their semantics per sequence (p_i = i + len_b - qlen_b, the memory contract of the window with
+ * first_b = 64 * floor(max(0, len_b - qlen_b - window + 1) / 64), the layouts, tables and rounding of the rotation) and their codes.
+ *   fasn_fwd_kvvarlen_window     fasn_fwd_kvvarlen with a forward kernel of its own; the schedule and combine kernels are the same. The
+ *                                split rule runs over items_max * (H / kv_group) blocks and the tiles a window can touch, so the workspace
+ *                                is fasn_fwd_kvvarlen_window_workspace_bytes(args, window): the table, then the partials, never more than
+ *                                the base call's. fasn_kvvarlen_window_plan writes its launches.
+ *   fasn_kvvarlen_rope_append    ONE launch in the place of fasn_kvvarlen_append: token cu[b] + i of k_new is rotated at position
+ *                                seqlens[b] + i into the cache (dropped at a negative position or at / beyond the capacity), v_new copied
+ *                                beside it, the query token rotated at p_i into q_out; q_out, k_new, v_new are views of
+ *                                [1, heads, total_tokens, D]. Tokens at or beyond cu[B] are neither read nor written. The forward that
+ *                                follows reads q_out in the place of q. Its grid is
+ *                                ceil(((k_new ? total_tokens * (H / kv_group) : 0) + total_tokens * H) * (D / 16) / 256): shapes only.
+ * Every rule and error code of fasn_fwd_kvvarlen holds and is checked first, then the operand's rules with the operand's codes, before
+ * any HIP call. There is no packed ALiBi call.
  */
 typedef struct fasn_kvvarlen_args {
     fasn_kvprefill_args pf;
@@ -464,6 +480,13 @@ size_t fasn_fwd_kvvarlen_workspace_bytes(const fasn_kvvarlen_args* args);
 int fasn_fwd_kvvarlen(const fasn_kvvarlen_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
 int fasn_kvvarlen_append(const fasn_kvvarlen_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
 int fasn_kvvarlen_plan(const fasn_kvvarlen_args* args, char* buf, size_t cap);
+size_t fasn_fwd_kvvarlen_window_workspace_bytes(const fasn_kvvarlen_args* args, const fasn_kv_window* window);
+int fasn_fwd_kvvarlen_window(const fasn_kvvarlen_args* args, const fasn_kv_window* window, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvvarlen_window_plan(const fasn_kvvarlen_args* args, const fasn_kv_window* window, char* buf, size_t cap);
+int fasn_kvvarlen_rope_append(const fasn_kvvarlen_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
+                              const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvvarlen_rope_append_plan(const fasn_kvvarlen_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
+                                   const fasn_view4* v_new, char* buf, size_t cap);
 
 /*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,

@@ -3,7 +3,9 @@
 One block per call: fasn_fwd_path, fasn_bwd_path, fasn_fwd_workspace_bytes and the fasn_launch_plan text of the forward, the forward with its
 workspace and the backward (dummy aligned addresses, as tests/baseline_plans.py; nothing is launched). Two trees launch the same kernels with
 the same grids iff their outputs are byte-identical - run it with REPO_ROOT = an export of the other commit, built. Also lists the kernels of
-the library's attention families that no plan named: an instantiation no call can reach, or an axis this sweep lacks."""
+the library's attention families that no plan named: an instantiation no call can reach, or an axis this sweep lacks.
+The token-packed sliding-window and rotary K/V-cache calls (fasn_kvvarlen_window_plan, fasn_kvvarlen_rope_append_plan) are swept too, where the
+library has them: every head dim and dtype, one split and several, with and without new rows; their kernels count as families that must be reached."""
 import ctypes, hashlib, itertools, os, re, sys
 
 ROOT = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -84,9 +86,50 @@ def calls():
         yield f"baseline {name}", baseline_plans.bwd_args(pkg, name)
 
 
+def kv_packed_calls():
+    """(header, plan function, its operands) of the packed window and rotary calls: fasn_kvvarlen_args over dummy addresses, q / o / q_out /
+    k_new / v_new as [1, heads, T, D] views of [T, heads, D] buffers"""
+    if not hasattr(lib, "fasn_kvvarlen_window_plan"):   # (a tree from before these calls)
+        return
+    for D, dt, (H, Hkv), (B, Sq, T, pages) in itertools.product((32, 64, 128, 256), (0, 1), ((8, 8), (64, 8), (12, 4)),
+                                                                ((4, 48, 64, 64), (257, 4096, 4352, 32), (3, 40, 51, 16))):
+        def block(add):
+            va = L.KvVarlenArgs()
+            a = va.pf.kv
+            for v in (a.q, a.o):
+                view(v, (0, D, H * D, 1))
+            a.lse = a.k_cache = a.v_cache = a.block_table = a.seqlens = DUMMY
+            for i, st in enumerate((256 * Hkv * D, Hkv * D, D)):
+                a.k_stride[i] = a.v_stride[i] = st
+            a.block_table_stride = a.max_pages = pages
+            a.seqlen_add, a.page_size = (Sq if add else 0), 256
+            a.B, a.H, a.kv_group, a.Sq, a.D, a.dtype = B, H, H // Hkv, Sq, D, dt
+            a.scale, a.softmax_n, a.causal = D ** -0.5, 1.0, 1
+            va.cu_seqlens_q, va.total_tokens, va.reserved = DUMMY, T, 0
+            return va
+        hdr = f"kvvarlen D={D} dt={dt} heads={H}/{Hkv} B={B} Sq={Sq} T={T} pages={pages}"
+        for W in (1, 128, 3000, 2 ** 31 - 1):
+            yield f"{hdr} window={W}", lib.fasn_kvvarlen_window_plan, (block(False), L.KvWindow(window=W, reserved=0))
+        rope = L.KvRope()
+        rope.cos = rope.sin = DUMMY
+        rope.row_stride, rope.rows, rope.rotary_dim, rope.table_dtype, rope.interleaved = D // 2, 256 * pages, D, L.FASN_DTYPE_F32, 0
+        qo, kn = L.View4(), L.View4()
+        view(qo, (0, D, H * D, 1))
+        view(kn, (0, D, Hkv * D, 1))
+        yield f"{hdr} rope+append", lib.fasn_kvvarlen_rope_append_plan, (block(True), rope, qo, kn, kn)
+        yield f"{hdr} rope", lib.fasn_kvvarlen_rope_append_plan, (block(False), rope, qo, None, None)
+
+
 def main():
     out, named, ncalls = [], set(), 0
     buf = ctypes.create_string_buffer(1 << 15)
+    for hdr, plan, operands in kv_packed_calls():
+        ncalls += 1
+        rc = plan(*operands, buf, len(buf))
+        out.append(f"{hdr} rc={rc}")
+        for line in buf.value.decode().splitlines():
+            out.append("    " + line)
+            named.add(line.split(" grid=")[0])
     for hdr, a in calls():
         ncalls += 1
         out.append(f"{hdr} fwd_path={lib.fasn_fwd_path(a.fwd)} bwd_path={lib.fasn_bwd_path(a)} ws={lib.fasn_fwd_workspace_bytes(a.fwd)}")
@@ -101,8 +144,8 @@ def main():
         open(OUT, "w").write(text)
     print(f"{ncalls} calls, {len(out)} lines, sha256 {hashlib.sha256(text.encode()).hexdigest()}")
     table = spill_map.kernel_table(os.path.join(ROOT, "flash-attention-softmax-n_amd", "libfasn.so"))
-    names = {re.sub(r"\(fasn::\w+\)$", "", d).replace("void fasn::", "") for d in spill_map.demangle(list(table)).values()}
-    att = {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_", n)}
+    names = {re.sub(r"\(fasn::\w+(, fasn::\w+)*\)$", "", d).replace("void fasn::", "") for d in spill_map.demangle(list(table)).values()}
+    att = {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel", n)}
     miss = sorted(att - named)
     print(f"library kernels {len(names)}, attention families {len(att)}, named by the sweep {len(att & named)}, named but not in the library {len(named - names)}, never named {len(miss)}")
     for n in miss:
