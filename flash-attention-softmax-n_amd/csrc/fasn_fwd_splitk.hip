@@ -9,11 +9,15 @@ int launch_splitk_one(FwdParams p, hipStream_t s) {
     constexpr int BM = 128;
     // memory-bound: D <= 64: K/V go straight to LDS, two tiles ahead (three buffers of 8-16 KiB, three workgroups per CU);
     // D = 128: register staging, two LDS buffers, so that two workgroups (2 x 64 KiB) fit on a CU
-    constexpr int RING = (D == 128 && MODE != MODE_GENERAL) ? 0 : 2;   // (the D = 128 mask/bias kernel spills with staging registers)
+    // (the D = 128 mask/bias kernel spills with staging registers; so does the causal one once Q is prescaled - 5 VGPRs with SEED = 2 - and
+    // goes direct-to-LDS as well: one workgroup of 96 KiB per CU instead of two)
+    constexpr int RING = (D == 128 && MODE == MODE_PLAIN) ? 0 : 2;
     constexpr int OCC = 2;
     constexpr int smem = fwd_smem(D, RING, MODE, 4, 1);
     p.nqblk = (p.Sq + BM - 1) / BM;
-    constexpr auto kern = &fasn_fwd_kernel<Tag, D, 1, MODE, OCC, 4, 0, 0, RING, 1>;
+    // SEED = 2 as every other vector forward: Q is prescaled by scale*log2e and rounded to the operand type, which is what the backward
+    // kernels recompute P from - with the scale applied in fp32 here, lse and the backward's logits differed by up to u |x|
+    constexpr auto kern = &fasn_fwd_kernel<Tag, D, 1, MODE, OCC, 4, 0, 0, RING, 1, 2>;
     ensure_smem<kern>(smem);
     FASN_LAUNCH(kern, dim3((unsigned)(p.nqblk * p.nsplit * p.B * p.H)), dim3(256), smem, s, p);
     const int64_t nthr = (int64_t)p.B * p.H * p.Sq * (D / 4);
