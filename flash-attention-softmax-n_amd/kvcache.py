@@ -29,7 +29,11 @@ from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _vi
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
 _KV_HEAD_DIMS = (32, 64, 128, 256)   # the head dims flash_attention_n trains at; any other size is refused (a cache is never padded)
+_INT_MAX = 2 ** 31 - 1   # what an int32 member of an argument block holds: host integers are clamped to it
 _MAX_ROWS = 128   # query heads per K/V head x query positions: the rows of one workgroup
+
+
+_BLOCKS = {"kvcache": KvCacheArgs, "kvprefill": KvPrefillArgs, "kvvarlen": KvVarlenArgs}   # entry-point stem -> its argument block
 
 
 def _check_cache(name: str, t: Tensor, paged: bool, D: int) -> None:
@@ -90,13 +94,29 @@ def _check_group_limit(fn, query, k_cache) -> None:
                          "K/V head share one workgroup)")
 
 
-def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal, return_lse,
-             max_rows=None, args=None, alibi_slopes=None, packed_sq=None):
-    """The argument checks both entry points share (they need no device and come first) and the filled fasn_kvcache_args.
-    Returns (args, out, lse, k_new, v_new, keep, alibi): `keep` holds the tensors whose addresses the arguments carry, `alibi` is the
-    filled fasn_alibi_slopes or None. `packed_sq` (flash_attention_n_kvcache_varlen): `query` is the [B, H, T, D] view of a token-packed
-    buffer - batch stride 0, B sequences - and packed_sq the bound of a sequence's query length: out / lse are token-packed ([T, H, D]
-    behind a [1, H, T, D] view, [H, T]) and the block carries Sq = packed_sq."""
+class _Call:
+    """A checked call, ready to launch: `stem` names the entry points (fasn_{stem}_append, fasn_fwd_{stem}...), `args` is the block they
+    take and `kv` the fasn_kvcache_args inside it. The rest are the tensors whose addresses the block carries - they live as long as
+    the call does, so until its launches are issued."""
+    __slots__ = ("stem", "args", "kv", "dev", "packed", "qshape", "dtype", "out", "lse", "k_new", "v_new", "alibi", "keep")
+
+
+def _query_shaped(c) -> Tensor:
+    """uninitialised, in the layout of `out` (and of the rotated queries): [B, H, Sq, D], or the [1, H, T, D] view of a packed [T, H, D]"""
+    B, H, Sq, D = c.qshape
+    if c.packed:   # (Sq is T here: one row per token, whatever B is)
+        return torch.empty((Sq, H, D), dtype=c.dtype, device=c.dev).unsqueeze(0).transpose(1, 2)
+    return torch.empty((B, H, Sq, D), dtype=c.dtype, device=c.dev)
+
+
+def _prepare(fn, stem, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal, return_lse,
+             alibi_slopes=None, query_seqlens=None, by_shape=False, cu_seqlens_q=None, max_seqlen_q=None) -> _Call:
+    """The argument checks every entry point shares (they need no device and come first), the outputs and the filled argument block.
+    `stem` says which block: "kvcache" (fasn_kvcache_args, at most _MAX_ROWS rows), "kvprefill" (fasn_kvprefill_args, with
+    `query_seqlens`) or "kvvarlen" (fasn_kvvarlen_args: `query` is the [B, H, T, D] view of _packed_query, k_new / v_new and the outputs
+    are token-packed, `cu_seqlens_q` and `max_seqlen_q` go into the block). `by_shape` (the window and rope calls, on "kvprefill"): the
+    decode kernels run on the block's first member where the shapes allow them."""
+    packed = stem == "kvvarlen"
     if query.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("query must be [B, H, Sq, D] and the caches [num_pages, page_size, Hkv, D] (paged) or [B, capacity, Hkv, D] (dense)")
     if query.dtype not in _KV_DTYPES:
@@ -123,8 +143,8 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
     if Hkv < 1 or H % Hkv != 0:
         raise ValueError(f"the cache has {Hkv} K/V heads: must divide the {H} query heads (grouped-query attention)")
     G = H // Hkv
-    if max_rows is not None and G * Sq > max_rows:
-        raise ValueError(f"(query heads per K/V head) x (query positions) = {G} x {Sq} = {G * Sq} rows exceed the {max_rows} of one pass; "
+    if stem == "kvcache" and G * Sq > _MAX_ROWS:
+        raise ValueError(f"(query heads per K/V head) x (query positions) = {G} x {Sq} = {G * Sq} rows exceed the {_MAX_ROWS} of one pass; "
                          "split the query positions over several calls, or use flash_attention_n_kvcache_prefill")
     if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B or not cache_seqlens.is_contiguous():
         raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
@@ -146,12 +166,12 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
         raise ValueError("k_new and v_new come together")
     if k_new is not None:
         for name, t in (("k_new", k_new), ("v_new", v_new)):
-            if packed_sq is not None:   # (Sq is T here)
+            if packed:   # (Sq is T here)
                 if t.dtype != query.dtype or tuple(t.shape) != (Sq, Hkv, D):
                     raise ValueError(f"{name} must be [T, Hkv, D] = [{Sq}, {Hkv}, {D}] in {query.dtype}, token-packed like query; got {tuple(t.shape)} {t.dtype}")
             elif t.dtype != query.dtype or tuple(t.shape) != (B, Hkv, Sq, D):
                 raise ValueError(f"{name} must be [B, Hkv, Sq, D] = [{B}, {Hkv}, {Sq}, {D}] in {query.dtype}; got {tuple(t.shape)} {t.dtype}")
-        if packed_sq is not None:
+        if packed:
             k_new, v_new = k_new.unsqueeze(0).transpose(1, 2), v_new.unsqueeze(0).transpose(1, 2)   # [1, Hkv, T, D] views
         k_new, v_new = _rows(k_new), _rows(v_new)
     query = _rows(query)
@@ -170,14 +190,21 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
         raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
                            "(there is deliberately no CPU fallback)")
 
-    if packed_sq is None:
-        out = torch.empty((B, H, Sq, D), dtype=query.dtype, device=dev)
-        lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
-    else:   # Sq is T here: one row per token, whatever B is
-        out = torch.empty((Sq, H, D), dtype=query.dtype, device=dev).unsqueeze(0).transpose(1, 2)
-        lse = torch.empty((H, Sq), dtype=torch.float32, device=dev) if return_lse else None
-        Sq = packed_sq
-    a = args if args is not None else KvCacheArgs()
+    c = _Call()
+    c.dev, c.packed, c.qshape, c.dtype = dev, packed, (B, H, Sq, D), query.dtype
+    c.out = out = _query_shaped(c)
+    c.lse = lse = torch.empty((H, Sq) if packed else (B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+    top = _BLOCKS[stem]()
+    if stem == "kvprefill":
+        a = top.kv
+        top.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
+    elif packed:
+        a = top.pf.kv
+        top.pf.q_seqlens = None
+        top.cu_seqlens_q, top.total_tokens, top.reserved = cu_seqlens_q.data_ptr(), Sq, 0
+        Sq = min(max_seqlen_q, _INT_MAX)   # the block carries the bound of a sequence's query length
+    else:
+        a = top
     a.q, a.o = _view4(query), _view4(out)
     a.lse = None if lse is None else lse.data_ptr()
     a.k_cache, a.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
@@ -201,12 +228,16 @@ def _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_n
         a.n_stride_b, a.n_stride_h = _n_strides(nt)
     else:
         a.n, a.n_stride_b, a.n_stride_h = None, 0, 0
-    alibi = None
+    c.alibi = None
     if st is not None:
-        alibi = AlibiSlopes()
-        alibi.slopes = st.data_ptr()
-        alibi.stride_b, alibi.stride_h = _n_strides(st)
-    return a, out, lse, k_new, v_new, (query, nt, st), alibi
+        c.alibi = AlibiSlopes()
+        c.alibi.slopes = st.data_ptr()
+        c.alibi.stride_b, c.alibi.stride_h = _n_strides(st)
+    # the one place that chooses the decode kernels over the prefill kernels, by shapes alone (capturable): both give the same function
+    if by_shape and query_seqlens is None and G * Sq <= _MAX_ROWS:
+        stem, top = "kvcache", a   # (the prefill block's first member is the decode call's block)
+    c.stem, c.args, c.kv, c.k_new, c.v_new, c.keep = stem, top, a, k_new, v_new, (query, nt, st)
+    return c
 
 
 def _on_device(dev, launch) -> None:
@@ -218,29 +249,53 @@ def _on_device(dev, launch) -> None:
             launch()
 
 
-def _append(lib, decode, args, k_new, v_new, stream) -> None:
-    """k_new / v_new -> the cache rows behind the lengths (`args`: the KvCacheArgs of the decode kernels, the KvPrefillArgs of the prefill kernels)"""
-    if k_new is not None:
-        name = "fasn_kvcache_append" if decode else "fasn_kvprefill_append"
-        _lib.check(getattr(lib, name)(args, _view4(k_new), _view4(v_new), stream), name)
+def _append(lib, c, stream, rope=None, q_rot=None) -> None:
+    """k_new / v_new -> the cache rows behind the lengths; with `rope` the one launch that rotates them on the way and the queries into
+    `q_rot`, which the forward then reads"""
+    if rope is not None:
+        name = f"fasn_{c.stem}_rope_append"
+        kn_view = None if c.k_new is None else _view4(c.k_new)
+        vn_view = None if c.v_new is None else _view4(c.v_new)
+        _lib.check(getattr(lib, name)(c.args, rope, _view4(q_rot), kn_view, vn_view, stream), name)
+        c.kv.q = _view4(q_rot)
+    elif c.k_new is not None:
+        name = f"fasn_{c.stem}_append"
+        _lib.check(getattr(lib, name)(c.args, _view4(c.k_new), _view4(c.v_new), stream), name)
 
 
-def _forward(lib, decode, args, dev, stream, alibi=None, win=None) -> None:
-    """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (`alibi`) or of their window siblings (`win`)"""
-    stem = "kvcache" if decode else "kvprefill"
-    name, operand = (f"fasn_fwd_{stem}_alibi", (alibi,)) if alibi is not None else (f"fasn_fwd_{stem}_window", (win,)) if win is not None else (
-        f"fasn_fwd_{stem}", ())
-    if win is None:   # (the ALiBi kernels: the base call's workspace)
-        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_workspace_bytes")(args)
+def _forward(lib, c, stream, win=None) -> None:
+    """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (c.alibi) or of their window siblings (`win`)"""
+    stem = c.stem
+    if win is not None:
+        name, operand = f"fasn_fwd_{stem}_window", (win,)
+        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_window_workspace_bytes")(c.args, win)
+    else:   # (the ALiBi kernels: the base call's workspace)
+        name, operand = (f"fasn_fwd_{stem}_alibi", (c.alibi,)) if c.alibi is not None else (f"fasn_fwd_{stem}", ())
+        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_workspace_bytes")(c.args)
+    # torch's caching allocator: capturable, as _launch_fwd's. Decode always combines its split partials and a packed call always has its
+    # item table: both always pass a pointer; a prefill of one split has no partials and takes no workspace
+    if stem != "kvprefill":
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=c.dev)
     else:
-        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_window_workspace_bytes")(args, win)
-    # torch's caching allocator: capturable, as _launch_fwd's. Decode always combines its split partials and always passes a pointer; a
-    # prefill of one split has no partials and takes no workspace
-    if decode:
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-    else:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev) if ws_bytes else None
-    _lib.check(getattr(lib, name)(args, *operand, None if ws is None else ws.data_ptr(), ws_bytes, stream), name)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=c.dev) if ws_bytes else None
+    _lib.check(getattr(lib, name)(c.args, *operand, None if ws is None else ws.data_ptr(), ws_bytes, stream), name)
+
+
+def _run(c, window=None, rope=None):
+    """What every call does once it is checked: the library, the rotated-query temporary, then under the query's device the stream,
+    the append and the forward; the outputs in the caller's layout."""
+    lib = _lib.load()
+    win = None if window is None else KvWindow(window=min(window, _INT_MAX), reserved=0)
+    q_rot = None if rope is None else _query_shaped(c)   # (torch's caching allocator: a captured graph owns it)
+
+    def launch():
+        stream = _stream_ptr(c.dev)
+        _append(lib, c, stream, rope, q_rot)
+        _forward(lib, c, stream, win)
+
+    _on_device(c.dev, launch)
+    out = c.out.transpose(1, 2).squeeze(0) if c.packed else c.out   # packed: [T, H, D] (lse is [H, T] as allocated)
+    return out if c.lse is None else (out, c.lse)
 
 
 def _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q):
@@ -268,34 +323,10 @@ def _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
     T = query.shape[0]
     if T < 1:
         raise ValueError(f"{fn}: the token buffer is empty (query is {tuple(query.shape)})")
-    # the [B, H, T, D] view of the buffer (batch stride 0): what _prepare takes as a query of B sequences
+    # the [B, H, T, D] view of the buffer (batch stride 0): the query of B sequences that _prepare checks and fills "kvvarlen" from
     q4 = _rows(query.unsqueeze(0).transpose(1, 2)).expand(B, -1, -1, -1)
     _check_group_limit(fn, q4, k_cache)
     return B, T, q4
-
-
-def _packed_prepare(fn, q4, T, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table, k_new, v_new, softmax_n_param, scale,
-                    is_causal, return_lse):
-    """_prepare on the view of _packed_query, and the filled fasn_kvvarlen_args. Returns (va, out, lse, k_new, v_new, keep)."""
-    va = KvVarlenArgs()
-    _a, out, lse, k_new, v_new, keep, _alibi = _prepare(fn, q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
-                                                        softmax_n_param, scale, is_causal, return_lse, args=va.pf.kv,
-                                                        packed_sq=min(max_seqlen_q, 2 ** 31 - 1))
-    va.pf.q_seqlens = None
-    va.cu_seqlens_q, va.total_tokens, va.reserved = cu_seqlens_q.data_ptr(), T, 0
-    return va, out, lse, k_new, v_new, keep
-
-
-def _packed_forward(lib, va, dev, stream, win=None) -> None:
-    """workspace bytes -> allocate -> the packed forward, or its window sibling (`win`). The item table (+ the split partials): never 0"""
-    if win is None:
-        ws_bytes = lib.fasn_fwd_kvvarlen_workspace_bytes(va)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        _lib.check(lib.fasn_fwd_kvvarlen(va, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvvarlen")
-    else:
-        ws_bytes = lib.fasn_fwd_kvvarlen_window_workspace_bytes(va, win)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-        _lib.check(lib.fasn_fwd_kvvarlen_window(va, win, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_kvvarlen_window")
 
 
 def _check_rotary_tables(fn, rotary_cos, rotary_sin, query) -> None:
@@ -341,7 +372,7 @@ def _rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query) -> KvRope:
     rope = KvRope()
     rope.cos, rope.sin = rotary_cos.data_ptr(), rotary_sin.data_ptr()
     rope.row_stride = rotary_cos.stride(0) if rows > 1 else rd // 2
-    rope.rows, rope.rotary_dim = min(rows, 2 ** 31 - 1), rd
+    rope.rows, rope.rotary_dim = min(rows, _INT_MAX), rd
     rope.table_dtype = _lib.FASN_DTYPE_F32 if rotary_cos.dtype == torch.float32 else _KV_DTYPES[query.dtype]
     rope.interleaved = 1 if rotary_interleaved else 0
     return rope
@@ -385,18 +416,8 @@ def flash_attention_n_kvcache(
                   never read on the host, no gradient. What is visible does not change; lse includes the bias.
     :return: [B, H, Sq, D] in query's dtype (and lse). Rows that see no key give exactly 0 and lse = log n (-inf for n = 0).
     """
-    a, out, lse, k_new, v_new, _keep, alibi = _prepare("flash_attention_n_kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
-                                                       softmax_n_param, scale, is_causal, return_lse, max_rows=_MAX_ROWS, alibi_slopes=alibi_slopes)
-    lib = _lib.load()
-    dev = query.device
-
-    def launch():
-        stream = _stream_ptr(dev)
-        _append(lib, True, a, k_new, v_new, stream)
-        _forward(lib, True, a, dev, stream, alibi=alibi)
-
-    _on_device(dev, launch)
-    return (out, lse) if return_lse else out
+    return _run(_prepare("flash_attention_n_kvcache", "kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
+                         softmax_n_param, scale, is_causal, return_lse, alibi_slopes=alibi_slopes))
 
 
 def flash_attention_n_kvcache_prefill(
@@ -432,22 +453,10 @@ def flash_attention_n_kvcache_prefill(
              for n = 0); padding positions i >= qlen_b give exactly 0 and lse = -inf whatever n is.
     """
     fn = "flash_attention_n_kvcache_prefill"
-    pa = KvPrefillArgs()
     _check_query_seqlens(fn, query_seqlens, query)
     _check_group_limit(fn, query, k_cache)
-    _a, out, lse, k_new, v_new, _keep, alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
-                                                        softmax_n_param, scale, is_causal, return_lse, args=pa.kv, alibi_slopes=alibi_slopes)
-    pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
-    lib = _lib.load()
-    dev = query.device
-
-    def launch():
-        stream = _stream_ptr(dev)
-        _append(lib, False, pa, k_new, v_new, stream)
-        _forward(lib, False, pa, dev, stream, alibi=alibi)
-
-    _on_device(dev, launch)
-    return (out, lse) if return_lse else out
+    return _run(_prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale,
+                         is_causal, return_lse, alibi_slopes=alibi_slopes, query_seqlens=query_seqlens))
 
 
 def flash_attention_n_kvcache_varlen(
@@ -500,21 +509,9 @@ def flash_attention_n_kvcache_varlen(
         if value is not None:
             raise NotImplementedError(f"{fn}: {name} is not supported on token-packed queries (no packed ALiBi, window or rotary kernels yet); "
                                       "pad the step and use flash_attention_n_kvcache_prefill / _window / _rope with query_seqlens")
-    _B, T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
-    va, out, lse, k_new, v_new, _keep = _packed_prepare(fn, q4, T, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
-                                                        k_new, v_new, softmax_n_param, scale, is_causal, return_lse)
-    lib = _lib.load()
-    dev = query.device
-
-    def launch():
-        stream = _stream_ptr(dev)
-        if k_new is not None:
-            _lib.check(lib.fasn_kvvarlen_append(va, _view4(k_new), _view4(v_new), stream), "fasn_kvvarlen_append")
-        _packed_forward(lib, va, dev, stream)
-
-    _on_device(dev, launch)
-    out = out.transpose(1, 2).squeeze(0)   # [T, H, D]
-    return (out, lse) if return_lse else out
+    _B, _T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    return _run(_prepare(fn, "kvvarlen", q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale,
+                         is_causal, return_lse, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q))
 
 
 def flash_attention_n_kvcache_varlen_window(
@@ -549,22 +546,9 @@ def flash_attention_n_kvcache_varlen_window(
     """
     fn = "flash_attention_n_kvcache_varlen_window"
     _check_window(fn, window)
-    _B, T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
-    va, out, lse, k_new, v_new, _keep = _packed_prepare(fn, q4, T, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
-                                                        k_new, v_new, softmax_n_param, scale, True, return_lse)
-    win = KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
-    lib = _lib.load()
-    dev = query.device
-
-    def launch():
-        stream = _stream_ptr(dev)
-        if k_new is not None:
-            _lib.check(lib.fasn_kvvarlen_append(va, _view4(k_new), _view4(v_new), stream), "fasn_kvvarlen_append")
-        _packed_forward(lib, va, dev, stream, win=win)
-
-    _on_device(dev, launch)
-    out = out.transpose(1, 2).squeeze(0)   # [T, H, D]
-    return (out, lse) if return_lse else out
+    _B, _T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    return _run(_prepare(fn, "kvvarlen", q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale,
+                         True, return_lse, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q), window=window)
 
 
 def flash_attention_n_kvcache_varlen_rope(
@@ -610,28 +594,12 @@ def flash_attention_n_kvcache_varlen_rope(
         _check_window(fn, window, or_none="None or ")
         if not is_causal:
             raise ValueError(f"{fn}: a sliding window is always causal; window={window} needs is_causal=True")
-    _B, T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    _B, _T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
     _check_rotary_tables(fn, rotary_cos, rotary_sin, query)
     _check_rotary_fit(fn, rotary_cos, rotary_sin, q4, k_cache, block_table)
-    va, out, lse, k_new, v_new, _keep = _packed_prepare(fn, q4, T, k_cache, v_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q, block_table,
-                                                        k_new, v_new, softmax_n_param, scale, is_causal, return_lse)
-    win = None if window is None else KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
-    rope = _rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query)
-    lib = _lib.load()
-    dev = query.device
-    q_rot = torch.empty(tuple(query.shape), dtype=query.dtype, device=dev).unsqueeze(0).transpose(1, 2)   # [1, H, T, D] view of [T, H, D]
-    kn_view = None if k_new is None else _view4(k_new)
-    vn_view = None if v_new is None else _view4(v_new)
-
-    def launch():
-        stream = _stream_ptr(dev)
-        _lib.check(lib.fasn_kvvarlen_rope_append(va, rope, _view4(q_rot), kn_view, vn_view, stream), "fasn_kvvarlen_rope_append")
-        va.pf.kv.q = _view4(q_rot)   # the forward reads the rotated queries
-        _packed_forward(lib, va, dev, stream, win=win)
-
-    _on_device(dev, launch)
-    out = out.transpose(1, 2).squeeze(0)   # [T, H, D]
-    return (out, lse) if return_lse else out
+    c = _prepare(fn, "kvvarlen", q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
+                 return_lse, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q)
+    return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query))
 
 
 def flash_attention_n_kvcache_window(
@@ -673,23 +641,8 @@ def flash_attention_n_kvcache_window(
     _check_window(fn, window)
     _check_query_seqlens(fn, query_seqlens, query)
     _check_group_limit(fn, query, k_cache)
-    pa = KvPrefillArgs()   # (its first member is the decode call's argument block)
-    a, out, lse, k_new, v_new, _keep, _alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
-                                                        softmax_n_param, scale, True, return_lse, args=pa.kv)
-    pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
-    decode = query_seqlens is None and a.kv_group * a.Sq <= _MAX_ROWS
-    win = KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
-    lib = _lib.load()
-    dev = query.device
-
-    def launch():
-        stream = _stream_ptr(dev)
-        args = a if decode else pa
-        _append(lib, decode, args, k_new, v_new, stream)
-        _forward(lib, decode, args, dev, stream, win=win)
-
-    _on_device(dev, launch)
-    return (out, lse) if return_lse else out
+    return _run(_prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale,
+                         True, return_lse, query_seqlens=query_seqlens, by_shape=True), window=window)
 
 
 def flash_attention_n_kvcache_rope(
@@ -746,29 +699,9 @@ def flash_attention_n_kvcache_rope(
     _check_query_seqlens(fn, query_seqlens, query)
     _check_group_limit(fn, query, k_cache)
     _check_rotary_fit(fn, rotary_cos, rotary_sin, query, k_cache, block_table)
-    pa = KvPrefillArgs()   # (its first member is the decode call's argument block)
-    a, out, lse, k_new, v_new, _keep, _alibi = _prepare(fn, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
-                                                        softmax_n_param, scale, is_causal, return_lse, args=pa.kv)
-    pa.q_seqlens = None if query_seqlens is None else query_seqlens.data_ptr()
-    decode = query_seqlens is None and a.kv_group * a.Sq <= _MAX_ROWS
-    win = None if window is None else KvWindow(window=min(window, 2 ** 31 - 1), reserved=0)
-    rope = _rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query)
-    lib = _lib.load()
-    dev = query.device
-    q_rot = torch.empty(tuple(query.shape), dtype=query.dtype, device=dev)   # (torch's caching allocator: a captured graph owns it)
-    kn_view = None if k_new is None else _view4(k_new)
-    vn_view = None if v_new is None else _view4(v_new)
-
-    def launch():
-        stream = _stream_ptr(dev)
-        args = a if decode else pa
-        name = "fasn_kvcache_rope_append" if decode else "fasn_kvprefill_rope_append"
-        _lib.check(getattr(lib, name)(args, rope, _view4(q_rot), kn_view, vn_view, stream), name)
-        a.q = _view4(q_rot)   # the forward reads the rotated queries
-        _forward(lib, decode, args, dev, stream, win=win)
-
-    _on_device(dev, launch)
-    return (out, lse) if return_lse else out
+    c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
+                 return_lse, query_seqlens=query_seqlens, by_shape=True)
+    return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query))
 
 
 def _rows(t: Tensor) -> Tensor:

@@ -1,7 +1,7 @@
 """Three witnesses for the K/V-cache calls whose expected values are exact or carry a derived bound, compared per row and per element.
 
 Why. The K/V tests draw q, k ~ N(0, 0.5^2): at D = 64 the logits have a standard deviation of 0.25, every softmax is close to a plain
-average, the running maximum hardly moves and the split-K combine weights are all about 1. Their gate (test_gpu_kvcache._check) is one
+average, the running maximum hardly moves and the split-K combine weights are all about 1. Their gate (kv_support._check) is one
 number per tensor, REL_TRUE * max|want|, which the rows of short sequences set for the rows of long ones. A fault that depends on the
 position - a causal limit one key off in the rows of one sequence, a 64-key tile dropped at a seam, a split merged with the wrong weight -
 moves a long row by less than that and passes. The witnesses below make one key (or one count) decide every row:
@@ -31,10 +31,9 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_gpu_kvcache as dec   # noqa: E402
-import test_gpu_kvwindow as winmod   # noqa: E402
+import kv_support as ks   # noqa: E402
 
-_rand, _Paged, _n_values, _poison = dec._rand, dec._Paged, dec._n_values, winmod._poison
+_rand, _Paged, _n_values, _poison = ks._rand, ks._Paged, ks._n_values, ks._poison
 NAN = float("nan")
 DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
 U = {torch.bfloat16: 2.0 ** -8, torch.float16: 2.0 ** -11}   # unit roundoff of the operand / output type

@@ -1,155 +1,25 @@
 """flash_attention_n_kvcache on the GPU: paged / dense K/V cache, lengths in device memory, grouped-query heads as rows of one problem,
 a softmax_n per query head, append, graph replay.
 
-Reference of every case: the visible pages gathered into dense [B, Hkv, Smax, D] tensors on the device, the per-batch visibility (length
-and per-batch bottom-right causal limit) as a boolean mask, fp32 torch with the explicit sink column, one n per (batch, head). Gates: the
-project's own (REF_ATOL and REL_TRUE as tests/test_gpu_parity.py::_check applies them) on `out`, atol 1e-4 scaled the same way on `lse`.
-Second, independent witness: flash_attention_n on the gathered dense K/V with the same mask and n, same gates."""
+Reference, gates and second witness are those of tests/kv_support.py: the visible pages gathered into dense [B, Hkv, Smax, D] tensors on
+the device, the per-batch visibility as a boolean mask, fp32 torch with the explicit sink column; REF_ATOL / REL_TRUE on `out`, the
+1e-4-scaled gate on `lse`; flash_attention_n on the gathered dense K/V with the same mask and n as the witness."""
 import math
+import os
+import sys
 
 import pytest
 import torch
 
-from flash_attention_softmax_n_amd import synth
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import kv_support as ks   # noqa: E402
+from flash_attention_softmax_n_amd import synth   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-REF_ATOL = {torch.float16: 1e-2, torch.bfloat16: 5e-2}
-REL_TRUE = {torch.float16: 2.0 ** -9, torch.bfloat16: 2.0 ** -6}
-NAN = float("nan")
-
-
-def _rand(shape, dtype, dev, seed, std=0.5):
-    return synth.counter_normal(shape, seed, std=std, dtype=dtype, device=dev)
-
-
-def _check(got, want, dtype, what):
-    got, want = got.detach().float().cpu(), want.detach().float().cpu()
-    assert torch.isfinite(got).all(), f"{what}: non-finite values"
-    err = (got - want).abs().max().item() if got.numel() else 0.0
-    scale = want.abs().max().item() if want.numel() else 0.0
-    atol = REF_ATOL[dtype] * max(1.0, scale)
-    print(f"{what}: max-abs {err:.3e} (atol {atol:.3e}, relative gate {REL_TRUE[dtype] * max(scale, 1e-2):.3e})")
-    assert err <= atol, f"{what}: max-abs {err:.3e} > reference atol {atol:.3e}"
-    lim = REL_TRUE[dtype] * max(scale, 1e-2)
-    assert err <= lim, f"{what}: max-abs {err:.3e} > {lim:.3e} (relative gate)"
-
-
-def _check_lse(got, want, what):
-    got, want = got.detach().float().cpu(), want.detach().float().cpu()
-    assert not torch.isnan(got).any(), f"{what}: NaN"
-    inf = torch.isinf(want)
-    assert torch.equal(torch.isinf(got), inf) and torch.equal(got[inf], want[inf]), f"{what}: -inf rows differ"
-    if (~inf).any():
-        err = (got[~inf] - want[~inf]).abs().max().item()
-        atol = 1e-4 * max(1.0, want[~inf].abs().max().item())
-        print(f"{what}: max-abs {err:.3e} (atol {atol:.3e})")
-        assert err <= atol, f"{what}: max-abs {err:.3e} > {atol:.3e}"
-
-
-def _visibility(lens, Sq, S, causal, dev):
-    """[B, 1, Sq, S] bool: key j of batch element b is visible to position i"""
-    ln = torch.as_tensor(lens, device=dev).view(-1, 1, 1, 1)
-    i = torch.arange(Sq, device=dev).view(1, 1, Sq, 1)
-    j = torch.arange(S, device=dev).view(1, 1, 1, S)
-    vis = j < ln
-    if causal:
-        vis = vis & (j <= i + ln - Sq)
-    return vis.expand(len(lens), 1, Sq, S)
-
-
-def _reference(q, kd, vd, vis, n, scale=None):
-    """fp32 torch on the device: Z_i = n + sum_j exp(x_ij) (the sink column: logit 0, weight n, value 0). kd / vd: [B, Hkv, S, D] with
-    finite values everywhere; n: float or tensor broadcasting to [B, H]. Returns (o [B,H,Sq,D], lse [B,H,Sq])."""
-    B, H, Sq, D = q.shape
-    Hkv, S = kd.shape[1], kd.shape[2]
-    G = H // Hkv
-    qf = q.float().view(B, Hkv, G, Sq, D)
-    s = torch.einsum("bkgqd,bksd->bkgqs", qf, kd.float()).view(B, H, Sq, S) * (D ** -0.5 if scale is None else scale)
-    s = s.masked_fill(~vis, float("-inf"))
-    nt = torch.as_tensor(n, dtype=torch.float32, device=q.device)
-    nb = nt.reshape((1,) * (2 - nt.dim()) + tuple(nt.shape)).expand(B, H)[..., None, None]
-    m = s.amax(-1, keepdim=True)
-    m = torch.where(nb > 0, m.clamp_min(0.0), m)
-    m = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
-    e = torch.exp(s - m)
-    z = nb * torch.exp(-m) + e.sum(-1, keepdim=True)
-    p = e / torch.where(z > 0, z, torch.ones_like(z))
-    o = torch.einsum("bkgqs,bksd->bkgqd", p.view(B, Hkv, G, Sq, S), vd.float()).reshape(B, H, Sq, D)
-    lse = (m + torch.log(z)).squeeze(-1)
-    return o, lse
-
-
-class _Paged:
-    """A paged cache built from dense data: shuffled, non-contiguous page ids; every row at or beyond len_b inside a needed page is NaN,
-    every table entry beyond the needed pages points at a poison page full of NaN."""
-
-    def __init__(self, kd, vd, lens, page, max_pages, seed, alloc_all=False, spare=2, guard=None):
-        B, Hkv, Smax, D = kd.shape
-        dev, dtype = kd.device, kd.dtype
-        assert Smax == page * max_pages
-        need = [max_pages if alloc_all else (ln + page - 1) // page for ln in lens]
-        n_ids = sum(need) + spare + 1
-        gen = torch.Generator().manual_seed(seed)
-        ids = torch.randperm(n_ids, generator=gen).tolist()
-        self.poison = ids.pop()
-        extra = 0 if guard is None else 1
-        self.k = torch.full((n_ids + extra, page, Hkv, D), NAN, dtype=dtype, device=dev)
-        self.v = torch.full((n_ids + extra, page, Hkv, D), NAN, dtype=dtype, device=dev)
-        if guard is not None:   # trailing page no table names
-            self.k[n_ids] = guard
-            self.v[n_ids] = guard
-        table = torch.full((B, max_pages), self.poison, dtype=torch.int32)
-        for b in range(B):
-            for s in range(need[b]):
-                pid = ids.pop()
-                table[b, s] = pid
-                rows = max(0, min(page, lens[b] - s * page))
-                if rows:
-                    self.k[pid, :rows] = kd[b, :, s * page:s * page + rows].transpose(0, 1)
-                    self.v[pid, :rows] = vd[b, :, s * page:s * page + rows].transpose(0, 1)
-        self.table = table.to(dev)
-        self.lens = torch.tensor(lens, dtype=torch.int32, device=dev)
-        self.page, self.max_pages = page, max_pages
-
-
-def _gather(pool, table, lens, page):
-    """the visible rows of a paged cache as dense [B, Hkv, Smax, D] (rows at or beyond len_b: zeros) - read through the block table"""
-    B, max_pages = table.shape
-    need = max(1, max((ln + page - 1) // page for ln in lens))
-    t = table[:, :need].long()
-    d = pool[t]                                   # [B, need, page, Hkv, D]
-    d = d.reshape(B, need * page, pool.shape[2], pool.shape[3]).permute(0, 2, 1, 3)
-    keep = torch.arange(need * page, device=pool.device).view(1, 1, -1, 1) < torch.as_tensor(lens, device=pool.device).view(-1, 1, 1, 1)
-    return torch.where(keep, d, torch.zeros_like(d)).contiguous()
-
-
-def _run_case(pkg, dev, B, H, Hkv, Sq, D, dtype, page, lens, n, causal=True, seed=1, max_pages=None, what="", witness=True, scale=None):
-    max_pages = max_pages or max(1, max((ln + page - 1) // page for ln in lens)) + 1
-    Smax = page * max_pages
-    q = _rand((B, H, Sq, D), dtype, dev, seed)
-    kd = _rand((B, Hkv, Smax, D), dtype, dev, seed + 1)
-    vd = _rand((B, Hkv, Smax, D), dtype, dev, seed + 2, std=1.0)
-    pc = _Paged(kd, vd, lens, page, max_pages, seed)
-    out, lse = pkg.flash_attention_n_kvcache(q, pc.k, pc.v, pc.lens, block_table=pc.table, softmax_n_param=n, is_causal=causal,
-                                             return_lse=True, scale=scale)
-    kg, vg = _gather(pc.k, pc.table, lens, page), _gather(pc.v, pc.table, lens, page)
-    vis = _visibility(lens, Sq, kg.shape[2], causal, dev)
-    o_ref, lse_ref = _reference(q, kg, vg, vis, n, scale)
-    _check(out, o_ref, dtype, f"{what} out")
-    _check_lse(lse, lse_ref, f"{what} lse")
-    if witness:
-        wit = pkg.flash_attention_n(q, kg, vg, softmax_n_param=n, attn_mask=vis, scale=scale)
-        _check(out, wit, dtype, f"{what} out vs flash_attention_n")
-    return out, lse, o_ref, lse_ref
-
-
-def _n_values(shape, dev, seed, zeros=True):
-    n = synth.counter_normal(shape, seed, std=1.0, dtype=torch.float32, device=dev).abs() + 0.25
-    if zeros:
-        flat = n.view(-1)
-        flat[::3] = 0.0   # exact zeros next to positive entries
-    return n
+NAN = ks.NAN
+_rand, _check, _check_lse, _visibility, _reference, _Paged, _gather, _run_case, _n_values = (
+    ks._rand, ks._check, ks._check_lse, ks._visibility, ks.reference, ks._Paged, ks._gather, ks._run_case_decode, ks._n_values)
 
 
 # ---------------------------------------------------------------- 1. shapes x pages x ragged lengths

@@ -1,7 +1,7 @@
 """flash_attention_n_kvcache and flash_attention_n_kvcache_prefill at head dims 32 and 256, on the GPU.
 
-References, second witness (flash_attention_n on the gathered dense K/V) and gates are those of tests/test_gpu_kvcache.py,
-tests/test_gpu_kvprefill.py and tests/test_gpu_kvalibi.py, whose helpers and runners are imported unchanged: REF_ATOL and REL_TRUE on
+References, second witness (flash_attention_n on the gathered dense K/V) and gates are those of tests/kv_support.py,
+whose helpers and runners the decode, prefill and ALiBi suites use too: REF_ATOL and REL_TRUE on
 `out`, 1e-4 x max(1, |lse|) on `lse`. Caches are _Paged: every row at or beyond len_b and every unneeded table entry is NaN, and _check
 asserts finite outputs. Shapes are the smallest at which the named thing can go wrong at these head dims: three LDS buffers per operand at
 D = 32, two of 32 KiB at D = 256 (the second V buffer ends at 128 KiB), one workgroup per CU at D = 256."""
@@ -12,23 +12,20 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_gpu_kvalibi as ali   # noqa: E402
-import test_gpu_kvcache as dec   # noqa: E402
-import test_gpu_kvprefill as pre   # noqa: E402
-import test_kvcache_cpu as dcpu   # noqa: E402
-import test_kvprefill_cpu as pcpu   # noqa: E402
+import kv_args   # noqa: E402
+import kv_support as ks   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
+NAN = ks.NAN
 _run_case, _Paged, _gather, _visibility, _reference, _n_values, _check, _check_lse, _rand = (
-    dec._run_case, dec._Paged, dec._gather, dec._visibility, dec._reference, dec._n_values, dec._check, dec._check_lse, dec._rand)
+    ks._run_case_decode, ks._Paged, ks._gather, ks._visibility, ks.reference, ks._n_values, ks._check, ks._check_lse, ks._rand)
 DIMS = [32, 256]
 DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
 
 
 def _dec_splits(pkg, alibi=False, **shape):
-    plan = pkg._lib.kvcache_plan(dcpu._args(pkg, **shape), ali._alibi_operand(pkg) if alibi else None)
+    plan = pkg._lib.kvcache_plan(kv_args._args_decode(pkg, **shape), ks._alibi_operand(pkg) if alibi else None)
     G = shape["H"] // shape["Hkv"]
     assert plan[0][0].startswith("fasn_kvcache_fwd_alibi_kernel<" if alibi else "fasn_kvcache_fwd_kernel<") and f", {shape['D']}>" in plan[0][0]
     assert G * shape["Sq"] <= 128
@@ -36,7 +33,7 @@ def _dec_splits(pkg, alibi=False, **shape):
 
 
 def _pre_splits(pkg, alibi=False, **shape):
-    plan = pkg._lib.kvprefill_plan(pcpu._args(pkg, **shape), ali._alibi_operand(pkg) if alibi else None)
+    plan = pkg._lib.kvprefill_plan(kv_args._args_prefill(pkg, **shape), ks._alibi_operand(pkg) if alibi else None)
     assert plan[0][0].startswith("fasn_kvprefill_fwd_alibi_kernel<" if alibi else "fasn_kvprefill_fwd_kernel<") and f", {shape['D']}>" in plan[0][0]
     PB = 128 // (shape["H"] // shape["Hkv"])
     nsplit = plan[0][1] // (shape["B"] * shape["Hkv"] * -(-shape["Sq"] // PB))
@@ -74,7 +71,7 @@ def test_all_lds_buffers_within_one_split(pkg, dev, D, dtype, call):
         _run_case(pkg, dev, B, H, Hkv, Sq, D, DTYPES[dtype], page, lens, 1.0, seed=200 + D, max_pages=max_pages, what=f"one split D={D} {dtype}")
     else:
         assert _pre_splits(pkg, **shape) == 1
-        pre._run_case(pkg, dev, B, H, Hkv, Sq, D, DTYPES[dtype], page, lens, 1.0, seed=210 + D, max_pages=max_pages, what=f"prefill one split D={D} {dtype}")
+        ks._run_case_prefill(pkg, dev, B, H, Hkv, Sq, D, DTYPES[dtype], page, lens, 1.0, seed=210 + D, max_pages=max_pages, what=f"prefill one split D={D} {dtype}")
 
 
 # ---------------------------------------------------------------- 3. full and minimal row occupancy
@@ -177,8 +174,8 @@ def test_prefill_append_from_nothing(pkg, dev, D):
     assert torch.equal(pc.k.view(torch.int16), ke.view(torch.int16)), "k_cache: not exactly the new rows"
     assert torch.equal(pc.v.view(torch.int16), ve.view(torch.int16)), "v_cache: not exactly the new rows"
     assert (pc.k[-1] == 7.0).all() and (pc.v[-1] == 7.0).all(), "guard page behind the cache was written"
-    kg, vg = pre._visible_dense(kn, qlens), pre._visible_dense(vn, qlens)
-    pre._check_all(pkg, out, lse, q, kg, vg, qlens, qlens, 1.0, True, dtype, f"prefill append D={D}")
+    kg, vg = ks._visible_dense(kn, qlens), ks._visible_dense(vn, qlens)
+    ks._check_all(pkg, out, lse, q, kg, vg, qlens, qlens, 1.0, True, dtype, f"prefill append D={D}")
     _check(out[:1], pkg.flash_attention_n(q[:1], kn[:1], vn[:1], softmax_n_param=1.0, is_causal=True), dtype, f"prefill append D={D} vs flash_attention_n(is_causal)")
 
 
@@ -201,7 +198,7 @@ def test_dense_cache_in_a_fused_buffer(pkg, dev, D, call, causal):
     out, lse = fa(q, kc, vc, sl, softmax_n_param=0.5, is_causal=causal, return_lse=True)
     keep = torch.arange(cap, device=dev).view(1, -1, 1, 1) < sl.view(-1, 1, 1, 1)
     kg, vg = (torch.where(keep, t, torch.zeros_like(t)).permute(0, 2, 1, 3).contiguous() for t in (kc, vc))
-    pre._check_all(pkg, out, lse, q, kg, vg, lens, [Sq] * B, 0.5, causal, dtype, f"dense {call} D={D} causal={causal}")
+    ks._check_all(pkg, out, lse, q, kg, vg, lens, [Sq] * B, 0.5, causal, dtype, f"dense {call} D={D} causal={causal}")
 
 
 # ---------------------------------------------------------------- 8. ALiBi slopes on both calls
@@ -212,10 +209,10 @@ def test_alibi(pkg, dev, D, call, form):
     B, H, Hkv, page = 3, 16, 4, 64
     Sq = 3 if call == "decode" else 70
     lens = [0, page + 1, 3 * page + 7]
-    slopes = ali._slopes(H, dev)
+    slopes = ks._slopes(H, dev)
     if form == "BH":
         slopes = (slopes.view(1, H) * torch.tensor([1.0, 0.5, 3.0], device=dev).view(B, 1)).contiguous()
-    run = ali._run_decode if call == "decode" else ali._run_prefill
+    run = ks._run_alibi_decode if call == "decode" else ks._run_alibi_prefill
     run(pkg, dev, B, H, Hkv, Sq, D, torch.bfloat16, page, lens, _n_values((H,), dev, 800), slopes, seed=801 + D, what=f"alibi {call} D={D} slopes[{form}]")
 
 
@@ -228,8 +225,8 @@ def test_alibi_weight_in_the_last_split(pkg, dev, D, call):
     shape = dict(B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages)
     nsplit = _dec_splits(pkg, alibi=True, **shape) if call == "decode" else _pre_splits(pkg, alibi=True, **shape)
     assert nsplit > 1
-    run = ali._run_decode if call == "decode" else ali._run_prefill
-    run(pkg, dev, B, H, Hkv, Sq, D, torch.float16, page, lens, 1.0, ali._steep(H, dev), seed=850 + D, max_pages=max_pages, what=f"alibi {call} D={D} steep, {nsplit} splits")
+    run = ks._run_alibi_decode if call == "decode" else ks._run_alibi_prefill
+    run(pkg, dev, B, H, Hkv, Sq, D, torch.float16, page, lens, 1.0, ks._steep(H, dev), seed=850 + D, max_pages=max_pages, what=f"alibi {call} D={D} steep, {nsplit} splits")
 
 
 # ---------------------------------------------------------------- 9. prefill
@@ -244,8 +241,8 @@ def test_prefill_one_split(pkg, dev, D, dtype, heads, causal):
     B, Sq, page, max_pages = 4, 300, 64, 8
     shape = dict(B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages)
     assert _pre_splits(pkg, **shape) == 1
-    assert pkg._lib.load().fasn_fwd_kvprefill_workspace_bytes(pcpu._args(pkg, **shape)) == 0
-    pre._run_case(pkg, dev, B, H, Hkv, Sq, D, DTYPES[dtype], page, [0, Sq - 5, page + 1, 6 * page], _n_values((B, H), dev, 900), causal=causal,
+    assert pkg._lib.load().fasn_fwd_kvprefill_workspace_bytes(kv_args._args_prefill(pkg, **shape)) == 0
+    ks._run_case_prefill(pkg, dev, B, H, Hkv, Sq, D, DTYPES[dtype], page, [0, Sq - 5, page + 1, 6 * page], _n_values((B, H), dev, 900), causal=causal,
                   seed=901 + D + H, max_pages=max_pages, qlens=[Sq, 1, 0, 129], what=f"prefill D={D} {dtype} H={H}/{Hkv} causal={causal}")
 
 
@@ -253,9 +250,9 @@ def test_prefill_one_split(pkg, dev, D, dtype, heads, causal):
 def test_prefill_several_splits(pkg, dev, D):
     shape = dict(B=1, H=16, Hkv=2, Sq=64, D=D, page=256, max_pages=40)
     assert _pre_splits(pkg, **shape) > 1
-    pre._run_case(pkg, dev, 1, 16, 2, 64, D, torch.bfloat16, 256, [9000], _n_values((16,), dev, 950), seed=951 + D, max_pages=40, what=f"prefill split plan D={D}")
-    pre._run_case(pkg, dev, 1, 16, 2, 64, D, torch.float16, 256, [9000], 0.0, causal=False, seed=952 + D, max_pages=40, what=f"prefill split plan D={D} non-causal", qlens=[33])
-    pre._run_case(pkg, dev, 1, 16, 2, 64, D, torch.float16, 256, [20], 1.0, seed=953 + D, max_pages=40, what=f"prefill split plan D={D}, most splits empty")
+    ks._run_case_prefill(pkg, dev, 1, 16, 2, 64, D, torch.bfloat16, 256, [9000], _n_values((16,), dev, 950), seed=951 + D, max_pages=40, what=f"prefill split plan D={D}")
+    ks._run_case_prefill(pkg, dev, 1, 16, 2, 64, D, torch.float16, 256, [9000], 0.0, causal=False, seed=952 + D, max_pages=40, what=f"prefill split plan D={D} non-causal", qlens=[33])
+    ks._run_case_prefill(pkg, dev, 1, 16, 2, 64, D, torch.float16, 256, [20], 1.0, seed=953 + D, max_pages=40, what=f"prefill split plan D={D}, most splits empty")
 
 
 # ---------------------------------------------------------------- 10. prompt -> chunked prefill -> two decode steps at D = 256

@@ -1,7 +1,7 @@
 """flash_attention_n_kvcache_prefill on the GPU: any number of query positions over a paged / dense K/V cache, cache lengths and query
 lengths in device memory, row blocks of (query heads of a K/V head) x positions, append, both launch plans, graph replay.
 
-Reference, gates and second witness are those of tests/test_gpu_kvcache.py (its helpers are imported): the visible rows gathered through
+Reference, gates and second witness are those of tests/kv_support.py: the visible rows gathered through
 the table, visibility as a boolean mask, fp32 torch with the explicit sink column; REF_ATOL / REL_TRUE on `out`, the 1e-4-scaled gate on
 `lse`; flash_attention_n with that mask as the witness. With `query_seqlens` the reference is computed per batch element on
 q[b, :, :qlen_b]; padding positions must be exactly 0 / -inf."""
@@ -13,95 +13,16 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_gpu_kvcache as dec   # noqa: E402
-import test_kvprefill_cpu as cpu   # noqa: E402
+import kv_args   # noqa: E402
+import kv_support as ks   # noqa: E402
 from flash_attention_softmax_n_amd import synth   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
+NAN = ks.NAN
 _rand, _check, _check_lse, _visibility, _reference, _Paged, _gather, _n_values = (
-    dec._rand, dec._check, dec._check_lse, dec._visibility, dec._reference, dec._Paged, dec._gather, dec._n_values)
-
-
-def _visible_dense(kd, lens):
-    """dense [B, Hkv, S, D] with the rows at or beyond len_b zeroed (what _gather gives for a paged cache)"""
-    keep = torch.arange(kd.shape[2], device=kd.device).view(1, 1, -1, 1) < torch.as_tensor(lens, device=kd.device).view(-1, 1, 1, 1)
-    return torch.where(keep, kd, torch.zeros_like(kd))
-
-
-def _mask(lens, qlens, Sq, S, causal, dev):
-    """[B, 1, Sq, S] bool: position i < qlen_b sees key j iff j < len_b and (causal) j <= i + len_b - qlen_b; padding positions see nothing"""
-    ln = torch.as_tensor(lens, device=dev).view(-1, 1, 1, 1)
-    ql = torch.as_tensor(qlens, device=dev).view(-1, 1, 1, 1)
-    i = torch.arange(Sq, device=dev).view(1, 1, Sq, 1)
-    j = torch.arange(S, device=dev).view(1, 1, 1, S)
-    vis = (j < ln) & (i < ql)
-    if causal:
-        vis = vis & (j <= i + ln - ql)
-    return vis
-
-
-def _reference_ragged(q, kg, vg, lens, qlens, n, causal, scale=None):
-    """per batch element on q[b, :, :qlen_b] (the decode tests' reference and visibility); padding positions: 0 / -inf"""
-    B, H, Sq, D = q.shape
-    dev = q.device
-    o = torch.zeros(B, H, Sq, D, dtype=torch.float32, device=dev)
-    lse = torch.full((B, H, Sq), float("-inf"), dtype=torch.float32, device=dev)
-    nt = torch.as_tensor(n, dtype=torch.float32, device=dev)
-    nb = nt.reshape((1,) * (2 - nt.dim()) + tuple(nt.shape)).expand(B, H)
-    for b in range(B):
-        ql = qlens[b]
-        if ql == 0:
-            continue
-        vis = _visibility([lens[b]], ql, kg.shape[2], causal, dev)
-        ob, lb = _reference(q[b:b + 1, :, :ql], kg[b:b + 1], vg[b:b + 1], vis, nb[b:b + 1], scale)
-        o[b, :, :ql] = ob[0]
-        lse[b, :, :ql] = lb[0]
-    return o, lse
-
-
-def _check_all(pkg, out, lse, q, kg, vg, lens, qlens, n, causal, dtype, what, witness=True, scale=None):
-    B, H, Sq, D = q.shape
-    o_ref, lse_ref = _reference_ragged(q, kg, vg, lens, qlens, n, causal, scale)
-    _check(out, o_ref, dtype, f"{what} out")
-    _check_lse(lse, lse_ref, f"{what} lse")
-    for b in range(B):   # padding: exactly 0 / -inf, whatever n is
-        assert (out[b, :, qlens[b]:] == 0).all() and (lse[b, :, qlens[b]:] == float("-inf")).all(), f"{what}: padding rows of batch element {b}"
-    if witness:
-        qz = q.clone()
-        for b in range(B):
-            qz[b, :, qlens[b]:] = 0
-        wit = pkg.flash_attention_n(qz, kg, vg, softmax_n_param=n, attn_mask=_mask(lens, qlens, Sq, kg.shape[2], causal, q.device), scale=scale)
-        _check(out, wit, dtype, f"{what} out vs flash_attention_n")
-
-
-def _run_case(pkg, dev, B, H, Hkv, Sq, D, dtype, page, lens, n, causal=True, seed=1, max_pages=None, what="", witness=True, scale=None, qlens=None):
-    """no append: `lens` are the keys in the cache"""
-    max_pages = max_pages or max(1, max((ln + page - 1) // page for ln in lens)) + 1
-    Smax = page * max_pages
-    q = _rand((B, H, Sq, D), dtype, dev, seed)
-    kd = _rand((B, Hkv, Smax, D), dtype, dev, seed + 1)
-    vd = _rand((B, Hkv, Smax, D), dtype, dev, seed + 2, std=1.0)
-    pc = _Paged(kd, vd, lens, page, max_pages, seed)
-    qs = None if qlens is None else torch.tensor(qlens, dtype=torch.int32, device=dev)
-    out, lse = pkg.flash_attention_n_kvcache_prefill(q, pc.k, pc.v, pc.lens, block_table=pc.table, query_seqlens=qs, softmax_n_param=n,
-                                                     is_causal=causal, return_lse=True, scale=scale)
-    kg, vg = _gather(pc.k, pc.table, lens, page), _gather(pc.v, pc.table, lens, page)
-    _check_all(pkg, out, lse, q, kg, vg, lens, qlens or [Sq] * B, n, causal, dtype, what, witness, scale)
-    return out, lse
-
-
-def _plan_names(pkg, **shape):
-    return [k[0].split("<")[0] for k in pkg._lib.kvprefill_plan(cpu._args(pkg, **shape))]
-
-
-def _poke_rows(pc, b, lo, hi, value):
-    """cache rows lo .. hi - 1 of batch element b, through the table"""
-    for pos in range(lo, hi):
-        pid = int(pc.table[b, pos // pc.page])
-        pc.k[pid, pos % pc.page] = value
-        pc.v[pid, pos % pc.page] = value
+    ks._rand, ks._check, ks._check_lse, ks._visibility, ks.reference, ks._Paged, ks._gather, ks._n_values)
+_visible_dense, _check_all, _run_case, _plan_names, _poke_rows = ks._visible_dense, ks._check_all, ks._run_case_prefill, ks._plan_names, ks._poke_rows
 
 
 # ---------------------------------------------------------------- 1. parity grid
@@ -363,7 +284,7 @@ def test_plan_without_a_combine_kernel(pkg, dev, D):
     """many row blocks: one split, the forward kernel stores o / lse itself, no workspace"""
     shape = dict(B=2, H=64, Hkv=8, Sq=1024, D=D, page=256, max_pages=9)
     assert _plan_names(pkg, **shape) == ["fasn_kvprefill_fwd_kernel"]
-    assert pkg._lib.load().fasn_fwd_kvprefill_workspace_bytes(cpu._args(pkg, **shape)) == 0
+    assert pkg._lib.load().fasn_fwd_kvprefill_workspace_bytes(kv_args._args_prefill(pkg, **shape)) == 0
     _run_case(pkg, dev, 2, 64, 8, 1024, D, torch.bfloat16, 256, [2048, 1025], _n_values((64,), dev, 810), seed=811, max_pages=9, what=f"one-split plan D={D}")
 
 

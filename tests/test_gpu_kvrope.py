@@ -16,46 +16,15 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_gpu_kvcache as dec   # noqa: E402
-import test_gpu_kvprefill as pre   # noqa: E402
-import test_gpu_kvwindow as win   # noqa: E402
+import kv_support as ks   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-_rand, _check, _check_lse, _Paged, _n_values = dec._rand, dec._check, dec._check_lse, dec._Paged, dec._n_values
+NAN = ks.NAN
+_rand, _check, _check_lse, _Paged, _n_values, _tables, _rotate, _bits = (
+    ks._rand, ks._check, ks._check_lse, ks._Paged, ks._n_values, ks._tables, ks._rotate, ks._bits)
 DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
 MAX_ROWS = 128   # rows of the decode kernels: the dispatch rule of the window function
-
-
-def _tables(rows, rd, dev, dtype, base=10000.0):
-    inv = base ** (-torch.arange(0, rd, 2, dtype=torch.float64) / rd)
-    ang = torch.arange(rows, dtype=torch.float64)[:, None] * inv[None]
-    return ang.cos().to(dtype).to(dev), ang.sin().to(dtype).to(dev)
-
-
-def _rotate(x, pos, cos, sin, interleaved):
-    """x [B, heads, S, D] in a 16-bit type, pos [B, S] (any integers: clamped to the table's rows here, as the kernel clamps). Eager torch,
-    fp32, every product and the sum an operation of its own, one rounding to x.dtype."""
-    rd = 2 * cos.shape[1]
-    p = pos.clamp(0, cos.shape[0] - 1).to(x.device)
-    c, s = cos[p].float()[:, None], sin[p].float()[:, None]   # [B, 1, S, rd / 2]
-    if interleaved:
-        x1, x2 = x[..., 0:rd:2].float(), x[..., 1:rd:2].float()
-    else:
-        x1, x2 = x[..., :rd // 2].float(), x[..., rd // 2:rd].float()
-    y1 = (x1 * c - x2 * s).to(x.dtype)
-    y2 = (x2 * c + x1 * s).to(x.dtype)
-    out = x.clone()
-    if interleaved:
-        out[..., 0:rd:2], out[..., 1:rd:2] = y1, y2
-    else:
-        out[..., :rd // 2], out[..., rd // 2:rd] = y1, y2
-    return out
-
-
-def _bits(t):
-    return t.view(torch.int16)
 
 
 def _both_routes(pkg, q, kn, vn, k0, v0, sl, cos, sin, q_rot, k_rot, table=None, qs=None, window=None, causal=True, n=1.0, interleaved=False,
@@ -139,15 +108,15 @@ def _run(pkg, dev, B, H, Hkv, Sq, D, dtype, page, max_pages, lens, seed, qlens=N
         kd[b, :, lens[b]:lens[b] + m] = k_rot[b, :, :m]
         vd[b, :, lens[b]:lens[b] + m] = vn[b, :, :m]
     if window is not None:
-        assert win._poison(pc.k, pc.v, pc.table, page, pc.poison, total, ql, window) > 0
+        assert ks._poison(pc.k, pc.v, pc.table, page, pc.poison, total, ql, window) > 0
     qs = torch.tensor(ql, dtype=torch.int32, device=dev) if (qlens is not None or prefill) else None
     out, lse, kR, vR = _both_routes(pkg, q, kn, vn, pc.k, pc.v, pc.lens, cos, sin, q_rot, k_rot, table=pc.table, qs=qs, window=window,
                                     causal=causal, n=n, interleaved=interleaved, what=what)
-    kg, vg = pre._visible_dense(kd, total), pre._visible_dense(vd, total)
+    kg, vg = ks._visible_dense(kd, total), ks._visible_dense(vd, total)
     if window is not None:
-        o_ref, l_ref = win._reference_window(q_rot, kg, vg, total, ql, n, window)
+        o_ref, l_ref = ks.reference_rows(q_rot, kg, vg, total, ql, n, window)
     else:
-        o_ref, l_ref = pre._reference_ragged(q_rot, kg, vg, total, ql, n, causal)
+        o_ref, l_ref = ks.reference_rows(q_rot, kg, vg, total, ql, n, causal)
     _check(out, o_ref, dtype, f"{what} out")
     _check_lse(lse, l_ref, f"{what} lse")
     for b in range(B):   # padding: exactly 0 / -inf
@@ -228,7 +197,7 @@ def test_query_only_dense(pkg, dev, causal, kernels):
     what = f"query only causal={causal} {kernels}"
     out, lse, kR, vR = _both_routes(pkg, q, None, None, kc, vc, sl, cos, sin, q_rot, None, qs=qs, causal=causal, n=0.5, what=what)
     assert torch.equal(_bits(kR), _bits(kc)) and torch.equal(_bits(vR), _bits(vc)), "the cache was written without k_new"
-    o_ref, l_ref = pre._reference_ragged(q_rot, kg, vg, lens, [Sq] * B, 0.5, causal)
+    o_ref, l_ref = ks.reference_rows(q_rot, kg, vg, lens, [Sq] * B, 0.5, causal)
     _check(out, o_ref, dtype, f"{what} out")
     _check_lse(lse, l_ref, f"{what} lse")
 
@@ -261,7 +230,7 @@ def test_graph_replay_follows_the_lengths(pkg, dev):
         sl.add_(1)
         return res
 
-    g, (go, gl) = win._capture(lambda: step(k_g, v_g, sl_g))   # (a single stream: the captured graph is one chain, no parallel branches)
+    g, (go, gl) = ks._capture(lambda: step(k_g, v_g, sl_g))   # (a single stream: the captured graph is one chain, no parallel branches)
     with torch.no_grad():   # the warm-up runs appended and advanced: back to the start
         k_g.copy_(pc.k)
         v_g.copy_(pc.v)

@@ -1,11 +1,10 @@
 """flash_attention_n_kvcache_varlen on the GPU: the prefill call on token-packed queries - one [T, H, D] buffer, cu_seqlens_q in device
 memory, an item table built on the device so that the grid follows the tokens.
 
-Reference and gates are those of tests/test_gpu_kvcache.py (its helpers are imported through test_gpu_kvprefill): per sequence, fp32
+Reference and gates are those of tests/kv_support.py: per sequence, fp32
 torch on the rows gathered through the table with the explicit sink column; REF_ATOL / REL_TRUE on `out`, the 1e-4-scaled gate on `lse`.
 Second witness: flash_attention_n_kvcache_prefill on the same cache with the queries padded and query_seqlens = qlens, under the same
 gates. The rows of the buffer at or beyond cu[B] hold NaN on the way in and are not looked at on the way out."""
-import itertools
 import math
 import os
 import sys
@@ -14,18 +13,14 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_gpu_kvprefill as pf   # noqa: E402
-import test_kvvarlen_cpu as cpu   # noqa: E402
+import kv_support as ks   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
+NAN = ks.NAN
 _rand, _check, _check_lse, _visibility, _reference, _Paged, _gather, _n_values = (
-    pf._rand, pf._check, pf._check_lse, pf._visibility, pf._reference, pf._Paged, pf._gather, pf._n_values)
-
-
-def _cu(qlens, dev):
-    return torch.tensor([0] + list(itertools.accumulate(qlens)), dtype=torch.int32, device=dev)
+    ks._rand, ks._check, ks._check_lse, ks._visibility, ks.reference, ks._Paged, ks._gather, ks._n_values)
+_cu, _plan, _nsplit, SPLIT, _split_plan = ks._cu, ks._varlen_plan, ks._varlen_nsplit, ks.VARLEN_SPLIT, ks._varlen_split_plan
 
 
 def _packed_reference(q, qlens, kg, vg, lens, n, causal):
@@ -87,14 +82,6 @@ def _run_packed(pkg, dev, H, Hkv, D, dtype, page, qlens, lens, n, causal=True, s
     return out, lse, q, pc
 
 
-def _plan(pkg, B, H, Hkv, Sq, D, T, page, max_pages, dtype=torch.bfloat16):
-    return pkg._lib.kvvarlen_plan(cpu._args(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, T=T, page=page, max_pages=max_pages, dtype=1 if dtype == torch.bfloat16 else 0))
-
-
-def _nsplit(plan, B, Hkv, Sq, T, PB):
-    return plan[1][1] // (cpu.items_max(B, Sq, T, PB) * Hkv)
-
-
 # ---------------------------------------------------------------- 1. parity
 @pytest.mark.parametrize("causal", [True, False])
 @pytest.mark.parametrize("page", [64, 256])
@@ -142,16 +129,6 @@ def test_neighbouring_sequences_do_not_touch_each_other(pkg, dev, cache):
 
 
 # ---------------------------------------------------------------- 3. several splits
-SPLIT = dict(H=8, Hkv=1, D=64, page=256, max_pages=16, qlens=[1, 40])
-
-
-def _split_plan(pkg):
-    c = SPLIT
-    plan = _plan(pkg, 2, c["H"], c["Hkv"], 40, c["D"], 41 + 7, c["page"], c["max_pages"])
-    assert [k[0].split("<")[0] for k in plan] == ["fasn_kvvarlen_schedule_kernel", "fasn_kvvarlen_fwd_kernel", "fasn_kvvarlen_combine_kernel"]
-    assert _nsplit(plan, 2, c["Hkv"], 40, 48, 16) >= 2
-
-
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
 def test_several_splits(pkg, dev, dtype):
     c = SPLIT

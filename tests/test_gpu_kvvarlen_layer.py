@@ -1,20 +1,19 @@
 """flash_attention_n_kvcache_varlen_window and flash_attention_n_kvcache_varlen_rope on the GPU: a sliding window and rotary position
 embedding on token-packed queries - one [T, H, D] buffer, cu_seqlens_q in device memory.
 
-Window. Reference: test_gpu_kvwindow._reference_window (fp32 torch, explicit sink column, the visibility j < len_b and
+Window. Reference: kv_support.reference_rows (fp32 torch, explicit sink column, the visibility j < len_b and
 p_i - W < j <= p_i) per sequence on its own tokens, under the cache tests' gates (REF_ATOL / REL_TRUE on `out`, 1e-4 on `lse`; imported).
 Second witness: flash_attention_n_kvcache_window on the same cache with the queries padded and query_seqlens = qlens - the same bits
 where both launches have the same split count (the two plan calls say), the gates otherwise. Then the rows below
 first_b = 64 * floor(max(0, len_b - qlen_b - W + 1) / 64) become NaN and the table entries of pages wholly below it the poison page
-(test_gpu_kvwindow._poison), and the call must return the bits it returned before. The three witnesses of tests/kv_witness.py (every
+(kv_support._poison), and the call must return the bits it returned before. The three witnesses of tests/kv_witness.py (every
 visible key exactly once; one key decides; a realistic dynamic range) run through a runner defined here.
 
 Rope. Bit for bit against the torch-rotated route, as tests/test_gpu_kvrope.py has it for the padded call: flash_attention_n_kvcache_varlen
-(or _varlen_window) fed test_gpu_kvrope._rotate'd query / k_new on a clone of the pools - K pool, V pool, out and lse equal as integers -
+(or _varlen_window) fed kv_support._rotate'd query / k_new on a clone of the pools - K pool, V pool, out and lse equal as integers -
 then the gates against the fp32 reference on the rotated inputs and against the padded flash_attention_n_kvcache_rope(query_seqlens=).
 
 The rows of the token buffers at or beyond cu[B] hold NaN on the way in and are not looked at on the way out."""
-import itertools
 import os
 import sys
 
@@ -23,24 +22,17 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kv_witness as kw   # noqa: E402
-import test_gpu_kvcache as dec   # noqa: E402
-import test_gpu_kvprefill as pf   # noqa: E402
-import test_gpu_kvrope as rp   # noqa: E402
-import test_gpu_kvwindow as win   # noqa: E402
-import test_kvprefill_cpu as pcpu   # noqa: E402
-import test_kvvarlen_layer_cpu as cpu   # noqa: E402
+import kv_args   # noqa: E402
+import kv_support as ks   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-_rand, _Paged, _gather, _check, _check_lse, _poison, _n_values = dec._rand, dec._Paged, dec._gather, dec._check, dec._check_lse, win._poison, dec._n_values
+NAN = ks.NAN
+_rand, _Paged, _gather, _check, _check_lse, _poison, _n_values, _cu, _bits = (
+    ks._rand, ks._Paged, ks._gather, ks._check, ks._check_lse, ks._poison, ks._n_values, ks._cu, ks._bits)
 DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
 VQ = lambda PB: [1, 0, PB, PB + 1, 2 * PB + 3, 1]   # noqa: E731  a decode token, an empty sequence, a block, a block edge, blocks, a token
 VL = lambda page: [300, 5, 0, page + 1, 2 * page, 64]   # noqa: E731
-
-
-def _cu(qlens, dev):
-    return torch.tensor([0] + list(itertools.accumulate(qlens)), dtype=torch.int32, device=dev)
 
 
 def _pad(t, qlens):
@@ -62,9 +54,7 @@ def _unpad(o, lse, qlens):
 def _reference(q, qlens, kg, vg, lens, n, window, causal=True):
     """fp32, per sequence on its own tokens: (o [sum qlens, H, D], lse [H, sum qlens])"""
     qp = _pad(q[:sum(qlens)], qlens)
-    if window is None:
-        return _unpad(*pf._reference_ragged(qp, kg, vg, lens, qlens, n, causal), qlens)
-    return _unpad(*win._reference_window(qp, kg, vg, lens, qlens, n, window), qlens)
+    return _unpad(*ks.reference_rows(qp, kg, vg, lens, qlens, n, causal if window is None else window), qlens)
 
 
 def _nsplits(pkg, B, H, Hkv, Sq, D, T, page, max_pages, dtype, W):
@@ -72,10 +62,10 @@ def _nsplits(pkg, B, H, Hkv, Sq, D, T, page, max_pages, dtype, W):
     shape = dict(B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages, dtype=1 if dtype == torch.bfloat16 else 0)
     PB = 128 // (H // Hkv)
     operand = pkg._lib.KvWindow(window=min(W, 2 ** 31 - 1), reserved=0)
-    packed = pkg._lib.kvvarlen_window_plan(cpu._args(pkg, T=T, **shape), operand)
+    packed = pkg._lib.kvvarlen_window_plan(kv_args._args_varlen(pkg, T=T, **shape), operand)
     assert [k[0].split("<")[0] for k in packed[:2]] == ["fasn_kvvarlen_schedule_kernel", "fasn_kvvarlen_fwd_window_kernel"]
-    padded = pkg._lib.kvprefill_window_plan(pcpu._args(pkg, **shape), operand)
-    return packed[1][1] // (cpu.items_max(B, Sq, T, PB) * Hkv), padded[0][1] // (B * Hkv * -(-Sq // PB))
+    padded = pkg._lib.kvprefill_window_plan(kv_args._args_prefill(pkg, **shape), operand)
+    return packed[1][1] // (kv_args.items_max(B, Sq, T, PB) * Hkv), padded[0][1] // (B * Hkv * -(-Sq // PB))
 
 
 def _run_window(pkg, dev, H, Hkv, D, dtype, page, qlens, lens, n, W, seed=1, max_pages=None, tail=7, what=""):
@@ -278,13 +268,9 @@ def test_witness_c_realistic_dynamic_range(pkg, dev, name, dtype, std):
 
 
 # ---------------------------------------------------------------- 4. rope: bit for bit against the torch-rotated route
-def _bits(t):
-    return t.view(torch.int16)
-
-
 def _rotate_packed(x, pos, cos, sin, interleaved):
-    """test_gpu_kvrope._rotate on [n, heads, D] rows at positions pos [n]"""
-    return rp._rotate(x.transpose(0, 1).unsqueeze(0), pos[None], cos, sin, interleaved)[0].transpose(0, 1).contiguous()
+    """kv_support._rotate on [n, heads, D] rows at positions pos [n]"""
+    return ks._rotate(x.transpose(0, 1).unsqueeze(0), pos[None], cos, sin, interleaved)[0].transpose(0, 1).contiguous()
 
 
 def _run_rope(pkg, dev, H, Hkv, D, dtype, page, max_pages, qlens, lens, seed, rd=None, table_dtype=torch.float32, interleaved=False, window=None,
@@ -298,7 +284,7 @@ def _run_rope(pkg, dev, H, Hkv, D, dtype, page, max_pages, qlens, lens, seed, rd
     vn = _rand((T, Hkv, D), dtype, dev, seed + 2, std=1.0)
     for t in (q, kn, vn):
         t[used:] = NAN
-    cos, sin = rp._tables(cap, rd, dev, table_dtype)
+    cos, sin = ks._tables(cap, rd, dev, table_dtype)
     kd = _rand((B, Hkv, cap, D), dtype, dev, seed + 3)
     vd = _rand((B, Hkv, cap, D), dtype, dev, seed + 4, std=1.0)
     pc = _Paged(kd, vd, lens, page, max_pages, seed, alloc_all=True, guard=7.0)   # rows at or beyond the length: NaN until the append writes them
@@ -347,7 +333,7 @@ def _run_rope(pkg, dev, H, Hkv, D, dtype, page, max_pages, qlens, lens, seed, rd
     if not append:
         assert torch.equal(_bits(kR), _bits(pc.k)) and torch.equal(_bits(vR), _bits(pc.v)), f"{what}: the cache was written without k_new"
     if check_ref:   # (a sequence that lost rows at the capacity is aligned by its clamped length: the dense picture above does not hold it)
-        kg, vg = pf._visible_dense(kd, total), pf._visible_dense(vd, total)
+        kg, vg = ks._visible_dense(kd, total), ks._visible_dense(vd, total)
         o_ref, l_ref = _reference(q_rot, qlens, kg, vg, total, n, window, causal)
         _check(out[:used], o_ref, dtype, f"{what} out")
         _check_lse(lse[:, :used], l_ref, f"{what} lse")
@@ -415,7 +401,7 @@ def test_graph_replay_follows_offsets_lengths_table_and_query(pkg, dev):
     kd = _rand((B, Hkv, cap, D), dtype, dev, 603)
     vd = _rand((B, Hkv, cap, D), dtype, dev, 604, std=1.0)
     pc = _Paged(kd, vd, [cap] * B, page, max_pages, 605, alloc_all=True)   # every row finite: the lengths move
-    cos, sin = rp._tables(cap, D, dev, torch.float32)
+    cos, sin = ks._tables(cap, D, dev, torch.float32)
     n = _n_values((H,), dev, 606)
     cu = _cu([1, 1, 1, 1], dev)
     sl = torch.tensor([62, 100, 5, 300], dtype=torch.int32, device=dev)
@@ -426,7 +412,7 @@ def test_graph_replay_follows_offsets_lengths_table_and_query(pkg, dev):
         return pkg.flash_attention_n_kvcache_varlen_rope(q_, kc, vc, sl_, cu_, Sq, cos, sin, block_table=tab, k_new=kn_, v_new=vn_, softmax_n_param=n,
                                                          return_lse=True, window=W)
 
-    g, (go, glse) = win._capture(lambda: call(q, kn, vn, pc.k, pc.v, sl, cu, table))
+    g, (go, glse) = ks._capture(lambda: call(q, kn, vn, pc.k, pc.v, sl, cu, table))
     with torch.no_grad():   # the warm-up runs appended: the eager pools follow
         k_e.copy_(pc.k)
         v_e.copy_(pc.v)
@@ -459,7 +445,7 @@ def test_refusals_on_the_device(pkg, dev):
     sl = torch.zeros(2, dtype=torch.int32, device=dev)
     cu = torch.tensor([0, 4, 9], dtype=torch.int32, device=dev)
     bt = torch.zeros(2, 2, dtype=torch.int32, device=dev)
-    cos, sin = rp._tables(128, 32, dev, torch.float32)
+    cos, sin = ks._tables(128, 32, dev, torch.float32)
     fw, fr = pkg.flash_attention_n_kvcache_varlen_window, pkg.flash_attention_n_kvcache_varlen_rope
     assert fw(q, kc, kc, sl, cu, 8, 5, block_table=bt).shape == (10, 8, 64)
     assert fr(q, kc, kc, sl, cu, 8, cos, sin, block_table=bt, window=5).shape == (10, 8, 64)

@@ -1,7 +1,7 @@
 """flash_attention_n_kvcache_window on the GPU: a sliding window of W keys over the paged / dense K/V cache, decode and prefill kernels.
 
-Reference of every case: test_gpu_kvcache._reference (fp32 torch, explicit sink column) per batch element on q[b, :, :qlen_b], as
-test_gpu_kvprefill._reference_ragged does it, with the visibility  j < len_b and p_i - W < j <= p_i,  p_i = i + len_b - qlen_b.
+Reference of every case: kv_support.reference_rows (fp32 torch, explicit sink column, per batch element on q[b, :, :qlen_b]) under the
+rule W: the visibility  j < len_b and p_i - W < j <= p_i,  p_i = i + len_b - qlen_b.
 Gates: those of the cache tests, imported unchanged (REF_ATOL / REL_TRUE on `out`, 1e-4 on `lse`). Second witness: flash_attention_n
 on the gathered dense K/V with the same visibility as a boolean attn_mask.
 
@@ -15,92 +15,17 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import test_gpu_kvcache as dec   # noqa: E402
-import test_gpu_kvprefill as pre   # noqa: E402
-import test_kvcache_cpu as dcpu   # noqa: E402
-import test_kvprefill_cpu as pcpu   # noqa: E402
+import kv_args   # noqa: E402
+import kv_support as ks   # noqa: E402
 from flash_attention_softmax_n_amd import synth   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-NAN = float("nan")
-_rand, _check, _check_lse, _Paged, _gather, _n_values, _reference = (
-    dec._rand, dec._check, dec._check_lse, dec._Paged, dec._gather, dec._n_values, dec._reference)
-REL_TRUE = dec.REL_TRUE
+NAN = ks.NAN
+_rand, _check, _check_lse, _Paged, _gather, _n_values, _check_all, _case, _capture, _poison, _first = (
+    ks._rand, ks._check, ks._check_lse, ks._Paged, ks._gather, ks._n_values, ks._check_all, ks._case, ks._capture, ks._poison, ks._first)
+REL_TRUE = ks.REL_TRUE
 DTYPES = {"fp16": torch.float16, "bf16": torch.bfloat16}
-
-
-def _win_mask(lens, qlens, Sq, S, W, dev):
-    """[B, 1, Sq, S] bool: position i < qlen_b sees key j iff j < len_b and p_i - W < j <= p_i; padding positions see nothing"""
-    ln = torch.as_tensor(lens, device=dev).view(-1, 1, 1, 1)
-    ql = torch.as_tensor(qlens, device=dev).view(-1, 1, 1, 1)
-    i = torch.arange(Sq, device=dev).view(1, 1, Sq, 1)
-    j = torch.arange(S, device=dev).view(1, 1, 1, S)
-    p = i + ln - ql
-    return (j < ln) & (i < ql) & (j <= p) & (j > p - W)
-
-
-def _reference_window(q, kg, vg, lens, qlens, n, W, scale=None):
-    """per batch element on q[b, :, :qlen_b]; padding positions: 0 / -inf"""
-    B, H, Sq, D = q.shape
-    dev = q.device
-    o = torch.zeros(B, H, Sq, D, dtype=torch.float32, device=dev)
-    lse = torch.full((B, H, Sq), float("-inf"), dtype=torch.float32, device=dev)
-    nt = torch.as_tensor(n, dtype=torch.float32, device=dev)
-    nb = nt.reshape((1,) * (2 - nt.dim()) + tuple(nt.shape)).expand(B, H)
-    for b in range(B):
-        ql = qlens[b]
-        if ql == 0:
-            continue
-        vis = _win_mask([lens[b]], [ql], ql, kg.shape[2], W, dev)
-        ob, lb = _reference(q[b:b + 1, :, :ql], kg[b:b + 1], vg[b:b + 1], vis, nb[b:b + 1], scale)
-        o[b, :, :ql] = ob[0]
-        lse[b, :, :ql] = lb[0]
-    return o, lse
-
-
-def _first(ln, ql, W):
-    return 64 * (max(0, ln - ql - W + 1) // 64)
-
-
-def _poison(k, v, table, page, poison_id, lens, qlens, W):
-    """rows below first_b: NaN; table entries of pages wholly below first_b: the poison page. `lens` are the lengths the forward sees
-    (an append included). Returns the number of poisoned rows."""
-    tbl = table.cpu()
-    rows = 0
-    for b, (ln, ql) in enumerate(zip(lens, qlens)):
-        first = _first(ln, ql, W)
-        rows += first
-        for s in range(-(-first // page)):
-            pid, cnt = int(tbl[b, s]), min(page, first - s * page)
-            k[pid, :cnt] = NAN
-            v[pid, :cnt] = NAN
-        table[b, :first // page] = poison_id
-    return rows
-
-
-def _check_all(pkg, out, lse, q, kg, vg, lens, qlens, n, W, dtype, what, witness=True, scale=None):
-    B, H, Sq, D = q.shape
-    o_ref, lse_ref = _reference_window(q, kg, vg, lens, qlens, n, W, scale)
-    _check(out, o_ref, dtype, f"{what} out")
-    _check_lse(lse, lse_ref, f"{what} lse")
-    for b in range(B):   # padding: exactly 0 / -inf, whatever n is
-        assert (out[b, :, qlens[b]:] == 0).all() and (lse[b, :, qlens[b]:] == float("-inf")).all(), f"{what}: padding rows of batch element {b}"
-    if witness:
-        qz = q.clone()
-        for b in range(B):
-            qz[b, :, qlens[b]:] = 0
-        wit = pkg.flash_attention_n(qz, kg, vg, softmax_n_param=n, attn_mask=_win_mask(lens, qlens, Sq, kg.shape[2], W, q.device), scale=scale)
-        _check(out, wit, dtype, f"{what} out vs flash_attention_n(attn_mask)")
-    return o_ref, lse_ref
-
-
-def _case(dev, B, H, Hkv, Sq, D, dtype, page, lens, seed, max_pages=None):
-    max_pages = max_pages or max(1, max((ln + page - 1) // page for ln in lens)) + 1
-    q = _rand((B, H, Sq, D), dtype, dev, seed)
-    kd = _rand((B, Hkv, page * max_pages, D), dtype, dev, seed + 1)
-    vd = _rand((B, Hkv, page * max_pages, D), dtype, dev, seed + 2, std=1.0)
-    return q, _Paged(kd, vd, lens, page, max_pages, seed)
 
 
 def _run(pkg, dev, B, H, Hkv, Sq, D, dtype, page, lens, n, windows, seed=1, max_pages=None, what="", witness=True, qlens=None, prefill=False):
@@ -151,7 +76,7 @@ def test_window_decides_and_a_wide_window_is_no_window(pkg, dev, call):
     kg, vg = _gather(pc.k, pc.table, lens, page), _gather(pc.v, pc.table, lens, page)
     fa = pkg.flash_attention_n_kvcache if call == "decode" else pkg.flash_attention_n_kvcache_prefill
     qs = None if call == "decode" else torch.full((B,), Sq, dtype=torch.int32, device=dev)
-    with_ref, _ = _reference_window(q, kg, vg, lens, [Sq] * B, 1.0, W)
+    with_ref, _ = ks.reference_rows(q, kg, vg, lens, [Sq] * B, 1.0, W)
     plain, plain_lse = fa(q, pc.k, pc.v, pc.lens, block_table=pc.table, softmax_n_param=1.0, return_lse=True)
     err = (plain.float() - with_ref).abs().max().item()
     gate = REL_TRUE[dtype] * max(with_ref.abs().max().item(), 1e-2)
@@ -159,7 +84,7 @@ def test_window_decides_and_a_wide_window_is_no_window(pkg, dev, call):
     assert err >= 10 * gate, "the window is a no-op at this shape: the tests of this file would show nothing"
     # a window at or beyond the capacity: the no-window reference (the imported one), through the window kernels
     capacity = page * pc.max_pages
-    o0, l0 = pre._reference_ragged(q, kg, vg, lens, [Sq] * B, 1.0, True)
+    o0, l0 = ks.reference_rows(q, kg, vg, lens, [Sq] * B, 1.0, True)
     for wide in (capacity, capacity + 1, 10 ** 12):
         out, lse = pkg.flash_attention_n_kvcache_window(q, pc.k, pc.v, pc.lens, wide, block_table=pc.table, query_seqlens=qs,
                                                         softmax_n_param=1.0, return_lse=True)
@@ -183,10 +108,10 @@ def test_split_k(pkg, dev, call):
     B, H, Hkv, D, page, max_pages, lens, W = 1, 64, 8, 64, 256, 20, [5000], 3000
     Sq, qlens = (1, None) if call == "decode" else (64, [37])
     if call == "decode":
-        plan = pkg._lib.kvcache_window_plan(dcpu._args(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), _window_operand(pkg, W))
+        plan = pkg._lib.kvcache_window_plan(kv_args._args_decode(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), _window_operand(pkg, W))
         assert plan[0][0].startswith("fasn_kvcache_fwd_window_kernel<") and plan[0][1] > B * Hkv, plan
     else:
-        plan = pkg._lib.kvprefill_window_plan(pcpu._args(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), _window_operand(pkg, W))
+        plan = pkg._lib.kvprefill_window_plan(kv_args._args_prefill(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), _window_operand(pkg, W))
         assert [k[0].split("<")[0] for k in plan] == ["fasn_kvprefill_fwd_window_kernel", "fasn_kvprefill_combine_kernel"]
         assert plan[0][1] > B * Hkv * -(-Sq // (128 // (H // Hkv))), plan
     assert _first(lens[0], (qlens or [Sq])[0], W) >= 7 * page                            # whole pages lie below the window: poisoned
@@ -250,7 +175,7 @@ def test_prefill_ragged_queries(pkg, dev, W, append):
     out, lse = pkg.flash_attention_n_kvcache_window(q, pc.k, pc.v, pc.lens, W, block_table=pc.table, k_new=kn if append else None,
                                                     v_new=vn if append else None, query_seqlens=qs, softmax_n_param=n, return_lse=True)
     assert torch.equal(pc.lens.cpu(), torch.tensor(lens, dtype=torch.int32)), "cache_seqlens was modified"
-    _check_all(pkg, out, lse, q, pre._visible_dense(kd, total), pre._visible_dense(vd, total), total, qlens, n, W, dtype,
+    _check_all(pkg, out, lse, q, ks._visible_dense(kd, total), ks._visible_dense(vd, total), total, qlens, n, W, dtype,
                f"prefill ragged W={W} append={append}")
 
 
@@ -295,19 +220,6 @@ def test_both_branches_agree(pkg, dev, W):
 
 
 # ---------------------------------------------------------------- 7. HIP graph: the window's first tile follows the lengths in device memory
-def _capture(fn):
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for _ in range(2):
-            fn()
-    torch.cuda.current_stream().wait_stream(side)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        res = fn()
-    return g, res
-
-
 # W = 64 on 64-key pages: one split, and the window start crosses a tile and page edge between the replays. The plan has several splits
 # only where a window spans 8 tiles (decode) / 32 tiles (prefill) and more, so those two shapes carry the same walk at longer lengths.
 REPLAYS = {
@@ -326,10 +238,10 @@ def test_graph_replay_follows_the_lengths(pkg, dev, shape):
     Sq, W, max_pages = s["Sq"], s["W"], s["max_pages"]
     operand = _window_operand(pkg, W)
     if s["prefill"]:
-        plan = pkg._lib.kvprefill_window_plan(pcpu._args(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), operand)
+        plan = pkg._lib.kvprefill_window_plan(kv_args._args_prefill(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), operand)
         assert (len(plan) == 2) == s["splits"], plan
     else:
-        plan = pkg._lib.kvcache_window_plan(dcpu._args(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), operand)
+        plan = pkg._lib.kvcache_window_plan(kv_args._args_decode(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), operand)
         assert (plan[0][1] > B * Hkv) == s["splits"], plan
     q = _rand((B, H, Sq, D), dtype, dev, 900)
     n_pages = B * max_pages
@@ -389,7 +301,7 @@ def test_gpt_oss_sliding_layer(pkg, dev):
         sl = torch.tensor(lens, dtype=torch.int32, device=dev)
         out, lse = pkg.flash_attention_n_kvcache_window(q, pc.k, pc.v, sl, W, block_table=pc.table, k_new=kn, v_new=vn, softmax_n_param=n,
                                                         return_lse=True)
-        _check_all(pkg, out, lse, q, pre._visible_dense(kd, total), pre._visible_dense(vd, total), total, [Sq] * B, n, W, dtype,
+        _check_all(pkg, out, lse, q, ks._visible_dense(kd, total), ks._visible_dense(vd, total), total, [Sq] * B, n, W, dtype,
                    f"GPT-OSS sliding layer Sq={Sq}")
         lens = total
 
@@ -405,7 +317,7 @@ def test_deterministic(pkg, dev, call):
     else:
         B, Sq, max_pages, lens, W = 1, 64, 20, [5000], 3000
     if call != "decode":
-        plan = pkg._lib.kvprefill_window_plan(pcpu._args(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), _window_operand(pkg, W))
+        plan = pkg._lib.kvprefill_window_plan(kv_args._args_prefill(pkg, B=B, H=H, Hkv=Hkv, Sq=Sq, D=D, page=page, max_pages=max_pages), _window_operand(pkg, W))
         assert len(plan) == (2 if call == "prefill several splits" else 1)
     q, pc = _case(dev, B, H, Hkv, Sq, D, dtype, page, lens, 1000, max_pages=max_pages)
     n = _n_values((H,), dev, 1001)

@@ -19,12 +19,8 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kv_witness as kw   # noqa: E402
-import test_gpu_kvcache as dec   # noqa: E402
-import test_gpu_kvprefill as pre   # noqa: E402
-import test_gpu_kvvarlen as vl   # noqa: E402
-import test_gpu_kvwindow as win   # noqa: E402
-import test_kvcache_cpu as dcpu   # noqa: E402
-import test_kvprefill_cpu as pcpu   # noqa: E402
+import kv_args   # noqa: E402
+import kv_support as ks   # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -67,8 +63,8 @@ SHAPES = {
     "varlen H12/4": Case("varlen", 12, 4, 64, 87, VL(64), qlens=VQ(42)),
     "varlen H12/4 full": Case("varlen", 12, 4, 64, 87, VL(64), qlens=VQ(42), causal=False),
     "varlen H12/4 D128 append": Case("varlen", 12, 4, 128, 87, VL(64), qlens=VQ(42), append=True),
-    "varlen split": Case("varlen", vl.SPLIT["H"], vl.SPLIT["Hkv"], vl.SPLIT["D"], 40, [4000, 2100], page=vl.SPLIT["page"],
-                         max_pages=vl.SPLIT["max_pages"], qlens=vl.SPLIT["qlens"], long=True),
+    "varlen split": Case("varlen", ks.VARLEN_SPLIT["H"], ks.VARLEN_SPLIT["Hkv"], ks.VARLEN_SPLIT["D"], 40, [4000, 2100], page=ks.VARLEN_SPLIT["page"],
+                         max_pages=ks.VARLEN_SPLIT["max_pages"], qlens=ks.VARLEN_SPLIT["qlens"], long=True),
 }
 ALIBI = {
     "alibi decode D64 Sq3": Case("decode", 16, 4, 64, 3, LENS, alibi=True),
@@ -86,20 +82,20 @@ def _assert_split(pkg, name, case):
     shape = dict(B=case.B, H=case.H, Hkv=case.Hkv, Sq=case.Sq, D=case.D, page=case.page, max_pages=case.max_pages)
     operand = None if case.window is None else pkg._lib.KvWindow(window=case.window, reserved=0)
     if case.route == "decode":
-        plan = pkg._lib.kvcache_plan(dcpu._args(pkg, **shape))
+        plan = pkg._lib.kvcache_plan(kv_args._args_decode(pkg, **shape))
         assert plan[0][0].startswith("fasn_kvcache_fwd_kernel<") and plan[0][1] > case.B * case.Hkv, plan
     elif case.route == "window_decode":
-        plan = pkg._lib.kvcache_window_plan(dcpu._args(pkg, **shape), operand)
+        plan = pkg._lib.kvcache_window_plan(kv_args._args_decode(pkg, **shape), operand)
         assert plan[0][0].startswith("fasn_kvcache_fwd_window_kernel<") and plan[0][1] > case.B * case.Hkv, plan
     elif case.route == "prefill":
-        assert pre._plan_names(pkg, **shape) == ["fasn_kvprefill_fwd_kernel", "fasn_kvprefill_combine_kernel"]
+        assert ks._plan_names(pkg, **shape) == ["fasn_kvprefill_fwd_kernel", "fasn_kvprefill_combine_kernel"]
     elif case.route == "window_prefill":
-        plan = pkg._lib.kvprefill_window_plan(pcpu._args(pkg, **shape), operand)
+        plan = pkg._lib.kvprefill_window_plan(kv_args._args_prefill(pkg, **shape), operand)
         assert [k[0].split("<")[0] for k in plan] == ["fasn_kvprefill_fwd_window_kernel", "fasn_kvprefill_combine_kernel"]
-        assert win._first(case.total[0], case.qlens[0], case.window) >= 7 * case.page   # whole pages lie below the window: poisoned
+        assert ks._first(case.total[0], case.qlens[0], case.window) >= 7 * case.page   # whole pages lie below the window: poisoned
     else:
         assert case.tail == 7
-        vl._split_plan(pkg)
+        ks._varlen_split_plan(pkg)
 
 
 def _seed(name):
@@ -148,7 +144,7 @@ def test_b_one_key_decides(pkg, dev, name, form, dtype):
     for b, (lse, want, kind) in enumerate(lses):
         for k in (0, 1, 2):   # rows of one kind together: log n is not measured against a key's thousands of nats
             if (kind == k).any():
-                dec._check_lse(lse[kind == k], want[kind == k], f"B {name} {form} {dtype} sequence {b} lse (rows of kind {k})")
+                ks._check_lse(lse[kind == k], want[kind == k], f"B {name} {form} {dtype} sequence {b} lse (rows of kind {k})")
     assert 1 in kinds and (form != "sink" or 2 in kinds)
 
 
@@ -165,4 +161,4 @@ def test_c_realistic_dynamic_range(pkg, dev, name, dtype, std):
     print(f"C {name} std {std} {dtype}: out at {max(ratios):.3g} of 3 u A + 1e-6")
     assert max(ratios) <= 1, f"out is {max(ratios):.3g}x (3 u A + 1e-6) from the fp64 reference, per sequence {ratios}"
     for b, ((_, lse), r) in enumerate(zip(got, refs)):
-        dec._check_lse(lse, r["lse"], f"C {name} std {std} {dtype} sequence {b} lse")
+        ks._check_lse(lse, r["lse"], f"C {name} std {std} {dtype} sequence {b} lse")

@@ -12,17 +12,11 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_kvcache_cpu as dec   # noqa: E402
-import test_kvprefill_cpu as pre   # noqa: E402
+import kv_args as ka   # noqa: E402
 
-DUMMY = 1 << 20
+DUMMY = ka.DUMMY
 NEW = ("fasn_fwd_kvcache_alibi", "fasn_fwd_kvprefill_alibi", "fasn_kvcache_alibi_plan", "fasn_kvprefill_alibi_plan")
-
-
-def _slopes(pkg, ptr=DUMMY + 512, sb=0, sh=1):
-    s = pkg._lib.AlibiSlopes()
-    s.slopes, s.stride_b, s.stride_h = ptr, sb, sh
-    return s
+_slopes, _renamed = ka._slopes, ka._renamed
 
 
 def test_symbols_are_exported_and_bound(pkg):
@@ -52,7 +46,7 @@ def test_validation_codes(pkg):
             return fn(a, s, DUMMY, big, None)
         return call
 
-    for which, make, kv in (("dec", dec._args, lambda a: a), ("pre", pre._args, lambda a: a.kv)):
+    for which, make, kv in (("dec", ka._args_decode, lambda a: a), ("pre", ka._args_prefill, lambda a: a.kv)):
         for plan in (False, True):
             call = run(which, plan)
             good = _slopes(pkg)
@@ -85,68 +79,64 @@ def test_validation_codes(pkg):
             assert call(make(pkg, seqlens=None), good) == -1
             assert call(make(pkg, D=96), None) == -3                                      # the base arguments are checked first
         assert run(which, True)(make(pkg, H=64, Hkv=8, Sq=17), _slopes(pkg)) == (-7 if which == "dec" else 0)   # the decode row limit
-    assert lib.fasn_fwd_kvprefill_alibi(pre._args(pkg, q_seqlens=DUMMY + 2), _slopes(pkg), DUMMY, big, None) == -4
-    a = pre._args(pkg, Sq=17)
+    assert lib.fasn_fwd_kvprefill_alibi(ka._args_prefill(pkg, q_seqlens=DUMMY + 2), _slopes(pkg), DUMMY, big, None) == -4
+    a = ka._args_prefill(pkg, Sq=17)
     a.kv.seqlen_add = 3
     assert lib.fasn_fwd_kvprefill_alibi(a, _slopes(pkg), DUMMY, big, None) == -1
     # the workspace is the base call's
-    a = dec._args(pkg)
+    a = ka._args_decode(pkg)
     need = lib.fasn_fwd_kvcache_workspace_bytes(a)
     assert need > 0
     assert lib.fasn_fwd_kvcache_alibi(a, _slopes(pkg), DUMMY, need - 1, None) == -8
     assert lib.fasn_fwd_kvcache_alibi(a, _slopes(pkg), None, need, None) == -8
     assert lib.fasn_fwd_kvcache_alibi(a, _slopes(pkg), DUMMY + 4, need, None) == -4
-    a = pre._args(pkg, **pre.CASES["gqa_chunk_long_cache"])
+    a = ka._args_prefill(pkg, **ka.PREFILL_CASES["gqa_chunk_long_cache"])
     need = lib.fasn_fwd_kvprefill_workspace_bytes(a)
     assert need > 0
     assert lib.fasn_fwd_kvprefill_alibi(a, _slopes(pkg), DUMMY, need - 1, None) == -8
     assert lib.fasn_fwd_kvprefill_alibi(a, _slopes(pkg), None, need, None) == -8
     assert lib.fasn_fwd_kvprefill_alibi(a, _slopes(pkg), DUMMY + 4, need, None) == -4
-    assert lib.fasn_kvcache_alibi_plan(dec._args(pkg), _slopes(pkg), None, 10) == -1
-    assert lib.fasn_kvcache_alibi_plan(dec._args(pkg), _slopes(pkg), buf, 8) == -1
-    assert lib.fasn_kvprefill_alibi_plan(pre._args(pkg), _slopes(pkg), buf, 8) == -1
-
-
-def _renamed(plan, old, new):
-    return [(k[0].replace(old + "<", new + "<"),) + tuple(k[1:]) for k in plan]
+    assert lib.fasn_kvcache_alibi_plan(ka._args_decode(pkg), _slopes(pkg), None, 10) == -1
+    assert lib.fasn_kvcache_alibi_plan(ka._args_decode(pkg), _slopes(pkg), buf, 8) == -1
+    assert lib.fasn_kvprefill_alibi_plan(ka._args_prefill(pkg), _slopes(pkg), buf, 8) == -1
 
 
 @pytest.mark.parametrize("dtype", [0, 1])
-@pytest.mark.parametrize("case", sorted(dec.CASES))
+@pytest.mark.parametrize("case", sorted(ka.DECODE_CASES))
 def test_decode_plan_is_the_base_plan_under_another_name(pkg, case, dtype):
-    c = dec.CASES[case]
-    base = pkg._lib.kvcache_plan(dec._args(pkg, dtype=dtype, **c))
-    plan = pkg._lib.kvcache_plan(dec._args(pkg, dtype=dtype, **c), _slopes(pkg))
+    c = ka.DECODE_CASES[case]
+    base = pkg._lib.kvcache_plan(ka._args_decode(pkg, dtype=dtype, **c))
+    plan = pkg._lib.kvcache_plan(ka._args_decode(pkg, dtype=dtype, **c), _slopes(pkg))
     tag = "fasn::%s_tag, %d" % ("bf16" if dtype else "f16", c["D"])
     assert [k[0] for k in plan] == [f"fasn_kvcache_fwd_alibi_kernel<{tag}>", f"fasn_kvcache_combine_kernel<{tag}>"]
     assert plan == _renamed(base, "fasn_kvcache_fwd_kernel", "fasn_kvcache_fwd_alibi_kernel")   # grid, block, LDS: equal
     # other lengths, other slopes, other slope strides (other device pointers): the same launches
-    other = pkg._lib.kvcache_plan(dec._args(pkg, dtype=dtype, seqlens=DUMMY + 4096, **c), _slopes(pkg, ptr=DUMMY + 8192, sb=c["H"], sh=1))
+    other = pkg._lib.kvcache_plan(ka._args_decode(pkg, dtype=dtype, seqlens=DUMMY + 4096, **c), _slopes(pkg, ptr=DUMMY + 8192, sb=c["H"], sh=1))
     assert other == plan
     # and the base plan did not move
     assert [k[0] for k in base] == [f"fasn_kvcache_fwd_kernel<{tag}>", f"fasn_kvcache_combine_kernel<{tag}>"]
 
 
 @pytest.mark.parametrize("dtype", [0, 1])
-@pytest.mark.parametrize("case", sorted(pre.CASES))
+@pytest.mark.parametrize("case", sorted(ka.PREFILL_CASES))
 def test_prefill_plan_is_the_base_plan_under_another_name(pkg, case, dtype):
-    c = pre.CASES[case]
+    c = ka.PREFILL_CASES[case]
     lib = pkg._lib.load()
-    base = pkg._lib.kvprefill_plan(pre._args(pkg, dtype=dtype, **c))
-    plan = pkg._lib.kvprefill_plan(pre._args(pkg, dtype=dtype, **c), _slopes(pkg))
+    base = pkg._lib.kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, **c))
+    plan = pkg._lib.kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, **c), _slopes(pkg))
     tag = "fasn::%s_tag, %d" % ("bf16" if dtype else "f16", c["D"])
     assert plan[0][0] == f"fasn_kvprefill_fwd_alibi_kernel<{tag}>"
-    assert len(plan) == (2 if pre.SPLIT[case] else 1)                                     # one split / several: both plans
+    assert len(plan) == (2 if ka.PREFILL_SPLIT[case] else 1)                                     # one split / several: both plans
     assert plan == _renamed(base, "fasn_kvprefill_fwd_kernel", "fasn_kvprefill_fwd_alibi_kernel")
     assert base[0][0] == f"fasn_kvprefill_fwd_kernel<{tag}>"
-    other = pkg._lib.kvprefill_plan(pre._args(pkg, dtype=dtype, seqlens=DUMMY + 4096, q_seqlens=DUMMY + 8192, **c), _slopes(pkg, ptr=DUMMY + 16384, sb=c["H"]))
+    other = pkg._lib.kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, seqlens=DUMMY + 4096, q_seqlens=DUMMY + 8192, **c), _slopes(pkg, ptr=DUMMY + 16384, sb=c["H"]))
     assert other == plan
-    appended = pre._args(pkg, dtype=dtype, **c)
+    appended = ka._args_prefill(pkg, dtype=dtype, **c)
     appended.kv.seqlen_add = c["Sq"]
     assert pkg._lib.kvprefill_plan(appended, _slopes(pkg)) == plan
     # the workspace is the base call's: the size fits exactly
-    ws = lib.fasn_fwd_kvprefill_workspace_bytes(pre._args(pkg, dtype=dtype, **c))
-    assert (ws > 0) == pre.SPLIT[case]
+    ws = lib.fasn_fwd_kvprefill_workspace_bytes(ka._args_prefill(pkg, dtype=dtype, **c))
+    assert (ws > 0) == ka.PREFILL_SPLIT[case]
     if ws:
         assert ws == plan[0][1] * 128 * (c["D"] + 2) * 4
 
@@ -165,10 +155,10 @@ def test_new_kernels_do_not_spill(pkg):
     by_pretty = dict(zip(pretty, names))
     wanted = set()
     for dtype in (0, 1):
-        for c in dec.CASES.values():
-            wanted.add(pkg._lib.kvcache_plan(dec._args(pkg, dtype=dtype, **c), _slopes(pkg))[0][0])
-        for c in pre.CASES.values():
-            wanted.add(pkg._lib.kvprefill_plan(pre._args(pkg, dtype=dtype, **c), _slopes(pkg))[0][0])
+        for c in ka.DECODE_CASES.values():
+            wanted.add(pkg._lib.kvcache_plan(ka._args_decode(pkg, dtype=dtype, **c), _slopes(pkg))[0][0])
+        for c in ka.PREFILL_CASES.values():
+            wanted.add(pkg._lib.kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, **c), _slopes(pkg))[0][0])
     assert len(wanted) == 8 and all("_alibi_kernel<" in n for n in wanted), wanted         # 2 kernels x 2 dtypes x 2 head dims
     for name in sorted(wanted):
         hit = [m for d, m in by_pretty.items() if d.startswith("void fasn::" + name + "(")]

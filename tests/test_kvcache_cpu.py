@@ -12,25 +12,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-DUMMY = 1 << 20
-
-
-def _args(pkg, B=4, H=64, Hkv=8, Sq=1, D=64, page=256, max_pages=32, dtype=1, paged=True, seqlens=DUMMY):
-    a = pkg._lib.KvCacheArgs()
-    for v in (a.q, a.o):
-        v.ptr = DUMMY
-        for i, s in enumerate((H * Sq * D, Sq * D, D, 1)):
-            v.stride[i] = s
-    a.lse = DUMMY
-    a.k_cache = a.v_cache = DUMMY
-    for i, s in enumerate((page * Hkv * D, Hkv * D, D)):
-        a.k_stride[i] = a.v_stride[i] = s
-    a.block_table = DUMMY if paged else None
-    a.block_table_stride, a.max_pages = max_pages, max_pages
-    a.seqlens, a.seqlen_add, a.page_size = seqlens, 0, page
-    a.B, a.H, a.kv_group, a.Sq, a.D, a.dtype = B, H, H // Hkv, Sq, D, dtype
-    a.scale, a.softmax_n, a.causal = D ** -0.5, 1.0, 1
-    return a
+from kv_args import DECODE_CASES as CASES, DUMMY, _args_decode as _args   # noqa: E402
 
 
 def test_validation_codes(pkg):
@@ -82,12 +64,6 @@ def test_validation_codes(pkg):
     assert lib.fasn_kvcache_plan(_args(pkg, D=96), buf, len(buf)) == -3
     # the dense cache: one page per batch element whose size need not be a multiple of 64
     assert lib.fasn_fwd_kvcache_workspace_bytes(_args(pkg, page=200, paged=False)) > 0
-
-
-CASES = {
-    "gqa": dict(B=4, H=64, Hkv=8, Sq=1, D=64, page=256, max_pages=32),
-    "mha": dict(B=64, H=16, Hkv=16, Sq=1, D=128, page=256, max_pages=32),
-}
 
 
 @pytest.mark.parametrize("case", sorted(CASES))

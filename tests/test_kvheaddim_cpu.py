@@ -15,11 +15,9 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_kvalibi_cpu as ali   # noqa: E402
-import test_kvcache_cpu as dec   # noqa: E402
-import test_kvprefill_cpu as pre   # noqa: E402
+import kv_args as ka   # noqa: E402
 
-DUMMY = dec.DUMMY
+DUMMY = ka.DUMMY
 NEW_DIMS = (32, 256)
 TAGS = {0: "fasn::f16_tag", 1: "fasn::bf16_tag"}
 LDS_BYTES = {32: 2 * 3 * 64 * 32 * 2, 256: 2 * 2 * 64 * 256 * 2}   # K and V, three / two buffers of 64 keys
@@ -62,12 +60,12 @@ def _pre_nsplit(c, D):
 def test_plan_entry_points_accept_the_new_head_dims(pkg, D, dtype):
     lib = pkg._lib.load()
     buf = ctypes.create_string_buffer(4096)
-    s = ali._slopes(pkg)
-    assert lib.fasn_kvcache_plan(dec._args(pkg, D=D, dtype=dtype), buf, len(buf)) > 0
-    assert lib.fasn_kvcache_alibi_plan(dec._args(pkg, D=D, dtype=dtype), s, buf, len(buf)) > 0
-    assert lib.fasn_kvprefill_plan(pre._args(pkg, D=D, dtype=dtype, Sq=300), buf, len(buf)) > 0
-    assert lib.fasn_kvprefill_alibi_plan(pre._args(pkg, D=D, dtype=dtype, Sq=300), s, buf, len(buf)) > 0
-    assert lib.fasn_fwd_kvcache_workspace_bytes(dec._args(pkg, D=D, dtype=dtype)) > 0
+    s = ka._slopes(pkg)
+    assert lib.fasn_kvcache_plan(ka._args_decode(pkg, D=D, dtype=dtype), buf, len(buf)) > 0
+    assert lib.fasn_kvcache_alibi_plan(ka._args_decode(pkg, D=D, dtype=dtype), s, buf, len(buf)) > 0
+    assert lib.fasn_kvprefill_plan(ka._args_prefill(pkg, D=D, dtype=dtype, Sq=300), buf, len(buf)) > 0
+    assert lib.fasn_kvprefill_alibi_plan(ka._args_prefill(pkg, D=D, dtype=dtype, Sq=300), s, buf, len(buf)) > 0
+    assert lib.fasn_fwd_kvcache_workspace_bytes(ka._args_decode(pkg, D=D, dtype=dtype)) > 0
     assert lib.fasn_abi_version() == 6
 
 
@@ -75,22 +73,22 @@ def test_plan_entry_points_accept_the_new_head_dims(pkg, D, dtype):
 def test_other_head_dims_are_still_refused(pkg, D):
     lib = pkg._lib.load()
     buf = ctypes.create_string_buffer(4096)
-    s = ali._slopes(pkg)
+    s = ka._slopes(pkg)
     big = ctypes.c_size_t(-1).value
     nv = pkg._lib.View4()
     nv.ptr = DUMMY
     for i, st in enumerate((8 * D, D, D, 1)):
         nv.stride[i] = st
-    assert lib.fasn_kvcache_plan(dec._args(pkg, D=D), buf, len(buf)) == -3
-    assert lib.fasn_kvcache_alibi_plan(dec._args(pkg, D=D), s, buf, len(buf)) == -3
-    assert lib.fasn_kvprefill_plan(pre._args(pkg, D=D), buf, len(buf)) == -3
-    assert lib.fasn_kvprefill_alibi_plan(pre._args(pkg, D=D), s, buf, len(buf)) == -3
-    assert lib.fasn_fwd_kvcache(dec._args(pkg, D=D), DUMMY, big, None) == -3
-    assert lib.fasn_fwd_kvprefill(pre._args(pkg, D=D), DUMMY, big, None) == -3
-    assert lib.fasn_kvcache_append(dec._args(pkg, D=D), nv, nv, None) == -3
-    assert lib.fasn_kvprefill_append(pre._args(pkg, D=D), nv, nv, None) == -3
-    assert lib.fasn_fwd_kvcache_workspace_bytes(dec._args(pkg, D=D)) == 0
-    assert lib.fasn_fwd_kvprefill_workspace_bytes(pre._args(pkg, D=D)) == 0
+    assert lib.fasn_kvcache_plan(ka._args_decode(pkg, D=D), buf, len(buf)) == -3
+    assert lib.fasn_kvcache_alibi_plan(ka._args_decode(pkg, D=D), s, buf, len(buf)) == -3
+    assert lib.fasn_kvprefill_plan(ka._args_prefill(pkg, D=D), buf, len(buf)) == -3
+    assert lib.fasn_kvprefill_alibi_plan(ka._args_prefill(pkg, D=D), s, buf, len(buf)) == -3
+    assert lib.fasn_fwd_kvcache(ka._args_decode(pkg, D=D), DUMMY, big, None) == -3
+    assert lib.fasn_fwd_kvprefill(ka._args_prefill(pkg, D=D), DUMMY, big, None) == -3
+    assert lib.fasn_kvcache_append(ka._args_decode(pkg, D=D), nv, nv, None) == -3
+    assert lib.fasn_kvprefill_append(ka._args_prefill(pkg, D=D), nv, nv, None) == -3
+    assert lib.fasn_fwd_kvcache_workspace_bytes(ka._args_decode(pkg, D=D)) == 0
+    assert lib.fasn_fwd_kvprefill_workspace_bytes(ka._args_prefill(pkg, D=D)) == 0
 
 
 @pytest.mark.parametrize("D", NEW_DIMS)
@@ -100,7 +98,7 @@ def test_validation_codes_hold_at_the_new_head_dims(pkg, D):
     lib = pkg._lib.load()
     big = ctypes.c_size_t(-1).value
     buf = ctypes.create_string_buffer(4096)
-    good = ali._slopes(pkg)
+    good = ka._slopes(pkg)
     nv = pkg._lib.View4()
     nv.ptr = DUMMY
     for i, st in enumerate((8 * D, D, D, 1)):
@@ -113,7 +111,7 @@ def test_validation_codes_hold_at_the_new_head_dims(pkg, D):
         "dec": [lambda a: neg(lib.fasn_kvcache_plan(a, buf, len(buf))), lambda a: neg(lib.fasn_kvcache_alibi_plan(a, good, buf, len(buf)))],
         "pre": [lambda a: neg(lib.fasn_kvprefill_plan(a, buf, len(buf))), lambda a: neg(lib.fasn_kvprefill_alibi_plan(a, good, buf, len(buf)))],
     }
-    for which, make, kv in (("dec", dec._args, lambda a: a), ("pre", pre._args, lambda a: a.kv)):
+    for which, make, kv in (("dec", ka._args_decode, lambda a: a), ("pre", ka._args_prefill, lambda a: a.kv)):
         for call in calls[which]:
             assert call(make(pkg, D=D)) == 0
             assert call(make(pkg, D=D, B=0)) == -1
@@ -138,23 +136,23 @@ def test_validation_codes_hold_at_the_new_head_dims(pkg, D):
             assert call(make(pkg, D=D, seqlens=None)) == -1
             assert call(make(pkg, D=D, H=64, Hkv=8, Sq=17)) == (-7 if which == "dec" else 0)   # the decode row limit: G * Sq = 136 rows
             assert call(make(pkg, D=D, H=64, Hkv=8, Sq=16)) == 0                          # 128 rows
-    assert lib.fasn_kvprefill_plan(pre._args(pkg, D=D, H=256, Hkv=1), buf, len(buf)) == -7
-    assert lib.fasn_kvprefill_plan(pre._args(pkg, D=D, q_seqlens=DUMMY + 2), buf, len(buf)) == -4
+    assert lib.fasn_kvprefill_plan(ka._args_prefill(pkg, D=D, H=256, Hkv=1), buf, len(buf)) == -7
+    assert lib.fasn_kvprefill_plan(ka._args_prefill(pkg, D=D, q_seqlens=DUMMY + 2), buf, len(buf)) == -4
     # the operand of the *_alibi entry points
-    assert lib.fasn_kvcache_alibi_plan(dec._args(pkg, D=D), None, buf, len(buf)) == -1
-    assert lib.fasn_kvprefill_alibi_plan(pre._args(pkg, D=D), ali._slopes(pkg, ptr=DUMMY + 2), buf, len(buf)) == -4
+    assert lib.fasn_kvcache_alibi_plan(ka._args_decode(pkg, D=D), None, buf, len(buf)) == -1
+    assert lib.fasn_kvprefill_alibi_plan(ka._args_prefill(pkg, D=D), ka._slopes(pkg, ptr=DUMMY + 2), buf, len(buf)) == -4
     # append: the same argument rules, then the views
-    assert lib.fasn_kvcache_append(dec._args(pkg, D=D, page=48), nv, nv, None) == -7
-    assert lib.fasn_kvcache_append(dec._args(pkg, D=D), None, nv, None) == -1
-    assert lib.fasn_kvprefill_append(pre._args(pkg, D=D, page=48), nv, nv, None) == -7
-    assert lib.fasn_kvprefill_append(pre._args(pkg, D=D), nv, None, None) == -1
+    assert lib.fasn_kvcache_append(ka._args_decode(pkg, D=D, page=48), nv, nv, None) == -7
+    assert lib.fasn_kvcache_append(ka._args_decode(pkg, D=D), None, nv, None) == -1
+    assert lib.fasn_kvprefill_append(ka._args_prefill(pkg, D=D, page=48), nv, nv, None) == -7
+    assert lib.fasn_kvprefill_append(ka._args_prefill(pkg, D=D), nv, None, None) == -1
     # workspace too small, missing, unaligned: decode, and the several-split prefill plan
-    a = dec._args(pkg, D=D)
+    a = ka._args_decode(pkg, D=D)
     need = lib.fasn_fwd_kvcache_workspace_bytes(a)
     assert need > 0
     for fwd in (lambda w, n: lib.fasn_fwd_kvcache(a, w, n, None), lambda w, n: lib.fasn_fwd_kvcache_alibi(a, good, w, n, None)):
         assert fwd(DUMMY, need - 1) == -8 and fwd(None, need) == -8 and fwd(DUMMY + 4, need) == -4
-    pa = pre._args(pkg, D=D, **PRE_CASES["chunk_long_cache"])
+    pa = ka._args_prefill(pkg, D=D, **PRE_CASES["chunk_long_cache"])
     need = lib.fasn_fwd_kvprefill_workspace_bytes(pa)
     assert need > 0
     for fwd in (lambda w, n: lib.fasn_fwd_kvprefill(pa, w, n, None), lambda w, n: lib.fasn_fwd_kvprefill_alibi(pa, good, w, n, None)):
@@ -168,7 +166,7 @@ def test_validation_codes_hold_at_the_new_head_dims(pkg, D):
 def test_decode_plan(pkg, D, case, dtype):
     c = dict(DEC_CASES[case], D=D)
     lib = pkg._lib.load()
-    plan = pkg._lib.kvcache_plan(dec._args(pkg, dtype=dtype, **c))
+    plan = pkg._lib.kvcache_plan(ka._args_decode(pkg, dtype=dtype, **c))
     tag = "%s, %d" % (TAGS[dtype], D)
     assert [k[0] for k in plan] == [f"fasn_kvcache_fwd_kernel<{tag}>", f"fasn_kvcache_combine_kernel<{tag}>"]
     assert all(k[1] > 0 and k[2] == 256 for k in plan)
@@ -177,17 +175,17 @@ def test_decode_plan(pkg, D, case, dtype):
     nsplit = _dec_nsplit(c, D)
     assert plan[0][1] == BK * nsplit
     assert plan[1][1] == -(-BK * R * (D // 4) // 256)
-    assert lib.fasn_fwd_kvcache_workspace_bytes(dec._args(pkg, dtype=dtype, **c)) == BK * nsplit * R * (D + 2) * 4
+    assert lib.fasn_fwd_kvcache_workspace_bytes(ka._args_decode(pkg, dtype=dtype, **c)) == BK * nsplit * R * (D + 2) * 4
     # other lengths, another table, other slopes (other device pointers): the same launches
-    other = dec._args(pkg, dtype=dtype, seqlens=DUMMY + 4096, **c)
+    other = ka._args_decode(pkg, dtype=dtype, seqlens=DUMMY + 4096, **c)
     other.block_table = DUMMY + 65536
     assert pkg._lib.kvcache_plan(other) == plan
-    appended = dec._args(pkg, dtype=dtype, **c)
+    appended = ka._args_decode(pkg, dtype=dtype, **c)
     appended.seqlen_add = c["Sq"]
     assert pkg._lib.kvcache_plan(appended) == plan
-    al = pkg._lib.kvcache_plan(dec._args(pkg, dtype=dtype, **c), ali._slopes(pkg))
-    assert al == ali._renamed(plan, "fasn_kvcache_fwd_kernel", "fasn_kvcache_fwd_alibi_kernel") and al != plan
-    assert pkg._lib.kvcache_plan(other, ali._slopes(pkg, ptr=DUMMY + 8192, sb=c["H"], sh=1)) == al
+    al = pkg._lib.kvcache_plan(ka._args_decode(pkg, dtype=dtype, **c), ka._slopes(pkg))
+    assert al == ka._renamed(plan, "fasn_kvcache_fwd_kernel", "fasn_kvcache_fwd_alibi_kernel") and al != plan
+    assert pkg._lib.kvcache_plan(other, ka._slopes(pkg, ptr=DUMMY + 8192, sb=c["H"], sh=1)) == al
 
 
 @pytest.mark.parametrize("dtype", [0, 1])
@@ -196,7 +194,7 @@ def test_decode_plan(pkg, D, case, dtype):
 def test_prefill_plan(pkg, D, case, dtype):
     c = dict(PRE_CASES[case], D=D)
     lib = pkg._lib.load()
-    plan = pkg._lib.kvprefill_plan(pre._args(pkg, dtype=dtype, **c))
+    plan = pkg._lib.kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, **c))
     tag = "%s, %d" % (TAGS[dtype], D)
     base, nsplit = _pre_nsplit(c, D)
     assert (nsplit > 1) == PRE_SPLIT[case]
@@ -204,22 +202,22 @@ def test_prefill_plan(pkg, D, case, dtype):
     assert [k[0] for k in plan] == want
     assert all(k[1] > 0 and k[2] == 256 for k in plan)
     assert plan[0][3] == LDS_BYTES[D] <= 163840 and plan[0][1] == base * nsplit
-    ws = lib.fasn_fwd_kvprefill_workspace_bytes(pre._args(pkg, dtype=dtype, **c))
+    ws = lib.fasn_fwd_kvprefill_workspace_bytes(ka._args_prefill(pkg, dtype=dtype, **c))
     assert ws == (base * nsplit * 128 * (D + 2) * 4 if nsplit > 1 else 0)
     if nsplit > 1:
         assert plan[1][3] == 0 and plan[1][1] == -(-base * 128 * (D // 4) // 256)
     else:   # one split: a NULL workspace is accepted by the recording call
         buf = ctypes.create_string_buffer(4096)
-        assert lib.fasn_kvprefill_plan(pre._args(pkg, dtype=dtype, **c), buf, len(buf)) > 0
-    other = pre._args(pkg, dtype=dtype, seqlens=DUMMY + 4096, q_seqlens=DUMMY + 8192, **c)
+        assert lib.fasn_kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, **c), buf, len(buf)) > 0
+    other = ka._args_prefill(pkg, dtype=dtype, seqlens=DUMMY + 4096, q_seqlens=DUMMY + 8192, **c)
     other.kv.block_table = DUMMY + 65536
     assert pkg._lib.kvprefill_plan(other) == plan and lib.fasn_fwd_kvprefill_workspace_bytes(other) == ws
-    appended = pre._args(pkg, dtype=dtype, **c)
+    appended = ka._args_prefill(pkg, dtype=dtype, **c)
     appended.kv.seqlen_add = c["Sq"]
     assert pkg._lib.kvprefill_plan(appended) == plan
-    al = pkg._lib.kvprefill_plan(pre._args(pkg, dtype=dtype, **c), ali._slopes(pkg))
-    assert al == ali._renamed(plan, "fasn_kvprefill_fwd_kernel", "fasn_kvprefill_fwd_alibi_kernel") and al != plan
-    assert pkg._lib.kvprefill_plan(other, ali._slopes(pkg, ptr=DUMMY + 16384, sb=c["H"])) == al
+    al = pkg._lib.kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, **c), ka._slopes(pkg))
+    assert al == ka._renamed(plan, "fasn_kvprefill_fwd_kernel", "fasn_kvprefill_fwd_alibi_kernel") and al != plan
+    assert pkg._lib.kvprefill_plan(other, ka._slopes(pkg, ptr=DUMMY + 16384, sb=c["H"])) == al
 
 
 def _plan_text(pkg):
@@ -229,12 +227,12 @@ def _plan_text(pkg):
         for dtype in (0, 1):
             for name in sorted(DEC_CASES):
                 buf = ctypes.create_string_buffer(4096)
-                rc = lib.fasn_kvcache_plan(dec._args(pkg, D=D, dtype=dtype, **DEC_CASES[name]), buf, len(buf))
+                rc = lib.fasn_kvcache_plan(ka._args_decode(pkg, D=D, dtype=dtype, **DEC_CASES[name]), buf, len(buf))
                 assert rc > 0, (name, D, dtype, rc)
                 got += [f"decode {name} {line}" for line in buf.value.decode().splitlines()]
             for name in sorted(PRE_CASES):
                 buf = ctypes.create_string_buffer(4096)
-                rc = lib.fasn_kvprefill_plan(pre._args(pkg, D=D, dtype=dtype, **PRE_CASES[name]), buf, len(buf))
+                rc = lib.fasn_kvprefill_plan(ka._args_prefill(pkg, D=D, dtype=dtype, **PRE_CASES[name]), buf, len(buf))
                 assert rc > 0, (name, D, dtype, rc)
                 got += [f"prefill {name} {line}" for line in buf.value.decode().splitlines()]
     return got
@@ -250,14 +248,14 @@ def test_plans_of_the_existing_head_dims_did_not_move(pkg, golden_dir):
     workgroups), and the prefill cases of test_kvprefill_cpu: the grids its own test derives"""
     lib = pkg._lib.load()
     got = []
-    for name in sorted(dec.CASES):
+    for name in sorted(ka.DECODE_CASES):
         buf = ctypes.create_string_buffer(4096)
-        assert lib.fasn_kvcache_plan(dec._args(pkg, **dec.CASES[name]), buf, len(buf)) > 0
+        assert lib.fasn_kvcache_plan(ka._args_decode(pkg, **ka.DECODE_CASES[name]), buf, len(buf)) > 0
         got += [f"{name} {line}" for line in buf.value.decode().splitlines()]
     assert got == open(os.path.join(golden_dir, "kvcache_plans.txt")).read().splitlines()
-    for name, c in pre.CASES.items():
+    for name, c in ka.PREFILL_CASES.items():
         base, nsplit = _pre_nsplit(c, c["D"])
-        assert pkg._lib.kvprefill_plan(pre._args(pkg, **c))[0][1] == base * nsplit
+        assert pkg._lib.kvprefill_plan(ka._args_prefill(pkg, **c))[0][1] == base * nsplit
 
 
 # ---------------------------------------------------------------- registers
@@ -276,9 +274,9 @@ def test_new_kernels_do_not_spill(pkg):
     fwd, side = set(), set()
     for D in NEW_DIMS:
         for dtype in (0, 1):
-            for al in (None, ali._slopes(pkg)):
-                d = pkg._lib.kvcache_plan(dec._args(pkg, D=D, dtype=dtype, **DEC_CASES["gqa"]), al)
-                p = pkg._lib.kvprefill_plan(pre._args(pkg, D=D, dtype=dtype, **PRE_CASES["chunk_long_cache"]), al)
+            for al in (None, ka._slopes(pkg)):
+                d = pkg._lib.kvcache_plan(ka._args_decode(pkg, D=D, dtype=dtype, **DEC_CASES["gqa"]), al)
+                p = pkg._lib.kvprefill_plan(ka._args_prefill(pkg, D=D, dtype=dtype, **PRE_CASES["chunk_long_cache"]), al)
                 fwd |= {d[0][0], p[0][0]}
                 side |= {d[1][0], p[1][0]}
         side |= {"fasn_kvcache_append_kernel<%d>" % D, "fasn_kvprefill_append_kernel<%d>" % D}

@@ -12,32 +12,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-DUMMY = 1 << 20
-
-
-def _kv(a, B=4, H=64, Hkv=8, Sq=1, D=64, page=256, max_pages=32, dtype=1, paged=True, seqlens=DUMMY):
-    """the fields test_kvcache_cpu._args sets, on an embedded or free-standing fasn_kvcache_args"""
-    for v in (a.q, a.o):
-        v.ptr = DUMMY
-        for i, s in enumerate((H * Sq * D, Sq * D, D, 1)):
-            v.stride[i] = s
-    a.lse = DUMMY
-    a.k_cache = a.v_cache = DUMMY
-    for i, s in enumerate((page * Hkv * D, Hkv * D, D)):
-        a.k_stride[i] = a.v_stride[i] = s
-    a.block_table = DUMMY if paged else None
-    a.block_table_stride, a.max_pages = max_pages, max_pages
-    a.seqlens, a.seqlen_add, a.page_size = seqlens, 0, page
-    a.B, a.H, a.kv_group, a.Sq, a.D, a.dtype = B, H, H // Hkv, Sq, D, dtype
-    a.scale, a.softmax_n, a.causal = D ** -0.5, 1.0, 1
-    return a
-
-
-def _args(pkg, q_seqlens=None, **kw):
-    pa = pkg._lib.KvPrefillArgs()
-    _kv(pa.kv, **kw)
-    pa.q_seqlens = q_seqlens
-    return pa
+from kv_args import DECODE_CASES, DUMMY, PREFILL_CASES as CASES, PREFILL_SPLIT as SPLIT, _args_decode, _args_prefill as _args   # noqa: E402
 
 
 def test_args_struct_extends_the_cache_struct(pkg):
@@ -110,16 +85,6 @@ def test_validation_codes(pkg):
     assert plan(_args(pkg, page=200, paged=False, Sq=300)) == 0
 
 
-# one split (many row blocks) / several splits (small batch, long cache)
-CASES = {
-    "gqa_prompts": dict(B=4, H=64, Hkv=8, Sq=2048, D=64, page=256, max_pages=32),
-    "mha_prompts": dict(B=8, H=16, Hkv=16, Sq=4096, D=128, page=256, max_pages=16),
-    "gqa_chunk_long_cache": dict(B=1, H=64, Hkv=8, Sq=64, D=64, page=256, max_pages=128),
-    "mha_chunk_long_cache": dict(B=2, H=16, Hkv=16, Sq=256, D=128, page=256, max_pages=64),
-}
-SPLIT = {"gqa_prompts": False, "mha_prompts": False, "gqa_chunk_long_cache": True, "mha_chunk_long_cache": True}
-
-
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_workspace_and_plan(pkg, case):
     c = CASES[case]
@@ -174,13 +139,12 @@ def test_new_kernels_do_not_spill(pkg, case):
 
 
 def test_decode_plans_did_not_move(pkg, golden_dir):
-    """The decode plans of test_kvcache_cpu.CASES, byte for byte those recorded from the commit before the prefill kernels were added"""
-    import test_kvcache_cpu as dec
+    """The decode plans of kv_args.DECODE_CASES, byte for byte those recorded from the commit before the prefill kernels were added"""
     lib = pkg._lib.load()
     got = []
-    for name in sorted(dec.CASES):
+    for name in sorted(DECODE_CASES):
         buf = ctypes.create_string_buffer(4096)
-        rc = lib.fasn_kvcache_plan(dec._args(pkg, **dec.CASES[name]), buf, len(buf))
+        rc = lib.fasn_kvcache_plan(_args_decode(pkg, **DECODE_CASES[name]), buf, len(buf))
         assert rc > 0, (name, rc)
         got += [f"{name} {line}" for line in buf.value.decode().splitlines()]
     want = open(os.path.join(golden_dir, "kvcache_plans.txt")).read().splitlines()

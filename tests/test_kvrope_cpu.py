@@ -14,31 +14,14 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_kvcache_cpu as dec   # noqa: E402
-import test_kvprefill_cpu as pre   # noqa: E402
+import kv_args as ka   # noqa: E402
 
-DUMMY = dec.DUMMY
+DUMMY = ka.DUMMY
 NEW = ("fasn_kvcache_rope_append", "fasn_kvprefill_rope_append", "fasn_kvcache_rope_append_plan", "fasn_kvprefill_rope_append_plan")
 DIMS = (32, 64, 128, 256)
 TAGS = {0: "fasn::f16_tag", 1: "fasn::bf16_tag"}
 EINVAL, EDTYPE, EHEADDIM, EALIGN, ESTRIDE, EUNSUPPORTED = -1, -2, -3, -4, -5, -7
-CAPACITY = 256 * 32   # of dec._args / pre._args
-
-
-def _rope(pkg, rows=CAPACITY, rd=64, table_dtype=2, interleaved=0, row_stride=None, cos=DUMMY, sin=DUMMY):
-    r = pkg._lib.KvRope()
-    r.cos, r.sin = cos, sin
-    r.row_stride = rd // 2 if row_stride is None else row_stride
-    r.rows, r.rotary_dim, r.table_dtype, r.interleaved = rows, rd, table_dtype, interleaved
-    return r
-
-
-def _view(pkg, heads, Sq, D, ptr=DUMMY):
-    v = pkg._lib.View4()
-    v.ptr = ptr
-    for i, s in enumerate((heads * Sq * D, Sq * D, D, 1)):
-        v.stride[i] = s
-    return v
+CAPACITY, _rope, _view = ka.CAPACITY, ka._rope, ka._view
 
 
 def _header():
@@ -85,7 +68,7 @@ def _callers(pkg, which, how):
 
 @pytest.mark.parametrize("which", ["dec", "pre"])
 def test_validation_codes(pkg, which):
-    make, kv = (dec._args, lambda a: a) if which == "dec" else (pre._args, lambda a: a.kv)
+    make, kv = (ka._args_decode, lambda a: a) if which == "dec" else (ka._args_prefill, lambda a: a.kv)
     H, Hkv, Sq, D = 64, 8, 1, 64
 
     def appended(**kw):
@@ -177,8 +160,8 @@ def test_validation_codes(pkg, which):
     else:
         assert _callers(pkg, "pre", "plan")(appended(H=64, Hkv=8, Sq=17), _rope(pkg), _view(pkg, 64, 17, 64), _view(pkg, 8, 17, 64),
                                             _view(pkg, 8, 17, 64)) == 0
-        assert lib.fasn_kvprefill_rope_append(pre._args(pkg, q_seqlens=DUMMY + 2), _rope(pkg), qo, None, None, None) == EALIGN
-        a = pre._args(pkg, Sq=17)
+        assert lib.fasn_kvprefill_rope_append(ka._args_prefill(pkg, q_seqlens=DUMMY + 2), _rope(pkg), qo, None, None, None) == EALIGN
+        a = ka._args_prefill(pkg, Sq=17)
         a.kv.seqlen_add = 3
         assert lib.fasn_kvprefill_rope_append(a, _rope(pkg), _view(pkg, 64, 17, 64), None, None, None) == EINVAL
         assert lib.fasn_kvprefill_rope_append_plan(appended(), _rope(pkg), qo, kn, kn, ctypes.create_string_buffer(8), 8) == EINVAL
@@ -198,10 +181,10 @@ def test_plan_is_one_launch_whose_grid_depends_on_shapes_only(pkg, which, D, dty
 
         def args(seqlens=DUMMY, **kw):
             if which == "dec":
-                a = dec._args(pkg, D=D, dtype=dtype, seqlens=seqlens, **c)
+                a = ka._args_decode(pkg, D=D, dtype=dtype, seqlens=seqlens, **c)
                 a.seqlen_add = Sq
                 return a
-            a = pre._args(pkg, D=D, dtype=dtype, seqlens=seqlens, **dict(c, **kw))
+            a = ka._args_prefill(pkg, D=D, dtype=dtype, seqlens=seqlens, **dict(c, **kw))
             a.kv.seqlen_add = Sq
             return a
         qo, kn = _view(pkg, H, Sq, D), _view(pkg, Hkv, Sq, D)
@@ -221,13 +204,13 @@ def test_plan_is_one_launch_whose_grid_depends_on_shapes_only(pkg, which, D, dty
 def test_plan_line_names_the_kernel(pkg):
     lib = pkg._lib.load()
     buf = ctypes.create_string_buffer(4096)
-    a = dec._args(pkg)
+    a = ka._args_decode(pkg)
     a.seqlen_add = 1
     rc = lib.fasn_kvcache_rope_append_plan(a, _rope(pkg), _view(pkg, 64, 1, 64), _view(pkg, 8, 1, 64), _view(pkg, 8, 1, 64), buf, len(buf))
     assert rc == len(buf.value) > 0
     assert buf.value.decode() == "fasn_kvrope_kernel<fasn::bf16_tag, 64> grid=5 block=256 lds=0 cfg=bf16,D=64\n"
     # the plans of the forwards that follow did not move
-    assert [k[0] for k in pkg._lib.kvcache_plan(dec._args(pkg))] == ["fasn_kvcache_fwd_kernel<fasn::bf16_tag, 64>", "fasn_kvcache_combine_kernel<fasn::bf16_tag, 64>"]
+    assert [k[0] for k in pkg._lib.kvcache_plan(ka._args_decode(pkg))] == ["fasn_kvcache_fwd_kernel<fasn::bf16_tag, 64>", "fasn_kvcache_combine_kernel<fasn::bf16_tag, 64>"]
 
 
 def test_new_kernels_do_not_spill(pkg):
@@ -243,7 +226,7 @@ def test_new_kernels_do_not_spill(pkg):
     wanted = set()
     for D in DIMS:
         for dtype in (0, 1):
-            a = dec._args(pkg, D=D, dtype=dtype)
+            a = ka._args_decode(pkg, D=D, dtype=dtype)
             a.seqlen_add = 1
             wanted.add(pkg._lib.kvrope_plan(a, _rope(pkg, rd=16), _view(pkg, 64, 1, D), _view(pkg, 8, 1, D), _view(pkg, 8, 1, D))[0][0])
     assert len(wanted) == 8 and all(n.startswith("fasn_kvrope_kernel<") for n in wanted), wanted

@@ -20,32 +20,15 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_kvhost_matrix_cpu as hm   # noqa: E402
-import test_kvprefill_cpu as pre   # noqa: E402
+import kv_args as ka   # noqa: E402
 
-DUMMY = 1 << 20
-BIG = ctypes.c_size_t(-1).value
+DUMMY, BIG = ka.DUMMY, ka.BIG
+_args, items_max, plan_cases = ka._args_varlen, ka.items_max, ka.plan_cases
 MATRIX = os.path.join(ROOT, "tests", "golden", "kvvarlen_host_matrix.txt")
 PLANS = os.path.join(ROOT, "tests", "golden", "kvvarlen_plans.txt")
 
 
-def _args(pkg, T=64, cu=DUMMY + 8192, **kw):
-    """a fasn_kvvarlen_args over test_kvprefill_cpu._kv's block: B sequences, Sq = max_seqlen_q, q / o as [1, H, T, D] views of [T, H, D]"""
-    va = pkg._lib.KvVarlenArgs()
-    a = pre._kv(va.pf.kv, **kw)
-    for v in (a.q, a.o):
-        for i, s in enumerate((0, a.D, a.H * a.D, 1)):
-            v.stride[i] = s
-    va.pf.q_seqlens = None
-    va.cu_seqlens_q, va.total_tokens, va.reserved = cu, T, 0
-    return va
-
-
 # ---------------------------------------------------------------- the schedule, mirrored
-def items_max(B, max_seqlen_q, T, PB):
-    return min(B * -(-max_seqlen_q // PB), T // PB + B)
-
-
 def schedule(cu, max_seqlen_q, T, PB):
     """fasn_kvvarlen_schedule_kernel in Python: [(b, rb, token0, qlen)], sequences in order, the last row block of a sequence first,
     cut at items_max"""
@@ -166,11 +149,11 @@ def test_args_struct_extends_the_prefill_struct(pkg):
 # ---------------------------------------------------------------- the order of the C ABI's checks
 BASES = ("pre_paged_qlens", "pre_dense_oddpage", "d256")
 PACKED_RULES = [
-    ("cu_null", lambda c: setattr(c, "cu", None)), ("q_seqlens_set", hm._attr("qlens", DUMMY + 4096)), ("tokens_0", lambda c: setattr(c, "T", 0)),
+    ("cu_null", lambda c: setattr(c, "cu", None)), ("q_seqlens_set", ka._attr("qlens", DUMMY + 4096)), ("tokens_0", lambda c: setattr(c, "T", 0)),
     ("reserved_1", lambda c: setattr(c, "reserved", 1)), ("cu_odd", lambda c: setattr(c, "cu", DUMMY + 2)),
     ("table_over", lambda c: (setattr(c.kv, "B", 1 << 22), setattr(c.kv, "Sq", 1), setattr(c.kv, "seqlen_add", 1), setattr(c, "T", 1 << 28))),
 ]
-CHAIN = hm.BASE_RULES + PACKED_RULES
+CHAIN = ka.BASE_RULES + PACKED_RULES
 
 
 def matrix_cases():
@@ -183,7 +166,7 @@ def matrix_cases():
 
 def _matrix_line(pkg, name, base, rules):
     L, lib = pkg._lib, pkg._lib.load()
-    c = hm.Case(L, dict(hm.BASES[base], qlens=False))
+    c = ka.Case(L, dict(ka.BASES[base], qlens=False))
     c.cu, c.T, c.reserved = DUMMY + 8192, 3 * c.kv.Sq + 5, 0
     for rule in rules:
         rule(c)
@@ -192,7 +175,7 @@ def _matrix_line(pkg, name, base, rules):
     va.pf.q_seqlens = c.qlens
     va.cu_seqlens_q, va.total_tokens, va.reserved = c.cu, c.T, c.reserved
     args = None if c.null else va
-    plan = hm._plan(lib.fasn_kvvarlen_plan, args)
+    plan = ka._plan(lib.fasn_kvvarlen_plan, args)
     got = [plan, str(lib.fasn_fwd_kvvarlen_workspace_bytes(args))]
     if plan.startswith("-"):   # the block itself is refused: the calls that would launch return the same way, before any HIP call
         got.append(f"fwd={lib.fasn_fwd_kvvarlen(args, 256, BIG, None)},{lib.fasn_kvvarlen_append(args, c.kn, c.vn, None)}")
@@ -220,16 +203,6 @@ def test_return_codes_equal_the_recorded_matrix(pkg):
 
 
 # ---------------------------------------------------------------- launch plans
-def plan_cases():
-    """each head dim x G in {1, 8} x a small step (several splits: few items, long cache) and a large one (one split)"""
-    out = {}
-    for D in (32, 64, 128, 256):
-        for H, Hkv in ((8, 8), (64, 8)):
-            out[f"D{D}_G{H // Hkv}_small"] = dict(B=4, H=H, Hkv=Hkv, Sq=48, D=D, page=256, max_pages=64, T=64)
-            out[f"D{D}_G{H // Hkv}_large"] = dict(B=257, H=H, Hkv=Hkv, Sq=4096, D=D, page=256, max_pages=32, T=4352)
-    return out
-
-
 def plan_lines(pkg):
     lib = pkg._lib.load()
     got = []
@@ -268,7 +241,7 @@ def test_plan_follows_the_item_table(pkg, case):
     other.pf.kv.seqlen_add = c["Sq"]
     assert pkg._lib.kvvarlen_plan(other) == plan
     # the padded call's grid for the same step, for the record: B * Hkv * ceil(Sq / PB) blocks against items_max * Hkv
-    padded = pkg._lib.kvprefill_plan(pre._args(pkg, **{k: v for k, v in c.items() if k != "T"}))
+    padded = pkg._lib.kvprefill_plan(ka._args_prefill(pkg, **{k: v for k, v in c.items() if k != "T"}))
     assert padded[0][1] >= plan[1][1] // nsplit
 
 

@@ -20,31 +20,16 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_kvrope_cpu as rcpu   # noqa: E402
-import test_kvvarlen_cpu as vcpu   # noqa: E402
+import kv_args as ka   # noqa: E402
 
-DUMMY = vcpu.DUMMY
-BIG = vcpu.BIG
+DUMMY, BIG = ka.DUMMY, ka.BIG
 PLANS = os.path.join(ROOT, "tests", "golden", "kvvarlen_layer_plans.txt")
 EINVAL, EDTYPE, EHEADDIM, EALIGN, ESTRIDE, EUNSUPPORTED, EWORKSPACE = -1, -2, -3, -4, -5, -7, -8
 NEW = ("fasn_fwd_kvvarlen_window_workspace_bytes", "fasn_fwd_kvvarlen_window", "fasn_kvvarlen_window_plan", "fasn_kvvarlen_rope_append",
        "fasn_kvvarlen_rope_append_plan")
 DIMS = (32, 64, 128, 256)
 TAGS = {0: "fasn::f16_tag", 1: "fasn::bf16_tag"}
-_args, items_max = vcpu._args, vcpu.items_max
-
-
-def _win(pkg, window=128, reserved=0):
-    return pkg._lib.KvWindow(window=window, reserved=reserved)
-
-
-def _tview(pkg, heads, D, ptr=DUMMY):
-    """a [1, heads, T, D] view of a [T, heads, D] buffer"""
-    v = pkg._lib.View4()
-    v.ptr = ptr
-    for i, s in enumerate((0, D, heads * D, 1)):
-        v.stride[i] = s
-    return v
+_args, items_max, _win, _tview = ka._args_varlen, ka.items_max, ka._win, ka._tview
 
 
 def _appended(pkg, **kw):
@@ -242,7 +227,7 @@ def test_window_return_codes(pkg):
     assert lib.fasn_kvvarlen_window_plan(nc, _win(pkg, 0), buf, len(buf)) == EINVAL   # the operand's own values before what it asks of the block
     # accepted: any window >= 1; the workspace is always asked for (the item table), NULL / short EWORKSPACE, misaligned EALIGN
     for W in (1, 128, 1 << 13, 2 ** 31 - 1):
-        for c in vcpu.plan_cases().values():
+        for c in ka.plan_cases().values():
             va = _args(pkg, **c)
             assert lib.fasn_kvvarlen_window_plan(va, _win(pkg, W), buf, len(buf)) > 0
             assert lib.fasn_fwd_kvvarlen_window_workspace_bytes(va, _win(pkg, W)) >= 32
@@ -256,8 +241,8 @@ def test_window_return_codes(pkg):
 def test_rope_return_codes(pkg):
     """the operand's codes as tests/test_kvrope_cpu.py has them for the padded calls"""
     lib = pkg._lib.load()
-    H, Hkv, D, CAP = 64, 8, 64, rcpu.CAPACITY
-    _rope = rcpu._rope
+    H, Hkv, D, CAP = 64, 8, 64, ka.CAPACITY
+    _rope = ka._rope
     qo, kn = _tview(pkg, H, D), _tview(pkg, Hkv, D)
     buf = ctypes.create_string_buffer(4096)
 
@@ -317,7 +302,7 @@ GOLDEN_WINDOWS = (1, 128, 3000)
 def plan_lines(pkg):
     lib = pkg._lib.load()
     got = []
-    for name, c in sorted(vcpu.plan_cases().items()):
+    for name, c in sorted(ka.plan_cases().items()):
         for W in GOLDEN_WINDOWS:
             va = _args(pkg, **c)
             buf = ctypes.create_string_buffer(4096)
@@ -330,7 +315,7 @@ def plan_lines(pkg):
             va = _appended(pkg, **c) if new else _args(pkg, **c)
             kn = _tview(pkg, Hkv, D) if new else None
             buf = ctypes.create_string_buffer(4096)
-            rc = lib.fasn_kvvarlen_rope_append_plan(va, rcpu._rope(pkg, rows=c["page"] * c["max_pages"], rd=min(D, 64)), _tview(pkg, H, D), kn, kn, buf, len(buf))
+            rc = lib.fasn_kvvarlen_rope_append_plan(va, ka._rope(pkg, rows=c["page"] * c["max_pages"], rd=min(D, 64)), _tview(pkg, H, D), kn, kn, buf, len(buf))
             assert rc > 0, (name, new, rc)
             got += [f"{name} rope{'+append' if new else ''} {line}" for line in buf.value.decode().splitlines()]
     return got
@@ -401,13 +386,13 @@ def test_rope_plan_is_one_launch_whose_grid_depends_on_shapes_only(pkg, dtype, D
     for c in (dict(B=4, H=64, Hkv=8, Sq=48, T=64), dict(B=3, H=8, Hkv=2, Sq=3, T=1), dict(B=257, H=16, Hkv=16, Sq=4096, T=4352), dict(B=2, H=12, Hkv=4, Sq=70, T=77)):
         H, Hkv, T = c["H"], c["Hkv"], c["T"]
         qo, kn = _tview(pkg, H, D), _tview(pkg, Hkv, D)
-        rope = rcpu._rope(pkg, rd=16)
+        rope = ka._rope(pkg, rd=16)
         plan = pkg._lib.kvrope_plan(_appended(pkg, D=D, dtype=dtype, **c), rope, qo, kn, kn)
         assert plan == [(f"fasn_kvvarlen_rope_kernel<{TAGS[dtype]}, {D}>", -(-((T * Hkv + T * H) * (D // 16)) // 256), 256, 0)]
         only_q = pkg._lib.kvrope_plan(_args(pkg, D=D, dtype=dtype, **c), rope, qo)
         assert only_q == [(plan[0][0], -(-(T * H * (D // 16)) // 256), 256, 0)]
         other = _appended(pkg, D=D, dtype=dtype, cu=DUMMY + 64, seqlens=DUMMY + 4096, **c)   # other offsets and lengths: the same launch
-        assert pkg._lib.kvrope_plan(other, rcpu._rope(pkg, rd=16, interleaved=1, table_dtype=dtype), qo, kn, kn) == plan
+        assert pkg._lib.kvrope_plan(other, ka._rope(pkg, rd=16, interleaved=1, table_dtype=dtype), qo, kn, kn) == plan
 
 
 # ---------------------------------------------------------------- registers
@@ -422,9 +407,9 @@ def test_new_kernels_do_not_spill(pkg, D):
     pretty = subprocess.run([spill_map.CXXFILT], input="\n".join(names), capture_output=True, text=True, check=True).stdout.splitlines()
     by_pretty = dict(zip(pretty, names))
     for dtype in (0, 1):
-        c = vcpu.plan_cases()[f"D{D}_G8_small"]
+        c = ka.plan_cases()[f"D{D}_G8_small"]
         wanted = [pkg._lib.kvvarlen_window_plan(_args(pkg, dtype=dtype, **c), _win(pkg, 3000))[1][0],
-                  pkg._lib.kvrope_plan(_args(pkg, dtype=dtype, **c), rcpu._rope(pkg, rows=c["page"] * c["max_pages"], rd=16), _tview(pkg, c["H"], D))[0][0]]
+                  pkg._lib.kvrope_plan(_args(pkg, dtype=dtype, **c), ka._rope(pkg, rows=c["page"] * c["max_pages"], rd=16), _tview(pkg, c["H"], D))[0][0]]
         assert wanted == [f"fasn_kvvarlen_fwd_window_kernel<{TAGS[dtype]}, {D}>", f"fasn_kvvarlen_rope_kernel<{TAGS[dtype]}, {D}>"]
         for name in wanted:
             hit = [m for d, m in by_pretty.items() if d.startswith("void fasn::" + name + "(")]

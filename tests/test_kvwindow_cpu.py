@@ -14,23 +14,15 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
-import test_kvcache_cpu as dec   # noqa: E402
-import test_kvprefill_cpu as pre   # noqa: E402
+import kv_args as ka   # noqa: E402
 
-DUMMY = dec.DUMMY
+DUMMY = ka.DUMMY
 NEW = ("fasn_fwd_kvcache_window_workspace_bytes", "fasn_fwd_kvcache_window", "fasn_kvcache_window_plan",
        "fasn_fwd_kvprefill_window_workspace_bytes", "fasn_fwd_kvprefill_window", "fasn_kvprefill_window_plan")
 DIMS = (32, 64, 128, 256)
 TAGS = {0: "fasn::f16_tag", 1: "fasn::bf16_tag"}
 GOLDEN_WINDOWS = (1, 128, 1000)
-
-
-def _win(pkg, window=128, reserved=0):
-    return pkg._lib.KvWindow(window=window, reserved=reserved)
-
-
-def _renamed(plan, old, new):
-    return [(k[0].replace(old + "<", new + "<"),) + tuple(k[1:]) for k in plan]
+_win, _renamed = ka._win, ka._renamed
 
 
 def test_symbols_are_exported_and_bound(pkg):
@@ -63,7 +55,7 @@ def test_validation_codes(pkg):
             return getattr(lib, f"fasn_fwd_{stem}_window")(a, w, DUMMY, big, None)
         return call
 
-    for which, make, kv in (("dec", dec._args, lambda a: a), ("pre", pre._args, lambda a: a.kv)):
+    for which, make, kv in (("dec", ka._args_decode, lambda a: a), ("pre", ka._args_prefill, lambda a: a.kv)):
         for how in ("fwd", "plan"):
             call = run(which, how)
             good = _win(pkg)
@@ -108,19 +100,19 @@ def test_validation_codes(pkg):
         a = make(pkg)
         kv(a).causal = 0
         assert ws(a, _win(pkg)) is None
-    assert lib.fasn_fwd_kvprefill_window(pre._args(pkg, q_seqlens=DUMMY + 2), _win(pkg), DUMMY, big, None) == -4
-    a = pre._args(pkg, Sq=17)
+    assert lib.fasn_fwd_kvprefill_window(ka._args_prefill(pkg, q_seqlens=DUMMY + 2), _win(pkg), DUMMY, big, None) == -4
+    a = ka._args_prefill(pkg, Sq=17)
     a.kv.seqlen_add = 3
     assert lib.fasn_fwd_kvprefill_window(a, _win(pkg), DUMMY, big, None) == -1
     # then the workspace: missing, too small, misaligned - sized by the window call's own size function
-    a = dec._args(pkg)
+    a = ka._args_decode(pkg)
     need = lib.fasn_fwd_kvcache_window_workspace_bytes(a, _win(pkg))
     assert 0 < need <= lib.fasn_fwd_kvcache_workspace_bytes(a)
     assert lib.fasn_fwd_kvcache_window(a, _win(pkg), DUMMY, need - 1, None) == -8
     assert lib.fasn_fwd_kvcache_window(a, _win(pkg), None, need, None) == -8
     assert lib.fasn_fwd_kvcache_window(a, _win(pkg), DUMMY + 4, need, None) == -4
     assert lib.fasn_fwd_kvcache_window(a, None, None, 0, None) == -1                      # (the operand before the workspace)
-    a = pre._args(pkg, **pre.CASES["gqa_chunk_long_cache"])
+    a = ka._args_prefill(pkg, **ka.PREFILL_CASES["gqa_chunk_long_cache"])
     wide = _win(pkg, window=1 << 20)                                                      # several splits: the base plan
     need = lib.fasn_fwd_kvprefill_window_workspace_bytes(a, wide)
     assert need == lib.fasn_fwd_kvprefill_workspace_bytes(a) > 0
@@ -128,9 +120,9 @@ def test_validation_codes(pkg):
     assert lib.fasn_fwd_kvprefill_window(a, wide, None, need, None) == -8
     assert lib.fasn_fwd_kvprefill_window(a, wide, DUMMY + 4, need, None) == -4
     assert lib.fasn_fwd_kvprefill_window_workspace_bytes(a, _win(pkg)) == 0               # one split under W = 128: no workspace at all
-    assert lib.fasn_kvcache_window_plan(dec._args(pkg), _win(pkg), None, 10) == -1
-    assert lib.fasn_kvcache_window_plan(dec._args(pkg), _win(pkg), buf, 8) == -1
-    assert lib.fasn_kvprefill_window_plan(pre._args(pkg), _win(pkg), buf, 8) == -1
+    assert lib.fasn_kvcache_window_plan(ka._args_decode(pkg), _win(pkg), None, 10) == -1
+    assert lib.fasn_kvcache_window_plan(ka._args_decode(pkg), _win(pkg), buf, 8) == -1
+    assert lib.fasn_kvprefill_window_plan(ka._args_prefill(pkg), _win(pkg), buf, 8) == -1
 
 
 def _dec_window_nsplit(c, D, W):
@@ -149,83 +141,83 @@ def _pre_window_nsplit(c, D, W):
 
 @pytest.mark.parametrize("dtype", [0, 1])
 @pytest.mark.parametrize("D", DIMS)
-@pytest.mark.parametrize("case", sorted(dec.CASES))
+@pytest.mark.parametrize("case", sorted(ka.DECODE_CASES))
 def test_decode_plan(pkg, case, D, dtype):
-    c = dict(dec.CASES[case], D=D)
+    c = dict(ka.DECODE_CASES[case], D=D)
     lib = pkg._lib.load()
     capacity = c["page"] * c["max_pages"]
-    base = pkg._lib.kvcache_plan(dec._args(pkg, dtype=dtype, **c))
-    base_ws = lib.fasn_fwd_kvcache_workspace_bytes(dec._args(pkg, dtype=dtype, **c))
+    base = pkg._lib.kvcache_plan(ka._args_decode(pkg, dtype=dtype, **c))
+    base_ws = lib.fasn_fwd_kvcache_workspace_bytes(ka._args_decode(pkg, dtype=dtype, **c))
     tag = "%s, %d" % (TAGS[dtype], D)
     BK, R = c["B"] * c["Hkv"], c["H"] // c["Hkv"] * c["Sq"]
     # W >= capacity: the base plan under the new kernel name
     for W in (capacity, capacity + 1, 2 ** 31 - 1):
-        plan = pkg._lib.kvcache_window_plan(dec._args(pkg, dtype=dtype, **c), _win(pkg, W))
+        plan = pkg._lib.kvcache_window_plan(ka._args_decode(pkg, dtype=dtype, **c), _win(pkg, W))
         assert plan == _renamed(base, "fasn_kvcache_fwd_kernel", "fasn_kvcache_fwd_window_kernel") and plan != base
-        assert lib.fasn_fwd_kvcache_window_workspace_bytes(dec._args(pkg, dtype=dtype, **c), _win(pkg, W)) == base_ws
+        assert lib.fasn_fwd_kvcache_window_workspace_bytes(ka._args_decode(pkg, dtype=dtype, **c), _win(pkg, W)) == base_ws
     for W in (1, 128, 1000, 3000):
-        plan = pkg._lib.kvcache_window_plan(dec._args(pkg, dtype=dtype, **c), _win(pkg, W))
+        plan = pkg._lib.kvcache_window_plan(ka._args_decode(pkg, dtype=dtype, **c), _win(pkg, W))
         assert [k[0] for k in plan] == [f"fasn_kvcache_fwd_window_kernel<{tag}>", f"fasn_kvcache_combine_kernel<{tag}>"]
         nsplit = _dec_window_nsplit(c, D, W)
         assert plan[0][1] == BK * nsplit <= base[0][1] and plan[0][2:] == base[0][2:] and plan[1] == base[1]
-        ws = lib.fasn_fwd_kvcache_window_workspace_bytes(dec._args(pkg, dtype=dtype, **c), _win(pkg, W))
+        ws = lib.fasn_fwd_kvcache_window_workspace_bytes(ka._args_decode(pkg, dtype=dtype, **c), _win(pkg, W))
         assert ws == BK * nsplit * R * (D + 2) * 4 <= base_ws
         if W <= 128 and capacity >= 2048:
             assert nsplit == 1
         # other lengths, another table (other device pointers), an append: the same launches
-        other = dec._args(pkg, dtype=dtype, seqlens=DUMMY + 4096, **c)
+        other = ka._args_decode(pkg, dtype=dtype, seqlens=DUMMY + 4096, **c)
         other.block_table = DUMMY + 65536
         assert pkg._lib.kvcache_window_plan(other, _win(pkg, W)) == plan
-        appended = dec._args(pkg, dtype=dtype, **c)
+        appended = ka._args_decode(pkg, dtype=dtype, **c)
         appended.seqlen_add = c["Sq"]
         assert pkg._lib.kvcache_window_plan(appended, _win(pkg, W)) == plan
     # and the base plan did not move
     assert [k[0] for k in base] == [f"fasn_kvcache_fwd_kernel<{tag}>", f"fasn_kvcache_combine_kernel<{tag}>"]
-    assert pkg._lib.kvcache_plan(dec._args(pkg, dtype=dtype, **c)) == base
+    assert pkg._lib.kvcache_plan(ka._args_decode(pkg, dtype=dtype, **c)) == base
 
 
 @pytest.mark.parametrize("dtype", [0, 1])
 @pytest.mark.parametrize("D", DIMS)
-@pytest.mark.parametrize("case", sorted(pre.CASES))
+@pytest.mark.parametrize("case", sorted(ka.PREFILL_CASES))
 def test_prefill_plan(pkg, case, D, dtype):
-    c = dict(pre.CASES[case], D=D)
+    c = dict(ka.PREFILL_CASES[case], D=D)
     lib = pkg._lib.load()
     capacity = c["page"] * c["max_pages"]
-    base = pkg._lib.kvprefill_plan(pre._args(pkg, dtype=dtype, **c))
-    base_ws = lib.fasn_fwd_kvprefill_workspace_bytes(pre._args(pkg, dtype=dtype, **c))
+    base = pkg._lib.kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, **c))
+    base_ws = lib.fasn_fwd_kvprefill_workspace_bytes(ka._args_prefill(pkg, dtype=dtype, **c))
     tag = "%s, %d" % (TAGS[dtype], D)
     for W in (capacity, capacity + 1, 2 ** 31 - 1):
-        plan = pkg._lib.kvprefill_window_plan(pre._args(pkg, dtype=dtype, **c), _win(pkg, W))
+        plan = pkg._lib.kvprefill_window_plan(ka._args_prefill(pkg, dtype=dtype, **c), _win(pkg, W))
         assert plan == _renamed(base, "fasn_kvprefill_fwd_kernel", "fasn_kvprefill_fwd_window_kernel") and plan != base
-        assert lib.fasn_fwd_kvprefill_window_workspace_bytes(pre._args(pkg, dtype=dtype, **c), _win(pkg, W)) == base_ws
+        assert lib.fasn_fwd_kvprefill_window_workspace_bytes(ka._args_prefill(pkg, dtype=dtype, **c), _win(pkg, W)) == base_ws
     for W in (1, 128, 1000, 3000):
-        plan = pkg._lib.kvprefill_window_plan(pre._args(pkg, dtype=dtype, **c), _win(pkg, W))
+        plan = pkg._lib.kvprefill_window_plan(ka._args_prefill(pkg, dtype=dtype, **c), _win(pkg, W))
         blocks, nsplit = _pre_window_nsplit(c, D, W)
         want = [f"fasn_kvprefill_fwd_window_kernel<{tag}>"] + ([f"fasn_kvprefill_combine_kernel<{tag}>"] if nsplit > 1 else [])
         assert [k[0] for k in plan] == want                                               # one split: one launch
         assert plan[0][1] == blocks * nsplit <= base[0][1] and plan[0][2:] == base[0][2:]
-        ws = lib.fasn_fwd_kvprefill_window_workspace_bytes(pre._args(pkg, dtype=dtype, **c), _win(pkg, W))
+        ws = lib.fasn_fwd_kvprefill_window_workspace_bytes(ka._args_prefill(pkg, dtype=dtype, **c), _win(pkg, W))
         assert ws == (blocks * nsplit * 128 * (D + 2) * 4 if nsplit > 1 else 0) <= base_ws
         if W <= 128 and capacity >= 2048:
             assert nsplit == 1 and ws == 0 and len(plan) == 1
-        other = pre._args(pkg, dtype=dtype, seqlens=DUMMY + 4096, q_seqlens=DUMMY + 8192, **c)
+        other = ka._args_prefill(pkg, dtype=dtype, seqlens=DUMMY + 4096, q_seqlens=DUMMY + 8192, **c)
         other.kv.block_table = DUMMY + 65536
         assert pkg._lib.kvprefill_window_plan(other, _win(pkg, W)) == plan
-        appended = pre._args(pkg, dtype=dtype, **c)
+        appended = ka._args_prefill(pkg, dtype=dtype, **c)
         appended.kv.seqlen_add = c["Sq"]
         assert pkg._lib.kvprefill_window_plan(appended, _win(pkg, W)) == plan
     assert base[0][0] == f"fasn_kvprefill_fwd_kernel<{tag}>"
-    assert pkg._lib.kvprefill_plan(pre._args(pkg, dtype=dtype, **c)) == base
+    assert pkg._lib.kvprefill_plan(ka._args_prefill(pkg, dtype=dtype, **c)) == base
 
 
 def test_a_window_of_128_on_an_8192_key_cache_is_one_split(pkg):
     c = dict(B=64, H=64, Hkv=8, Sq=1, D=64, page=256, max_pages=32)
     assert c["page"] * c["max_pages"] == 8192
-    assert pkg._lib.kvcache_window_plan(dec._args(pkg, **c), _win(pkg, 128))[0][1] == 64 * 8
+    assert pkg._lib.kvcache_window_plan(ka._args_decode(pkg, **c), _win(pkg, 128))[0][1] == 64 * 8
     c["B"] = 1
-    assert pkg._lib.kvcache_plan(dec._args(pkg, **c))[0][1] == 8 * 32                     # the base plan: 32 splits of 4 tiles
-    assert pkg._lib.kvcache_window_plan(dec._args(pkg, **c), _win(pkg, 128))[0][1] == 8
-    assert pkg._lib.kvcache_window_plan(dec._args(pkg, **c), _win(pkg, 3000))[0][1] == 8 * 12   # 48 tiles, 4 per split
+    assert pkg._lib.kvcache_plan(ka._args_decode(pkg, **c))[0][1] == 8 * 32                     # the base plan: 32 splits of 4 tiles
+    assert pkg._lib.kvcache_window_plan(ka._args_decode(pkg, **c), _win(pkg, 128))[0][1] == 8
+    assert pkg._lib.kvcache_window_plan(ka._args_decode(pkg, **c), _win(pkg, 3000))[0][1] == 8 * 12   # 48 tiles, 4 per split
 
 
 def _plan_text(pkg):
@@ -234,14 +226,14 @@ def _plan_text(pkg):
     for W in GOLDEN_WINDOWS:
         for D in DIMS:
             for dtype in (0, 1):
-                for name in sorted(dec.CASES):
+                for name in sorted(ka.DECODE_CASES):
                     buf = ctypes.create_string_buffer(4096)
-                    rc = lib.fasn_kvcache_window_plan(dec._args(pkg, dtype=dtype, **dict(dec.CASES[name], D=D)), _win(pkg, W), buf, len(buf))
+                    rc = lib.fasn_kvcache_window_plan(ka._args_decode(pkg, dtype=dtype, **dict(ka.DECODE_CASES[name], D=D)), _win(pkg, W), buf, len(buf))
                     assert rc > 0, (name, D, dtype, W, rc)
                     got += [f"W={W} decode {name} {line}" for line in buf.value.decode().splitlines()]
-                for name in sorted(pre.CASES):
+                for name in sorted(ka.PREFILL_CASES):
                     buf = ctypes.create_string_buffer(4096)
-                    rc = lib.fasn_kvprefill_window_plan(pre._args(pkg, dtype=dtype, **dict(pre.CASES[name], D=D)), _win(pkg, W), buf, len(buf))
+                    rc = lib.fasn_kvprefill_window_plan(ka._args_prefill(pkg, dtype=dtype, **dict(ka.PREFILL_CASES[name], D=D)), _win(pkg, W), buf, len(buf))
                     assert rc > 0, (name, D, dtype, W, rc)
                     got += [f"W={W} prefill {name} {line}" for line in buf.value.decode().splitlines()]
     return got
@@ -267,8 +259,8 @@ def test_new_kernels_do_not_spill(pkg):
     wanted = set()
     for D in DIMS:
         for dtype in (0, 1):
-            wanted.add(pkg._lib.kvcache_window_plan(dec._args(pkg, dtype=dtype, **dict(dec.CASES["gqa"], D=D)), _win(pkg))[0][0])
-            wanted.add(pkg._lib.kvprefill_window_plan(pre._args(pkg, dtype=dtype, **dict(pre.CASES["gqa_prompts"], D=D)), _win(pkg))[0][0])
+            wanted.add(pkg._lib.kvcache_window_plan(ka._args_decode(pkg, dtype=dtype, **dict(ka.DECODE_CASES["gqa"], D=D)), _win(pkg))[0][0])
+            wanted.add(pkg._lib.kvprefill_window_plan(ka._args_prefill(pkg, dtype=dtype, **dict(ka.PREFILL_CASES["gqa_prompts"], D=D)), _win(pkg))[0][0])
     assert len(wanted) == 16 and all("_fwd_window_kernel<" in n for n in wanted), wanted
     for name in sorted(wanted):
         hit = [m for d, m in by_pretty.items() if d.startswith("void fasn::" + name + "(")]

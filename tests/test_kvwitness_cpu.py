@@ -24,7 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kv_witness as kw   # noqa: E402
-import test_gpu_kvcache as dec   # noqa: E402
+import kv_support as ks   # noqa: E402
 
 CPU = torch.device("cpu")
 LENS = [300, 5, 4000]
@@ -166,7 +166,7 @@ def test_b_sees_the_edges_in_every_sequence(fault, dtype):
         assert r >= 10
         if B_CLAIMS[fault] == "ascending":   # (descending: the logits reach 2e6 nats and 1e-4 of that is wider than one key's 32)
             with pytest.raises(AssertionError):
-                dec._check_lse(bad[b]["lse"], refs[b]["lse"], "mutated lse")
+                ks._check_lse(bad[b]["lse"], refs[b]["lse"], "mutated lse")
 
 
 @pytest.mark.parametrize("form", kw.B_FORMS)
@@ -183,7 +183,7 @@ def test_b_sees_an_equal_weight_merge_and_passes_unmutated(form):
             assert {1, 2} <= set(kind.unique().tolist()) or form != "sink", "the sink decides in some heads and a key in others"
             assert kw.gate_b(refs[b]["out"].to(dt), kind, want, dt) <= 0.5 + 1e-9, "the rounded reference: one rounding of two"
             assert kw.gate_b(good[b]["out"], kind, want, dt) <= 0.5   # (where the sink decides, e^-32 |v| / n is a quarter of 1e-12)
-            dec._check_lse(good[b]["lse"], refs[b]["lse"], "merged lse")
+            ks._check_lse(good[b]["lse"], refs[b]["lse"], "merged lse")
             if case.total[b] > 4 * kw.KT:   # more than one range holds a key
                 r = kw.gate_b(bad[b]["out"], kind, want, dt)
                 print(f"B {form} {name} sequence {b}: equal-weight merge {r:.3g}x the gate")
@@ -267,7 +267,7 @@ def test_reference_agrees_with_the_suites_reference():
             kd = torch.zeros(1, case.Hkv, S, case.D, dtype=dt)
             vd = torch.zeros(1, case.Hkv, S, case.D, dtype=dt)
             kd[0, :, :ln], vd[0, :, :ln] = inp["kd"][b, :, :ln], inp["vd"][b, :, :ln]
-            o, lse = dec._reference(inp["q"][b:b + 1, :, :ql], kd, vd, dec._visibility([ln], ql, S, causal, CPU), inp["n"].view(1, -1))
-            dec._check(refs[b]["out"], o[0], dt, f"fp64 reference vs _reference, sequence {b} causal={causal} out")
-            dec._check_lse(refs[b]["lse"], lse[0], f"fp64 reference vs _reference, sequence {b} causal={causal} lse")
+            o, lse = ks.reference(inp["q"][b:b + 1, :, :ql], kd, vd, ks._visibility([ln], ql, S, causal, CPU), inp["n"].view(1, -1))
+            ks._check(refs[b]["out"], o[0], dt, f"fp64 reference vs _reference, sequence {b} causal={causal} out")
+            ks._check_lse(refs[b]["lse"], lse[0], f"fp64 reference vs _reference, sequence {b} causal={causal} lse")
             assert (refs[b]["out"].float() - o[0]).abs().max() <= 1e-5

@@ -144,9 +144,9 @@ def main():
 
         if Sq > 1:   # the two append launches alone, through the C ABI
             lib = _lib.load()
-            pa = _lib.KvPrefillArgs()
             with torch.no_grad():
-                _prep = fa.kvcache._prepare("bench_kvrope", q, pool_k, pool_v, sl, table, kn, vn, n, None, True, False, args=pa.kv)
+                _prep = fa.kvcache._prepare("bench_kvrope", "kvprefill", q, pool_k, pool_v, sl, table, kn, vn, n, None, True, False)
+            pa = _prep.args
             q_out = torch.empty_like(q)
             rope = _lib.KvRope()
             rope.cos, rope.sin, rope.row_stride, rope.rows = cos.data_ptr(), sin.data_ptr(), cos.stride(0), rows

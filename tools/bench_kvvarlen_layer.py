@@ -52,8 +52,9 @@ def rope_alone(q, kn, vn, pool_k, pool_v, sl, cu, Sq, table, cos, sin):
     """a callable that makes the one launch of fasn_kvvarlen_rope_append on the current stream"""
     kc, ffa = fa.kvcache, fa.flash_attn
     fn = "bench_kvvarlen_layer"
-    _B, T, q4 = kc._packed_query(fn, q, pool_k, sl, cu, Sq)
-    va, _out, _lse, kn4, vn4, keep = kc._packed_prepare(fn, q4, T, pool_k, pool_v, sl, cu, Sq, table, kn, vn, 1.0, None, True, False)
+    _B, _T, q4 = kc._packed_query(fn, q, pool_k, sl, cu, Sq)
+    keep = kc._prepare(fn, "kvvarlen", q4, pool_k, pool_v, sl, table, kn, vn, 1.0, None, True, False, cu_seqlens_q=cu, max_seqlen_q=Sq)
+    va, kn4, vn4 = keep.args, keep.k_new, keep.v_new
     rope = kc._rope_operand(cos, sin, False, q)
     q_rot = torch.empty_like(q).unsqueeze(0).transpose(1, 2)
     lib = fa._lib.load()
