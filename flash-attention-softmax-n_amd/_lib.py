@@ -33,6 +33,9 @@ EXPORTS = (
     "fasn_fwd_kvvarlen_workspace_bytes", "fasn_fwd_kvvarlen", "fasn_kvvarlen_append", "fasn_kvvarlen_plan",
     "fasn_fwd_kvvarlen_window_workspace_bytes", "fasn_fwd_kvvarlen_window", "fasn_kvvarlen_window_plan",
     "fasn_kvvarlen_rope_append", "fasn_kvvarlen_rope_append_plan",
+    "fasn_fwd_kvcache_tree_workspace_bytes", "fasn_fwd_kvcache_tree", "fasn_kvcache_tree_plan",
+    "fasn_fwd_kvprefill_tree_workspace_bytes", "fasn_fwd_kvprefill_tree", "fasn_kvprefill_tree_plan",
+    "fasn_kvcache_tree_rope_append", "fasn_kvprefill_tree_rope_append", "fasn_kvcache_tree_commit",
 )
 
 
@@ -108,6 +111,25 @@ class KvRope(Structure):
                 ("table_dtype", c_int32), ("interleaved", c_int32)]
 
 
+class KvTree(Structure):
+    """fasn_kv_tree (include/fasn.h): the token tree of the *_tree cache calls - one int64 word per node in device memory, bit t of word
+    (b, i): node i sees node t - and the sliding window (0: none); reserved = 0"""
+    _fields_ = [("mask", c_void_p), ("batch_stride", c_int64), ("window", c_int32), ("reserved", c_int32)]
+
+
+class KvTreeCommit(Structure):
+    """fasn_kv_tree_commit (include/fasn.h): the cache and the accepted path of fasn_kvcache_tree_commit"""
+    _fields_ = [
+        ("k_cache", c_void_p), ("v_cache", c_void_p),
+        ("k_stride", c_int64 * 3), ("v_stride", c_int64 * 3),
+        ("block_table", c_void_p), ("block_table_stride", c_int64), ("max_pages", c_int32), ("page_size", c_int32),
+        ("seqlens", c_void_p),
+        ("B", c_int32), ("Hkv", c_int32), ("D", c_int32), ("A", c_int32),
+        ("accepted", c_void_p), ("accepted_stride", c_int64), ("accepted_lens", c_void_p),
+        ("nodes", c_int32), ("reserved", c_int32),
+    ]
+
+
 class FasnError(RuntimeError):
     pass
 
@@ -116,8 +138,9 @@ _lib = None
 
 
 def _kv_bindings():
-    """(name, restype, argtypes) of the 31 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
-    block (fasn_kvprefill_args), `operands` come between the block and the tail; then the nine of the packed block (fasn_kvvarlen_args)"""
+    """(name, restype, argtypes) of the 40 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
+    block (fasn_kvprefill_args), `operands` come between the block and the tail; then the nine of the packed block (fasn_kvvarlen_args)
+    and the commit of a token tree, which has a block of its own"""
     view, text = POINTER(View4), [c_char_p, c_size_t]
     launch = [c_void_p]                          # the stream
     forward = [c_void_p, c_size_t, c_void_p]     # workspace, its bytes, the stream
@@ -134,7 +157,11 @@ def _kv_bindings():
                 (f"fasn_{stem}_plan", c_int32, [], text),
                 (f"fasn_{stem}_alibi_plan", c_int32, [POINTER(AlibiSlopes)], text),
                 (f"fasn_{stem}_window_plan", c_int32, [POINTER(KvWindow)], text),
-                (f"fasn_{stem}_rope_append_plan", c_int32, rope, text)):
+                (f"fasn_{stem}_rope_append_plan", c_int32, rope, text),
+                (f"fasn_fwd_{stem}_tree_workspace_bytes", c_size_t, [POINTER(KvTree)], []),
+                (f"fasn_fwd_{stem}_tree", c_int32, [POINTER(KvTree)], forward),
+                (f"fasn_{stem}_tree_plan", c_int32, [POINTER(KvTree)], text),
+                (f"fasn_{stem}_tree_rope_append", c_int32, [POINTER(KvRope), POINTER(KvTree), view, view, view], launch)):
             yield name, restype, [block] + operands + tail
     packed = [POINTER(KvVarlenArgs)]
     yield "fasn_fwd_kvvarlen_workspace_bytes", c_size_t, packed
@@ -146,6 +173,7 @@ def _kv_bindings():
     yield "fasn_kvvarlen_window_plan", c_int32, packed + [POINTER(KvWindow)] + text
     yield "fasn_kvvarlen_rope_append", c_int32, packed + rope + launch
     yield "fasn_kvvarlen_rope_append_plan", c_int32, packed + rope + text
+    yield "fasn_kvcache_tree_commit", c_int32, [POINTER(KvTreeCommit)] + launch
 
 
 def load():
@@ -287,6 +315,12 @@ def kvprefill_window_plan(args, win):
     """The kernels fasn_fwd_kvprefill_window would launch for `args` (a KvPrefillArgs) under `win` (a KvWindow), as launch_plan returns
     them. Nothing is launched."""
     return _kv_plan("fasn_kvprefill_window_plan", args, win)
+
+
+def kvtree_plan(args, tree):
+    """The kernels fasn_fwd_kvcache_tree (`args` a KvCacheArgs) or fasn_fwd_kvprefill_tree (a KvPrefillArgs) would launch under `tree` (a
+    KvTree), as launch_plan returns them. Nothing is launched."""
+    return _kv_plan("fasn_kvprefill_tree_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_tree_plan", args, tree)
 
 
 def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):

@@ -32,6 +32,7 @@ struct KvFwd {
     KvAlibi al;
     KvWindow kw;
     KvPacked pk;          // KV_VARLEN only
+    KvTree kt;            // KV_TREE only
 };
 
 inline bool kv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -41,8 +42,11 @@ int kv_build(const KvArgs& in, KvPrefillParams& pp, KvPacked* pk = nullptr);
 int kv_pack_new(const fasn_view4& k_new, const fasn_view4& v_new, KvParams& p);   // the views' checks, then p.kn / vn / kns / vns
 int kv_build_append(const KvArgs& in, const fasn_view4* k_new, const fasn_view4* v_new, KvPrefillParams& pp, KvPacked* pk = nullptr);
 size_t kv_workspace_bytes(const KvArgs& in, KvVariant variant, const void* operand);
-// everything a forward does before its launches: base checks, the variant's operand (nothing, a fasn_alibi_slopes, a fasn_kv_window),
-// then the workspace
+// the token-tree operand's checks, behind the base arguments' (the tree forwards and the tree rotary appends share them): `kt` with the
+// window as the kernels take it - capacity + 1 when there is none
+int kv_check_tree(const fasn_kvcache_args* a, const fasn_kv_tree* t, int capacity, KvTree& kt);
+// everything a forward does before its launches: base checks, the variant's operand (nothing, a fasn_alibi_slopes, a fasn_kv_window, a
+// fasn_kv_tree), then the workspace
 int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, KvFwd& f);
 
 // dtype x head dim -> f(tag, std::integral_constant<int, D>) (kv_build let only these four head dims through)
@@ -75,6 +79,13 @@ void kv_launch_variant(const KvFwd& f, const P& p, unsigned grid, int smem, hipS
         ensure_smem<Base>(smem);
         FASN_LAUNCH(Base, dim3(grid), dim3(256), smem, s, p);
     }
+}
+
+// ... and its token-tree sibling (KV_TREE), on the same grid and LDS: no packed call has one, so it stays out of the list above
+template <auto Tree, typename P>
+void kv_launch_tree(const KvFwd& f, const P& p, unsigned grid, int smem, hipStream_t s) {
+    ensure_smem<Tree>(smem);
+    FASN_LAUNCH(Tree, dim3(grid), dim3(256), smem, s, p, f.kt);
 }
 
 // A call's launches as text: the call itself under the launch recorder (nothing is launched, no device is touched). The forwards are

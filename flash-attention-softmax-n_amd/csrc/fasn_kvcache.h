@@ -5,7 +5,9 @@
 //   fasn_kvcache_fwd_kernel      split-K walk over the pages of one (batch element, K/V head): un-normalised partials
 //   fasn_kvcache_fwd_alibi_kernel  the same walk with the ALiBi term -slope_h |j - p_i| in the scores (fasn_kvcache_fwd.inc holds both)
 //   fasn_kvcache_fwd_window_kernel  the same walk over the tiles of a sliding window only: key j is visible iff p_i - W < j <= p_i
+//   fasn_kvcache_fwd_tree_kernel  the same walk where the Sq new positions are the nodes of a token tree: a 64-bit word per node (KvTree)
 //   fasn_kvcache_combine_kernel  merges the partials and scatters the rows back to o[b, h, pos, :] / lse[b, h, pos]
+//   fasn_kvcache_tree_commit_kernel  moves the cache rows of an accepted path of a token tree behind the prefix (KvCommit)
 //
 // Rows. The G = H / Hkv query heads that share a K/V head times the Sq query positions are the rows of ONE problem:
 //   row r = g * Sq + pos   (g = query head of the group, pos = query position),   query head h = hkv * G + g,   R = G * Sq <= 128
@@ -118,14 +120,27 @@ FASN_DEV float kv_alibi_term(float nslope2, float dk0, int kb, int r) {
 struct KvWindow {
     int w;
 };
-// which forward kernel a call launches; its operand is nothing, a fasn_alibi_slopes or a fasn_kv_window
-enum KvVariant { KV_BASE, KV_ALIBI, KV_WINDOW };
+// Token tree (fasn_fwd_kvcache_tree / fasn_fwd_kvprefill_tree): the qlen_b new positions of a batch element are the NODES of a tree of
+// draft tokens (speculative decoding), node i in cache row base_b + i, base_b = len_b - qlen_b. Bit t of mask[b * sb + i] says that node i
+// sees node t (bits at or beyond qlen_b are ignored, bit 63 is an ordinary bit); every node sees the prefix j < base_b. The position of a
+// node is base_b + depth_i, depth_i = max(popcount(word & valid bits) - 1, 0): a well-formed row holds the node and its ancestors. Under
+// a window a prefix key needs j > p_i - w; w is a RUN-TIME integer here, capacity + 1 (beyond every position) when there is no window:
+// one tree kernel per call, not one per window. The word is read per lane inside the masked branch; nothing about memory depends on it.
+struct KvTree {
+    const long long* mask;   // [B][sb] words, device
+    int64_t sb;              // batch stride, elements
+    int w;                   // 1 .. capacity: the window; capacity + 1: none
+};
+// which forward kernel a call launches; its operand is nothing, a fasn_alibi_slopes, a fasn_kv_window or a fasn_kv_tree
+enum KvVariant { KV_BASE, KV_ALIBI, KV_WINDOW, KV_TREE };
 
 // fasn_kvcache_fwd_kernel<Tag, D>(KvParams), fasn_kvcache_fwd_alibi_kernel<Tag, D>(KvParams, KvAlibi) and
 // fasn_kvcache_fwd_window_kernel<Tag, D>(KvParams, KvWindow): one text, compiled three times.
 // (A bool-templated device function behind two __global__ wrappers was tried first: the compiler then schedules and allocates the
 // kernel WITHOUT the bias differently - four more VGPRs at D = 64 - and the existing instantiations are to stay byte for byte what
 // they were; tools/kernel_digest.py shows they do.)
+// fasn_kvcache_fwd_tree_kernel<Tag, D>(KvParams, KvTree) is the fourth compilation (FASN_KV_TREE = 1, the other two at 0).
+#define FASN_KV_TREE 0
 #define FASN_KV_WINDOW 0
 #define FASN_KV_ALIBI 0
 #include "fasn_kvcache_fwd.inc"
@@ -137,6 +152,12 @@ enum KvVariant { KV_BASE, KV_ALIBI, KV_WINDOW };
 #define FASN_KV_ALIBI 0
 #define FASN_KV_WINDOW 1
 #include "fasn_kvcache_fwd.inc"
+#undef FASN_KV_WINDOW
+#undef FASN_KV_TREE
+#define FASN_KV_WINDOW 0
+#define FASN_KV_TREE 1
+#include "fasn_kvcache_fwd.inc"
+#undef FASN_KV_TREE
 #undef FASN_KV_WINDOW
 #undef FASN_KV_ALIBI
 
@@ -194,6 +215,63 @@ __global__ void __launch_bounds__(256) fasn_kvcache_append_kernel(const KvParams
     const u32x4 vx = gload16(p.vn + (b * p.vns[0] + hkv * p.vns[1] + (int64_t)i * p.vns[2]) * 2 + ch * 16);
     gstore16(p.k + (page * p.kps + (int64_t)rip * p.krs + (int64_t)hkv * p.khs) * 2 + ch * 16, kx);
     gstore16(p.v + (page * p.vps + (int64_t)rip * p.vrs + (int64_t)hkv * p.vhs) * 2 + ch * 16, vx);
+}
+
+// Commit of an accepted path of a token tree (fasn_kvcache_tree_commit): for k < alen_b = clamp(accepted_lens[b], 0, A) the K and V rows
+// base_b + accepted[b, k] move to the rows base_b + k, base_b = seqlens[b], through the block table.
+//
+// Hazards. A path is strictly increasing, so accepted[b, k] >= k: row base_b + k can be the SOURCE of an earlier move (k' < k with
+// accepted[b, k'] = k) and the DESTINATION of move k. One thread owns one 16-byte column chunk of one (b, hkv) in K and in V and walks
+// k = 0, 1, .. upward: move k reads row accepted[k] >= k and writes row k, every later move k' > k of the thread reads a row
+// accepted[k'] >= k' > k - a row no earlier move of the thread has written - and no other thread touches the thread's bytes. Program
+// order inside one thread is all the ordering there is to keep: no LDS, no barrier, no second buffer. The rule is enforced, not assumed:
+// a move whose index lies outside [k, nodes) is skipped, so is one whose source or destination row is negative or at / beyond the
+// capacity. A malformed path therefore gives unspecified rows inside [base_b, base_b + alen_b) and never touches memory outside the
+// cache; accepted[b, k] == k moves nothing. `seqlens` is not modified.
+struct KvCommit {
+    char* k;
+    char* v;
+    int64_t kps, krs, khs;            // element strides (page, row, head), as KvParams
+    int64_t vps, vrs, vhs;
+    const int* bt;       // block table [B][bts] or nullptr (dense: page = batch element)
+    int64_t bts;
+    const int* seqlens;  // [B], device: base_b
+    int page_size;
+    int capacity;
+    int B, Hkv;
+    const int* acc;      // [B][accs] node indices, device
+    int64_t accs;
+    const int* alens;    // [B], device
+    int A;               // <= 64
+    int nodes;           // node indices lie in [0, nodes)
+};
+template <int D>
+__global__ void __launch_bounds__(256) fasn_kvcache_tree_commit_kernel(const KvCommit c) {
+    constexpr int CPR = D / 8;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (int64_t)c.B * c.Hkv * CPR) return;
+    const int ch = (int)(gid % CPR);
+    const int64_t rest = gid / CPR;
+    const int hkv = (int)(rest % c.Hkv), b = (int)(rest / c.Hkv);
+    const int64_t base = c.seqlens[b];
+    const int alen = min(max(c.alens[b], 0), c.A);
+    const int* const acc = c.acc + (int64_t)b * c.accs;
+    const int* const bt = c.bt != nullptr ? c.bt + (int64_t)b * c.bts : nullptr;
+    char* const kh = c.k + (int64_t)hkv * c.khs * 2 + ch * 16;
+    char* const vh = c.v + (int64_t)hkv * c.vhs * 2 + ch * 16;
+    for (int k = 0; k < alen; ++k) {
+        const int node = acc[k];
+        if (node <= k || node >= c.nodes) continue;   // (node == k: the row is where it belongs)
+        const int64_t src = base + node, dst = base + k;
+        if (dst < 0 || src >= c.capacity) continue;
+        const int sslot = (int)(src / c.page_size), srip = (int)(src % c.page_size);
+        const int dslot = (int)(dst / c.page_size), drip = (int)(dst % c.page_size);
+        const int64_t spage = bt != nullptr ? bt[sslot] : b, dpage = bt != nullptr ? bt[dslot] : b;
+        const u32x4 kx = gload16(kh + (spage * c.kps + (int64_t)srip * c.krs) * 2);
+        const u32x4 vx = gload16(vh + (spage * c.vps + (int64_t)srip * c.vrs) * 2);
+        gstore16(kh + (dpage * c.kps + (int64_t)drip * c.krs) * 2, kx);
+        gstore16(vh + (dpage * c.vps + (int64_t)drip * c.vrs) * 2, vx);
+    }
 }
 
 }  // namespace fasn

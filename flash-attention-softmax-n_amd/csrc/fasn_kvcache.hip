@@ -1,4 +1,5 @@
-// K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi|_window], fasn_kvcache_append, fasn_kvcache[_alibi|_window]_plan), in two parts:
+// K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi|_window|_tree], fasn_kvcache_append, fasn_kvcache[_alibi|_window|_tree]_plan,
+// fasn_kvcache_tree_commit), in two parts:
 //   1. the host layer of the whole K/V-cache family (fasn_kv_host.h declares it; fasn_kvprefill.hip, fasn_kvvarlen.hip and fasn_kvrope.hip call it): argument
 //      checks, parameter packing, the launch plan - which depends on shapes and capacity only, never on the lengths in device memory -
 //      the operand checks of the ALiBi and window variants and the workspace rule;
@@ -135,7 +136,32 @@ int kv_build_append(const KvArgs& in, const fasn_view4* k_new, const fasn_view4*
     return kv_pack_new(*k_new, *v_new, pp.kv);
 }
 
+// The tree operand of the *_tree entry points (checked after the base arguments, before any HIP call). The kernels take the window as a
+// run-time integer: capacity + 1 - beyond every position - stands for "none" and for every window at or beyond the capacity.
+int kv_check_tree(const fasn_kvcache_args* a, const fasn_kv_tree* t, int capacity, KvTree& kt) {
+    if (t == nullptr || t->mask == nullptr || t->reserved != 0) return FASN_EINVAL;
+    if (a->Sq > 64) return FASN_EUNSUPPORTED;   // one 64-bit word per node
+    if (!a->causal) return FASN_EUNSUPPORTED;
+    if (t->window < 0 || t->batch_stride < 0) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(t->mask) % 8) return FASN_EALIGN;
+    kt = KvTree{reinterpret_cast<const long long*>(t->mask), t->batch_stride, t->window >= 1 && t->window <= capacity ? t->window : capacity + 1};
+    return FASN_OK;
+}
+
 namespace {
+
+// The plan under a tree: the base call's rule; with a window the window call's rule over the tiles the windows of the Sq nodes can touch
+// (every row block walks them all: span Sq, whatever PB is), never more splits than the base plan has.
+int kv_build_tree(const fasn_kvcache_args* a, const fasn_kv_tree* t, int64_t blocks, KvPrefillParams& pp, KvTree& kt) {
+    KvParams& p = pp.kv;
+    const int rc = kv_check_tree(a, t, p.capacity, kt);
+    if (rc) return rc;
+    if (t->window >= 1) {
+        const int64_t cap_tiles = ((int64_t)p.capacity + KV_KT - 1) / KV_KT;
+        p.nsplit = (int)kv_nsplit(a->D, blocks, kv_window_tiles(cap_tiles, t->window, a->Sq), kv_min_tps(p.R));
+    }
+    return FASN_OK;
+}
 
 // The ALiBi operand of the *_alibi entry points (checked after the base arguments, before any HIP call): the rules of `n`
 int kv_build_alibi(const fasn_kvcache_args* a, const fasn_alibi_slopes* s, KvAlibi& al) {
@@ -166,6 +192,11 @@ int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, K
     f.variant = variant;
     f.al = KvAlibi{};
     f.kw = KvWindow{};
+    f.kt = KvTree{};
+    if (variant == KV_TREE) {   // (decode and prefill only: there is no packed tree call)
+        if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
+        return kv_build_tree(in.a, static_cast<const fasn_kv_tree*>(operand), (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kt);
+    }
     if (variant == KV_ALIBI) return kv_build_alibi(in.a, static_cast<const fasn_alibi_slopes*>(operand), f.al);
     if (variant == KV_WINDOW) {
         const int64_t blocks = in.call == KV_VARLEN ? (int64_t)f.pk.items_max * f.pp.kv.Hkv : (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb;
@@ -215,8 +246,11 @@ namespace {
 template <typename Tag, int D>
 int kv_launch_fwd(const KvFwd& f, hipStream_t s) {
     const KvParams& p = f.pp.kv;
-    kv_launch_variant<&fasn_kvcache_fwd_kernel<Tag, D>, &fasn_kvcache_fwd_alibi_kernel<Tag, D>, &fasn_kvcache_fwd_window_kernel<Tag, D>>(
-        f, p, (unsigned)(p.B * p.Hkv * p.nsplit), kv_smem(D), s);
+    if (f.variant == KV_TREE)
+        kv_launch_tree<&fasn_kvcache_fwd_tree_kernel<Tag, D>>(f, p, (unsigned)(p.B * p.Hkv * p.nsplit), kv_smem(D), s);
+    else
+        kv_launch_variant<&fasn_kvcache_fwd_kernel<Tag, D>, &fasn_kvcache_fwd_alibi_kernel<Tag, D>, &fasn_kvcache_fwd_window_kernel<Tag, D>>(
+            f, p, (unsigned)(p.B * p.Hkv * p.nsplit), kv_smem(D), s);
     const int64_t nthr = (int64_t)p.B * p.Hkv * p.R * (D / 4);
     FASN_LAUNCH((fasn_kvcache_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
@@ -242,6 +276,52 @@ int kv_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn
 }
 int kv_forward_plan(const fasn_kvcache_args* args, KvVariant variant, const void* operand, char* buf, size_t cap) {
     return kv_plan(buf, cap, [&] { return kv_forward(args, variant, operand, kv_plan_workspace(), ~size_t(0), nullptr); });
+}
+
+// fasn_kvcache_tree_commit: the cache's rules as kv_build states them for the members this block has, then its own operands
+template <int D>
+int kv_launch_commit(const KvCommit& c, hipStream_t s) {
+    const int64_t nthr = (int64_t)c.B * c.Hkv * (D / 8);
+    if ((nthr + 255) / 256 > INT_MAX) return FASN_EINVAL;
+    FASN_LAUNCH((fasn_kvcache_tree_commit_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, c);
+    return launch_rc();
+}
+int kv_commit(const fasn_kv_tree_commit* a, fasn_stream_t stream) {
+    if (a == nullptr) return FASN_EINVAL;
+    if (a->B <= 0 || a->Hkv <= 0 || a->D <= 0 || a->page_size <= 0) return FASN_EINVAL;
+    if (!kv_head_dim_ok(a->D)) return FASN_EHEADDIM;
+    if (a->seqlens == nullptr || a->k_cache == nullptr || a->v_cache == nullptr) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(a->seqlens) % 4 || reinterpret_cast<uintptr_t>(a->block_table) % 4) return FASN_EALIGN;
+    if (!kv_aligned16(a->k_cache) || !kv_aligned16(a->v_cache)) return FASN_EALIGN;
+    for (int i = 0; i < 3; ++i)
+        if (a->k_stride[i] % 8 != 0 || a->v_stride[i] % 8 != 0 || a->k_stride[i] < 0 || a->v_stride[i] < 0) return FASN_EALIGN;
+    const bool paged = a->block_table != nullptr;
+    if (paged && (a->max_pages <= 0 || a->block_table_stride < a->max_pages)) return FASN_EINVAL;
+    if (paged && a->page_size % KV_KT != 0) return FASN_EUNSUPPORTED;
+    const int64_t capacity = paged ? (int64_t)a->max_pages * a->page_size : (int64_t)a->page_size;
+    if (capacity > INT_MAX - 2 * KV_KT) return FASN_EINVAL;
+    if (a->k_stride[1] < a->D || a->v_stride[1] < a->D) return FASN_EINVAL;
+    if (a->accepted == nullptr || a->accepted_lens == nullptr || a->reserved != 0) return FASN_EINVAL;
+    if (a->A > 64 || a->nodes > 64) return FASN_EUNSUPPORTED;
+    if (a->A < 1 || a->nodes < 1 || a->accepted_stride < a->A) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(a->accepted) % 4 || reinterpret_cast<uintptr_t>(a->accepted_lens) % 4) return FASN_EALIGN;
+    KvCommit c{};
+    c.k = static_cast<char*>(a->k_cache);
+    c.v = static_cast<char*>(a->v_cache);
+    c.kps = a->k_stride[0], c.krs = a->k_stride[1], c.khs = a->k_stride[2];
+    c.vps = a->v_stride[0], c.vrs = a->v_stride[1], c.vhs = a->v_stride[2];
+    c.bt = a->block_table;
+    c.bts = a->block_table_stride;
+    c.seqlens = a->seqlens;
+    c.page_size = a->page_size;
+    c.capacity = (int)capacity;
+    c.B = a->B, c.Hkv = a->Hkv;
+    c.acc = a->accepted;
+    c.accs = a->accepted_stride;
+    c.alens = a->accepted_lens;
+    c.A = a->A;
+    c.nodes = a->nodes;
+    return kv_dispatch_d(a->D, [&](auto d) { return kv_launch_commit<decltype(d)::value>(c, (hipStream_t)stream); });
 }
 
 }  // namespace
@@ -282,5 +362,19 @@ int fasn_kvcache_alibi_plan(const fasn_kvcache_args* args, const fasn_alibi_slop
 int fasn_kvcache_window_plan(const fasn_kvcache_args* args, const fasn_kv_window* window, char* buf, size_t cap) {
     return kv_forward_plan(args, KV_WINDOW, window, buf, cap);
 }
+
+size_t fasn_fwd_kvcache_tree_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_tree* tree) {
+    return kv_workspace_bytes(kv_args(args), KV_TREE, tree);
+}
+
+int fasn_fwd_kvcache_tree(const fasn_kvcache_args* args, const fasn_kv_tree* tree, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return kv_forward(args, KV_TREE, tree, workspace, workspace_bytes, stream);
+}
+
+int fasn_kvcache_tree_plan(const fasn_kvcache_args* args, const fasn_kv_tree* tree, char* buf, size_t cap) {
+    return kv_forward_plan(args, KV_TREE, tree, buf, cap);
+}
+
+int fasn_kvcache_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t stream) { return kv_commit(commit, stream); }
 
 }  // extern "C"

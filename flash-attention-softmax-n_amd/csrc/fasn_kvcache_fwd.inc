@@ -1,8 +1,12 @@
 // fasn_kvcache_fwd.inc - the text of the decode forward kernel, included by fasn_kvcache.h once per variant (no include guard):
 // FASN_KV_ALIBI / FASN_KV_WINDOW = 0 / 0, 1 / 0, 0 / 1. With both at 0 the preprocessor leaves fasn_kvcache_fwd_kernel exactly as it was
 // before the variants existed, and with FASN_KV_WINDOW == 0 the ALiBi kernel as it was before the window kernel did.
+// FASN_KV_TREE = 1 (with the other two at 0; undefined counts as 0) is the token-tree sibling: the new positions see the prefix and the
+// nodes their word of `tree.mask` names, the window is a run-time integer. With FASN_KV_TREE == 0 the three kernels above are what they were.
 template <typename Tag, int D>
-#if FASN_KV_ALIBI
+#if FASN_KV_TREE
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_tree_kernel(const KvParams p, const KvTree tree) {
+#elif FASN_KV_ALIBI
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_alibi_kernel(const KvParams p, const KvAlibi al) {
 #elif FASN_KV_WINDOW
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_window_kernel(const KvParams p, const KvWindow win) {
@@ -38,7 +42,14 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     // ---- this split's tile range, from the length in device memory
     const int len = kv_len(p, b);
     const int tiles_b = (len + KV_KT - 1) / KV_KT;
-#if FASN_KV_WINDOW
+#if FASN_KV_TREE
+    // node i sits in cache row base + i; the walk starts at the tile of the first key a node at depth 0 can see under the window (no
+    // window: tree.w is beyond the capacity and tlo is 0, the base kernel's split of [0, tiles_b))
+    const int base = len - p.Sq;
+    const int tlo = min(max(0, base - tree.w + 1) / KV_KT, tiles_b);
+    const int tps = (tiles_b - tlo + p.nsplit - 1) / p.nsplit;
+    const int t0 = min(tlo + split * tps, tiles_b);
+#elif FASN_KV_WINDOW
     // the walk starts at the tile of the first key that the FIRST row's window holds; the splits share [tlo, tiles_b). Tiles below tlo
     // get no request and no table read: their pages may be gone
     const int tlo = min(max(0, len - p.Sq - win.w + 1) / KV_KT, tiles_b);
@@ -130,8 +141,10 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     for (int d = 0; d < DB; ++d)
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
+#if !FASN_KV_TREE
     const int vis = !row_ok ? -1 : (p.causal ? pos + len - p.Sq : len - 1);   // last visible key of the row
     const int all_vis = p.causal ? len - p.Sq : len - 1;                          // every row sees the keys up to here
+#endif
 
 #pragma unroll
     for (int s = 0; s < KS; ++s) retire_loads(qf[s]);
@@ -177,7 +190,11 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
             // the bias is part of the score before the maximum is taken; k0 is the absolute key index in every split
             const float dk0 = (float)(k0 + 4 * hi - qpos);
 #endif
-#if FASN_KV_WINDOW
+#if FASN_KV_TREE
+            // the tile lies wholly in the prefix and wholly inside the window of the deepest position a node can have, base + Sq - 1:
+            // conservative for every depth, every row sees the whole tile
+            if (k0 + KV_KT - 1 < base && k0 > len - 1 - tree.w) {
+#elif FASN_KV_WINDOW
             // ... and not below the window of the LAST row, len - W, either: then every row's window holds the whole tile
             if (k0 + KV_KT - 1 <= all_vis && k0 >= len - win.w) {
 #else
@@ -195,7 +212,23 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
                         mx = fmaxf(mx, sacc[kb][r]);
                     }
             } else {
-#if FASN_KV_WINDOW
+#if FASN_KV_TREE
+                // The row's word and depth are fetched HERE, not in front of the tile loop: at most two tiles per workgroup take this
+                // branch (those that touch [base, len) or the window's lower edge) and three more registers across the loop are what the
+                // D = 128 kernel does not have. Bits at or beyond Sq are dropped, so a key at or beyond len is hidden by construction;
+                // a lane without a row sees nothing of the tree. p_row = base + depth is the position the window is taken at.
+                unsigned long long word = 0ull;
+                if (row_ok) word = (unsigned long long)tree.mask[b * tree.sb + pos] & (~0ull >> (64 - p.Sq));
+                const int p_row = base + max(__builtin_popcountll(word) - 1, 0);
+                // The lane's 64 visibility bits of this tile, bit c = key k0 + c, built once: the word moved into the tile's frame (node t is
+                // key base + t; what falls off either end belongs to another tile) and the tile's prefix keys c < base - k0 that the
+                // window of p_row holds, c >= p_row - w + 1 - k0. A score then costs one bit test on a literal position.
+                const int off = base - k0;
+                unsigned long long vm = off >= 0 ? (off < 64 ? word << off : 0ull) : (off > -64 ? word >> -off : 0ull);
+                const int phi = min(off, 64), plo = max(p_row - tree.w + 1 - k0, 0);
+                if (phi > plo) vm |= (~0ull >> (64 - (phi - plo))) << plo;
+                vm >>= 4 * hi;
+#elif FASN_KV_WINDOW
                 // vis - W < key <= vis as ONE unsigned compare of the distance vis - key, which is dvis minus the register's literal (a
                 // lane without a row has vis = -1: its distances wrap beyond every W). dvis is made opaque per tile, or the compiler
                 // hoists the 32 loop-invariant parts of the distances out of the loop and keeps them in registers across it.
@@ -207,7 +240,9 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-#if FASN_KV_ALIBI
+#if FASN_KV_TREE
+                        const float y = ((vm >> (kb * 32 + (r & 3) + 8 * (r >> 2))) & 1ull) != 0ull ? sacc[kb][r] * p.c : -INFINITY;
+#elif FASN_KV_ALIBI
                         const float y = key <= vis ? __builtin_fmaf(sacc[kb][r], p.c, kv_alibi_term(nslope2, dk0, kb, r)) : -INFINITY;
 #elif FASN_KV_WINDOW
                         const float y = (unsigned)(dvis - (kb * 32 + (r & 3) + 8 * (r >> 2))) < (unsigned)win.w ? sacc[kb][r] * p.c : -INFINITY;

@@ -7,6 +7,7 @@
 //                                  o / lse itself, with several it writes un-normalised partials
 //   fasn_kvprefill_fwd_alibi_kernel  the same kernel with the ALiBi term -slope_h |j - p_i| in the scores (fasn_kvprefill_fwd.inc holds both)
 //   fasn_kvprefill_fwd_window_kernel  the same kernel over the tiles of a sliding window only (fasn_kvcache.h: KvWindow)
+//   fasn_kvprefill_fwd_tree_kernel  the same kernel on the nodes of a token tree (fasn_kvcache.h: KvTree): every row block walks to len_b
 //   fasn_kvprefill_combine_kernel  (several splits only) merges the partials and scatters the rows of the block map
 //
 // Row blocks. A workgroup owns KVP_ROWS = 128 row slots: the G query heads of one K/V head times PB = 128 / G consecutive positions,
@@ -49,7 +50,9 @@ FASN_DEV int kvp_len(const KvPrefillParams& pp, int b, int qlen) {
 // fasn_kvprefill_fwd_kernel<Tag, D>(KvPrefillParams), fasn_kvprefill_fwd_alibi_kernel<Tag, D>(KvPrefillParams, KvAlibi) and
 // fasn_kvprefill_fwd_window_kernel<Tag, D>(KvPrefillParams, KvWindow): one text, compiled three times, for the reason fasn_kvcache.h gives.
 // (FASN_KV_PACKED: the token-packed siblings of fasn_kvvarlen.h, a fourth and - under a window - a fifth compilation of the same text.)
+// (FASN_KV_TREE: fasn_kvprefill_fwd_tree_kernel<Tag, D>(KvPrefillParams, KvTree), the token-tree sibling, one more compilation.)
 #define FASN_KV_PACKED 0
+#define FASN_KV_TREE 0
 #define FASN_KV_WINDOW 0
 #define FASN_KV_ALIBI 0
 #include "fasn_kvprefill_fwd.inc"
@@ -61,6 +64,12 @@ FASN_DEV int kvp_len(const KvPrefillParams& pp, int b, int qlen) {
 #define FASN_KV_ALIBI 0
 #define FASN_KV_WINDOW 1
 #include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_WINDOW
+#undef FASN_KV_TREE
+#define FASN_KV_WINDOW 0
+#define FASN_KV_TREE 1
+#include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_TREE
 #undef FASN_KV_WINDOW
 #undef FASN_KV_ALIBI
 #undef FASN_KV_PACKED

@@ -11,8 +11,11 @@ template <typename Tag, int D>
 int kvp_launch_fwd(const KvFwd& f, hipStream_t s) {
     const KvPrefillParams& pp = f.pp;
     const KvParams& p = pp.kv;
-    kv_launch_variant<&fasn_kvprefill_fwd_kernel<Tag, D>, &fasn_kvprefill_fwd_alibi_kernel<Tag, D>, &fasn_kvprefill_fwd_window_kernel<Tag, D>>(
-        f, pp, (unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit), kv_smem(D), s);
+    if (f.variant == KV_TREE)
+        kv_launch_tree<&fasn_kvprefill_fwd_tree_kernel<Tag, D>>(f, pp, (unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit), kv_smem(D), s);
+    else
+        kv_launch_variant<&fasn_kvprefill_fwd_kernel<Tag, D>, &fasn_kvprefill_fwd_alibi_kernel<Tag, D>, &fasn_kvprefill_fwd_window_kernel<Tag, D>>(
+            f, pp, (unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit), kv_smem(D), s);
     if (p.nsplit > 1) {
         const int64_t nthr = (int64_t)p.B * p.Hkv * pp.nrb * KVP_ROWS * (D / 4);
         FASN_LAUNCH((fasn_kvprefill_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, pp);
@@ -80,6 +83,18 @@ int fasn_kvprefill_alibi_plan(const fasn_kvprefill_args* args, const fasn_alibi_
 
 int fasn_kvprefill_window_plan(const fasn_kvprefill_args* args, const fasn_kv_window* window, char* buf, size_t cap) {
     return kvp_forward_plan(args, KV_WINDOW, window, buf, cap);
+}
+
+size_t fasn_fwd_kvprefill_tree_workspace_bytes(const fasn_kvprefill_args* args, const fasn_kv_tree* tree) {
+    return kv_workspace_bytes(kv_args(args), KV_TREE, tree);
+}
+
+int fasn_fwd_kvprefill_tree(const fasn_kvprefill_args* args, const fasn_kv_tree* tree, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return kvp_forward(args, KV_TREE, tree, workspace, workspace_bytes, stream);
+}
+
+int fasn_kvprefill_tree_plan(const fasn_kvprefill_args* args, const fasn_kv_tree* tree, char* buf, size_t cap) {
+    return kvp_forward_plan(args, KV_TREE, tree, buf, cap);
 }
 
 }  // extern "C"

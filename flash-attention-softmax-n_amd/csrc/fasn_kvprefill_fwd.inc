@@ -6,8 +6,12 @@
 // the three kernels above are what they were. The switch is orthogonal to the other two: FASN_KV_PACKED = 1 with FASN_KV_WINDOW = 1
 // (fasn_kvvarlen.h) is the packed window sibling - the body's window blocks read qlen, len, pos0 and pos_hi, which the packed branch
 // defines from the item - and a packed ALiBi sibling would be one more inclusion.
+// FASN_KV_TREE = 1 (fasn_kvprefill.h, with the other three at 0; undefined counts as 0) is the token-tree sibling (fasn_kvcache.h: KvTree):
+// every row block walks to len_b, because a node may see any node. With FASN_KV_TREE == 0 the kernels above are what they were.
 template <typename Tag, int D>
-#if FASN_KV_PACKED && FASN_KV_WINDOW
+#if FASN_KV_TREE
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_tree_kernel(const KvPrefillParams pp, const KvTree tree) {
+#elif FASN_KV_PACKED && FASN_KV_WINDOW
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvvarlen_fwd_window_kernel(const KvPrefillParams pp, const KvPacked pk, const KvWindow win) {
 #elif FASN_KV_PACKED
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvvarlen_fwd_kernel(const KvPrefillParams pp, const KvPacked pk) {
@@ -103,10 +107,21 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     const bool row_ok = slot_ok && pos < qlen;    // a real position
 
     // ---- the block's key range, from the lengths in device memory, and this split's share of it
+#if FASN_KV_TREE
+    // node i sits in cache row base + i and may see any node: the block's keys end at len_b, whatever its positions are. The walk starts
+    // at the tile of the first key a node at depth 0 can see under the window (no window: tree.w is beyond the capacity and tlo is 0)
+    const int base = len - qlen;
+    const int tiles_b = (len + KV_KT - 1) / KV_KT;
+    const int tlo = min(max(0, base - tree.w + 1) / KV_KT, tiles_b);
+    const int tps = (tiles_b - tlo + p.nsplit - 1) / p.nsplit;
+    const int t0 = min(tlo + split * tps, tiles_b);
+#else
     const int pos_hi = min(pos0 + pp.PB, qlen) - 1;
     const int kend = p.causal ? max(0, min(len, pos_hi + len - qlen + 1)) : len;
     const int tiles_b = (kend + KV_KT - 1) / KV_KT;
-#if FASN_KV_WINDOW
+#endif
+#if FASN_KV_TREE
+#elif FASN_KV_WINDOW
     // the walk starts at the tile of the first key that the window of the block's FIRST position holds; the splits share
     // [tlo, tiles_b). Tiles below tlo get no request and no table read: their pages may be gone
     const int tlo = min(max(0, pos0 + len - qlen - win.w + 1) / KV_KT, tiles_b);
@@ -194,8 +209,10 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     for (int d = 0; d < DB; ++d)
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
+#if !FASN_KV_TREE
     const int vis = !row_ok ? -1 : (p.causal ? pos + len - qlen : len - 1);   // last visible key of the row
     const int all_vis = p.causal ? pos0 + len - qlen : len - 1;                // every real row of the block sees the keys up to here
+#endif
 
 #pragma unroll
     for (int s = 0; s < KS; ++s) retire_loads(qf[s]);
@@ -263,7 +280,11 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 #endif
             // raw scores (times ce: log2 domain); hidden keys (beyond the row's limit, which is below len_b) go to -inf
             float mx = -INFINITY;
-#if FASN_KV_WINDOW
+#if FASN_KV_TREE
+            // the tile lies wholly in the prefix and wholly inside the window of the deepest position a node can have, len - 1
+            // (fasn_kvcache_fwd.inc): every row sees the whole tile
+            if (k0 + KV_KT - 1 < base && k0 > len - 1 - tree.w) {
+#elif FASN_KV_WINDOW
             // ... and not below the window of the block's LAST real position either: then every row's window holds the whole tile
             if (k0 + KV_KT - 1 <= all_vis && k0 > pos_hi + len - qlen - win.w) {
 #else
@@ -274,7 +295,21 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 #pragma unroll
                     for (int r = 0; r < 16; ++r) mx = fmaxf(mx, sacc[kb][r]);
             } else {
-#if FASN_KV_WINDOW
+#if FASN_KV_TREE
+                // the row's word and depth, fetched inside the branch that at most two tiles of a workgroup take (fasn_kvcache_fwd.inc);
+                // bits at or beyond qlen_b are dropped, a padding slot sees nothing of the tree
+                unsigned long long word = 0ull;
+                if (row_ok) word = (unsigned long long)tree.mask[b * tree.sb + pos] & (~0ull >> (64 - qlen));
+                const int p_row = base + max(__builtin_popcountll(word) - 1, 0);
+                // The lane's 64 visibility bits of this tile, bit c = key k0 + c, built once: the word moved into the tile's frame (node t is
+                // key base + t; what falls off either end belongs to another tile) and the tile's prefix keys c < base - k0 that the
+                // window of p_row holds, c >= p_row - w + 1 - k0. A score then costs one bit test on a literal position.
+                const int off = base - k0;
+                unsigned long long vm = off >= 0 ? (off < 64 ? word << off : 0ull) : (off > -64 ? word >> -off : 0ull);
+                const int phi = min(off, 64), plo = max(p_row - tree.w + 1 - k0, 0);
+                if (phi > plo) vm |= (~0ull >> (64 - (phi - plo))) << plo;
+                vm >>= 4 * hi;
+#elif FASN_KV_WINDOW
                 // vis - W < key <= vis as one unsigned compare of the distance dvis - literal, dvis opaque per tile (fasn_kvcache_fwd.inc)
                 int dvis = vis - k0 - 4 * hi;
                 asm volatile("" : "+v"(dvis));
@@ -284,7 +319,9 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-#if FASN_KV_WINDOW
+#if FASN_KV_TREE
+                        const float y = ((vm >> (kb * 32 + (r & 3) + 8 * (r >> 2))) & 1ull) != 0ull ? sacc[kb][r] : -INFINITY;
+#elif FASN_KV_WINDOW
                         const float y = (unsigned)(dvis - (kb * 32 + (r & 3) + 8 * (r >> 2))) < (unsigned)win.w ? sacc[kb][r] : -INFINITY;
 #else
                         const float y = key <= vis ? sacc[kb][r] : -INFINITY;

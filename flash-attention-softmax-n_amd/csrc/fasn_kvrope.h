@@ -124,6 +124,58 @@ __global__ void __launch_bounds__(256) fasn_kvrope_kernel(const KvRopeParams rp)
 #include "fasn_kvrope_unit.inc"
 }
 
+// fasn_kvrope_kernel at DEPTH positions (fasn_kvcache.h: KvTree): the new rows are the nodes of a token tree. Node i of k_new / v_new is
+// still WRITTEN to cache row seqlens[b] + i, but rotated at seqlens[b] + d_i, and the query at p_i = len_b - qlen_b + d_i, with
+// d_i = max(popcount(mask[b, i] & the low qlen_b bits) - 1, 0). Everything else - the v_new copy, the dropped rows at or beyond the
+// capacity, the untouched padding rows, the table-row clamp, layouts, table types, arithmetic - is the kernel's above: same lanes, same
+// grid, the same unit text. The window member of the operand takes no part here.
+template <typename Tag, int D>
+__global__ void __launch_bounds__(256) fasn_kvrope_tree_kernel(const KvRopeParams rp, const KvTree tree) {
+    const KvParams& p = rp.kv;
+    constexpr int UPR = D / 16;   // units per row
+    int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= rp.nkv + rp.nq) return;
+    const bool isq = gid >= rp.nkv;
+    if (isq) gid -= rp.nkv;
+    const int u = (int)(gid % UPR);
+    int64_t rest = gid / UPR;
+    const int i = (int)(rest % p.Sq);
+    rest /= p.Sq;
+    const int heads = isq ? p.H : p.Hkv;
+    const int h = (int)(rest % heads), b = (int)(rest / heads);
+    int qlen = p.Sq;
+    if (rp.qlens != nullptr) qlen = min(max(rp.qlens[b], 0), p.Sq);
+    if (i >= qlen) return;   // padding rows: neither read nor written (qlen >= 1 from here on)
+    const unsigned long long word = (unsigned long long)tree.mask[b * tree.sb + i] & (~0ull >> (64 - qlen));
+    const int depth = max(__builtin_popcountll(word) - 1, 0);
+    int64_t pos;
+    const char* src;
+    char* dst;
+    if (!isq) {
+        const int64_t at = (int64_t)p.seqlens[b] + i;   // the row written
+        if (at < 0 || at >= p.capacity) return;         // dropped: the host does not know the lengths
+        pos = (int64_t)p.seqlens[b] + depth;            // the position rotated at
+        const int slot = (int)(at / p.page_size), rip = (int)(at % p.page_size);
+        const int64_t page = p.bt != nullptr ? p.bt[(int64_t)b * p.bts + slot] : b;
+        src = p.kn + (b * p.kns[0] + h * p.kns[1] + (int64_t)i * p.kns[2]) * 2;
+        dst = p.k + (page * p.kps + (int64_t)rip * p.krs + (int64_t)h * p.khs) * 2;
+        const char* const vsrc = p.vn + (b * p.vns[0] + h * p.vns[1] + (int64_t)i * p.vns[2]) * 2 + u * 32;
+        char* const vdst = p.v + (page * p.vps + (int64_t)rip * p.vrs + (int64_t)h * p.vhs) * 2 + u * 32;
+        const u32x4 v0 = gload16(vsrc), v1 = gload16(vsrc + 16);
+        gstore16(vdst, v0);
+        gstore16(vdst + 16, v1);
+    } else {
+        // len_b per lane, as in fasn_kvrope_kernel
+        int len;
+        if (rp.add_qlen < 0) len = min(max(p.seqlens[b] + p.seqlen_add, 0), p.capacity);
+        else len = (int)min(max((int64_t)p.seqlens[b] + (rp.add_qlen ? qlen : 0), (int64_t)0), (int64_t)p.capacity);
+        pos = (int64_t)depth + len - qlen;
+        src = p.q + (b * p.qs[0] + h * p.qs[1] + (int64_t)i * p.qs[2]) * 2;
+        dst = rp.qo + (b * rp.qos[0] + h * rp.qos[1] + (int64_t)i * rp.qos[2]) * 2;
+    }
+#include "fasn_kvrope_unit.inc"
+}
+
 // fasn_kvrope_kernel on TOKEN-PACKED rows (fasn_kvvarlen.h): one lane per (token t < T, head, unit), the K/V units first. The token's
 // sequence is found as fasn_kvvarlen_append_kernel finds it - a binary search in cu - and a token of no sequence (at or beyond cu[B])
 // or beyond its sequence's clamped length leaves before it reads a row. qlen_b is the schedule kernel's, the T - token0 clamp included:

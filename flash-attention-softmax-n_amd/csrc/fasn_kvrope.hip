@@ -1,5 +1,5 @@
 // Rotary rotate-and-append on the K/V-cache calls (include/fasn.h: fasn_kvcache_rope_append, fasn_kvprefill_rope_append,
-// fasn_kvvarlen_rope_append and their *_plan siblings): the base call's argument checks first (the family's, fasn_kv_host.h), then the operand's, which live here, and the
+// fasn_kvvarlen_rope_append and their *_plan siblings, fasn_kvcache_tree_rope_append / fasn_kvprefill_tree_rope_append): the base call's argument checks first (the family's, fasn_kv_host.h), then the operand's, which live here, and the
 // one launch of fasn_kvrope.h - whose grid depends on shapes only, never on the lengths in device memory.
 #include <limits.h>
 #include "fasn_kv_host.h"
@@ -49,12 +49,19 @@ int kvr_launch(const KvRopeParams& rp, hipStream_t s) {
     return launch_rc();
 }
 template <typename Tag, int D>
+int kvr_launch_tree(const KvRopeParams& rp, const KvTree& kt, hipStream_t s) {
+    FASN_LAUNCH((fasn_kvrope_tree_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, kt);
+    return launch_rc();
+}
+template <typename Tag, int D>
 int kvr_launch_packed(const KvRopeParams& rp, const KvPacked& pk, hipStream_t s) {
     FASN_LAUNCH((fasn_kvvarlen_rope_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, pk);
     return launch_rc();
 }
 
-int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
+// `tree`: the *_tree_rope_append calls (the rotation at depth positions); its operand is checked behind the rope operand
+int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream,
+             bool tree = false, const fasn_kv_tree* tree_operand = nullptr) {
     KvPrefillParams pp;
     KvPacked pk{};
     int rc = kv_build(in, pp, &pk);
@@ -65,6 +72,12 @@ int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out
     const bool packed = in.call == KV_VARLEN;
     const int64_t rows = packed ? (int64_t)pk.T : (int64_t)pp.kv.B * pp.kv.Sq;
     if ((rc = kvr_build(in.a, in.call != KV_DECODE, rows, rope, q_out, k_new, v_new, rp))) return rc;
+    if (tree) {
+        KvTree kt{};
+        if (packed) return FASN_EUNSUPPORTED;
+        if ((rc = kv_check_tree(in.a, tree_operand, pp.kv.capacity, kt))) return rc;
+        return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch_tree<decltype(tag), decltype(d)::value>(rp, kt, (hipStream_t)stream); });
+    }
     if (packed)
         return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch_packed<decltype(tag), decltype(d)::value>(rp, pk, (hipStream_t)stream); });
     return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch<decltype(tag), decltype(d)::value>(rp, (hipStream_t)stream); });
@@ -85,6 +98,16 @@ int fasn_kvcache_rope_append(const fasn_kvcache_args* args, const fasn_kv_rope* 
 int fasn_kvprefill_rope_append(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                                const fasn_view4* v_new, fasn_stream_t stream) {
     return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream);
+}
+
+int fasn_kvcache_tree_rope_append(const fasn_kvcache_args* args, const fasn_kv_rope* rope, const fasn_kv_tree* tree, const fasn_view4* q_out,
+                                  const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
+    return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream, true, tree);
+}
+
+int fasn_kvprefill_tree_rope_append(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_kv_tree* tree, const fasn_view4* q_out,
+                                    const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
+    return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream, true, tree);
 }
 
 int fasn_kvcache_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,

@@ -15,6 +15,9 @@ flash_attention_n_kvcache_varlen is the prefill call on TOKEN-PACKED queries (fa
 buffer and `cu_seqlens_q` on the device - a continuous-batching step of prompt chunks and decode tokens whose grid follows the tokens.
 flash_attention_n_kvcache_varlen_window and flash_attention_n_kvcache_varlen_rope are the sliding-window and the rotary call on the same
 packed buffers (fasn_fwd_kvvarlen_window / fasn_kvvarlen_rope_append): a served GPT-OSS or Mistral layer in one token-packed step.
+flash_attention_n_kvcache_tree verifies a TREE of draft tokens in one step (speculative decoding: fasn_fwd_kvcache_tree / fasn_fwd_kvprefill_tree,
+fasn_kv*_tree_rope_append): one int64 word per node on the device says which nodes it sees, its position is the prefix length plus its
+depth; flash_attention_n_kvcache_tree_commit moves the accepted path's cache rows behind the prefix (fasn_kvcache_tree_commit).
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -24,13 +27,14 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs, KvRope, KvVarlenArgs, KvWindow
+from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs, KvRope, KvTree, KvTreeCommit, KvVarlenArgs, KvWindow
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
 _KV_HEAD_DIMS = (32, 64, 128, 256)   # the head dims flash_attention_n trains at; any other size is refused (a cache is never padded)
 _INT_MAX = 2 ** 31 - 1   # what an int32 member of an argument block holds: host integers are clamped to it
 _MAX_ROWS = 128   # query heads per K/V head x query positions: the rows of one workgroup
+_MAX_NODES = 64   # nodes of a token tree: one bit of an int64 word each
 
 
 _BLOCKS = {"kvcache": KvCacheArgs, "kvprefill": KvPrefillArgs, "kvvarlen": KvVarlenArgs}   # entry-point stem -> its argument block
@@ -249,24 +253,29 @@ def _on_device(dev, launch) -> None:
             launch()
 
 
-def _append(lib, c, stream, rope=None, q_rot=None) -> None:
+def _append(lib, c, stream, rope=None, q_rot=None, tree=None) -> None:
     """k_new / v_new -> the cache rows behind the lengths; with `rope` the one launch that rotates them on the way and the queries into
-    `q_rot`, which the forward then reads"""
+    `q_rot`, which the forward then reads - under `tree` at the nodes' depth positions"""
     if rope is not None:
-        name = f"fasn_{c.stem}_rope_append"
+        name = f"fasn_{c.stem}_rope_append" if tree is None else f"fasn_{c.stem}_tree_rope_append"
         kn_view = None if c.k_new is None else _view4(c.k_new)
         vn_view = None if c.v_new is None else _view4(c.v_new)
-        _lib.check(getattr(lib, name)(c.args, rope, _view4(q_rot), kn_view, vn_view, stream), name)
+        operand = (rope,) if tree is None else (rope, tree)
+        _lib.check(getattr(lib, name)(c.args, *operand, _view4(q_rot), kn_view, vn_view, stream), name)
         c.kv.q = _view4(q_rot)
     elif c.k_new is not None:
         name = f"fasn_{c.stem}_append"
         _lib.check(getattr(lib, name)(c.args, _view4(c.k_new), _view4(c.v_new), stream), name)
 
 
-def _forward(lib, c, stream, win=None) -> None:
-    """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (c.alibi) or of their window siblings (`win`)"""
+def _forward(lib, c, stream, win=None, tree=None) -> None:
+    """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (c.alibi), of their window siblings (`win`)
+    or of their token-tree siblings (`tree`, which carries its window)"""
     stem = c.stem
-    if win is not None:
+    if tree is not None:
+        name, operand = f"fasn_fwd_{stem}_tree", (tree,)
+        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_tree_workspace_bytes")(c.args, tree)
+    elif win is not None:
         name, operand = f"fasn_fwd_{stem}_window", (win,)
         ws_bytes = getattr(lib, f"fasn_fwd_{stem}_window_workspace_bytes")(c.args, win)
     else:   # (the ALiBi kernels: the base call's workspace)
@@ -281,17 +290,23 @@ def _forward(lib, c, stream, win=None) -> None:
     _lib.check(getattr(lib, name)(c.args, *operand, None if ws is None else ws.data_ptr(), ws_bytes, stream), name)
 
 
-def _run(c, window=None, rope=None):
+def _run(c, window=None, rope=None, tree_mask=None):
     """What every call does once it is checked: the library, the rotated-query temporary, then under the query's device the stream,
-    the append and the forward; the outputs in the caller's layout."""
+    the append and the forward; the outputs in the caller's layout. `tree_mask` ([B, Sq] int64): the token-tree operand, which takes the
+    window with it."""
     lib = _lib.load()
+    tree = None
+    if tree_mask is not None:
+        tree = KvTree(mask=tree_mask.data_ptr(), batch_stride=tree_mask.stride(0) if tree_mask.shape[0] > 1 else tree_mask.shape[1],
+                      window=0 if window is None else min(window, _INT_MAX), reserved=0)
+        window = None
     win = None if window is None else KvWindow(window=min(window, _INT_MAX), reserved=0)
     q_rot = None if rope is None else _query_shaped(c)   # (torch's caching allocator: a captured graph owns it)
 
     def launch():
         stream = _stream_ptr(c.dev)
-        _append(lib, c, stream, rope, q_rot)
-        _forward(lib, c, stream, win)
+        _append(lib, c, stream, rope, q_rot, tree)
+        _forward(lib, c, stream, win, tree)
 
     _on_device(c.dev, launch)
     out = c.out.transpose(1, 2).squeeze(0) if c.packed else c.out   # packed: [T, H, D] (lse is [H, T] as allocated)
@@ -702,6 +717,173 @@ def flash_attention_n_kvcache_rope(
     c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
                  return_lse, query_seqlens=query_seqlens, by_shape=True)
     return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query))
+
+
+def _check_tree_mask(fn, tree_mask, query) -> Tensor:
+    """tree_mask as the kernels read it: int64 [B, Sq] on the query's device with unit node stride (a small per-step tensor: made contiguous
+    when it is not). The values are not looked at: any word is legal."""
+    if not isinstance(tree_mask, Tensor) or tree_mask.dtype != torch.int64:
+        got = tree_mask.dtype if isinstance(tree_mask, Tensor) else type(tree_mask).__name__
+        raise TypeError(f"{fn}: tree_mask must be an int64 tensor (one 64-bit word per node: bit t of word i says node i sees node t); got {got}")
+    if query.dim() == 4:
+        B, Sq = query.shape[0], query.shape[2]
+        if Sq > _MAX_NODES:
+            raise ValueError(f"{fn}: a tree of {Sq} nodes is not supported (at most {_MAX_NODES}: one bit of an int64 word per node); verify a "
+                             "larger tree in several calls")
+        if tuple(tree_mask.shape) != (B, Sq):
+            raise ValueError(f"{fn}: tree_mask must be [B, Sq] = [{B}, {Sq}], one word per node of query; got {tuple(tree_mask.shape)}")
+    if tree_mask.device != query.device:
+        raise RuntimeError(f"tree_mask is on {tree_mask.device}, query on {query.device}: every operand must live on the query's device "
+                           "(the words are read by the kernels, never on the host)")
+    return tree_mask if tree_mask.stride(-1) == 1 and tree_mask.stride(0) >= 0 else tree_mask.contiguous()
+
+
+def flash_attention_n_kvcache_tree(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        tree_mask: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        query_seqlens: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        return_lse: bool = False,
+        window: Optional[int] = None,
+        rotary_cos: Optional[Tensor] = None,
+        rotary_sin: Optional[Tensor] = None,
+        rotary_interleaved: bool = False):
+    """softmax_n attention of a TREE of draft tokens against a K/V cache, on MI355X: the verification step of speculative decoding
+    (EAGLE, Medusa, SpecInfer). The Sq new positions are the nodes of the tree, in any order in which a node follows its ancestors; every
+    node sees the cached prefix and the nodes its mask word names - its ancestors and itself - never its siblings.
+
+    With qlen_b = clamp(query_seqlens[b], 0, Sq) (None: Sq), len_b = clamp(cache_seqlens[b] + (qlen_b if k_new is given else 0), 0,
+    capacity) and base_b = len_b - qlen_b, node i sits in cache row base_b + i and sees key j iff
+        j < base_b                       (the prefix; under `window` also j > p_i - window), or
+        j = base_b + t, t < qlen_b, and bit t of tree_mask[b, i] is set.
+    Its position is p_i = base_b + d_i with the depth d_i = max(popcount(tree_mask[b, i] & the low qlen_b bits) - 1, 0): a well-formed row
+    holds the node itself and exactly its ancestors, so no position tensor exists. The cache, `block_table`, `cache_seqlens`, `k_new` /
+    `v_new`, `query_seqlens`, `softmax_n_param`, `scale`, dtypes, head dims, alignment rules and refusals are those of
+    flash_attention_n_kvcache_prefill; the kernels are chosen by shapes alone as in flash_attention_n_kvcache_window (query_seqlens=None and
+    (H // Hkv) * Sq <= 128: the decode kernels). What differs:
+
+    :param query: [B, H, Sq, D] with Sq <= 64.
+    :param tree_mask: int64 [B, Sq] ON THE DEVICE. Bits t >= qlen_b are ignored; bit 63 - the sign bit - is an ordinary bit. The words may
+                  hold anything: upper-triangular bits, a missing self bit and an all-zero row are legal, the result is what the rule
+                  above says and no memory access depends on the mask. The chain (bit t iff t <= i) is causal attention, bit for bit.
+    :param window: None, or a Python int >= 1: the prefix keys are those of flash_attention_n_kvcache_window at position p_i. With
+                  first_b = 64 * floor(max(0, base_b - window + 1) / 64), cache rows below first_b and the block-table entries of pages
+                  wholly below it are never read (that call's memory contract).
+    :param rotary_cos, rotary_sin, rotary_interleaved: both tables or neither, as in flash_attention_n_kvcache_rope. Node i of k_new is
+                  written to cache row cache_seqlens[b] + i but rotated at cache_seqlens[b] + d_i; the query node is rotated at p_i.
+    :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32). A node that sees nothing gives exactly 0 and lse = log n (-inf for
+             n = 0); padding positions i >= qlen_b give exactly 0 and lse = -inf and are neither read nor rotated.
+
+    After acceptance flash_attention_n_kvcache_tree_commit moves the accepted path's rows behind the prefix; `cache_seqlens` stays the
+    caller's to advance. Nothing is read on the host: the launches depend on shapes, the capacity and `window` only, so one captured graph
+    serves every step while `tree_mask`, `cache_seqlens` and the cache change in place. Always causal; no ALiBi, no packed queries, no
+    gradient."""
+    fn = "flash_attention_n_kvcache_tree"
+    if window is not None:
+        _check_window(fn, window, or_none="None or ")
+    tree_mask = _check_tree_mask(fn, tree_mask, query)
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError(f"{fn}: rotary_cos and rotary_sin come together (both tables, or neither)")
+    rotary = rotary_cos is not None
+    if rotary:
+        _check_rotary_tables(fn, rotary_cos, rotary_sin, query)
+    _check_query_seqlens(fn, query_seqlens, query)
+    _check_group_limit(fn, query, k_cache)
+    if rotary:
+        _check_rotary_fit(fn, rotary_cos, rotary_sin, query, k_cache, block_table)
+    c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, True,
+                 return_lse, query_seqlens=query_seqlens, by_shape=True)
+    return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query) if rotary else None, tree_mask=tree_mask)
+
+
+def flash_attention_n_kvcache_tree_commit(
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        accepted: Tensor,
+        accepted_lens: Tensor,
+        block_table: Optional[Tensor] = None) -> None:
+    """Compaction after acceptance, on MI355X: the K and V rows of the accepted root-to-leaf path of a verified tree move behind the prefix,
+    in place, through the block table.
+
+    :param k_cache, v_cache, block_table: the cache of the tree call.
+    :param cache_seqlens: int32 [B] ON THE DEVICE: base_b, the prefix length - the value that was passed to the tree call. Not modified:
+                  the caller advances it by the accepted length.
+    :param accepted: int32 [B, A] on the device, A <= 64: accepted[b, k] is the node (its index in the tree call's `query`) at depth k of
+                  the path. A path is strictly increasing, so accepted[b, k] >= k.
+    :param accepted_lens: int32 [B] on the device: alen_b = clamp(accepted_lens[b], 0, A) nodes of the path count.
+
+    For k < alen_b row base_b + accepted[b, k] is copied to row base_b + k. An index outside [k, 64), or a row at or beyond the capacity,
+    skips that move: a malformed path gives unspecified rows and never touches memory outside the cache; accepted[b, k] == k moves nothing.
+    Rotated keys need no re-rotation: node k of a path has depth k and lands at the position it was rotated for. Nothing is read on the
+    host: the launch depends on shapes only and replays in a captured graph."""
+    fn = "flash_attention_n_kvcache_tree_commit"
+    if k_cache.dim() != 4 or v_cache.dim() != 4:
+        raise ValueError(f"{fn}: the caches must be [num_pages, page_size, Hkv, D] (paged) or [B, capacity, Hkv, D] (dense)")
+    if k_cache.dtype not in _KV_DTYPES or v_cache.dtype != k_cache.dtype:
+        raise TypeError(f"{fn}: k_cache and v_cache must share one dtype, fp16 or bf16; got {k_cache.dtype} and {v_cache.dtype}")
+    dev = k_cache.device
+    tensors = {"v_cache": v_cache, "cache_seqlens": cache_seqlens, "accepted": accepted, "accepted_lens": accepted_lens, "block_table": block_table}
+    for name, t in tensors.items():
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}, k_cache on {dev}: every operand must live on the cache's device "
+                               "(the path and the lengths are read by the kernel, never on the host)")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"k_cache and v_cache must have one shape; got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+    page_size, Hkv, D = k_cache.shape[1], k_cache.shape[2], k_cache.shape[3]
+    if D not in _KV_HEAD_DIMS:
+        raise ValueError(f"{fn}: head dim {D} is not supported (supported: {_KV_HEAD_DIMS})")
+    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or not cache_seqlens.is_contiguous():
+        raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [B] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
+    B = cache_seqlens.shape[0]
+    if accepted.dtype != torch.int32 or accepted.dim() != 2 or accepted.shape[0] != B or accepted.shape[1] < 1:
+        raise ValueError(f"{fn}: accepted must be an int32 tensor [B, A] = [{B}, A >= 1] of node indices; got {accepted.dtype} {tuple(accepted.shape)}")
+    A = accepted.shape[1]
+    if A > _MAX_NODES:
+        raise ValueError(f"{fn}: accepted is {A} nodes wide; a path has at most {_MAX_NODES} (the nodes of a tree)")
+    if accepted_lens.dtype != torch.int32 or accepted_lens.dim() != 1 or accepted_lens.shape[0] != B or not accepted_lens.is_contiguous():
+        raise ValueError(f"{fn}: accepted_lens must be a contiguous int32 tensor of shape [{B}]; got {accepted_lens.dtype} {tuple(accepted_lens.shape)}")
+    paged = block_table is not None
+    if paged:
+        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.stride(1) != 1:
+            raise ValueError(f"block_table must be an int32 tensor [B, max_pages] with unit column stride; got {block_table.dtype} {tuple(block_table.shape)}")
+        if block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"block_table must be [{B}, max_pages >= 1]: one row of page ids per batch element; got {tuple(block_table.shape)}")
+        if page_size % 64 != 0:
+            raise ValueError(f"page_size {page_size} is not supported: a paged cache needs page_size % 64 == 0 (a 64-key tile never straddles a page)")
+    elif k_cache.shape[0] != B:
+        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, Hkv, D] with B = {B}; got {tuple(k_cache.shape)}")
+    _check_cache("k_cache", k_cache, paged, D)
+    _check_cache("v_cache", v_cache, paged, D)
+    if accepted.stride(1) != 1 or accepted.stride(0) < A:
+        accepted = accepted.contiguous()
+    if not k_cache.is_cuda:
+        raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
+                           "(there is deliberately no CPU fallback)")
+    a = KvTreeCommit()
+    a.k_cache, a.v_cache = k_cache.data_ptr(), v_cache.data_ptr()
+    for i in range(3):
+        a.k_stride[i] = k_cache.stride(i) if k_cache.size(i) > 1 else 0
+        a.v_stride[i] = v_cache.stride(i) if v_cache.size(i) > 1 else 0
+    if k_cache.size(1) == 1:
+        a.k_stride[1] = a.v_stride[1] = D
+    if paged:
+        a.block_table, a.block_table_stride, a.max_pages = block_table.data_ptr(), block_table.stride(0) if B > 1 else block_table.shape[1], block_table.shape[1]
+    else:
+        a.block_table, a.block_table_stride, a.max_pages = None, 0, 1
+    a.page_size, a.seqlens = page_size, cache_seqlens.data_ptr()
+    a.B, a.Hkv, a.D, a.A = B, Hkv, D, A
+    a.accepted, a.accepted_stride, a.accepted_lens = accepted.data_ptr(), accepted.stride(0) if B > 1 else A, accepted_lens.data_ptr()
+    a.nodes, a.reserved = _MAX_NODES, 0
+    lib = _lib.load()
+    _on_device(dev, lambda: _lib.check(lib.fasn_kvcache_tree_commit(a, _stream_ptr(dev)), "fasn_kvcache_tree_commit"))
 
 
 def _rows(t: Tensor) -> Tensor:

@@ -489,6 +489,81 @@ int fasn_kvvarlen_rope_append_plan(const fasn_kvvarlen_args* args, const fasn_kv
                                    const fasn_view4* v_new, char* buf, size_t cap);
 
 /*
+ * TOKEN-TREE ATTENTION on the cache calls (speculative-decoding verification: EAGLE, Medusa, SpecInfer; additions within ABI 6, the
+ * argument blocks above keep their layouts). The qlen_b new positions of a batch element are the NODES of a tree of draft tokens, in the
+ * order of q. With len_b / qlen_b as the base call defines them (clamps and append included) and base_b = len_b - qlen_b:
+ *   rows       node i sits in cache row base_b + i.
+ *   mask       int64 words in DEVICE memory, word (b, i) at mask[b * batch_stride + i], i < Sq <= 64. Bit t says that node i sees node t;
+ *              bits t >= qlen_b are ignored, bit 63 (the sign bit) is an ordinary bit.
+ *   sees       node i sees key j iff j < base_b (the prefix; under a window also j > p_i - window), or j = base_b + t with t < qlen_b
+ *              and bit t set.
+ *   position   p_i = base_b + d_i, d_i = max(popcount(word & the low qlen_b bits) - 1, 0): a well-formed row holds the node itself and
+ *              exactly its ancestors, so popcount - 1 is its depth and no position tensor exists.
+ *   anything   may stand in the mask - upper-triangular bits, a missing self bit, an all-zero row: the result is what the rule says and
+ *              no access depends on the mask. A row that sees nothing gives 0 and lse = log n (-inf for n = 0); positions i >= qlen_b
+ *              give 0 / -inf and are neither read nor rotated.
+ *   window     0: none; >= 1: first_b = 64 * floor(max(0, base_b - window + 1) / 64), and pages wholly below first_b are never read -
+ *              neither their rows nor their table entries (the MEMORY CONTRACT of the *_window calls).
+ * softmax_n, `n`, scale, lse, split-K, the combine kernels and the stale-memory rules are the base call's.
+ *
+ *   fasn_fwd_kvcache_tree / fasn_fwd_kvprefill_tree   the base call with the operand: one forward kernel of their own each (the window is a
+ *              run-time integer of it), the same combine kernels, the appends of the base calls. The plan is the base call's rule; with a
+ *              window it is the *_window rule with span Sq (every row block walks the window of all Sq nodes). The workspace is
+ *              fasn_fwd_kv{cache,prefill}_tree_workspace_bytes(args, tree); the *_tree_plan calls write the launches as text.
+ *   fasn_kvcache_tree_rope_append / fasn_kvprefill_tree_rope_append   the *_rope_append call at DEPTH positions: node i of k_new is
+ *              written to cache row seqlens[b] + i but rotated at seqlens[b] + d_i, the query node at p_i. Everything else is the
+ *              *_rope_append call's (tree->window takes no part).
+ *   fasn_kvcache_tree_commit   after acceptance: for k < clamp(accepted_lens[b], 0, A) the K and V rows seqlens[b] + accepted[b, k] move
+ *              to the rows seqlens[b] + k, through the block table; seqlens[b] = base_b, the prefix length that was passed to the tree
+ *              call. A path is strictly increasing (accepted[b, k] >= k); an index outside [k, nodes) or a row at / beyond the capacity
+ *              skips that move, so a malformed path gives unspecified rows and never touches memory outside the cache. accepted[b, k] == k
+ *              moves nothing. `seqlens` is not modified. Rotated keys need no re-rotation: node k of a path has depth k and lands at the
+ *              position it was rotated for.
+ * Every rule and error code of the base call holds and is checked first (the rope calls: then the rope operand's); then tree == NULL,
+ * mask == NULL or reserved != 0 is FASN_EINVAL, Sq > 64 FASN_EUNSUPPORTED, args->causal == 0 FASN_EUNSUPPORTED, window < 0 FASN_EINVAL,
+ * a mask that is not 8-byte aligned FASN_EALIGN and a negative batch_stride FASN_EINVAL. Not here: ALiBi, packed queries, gradients.
+ */
+typedef struct fasn_kv_tree {
+    const int64_t* mask;         /* DEVICE, word (b, i) at mask[b * batch_stride + i] */
+    int64_t batch_stride;        /* elements */
+    int32_t window;              /* 0: none; >= 1: the sliding window of the *_window calls */
+    int32_t reserved;            /* 0 */
+} fasn_kv_tree;
+
+typedef struct fasn_kv_tree_commit {
+    void* k_cache;               /* the cache as fasn_kvcache_args names it: pools, strides, table, lengths, page size */
+    void* v_cache;
+    int64_t k_stride[3];
+    int64_t v_stride[3];
+    const int32_t* block_table;
+    int64_t block_table_stride;
+    int32_t max_pages;
+    int32_t page_size;
+    const int32_t* seqlens;      /* DEVICE [B]: base_b, the prefix length */
+    int32_t B;
+    int32_t Hkv;                 /* K/V heads */
+    int32_t D;                   /* 32, 64, 128, 256; 16-bit elements */
+    int32_t A;                   /* columns of accepted, 1 .. 64 */
+    const int32_t* accepted;     /* DEVICE, node (b, k) at accepted[b * accepted_stride + k] */
+    int64_t accepted_stride;     /* elements, >= A */
+    const int32_t* accepted_lens;/* DEVICE [B] */
+    int32_t nodes;               /* node indices lie in [0, nodes), 1 .. 64: the Sq of the tree call */
+    int32_t reserved;            /* 0 */
+} fasn_kv_tree_commit;
+
+size_t fasn_fwd_kvcache_tree_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_tree* tree);
+int fasn_fwd_kvcache_tree(const fasn_kvcache_args* args, const fasn_kv_tree* tree, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvcache_tree_plan(const fasn_kvcache_args* args, const fasn_kv_tree* tree, char* buf, size_t cap);
+size_t fasn_fwd_kvprefill_tree_workspace_bytes(const fasn_kvprefill_args* args, const fasn_kv_tree* tree);
+int fasn_fwd_kvprefill_tree(const fasn_kvprefill_args* args, const fasn_kv_tree* tree, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvprefill_tree_plan(const fasn_kvprefill_args* args, const fasn_kv_tree* tree, char* buf, size_t cap);
+int fasn_kvcache_tree_rope_append(const fasn_kvcache_args* args, const fasn_kv_rope* rope, const fasn_kv_tree* tree, const fasn_view4* q_out,
+                                  const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvprefill_tree_rope_append(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_kv_tree* tree, const fasn_view4* q_out,
+                                    const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvcache_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t stream);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).
