@@ -17,13 +17,14 @@ FASN_BIAS_NONE, FASN_BIAS_SAME, FASN_BIAS_F32 = 0, 1, 2
 FASN_PATH_NAMES = {0: "plain", 1: "key-padding", 2: "vector mask/bias", 3: "vector bias + key-padding", 4: "element-load (slow)", 5: "fp32"}
 FASN_PATH_ELEMENT = 4
 FASN_PLAN_FWD, FASN_PLAN_BWD, FASN_PLAN_FWD_WS = 0, 1, 2
+FASN_ROW_FWD, FASN_ROW_BWD = 0, 1
 
 # every entry point include/fasn.h declares (tests check the .so exports all of them)
 EXPORTS = (
     "fasn_abi_version", "fasn_strerror", "fasn_supported", "fasn_fwd", "fasn_fwd_path", "fasn_bwd_path", "fasn_fwd_workspace_bytes", "fasn_fwd_ws",
     "fasn_bwd_workspace_bytes", "fasn_bwd", "fasn_rng_advance", "fasn_launch_plan",
     "fasn_fwd_n", "fasn_bwd_dn_workspace_bytes", "fasn_bwd_dn",
-    "fasn_softmax_n_fwd", "fasn_softmax_n_bwd", "fasn_moments",
+    "fasn_softmax_n_fwd", "fasn_softmax_n_bwd", "fasn_moments", "fasn_softmax_n_plan", "fasn_moments_plan",
     "fasn_fwd_kvcache_workspace_bytes", "fasn_fwd_kvcache", "fasn_kvcache_append", "fasn_kvcache_plan",
     "fasn_fwd_kvprefill_workspace_bytes", "fasn_fwd_kvprefill", "fasn_kvprefill_append", "fasn_kvprefill_plan",
     "fasn_fwd_kvcache_alibi", "fasn_fwd_kvprefill_alibi", "fasn_kvcache_alibi_plan", "fasn_kvprefill_alibi_plan",
@@ -224,6 +225,10 @@ def load():
     lib.fasn_softmax_n_bwd.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int32, c_void_p]
     lib.fasn_moments.restype = c_int32
     lib.fasn_moments.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_void_p]
+    lib.fasn_softmax_n_plan.restype = c_int32
+    lib.fasn_softmax_n_plan.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int32, c_char_p, c_size_t]
+    lib.fasn_moments_plan.restype = c_int32
+    lib.fasn_moments_plan.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_char_p, c_size_t]
     for name, restype, argtypes in _kv_bindings():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -329,6 +334,19 @@ def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):
     what = ("fasn_kvvarlen_rope_append_plan" if isinstance(args, KvVarlenArgs) else
             "fasn_kvprefill_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_rope_append_plan")
     return _kv_plan(what, args, rope, q_out, k_new, v_new)
+
+
+def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):
+    """The one launch of fasn_softmax_n_fwd (`which` = FASN_ROW_FWD: a, b = the addresses of x and y, c is not read) or fasn_softmax_n_bwd
+    (FASN_ROW_BWD: y, dy, dx) for these rows, columns, row strides (in elements) and FASN_DTYPE_*, as launch_plan returns it. Only the
+    alignment of the addresses is read. Nothing is launched."""
+    return _kv_plan("fasn_softmax_n_plan", which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype)
+
+
+def moments_plan(x, sums, rows, cols, row_stride, dtype):
+    """The one launch of fasn_moments for these arguments (x, sums: addresses), as launch_plan returns it; the grid is the number of
+    chunks a row is cut into. Nothing is launched."""
+    return _kv_plan("fasn_moments_plan", x, sums, rows, cols, row_stride, dtype)
 
 
 def check(rc, what):

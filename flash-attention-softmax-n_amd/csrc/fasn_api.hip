@@ -109,6 +109,7 @@ void log_launch(const char* tag_name, unsigned grid, unsigned block, int smem) {
     const char* b = dm ? strstr(dm, "&(void ") : nullptr;
     b = b ? b + 7 : (dm ? dm : tag_name);
     if (strncmp(b, "fasn::", 6) == 0) b += 6;
+    if (strncmp(b, "(anonymous namespace)::", 23) == 0) b += 23;   // (fasn_moments.hip keeps its kernel file-local)
     size_t n = 0;
     for (int depth = 0; b[n] != 0; ++n) {   // the name ends at the parameter list: the first '(' outside the template arguments
         if (b[n] == '<') ++depth;

@@ -1,6 +1,8 @@
 // fasn_softmax.hip — stand-alone softmax_n over the last dimension (fwd + bwd).
 //   y_i = exp(x_i - m) / (n * exp(-m) + sum_j exp(x_j - m)),  m = max(x) (and m >= 0 when n > 0 so that
-//   n * exp(-m) cannot overflow) — reference: flash_attention_softmax_n/core/functional.py:15-29.
+//   n * exp(-m) cannot overflow) — reference: flash_attention_softmax_n/core/functional.py:15-29. At n == 0 the denominator is the sum
+//   alone: softmax_n(x, 0) is softmax(x) for every finite row, the ones below -88 too, where exp(-m) is inf in fp32. A row that is wholly
+//   -inf gives 0 when n > 0 (the denominator is n) and NaN when n == 0 (0 / 0, as torch.softmax).
 //   dx_i = y_i * (dy_i - sum_j dy_j y_j)   (n enters only through y).
 // One workgroup per row at a time, rows taken in a grid-stride loop (the grid is capped: HIP rejects launches of 2^32 or more
 // threads, so rows >= 2^24 cannot have a workgroup each); the row is cached in registers when it fits (cols <= 256*EPT), fp32 math.
@@ -8,6 +10,7 @@
 #include <math.h>
 #include "fasn.h"
 #include "fasn_common.h"
+#include "fasn_plan.h"
 
 namespace fasn {
 
@@ -66,7 +69,7 @@ __global__ void __launch_bounds__(256) softmax_n_fwd_kernel(const void* x, void*
     }
     mx = block_reduce<true>(mx, red);
     if (n > 0.f) mx = fmaxf(mx, 0.f);
-    if (mx == -INFINITY) mx = 0.f;  // all -inf, n == 0: exp(-inf)/0 -> NaN like the reference
+    if (mx == -INFINITY) mx = 0.f;  // all -inf, n == 0: exp(-inf) / 0 -> NaN, as torch.softmax
     float sum = 0.f;
     if (cached) {
 #pragma unroll
@@ -78,7 +81,7 @@ __global__ void __launch_bounds__(256) softmax_n_fwd_kernel(const void* x, void*
         for (int64_t c = threadIdx.x; c < cols; c += 256) sum += __expf(IO<DT>::ld(x, xo + c) - mx);
     }
     sum = block_reduce<false>(sum, red);
-    const float inv = 1.0f / (n * __expf(-mx) + sum);
+    const float inv = 1.0f / (n > 0.f ? n * __expf(-mx) + sum : sum);   // n == 0: m is not clamped, e^-m may be inf and 0 * inf is NaN
     if (cached) {
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
@@ -184,20 +187,21 @@ __global__ void __launch_bounds__(256) softmax_n_fwd_wave_kernel(const char* x, 
         }
         mx = wave_max(mx);
         if (n > 0.f) mx = fmaxf(mx, 0.f);
-        if (mx == -INFINITY) mx = 0.f;  // all -inf, n == 0: exp(-inf)/0 -> NaN like the reference
-        const float mx2 = mx * kLog2e;
+        if (mx == -INFINITY) mx = 0.f;  // all -inf, n == 0: exp(-inf) / 0 -> NaN, as torch.softmax
+        // the exponent is (x - m) log2 e with the difference taken first: fma(x, log2 e, -round(m log2 e)) leaves the rounding of m log2 e,
+        // 2^-24 |m|, in every exponent - at the maximum itself too, where |m| >= 2^31 turns e^0 into 0 or inf
         float sum = 0.f;
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const bool ok = lane + 64 * i < nvec;
 #pragma unroll
             for (int e = 0; e < EPV; ++e) {
-                v[i][e] = ok ? fast_exp2(__builtin_fmaf(v[i][e], kLog2e, -mx2)) : 0.f;
+                v[i][e] = ok ? fast_exp2((v[i][e] - mx) * kLog2e) : 0.f;
                 sum += v[i][e];
             }
         }
         sum = wave_sum(sum);
-        const float inv = 1.0f / (n * __expf(-mx) + sum);
+        const float inv = 1.0f / (n > 0.f ? n * __expf(-mx) + sum : sum);   // n == 0: m is not clamped, e^-m may be inf and 0 * inf is NaN
         u32x4* yr = reinterpret_cast<u32x4*>(y + row * ys_bytes);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -269,20 +273,19 @@ __global__ void __launch_bounds__(256) softmax_n_fwd_block_kernel(const char* x,
         }
         mx = block_reduce<true>(mx, red);
         if (n > 0.f) mx = fmaxf(mx, 0.f);
-        if (mx == -INFINITY) mx = 0.f;  // all -inf, n == 0: exp(-inf)/0 -> NaN like the reference
-        const float mx2 = mx * kLog2e;
-        float sum = 0.f;
+        if (mx == -INFINITY) mx = 0.f;  // all -inf, n == 0: exp(-inf) / 0 -> NaN, as torch.softmax
+        float sum = 0.f;   // (the exponent: as in the wave kernel)
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
             const bool ok = (int)threadIdx.x + 256 * i < nvec;
 #pragma unroll
             for (int e = 0; e < EPV; ++e) {
-                v[i][e] = ok ? fast_exp2(__builtin_fmaf(v[i][e], kLog2e, -mx2)) : 0.f;
+                v[i][e] = ok ? fast_exp2((v[i][e] - mx) * kLog2e) : 0.f;
                 sum += v[i][e];
             }
         }
         sum = block_reduce<false>(sum, red);
-        const float inv = 1.0f / (n * __expf(-mx) + sum);
+        const float inv = 1.0f / (n > 0.f ? n * __expf(-mx) + sum : sum);   // n == 0: m is not clamped, e^-m may be inf and 0 * inf is NaN
         u32x4* yr = reinterpret_cast<u32x4*>(y + row * ys_bytes);
 #pragma unroll
         for (int i = 0; i < NV; ++i) {
@@ -331,59 +334,77 @@ __global__ void __launch_bounds__(256) softmax_n_bwd_block_kernel(const char* y,
     }
 }
 
-template <int DT>
-static bool launch_fwd_wave(const void* x, void* y, int64_t rows, int64_t cols, int64_t xs, int64_t ys, float n, hipStream_t s) {
-    constexpr int esz = DT == FASN_DTYPE_F32 ? 4 : 2, EPV = VecIO<DT>::EPV;
-    if (cols % EPV || (xs * esz) % 16 || (ys * esz) % 16 || reinterpret_cast<uintptr_t>(x) % 16 || reinterpret_cast<uintptr_t>(y) % 16) return false;
+// ---- dispatch. One function per direction picks the kernel, its NV and its grid from what the call was given; the launchers below and
+// the plan calls (fasn_softmax_n_plan: the same entry points under the launch recorder) both go through it.
+enum RowKernel { ROW_ELEMENT = 0, ROW_WAVE = 1, ROW_BLOCK = 2 };
+struct RowSelect {
+    RowKernel kernel;
+    int nv;          // 16-byte vectors per lane (wave) or per thread (block); 0 for the element-load kernels
+    unsigned grid;
+};
+static unsigned row_grid(int64_t groups) { return (unsigned)(groups < kMaxRowGrid ? groups : kMaxRowGrid); }
+static bool off16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 != 0; }
+
+// forward: wave NV 2 / 4 / 8 / 16 up to 128 / 256 / 512 / 1024 vectors a row, block NV 8 / 16 up to 2048 / 4096; rows that do not move in
+// aligned 16-byte pieces, and longer ones, take the element-load kernel
+static RowSelect select_fwd(const void* x, const void* y, int64_t rows, int64_t cols, int64_t xs, int64_t ys, int dtype) {
+    const int esz = dtype == FASN_DTYPE_F32 ? 4 : 2, EPV = 16 / esz;
     const int64_t nvec = cols / EPV;
-    if (nvec > 256 * 16) return false;
+    if (cols % EPV || (xs * esz) % 16 || (ys * esz) % 16 || off16(x) || off16(y) || nvec > 256 * 16) return {ROW_ELEMENT, 0, row_grid(rows)};
+    if (nvec > 64 * 16) return {ROW_BLOCK, nvec <= 256 * 8 ? 8 : 16, row_grid(rows)};   // too long for one wave's registers
+    return {ROW_WAVE, nvec <= 64 * 2 ? 2 : nvec <= 64 * 4 ? 4 : nvec <= 64 * 8 ? 8 : 16, row_grid((rows + 3) / 4)};
+}
+// backward (two operands in registers): wave NV 2 / 4 / 8 up to 128 / 256 / 512 vectors, block NV 4 / 8 / 16 up to 1024 / 2048 / 4096
+static RowSelect select_bwd(const void* y, const void* dy, const void* dx, int64_t rows, int64_t cols, int64_t ys, int64_t dys, int64_t dxs, int dtype) {
+    const int esz = dtype == FASN_DTYPE_F32 ? 4 : 2, EPV = 16 / esz;
+    const int64_t nvec = cols / EPV;
+    if (cols % EPV || (ys * esz) % 16 || (dys * esz) % 16 || (dxs * esz) % 16 || off16(y) || off16(dy) || off16(dx) || nvec > 256 * 16)
+        return {ROW_ELEMENT, 0, row_grid(rows)};
+    if (nvec > 64 * 8) return {ROW_BLOCK, nvec <= 256 * 4 ? 4 : nvec <= 256 * 8 ? 8 : 16, row_grid(rows)};
+    return {ROW_WAVE, nvec <= 64 * 2 ? 2 : nvec <= 64 * 4 ? 4 : 8, row_grid((rows + 3) / 4)};
+}
+
+template <int DT>
+static int launch_fwd(const void* x, void* y, int64_t rows, int64_t cols, int64_t xs, int64_t ys, float n, hipStream_t s) {
+    constexpr int esz = DT == FASN_DTYPE_F32 ? 4 : 2;
+    const RowSelect r = select_fwd(x, y, rows, cols, xs, ys, DT);
+    const dim3 grid(r.grid);
     const char* xp = (const char*)x;
     char* yp = (char*)y;
-    if (nvec > 64 * 16) {   // too long for one wave's registers: one workgroup per row
-        const dim3 bgrid((unsigned)(rows < kMaxRowGrid ? rows : kMaxRowGrid));
-#define FASN_SM_FWDB(NV) hipLaunchKernelGGL((softmax_n_fwd_block_kernel<DT, NV>), bgrid, dim3(256), 0, s, xp, yp, rows, (int)cols, xs * esz, ys * esz, n)
-        if (nvec <= 256 * 8) FASN_SM_FWDB(8);
-        else FASN_SM_FWDB(16);
-#undef FASN_SM_FWDB
-        return true;
+#define FASN_SM_FWD(kern, NV) FASN_LAUNCH((kern<DT, NV>), grid, dim3(256), 0, s, xp, yp, rows, (int)cols, xs * esz, ys * esz, n)
+    switch (r.kernel * 100 + r.nv) {
+        case ROW_WAVE * 100 + 2: FASN_SM_FWD(softmax_n_fwd_wave_kernel, 2); break;
+        case ROW_WAVE * 100 + 4: FASN_SM_FWD(softmax_n_fwd_wave_kernel, 4); break;
+        case ROW_WAVE * 100 + 8: FASN_SM_FWD(softmax_n_fwd_wave_kernel, 8); break;
+        case ROW_WAVE * 100 + 16: FASN_SM_FWD(softmax_n_fwd_wave_kernel, 16); break;
+        case ROW_BLOCK * 100 + 8: FASN_SM_FWD(softmax_n_fwd_block_kernel, 8); break;
+        case ROW_BLOCK * 100 + 16: FASN_SM_FWD(softmax_n_fwd_block_kernel, 16); break;
+        case ROW_ELEMENT * 100: FASN_LAUNCH(softmax_n_fwd_kernel<DT>, grid, dim3(256), 0, s, x, y, rows, cols, xs, ys, n); break;
+        default: return FASN_EUNSUPPORTED;   // (a selection without a kernel: not reachable)
     }
-    const int64_t blocks = (rows + 3) / 4;
-    const dim3 grid((unsigned)(blocks < kMaxRowGrid ? blocks : kMaxRowGrid));
-#define FASN_SM_FWD(NV) hipLaunchKernelGGL((softmax_n_fwd_wave_kernel<DT, NV>), grid, dim3(256), 0, s, xp, yp, rows, (int)cols, xs * esz, ys * esz, n)
-    if (nvec <= 64 * 2) FASN_SM_FWD(2);
-    else if (nvec <= 64 * 4) FASN_SM_FWD(4);
-    else if (nvec <= 64 * 8) FASN_SM_FWD(8);
-    else FASN_SM_FWD(16);
 #undef FASN_SM_FWD
-    return true;
+    return launch_rc();
 }
 template <int DT>
-static bool launch_bwd_wave(const void* y, const void* dy, void* dx, int64_t rows, int64_t cols, int64_t ys, int64_t dys, int64_t dxs, hipStream_t s) {
-    constexpr int esz = DT == FASN_DTYPE_F32 ? 4 : 2, EPV = VecIO<DT>::EPV;
-    if (cols % EPV || (ys * esz) % 16 || (dys * esz) % 16 || (dxs * esz) % 16 || reinterpret_cast<uintptr_t>(y) % 16 || reinterpret_cast<uintptr_t>(dy) % 16 ||
-        reinterpret_cast<uintptr_t>(dx) % 16)
-        return false;
-    const int64_t nvec = cols / EPV;
-    if (nvec > 256 * 16) return false;
+static int launch_bwd(const void* y, const void* dy, void* dx, int64_t rows, int64_t cols, int64_t ys, int64_t dys, int64_t dxs, hipStream_t s) {
+    constexpr int esz = DT == FASN_DTYPE_F32 ? 4 : 2;
+    const RowSelect r = select_bwd(y, dy, dx, rows, cols, ys, dys, dxs, DT);
+    const dim3 grid(r.grid);
     const char *yp = (const char*)y, *gp = (const char*)dy;
     char* xp = (char*)dx;
-    if (nvec > 64 * 8) {   // too long for one wave's registers: one workgroup per row
-        const dim3 bgrid((unsigned)(rows < kMaxRowGrid ? rows : kMaxRowGrid));
-#define FASN_SM_BWDB(NV) hipLaunchKernelGGL((softmax_n_bwd_block_kernel<DT, NV>), bgrid, dim3(256), 0, s, yp, gp, xp, rows, (int)cols, ys * esz, dys * esz, dxs * esz)
-        if (nvec <= 256 * 4) FASN_SM_BWDB(4);
-        else if (nvec <= 256 * 8) FASN_SM_BWDB(8);
-        else FASN_SM_BWDB(16);
-#undef FASN_SM_BWDB
-        return true;
+#define FASN_SM_BWD(kern, NV) FASN_LAUNCH((kern<DT, NV>), grid, dim3(256), 0, s, yp, gp, xp, rows, (int)cols, ys * esz, dys * esz, dxs * esz)
+    switch (r.kernel * 100 + r.nv) {
+        case ROW_WAVE * 100 + 2: FASN_SM_BWD(softmax_n_bwd_wave_kernel, 2); break;
+        case ROW_WAVE * 100 + 4: FASN_SM_BWD(softmax_n_bwd_wave_kernel, 4); break;
+        case ROW_WAVE * 100 + 8: FASN_SM_BWD(softmax_n_bwd_wave_kernel, 8); break;
+        case ROW_BLOCK * 100 + 4: FASN_SM_BWD(softmax_n_bwd_block_kernel, 4); break;
+        case ROW_BLOCK * 100 + 8: FASN_SM_BWD(softmax_n_bwd_block_kernel, 8); break;
+        case ROW_BLOCK * 100 + 16: FASN_SM_BWD(softmax_n_bwd_block_kernel, 16); break;
+        case ROW_ELEMENT * 100: FASN_LAUNCH(softmax_n_bwd_kernel<DT>, grid, dim3(256), 0, s, y, dy, dx, rows, cols, ys, dys, dxs); break;
+        default: return FASN_EUNSUPPORTED;
     }
-    const int64_t blocks = (rows + 3) / 4;
-    const dim3 grid((unsigned)(blocks < kMaxRowGrid ? blocks : kMaxRowGrid));
-#define FASN_SM_BWD(NV) hipLaunchKernelGGL((softmax_n_bwd_wave_kernel<DT, NV>), grid, dim3(256), 0, s, yp, gp, xp, rows, (int)cols, ys * esz, dys * esz, dxs * esz)
-    if (nvec <= 64 * 2) FASN_SM_BWD(2);
-    else if (nvec <= 64 * 4) FASN_SM_BWD(4);
-    else FASN_SM_BWD(8);
 #undef FASN_SM_BWD
-    return true;
+    return launch_rc();
 }
 
 }  // namespace fasn
@@ -396,48 +417,33 @@ int fasn_softmax_n_fwd(const void* x, void* y, int64_t rows, int64_t cols, int64
                        int32_t dtype, fasn_stream_t stream) {
     if (x == nullptr || y == nullptr || rows <= 0 || cols <= 0 || !(n >= 0.f)) return FASN_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    {   // rows that fit a wave's registers and move in 16-byte pieces: one wave per row, no LDS
-        bool done = false;
-        switch (dtype) {
-            case FASN_DTYPE_F16: done = launch_fwd_wave<FASN_DTYPE_F16>(x, y, rows, cols, x_row_stride, y_row_stride, n, s); break;
-            case FASN_DTYPE_BF16: done = launch_fwd_wave<FASN_DTYPE_BF16>(x, y, rows, cols, x_row_stride, y_row_stride, n, s); break;
-            case FASN_DTYPE_F32: done = launch_fwd_wave<FASN_DTYPE_F32>(x, y, rows, cols, x_row_stride, y_row_stride, n, s); break;
-            default: return FASN_EDTYPE;
-        }
-        if (done) return hipGetLastError() == hipSuccess ? FASN_OK : FASN_ELAUNCH;
-    }
-    const dim3 grid((unsigned)(rows < kMaxRowGrid ? rows : kMaxRowGrid));
     switch (dtype) {
-        case FASN_DTYPE_F16: hipLaunchKernelGGL(softmax_n_fwd_kernel<FASN_DTYPE_F16>, grid, dim3(256), 0, s, x, y, rows, cols, x_row_stride, y_row_stride, n); break;
-        case FASN_DTYPE_BF16: hipLaunchKernelGGL(softmax_n_fwd_kernel<FASN_DTYPE_BF16>, grid, dim3(256), 0, s, x, y, rows, cols, x_row_stride, y_row_stride, n); break;
-        case FASN_DTYPE_F32: hipLaunchKernelGGL(softmax_n_fwd_kernel<FASN_DTYPE_F32>, grid, dim3(256), 0, s, x, y, rows, cols, x_row_stride, y_row_stride, n); break;
+        case FASN_DTYPE_F16: return launch_fwd<FASN_DTYPE_F16>(x, y, rows, cols, x_row_stride, y_row_stride, n, s);
+        case FASN_DTYPE_BF16: return launch_fwd<FASN_DTYPE_BF16>(x, y, rows, cols, x_row_stride, y_row_stride, n, s);
+        case FASN_DTYPE_F32: return launch_fwd<FASN_DTYPE_F32>(x, y, rows, cols, x_row_stride, y_row_stride, n, s);
         default: return FASN_EDTYPE;
     }
-    return hipGetLastError() == hipSuccess ? FASN_OK : FASN_ELAUNCH;
 }
 
 int fasn_softmax_n_bwd(const void* y, const void* dy, void* dx, int64_t rows, int64_t cols, int64_t y_row_stride, int64_t dy_row_stride,
                        int64_t dx_row_stride, int32_t dtype, fasn_stream_t stream) {
     if (y == nullptr || dy == nullptr || dx == nullptr || rows <= 0 || cols <= 0) return FASN_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    {
-        bool done = false;
-        switch (dtype) {
-            case FASN_DTYPE_F16: done = launch_bwd_wave<FASN_DTYPE_F16>(y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride, s); break;
-            case FASN_DTYPE_BF16: done = launch_bwd_wave<FASN_DTYPE_BF16>(y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride, s); break;
-            case FASN_DTYPE_F32: done = launch_bwd_wave<FASN_DTYPE_F32>(y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride, s); break;
-            default: return FASN_EDTYPE;
-        }
-        if (done) return hipGetLastError() == hipSuccess ? FASN_OK : FASN_ELAUNCH;
-    }
-    const dim3 grid((unsigned)(rows < kMaxRowGrid ? rows : kMaxRowGrid));
     switch (dtype) {
-        case FASN_DTYPE_F16: hipLaunchKernelGGL(softmax_n_bwd_kernel<FASN_DTYPE_F16>, grid, dim3(256), 0, s, y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride); break;
-        case FASN_DTYPE_BF16: hipLaunchKernelGGL(softmax_n_bwd_kernel<FASN_DTYPE_BF16>, grid, dim3(256), 0, s, y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride); break;
-        case FASN_DTYPE_F32: hipLaunchKernelGGL(softmax_n_bwd_kernel<FASN_DTYPE_F32>, grid, dim3(256), 0, s, y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride); break;
+        case FASN_DTYPE_F16: return launch_bwd<FASN_DTYPE_F16>(y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride, s);
+        case FASN_DTYPE_BF16: return launch_bwd<FASN_DTYPE_BF16>(y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride, s);
+        case FASN_DTYPE_F32: return launch_bwd<FASN_DTYPE_F32>(y, dy, dx, rows, cols, y_row_stride, dy_row_stride, dx_row_stride, s);
         default: return FASN_EDTYPE;
     }
-    return hipGetLastError() == hipSuccess ? FASN_OK : FASN_ELAUNCH;
+}
+
+int fasn_softmax_n_plan(int32_t which, const void* a, const void* b, const void* c, int64_t rows, int64_t cols, int64_t a_row_stride,
+                        int64_t b_row_stride, int64_t c_row_stride, int32_t dtype, char* buf, size_t cap) {
+    if (which != FASN_ROW_FWD && which != FASN_ROW_BWD) return FASN_EINVAL;
+    return record_plan(buf, cap, [&] {
+        return which == FASN_ROW_FWD ? fasn_softmax_n_fwd(a, const_cast<void*>(b), rows, cols, a_row_stride, b_row_stride, 0.f, dtype, nullptr)
+                                     : fasn_softmax_n_bwd(a, b, const_cast<void*>(c), rows, cols, a_row_stride, b_row_stride, c_row_stride, dtype, nullptr);
+    });
 }
 
 }  // extern "C"

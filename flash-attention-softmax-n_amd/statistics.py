@@ -2,8 +2,8 @@
 
 Same functions as the reference's flash_attention_softmax_n/analysis/statistics.py:9-79 (used there to measure activation
 and weight outliers: variance, skewness, excess kurtosis, per sample or over given dims). The reference runs mean / subtract /
-pow / mean for every statistic; here one kernel reads each element once and returns the raw power sums in fp64, and the
-central moments follow from them. Only orders k <= 4 exist (what the reference's own statistics use).
+pow / mean for every statistic; here one kernel reads each element once and returns the power sums about the row's first
+element in fp64, and the central moments follow from them. Only orders k <= 4 exist (what the reference's own statistics use).
 """
 from typing import Optional, Tuple, Union
 
@@ -18,7 +18,10 @@ _MAX_ROWS = 65535
 
 
 def _power_sums(x: Tensor, dim: _Dim):
-    """returns (count per output element, fp64 sums [rows, 4], output shape)"""
+    """returns (count per output element, fp64 sums [rows, 4], output shape). sums[r, k - 1] is the sum of (x - pivot_r)^k over row r of the
+    [rows, cols] picture, pivot_r the row's first element, subtracted in fp64: the power sums about a point inside the data. Central
+    moments are the same about any point, so _central applies the raw-moment formulas to them unchanged - and without the cancellation
+    those formulas suffer about 0 when the mean is large against the spread."""
     if not x.is_cuda:
         raise RuntimeError("statistics: device tensors only (no CPU fallback)")
     if x.dtype not in _DT:

@@ -577,13 +577,36 @@ int fasn_softmax_n_bwd(const void* y, const void* dy, void* dx, int64_t rows, in
                        int32_t dtype, fasn_stream_t stream);
 
 /*
- * Raw power sums of every row of a [rows, cols] matrix in ONE pass (col stride 1, row stride in elements):
- * sums[row][0..3] += sum x, sum x^2, sum x^3, sum x^4 (fp64; the caller zeroes `sums`). Replaces the repeated
+ * Power sums of every row of a [rows, cols] matrix in ONE pass (col stride 1, row stride in elements), taken about the row's
+ * first element so that central moments formed from them do not cancel on data with a large offset:
+ * sums[row][0..3] += sum d, sum d^2, sum d^3, sum d^4 with d = x - x[row][0] in fp64 (the caller zeroes `sums`). Replaces the repeated
  * mean / subtract / pow passes of flash_attention_softmax_n/analysis/statistics.py:9-79 (variance, skewness, kurtosis of
  * activations) for device tensors. dtype: FASN_DTYPE_F16 / BF16 / F32; rows <= 65535.
  */
 int fasn_moments(const void* x, double* sums, int64_t rows, int64_t cols, int64_t row_stride, int32_t dtype,
                  fasn_stream_t stream);
+
+/*
+ * The one launch of the row kernels as text (ABI 6, in the line format of fasn_launch_plan): which kernel template, with which
+ * arguments, on which grid. The plan calls ARE the calls above under the launch recorder: the same argument checks with the same
+ * FASN_E* codes, the same selection function, no kernel run, no device touched, no HIP call made. Pointers only have to be
+ * non-NULL; their alignment is read, since a pointer off 16 bytes sends a call to the element-load kernels. Return value as for
+ * fasn_launch_plan: the bytes written, a FASN_E* code, or FASN_EINVAL when `cap` is too small.
+ *
+ * fasn_softmax_n_plan: `which` = FASN_ROW_FWD takes (a, b) = (x, y) and their row strides, c and c_row_stride are not read;
+ * FASN_ROW_BWD takes (a, b, c) = (y, dy, dx). n is no argument: it does not enter the selection (a negative n is refused by the
+ * forward alone). The kernels: softmax_n_{fwd,bwd}_wave_kernel<dtype, NV> (one wave per row, four rows per workgroup, NV 16-byte vectors
+ * per lane), softmax_n_{fwd,bwd}_block_kernel<dtype, NV> (one workgroup per row, NV vectors per thread), and softmax_n_{fwd,bwd}_kernel<dtype>
+ * (element loads: any alignment, any stride, any length).
+ *
+ * fasn_moments_plan: the arguments of fasn_moments; grid= is the number of chunks a row is cut into (grid.x; grid.y is `rows`).
+ */
+#define FASN_ROW_FWD 0
+#define FASN_ROW_BWD 1
+int fasn_softmax_n_plan(int32_t which, const void* a, const void* b, const void* c, int64_t rows, int64_t cols, int64_t a_row_stride,
+                        int64_t b_row_stride, int64_t c_row_stride, int32_t dtype, char* buf, size_t cap);
+int fasn_moments_plan(const void* x, const double* sums, int64_t rows, int64_t cols, int64_t row_stride, int32_t dtype, char* buf,
+                      size_t cap);
 
 #ifdef __cplusplus
 }

@@ -178,8 +178,12 @@ def attend(q, k, v, w, n, scale, bias=None, keep=None, p_eff=0.0, do=None, row_w
     e = w * torch.exp(x - m.unsqueeze(-1))
     l = torch.where(n > 0, n * torch.exp(-m), torch.zeros_like(m)) + e.sum(-1)
     f = torch.ones_like(e) if keep is None else keep / (1.0 - p_eff)
-    ef = e * f
-    acc, acc_abs = ef @ v, ef @ v.abs()
+    # the dropout factor is applied AFTER the sums over keys and rows: in witness A e keep, P keep (Z a power of two), v and dO are small
+    # integers or dyadic fractions, so these sums are exact in whatever order the host's BLAS takes them, and the one division that follows
+    # rounds the same everywhere. Summing e f v instead left host-dependent ulps in acc and dV - enough to turn "one count is exactly four
+    # gates" into 3.999999999999998 on one machine and 4 on another.
+    ek, live = (e, 1.0) if keep is None else (e * keep, 1.0 - p_eff)
+    acc, acc_abs = (ek @ v) / live, (ek @ v.abs()) / live
     has = l > 0
     safe = torch.where(has, l, torch.ones_like(l))
     out, A = acc / safe.unsqueeze(-1), acc_abs / safe.unsqueeze(-1)
@@ -190,7 +194,8 @@ def attend(q, k, v, w, n, scale, bias=None, keep=None, p_eff=0.0, do=None, row_w
         return r
     Pf = P * f
     rows = torch.ones(N, L, 1, dtype=torch.float64) if row_w is None else row_w.unsqueeze(-1)
-    r["dV"], r["dV_abs"] = Pf.transpose(1, 2) @ (rows * do), Pf.transpose(1, 2) @ (rows * do.abs())
+    Pk = P if keep is None else P * keep
+    r["dV"], r["dV_abs"] = (Pk.transpose(1, 2) @ (rows * do)) / live, (Pk.transpose(1, 2) @ (rows * do.abs())) / live
     dP, dP_abs = f * (do @ v.transpose(1, 2)), f * (do.abs() @ v.abs().transpose(1, 2))
     delta, delta_abs = (do * out).sum(-1), (do * out).abs().sum(-1)
     if delta_mode == "zero":

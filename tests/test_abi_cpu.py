@@ -26,6 +26,7 @@ def test_library_exports_every_header_symbol(pkg):
     for name in names:
         assert hasattr(lib, name), f"libfasn.so does not export {name}"
     assert set(pkg._lib.EXPORTS) == set(names)
+    assert {"fasn_softmax_n_plan", "fasn_moments_plan"} <= set(names)   # the row kernels' plans (tests/test_rowops_cpu.py runs them)
 
 
 def test_library_exports_nothing_but_the_header(pkg):

@@ -1412,7 +1412,7 @@ def test_softmax_n_kernel(pkg, dev, golden_dir, n, dtype):
     assert (x.grad.cpu().float() - xc.grad).abs().max().item() <= 4 * tol * max(xc.grad.abs().max().item(), 1e-3) + 1e-7
     z = pkg.softmax_n(x.detach().transpose(1, 2), n=n, dim=1)  # non-last dim
     assert torch.allclose(z.transpose(1, 2).float(), y.detach().float(), atol=1e-6)
-    w = synth.counter_normal((3, 5000), 5, std=3.0, dtype=dtype, device=dev)  # cols > register cache
+    w = synth.counter_normal((3, 5000), 5, std=3.0, dtype=dtype, device=dev)  # a wave kernel still (NV = 16; fp32: the NV = 8 block kernel)
     assert torch.allclose(pkg.softmax_n(w, n=n).float().cpu(), ref_softmax_n(w.cpu().float(), n=n), atol=tol, rtol=tol)
     # rows too long for one wave's registers: one workgroup per row, forward and backward (12288 and 32768 take the 16-byte kernels,
     # 40000 the element-load kernels)
