@@ -37,6 +37,8 @@ EXPORTS = (
     "fasn_fwd_kvcache_tree_workspace_bytes", "fasn_fwd_kvcache_tree", "fasn_kvcache_tree_plan",
     "fasn_fwd_kvprefill_tree_workspace_bytes", "fasn_fwd_kvprefill_tree", "fasn_kvprefill_tree_plan",
     "fasn_kvcache_tree_rope_append", "fasn_kvprefill_tree_rope_append", "fasn_kvcache_tree_commit",
+    "fasn_fwd_kvcache_fp8_workspace_bytes", "fasn_fwd_kvcache_fp8", "fasn_kvcache_fp8_plan", "fasn_kvcache_fp8_append",
+    "fasn_fwd_kvprefill_fp8_workspace_bytes", "fasn_fwd_kvprefill_fp8", "fasn_kvprefill_fp8_plan", "fasn_kvprefill_fp8_append",
 )
 
 
@@ -118,6 +120,13 @@ class KvTree(Structure):
     _fields_ = [("mask", c_void_p), ("batch_stride", c_int64), ("window", c_int32), ("reserved", c_int32)]
 
 
+class KvFp8(Structure):
+    """fasn_kv_fp8 (include/fasn.h): the per-(batch, K/V head) fp32 scales of an e4m3fn cache in device memory, for the *_fp8 cache calls;
+    reserved = 0"""
+    _fields_ = [("k_scale", c_void_p), ("v_scale", c_void_p), ("k_sb", c_int64), ("k_sh", c_int64), ("v_sb", c_int64), ("v_sh", c_int64),
+                ("reserved", c_int32)]
+
+
 class KvTreeCommit(Structure):
     """fasn_kv_tree_commit (include/fasn.h): the cache and the accepted path of fasn_kvcache_tree_commit"""
     _fields_ = [
@@ -139,7 +148,7 @@ _lib = None
 
 
 def _kv_bindings():
-    """(name, restype, argtypes) of the 40 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
+    """(name, restype, argtypes) of the 48 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
     block (fasn_kvprefill_args), `operands` come between the block and the tail; then the nine of the packed block (fasn_kvvarlen_args)
     and the commit of a token tree, which has a block of its own"""
     view, text = POINTER(View4), [c_char_p, c_size_t]
@@ -162,7 +171,11 @@ def _kv_bindings():
                 (f"fasn_fwd_{stem}_tree_workspace_bytes", c_size_t, [POINTER(KvTree)], []),
                 (f"fasn_fwd_{stem}_tree", c_int32, [POINTER(KvTree)], forward),
                 (f"fasn_{stem}_tree_plan", c_int32, [POINTER(KvTree)], text),
-                (f"fasn_{stem}_tree_rope_append", c_int32, [POINTER(KvRope), POINTER(KvTree), view, view, view], launch)):
+                (f"fasn_{stem}_tree_rope_append", c_int32, [POINTER(KvRope), POINTER(KvTree), view, view, view], launch),
+                (f"fasn_fwd_{stem}_fp8_workspace_bytes", c_size_t, [POINTER(KvFp8)], []),
+                (f"fasn_fwd_{stem}_fp8", c_int32, [POINTER(KvFp8)], forward),
+                (f"fasn_{stem}_fp8_plan", c_int32, [POINTER(KvFp8)], text),
+                (f"fasn_{stem}_fp8_append", c_int32, [POINTER(KvFp8), view, view], launch)):
             yield name, restype, [block] + operands + tail
     packed = [POINTER(KvVarlenArgs)]
     yield "fasn_fwd_kvvarlen_workspace_bytes", c_size_t, packed
@@ -326,6 +339,12 @@ def kvtree_plan(args, tree):
     """The kernels fasn_fwd_kvcache_tree (`args` a KvCacheArgs) or fasn_fwd_kvprefill_tree (a KvPrefillArgs) would launch under `tree` (a
     KvTree), as launch_plan returns them. Nothing is launched."""
     return _kv_plan("fasn_kvprefill_tree_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_tree_plan", args, tree)
+
+
+def kvfp8_plan(args, fp8):
+    """The kernels fasn_fwd_kvcache_fp8 (`args` a KvCacheArgs) or fasn_fwd_kvprefill_fp8 (a KvPrefillArgs) would launch under `fp8` (a
+    KvFp8), as launch_plan returns them. Nothing is launched."""
+    return _kv_plan("fasn_kvprefill_fp8_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_plan", args, fp8)
 
 
 def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):

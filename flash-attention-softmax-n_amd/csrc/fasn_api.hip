@@ -52,6 +52,12 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
         {"fasn_kvvarlen_fwd_kernel", "T D"},
         {"fasn_kvvarlen_combine_kernel", "T D"},
         {"fasn_kvvarlen_append_kernel", "D"},
+        {"fasn_kvcache_fwd_fp8_kernel", "T D"},
+        {"fasn_kvcache_fp8_combine_kernel", "T D"},
+        {"fasn_kvcache_fp8_append_kernel", "T D"},
+        {"fasn_kvprefill_fwd_fp8_kernel", "T D"},
+        {"fasn_kvprefill_fp8_combine_kernel", "T D"},
+        {"fasn_kvprefill_fp8_append_kernel", "T D"},
     };
     static const char* const modes[] = {"plain", "causal", "bias+mask", "element-load", "bias", "mask", "keypad", "bias+keypad"};
     if (cap == 0) return 0;

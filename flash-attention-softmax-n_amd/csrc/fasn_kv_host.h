@@ -1,7 +1,8 @@
 // fasn_kv_host.h — the ONE host layer of the K/V-cache family (decode, prefill, packed prefill, rotary append): argument checks, parameter
 // packing, the launch plan, the workspace rule, the launch recorder and the dtype x head-dim dispatch. fasn_kvcache.hip defines what is
-// declared here; fasn_kvcache.hip, fasn_kvprefill.hip, fasn_kvvarlen.hip and fasn_kvrope.hip each instantiate and launch the kernels of
-// their own header (fasn_kvrope.hip: also the packed rotary append, fasn_kvvarlen.hip: also the packed window forward).
+// declared here; fasn_kvcache.hip, fasn_kvprefill.hip, fasn_kvvarlen.hip, fasn_kvrope.hip and fasn_kvfp8.hip each instantiate and launch the
+// kernels of their own header (fasn_kvrope.hip: also the packed rotary append, fasn_kvvarlen.hip: also the packed window forward,
+// fasn_kvfp8.hip: the decode and the prefill call over an FP8 cache).
 #pragma once
 #include <type_traits>
 #include "fasn.h"
@@ -33,6 +34,7 @@ struct KvFwd {
     KvWindow kw;
     KvPacked pk;          // KV_VARLEN only
     KvTree kt;            // KV_TREE only
+    KvFp8 f8;             // KV_FP8 only
 };
 
 inline bool kv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -45,8 +47,11 @@ size_t kv_workspace_bytes(const KvArgs& in, KvVariant variant, const void* opera
 // the token-tree operand's checks, behind the base arguments' (the tree forwards and the tree rotary appends share them): `kt` with the
 // window as the kernels take it - capacity + 1 when there is none
 int kv_check_tree(const fasn_kvcache_args* a, const fasn_kv_tree* t, int capacity, KvTree& kt);
+// the FP8 operand's checks, behind the base arguments' (the FP8 forwards and the quantising appends share them): the scales, and the rules
+// of a cache whose strides count bytes
+int kv_check_fp8(const fasn_kvcache_args* a, const fasn_kv_fp8* o, KvFp8& f8);
 // everything a forward does before its launches: base checks, the variant's operand (nothing, a fasn_alibi_slopes, a fasn_kv_window, a
-// fasn_kv_tree), then the workspace
+// fasn_kv_tree, a fasn_kv_fp8), then the workspace
 int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, KvFwd& f);
 
 // dtype x head dim -> f(tag, std::integral_constant<int, D>) (kv_build let only these four head dims through)

@@ -131,8 +131,18 @@ struct KvTree {
     int64_t sb;              // batch stride, elements
     int w;                   // 1 .. capacity: the window; capacity + 1: none
 };
-// which forward kernel a call launches; its operand is nothing, a fasn_alibi_slopes, a fasn_kv_window or a fasn_kv_tree
-enum KvVariant { KV_BASE, KV_ALIBI, KV_WINDOW, KV_TREE };
+// FP8 cache (fasn_fwd_kvcache_fp8 / fasn_fwd_kvprefill_fp8, kernels in fasn_kvfp8.h): a cache element is an OCP e4m3fn code whose value is
+// the exact upcast of the code times one fp32 scale per (batch element, K/V head), addressed as the per-head n is. KvParams::k / v are the
+// code pools and the cache strides count codes (bytes); everything else in KvParams keeps its meaning.
+struct KvFp8 {
+    const float* ks;     // k_scale, device
+    const float* vs;     // v_scale, device
+    int ksb, ksh;        // element strides (batch, K/V head)
+    int vsb, vsh;
+};
+constexpr bool kv_fp8_head_dim_ok(int D) { return D == 64 || D == 128; }
+// which forward kernel a call launches; its operand is nothing, a fasn_alibi_slopes, a fasn_kv_window, a fasn_kv_tree or a fasn_kv_fp8
+enum KvVariant { KV_BASE, KV_ALIBI, KV_WINDOW, KV_TREE, KV_FP8 };
 
 // fasn_kvcache_fwd_kernel<Tag, D>(KvParams), fasn_kvcache_fwd_alibi_kernel<Tag, D>(KvParams, KvAlibi) and
 // fasn_kvcache_fwd_window_kernel<Tag, D>(KvParams, KvWindow): one text, compiled three times.

@@ -2,7 +2,7 @@
 // fasn_kvcache_tree_commit), in two parts:
 //   1. the host layer of the whole K/V-cache family (fasn_kv_host.h declares it; fasn_kvprefill.hip, fasn_kvvarlen.hip and fasn_kvrope.hip call it): argument
 //      checks, parameter packing, the launch plan - which depends on shapes and capacity only, never on the lengths in device memory -
-//      the operand checks of the ALiBi and window variants and the workspace rule;
+//      the operand checks of the ALiBi, window, tree and FP8 variants and the workspace rule;
 //   2. the decode entry points and the launches of fasn_kvcache.h.
 #include <limits.h>
 #include <math.h>
@@ -148,6 +148,22 @@ int kv_check_tree(const fasn_kvcache_args* a, const fasn_kv_tree* t, int capacit
     return FASN_OK;
 }
 
+// The FP8 operand of the *_fp8 entry points (checked after the base arguments, before any HIP call). The base checks hold a 16-bit cache
+// to strides % 8 elements; here an element is a byte, so the same 16-byte rule is strides % 16. The scales follow the rules of `n`, per
+// K/V head.
+int kv_check_fp8(const fasn_kvcache_args* a, const fasn_kv_fp8* o, KvFp8& f8) {
+    if (o == nullptr || o->k_scale == nullptr || o->v_scale == nullptr || o->reserved != 0) return FASN_EINVAL;
+    if (!kv_fp8_head_dim_ok(a->D)) return FASN_EHEADDIM;
+    if (reinterpret_cast<uintptr_t>(o->k_scale) % 4 || reinterpret_cast<uintptr_t>(o->v_scale) % 4) return FASN_EALIGN;
+    for (int i = 0; i < 3; ++i)
+        if (a->k_stride[i] % 16 != 0 || a->v_stride[i] % 16 != 0) return FASN_EALIGN;
+    const int Hkv = a->H / (a->kv_group <= 1 ? 1 : a->kv_group);
+    if (o->k_sb < 0 || o->k_sh < 0 || (a->B - 1) * o->k_sb + (Hkv - 1) * o->k_sh >= (1ll << 31)) return FASN_EINVAL;
+    if (o->v_sb < 0 || o->v_sh < 0 || (a->B - 1) * o->v_sb + (Hkv - 1) * o->v_sh >= (1ll << 31)) return FASN_EINVAL;
+    f8 = KvFp8{o->k_scale, o->v_scale, (int)o->k_sb, (int)o->k_sh, (int)o->v_sb, (int)o->v_sh};
+    return FASN_OK;
+}
+
 namespace {
 
 // The plan under a tree: the base call's rule; with a window the window call's rule over the tiles the windows of the Sq nodes can touch
@@ -193,6 +209,11 @@ int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, K
     f.al = KvAlibi{};
     f.kw = KvWindow{};
     f.kt = KvTree{};
+    f.f8 = KvFp8{};
+    if (variant == KV_FP8) {   // (decode and prefill only: there is no packed FP8 call)
+        if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
+        return kv_check_fp8(in.a, static_cast<const fasn_kv_fp8*>(operand), f.f8);
+    }
     if (variant == KV_TREE) {   // (decode and prefill only: there is no packed tree call)
         if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
         return kv_build_tree(in.a, static_cast<const fasn_kv_tree*>(operand), (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kt);

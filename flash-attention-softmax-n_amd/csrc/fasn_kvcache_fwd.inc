@@ -3,8 +3,13 @@
 // before the variants existed, and with FASN_KV_WINDOW == 0 the ALiBi kernel as it was before the window kernel did.
 // FASN_KV_TREE = 1 (with the other two at 0; undefined counts as 0) is the token-tree sibling: the new positions see the prefix and the
 // nodes their word of `tree.mask` names, the window is a run-time integer. With FASN_KV_TREE == 0 the three kernels above are what they were.
+// FASN_KV_FP8 = 1 (fasn_kvfp8.h, with the other three at 0; undefined counts as 0) is the sibling over a cache of e4m3fn codes (KvFp8): a tile
+// is staged as D-byte rows, widened by all four waves into the 16-bit tile image the fragment reads take, and k_scale rides in the score
+// factor. With FASN_KV_FP8 == 0 the four kernels above are what they were.
 template <typename Tag, int D>
-#if FASN_KV_TREE
+#if FASN_KV_FP8
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_kernel(const KvParams p, const KvFp8 f8) {
+#elif FASN_KV_TREE
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_tree_kernel(const KvParams p, const KvTree tree) {
 #elif FASN_KV_ALIBI
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_alibi_kernel(const KvParams p, const KvAlibi al) {
@@ -23,10 +28,24 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     constexpr int DB = D / 32;
     constexpr int CPR = D / 8;
     constexpr int NLD = (KV_KT * CPR) / NT;
+    // what is staged: the tile as the cache holds it, EB bytes per element (the image of 16-bit rows itself unless the cache holds fp8 codes)
+#if FASN_KV_FP8
+    constexpr int EB = 1;
+#else
+    constexpr int EB = 2;
+#endif
+    constexpr int SROWB = D * EB;
+    constexpr int STILEB = KV_KT * SROWB;
+    constexpr int SCPR = SROWB / 16;
+    constexpr int SNLD = (KV_KT * SCPR) / NT;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const ldsK = smem;
-    char* const ldsV = smem + NBUF * TILEB;
+    char* const ldsV = smem + NBUF * STILEB;
+#if FASN_KV_FP8
+    char* const imgK = smem + 2 * NBUF * STILEB;   // the one 16-bit tile image per operand that the staged codes are widened into
+    char* const imgV = imgK + TILEB;
+#endif
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -72,6 +91,9 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
 #if FASN_KV_ALIBI
     float nslope2 = al.slopes[b * al.sb + h * al.sh] * -kLog2e;   // -slope * log2(e) of the row's query head: lane-private, read once, like n
 #endif
+#if FASN_KV_FP8
+    float c8 = p.c * f8.ks[b * f8.ksb + hkv * f8.ksh];   // k_scale acts on the fp32 scores: one uniform load in front of the tile loop, like n
+#endif
     const bool wave_rows = wave * 32 < p.R;   // a wave without rows only helps staging
 
     vec8 qf[KS];
@@ -86,17 +108,21 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     }
 
     // ---- staging: thread tid fills slots tid + i * 256 of the tile image (slot = 16 bytes; the chunk that belongs there after the swizzle)
-    unsigned kvoff[NLD], vvoff[NLD];
+    unsigned kvoff[SNLD], vvoff[SNLD];
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) {
+    for (int i = 0; i < SNLD; ++i) {
         const int ci = tid + i * NT;
+#if FASN_KV_FP8
+        const int r = ci / SCPR, ch = ci % SCPR;   // the staged codes lie as in the cache: the widening pass applies the swizzle
+#else
         const int r = ci / CPR, ch = (ci % CPR) ^ swz_f<D>(r);
-        kvoff[i] = (unsigned)(r * (int)p.krs * 2 + ch * 16);
-        vvoff[i] = (unsigned)(r * (int)p.vrs * 2 + ch * 16);
+#endif
+        kvoff[i] = (unsigned)(r * (int)p.krs * EB + ch * 16);
+        vvoff[i] = (unsigned)(r * (int)p.vrs * EB + ch * 16);
     }
     const uint32_t ldsK_w = lds_addr(ldsK) + wave * 1024, ldsV_w = lds_addr(ldsV) + wave * 1024;
-    const char* const kpool = p.k + (int64_t)hkv * p.khs * 2;
-    const char* const vpool = p.v + (int64_t)hkv * p.vhs * 2;
+    const char* const kpool = p.k + (int64_t)hkv * p.khs * EB;
+    const char* const vpool = p.v + (int64_t)hkv * p.vhs * EB;
 
     // the tile that is requested next: its index, page slot and tile inside the page advance together (no division in the loop)
     int u = t0;
@@ -114,15 +140,15 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     int u_page = page_of(u, u_slot);
     auto request_next = [&](int buf) {
         const int nvis = u < t1 ? min(KV_KT, len - u * KV_KT) : 0;   // rows of the tile below len_b (>= 1 inside the range)
-        const int64_t koff = ((int64_t)u_page * p.kps + (int64_t)u_tip * KV_KT * p.krs) * 2;
-        const int64_t voff = ((int64_t)u_page * p.vps + (int64_t)u_tip * KV_KT * p.vrs) * 2;
-        const uint32_t kbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.krs * 2 + ROWB) : 0u;
-        const uint32_t vbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.vrs * 2 + ROWB) : 0u;
+        const int64_t koff = ((int64_t)u_page * p.kps + (int64_t)u_tip * KV_KT * p.krs) * EB;
+        const int64_t voff = ((int64_t)u_page * p.vps + (int64_t)u_tip * KV_KT * p.vrs) * EB;
+        const uint32_t kbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.krs * EB + SROWB) : 0u;
+        const uint32_t vbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.vrs * EB + SROWB) : 0u;
         const u32x4 krw = make_rsrc_words(kpool + koff, kbytes), vrw = make_rsrc_words(vpool + voff, vbytes);
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            kv_dma16(krw, __builtin_amdgcn_readfirstlane(ldsK_w + buf * TILEB + i * NT * 16), kvoff[i]);
-            kv_dma16(vrw, __builtin_amdgcn_readfirstlane(ldsV_w + buf * TILEB + i * NT * 16), vvoff[i]);
+        for (int i = 0; i < SNLD; ++i) {
+            kv_dma16(krw, __builtin_amdgcn_readfirstlane(ldsK_w + buf * STILEB + i * NT * 16), kvoff[i]);
+            kv_dma16(vrw, __builtin_amdgcn_readfirstlane(ldsV_w + buf * STILEB + i * NT * 16), vvoff[i]);
         }
         ++u;
         if (++u_tip == p.tpp) {
@@ -153,10 +179,13 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     retire_loads(nslope2);
     const int qpos = pos + len - p.Sq;   // absolute position of the row's query
 #endif
+#if FASN_KV_FP8
+    retire_loads(c8);
+#endif
 
     // ---- the tile buffers start as zeros: a request that is out of range for its descriptor must leave nothing behind that is not
     // a finite number, whether the hardware fills the slot with zeros or leaves it alone (afterwards a slot holds zeros or visible rows)
-    for (int i = tid; i < 2 * NBUF * TILEB / 16; i += NT) *LDS_PTR(u32x4, smem + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    for (int i = tid; i < 2 * NBUF * STILEB / 16; i += NT) *LDS_PTR(u32x4, smem + i * 16) = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
     // ---- prologue: NBUF - 1 tiles in flight
 #pragma unroll
@@ -166,12 +195,24 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     for (int t = t0; t < t1; ++t) {
         // tile t has landed (this wave's share: the NBUF - 2 younger tiles may still be in flight), then everybody's share has, and
         // everybody is done with tile t - 1, whose buffer takes the next request
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * 2 * NLD) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * 2 * SNLD) : "memory");
         __syncthreads();
         request_next(buf == 0 ? NBUF - 1 : buf - 1);
+#if FASN_KV_FP8
+        // everybody is done with the image of tile t - 1 (the barrier above) and with the codes of tile t - 1 (widened before the barrier
+        // below, one tile ago): all four waves widen tile t, rows or not, then everybody's share of the image is there
+        kv_fp8_widen<E, D>(ldsK + buf * STILEB, imgK, tid);
+        kv_fp8_widen<E, D>(ldsV + buf * STILEB, imgV, tid);
+        __syncthreads();
+#endif
         if (wave_rows) {
+#if FASN_KV_FP8
+            const char* tK = imgK;
+            const char* tV = imgV;
+#else
             const char* tK = ldsK + buf * TILEB;
             const char* tV = ldsV + buf * TILEB;
+#endif
             const int k0 = t * KV_KT;
             f32x16 sacc[2];
 #pragma unroll
@@ -206,6 +247,8 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
                     for (int r = 0; r < 16; ++r) {
 #if FASN_KV_ALIBI
                         sacc[kb][r] = __builtin_fmaf(sacc[kb][r], p.c, kv_alibi_term(nslope2, dk0, kb, r));
+#elif FASN_KV_FP8
+                        sacc[kb][r] *= c8;
 #else
                         sacc[kb][r] *= p.c;
 #endif
@@ -246,6 +289,8 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
                         const float y = key <= vis ? __builtin_fmaf(sacc[kb][r], p.c, kv_alibi_term(nslope2, dk0, kb, r)) : -INFINITY;
 #elif FASN_KV_WINDOW
                         const float y = (unsigned)(dvis - (kb * 32 + (r & 3) + 8 * (r >> 2))) < (unsigned)win.w ? sacc[kb][r] * p.c : -INFINITY;
+#elif FASN_KV_FP8
+                        const float y = key <= vis ? sacc[kb][r] * c8 : -INFINITY;
 #else
                         const float y = key <= vis ? sacc[kb][r] * p.c : -INFINITY;
 #endif

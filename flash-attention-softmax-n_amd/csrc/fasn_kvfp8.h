@@ -1,0 +1,204 @@
+// fasn_kvfp8.h — the cache calls over an FP8 cache: decode and prefill on a paged or dense cache of OCP e4m3fn codes with one fp32 scale per
+// (batch element, K/V head) in device memory (fasn_kvcache.h: KvFp8). The 16-bit kernels of fasn_kvcache.h / fasn_kvprefill.h are not
+// touched; these are their siblings on the same grid and split rule.
+//
+//   fasn_kvcache_fwd_fp8_kernel / fasn_kvprefill_fwd_fp8_kernel   one more inclusion each of the forward texts under FASN_KV_FP8
+//   fasn_kvcache_fp8_combine_kernel / fasn_kvprefill_fp8_combine_kernel   the combine kernels with v_scale in front of the one rounding
+//   fasn_kvcache_fp8_append_kernel / fasn_kvprefill_fp8_append_kernel   k_new / v_new rows, quantised, -> the cache rows behind the lengths
+//
+// Semantics. value(code) = up(code) * scale[b, hkv], up() the exact upcast. All 254 finite codes are bf16 AND fp16 numbers, so the operands
+// of the 16-bit MFMAs are the codes themselves and the scales act in fp32:
+//   x_ij  = scale * k_scale[b, hkv] * (q_i . up(Kc_j))                        one factor c8 = c * k_scale on the fp32 scores
+//   out_i = v_scale[b, hkv] * sum_j p_ij up(Vc_j) / (n + sum_j p_ij)          on the fp32 output, before it is rounded once
+// Visibility, the lengths, the sink on split 0, lse, rows that see nothing and the stale-memory rules are the base call's.
+//
+// Widening. A tile is staged as KV_KT rows of D BYTES - half the buffer_load ... lds requests, descriptor ranges in bytes of the code rows,
+// rows at or beyond len_b still arrive as zeros (code 0x00 is +0) - into NBUF linear buffers per operand. Once tile t has landed all 256
+// threads widen it into ONE 16-bit tile image per operand, swizzled as fasn_common.h describes, and lds_read_rowfrag / lds_read_trfrag
+// run on that image unchanged; a second barrier per tile publishes it. LDS: D = 64: 2 x 3 x 4 KiB + 2 x 8 KiB = 40 KiB; D = 128:
+// 2 x 2 x 8 KiB + 2 x 16 KiB = 64 KiB - two workgroups per CU, as the 16-bit kernels.
+#pragma once
+#include "fasn_kvprefill.h"
+
+namespace fasn {
+
+constexpr int kv_fp8_smem(int D) { return 2 * kv_nbuf(D) * KV_KT * D + 2 * KV_KT * D * 2; }   // staged codes + one 16-bit image per operand
+
+// The widening pass of one operand: thread tid fills the slots tid + i * 256 of the 16-bit image - the slots it would have staged from a
+// 16-bit cache, slot ci = (row ci / CPR, chunk (ci % CPR) ^ swz) - from the 8 codes of that chunk in the linear code tile.
+// v_cvt_pk_f32_fp8 is exact for all 256 codes (OCP e4m3fn on gfx950: subnormals, both zeros, NaN -> NaN) and every finite code is
+// a bf16 and an fp16 number, so the conversion to the operand type rounds nothing. 64 lanes read 512 contiguous bytes, permuted in
+// 8-byte words, and write 1024 contiguous bytes: no bank conflict either way.
+template <typename E, int D>
+FASN_DEV void kv_fp8_widen(const char* src, char* img, int tid) {
+    constexpr int CPR = D / 8;
+    constexpr int NLD = (KV_KT * CPR) / 256;
+#pragma unroll
+    for (int i = 0; i < NLD; ++i) {
+        const int ci = tid + i * 256;
+        const int r = ci / CPR, ch = (ci % CPR) ^ swz_f<D>(r);
+        const u32x2 raw = *LDS_PTR(const u32x2, src + r * D + ch * 8);
+        f32x8 x;
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)raw[w], false), up = __builtin_amdgcn_cvt_pk_f32_fp8((int)raw[w], true);
+            x[4 * w] = lo[0], x[4 * w + 1] = lo[1], x[4 * w + 2] = up[0], x[4 * w + 3] = up[1];
+        }
+        const typename E::vec8 y = E::cvt8(x);
+        u32x4 out;
+        __builtin_memcpy(&out, &y, 16);
+        *LDS_PTR(u32x4, img + ci * 16) = out;
+    }
+}
+
+#define FASN_KV_FP8 1
+#include "fasn_kvcache_fwd.inc"
+#include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_FP8
+
+// fasn_kvcache_combine_kernel with v_scale[b, hkv] on the normalised fp32 row, in front of its one rounding
+template <typename Tag, int D>
+__global__ void __launch_bounds__(256) fasn_kvcache_fp8_combine_kernel(const KvParams p, const KvFp8 f8) {
+    using E = ET<Tag>;
+    constexpr int TPR = D / 4;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t rowg = gid / TPR;   // (b * Hkv + hkv, r)
+    const int c4 = (int)(gid % TPR) * 4;
+    if (rowg >= (int64_t)p.B * p.Hkv * p.R) return;
+    const int bk = (int)(rowg / p.R), r = (int)(rowg % p.R);
+    const int b = bk / p.Hkv, hkv = bk % p.Hkv, h = hkv * p.G + r / p.Sq, pos = r % p.Sq;
+    float mstar = -INFINITY;
+    for (int s = 0; s < p.nsplit; ++s) mstar = fmaxf(mstar, p.part_ml[(((int64_t)bk * p.nsplit + s) * p.R + r) * 2]);
+    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
+    float l = 0.f;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < p.nsplit; ++s) {
+        const int64_t base = ((int64_t)bk * p.nsplit + s) * p.R + r;
+        const float ms = p.part_ml[base * 2], ls = p.part_ml[base * 2 + 1];
+        if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
+        const float w = fast_exp2(ms - m_use);
+        l += ls * w;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(p.part_o + base * D + c4);
+        acc += a * w;
+    }
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    typename E::vec4 y = E::cvt4(acc * inv * f8.vs[b * f8.vsb + hkv * f8.vsh]);
+    u32x2 raw;
+    __builtin_memcpy(&raw, &y, 8);
+    gstore8(p.o + (b * p.os[0] + h * p.os[1] + (int64_t)pos * p.os[2] + c4) * 2, raw);
+    if (p.lse != nullptr && c4 == 0) p.lse[((int64_t)b * p.H + h) * p.Sq + pos] = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
+}
+
+// fasn_kvprefill_combine_kernel with v_scale[b, hkv], likewise
+template <typename Tag, int D>
+__global__ void __launch_bounds__(256) fasn_kvprefill_fp8_combine_kernel(const KvPrefillParams pp, const KvFp8 f8) {
+    using E = ET<Tag>;
+    const KvParams& p = pp.kv;
+    constexpr int TPR = D / 4;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t slot = gid / TPR;   // ((b * Hkv + hkv) * nrb + rb, r)
+    const int c4 = (int)(gid % TPR) * 4;
+    if (slot >= (int64_t)p.B * p.Hkv * pp.nrb * KVP_ROWS) return;
+    const int64_t blk = slot / KVP_ROWS;
+    const int r = (int)(slot % KVP_ROWS);
+    const int rb = (int)(blk % pp.nrb), bk = (int)(blk / pp.nrb);
+    const int g = r / pp.PB, pos = rb * pp.PB + r % pp.PB;
+    if (g >= p.G || pos >= p.Sq) return;
+    const int b = bk / p.Hkv, hkv = bk % p.Hkv, h = hkv * p.G + g;
+    char* const oat = p.o + (b * p.os[0] + h * p.os[1] + (int64_t)pos * p.os[2] + c4) * 2;
+    float* const lat = p.lse != nullptr && c4 == 0 ? p.lse + ((int64_t)b * p.H + h) * p.Sq + pos : nullptr;
+    int qlen = p.Sq;
+    if (pp.qlens != nullptr) qlen = min(max(pp.qlens[b], 0), p.Sq);
+    if (pos >= qlen) {
+        gstore8(oat, u32x2{0u, 0u});
+        if (lat != nullptr) *lat = -INFINITY;
+        return;
+    }
+    float mstar = -INFINITY;
+    for (int s = 0; s < p.nsplit; ++s) mstar = fmaxf(mstar, p.part_ml[((blk * p.nsplit + s) * KVP_ROWS + r) * 2]);
+    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
+    float l = 0.f;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < p.nsplit; ++s) {
+        const int64_t base = (blk * p.nsplit + s) * KVP_ROWS + r;
+        const float ms = p.part_ml[base * 2], ls = p.part_ml[base * 2 + 1];
+        if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
+        const float w = fast_exp2(ms - m_use);
+        l += ls * w;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(p.part_o + base * D + c4);
+        acc += a * w;
+    }
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    typename E::vec4 y = E::cvt4(acc * inv * f8.vs[b * f8.vsb + hkv * f8.vsh]);
+    u32x2 raw;
+    __builtin_memcpy(&raw, &y, 8);
+    gstore8(oat, raw);
+    if (lat != nullptr) *lat = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
+}
+
+// ---- quantising append
+// code = rne_e4m3(clamp(float(x) / s, -448, 448)); a NaN stays a NaN code. The division is the correctly rounded fp32 division (this build
+// has no fast-math). The clamp makes the saturation explicit - whatever the conversion instruction's mode does beyond 448 is never asked -
+// and is written so that a NaN falls through both comparisons; v_cvt_pk_fp8_f32 rounds to nearest even and turns NaN into 0x7f / 0xff.
+FASN_DEV float kv_fp8_prep(float x, float s) {
+    const float y = x / s;
+    return y > 448.f ? 448.f : (y < -448.f ? -448.f : y);
+}
+// 16 elements of a row in the query's dtype (two 16-byte loads) -> 16 codes
+template <typename E>
+FASN_DEV u32x4 kv_fp8_quant16(const char* src, float s) {
+    u32x4 out;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        const u32x4 raw = gload16(src + half * 16);
+        float x[8];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            x[2 * w] = kv_fp8_prep(E::to_f32((uint16_t)(raw[w] & 0xffffu)), s);
+            x[2 * w + 1] = kv_fp8_prep(E::to_f32((uint16_t)(raw[w] >> 16)), s);
+        }
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+            int pk = 0;
+            pk = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * w], x[4 * w + 1], pk, false);
+            pk = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * w + 2], x[4 * w + 3], pk, true);
+            out[2 * half + w] = (uint32_t)pk;
+        }
+    }
+    return out;
+}
+
+// k_new / v_new row i of (b, hkv), quantised -> cache row seqlens[b] + i: 16 codes (16 bytes stored) per thread and tensor. The rules of
+// fasn_kvcache_append_kernel / fasn_kvprefill_append_kernel: rows i >= qlen_b (PREFILL) are neither read nor written, positions at or
+// beyond the capacity (or negative) are dropped, `seqlens` is not modified.
+template <typename Tag, int D, bool PREFILL>
+FASN_DEV void kv_fp8_append(const KvParams& p, const int* qlens, const KvFp8& f8) {
+    using E = ET<Tag>;
+    constexpr int CPR = D / 16;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (int64_t)p.B * p.Hkv * p.Sq * CPR) return;
+    const int ch = (int)(gid % CPR);
+    int64_t rest = gid / CPR;
+    const int i = (int)(rest % p.Sq);
+    rest /= p.Sq;
+    const int hkv = (int)(rest % p.Hkv), b = (int)(rest / p.Hkv);
+    if (PREFILL && qlens != nullptr && i >= qlens[b]) return;
+    const int64_t key = (int64_t)p.seqlens[b] + i;
+    if (key < 0 || key >= p.capacity) return;
+    const int slot = (int)(key / p.page_size), rip = (int)(key % p.page_size);
+    const int64_t page = p.bt != nullptr ? p.bt[(int64_t)b * p.bts + slot] : b;
+    const u32x4 kx = kv_fp8_quant16<E>(p.kn + (b * p.kns[0] + hkv * p.kns[1] + (int64_t)i * p.kns[2]) * 2 + ch * 32, f8.ks[b * f8.ksb + hkv * f8.ksh]);
+    const u32x4 vx = kv_fp8_quant16<E>(p.vn + (b * p.vns[0] + hkv * p.vns[1] + (int64_t)i * p.vns[2]) * 2 + ch * 32, f8.vs[b * f8.vsb + hkv * f8.vsh]);
+    gstore16(p.k + page * p.kps + (int64_t)rip * p.krs + (int64_t)hkv * p.khs + ch * 16, kx);
+    gstore16(p.v + page * p.vps + (int64_t)rip * p.vrs + (int64_t)hkv * p.vhs + ch * 16, vx);
+}
+template <typename Tag, int D>
+__global__ void __launch_bounds__(256) fasn_kvcache_fp8_append_kernel(const KvParams p, const KvFp8 f8) {
+    kv_fp8_append<Tag, D, false>(p, nullptr, f8);
+}
+template <typename Tag, int D>
+__global__ void __launch_bounds__(256) fasn_kvprefill_fp8_append_kernel(const KvPrefillParams pp, const KvFp8 f8) {
+    kv_fp8_append<Tag, D, true>(pp.kv, pp.qlens, f8);
+}
+
+}  // namespace fasn

@@ -8,8 +8,13 @@
 // defines from the item - and a packed ALiBi sibling would be one more inclusion.
 // FASN_KV_TREE = 1 (fasn_kvprefill.h, with the other three at 0; undefined counts as 0) is the token-tree sibling (fasn_kvcache.h: KvTree):
 // every row block walks to len_b, because a node may see any node. With FASN_KV_TREE == 0 the kernels above are what they were.
+// FASN_KV_FP8 = 1 (fasn_kvfp8.h, with the other four at 0; undefined counts as 0) is the sibling over a cache of e4m3fn codes (fasn_kvcache.h:
+// KvFp8; fasn_kvcache_fwd.inc: staging, widening pass); v_scale multiplies the one-split direct store. With FASN_KV_FP8 == 0 the kernels
+// above are what they were.
 template <typename Tag, int D>
-#if FASN_KV_TREE
+#if FASN_KV_FP8
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_fp8_kernel(const KvPrefillParams pp, const KvFp8 f8) {
+#elif FASN_KV_TREE
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_tree_kernel(const KvPrefillParams pp, const KvTree tree) {
 #elif FASN_KV_PACKED && FASN_KV_WINDOW
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvvarlen_fwd_window_kernel(const KvPrefillParams pp, const KvPacked pk, const KvWindow win) {
@@ -33,10 +38,24 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     constexpr int DB = D / 32;
     constexpr int CPR = D / 8;
     constexpr int NLD = (KV_KT * CPR) / NT;
+    // what is staged: the tile as the cache holds it, EB bytes per element (fasn_kvcache_fwd.inc)
+#if FASN_KV_FP8
+    constexpr int EB = 1;
+#else
+    constexpr int EB = 2;
+#endif
+    constexpr int SROWB = D * EB;
+    constexpr int STILEB = KV_KT * SROWB;
+    constexpr int SCPR = SROWB / 16;
+    constexpr int SNLD = (KV_KT * SCPR) / NT;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const ldsK = smem;
-    char* const ldsV = smem + NBUF * TILEB;
+    char* const ldsV = smem + NBUF * STILEB;
+#if FASN_KV_FP8
+    char* const imgK = smem + 2 * NBUF * STILEB;   // the one 16-bit tile image per operand that the staged codes are widened into
+    char* const imgV = imgK + TILEB;
+#endif
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -138,6 +157,9 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 #if FASN_KV_ALIBI
     float nslope2 = al.slopes[b * al.sb + h * al.sh] * -kLog2e;   // -slope * log2(e) of the slot's query head: lane-private, read once, like n
 #endif
+#if FASN_KV_FP8
+    float c8 = p.c * f8.ks[b * f8.ksb + hkv * f8.ksh];   // k_scale acts on the fp32 scores: one uniform load in front of the tile loop, like n
+#endif
     const bool wave_rows = wave * 32 < p.G * pp.PB;   // a wave without row slots only helps staging
 
     vec8 qf[KS];
@@ -156,17 +178,21 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     }
 
     // ---- staging: thread tid fills slots tid + i * 256 of the tile image (slot = 16 bytes; the chunk that belongs there after the swizzle)
-    unsigned kvoff[NLD], vvoff[NLD];
+    unsigned kvoff[SNLD], vvoff[SNLD];
 #pragma unroll
-    for (int i = 0; i < NLD; ++i) {
+    for (int i = 0; i < SNLD; ++i) {
         const int ci = tid + i * NT;
+#if FASN_KV_FP8
+        const int r = ci / SCPR, ch = ci % SCPR;   // the staged codes lie as in the cache: the widening pass applies the swizzle
+#else
         const int r = ci / CPR, ch = (ci % CPR) ^ swz_f<D>(r);
-        kvoff[i] = (unsigned)(r * (int)p.krs * 2 + ch * 16);
-        vvoff[i] = (unsigned)(r * (int)p.vrs * 2 + ch * 16);
+#endif
+        kvoff[i] = (unsigned)(r * (int)p.krs * EB + ch * 16);
+        vvoff[i] = (unsigned)(r * (int)p.vrs * EB + ch * 16);
     }
     const uint32_t ldsK_w = lds_addr(ldsK) + wave * 1024, ldsV_w = lds_addr(ldsV) + wave * 1024;
-    const char* const kpool = p.k + (int64_t)hkv * p.khs * 2;
-    const char* const vpool = p.v + (int64_t)hkv * p.vhs * 2;
+    const char* const kpool = p.k + (int64_t)hkv * p.khs * EB;
+    const char* const vpool = p.v + (int64_t)hkv * p.vhs * EB;
 
     // the tile that is requested next: its index, page slot and tile inside the page advance together (no division in the loop)
     int u = t0;
@@ -182,15 +208,15 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     int u_page = page_of(u, u_slot);
     auto request_next = [&](int buf) {
         const int nvis = u < t1 ? min(KV_KT, len - u * KV_KT) : 0;   // rows of the tile below len_b (>= 1 inside the range)
-        const int64_t koff = ((int64_t)u_page * p.kps + (int64_t)u_tip * KV_KT * p.krs) * 2;
-        const int64_t voff = ((int64_t)u_page * p.vps + (int64_t)u_tip * KV_KT * p.vrs) * 2;
-        const uint32_t kbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.krs * 2 + ROWB) : 0u;
-        const uint32_t vbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.vrs * 2 + ROWB) : 0u;
+        const int64_t koff = ((int64_t)u_page * p.kps + (int64_t)u_tip * KV_KT * p.krs) * EB;
+        const int64_t voff = ((int64_t)u_page * p.vps + (int64_t)u_tip * KV_KT * p.vrs) * EB;
+        const uint32_t kbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.krs * EB + SROWB) : 0u;
+        const uint32_t vbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.vrs * EB + SROWB) : 0u;
         const u32x4 krw = make_rsrc_words(kpool + koff, kbytes), vrw = make_rsrc_words(vpool + voff, vbytes);
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            kv_dma16(krw, __builtin_amdgcn_readfirstlane(ldsK_w + buf * TILEB + i * NT * 16), kvoff[i]);
-            kv_dma16(vrw, __builtin_amdgcn_readfirstlane(ldsV_w + buf * TILEB + i * NT * 16), vvoff[i]);
+        for (int i = 0; i < SNLD; ++i) {
+            kv_dma16(krw, __builtin_amdgcn_readfirstlane(ldsK_w + buf * STILEB + i * NT * 16), kvoff[i]);
+            kv_dma16(vrw, __builtin_amdgcn_readfirstlane(ldsV_w + buf * STILEB + i * NT * 16), vvoff[i]);
         }
         ++u;
         if (++u_tip == p.tpp) {
@@ -230,13 +256,17 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     // The biased score y = fma(s, c, bias) replaces s in place, for any sign of c - fasn_kvcache_fwd_kernel's element pass with its
     // multiply turned into an fma - and the rest runs as the c <= 0 path does, with ce = 1: fma(y, 1, -m) is y - m exactly.
     constexpr float ce = 1.0f;
+#elif FASN_KV_FP8
+    retire_loads(c8);
+    const bool cpos = c8 > 0.f;
+    const float ce = cpos ? c8 : 1.0f;
 #else
     const bool cpos = p.c > 0.f;
     const float ce = cpos ? p.c : 1.0f;
 #endif
 
     // ---- the tile buffers start as zeros (fasn_kvcache.h: an out-of-range request must leave nothing behind that is not finite)
-    for (int i = tid; i < 2 * NBUF * TILEB / 16; i += NT) *LDS_PTR(u32x4, smem + i * 16) = u32x4{0u, 0u, 0u, 0u};
+    for (int i = tid; i < 2 * NBUF * STILEB / 16; i += NT) *LDS_PTR(u32x4, smem + i * 16) = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
     // ---- prologue: NBUF - 1 tiles in flight
 #pragma unroll
@@ -244,12 +274,23 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 
     int buf = 0;
     for (int t = t0; t < t1; ++t) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * 2 * NLD) : "memory");
+        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 2) * 2 * SNLD) : "memory");
         __syncthreads();
         request_next(buf == 0 ? NBUF - 1 : buf - 1);
+#if FASN_KV_FP8
+        // all four waves widen tile t into the image, between two barriers (fasn_kvcache_fwd.inc)
+        kv_fp8_widen<E, D>(ldsK + buf * STILEB, imgK, tid);
+        kv_fp8_widen<E, D>(ldsV + buf * STILEB, imgV, tid);
+        __syncthreads();
+#endif
         if (wave_rows) {
+#if FASN_KV_FP8
+            const char* tK = imgK;
+            const char* tV = imgV;
+#else
             const char* tK = ldsK + buf * TILEB;
             const char* tV = ldsV + buf * TILEB;
+#endif
             const int k0 = t * KV_KT;
             f32x16 sacc[2];
 #pragma unroll
@@ -275,7 +316,11 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
+#if FASN_KV_FP8
+                    for (int r = 0; r < 16; ++r) sacc[kb][r] *= c8;
+#else
                     for (int r = 0; r < 16; ++r) sacc[kb][r] *= p.c;
+#endif
             }
 #endif
             // raw scores (times ce: log2 domain); hidden keys (beyond the row's limit, which is below len_b) go to -inf
@@ -375,7 +420,12 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
     if (p.nsplit == 1) {
         // ---- the only split: normalise and store. Padding positions of a live block (qlen_b <= pos < Sq) store exact zeros / -inf.
         if (slot_ok) {
+#if FASN_KV_FP8
+            // v_scale acts on the fp32 output, in front of its one rounding: folded into the row's factor
+            const float inv = (row_ok && l_tot > 0.f) ? f8.vs[b * f8.vsb + hkv * f8.vsh] / l_tot : 0.f;
+#else
             const float inv = (row_ok && l_tot > 0.f) ? 1.0f / l_tot : 0.f;
+#endif
             if (!row_ok) {
 #pragma unroll
                 for (int d = 0; d < DB; ++d)

@@ -18,6 +18,8 @@ packed buffers (fasn_fwd_kvvarlen_window / fasn_kvvarlen_rope_append): a served 
 flash_attention_n_kvcache_tree verifies a TREE of draft tokens in one step (speculative decoding: fasn_fwd_kvcache_tree / fasn_fwd_kvprefill_tree,
 fasn_kv*_tree_rope_append): one int64 word per node on the device says which nodes it sees, its position is the prefix length plus its
 depth; flash_attention_n_kvcache_tree_commit moves the accepted path's cache rows behind the prefix (fasn_kvcache_tree_commit).
+flash_attention_n_kvcache_fp8 is the decode / prefill call over a cache of e4m3fn codes with per-(batch, K/V head) fp32 scales on the device
+(fasn_fwd_kvcache_fp8 / fasn_fwd_kvprefill_fp8, fasn_kv*_fp8_append): half the cache bytes per key, k_new / v_new quantised on the way in.
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -27,11 +29,12 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import AlibiSlopes, KvCacheArgs, KvPrefillArgs, KvRope, KvTree, KvTreeCommit, KvVarlenArgs, KvWindow
+from ._lib import AlibiSlopes, KvCacheArgs, KvFp8, KvPrefillArgs, KvRope, KvTree, KvTreeCommit, KvVarlenArgs, KvWindow
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
 _KV_HEAD_DIMS = (32, 64, 128, 256)   # the head dims flash_attention_n trains at; any other size is refused (a cache is never padded)
+_FP8_HEAD_DIMS = (64, 128)           # ... and those the FP8-cache kernels are built for
 _INT_MAX = 2 ** 31 - 1   # what an int32 member of an argument block holds: host integers are clamped to it
 _MAX_ROWS = 128   # query heads per K/V head x query positions: the rows of one workgroup
 _MAX_NODES = 64   # nodes of a token tree: one bit of an int64 word each
@@ -43,8 +46,9 @@ _BLOCKS = {"kvcache": KvCacheArgs, "kvprefill": KvPrefillArgs, "kvvarlen": KvVar
 def _check_cache(name: str, t: Tensor, paged: bool, D: int) -> None:
     if t.stride(3) != 1:
         raise ValueError(f"{name}: feature stride must be 1 (got {t.stride(3)}); a cache is never copied, so it cannot be made contiguous here")
-    if t.data_ptr() % 16 != 0 or any(t.stride(i) % 8 != 0 for i in range(3) if t.size(i) > 1):
-        raise ValueError(f"{name}: rows must be 16-byte aligned (base pointer % 16 == 0, page / row / head strides % 8 elements); "
+    per16 = 16 // t.element_size()   # elements of 16 bytes: 8 in a 16-bit cache, 16 codes in an FP8 cache
+    if t.data_ptr() % 16 != 0 or any(t.stride(i) % per16 != 0 for i in range(3) if t.size(i) > 1):
+        raise ValueError(f"{name}: rows must be 16-byte aligned (base pointer % 16 == 0, page / row / head strides % {per16} elements); "
                          f"got strides {tuple(t.stride())}")
     if t.size(1) > 1 and t.stride(1) < D:
         raise ValueError(f"{name}: rows overlap (row stride {t.stride(1)} < head dim {D})")
@@ -105,6 +109,28 @@ class _Call:
     __slots__ = ("stem", "args", "kv", "dev", "packed", "qshape", "dtype", "out", "lse", "k_new", "v_new", "alibi", "keep")
 
 
+def _scale_tensor(fn, name, value, query, Hkv) -> Tensor:
+    """k_scale / v_scale as the fp32 [1 or B, 1 or Hkv] tensor the FP8 kernels read per (batch, K/V head). A Python number becomes a
+    one-element tensor on the query's device, filled there; a tensor's values are not looked at (no host round trip: capturable)."""
+    B = query.shape[0]
+    if isinstance(value, (int, float)) and not isinstance(value, bool):
+        return torch.full((1, 1), float(value), dtype=torch.float32, device=query.device)
+    if not isinstance(value, Tensor) or not value.is_floating_point():
+        got = value.dtype if isinstance(value, Tensor) else type(value).__name__
+        raise TypeError(f"{fn}: {name} must be a Python float or a floating-point tensor; got {got}")
+    shape = (1,) * (2 - value.dim()) + tuple(value.shape)
+    if value.dim() > 2 or shape[0] not in (1, B) or shape[1] not in (1, Hkv):
+        raise ValueError(f"{fn}: {name} must broadcast to [B, Hkv] = [{B}, {Hkv}] ([Hkv], [1, Hkv], [B, 1], [B, Hkv] or 0-d; Hkv = K/V heads); "
+                         f"got {tuple(value.shape)}")
+    if value.device != query.device:
+        raise RuntimeError(f"{name} is on {value.device}, query on {query.device}: every operand must live on the query's device "
+                           "(the scales are read by the kernels, never on the host)")
+    if torch.is_grad_enabled() and value.requires_grad:
+        raise RuntimeError(f"{fn} is forward only (inference): {name} requires grad and the scales carry no gradient. Call it under "
+                           "torch.no_grad()")
+    return value.detach().float().reshape(shape)
+
+
 def _query_shaped(c) -> Tensor:
     """uninitialised, in the layout of `out` (and of the rotated queries): [B, H, Sq, D], or the [1, H, T, D] view of a packed [T, H, D]"""
     B, H, Sq, D = c.qshape
@@ -114,12 +140,12 @@ def _query_shaped(c) -> Tensor:
 
 
 def _prepare(fn, stem, query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal, return_lse,
-             alibi_slopes=None, query_seqlens=None, by_shape=False, cu_seqlens_q=None, max_seqlen_q=None) -> _Call:
+             alibi_slopes=None, query_seqlens=None, by_shape=False, cu_seqlens_q=None, max_seqlen_q=None, fp8=False) -> _Call:
     """The argument checks every entry point shares (they need no device and come first), the outputs and the filled argument block.
     `stem` says which block: "kvcache" (fasn_kvcache_args, at most _MAX_ROWS rows), "kvprefill" (fasn_kvprefill_args, with
     `query_seqlens`) or "kvvarlen" (fasn_kvvarlen_args: `query` is the [B, H, T, D] view of _packed_query, k_new / v_new and the outputs
     are token-packed, `cu_seqlens_q` and `max_seqlen_q` go into the block). `by_shape` (the window and rope calls, on "kvprefill"): the
-    decode kernels run on the block's first member where the shapes allow them."""
+    decode kernels run on the block's first member where the shapes allow them. `fp8`: the caches hold e4m3fn codes (the FP8 call)."""
     packed = stem == "kvvarlen"
     if query.dim() != 4 or k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError("query must be [B, H, Sq, D] and the caches [num_pages, page_size, Hkv, D] (paged) or [B, capacity, Hkv, D] (dense)")
@@ -132,7 +158,11 @@ def _prepare(fn, stem, query, k_cache, v_cache, cache_seqlens, block_table, k_ne
         if t is not None and t.device != dev:
             raise RuntimeError(f"{name} is on {t.device}, query on {dev}: every operand must live on the query's device "
                                "(the lengths and the block table are read by the kernels, never on the host)")
-    if k_cache.dtype != query.dtype or v_cache.dtype != query.dtype:
+    if fp8:
+        if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"{fn}: k_cache and v_cache must be torch.float8_e4m3fn (OCP e4m3fn codes; e5m2 and fnuz caches are not supported); "
+                            f"got {k_cache.dtype} and {v_cache.dtype}. A 16-bit cache is flash_attention_n_kvcache / _prefill's")
+    elif k_cache.dtype != query.dtype or v_cache.dtype != query.dtype:
         raise TypeError("query, k_cache and v_cache must share one dtype")
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (query, k_cache, v_cache, k_new, v_new)) or (
             torch.is_grad_enabled() and isinstance(softmax_n_param, Tensor) and softmax_n_param.requires_grad):
@@ -141,6 +171,8 @@ def _prepare(fn, stem, query, k_cache, v_cache, cache_seqlens, block_table, k_ne
     if D not in _KV_HEAD_DIMS:
         raise ValueError(f"{fn}: head dim {D} is not supported (supported: {_KV_HEAD_DIMS}); a cache is never "
                          "zero-padded on the host")
+    if fp8 and D not in _FP8_HEAD_DIMS:
+        raise ValueError(f"{fn}: head dim {D} is not supported on an FP8 cache (supported: {_FP8_HEAD_DIMS}; 32 and 256 have 16-bit kernels only)")
     if k_cache.shape != v_cache.shape or k_cache.shape[3] != D:
         raise ValueError(f"k_cache and v_cache must have one shape [*, *, Hkv, {D}]; got {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
     page_size, Hkv = k_cache.shape[1], k_cache.shape[2]
@@ -253,10 +285,14 @@ def _on_device(dev, launch) -> None:
             launch()
 
 
-def _append(lib, c, stream, rope=None, q_rot=None, tree=None) -> None:
+def _append(lib, c, stream, rope=None, q_rot=None, tree=None, fp8=None) -> None:
     """k_new / v_new -> the cache rows behind the lengths; with `rope` the one launch that rotates them on the way and the queries into
-    `q_rot`, which the forward then reads - under `tree` at the nodes' depth positions"""
-    if rope is not None:
+    `q_rot`, which the forward then reads - under `tree` at the nodes' depth positions; with `fp8` the launch that quantises them"""
+    if fp8 is not None:
+        if c.k_new is not None:
+            name = f"fasn_{c.stem}_fp8_append"
+            _lib.check(getattr(lib, name)(c.args, fp8, _view4(c.k_new), _view4(c.v_new), stream), name)
+    elif rope is not None:
         name = f"fasn_{c.stem}_rope_append" if tree is None else f"fasn_{c.stem}_tree_rope_append"
         kn_view = None if c.k_new is None else _view4(c.k_new)
         vn_view = None if c.v_new is None else _view4(c.v_new)
@@ -268,11 +304,14 @@ def _append(lib, c, stream, rope=None, q_rot=None, tree=None) -> None:
         _lib.check(getattr(lib, name)(c.args, _view4(c.k_new), _view4(c.v_new), stream), name)
 
 
-def _forward(lib, c, stream, win=None, tree=None) -> None:
-    """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (c.alibi), of their window siblings (`win`)
-    or of their token-tree siblings (`tree`, which carries its window)"""
+def _forward(lib, c, stream, win=None, tree=None, fp8=None) -> None:
+    """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (c.alibi), of their window siblings (`win`),
+    of their token-tree siblings (`tree`, which carries its window) or of their FP8-cache siblings (`fp8`)"""
     stem = c.stem
-    if tree is not None:
+    if fp8 is not None:
+        name, operand = f"fasn_fwd_{stem}_fp8", (fp8,)
+        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_fp8_workspace_bytes")(c.args, fp8)
+    elif tree is not None:
         name, operand = f"fasn_fwd_{stem}_tree", (tree,)
         ws_bytes = getattr(lib, f"fasn_fwd_{stem}_tree_workspace_bytes")(c.args, tree)
     elif win is not None:
@@ -290,10 +329,10 @@ def _forward(lib, c, stream, win=None, tree=None) -> None:
     _lib.check(getattr(lib, name)(c.args, *operand, None if ws is None else ws.data_ptr(), ws_bytes, stream), name)
 
 
-def _run(c, window=None, rope=None, tree_mask=None):
+def _run(c, window=None, rope=None, tree_mask=None, fp8_scales=None):
     """What every call does once it is checked: the library, the rotated-query temporary, then under the query's device the stream,
     the append and the forward; the outputs in the caller's layout. `tree_mask` ([B, Sq] int64): the token-tree operand, which takes the
-    window with it."""
+    window with it. `fp8_scales` (k_scale, v_scale as _scale_tensor returns them): the FP8 operand."""
     lib = _lib.load()
     tree = None
     if tree_mask is not None:
@@ -302,11 +341,16 @@ def _run(c, window=None, rope=None, tree_mask=None):
         window = None
     win = None if window is None else KvWindow(window=min(window, _INT_MAX), reserved=0)
     q_rot = None if rope is None else _query_shaped(c)   # (torch's caching allocator: a captured graph owns it)
+    fp8 = None
+    if fp8_scales is not None:
+        ks, vs = fp8_scales
+        fp8 = KvFp8(k_scale=ks.data_ptr(), v_scale=vs.data_ptr(), reserved=0)
+        (fp8.k_sb, fp8.k_sh), (fp8.v_sb, fp8.v_sh) = _n_strides(ks), _n_strides(vs)
 
     def launch():
         stream = _stream_ptr(c.dev)
-        _append(lib, c, stream, rope, q_rot, tree)
-        _forward(lib, c, stream, win, tree)
+        _append(lib, c, stream, rope, q_rot, tree, fp8)
+        _forward(lib, c, stream, win, tree, fp8)
 
     _on_device(c.dev, launch)
     out = c.out.transpose(1, 2).squeeze(0) if c.packed else c.out   # packed: [T, H, D] (lse is [H, T] as allocated)
@@ -717,6 +761,71 @@ def flash_attention_n_kvcache_rope(
     c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
                  return_lse, query_seqlens=query_seqlens, by_shape=True)
     return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query))
+
+
+def flash_attention_n_kvcache_fp8(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        k_scale,
+        v_scale,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        query_seqlens: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False,
+        alibi_slopes=None,
+        window=None,
+        rotary_cos=None,
+        rotary_sin=None,
+        cu_seqlens_q=None,
+        tree_mask=None):
+    """softmax_n attention against an FP8 K/V CACHE, on MI355X: decode, chunked prefill or prefill in one call over a cache of one-byte
+    e4m3fn codes with per-(batch element, K/V head) scales - half the bytes a key costs the HBM-bound decode call, twice the tokens per GiB.
+
+    A cache element is an OCP e4m3fn code (torch.float8_e4m3fn) and its value is the exact upcast of the code times the scale of its
+    (b, hkv). All 254 finite codes are fp16 and bf16 numbers, so the kernels hand the codes themselves to the 16-bit MFMAs and the scales
+    act in fp32 only:
+        x_ij  = scale * k_scale[b, hkv] * (q_i . up(Kc_j))
+        out_i = v_scale[b, hkv] * sum_j p_ij up(Vc_j) / (n + sum_j p_ij)          rounded once, after the scale
+    With power-of-two scales the result is, bit for bit, flash_attention_n_kvcache / _prefill on `k_cache.to(query.dtype)`. `block_table`,
+    `cache_seqlens`, `query_seqlens`, `softmax_n_param`, `scale`, `is_causal`, the outputs, visibility (len_b, qlen_b), rows that see
+    nothing and the stale-memory rules are those of flash_attention_n_kvcache_prefill; the kernels are chosen by shapes alone as in
+    flash_attention_n_kvcache_window (query_seqlens=None and (H // Hkv) * Sq <= 128: the decode kernels). What differs:
+
+    :param query: [B, H, Sq, D] fp16 / bf16, D in {64, 128}.
+    :param k_cache, v_cache: torch.float8_e4m3fn, paged [num_pages, page_size, Hkv, D] (page_size % 64 == 0) or dense [B, capacity, Hkv, D];
+                  feature stride 1, base pointer and page / row / head strides multiples of 16 BYTES; never copied. Rows at or beyond
+                  len_b may hold any byte (the NaN code 0x7f included); a NaN code in a visible row is a NaN.
+    :param k_scale, v_scale: a Python float, or a floating tensor on the query's device that broadcasts to [B, Hkv] ([Hkv], [1, Hkv],
+                  [B, 1], [B, Hkv] or 0-d). Read by the kernels, never on the host: a captured graph follows them. A non-positive or
+                  non-finite scale is the caller's error: the result is unspecified, no memory outside the buffers is touched.
+    :param k_new, v_new: optional [B, Hkv, Sq, D] in query's dtype: rows i < qlen_b are QUANTISED and written to the cache positions
+                  cache_seqlens[b] + i first - code = rne_e4m3(clamp(float(x) / s, -448, 448)), s the scale of (b, hkv), the division
+                  correctly rounded in fp32, saturating, NaN -> a NaN code - and then attended to. `cache_seqlens` is not modified.
+    :param alibi_slopes, window, rotary_cos, rotary_sin, cu_seqlens_q, tree_mask: anything but None is refused here: the FP8 cache has
+                  the base kernels only.
+    :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32).
+    """
+    fn = "flash_attention_n_kvcache_fp8"
+    for name, value in (("alibi_slopes", alibi_slopes), ("window", window), ("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin),
+                        ("cu_seqlens_q", cu_seqlens_q), ("tree_mask", tree_mask)):
+        if value is not None:
+            raise NotImplementedError(f"{fn}: {name} is not supported on an FP8 cache (no FP8 ALiBi, window, rotary, packed or tree kernels "
+                                      "yet); use a 16-bit cache with the call of that name")
+    _check_query_seqlens(fn, query_seqlens, query)
+    _check_group_limit(fn, query, k_cache)
+    Hkv = k_cache.shape[2] if k_cache.dim() == 4 and query.dim() == 4 else 1
+    scales = None
+    if query.dim() == 4:
+        scales = (_scale_tensor(fn, "k_scale", k_scale, query, Hkv), _scale_tensor(fn, "v_scale", v_scale, query, Hkv))
+    c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
+                 return_lse, query_seqlens=query_seqlens, by_shape=True, fp8=True)
+    return _run(c, fp8_scales=scales)
 
 
 def _check_tree_mask(fn, tree_mask, query) -> Tensor:

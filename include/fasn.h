@@ -564,6 +564,51 @@ int fasn_kvprefill_tree_rope_append(const fasn_kvprefill_args* args, const fasn_
 int fasn_kvcache_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t stream);
 
 /*
+ * FP8 K/V CACHE (additions within ABI 6): the base decode and prefill calls over a cache of OCP e4m3fn codes (torch.float8_e4m3fn;
+ * gfx950's FP8, not MI300's fnuz) with one fp32 scale per (batch element, K/V head) in device memory. One operand beside the unchanged
+ * argument blocks. In those blocks k_cache / v_cache point at BYTES, k_stride / v_stride count elements (= bytes) and `dtype` is the
+ * dtype of q, o, k_new and v_new (fp16 / bf16).
+ *
+ *   value      of a cache element = up(code) * scale[b, hkv], up() the exact upcast: all 254 finite codes are fp16 and bf16 numbers, so
+ *              the 16-bit MFMAs take the codes themselves and the scales act in fp32 only:
+ *                x_ij  = scale * k_scale[b, hkv] * (q_i . up(Kc_j))
+ *                out_i = v_scale[b, hkv] * sum_j p_ij up(Vc_j) / (n + sum_j p_ij)        rounded once, after the scale
+ *              No Q or P quantisation, no fp8 MFMA. A NaN code in a visible row is a NaN, as a NaN in a 16-bit cache is.
+ *   scales     scale (b, hkv) at k_scale[b * k_sb + hkv * k_sh] (v likewise): the rules of `n`, per K/V head; stride 0 broadcasts. Read
+ *              by the kernels only - a captured graph follows them. A non-positive or non-finite scale gives unspecified results and
+ *              touches no memory outside the buffers.
+ *   append     fasn_kv{cache,prefill}_fp8_append: code = rne_e4m3(clamp(float(x) / s, -448, 448)), s the scale of the row's (b, hkv), the
+ *              division correctly rounded in fp32, NaN -> a NaN code; rows, positions and the dropping beyond the capacity as
+ *              fasn_kv{cache,prefill}_append.
+ *   the rest   visibility, len_b / qlen_b, seqlen_add, softmax_n and `n`, the sink on split 0, lse, rows that see nothing, the
+ *              stale-memory rules (rows at or beyond len_b may hold any byte, 0x7f included), the split rule and the workspace size are
+ *              the base call's: fasn_fwd_kv{cache,prefill}_fp8_workspace_bytes, the *_fp8_plan calls write the launches as text.
+ * Every rule and error code of the base call holds and is checked first; then fp8 == NULL, a NULL scale or reserved != 0 is FASN_EINVAL,
+ * D other than 64 / 128 FASN_EHEADDIM, a scale pointer off 4 bytes or a cache stride that is not a multiple of 16 (bytes) FASN_EALIGN, a
+ * negative or overflowing scale stride FASN_EINVAL. Not here: ALiBi, windows, rotary appends, packed queries, trees, e5m2, gradients.
+ */
+typedef struct fasn_kv_fp8 {
+    const float* k_scale;        /* DEVICE */
+    const float* v_scale;        /* DEVICE */
+    int64_t k_sb;                /* element strides (batch, K/V head) */
+    int64_t k_sh;
+    int64_t v_sb;
+    int64_t v_sh;
+    int32_t reserved;            /* 0 */
+} fasn_kv_fp8;
+
+size_t fasn_fwd_kvcache_fp8_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8);
+int fasn_fwd_kvcache_fp8(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvcache_fp8_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, char* buf, size_t cap);
+int fasn_kvcache_fp8_append(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_view4* k_new, const fasn_view4* v_new,
+                            fasn_stream_t stream);
+size_t fasn_fwd_kvprefill_fp8_workspace_bytes(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8);
+int fasn_fwd_kvprefill_fp8(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvprefill_fp8_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, char* buf, size_t cap);
+int fasn_kvprefill_fp8_append(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_view4* k_new, const fasn_view4* v_new,
+                              fasn_stream_t stream);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).
