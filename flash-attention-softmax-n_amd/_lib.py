@@ -39,6 +39,9 @@ EXPORTS = (
     "fasn_kvcache_tree_rope_append", "fasn_kvprefill_tree_rope_append", "fasn_kvcache_tree_commit",
     "fasn_fwd_kvcache_fp8_workspace_bytes", "fasn_fwd_kvcache_fp8", "fasn_kvcache_fp8_plan", "fasn_kvcache_fp8_append",
     "fasn_fwd_kvprefill_fp8_workspace_bytes", "fasn_fwd_kvprefill_fp8", "fasn_kvprefill_fp8_plan", "fasn_kvprefill_fp8_append",
+    "fasn_fwd_kvcache_fp8_window_workspace_bytes", "fasn_fwd_kvcache_fp8_window", "fasn_kvcache_fp8_window_plan",
+    "fasn_fwd_kvprefill_fp8_window_workspace_bytes", "fasn_fwd_kvprefill_fp8_window", "fasn_kvprefill_fp8_window_plan",
+    "fasn_kvcache_fp8_rope_append", "fasn_kvprefill_fp8_rope_append", "fasn_kvcache_fp8_rope_append_plan", "fasn_kvprefill_fp8_rope_append_plan",
 )
 
 
@@ -148,7 +151,7 @@ _lib = None
 
 
 def _kv_bindings():
-    """(name, restype, argtypes) of the 48 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
+    """(name, restype, argtypes) of the 58 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
     block (fasn_kvprefill_args), `operands` come between the block and the tail; then the nine of the packed block (fasn_kvvarlen_args)
     and the commit of a token tree, which has a block of its own"""
     view, text = POINTER(View4), [c_char_p, c_size_t]
@@ -175,7 +178,12 @@ def _kv_bindings():
                 (f"fasn_fwd_{stem}_fp8_workspace_bytes", c_size_t, [POINTER(KvFp8)], []),
                 (f"fasn_fwd_{stem}_fp8", c_int32, [POINTER(KvFp8)], forward),
                 (f"fasn_{stem}_fp8_plan", c_int32, [POINTER(KvFp8)], text),
-                (f"fasn_{stem}_fp8_append", c_int32, [POINTER(KvFp8), view, view], launch)):
+                (f"fasn_{stem}_fp8_append", c_int32, [POINTER(KvFp8), view, view], launch),
+                (f"fasn_fwd_{stem}_fp8_window_workspace_bytes", c_size_t, [POINTER(KvFp8), POINTER(KvWindow)], []),
+                (f"fasn_fwd_{stem}_fp8_window", c_int32, [POINTER(KvFp8), POINTER(KvWindow)], forward),
+                (f"fasn_{stem}_fp8_window_plan", c_int32, [POINTER(KvFp8), POINTER(KvWindow)], text),
+                (f"fasn_{stem}_fp8_rope_append", c_int32, [POINTER(KvFp8)] + rope, launch),
+                (f"fasn_{stem}_fp8_rope_append_plan", c_int32, [POINTER(KvFp8)] + rope, text)):
             yield name, restype, [block] + operands + tail
     packed = [POINTER(KvVarlenArgs)]
     yield "fasn_fwd_kvvarlen_workspace_bytes", c_size_t, packed
@@ -345,6 +353,19 @@ def kvfp8_plan(args, fp8):
     """The kernels fasn_fwd_kvcache_fp8 (`args` a KvCacheArgs) or fasn_fwd_kvprefill_fp8 (a KvPrefillArgs) would launch under `fp8` (a
     KvFp8), as launch_plan returns them. Nothing is launched."""
     return _kv_plan("fasn_kvprefill_fp8_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_plan", args, fp8)
+
+
+def kvfp8_window_plan(args, fp8, win):
+    """The kernels fasn_fwd_kvcache_fp8_window (`args` a KvCacheArgs) or fasn_fwd_kvprefill_fp8_window (a KvPrefillArgs) would launch under
+    `fp8` (a KvFp8) and `win` (a KvWindow), as launch_plan returns them. Nothing is launched."""
+    return _kv_plan("fasn_kvprefill_fp8_window_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_window_plan", args, fp8, win)
+
+
+def kvfp8_rope_plan(args, fp8, rope, q_out, k_new=None, v_new=None):
+    """The one launch of fasn_kvcache_fp8_rope_append (`args` a KvCacheArgs) or fasn_kvprefill_fp8_rope_append (a KvPrefillArgs) under `fp8`
+    (a KvFp8) and `rope` (a KvRope), as launch_plan returns it. Nothing is launched."""
+    what = "fasn_kvprefill_fp8_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_rope_append_plan"
+    return _kv_plan(what, args, fp8, rope, q_out, k_new, v_new)
 
 
 def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):

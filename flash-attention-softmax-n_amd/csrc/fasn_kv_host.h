@@ -34,7 +34,12 @@ struct KvFwd {
     KvWindow kw;
     KvPacked pk;          // KV_VARLEN only
     KvTree kt;            // KV_TREE only
-    KvFp8 f8;             // KV_FP8 only
+    KvFp8 f8;             // KV_FP8 and KV_FP8_WINDOW (which fills kw too)
+};
+// the operand of KV_FP8_WINDOW: the two operands its entry points take, checked in this order
+struct KvFp8Window {
+    const fasn_kv_fp8* fp8;
+    const fasn_kv_window* window;
 };
 
 inline bool kv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

@@ -214,6 +214,12 @@ int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, K
         if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
         return kv_check_fp8(in.a, static_cast<const fasn_kv_fp8*>(operand), f.f8);
     }
+    if (variant == KV_FP8_WINDOW) {   // the FP8 operand's checks, then the window's rule and its plan: the 16-bit window call's
+        if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
+        const KvFp8Window* const o = static_cast<const KvFp8Window*>(operand);
+        if ((rc = kv_check_fp8(in.a, o->fp8, f.f8))) return rc;
+        return kv_build_window(in.a, o->window, (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kw);
+    }
     if (variant == KV_TREE) {   // (decode and prefill only: there is no packed tree call)
         if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
         return kv_build_tree(in.a, static_cast<const fasn_kv_tree*>(operand), (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kt);

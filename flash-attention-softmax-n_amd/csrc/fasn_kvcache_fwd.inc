@@ -6,8 +6,18 @@
 // FASN_KV_FP8 = 1 (fasn_kvfp8.h, with the other three at 0; undefined counts as 0) is the sibling over a cache of e4m3fn codes (KvFp8): a tile
 // is staged as D-byte rows, widened by all four waves into the 16-bit tile image the fragment reads take, and k_scale rides in the score
 // factor. With FASN_KV_FP8 == 0 the four kernels above are what they were.
-template <typename Tag, int D>
+// FASN_KV_FP8 is orthogonal to FASN_KV_WINDOW: both at 1 (fasn_kvfp8.h) is the sliding-window sibling over the FP8 cache - the window's tile
+// range, full-tile test and one-compare mask around the FP8 staging and widening. The score factor has ONE name for that, FASN_KV_SC:
+// c8 under FASN_KV_FP8, p.c otherwise (a macro, so that the kernels that were there keep their tokens).
 #if FASN_KV_FP8
+#define FASN_KV_SC c8
+#else
+#define FASN_KV_SC p.c
+#endif
+template <typename Tag, int D>
+#if FASN_KV_FP8 && FASN_KV_WINDOW
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_window_kernel(const KvParams p, const KvFp8 f8, const KvWindow win) {
+#elif FASN_KV_FP8
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_kernel(const KvParams p, const KvFp8 f8) {
 #elif FASN_KV_TREE
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_tree_kernel(const KvParams p, const KvTree tree) {
@@ -247,10 +257,8 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
                     for (int r = 0; r < 16; ++r) {
 #if FASN_KV_ALIBI
                         sacc[kb][r] = __builtin_fmaf(sacc[kb][r], p.c, kv_alibi_term(nslope2, dk0, kb, r));
-#elif FASN_KV_FP8
-                        sacc[kb][r] *= c8;
 #else
-                        sacc[kb][r] *= p.c;
+                        sacc[kb][r] *= FASN_KV_SC;
 #endif
                         mx = fmaxf(mx, sacc[kb][r]);
                     }
@@ -288,11 +296,9 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
 #elif FASN_KV_ALIBI
                         const float y = key <= vis ? __builtin_fmaf(sacc[kb][r], p.c, kv_alibi_term(nslope2, dk0, kb, r)) : -INFINITY;
 #elif FASN_KV_WINDOW
-                        const float y = (unsigned)(dvis - (kb * 32 + (r & 3) + 8 * (r >> 2))) < (unsigned)win.w ? sacc[kb][r] * p.c : -INFINITY;
-#elif FASN_KV_FP8
-                        const float y = key <= vis ? sacc[kb][r] * c8 : -INFINITY;
+                        const float y = (unsigned)(dvis - (kb * 32 + (r & 3) + 8 * (r >> 2))) < (unsigned)win.w ? sacc[kb][r] * FASN_KV_SC : -INFINITY;
 #else
-                        const float y = key <= vis ? sacc[kb][r] * p.c : -INFINITY;
+                        const float y = key <= vis ? sacc[kb][r] * FASN_KV_SC : -INFINITY;
 #endif
                         sacc[kb][r] = y;
                         mx = fmaxf(mx, y);
@@ -359,3 +365,4 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
             }
     }
 }
+#undef FASN_KV_SC

@@ -5,6 +5,8 @@
 //   fasn_kvcache_fwd_fp8_kernel / fasn_kvprefill_fwd_fp8_kernel   one more inclusion each of the forward texts under FASN_KV_FP8
 //   fasn_kvcache_fp8_combine_kernel / fasn_kvprefill_fp8_combine_kernel   the combine kernels with v_scale in front of the one rounding
 //   fasn_kvcache_fp8_append_kernel / fasn_kvprefill_fp8_append_kernel   k_new / v_new rows, quantised, -> the cache rows behind the lengths
+//   fasn_kvcache_fwd_fp8_window_kernel / fasn_kvprefill_fwd_fp8_window_kernel   the sliding-window siblings: FASN_KV_FP8 with FASN_KV_WINDOW
+//   fasn_kvrope_fp8_kernel   fasn_kvrope_kernel in front of this cache: rotate, round to the 16-bit type, quantise, append (and rotate q)
 //
 // Semantics. value(code) = up(code) * scale[b, hkv], up() the exact upcast. All 254 finite codes are bf16 AND fp16 numbers, so the operands
 // of the 16-bit MFMAs are the codes themselves and the scales act in fp32:
@@ -19,6 +21,7 @@
 // 2 x 2 x 8 KiB + 2 x 16 KiB = 64 KiB - two workgroups per CU, as the 16-bit kernels.
 #pragma once
 #include "fasn_kvprefill.h"
+#include "fasn_kvrope.h"
 
 namespace fasn {
 
@@ -54,6 +57,14 @@ FASN_DEV void kv_fp8_widen(const char* src, char* img, int tid) {
 #define FASN_KV_FP8 1
 #include "fasn_kvcache_fwd.inc"
 #include "fasn_kvprefill_fwd.inc"
+// fasn_kvcache_fwd_fp8_window_kernel / fasn_kvprefill_fwd_fp8_window_kernel(..., KvFp8, KvWindow): the sliding-window siblings, the product
+// of the two switches. From the window kernels: tlo, the split of [tlo, tiles_b) - tiles below tlo get no request and no table read -
+// the full-tile test and the one-compare mask on a per-tile opaque dvis. From the FP8 kernels: everything above. Same LDS, same grid
+// rule as the 16-bit window kernels; the FP8 combine kernels below serve both.
+#define FASN_KV_WINDOW 1
+#include "fasn_kvcache_fwd.inc"
+#include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_WINDOW
 #undef FASN_KV_FP8
 
 // fasn_kvcache_combine_kernel with v_scale[b, hkv] on the normalised fp32 row, in front of its one rounding
@@ -200,5 +211,81 @@ template <typename Tag, int D>
 __global__ void __launch_bounds__(256) fasn_kvprefill_fp8_append_kernel(const KvPrefillParams pp, const KvFp8 f8) {
     kv_fp8_append<Tag, D, true>(pp.kv, pp.qlens, f8);
 }
+
+// ---- rotate-quantise-append
+// 8 elements of the call's 16-bit type, as one 16-byte register value -> 8 codes: kv_fp8_quant16's arithmetic on values that are in
+// registers already (the rotated key, rounded once to the 16-bit type)
+template <typename E>
+FASN_DEV u32x2 kv_fp8_quant8(u32x4 raw, float s) {
+    float x[8];
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        x[2 * w] = kv_fp8_prep(E::to_f32((uint16_t)(raw[w] & 0xffffu)), s);
+        x[2 * w + 1] = kv_fp8_prep(E::to_f32((uint16_t)(raw[w] >> 16)), s);
+    }
+    u32x2 out;
+#pragma unroll
+    for (int w = 0; w < 2; ++w) {
+        int pk = 0;
+        pk = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * w], x[4 * w + 1], pk, false);
+        pk = __builtin_amdgcn_cvt_pk_fp8_f32(x[4 * w + 2], x[4 * w + 3], pk, true);
+        out[w] = (uint32_t)pk;
+    }
+    return out;
+}
+
+// fasn_kvrope_kernel (fasn_kvrope.h) in front of an FP8 cache: the same lanes, grid, positions, dropped rows and table handling, and the
+// same unit text for the rotation. A query unit is that kernel's: 16-bit in, 16-bit q_out. A K/V unit addresses the cache in BYTES: its
+// 16 key elements are rotated and rounded ONCE to the call's 16-bit type - the key the 16-bit kernel would have stored - and those 16-bit
+// values are quantised as kv_fp8_quant16 quantises k_new, so a rotated key has one definition across both cache types and the call is
+// "eager rotation, then fasn_kv*_fp8_append" byte for byte. Chunk c of a row (16 bytes of 16-bit elements) is the 8 codes at byte 8 c:
+// two 8-byte stores where the 16-bit kernel has two 16-byte stores; units at or beyond rotary_dim are quantised, not copied. The unit's
+// 16 v_new elements are quantised with v_scale and stored as one 16-byte group. No tree variant.
+#define FASN_KVROPE_FP8 1
+template <typename Tag, int D>
+__global__ void __launch_bounds__(256) fasn_kvrope_fp8_kernel(const KvRopeParams rp, const KvFp8 f8) {
+    using E = ET<Tag>;
+    const KvParams& p = rp.kv;
+    constexpr int UPR = D / 16;   // units per row
+    int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= rp.nkv + rp.nq) return;
+    const bool isq = gid >= rp.nkv;
+    if (isq) gid -= rp.nkv;
+    const int u = (int)(gid % UPR);
+    int64_t rest = gid / UPR;
+    const int i = (int)(rest % p.Sq);
+    rest /= p.Sq;
+    const int heads = isq ? p.H : p.Hkv;
+    const int h = (int)(rest % heads), b = (int)(rest / heads);
+    int qlen = p.Sq;
+    if (rp.qlens != nullptr) qlen = min(max(rp.qlens[b], 0), p.Sq);
+    if (i >= qlen) return;   // padding rows: neither read nor written
+    int64_t pos;
+    const char* src;
+    char* dst = nullptr;    // a query unit's row of q_out (16-bit)
+    char* dst8 = nullptr;   // a K/V unit's row of the code cache
+    float ksc = 1.f;
+    if (!isq) {
+        pos = (int64_t)p.seqlens[b] + i;
+        if (pos < 0 || pos >= p.capacity) return;   // dropped: the host does not know the lengths
+        const int slot = (int)(pos / p.page_size), rip = (int)(pos % p.page_size);
+        const int64_t page = p.bt != nullptr ? p.bt[(int64_t)b * p.bts + slot] : b;
+        src = p.kn + (b * p.kns[0] + h * p.kns[1] + (int64_t)i * p.kns[2]) * 2;
+        dst8 = p.k + page * p.kps + (int64_t)rip * p.krs + (int64_t)h * p.khs;
+        ksc = f8.ks[b * f8.ksb + h * f8.ksh];
+        const u32x4 vx = kv_fp8_quant16<E>(p.vn + (b * p.vns[0] + h * p.vns[1] + (int64_t)i * p.vns[2]) * 2 + u * 32, f8.vs[b * f8.vsb + h * f8.vsh]);
+        gstore16(p.v + page * p.vps + (int64_t)rip * p.vrs + (int64_t)h * p.vhs + u * 16, vx);
+    } else {
+        // len_b per lane, as in fasn_kvrope_kernel
+        int len;
+        if (rp.add_qlen < 0) len = min(max(p.seqlens[b] + p.seqlen_add, 0), p.capacity);
+        else len = (int)min(max((int64_t)p.seqlens[b] + (rp.add_qlen ? qlen : 0), (int64_t)0), (int64_t)p.capacity);
+        pos = (int64_t)i + len - qlen;
+        src = p.q + (b * p.qs[0] + h * p.qs[1] + (int64_t)i * p.qs[2]) * 2;
+        dst = rp.qo + (b * rp.qos[0] + h * rp.qos[1] + (int64_t)i * rp.qos[2]) * 2;
+    }
+#include "fasn_kvrope_unit.inc"
+}
+#undef FASN_KVROPE_FP8
 
 }  // namespace fasn

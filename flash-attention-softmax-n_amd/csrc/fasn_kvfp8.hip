@@ -1,6 +1,7 @@
-// FP8 K/V cache (include/fasn.h: fasn_fwd_kvcache_fp8, fasn_fwd_kvprefill_fp8, their *_workspace_bytes, *_plan and *_append calls): the
-// entry points and the launches of fasn_kvfp8.h. The argument checks, the FP8 operand's check, the launch plan and the workspace rule are
-// the family's (fasn_kv_host.h, defined in fasn_kvcache.hip), called here with a decode or a prefill block.
+// FP8 K/V cache (include/fasn.h: fasn_fwd_kvcache_fp8, fasn_fwd_kvprefill_fp8, their *_workspace_bytes, *_plan and *_append calls, and the
+// *_fp8_window siblings of the forwards): the entry points and the launches of fasn_kvfp8.h (its rotate-quantise-append is launched from
+// fasn_kvrope.hip, beside the rope operand's checks). The argument checks, the FP8 operand's check, the window's rule, the launch plan and
+// the workspace rule are the family's (fasn_kv_host.h, defined in fasn_kvcache.hip), called here with a decode or a prefill block.
 #include <limits.h>
 #include "fasn_kv_host.h"
 #include "fasn_kvfp8.h"
@@ -15,17 +16,24 @@ int kv8_dispatch(int dtype, int D, F f) {
     return D == 64 ? f(f16_tag{}, std::integral_constant<int, 64>{}) : f(f16_tag{}, std::integral_constant<int, 128>{});
 }
 
-template <auto Kern, typename P>
+// the forward of f.variant: the FP8 kernel, or its sliding-window sibling on the same LDS
+template <auto Kern, auto Window, typename P>
 void kv8_launch_fwd(const KvFwd& f, const P& p, unsigned grid, int smem, hipStream_t s) {
-    ensure_smem<Kern>(smem);
-    FASN_LAUNCH(Kern, dim3(grid), dim3(256), smem, s, p, f.f8);
+    if (f.variant == KV_FP8_WINDOW) {
+        ensure_smem<Window>(smem);
+        FASN_LAUNCH(Window, dim3(grid), dim3(256), smem, s, p, f.f8, f.kw);
+    } else {
+        ensure_smem<Kern>(smem);
+        FASN_LAUNCH(Kern, dim3(grid), dim3(256), smem, s, p, f.f8);
+    }
 }
 
 // decode: the forward and, always, the combine
 template <typename Tag, int D>
 int kv8_decode(const KvFwd& f, hipStream_t s) {
     const KvParams& p = f.pp.kv;
-    kv8_launch_fwd<&fasn_kvcache_fwd_fp8_kernel<Tag, D>>(f, p, (unsigned)(p.B * p.Hkv * p.nsplit), kv_fp8_smem(D), s);
+    const unsigned grid = (unsigned)(p.B * p.Hkv * p.nsplit);
+    kv8_launch_fwd<&fasn_kvcache_fwd_fp8_kernel<Tag, D>, &fasn_kvcache_fwd_fp8_window_kernel<Tag, D>>(f, p, grid, kv_fp8_smem(D), s);
     const int64_t nthr = (int64_t)p.B * p.Hkv * p.R * (D / 4);
     FASN_LAUNCH((fasn_kvcache_fp8_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p, f.f8);
     return launch_rc();
@@ -35,7 +43,8 @@ template <typename Tag, int D>
 int kv8_prefill(const KvFwd& f, hipStream_t s) {
     const KvPrefillParams& pp = f.pp;
     const KvParams& p = pp.kv;
-    kv8_launch_fwd<&fasn_kvprefill_fwd_fp8_kernel<Tag, D>>(f, pp, (unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit), kv_fp8_smem(D), s);
+    const unsigned grid = (unsigned)(p.B * p.Hkv * pp.nrb * p.nsplit);
+    kv8_launch_fwd<&fasn_kvprefill_fwd_fp8_kernel<Tag, D>, &fasn_kvprefill_fwd_fp8_window_kernel<Tag, D>>(f, pp, grid, kv_fp8_smem(D), s);
     if (p.nsplit > 1) {
         const int64_t nthr = (int64_t)p.B * p.Hkv * pp.nrb * KVP_ROWS * (D / 4);
         FASN_LAUNCH((fasn_kvprefill_fp8_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, pp, f.f8);
@@ -43,11 +52,14 @@ int kv8_prefill(const KvFwd& f, hipStream_t s) {
     return launch_rc();
 }
 
+// `windowed`: the *_fp8_window calls (a NULL window operand of theirs is refused by the window's rule, not taken for "no window")
 template <typename Args>
-int kv8_forward(const Args* args, const fasn_kv_fp8* fp8, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+int kv8_forward(const Args* args, const fasn_kv_fp8* fp8, void* workspace, size_t workspace_bytes, fasn_stream_t stream, bool windowed = false,
+                const fasn_kv_window* window = nullptr) {
     KvFwd f;
     const KvArgs in = kv_args(args);
-    const int rc = kv_build_forward(in, KV_FP8, fp8, workspace, workspace_bytes, f);
+    const KvFp8Window both{fp8, window};
+    const int rc = windowed ? kv_build_forward(in, KV_FP8_WINDOW, &both, workspace, workspace_bytes, f) : kv_build_forward(in, KV_FP8, fp8, workspace, workspace_bytes, f);
     if (rc) return rc;
     return kv8_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) {
         if (in.call == KV_DECODE) return kv8_decode<decltype(tag), decltype(d)::value>(f, (hipStream_t)stream);
@@ -76,8 +88,13 @@ int kv8_append(const Args* args, const fasn_kv_fp8* fp8, const fasn_view4* k_new
 }
 
 template <typename Args>
-int kv8_plan(const Args* args, const fasn_kv_fp8* fp8, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kv8_forward(args, fp8, kv_plan_workspace(), ~size_t(0), nullptr); });
+int kv8_plan(const Args* args, const fasn_kv_fp8* fp8, char* buf, size_t cap, bool windowed = false, const fasn_kv_window* window = nullptr) {
+    return kv_plan(buf, cap, [&] { return kv8_forward(args, fp8, kv_plan_workspace(), ~size_t(0), nullptr, windowed, window); });
+}
+template <typename Args>
+size_t kv8_window_workspace_bytes(const Args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window) {
+    const KvFp8Window both{fp8, window};
+    return kv_workspace_bytes(kv_args(args), KV_FP8_WINDOW, &both);
 }
 
 }  // namespace
@@ -109,6 +126,33 @@ int fasn_kvprefill_fp8_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* 
 
 int fasn_kvprefill_fp8_append(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
     return kv8_append(args, fp8, k_new, v_new, stream);
+}
+
+// ---- the sliding window over an FP8 cache: the FP8 operand's checks, then the window's rule and the 16-bit window call's plan
+size_t fasn_fwd_kvcache_fp8_window_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window) {
+    return kv8_window_workspace_bytes(args, fp8, window);
+}
+
+int fasn_fwd_kvcache_fp8_window(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, void* workspace, size_t workspace_bytes,
+                                fasn_stream_t stream) {
+    return kv8_forward(args, fp8, workspace, workspace_bytes, stream, true, window);
+}
+
+int fasn_kvcache_fp8_window_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, char* buf, size_t cap) {
+    return kv8_plan(args, fp8, buf, cap, true, window);
+}
+
+size_t fasn_fwd_kvprefill_fp8_window_workspace_bytes(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window) {
+    return kv8_window_workspace_bytes(args, fp8, window);
+}
+
+int fasn_fwd_kvprefill_fp8_window(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, void* workspace, size_t workspace_bytes,
+                                  fasn_stream_t stream) {
+    return kv8_forward(args, fp8, workspace, workspace_bytes, stream, true, window);
+}
+
+int fasn_kvprefill_fp8_window_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, char* buf, size_t cap) {
+    return kv8_plan(args, fp8, buf, cap, true, window);
 }
 
 }  // extern "C"

@@ -10,9 +10,17 @@
 // every row block walks to len_b, because a node may see any node. With FASN_KV_TREE == 0 the kernels above are what they were.
 // FASN_KV_FP8 = 1 (fasn_kvfp8.h, with the other four at 0; undefined counts as 0) is the sibling over a cache of e4m3fn codes (fasn_kvcache.h:
 // KvFp8; fasn_kvcache_fwd.inc: staging, widening pass); v_scale multiplies the one-split direct store. With FASN_KV_FP8 == 0 the kernels
-// above are what they were.
-template <typename Tag, int D>
+// above are what they were. FASN_KV_FP8 = 1 with FASN_KV_WINDOW = 1 (fasn_kvfp8.h) is the sliding-window sibling over the FP8 cache: the
+// window blocks of the body are orthogonal to the FP8 blocks. FASN_KV_SC is the score factor's one name (fasn_kvcache_fwd.inc).
 #if FASN_KV_FP8
+#define FASN_KV_SC c8
+#else
+#define FASN_KV_SC p.c
+#endif
+template <typename Tag, int D>
+#if FASN_KV_FP8 && FASN_KV_WINDOW
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_fp8_window_kernel(const KvPrefillParams pp, const KvFp8 f8, const KvWindow win) {
+#elif FASN_KV_FP8
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_fp8_kernel(const KvPrefillParams pp, const KvFp8 f8) {
 #elif FASN_KV_TREE
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_tree_kernel(const KvPrefillParams pp, const KvTree tree) {
@@ -316,11 +324,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
-#if FASN_KV_FP8
-                    for (int r = 0; r < 16; ++r) sacc[kb][r] *= c8;
-#else
-                    for (int r = 0; r < 16; ++r) sacc[kb][r] *= p.c;
-#endif
+                    for (int r = 0; r < 16; ++r) sacc[kb][r] *= FASN_KV_SC;
             }
 #endif
             // raw scores (times ce: log2 domain); hidden keys (beyond the row's limit, which is below len_b) go to -inf
@@ -465,3 +469,4 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_kerne
             }
     }
 }
+#undef FASN_KV_SC

@@ -1,9 +1,13 @@
 // Rotary rotate-and-append on the K/V-cache calls (include/fasn.h: fasn_kvcache_rope_append, fasn_kvprefill_rope_append,
-// fasn_kvvarlen_rope_append and their *_plan siblings, fasn_kvcache_tree_rope_append / fasn_kvprefill_tree_rope_append): the base call's argument checks first (the family's, fasn_kv_host.h), then the operand's, which live here, and the
-// one launch of fasn_kvrope.h - whose grid depends on shapes only, never on the lengths in device memory.
+// fasn_kvvarlen_rope_append and their *_plan siblings, fasn_kvcache_tree_rope_append / fasn_kvprefill_tree_rope_append, and
+// fasn_kvcache_fp8_rope_append / fasn_kvprefill_fp8_rope_append with their *_plan siblings - the rotate-quantise-append in front of an FP8
+// cache, whose FP8 operand is checked behind the base arguments and in front of the rope operand): the base call's argument checks first
+// (the family's, fasn_kv_host.h), then the operand's, which live here, and the one launch of fasn_kvrope.h (the FP8 sibling: of
+// fasn_kvfp8.h) - whose grid depends on shapes only, never on the lengths in device memory.
 #include <limits.h>
 #include "fasn_kv_host.h"
 #include "fasn_kvrope.h"
+#include "fasn_kvfp8.h"
 
 namespace fasn {
 namespace {
@@ -59,6 +63,17 @@ int kvr_launch_packed(const KvRopeParams& rp, const KvPacked& pk, hipStream_t s)
     return launch_rc();
 }
 
+// the rotate-quantise-append of fasn_kvfp8.h, at the two head dims the FP8 kernels are built for (kv_check_fp8 let only these through)
+template <typename Tag, int D>
+int kvr_launch_fp8(const KvRopeParams& rp, const KvFp8& f8, hipStream_t s) {
+    FASN_LAUNCH((fasn_kvrope_fp8_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, f8);
+    return launch_rc();
+}
+template <typename Tag>
+int kvr_launch_fp8_d(int D, const KvRopeParams& rp, const KvFp8& f8, hipStream_t s) {
+    return D == 64 ? kvr_launch_fp8<Tag, 64>(rp, f8, s) : kvr_launch_fp8<Tag, 128>(rp, f8, s);
+}
+
 // `tree`: the *_tree_rope_append calls (the rotation at depth positions); its operand is checked behind the rope operand
 int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream,
              bool tree = false, const fasn_kv_tree* tree_operand = nullptr) {
@@ -81,6 +96,23 @@ int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out
     if (packed)
         return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch_packed<decltype(tag), decltype(d)::value>(rp, pk, (hipStream_t)stream); });
     return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch<decltype(tag), decltype(d)::value>(rp, (hipStream_t)stream); });
+}
+
+// the *_fp8_rope_append calls: the base checks, the FP8 operand's (kv_check_fp8), the rope operand's (kvr_build), one launch on the grid
+// of the 16-bit rope append. Decode and prefill only.
+int kvr_call_fp8(const KvArgs& in, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
+                 fasn_stream_t stream) {
+    KvPrefillParams pp;
+    int rc = kv_build(in, pp);
+    if (rc) return rc;
+    KvFp8 f8{};
+    if ((rc = kv_check_fp8(in.a, fp8, f8))) return rc;
+    KvRopeParams rp{};
+    rp.kv = pp.kv;
+    rp.qlens = pp.qlens;
+    if ((rc = kvr_build(in.a, in.call != KV_DECODE, (int64_t)pp.kv.B * pp.kv.Sq, rope, q_out, k_new, v_new, rp))) return rc;
+    if (in.a->dtype == FASN_DTYPE_BF16) return kvr_launch_fp8_d<bf16_tag>(in.a->D, rp, f8, (hipStream_t)stream);
+    return kvr_launch_fp8_d<f16_tag>(in.a->D, rp, f8, (hipStream_t)stream);
 }
 
 }  // namespace
@@ -128,6 +160,26 @@ int fasn_kvvarlen_rope_append(const fasn_kvvarlen_args* args, const fasn_kv_rope
 int fasn_kvvarlen_rope_append_plan(const fasn_kvvarlen_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                                    const fasn_view4* v_new, char* buf, size_t cap) {
     return kv_plan(buf, cap, [&] { return kvr_call(kv_args(args), rope, q_out, k_new, v_new, nullptr); });
+}
+
+int fasn_kvcache_fp8_rope_append(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                 const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
+    return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, stream);
+}
+
+int fasn_kvprefill_fp8_rope_append(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                   const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
+    return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, stream);
+}
+
+int fasn_kvcache_fp8_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                      const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr); });
+}
+
+int fasn_kvprefill_fp8_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                        const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr); });
 }
 
 }  // extern "C"

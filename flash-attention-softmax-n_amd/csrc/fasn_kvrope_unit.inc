@@ -4,13 +4,25 @@
 //   Tag, rp (KvRopeParams), u (the lane's unit), src / dst (the row's first byte in the source and the destination), pos (its position).
 // Chunks c1 / c2 of src go to dst: rotated at table row clamp(pos, 0, rows - 1) when u is a rotated unit, copied otherwise. The kernel
 // ends here.
+// FASN_KVROPE_FP8 = 1 (fasn_kvfp8.h: fasn_kvrope_fp8_kernel; undefined counts as 0): a K/V unit (!isq) stores chunk c - the 16-bit values
+// every other kernel stores - as their 8 e4m3fn codes under the scale `ksc` at byte 8 c of the code row `dst8`; E = ET<Tag> is in scope
+// too. The store has one name for that; with FASN_KVROPE_FP8 == 0 it is the 16-byte store it was, token for token.
+#if FASN_KVROPE_FP8
+#define FASN_KVROPE_STORE(c, x)                                        \
+    do {                                                               \
+        if (isq) gstore16(dst + c * 16, x);                            \
+        else gstore8(dst8 + c * 8, kv_fp8_quant8<E>(x, ksc));          \
+    } while (0)
+#else
+#define FASN_KVROPE_STORE(c, x) gstore16(dst + c * 16, x)
+#endif
     const int ru = rp.rd / 16;   // rotated units
     const bool rot = u < ru;
     const int c1 = rot && !rp.interleaved ? u : 2 * u, c2 = rot && !rp.interleaved ? u + ru : 2 * u + 1;
     const u32x4 a = gload16(src + c1 * 16), bq = gload16(src + c2 * 16);
     if (!rot) {
-        gstore16(dst + c1 * 16, a);
-        gstore16(dst + c2 * 16, bq);
+        FASN_KVROPE_STORE(c1, a);
+        FASN_KVROPE_STORE(c2, bq);
         return;
     }
     const int64_t trow = min(max(pos, (int64_t)0), (int64_t)rp.rows - 1);
@@ -42,5 +54,6 @@
 #pragma unroll
         for (int j = 0; j < 8; ++j) e0[j] = y1[j], e1[j] = y2[j];
     }
-    gstore16(dst + c1 * 16, kvrope_round<Tag>(e0));
-    gstore16(dst + c2 * 16, kvrope_round<Tag>(e1));
+    FASN_KVROPE_STORE(c1, kvrope_round<Tag>(e0));
+    FASN_KVROPE_STORE(c2, kvrope_round<Tag>(e1));
+#undef FASN_KVROPE_STORE

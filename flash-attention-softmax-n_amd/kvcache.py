@@ -20,6 +20,8 @@ fasn_kv*_tree_rope_append): one int64 word per node on the device says which nod
 depth; flash_attention_n_kvcache_tree_commit moves the accepted path's cache rows behind the prefix (fasn_kvcache_tree_commit).
 flash_attention_n_kvcache_fp8 is the decode / prefill call over a cache of e4m3fn codes with per-(batch, K/V head) fp32 scales on the device
 (fasn_fwd_kvcache_fp8 / fasn_fwd_kvprefill_fp8, fasn_kv*_fp8_append): half the cache bytes per key, k_new / v_new quantised on the way in.
+flash_attention_n_kvcache_fp8_window is the sliding-window layer on that cache (fasn_fwd_kv*_fp8_window) and flash_attention_n_kvcache_fp8_rope
+the rotary call (fasn_kv*_fp8_rope_append: rotate, round to the 16-bit type, quantise, append - one launch), with or without a window.
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -287,8 +289,15 @@ def _on_device(dev, launch) -> None:
 
 def _append(lib, c, stream, rope=None, q_rot=None, tree=None, fp8=None) -> None:
     """k_new / v_new -> the cache rows behind the lengths; with `rope` the one launch that rotates them on the way and the queries into
-    `q_rot`, which the forward then reads - under `tree` at the nodes' depth positions; with `fp8` the launch that quantises them"""
-    if fp8 is not None:
+    `q_rot`, which the forward then reads - under `tree` at the nodes' depth positions; with `fp8` the launch that quantises them; with
+    `fp8` and `rope` the one launch that rotates, then quantises"""
+    if fp8 is not None and rope is not None:   # the rotate-quantise-append; without k_new / v_new it rotates the queries only
+        name = f"fasn_{c.stem}_fp8_rope_append"
+        kn_view = None if c.k_new is None else _view4(c.k_new)
+        vn_view = None if c.v_new is None else _view4(c.v_new)
+        _lib.check(getattr(lib, name)(c.args, fp8, rope, _view4(q_rot), kn_view, vn_view, stream), name)
+        c.kv.q = _view4(q_rot)
+    elif fp8 is not None:
         if c.k_new is not None:
             name = f"fasn_{c.stem}_fp8_append"
             _lib.check(getattr(lib, name)(c.args, fp8, _view4(c.k_new), _view4(c.v_new), stream), name)
@@ -306,9 +315,13 @@ def _append(lib, c, stream, rope=None, q_rot=None, tree=None, fp8=None) -> None:
 
 def _forward(lib, c, stream, win=None, tree=None, fp8=None) -> None:
     """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (c.alibi), of their window siblings (`win`),
-    of their token-tree siblings (`tree`, which carries its window) or of their FP8-cache siblings (`fp8`)"""
+    of their token-tree siblings (`tree`, which carries its window), of their FP8-cache siblings (`fp8`) or of the FP8 window siblings
+    (`fp8` and `win`)"""
     stem = c.stem
-    if fp8 is not None:
+    if fp8 is not None and win is not None:
+        name, operand = f"fasn_fwd_{stem}_fp8_window", (fp8, win)
+        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_fp8_window_workspace_bytes")(c.args, fp8, win)
+    elif fp8 is not None:
         name, operand = f"fasn_fwd_{stem}_fp8", (fp8,)
         ws_bytes = getattr(lib, f"fasn_fwd_{stem}_fp8_workspace_bytes")(c.args, fp8)
     elif tree is not None:
@@ -807,16 +820,20 @@ def flash_attention_n_kvcache_fp8(
     :param k_new, v_new: optional [B, Hkv, Sq, D] in query's dtype: rows i < qlen_b are QUANTISED and written to the cache positions
                   cache_seqlens[b] + i first - code = rne_e4m3(clamp(float(x) / s, -448, 448)), s the scale of (b, hkv), the division
                   correctly rounded in fp32, saturating, NaN -> a NaN code - and then attended to. `cache_seqlens` is not modified.
-    :param alibi_slopes, window, rotary_cos, rotary_sin, cu_seqlens_q, tree_mask: anything but None is refused here: the FP8 cache has
-                  the base kernels only.
+    :param alibi_slopes, window, rotary_cos, rotary_sin, cu_seqlens_q, tree_mask: anything but None is refused here. A sliding window
+                  and rotary embedding on an FP8 cache are calls of their own: flash_attention_n_kvcache_fp8_window,
+                  flash_attention_n_kvcache_fp8_rope. ALiBi, packed queries and token trees have 16-bit kernels only.
     :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32).
     """
     fn = "flash_attention_n_kvcache_fp8"
     for name, value in (("alibi_slopes", alibi_slopes), ("window", window), ("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin),
                         ("cu_seqlens_q", cu_seqlens_q), ("tree_mask", tree_mask)):
         if value is not None:
-            raise NotImplementedError(f"{fn}: {name} is not supported on an FP8 cache (no FP8 ALiBi, window, rotary, packed or tree kernels "
-                                      "yet); use a 16-bit cache with the call of that name")
+            if name in ("window", "rotary_cos", "rotary_sin"):
+                raise NotImplementedError(f"{fn}: {name} is not supported on an FP8 cache by this call; use flash_attention_n_kvcache_fp8_window "
+                                          "(a sliding window) or flash_attention_n_kvcache_fp8_rope (rotary embedding, with or without a window)")
+            raise NotImplementedError(f"{fn}: {name} is not supported on an FP8 cache (no FP8 ALiBi, packed or tree kernels yet); use a 16-bit "
+                                      "cache with the call of that name")
     _check_query_seqlens(fn, query_seqlens, query)
     _check_group_limit(fn, query, k_cache)
     Hkv = k_cache.shape[2] if k_cache.dim() == 4 and query.dim() == 4 else 1
@@ -826,6 +843,111 @@ def flash_attention_n_kvcache_fp8(
     c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
                  return_lse, query_seqlens=query_seqlens, by_shape=True, fp8=True)
     return _run(c, fp8_scales=scales)
+
+
+def _fp8_scales(fn, k_scale, v_scale, query, k_cache):
+    """both scales through _scale_tensor (malformed shapes are _prepare's to name)"""
+    if query.dim() != 4:
+        return None
+    Hkv = k_cache.shape[2] if k_cache.dim() == 4 else 1
+    return _scale_tensor(fn, "k_scale", k_scale, query, Hkv), _scale_tensor(fn, "v_scale", v_scale, query, Hkv)
+
+
+def flash_attention_n_kvcache_fp8_window(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        k_scale,
+        v_scale,
+        window: int,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        query_seqlens: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        return_lse: bool = False):
+    """softmax_n attention of a SLIDING-WINDOW layer against an FP8 K/V CACHE, on MI355X: flash_attention_n_kvcache_window's visibility and
+    memory contract over flash_attention_n_kvcache_fp8's cache - the sliding layers of GPT-OSS / Mistral keep the capacity gain, and the
+    pages below the window can still be freed.
+
+    Always causal. With qlen_b, len_b and p_i = i + len_b - qlen_b as in flash_attention_n_kvcache_window, position i < qlen_b sees key j
+    iff j < len_b and p_i - window < j <= p_i; the values, the scales, `k_new` / `v_new` (quantised on the way in), the caches' rules and the
+    refusals are those of flash_attention_n_kvcache_fp8, `query_seqlens` and the choice of kernels by shapes alone those of
+    flash_attention_n_kvcache_window. With power-of-two scales the result is, bit for bit, flash_attention_n_kvcache_window on
+    `k_cache.to(query.dtype)`; a window at or beyond the capacity sees what flash_attention_n_kvcache_fp8(is_causal=True) sees.
+
+    :param window: a Python int >= 1, a constant of the layer and part of a captured graph.
+    :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32).
+
+    Memory contract: flash_attention_n_kvcache_window's. With first_b = 64 * floor(max(0, len_b - qlen_b - window + 1) / 64), cache rows
+    j < first_b and the block-table entries of pages wholly below first_b are never read and may hold any byte. Nothing is read on the
+    host: the launches - those of flash_attention_n_kvcache_window for the same shapes and window - follow shapes, the capacity and
+    `window` only, so a captured graph follows `cache_seqlens`, `query_seqlens` and the scales.
+    """
+    fn = "flash_attention_n_kvcache_fp8_window"
+    _check_window(fn, window)
+    _check_query_seqlens(fn, query_seqlens, query)
+    _check_group_limit(fn, query, k_cache)
+    scales = _fp8_scales(fn, k_scale, v_scale, query, k_cache)
+    c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, True,
+                 return_lse, query_seqlens=query_seqlens, by_shape=True, fp8=True)
+    return _run(c, window=window, fp8_scales=scales)
+
+
+def flash_attention_n_kvcache_fp8_rope(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        k_scale,
+        v_scale,
+        rotary_cos: Tensor,
+        rotary_sin: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        query_seqlens: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False,
+        window: Optional[int] = None,
+        rotary_interleaved: bool = False):
+    """softmax_n attention against an FP8 K/V CACHE with ROTARY POSITION EMBEDDING applied to `query` and `k_new` on the way, on MI355X: one
+    step of a Llama / Mistral / GPT-OSS layer over the FP8 cache - rotate, quantise, append, attend - in the launches of
+    flash_attention_n_kvcache_fp8 with `k_new`.
+
+    ONE launch rotates row i < qlen_b of k_new[b] at position cache_seqlens[b] + i, rounds it once to query's dtype - the key
+    flash_attention_n_kvcache_rope would have stored - quantises THAT value with k_scale as flash_attention_n_kvcache_fp8 quantises k_new, and
+    writes the codes to the cache; quantises v_new beside it; and rotates query position i at p_i = i + len_b - qlen_b into a 16-bit
+    temporary the forward reads. So a rotated key has one definition across both cache types, and the call equals "rotate `query` and
+    `k_new` in eager torch, then flash_attention_n_kvcache_fp8 (or _fp8_window)" bit for bit. Positions, dropped rows, the tables
+    (`rotary_cos` / `rotary_sin`, `rotary_interleaved`: layouts, rotary_dim, rows >= capacity, the row clamp) and the rotation's
+    arithmetic are flash_attention_n_kvcache_rope's; the cache, the scales and the quantisation flash_attention_n_kvcache_fp8's.
+
+    :param k_new, v_new: optional. Without them only `query` is rotated, at p_i over the cache as it is.
+    :param window: None: flash_attention_n_kvcache_fp8's attention; a Python int >= 1: flash_attention_n_kvcache_fp8_window's (needs
+                  is_causal=True).
+    :return: as flash_attention_n_kvcache_fp8. `query`, `k_new`, `cache_seqlens` are not modified.
+
+    Nothing is read on the host: a captured graph follows `cache_seqlens`, `query_seqlens` and the scales. No ALiBi, no packed queries,
+    no token tree, no gradient.
+    """
+    fn = "flash_attention_n_kvcache_fp8_rope"
+    if window is not None:
+        _check_window(fn, window, or_none="None or ")
+        if not is_causal:
+            raise ValueError(f"{fn}: a sliding window is always causal; window={window} needs is_causal=True")
+    _check_rotary_tables(fn, rotary_cos, rotary_sin, query)
+    _check_query_seqlens(fn, query_seqlens, query)
+    _check_group_limit(fn, query, k_cache)
+    _check_rotary_fit(fn, rotary_cos, rotary_sin, query, k_cache, block_table)
+    scales = _fp8_scales(fn, k_scale, v_scale, query, k_cache)
+    c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
+                 return_lse, query_seqlens=query_seqlens, by_shape=True, fp8=True)
+    return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query), fp8_scales=scales)
 
 
 def _check_tree_mask(fn, tree_mask, query) -> Tensor:

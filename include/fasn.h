@@ -609,6 +609,40 @@ int fasn_kvprefill_fp8_append(const fasn_kvprefill_args* args, const fasn_kv_fp8
                               fasn_stream_t stream);
 
 /*
+ * FP8 K/V CACHE, THE LAYER (additions within ABI 6; no struct is new or changed): the sliding window and the rotary append over the FP8
+ * cache above - what a GPT-OSS / Mistral / Llama layer needs of it. Decode and prefill blocks only; a packed block has no such call.
+ *
+ *   window     fasn_fwd_kv{cache,prefill}_fp8_window: fasn_fwd_kv{cache,prefill}_window's visibility, tile walk and memory contract (rows
+ *              and block-table entries below the window's first tile are never read) with the FP8 call's values and scales. The plan
+ *              is the 16-bit window call's of the same shape and window - same grids, same workspace - with the FP8 kernels' LDS.
+ *              Checks: the base call's, then the FP8 operand's (as fasn_fwd_kv*_fp8), then the window's (window == NULL, window < 1 or
+ *              reserved != 0: FASN_EINVAL; a non-causal block: FASN_EUNSUPPORTED).
+ *   rope       fasn_kv{cache,prefill}_fp8_rope_append: fasn_kv{cache,prefill}_rope_append in front of an FP8 cache, ONE launch on the
+ *              same grid. q_out is that call's (16-bit). A key row is rotated and rounded once to `dtype` exactly as that call stores
+ *              it, and THAT value is quantised as fasn_kv*_fp8_append quantises k_new - code = rne_e4m3(clamp(float(x) / k_scale,
+ *              -448, 448)), NaN -> a NaN code - so the call equals "rotate in eager fp32 arithmetic, round to dtype, fasn_kv*_fp8_append"
+ *              byte for byte. Features at or beyond rotary_dim are quantised unrotated; v_new is quantised with v_scale. Positions,
+ *              dropped rows, padding rows and the table-row clamp are the 16-bit call's. k_new == v_new == NULL: queries only.
+ *              Checks: the base call's, then the FP8 operand's, then the rope operand's (as fasn_kv*_rope_append). No tree variant.
+ */
+size_t fasn_fwd_kvcache_fp8_window_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window);
+int fasn_fwd_kvcache_fp8_window(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, void* workspace,
+                                size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvcache_fp8_window_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, char* buf, size_t cap);
+size_t fasn_fwd_kvprefill_fp8_window_workspace_bytes(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window);
+int fasn_fwd_kvprefill_fp8_window(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, void* workspace,
+                                  size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvprefill_fp8_window_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, char* buf, size_t cap);
+int fasn_kvcache_fp8_rope_append(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                 const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvprefill_fp8_rope_append(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                   const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvcache_fp8_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                      const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
+int fasn_kvprefill_fp8_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                                        const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).
