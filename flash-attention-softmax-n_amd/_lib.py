@@ -42,6 +42,10 @@ EXPORTS = (
     "fasn_fwd_kvcache_fp8_window_workspace_bytes", "fasn_fwd_kvcache_fp8_window", "fasn_kvcache_fp8_window_plan",
     "fasn_fwd_kvprefill_fp8_window_workspace_bytes", "fasn_fwd_kvprefill_fp8_window", "fasn_kvprefill_fp8_window_plan",
     "fasn_kvcache_fp8_rope_append", "fasn_kvprefill_fp8_rope_append", "fasn_kvcache_fp8_rope_append_plan", "fasn_kvprefill_fp8_rope_append_plan",
+    "fasn_fwd_kvcache_fp8_tree_workspace_bytes", "fasn_fwd_kvcache_fp8_tree", "fasn_kvcache_fp8_tree_plan",
+    "fasn_fwd_kvprefill_fp8_tree_workspace_bytes", "fasn_fwd_kvprefill_fp8_tree", "fasn_kvprefill_fp8_tree_plan",
+    "fasn_kvcache_fp8_tree_rope_append", "fasn_kvprefill_fp8_tree_rope_append", "fasn_kvcache_fp8_tree_rope_append_plan",
+    "fasn_kvprefill_fp8_tree_rope_append_plan", "fasn_kvcache_fp8_tree_commit",
 )
 
 
@@ -151,9 +155,9 @@ _lib = None
 
 
 def _kv_bindings():
-    """(name, restype, argtypes) of the 58 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
+    """(name, restype, argtypes) of the 69 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
     block (fasn_kvprefill_args), `operands` come between the block and the tail; then the nine of the packed block (fasn_kvvarlen_args)
-    and the commit of a token tree, which has a block of its own"""
+    and the two commits of a token tree (16-bit and FP8 cache), which have a block of their own"""
     view, text = POINTER(View4), [c_char_p, c_size_t]
     launch = [c_void_p]                          # the stream
     forward = [c_void_p, c_size_t, c_void_p]     # workspace, its bytes, the stream
@@ -183,7 +187,12 @@ def _kv_bindings():
                 (f"fasn_fwd_{stem}_fp8_window", c_int32, [POINTER(KvFp8), POINTER(KvWindow)], forward),
                 (f"fasn_{stem}_fp8_window_plan", c_int32, [POINTER(KvFp8), POINTER(KvWindow)], text),
                 (f"fasn_{stem}_fp8_rope_append", c_int32, [POINTER(KvFp8)] + rope, launch),
-                (f"fasn_{stem}_fp8_rope_append_plan", c_int32, [POINTER(KvFp8)] + rope, text)):
+                (f"fasn_{stem}_fp8_rope_append_plan", c_int32, [POINTER(KvFp8)] + rope, text),
+                (f"fasn_fwd_{stem}_fp8_tree_workspace_bytes", c_size_t, [POINTER(KvFp8), POINTER(KvTree)], []),
+                (f"fasn_fwd_{stem}_fp8_tree", c_int32, [POINTER(KvFp8), POINTER(KvTree)], forward),
+                (f"fasn_{stem}_fp8_tree_plan", c_int32, [POINTER(KvFp8), POINTER(KvTree)], text),
+                (f"fasn_{stem}_fp8_tree_rope_append", c_int32, [POINTER(KvFp8), POINTER(KvRope), POINTER(KvTree), view, view, view], launch),
+                (f"fasn_{stem}_fp8_tree_rope_append_plan", c_int32, [POINTER(KvFp8), POINTER(KvRope), POINTER(KvTree), view, view, view], text)):
             yield name, restype, [block] + operands + tail
     packed = [POINTER(KvVarlenArgs)]
     yield "fasn_fwd_kvvarlen_workspace_bytes", c_size_t, packed
@@ -196,6 +205,7 @@ def _kv_bindings():
     yield "fasn_kvvarlen_rope_append", c_int32, packed + rope + launch
     yield "fasn_kvvarlen_rope_append_plan", c_int32, packed + rope + text
     yield "fasn_kvcache_tree_commit", c_int32, [POINTER(KvTreeCommit)] + launch
+    yield "fasn_kvcache_fp8_tree_commit", c_int32, [POINTER(KvTreeCommit)] + launch
 
 
 def load():
@@ -366,6 +376,19 @@ def kvfp8_rope_plan(args, fp8, rope, q_out, k_new=None, v_new=None):
     (a KvFp8) and `rope` (a KvRope), as launch_plan returns it. Nothing is launched."""
     what = "fasn_kvprefill_fp8_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_rope_append_plan"
     return _kv_plan(what, args, fp8, rope, q_out, k_new, v_new)
+
+
+def kvfp8_tree_plan(args, fp8, tree):
+    """The kernels fasn_fwd_kvcache_fp8_tree (`args` a KvCacheArgs) or fasn_fwd_kvprefill_fp8_tree (a KvPrefillArgs) would launch under `fp8`
+    (a KvFp8) and `tree` (a KvTree), as launch_plan returns them. Nothing is launched."""
+    return _kv_plan("fasn_kvprefill_fp8_tree_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_tree_plan", args, fp8, tree)
+
+
+def kvfp8_tree_rope_plan(args, fp8, rope, tree, q_out, k_new=None, v_new=None):
+    """The one launch of fasn_kvcache_fp8_tree_rope_append (`args` a KvCacheArgs) or fasn_kvprefill_fp8_tree_rope_append (a KvPrefillArgs)
+    under `fp8` (a KvFp8), `rope` (a KvRope) and `tree` (a KvTree), as launch_plan returns it. Nothing is launched."""
+    what = "fasn_kvprefill_fp8_tree_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_tree_rope_append_plan"
+    return _kv_plan(what, args, fp8, rope, tree, q_out, k_new, v_new)
 
 
 def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):

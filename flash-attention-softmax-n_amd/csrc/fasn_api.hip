@@ -61,6 +61,10 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
         {"fasn_kvcache_fwd_fp8_window_kernel", "T D"},
         {"fasn_kvprefill_fwd_fp8_window_kernel", "T D"},
         {"fasn_kvrope_fp8_kernel", "T D"},
+        {"fasn_kvcache_fwd_fp8_tree_kernel", "T D"},
+        {"fasn_kvprefill_fwd_fp8_tree_kernel", "T D"},
+        {"fasn_kvrope_fp8_tree_kernel", "T D"},
+        {"fasn_kvcache_fp8_tree_commit_kernel", "D"},
     };
     static const char* const modes[] = {"plain", "causal", "bias+mask", "element-load", "bias", "mask", "keypad", "bias+keypad"};
     if (cap == 0) return 0;

@@ -33,13 +33,19 @@ struct KvFwd {
     KvAlibi al;
     KvWindow kw;
     KvPacked pk;          // KV_VARLEN only
-    KvTree kt;            // KV_TREE only
-    KvFp8 f8;             // KV_FP8 and KV_FP8_WINDOW (which fills kw too)
+    KvTree kt;            // KV_TREE and KV_FP8_TREE
+    KvFp8 f8;             // KV_FP8, KV_FP8_WINDOW (which fills kw too) and KV_FP8_TREE (which fills kt too)
 };
 // the operand of KV_FP8_WINDOW: the two operands its entry points take, checked in this order
 struct KvFp8Window {
     const fasn_kv_fp8* fp8;
     const fasn_kv_window* window;
+};
+
+// the operand of KV_FP8_TREE, likewise: the FP8 operand's checks, then the tree operand's
+struct KvFp8Tree {
+    const fasn_kv_fp8* fp8;
+    const fasn_kv_tree* tree;
 };
 
 inline bool kv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -55,6 +61,9 @@ int kv_check_tree(const fasn_kvcache_args* a, const fasn_kv_tree* t, int capacit
 // the FP8 operand's checks, behind the base arguments' (the FP8 forwards and the quantising appends share them): the scales, and the rules
 // of a cache whose strides count bytes
 int kv_check_fp8(const fasn_kvcache_args* a, const fasn_kv_fp8* o, KvFp8& f8);
+// the checks of a fasn_kv_tree_commit block and the kernel's parameters (no HIP call). `fp8`: the cache holds codes - strides count bytes
+// and follow the FP8 calls' 16-byte rule, D is 64 or 128
+int kv_build_commit(const fasn_kv_tree_commit* a, bool fp8, KvCommit& c);
 // everything a forward does before its launches: base checks, the variant's operand (nothing, a fasn_alibi_slopes, a fasn_kv_window, a
 // fasn_kv_tree, a fasn_kv_fp8), then the workspace
 int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, KvFwd& f);

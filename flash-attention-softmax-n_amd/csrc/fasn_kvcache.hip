@@ -220,6 +220,12 @@ int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, K
         if ((rc = kv_check_fp8(in.a, o->fp8, f.f8))) return rc;
         return kv_build_window(in.a, o->window, (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kw);
     }
+    if (variant == KV_FP8_TREE) {   // the FP8 operand's checks, then the tree operand's and its plan: the 16-bit tree call's
+        if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
+        const KvFp8Tree* const o = static_cast<const KvFp8Tree*>(operand);
+        if ((rc = kv_check_fp8(in.a, o->fp8, f.f8))) return rc;
+        return kv_build_tree(in.a, o->tree, (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kt);
+    }
     if (variant == KV_TREE) {   // (decode and prefill only: there is no packed tree call)
         if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
         return kv_build_tree(in.a, static_cast<const fasn_kv_tree*>(operand), (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kt);
@@ -268,6 +274,47 @@ int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, v
     return FASN_OK;
 }
 
+// fasn_kvcache_tree_commit / fasn_kvcache_fp8_tree_commit: the cache's rules as kv_build states them for the members this block has (an FP8
+// cache: and kv_check_fp8's head dims and 16-byte stride rule, where the 16-bit rule stands), then its own operands
+int kv_build_commit(const fasn_kv_tree_commit* a, bool fp8, KvCommit& c) {
+    if (a == nullptr) return FASN_EINVAL;
+    if (a->B <= 0 || a->Hkv <= 0 || a->D <= 0 || a->page_size <= 0) return FASN_EINVAL;
+    if (!kv_head_dim_ok(a->D) || (fp8 && !kv_fp8_head_dim_ok(a->D))) return FASN_EHEADDIM;
+    if (a->seqlens == nullptr || a->k_cache == nullptr || a->v_cache == nullptr) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(a->seqlens) % 4 || reinterpret_cast<uintptr_t>(a->block_table) % 4) return FASN_EALIGN;
+    if (!kv_aligned16(a->k_cache) || !kv_aligned16(a->v_cache)) return FASN_EALIGN;
+    const int64_t smul = fp8 ? 16 : 8;
+    for (int i = 0; i < 3; ++i)
+        if (a->k_stride[i] % smul != 0 || a->v_stride[i] % smul != 0 || a->k_stride[i] < 0 || a->v_stride[i] < 0) return FASN_EALIGN;
+    const bool paged = a->block_table != nullptr;
+    if (paged && (a->max_pages <= 0 || a->block_table_stride < a->max_pages)) return FASN_EINVAL;
+    if (paged && a->page_size % KV_KT != 0) return FASN_EUNSUPPORTED;
+    const int64_t capacity = paged ? (int64_t)a->max_pages * a->page_size : (int64_t)a->page_size;
+    if (capacity > INT_MAX - 2 * KV_KT) return FASN_EINVAL;
+    if (a->k_stride[1] < a->D || a->v_stride[1] < a->D) return FASN_EINVAL;
+    if (a->accepted == nullptr || a->accepted_lens == nullptr || a->reserved != 0) return FASN_EINVAL;
+    if (a->A > 64 || a->nodes > 64) return FASN_EUNSUPPORTED;
+    if (a->A < 1 || a->nodes < 1 || a->accepted_stride < a->A) return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(a->accepted) % 4 || reinterpret_cast<uintptr_t>(a->accepted_lens) % 4) return FASN_EALIGN;
+    c = KvCommit{};
+    c.k = static_cast<char*>(a->k_cache);
+    c.v = static_cast<char*>(a->v_cache);
+    c.kps = a->k_stride[0], c.krs = a->k_stride[1], c.khs = a->k_stride[2];
+    c.vps = a->v_stride[0], c.vrs = a->v_stride[1], c.vhs = a->v_stride[2];
+    c.bt = a->block_table;
+    c.bts = a->block_table_stride;
+    c.seqlens = a->seqlens;
+    c.page_size = a->page_size;
+    c.capacity = (int)capacity;
+    c.B = a->B, c.Hkv = a->Hkv;
+    c.acc = a->accepted;
+    c.accs = a->accepted_stride;
+    c.alens = a->accepted_lens;
+    c.A = a->A;
+    c.nodes = a->nodes;
+    return FASN_OK;
+}
+
 namespace {
 
 template <typename Tag, int D>
@@ -305,7 +352,6 @@ int kv_forward_plan(const fasn_kvcache_args* args, KvVariant variant, const void
     return kv_plan(buf, cap, [&] { return kv_forward(args, variant, operand, kv_plan_workspace(), ~size_t(0), nullptr); });
 }
 
-// fasn_kvcache_tree_commit: the cache's rules as kv_build states them for the members this block has, then its own operands
 template <int D>
 int kv_launch_commit(const KvCommit& c, hipStream_t s) {
     const int64_t nthr = (int64_t)c.B * c.Hkv * (D / 8);
@@ -314,40 +360,9 @@ int kv_launch_commit(const KvCommit& c, hipStream_t s) {
     return launch_rc();
 }
 int kv_commit(const fasn_kv_tree_commit* a, fasn_stream_t stream) {
-    if (a == nullptr) return FASN_EINVAL;
-    if (a->B <= 0 || a->Hkv <= 0 || a->D <= 0 || a->page_size <= 0) return FASN_EINVAL;
-    if (!kv_head_dim_ok(a->D)) return FASN_EHEADDIM;
-    if (a->seqlens == nullptr || a->k_cache == nullptr || a->v_cache == nullptr) return FASN_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->seqlens) % 4 || reinterpret_cast<uintptr_t>(a->block_table) % 4) return FASN_EALIGN;
-    if (!kv_aligned16(a->k_cache) || !kv_aligned16(a->v_cache)) return FASN_EALIGN;
-    for (int i = 0; i < 3; ++i)
-        if (a->k_stride[i] % 8 != 0 || a->v_stride[i] % 8 != 0 || a->k_stride[i] < 0 || a->v_stride[i] < 0) return FASN_EALIGN;
-    const bool paged = a->block_table != nullptr;
-    if (paged && (a->max_pages <= 0 || a->block_table_stride < a->max_pages)) return FASN_EINVAL;
-    if (paged && a->page_size % KV_KT != 0) return FASN_EUNSUPPORTED;
-    const int64_t capacity = paged ? (int64_t)a->max_pages * a->page_size : (int64_t)a->page_size;
-    if (capacity > INT_MAX - 2 * KV_KT) return FASN_EINVAL;
-    if (a->k_stride[1] < a->D || a->v_stride[1] < a->D) return FASN_EINVAL;
-    if (a->accepted == nullptr || a->accepted_lens == nullptr || a->reserved != 0) return FASN_EINVAL;
-    if (a->A > 64 || a->nodes > 64) return FASN_EUNSUPPORTED;
-    if (a->A < 1 || a->nodes < 1 || a->accepted_stride < a->A) return FASN_EINVAL;
-    if (reinterpret_cast<uintptr_t>(a->accepted) % 4 || reinterpret_cast<uintptr_t>(a->accepted_lens) % 4) return FASN_EALIGN;
     KvCommit c{};
-    c.k = static_cast<char*>(a->k_cache);
-    c.v = static_cast<char*>(a->v_cache);
-    c.kps = a->k_stride[0], c.krs = a->k_stride[1], c.khs = a->k_stride[2];
-    c.vps = a->v_stride[0], c.vrs = a->v_stride[1], c.vhs = a->v_stride[2];
-    c.bt = a->block_table;
-    c.bts = a->block_table_stride;
-    c.seqlens = a->seqlens;
-    c.page_size = a->page_size;
-    c.capacity = (int)capacity;
-    c.B = a->B, c.Hkv = a->Hkv;
-    c.acc = a->accepted;
-    c.accs = a->accepted_stride;
-    c.alens = a->accepted_lens;
-    c.A = a->A;
-    c.nodes = a->nodes;
+    const int rc = kv_build_commit(a, false, c);
+    if (rc) return rc;
     return kv_dispatch_d(a->D, [&](auto d) { return kv_launch_commit<decltype(d)::value>(c, (hipStream_t)stream); });
 }
 

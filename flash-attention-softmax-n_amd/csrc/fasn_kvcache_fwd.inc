@@ -9,13 +9,17 @@
 // FASN_KV_FP8 is orthogonal to FASN_KV_WINDOW: both at 1 (fasn_kvfp8.h) is the sliding-window sibling over the FP8 cache - the window's tile
 // range, full-tile test and one-compare mask around the FP8 staging and widening. The score factor has ONE name for that, FASN_KV_SC:
 // c8 under FASN_KV_FP8, p.c otherwise (a macro, so that the kernels that were there keep their tokens).
+// FASN_KV_FP8 is orthogonal to FASN_KV_TREE in the same way: both at 1 (fasn_kvfp8.h) is the token-tree sibling over the FP8 cache - the tree's
+// tile range, full-tile test and per-lane visibility word around the FP8 staging and widening, FASN_KV_SC in both arms of the masked loop.
 #if FASN_KV_FP8
 #define FASN_KV_SC c8
 #else
 #define FASN_KV_SC p.c
 #endif
 template <typename Tag, int D>
-#if FASN_KV_FP8 && FASN_KV_WINDOW
+#if FASN_KV_FP8 && FASN_KV_TREE
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_tree_kernel(const KvParams p, const KvFp8 f8, const KvTree tree) {
+#elif FASN_KV_FP8 && FASN_KV_WINDOW
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_window_kernel(const KvParams p, const KvFp8 f8, const KvWindow win) {
 #elif FASN_KV_FP8
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_kernel(const KvParams p, const KvFp8 f8) {
@@ -292,7 +296,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
                     for (int r = 0; r < 16; ++r) {
                         const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
 #if FASN_KV_TREE
-                        const float y = ((vm >> (kb * 32 + (r & 3) + 8 * (r >> 2))) & 1ull) != 0ull ? sacc[kb][r] * p.c : -INFINITY;
+                        const float y = ((vm >> (kb * 32 + (r & 3) + 8 * (r >> 2))) & 1ull) != 0ull ? sacc[kb][r] * FASN_KV_SC : -INFINITY;
 #elif FASN_KV_ALIBI
                         const float y = key <= vis ? __builtin_fmaf(sacc[kb][r], p.c, kv_alibi_term(nslope2, dk0, kb, r)) : -INFINITY;
 #elif FASN_KV_WINDOW

@@ -7,6 +7,9 @@
 //   fasn_kvcache_fp8_append_kernel / fasn_kvprefill_fp8_append_kernel   k_new / v_new rows, quantised, -> the cache rows behind the lengths
 //   fasn_kvcache_fwd_fp8_window_kernel / fasn_kvprefill_fwd_fp8_window_kernel   the sliding-window siblings: FASN_KV_FP8 with FASN_KV_WINDOW
 //   fasn_kvrope_fp8_kernel   fasn_kvrope_kernel in front of this cache: rotate, round to the 16-bit type, quantise, append (and rotate q)
+//   fasn_kvcache_fwd_fp8_tree_kernel / fasn_kvprefill_fwd_fp8_tree_kernel   the token-tree siblings: FASN_KV_FP8 with FASN_KV_TREE
+//   fasn_kvrope_fp8_tree_kernel   fasn_kvrope_fp8_kernel at the depth positions of a token tree
+//   fasn_kvcache_fp8_tree_commit_kernel   the commit of an accepted path over code rows
 //
 // Semantics. value(code) = up(code) * scale[b, hkv], up() the exact upcast. All 254 finite codes are bf16 AND fp16 numbers, so the operands
 // of the 16-bit MFMAs are the codes themselves and the scales act in fp32:
@@ -65,6 +68,14 @@ FASN_DEV void kv_fp8_widen(const char* src, char* img, int tid) {
 #include "fasn_kvcache_fwd.inc"
 #include "fasn_kvprefill_fwd.inc"
 #undef FASN_KV_WINDOW
+// fasn_kvcache_fwd_fp8_tree_kernel / fasn_kvprefill_fwd_fp8_tree_kernel(..., KvFp8, KvTree): the token-tree siblings, the product of
+// FASN_KV_FP8 and FASN_KV_TREE. From the tree kernels: base, tlo and the split of [tlo, tiles_b), the conservative full-tile test, the
+// per-lane 64-bit visibility word built inside the masked branch, the run-time window tree.w. From the FP8 kernels: everything above.
+// Same LDS, same grid and split rule as the 16-bit tree call of the same shape; the FP8 combine kernels below serve these too.
+#define FASN_KV_TREE 1
+#include "fasn_kvcache_fwd.inc"
+#include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_TREE
 #undef FASN_KV_FP8
 
 // fasn_kvcache_combine_kernel with v_scale[b, hkv] on the normalised fp32 row, in front of its one rounding
@@ -240,7 +251,7 @@ FASN_DEV u32x2 kv_fp8_quant8(u32x4 raw, float s) {
 // values are quantised as kv_fp8_quant16 quantises k_new, so a rotated key has one definition across both cache types and the call is
 // "eager rotation, then fasn_kv*_fp8_append" byte for byte. Chunk c of a row (16 bytes of 16-bit elements) is the 8 codes at byte 8 c:
 // two 8-byte stores where the 16-bit kernel has two 16-byte stores; units at or beyond rotary_dim are quantised, not copied. The unit's
-// 16 v_new elements are quantised with v_scale and stored as one 16-byte group. No tree variant.
+// 16 v_new elements are quantised with v_scale and stored as one 16-byte group. The tree variant follows it.
 #define FASN_KVROPE_FP8 1
 template <typename Tag, int D>
 __global__ void __launch_bounds__(256) fasn_kvrope_fp8_kernel(const KvRopeParams rp, const KvFp8 f8) {
@@ -286,6 +297,93 @@ __global__ void __launch_bounds__(256) fasn_kvrope_fp8_kernel(const KvRopeParams
     }
 #include "fasn_kvrope_unit.inc"
 }
+
+// fasn_kvrope_fp8_kernel at DEPTH positions (fasn_kvcache.h: KvTree), as fasn_kvrope_tree_kernel relates to fasn_kvrope_kernel: node i of
+// k_new / v_new is still WRITTEN to cache row seqlens[b] + i, but rotated at seqlens[b] + d_i - then rounded once to the 16-bit type and
+// quantised with k_scale, v_new quantised beside it - and the query at p_i = len_b - qlen_b + d_i, with
+// d_i = max(popcount(mask[b, i] & the low qlen_b bits) - 1, 0). Same lanes, same grid, the same unit text; the window member of the
+// operand takes no part here.
+template <typename Tag, int D>
+__global__ void __launch_bounds__(256) fasn_kvrope_fp8_tree_kernel(const KvRopeParams rp, const KvFp8 f8, const KvTree tree) {
+    using E = ET<Tag>;
+    const KvParams& p = rp.kv;
+    constexpr int UPR = D / 16;   // units per row
+    int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= rp.nkv + rp.nq) return;
+    const bool isq = gid >= rp.nkv;
+    if (isq) gid -= rp.nkv;
+    const int u = (int)(gid % UPR);
+    int64_t rest = gid / UPR;
+    const int i = (int)(rest % p.Sq);
+    rest /= p.Sq;
+    const int heads = isq ? p.H : p.Hkv;
+    const int h = (int)(rest % heads), b = (int)(rest / heads);
+    int qlen = p.Sq;
+    if (rp.qlens != nullptr) qlen = min(max(rp.qlens[b], 0), p.Sq);
+    if (i >= qlen) return;   // padding rows: neither read nor written (qlen >= 1 from here on)
+    const unsigned long long word = (unsigned long long)tree.mask[b * tree.sb + i] & (~0ull >> (64 - qlen));
+    const int depth = max(__builtin_popcountll(word) - 1, 0);
+    int64_t pos;
+    const char* src;
+    char* dst = nullptr;    // a query unit's row of q_out (16-bit)
+    char* dst8 = nullptr;   // a K/V unit's row of the code cache
+    float ksc = 1.f;
+    if (!isq) {
+        const int64_t at = (int64_t)p.seqlens[b] + i;   // the row written
+        if (at < 0 || at >= p.capacity) return;         // dropped: the host does not know the lengths
+        pos = (int64_t)p.seqlens[b] + depth;            // the position rotated at
+        const int slot = (int)(at / p.page_size), rip = (int)(at % p.page_size);
+        const int64_t page = p.bt != nullptr ? p.bt[(int64_t)b * p.bts + slot] : b;
+        src = p.kn + (b * p.kns[0] + h * p.kns[1] + (int64_t)i * p.kns[2]) * 2;
+        dst8 = p.k + page * p.kps + (int64_t)rip * p.krs + (int64_t)h * p.khs;
+        ksc = f8.ks[b * f8.ksb + h * f8.ksh];
+        const u32x4 vx = kv_fp8_quant16<E>(p.vn + (b * p.vns[0] + h * p.vns[1] + (int64_t)i * p.vns[2]) * 2 + u * 32, f8.vs[b * f8.vsb + h * f8.vsh]);
+        gstore16(p.v + page * p.vps + (int64_t)rip * p.vrs + (int64_t)h * p.vhs + u * 16, vx);
+    } else {
+        // len_b per lane, as in fasn_kvrope_kernel
+        int len;
+        if (rp.add_qlen < 0) len = min(max(p.seqlens[b] + p.seqlen_add, 0), p.capacity);
+        else len = (int)min(max((int64_t)p.seqlens[b] + (rp.add_qlen ? qlen : 0), (int64_t)0), (int64_t)p.capacity);
+        pos = (int64_t)depth + len - qlen;
+        src = p.q + (b * p.qs[0] + h * p.qs[1] + (int64_t)i * p.qs[2]) * 2;
+        dst = rp.qo + (b * rp.qos[0] + h * rp.qos[1] + (int64_t)i * rp.qos[2]) * 2;
+    }
+#include "fasn_kvrope_unit.inc"
+}
 #undef FASN_KVROPE_FP8
+
+// ---- commit over code rows
+// fasn_kvcache_tree_commit_kernel (fasn_kvcache.h: KvCommit, the hazards and the skip rules are stated there) on a cache of codes: the strides
+// count codes, one thread owns 16 codes - one 16-byte chunk, D / 16 chunks per row - of one (b, hkv) in K and in V and walks k upward. The
+// program-order argument is that kernel's: move k reads row accepted[k] > k and writes row k, no later move of the thread reads a row an
+// earlier one wrote, and no other thread touches the thread's bytes.
+template <int D>
+__global__ void __launch_bounds__(256) fasn_kvcache_fp8_tree_commit_kernel(const KvCommit c) {
+    constexpr int CPR = D / 16;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (int64_t)c.B * c.Hkv * CPR) return;
+    const int ch = (int)(gid % CPR);
+    const int64_t rest = gid / CPR;
+    const int hkv = (int)(rest % c.Hkv), b = (int)(rest / c.Hkv);
+    const int64_t base = c.seqlens[b];
+    const int alen = min(max(c.alens[b], 0), c.A);
+    const int* const acc = c.acc + (int64_t)b * c.accs;
+    const int* const bt = c.bt != nullptr ? c.bt + (int64_t)b * c.bts : nullptr;
+    char* const kh = c.k + (int64_t)hkv * c.khs + ch * 16;
+    char* const vh = c.v + (int64_t)hkv * c.vhs + ch * 16;
+    for (int k = 0; k < alen; ++k) {
+        const int node = acc[k];
+        if (node <= k || node >= c.nodes) continue;   // (node == k: the row is where it belongs)
+        const int64_t src = base + node, dst = base + k;
+        if (dst < 0 || src >= c.capacity) continue;
+        const int sslot = (int)(src / c.page_size), srip = (int)(src % c.page_size);
+        const int dslot = (int)(dst / c.page_size), drip = (int)(dst % c.page_size);
+        const int64_t spage = bt != nullptr ? bt[sslot] : b, dpage = bt != nullptr ? bt[dslot] : b;
+        const u32x4 kx = gload16(kh + spage * c.kps + (int64_t)srip * c.krs);
+        const u32x4 vx = gload16(vh + spage * c.vps + (int64_t)srip * c.vrs);
+        gstore16(kh + dpage * c.kps + (int64_t)drip * c.krs, kx);
+        gstore16(vh + dpage * c.vps + (int64_t)drip * c.vrs, vx);
+    }
+}
 
 }  // namespace fasn

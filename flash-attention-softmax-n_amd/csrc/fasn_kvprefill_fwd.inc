@@ -12,13 +12,16 @@
 // KvFp8; fasn_kvcache_fwd.inc: staging, widening pass); v_scale multiplies the one-split direct store. With FASN_KV_FP8 == 0 the kernels
 // above are what they were. FASN_KV_FP8 = 1 with FASN_KV_WINDOW = 1 (fasn_kvfp8.h) is the sliding-window sibling over the FP8 cache: the
 // window blocks of the body are orthogonal to the FP8 blocks. FASN_KV_SC is the score factor's one name (fasn_kvcache_fwd.inc).
+// FASN_KV_FP8 = 1 with FASN_KV_TREE = 1 (fasn_kvfp8.h) is the token-tree sibling over the FP8 cache, by the same orthogonality.
 #if FASN_KV_FP8
 #define FASN_KV_SC c8
 #else
 #define FASN_KV_SC p.c
 #endif
 template <typename Tag, int D>
-#if FASN_KV_FP8 && FASN_KV_WINDOW
+#if FASN_KV_FP8 && FASN_KV_TREE
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_fp8_tree_kernel(const KvPrefillParams pp, const KvFp8 f8, const KvTree tree) {
+#elif FASN_KV_FP8 && FASN_KV_WINDOW
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_fp8_window_kernel(const KvPrefillParams pp, const KvFp8 f8, const KvWindow win) {
 #elif FASN_KV_FP8
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_fp8_kernel(const KvPrefillParams pp, const KvFp8 f8) {

@@ -1,7 +1,8 @@
 // Rotary rotate-and-append on the K/V-cache calls (include/fasn.h: fasn_kvcache_rope_append, fasn_kvprefill_rope_append,
 // fasn_kvvarlen_rope_append and their *_plan siblings, fasn_kvcache_tree_rope_append / fasn_kvprefill_tree_rope_append, and
 // fasn_kvcache_fp8_rope_append / fasn_kvprefill_fp8_rope_append with their *_plan siblings - the rotate-quantise-append in front of an FP8
-// cache, whose FP8 operand is checked behind the base arguments and in front of the rope operand): the base call's argument checks first
+// cache, whose FP8 operand is checked behind the base arguments and in front of the rope operand - and fasn_kvcache_fp8_tree_rope_append /
+// fasn_kvprefill_fp8_tree_rope_append, the same at the depth positions of a token tree: base, FP8 operand, tree operand, rope operand): the base call's argument checks first
 // (the family's, fasn_kv_host.h), then the operand's, which live here, and the one launch of fasn_kvrope.h (the FP8 sibling: of
 // fasn_kvfp8.h) - whose grid depends on shapes only, never on the lengths in device memory.
 #include <limits.h>
@@ -74,6 +75,16 @@ int kvr_launch_fp8_d(int D, const KvRopeParams& rp, const KvFp8& f8, hipStream_t
     return D == 64 ? kvr_launch_fp8<Tag, 64>(rp, f8, s) : kvr_launch_fp8<Tag, 128>(rp, f8, s);
 }
 
+template <typename Tag, int D>
+int kvr_launch_fp8_tree(const KvRopeParams& rp, const KvFp8& f8, const KvTree& kt, hipStream_t s) {
+    FASN_LAUNCH((fasn_kvrope_fp8_tree_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, f8, kt);
+    return launch_rc();
+}
+template <typename Tag>
+int kvr_launch_fp8_tree_d(int D, const KvRopeParams& rp, const KvFp8& f8, const KvTree& kt, hipStream_t s) {
+    return D == 64 ? kvr_launch_fp8_tree<Tag, 64>(rp, f8, kt, s) : kvr_launch_fp8_tree<Tag, 128>(rp, f8, kt, s);
+}
+
 // `tree`: the *_tree_rope_append calls (the rotation at depth positions); its operand is checked behind the rope operand
 int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream,
              bool tree = false, const fasn_kv_tree* tree_operand = nullptr) {
@@ -99,18 +110,25 @@ int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out
 }
 
 // the *_fp8_rope_append calls: the base checks, the FP8 operand's (kv_check_fp8), the rope operand's (kvr_build), one launch on the grid
-// of the 16-bit rope append. Decode and prefill only.
+// of the 16-bit rope append. Decode and prefill only. `tree`: the *_fp8_tree_rope_append calls (the rotation at depth positions); their
+// tree operand is checked behind the FP8 operand and in front of the rope operand, and the one launch is on the 16-bit tree rope grid.
 int kvr_call_fp8(const KvArgs& in, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
-                 fasn_stream_t stream) {
+                 fasn_stream_t stream, bool tree = false, const fasn_kv_tree* tree_operand = nullptr) {
     KvPrefillParams pp;
     int rc = kv_build(in, pp);
     if (rc) return rc;
     KvFp8 f8{};
     if ((rc = kv_check_fp8(in.a, fp8, f8))) return rc;
+    KvTree kt{};
+    if (tree && (rc = kv_check_tree(in.a, tree_operand, pp.kv.capacity, kt))) return rc;
     KvRopeParams rp{};
     rp.kv = pp.kv;
     rp.qlens = pp.qlens;
     if ((rc = kvr_build(in.a, in.call != KV_DECODE, (int64_t)pp.kv.B * pp.kv.Sq, rope, q_out, k_new, v_new, rp))) return rc;
+    if (tree) {
+        if (in.a->dtype == FASN_DTYPE_BF16) return kvr_launch_fp8_tree_d<bf16_tag>(in.a->D, rp, f8, kt, (hipStream_t)stream);
+        return kvr_launch_fp8_tree_d<f16_tag>(in.a->D, rp, f8, kt, (hipStream_t)stream);
+    }
     if (in.a->dtype == FASN_DTYPE_BF16) return kvr_launch_fp8_d<bf16_tag>(in.a->D, rp, f8, (hipStream_t)stream);
     return kvr_launch_fp8_d<f16_tag>(in.a->D, rp, f8, (hipStream_t)stream);
 }
@@ -180,6 +198,26 @@ int fasn_kvcache_fp8_rope_append_plan(const fasn_kvcache_args* args, const fasn_
 int fasn_kvprefill_fp8_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
                                         const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
     return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr); });
+}
+
+int fasn_kvcache_fp8_tree_rope_append(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
+                                      const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
+    return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, stream, true, tree);
+}
+
+int fasn_kvprefill_fp8_tree_rope_append(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
+                                        const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
+    return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, stream, true, tree);
+}
+
+int fasn_kvcache_fp8_tree_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
+                                           const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr, true, tree); });
+}
+
+int fasn_kvprefill_fp8_tree_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
+                                             const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr, true, tree); });
 }
 
 }  // extern "C"

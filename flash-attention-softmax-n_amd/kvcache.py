@@ -22,6 +22,8 @@ flash_attention_n_kvcache_fp8 is the decode / prefill call over a cache of e4m3f
 (fasn_fwd_kvcache_fp8 / fasn_fwd_kvprefill_fp8, fasn_kv*_fp8_append): half the cache bytes per key, k_new / v_new quantised on the way in.
 flash_attention_n_kvcache_fp8_window is the sliding-window layer on that cache (fasn_fwd_kv*_fp8_window) and flash_attention_n_kvcache_fp8_rope
 the rotary call (fasn_kv*_fp8_rope_append: rotate, round to the 16-bit type, quantise, append - one launch), with or without a window.
+flash_attention_n_kvcache_fp8_tree verifies a tree of draft tokens on that cache (fasn_fwd_kv*_fp8_tree, fasn_kv*_fp8_tree_rope_append) and
+flash_attention_n_kvcache_fp8_tree_commit moves the accepted path's code rows behind the prefix (fasn_kvcache_fp8_tree_commit).
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -290,12 +292,13 @@ def _on_device(dev, launch) -> None:
 def _append(lib, c, stream, rope=None, q_rot=None, tree=None, fp8=None) -> None:
     """k_new / v_new -> the cache rows behind the lengths; with `rope` the one launch that rotates them on the way and the queries into
     `q_rot`, which the forward then reads - under `tree` at the nodes' depth positions; with `fp8` the launch that quantises them; with
-    `fp8` and `rope` the one launch that rotates, then quantises"""
+    `fp8` and `rope` the one launch that rotates, then quantises - under `tree` at the nodes' depth positions too"""
     if fp8 is not None and rope is not None:   # the rotate-quantise-append; without k_new / v_new it rotates the queries only
-        name = f"fasn_{c.stem}_fp8_rope_append"
+        name = f"fasn_{c.stem}_fp8_rope_append" if tree is None else f"fasn_{c.stem}_fp8_tree_rope_append"
         kn_view = None if c.k_new is None else _view4(c.k_new)
         vn_view = None if c.v_new is None else _view4(c.v_new)
-        _lib.check(getattr(lib, name)(c.args, fp8, rope, _view4(q_rot), kn_view, vn_view, stream), name)
+        operand = (fp8, rope) if tree is None else (fp8, rope, tree)
+        _lib.check(getattr(lib, name)(c.args, *operand, _view4(q_rot), kn_view, vn_view, stream), name)
         c.kv.q = _view4(q_rot)
     elif fp8 is not None:
         if c.k_new is not None:
@@ -315,10 +318,13 @@ def _append(lib, c, stream, rope=None, q_rot=None, tree=None, fp8=None) -> None:
 
 def _forward(lib, c, stream, win=None, tree=None, fp8=None) -> None:
     """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (c.alibi), of their window siblings (`win`),
-    of their token-tree siblings (`tree`, which carries its window), of their FP8-cache siblings (`fp8`) or of the FP8 window siblings
-    (`fp8` and `win`)"""
+    of their token-tree siblings (`tree`, which carries its window), of their FP8-cache siblings (`fp8`), of the FP8 window siblings
+    (`fp8` and `win`) or of the FP8 token-tree siblings (`fp8` and `tree`)"""
     stem = c.stem
-    if fp8 is not None and win is not None:
+    if fp8 is not None and tree is not None:
+        name, operand = f"fasn_fwd_{stem}_fp8_tree", (fp8, tree)
+        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_fp8_tree_workspace_bytes")(c.args, fp8, tree)
+    elif fp8 is not None and win is not None:
         name, operand = f"fasn_fwd_{stem}_fp8_window", (fp8, win)
         ws_bytes = getattr(lib, f"fasn_fwd_{stem}_fp8_window_workspace_bytes")(c.args, fp8, win)
     elif fp8 is not None:
@@ -822,7 +828,8 @@ def flash_attention_n_kvcache_fp8(
                   correctly rounded in fp32, saturating, NaN -> a NaN code - and then attended to. `cache_seqlens` is not modified.
     :param alibi_slopes, window, rotary_cos, rotary_sin, cu_seqlens_q, tree_mask: anything but None is refused here. A sliding window
                   and rotary embedding on an FP8 cache are calls of their own: flash_attention_n_kvcache_fp8_window,
-                  flash_attention_n_kvcache_fp8_rope. ALiBi, packed queries and token trees have 16-bit kernels only.
+                  flash_attention_n_kvcache_fp8_rope; a token tree is flash_attention_n_kvcache_fp8_tree's. ALiBi and packed queries
+                  have 16-bit kernels only.
     :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32).
     """
     fn = "flash_attention_n_kvcache_fp8"
@@ -832,7 +839,10 @@ def flash_attention_n_kvcache_fp8(
             if name in ("window", "rotary_cos", "rotary_sin"):
                 raise NotImplementedError(f"{fn}: {name} is not supported on an FP8 cache by this call; use flash_attention_n_kvcache_fp8_window "
                                           "(a sliding window) or flash_attention_n_kvcache_fp8_rope (rotary embedding, with or without a window)")
-            raise NotImplementedError(f"{fn}: {name} is not supported on an FP8 cache (no FP8 ALiBi, packed or tree kernels yet); use a 16-bit "
+            if name == "tree_mask":
+                raise NotImplementedError(f"{fn}: {name} is not supported on an FP8 cache by this call; use flash_attention_n_kvcache_fp8_tree "
+                                          "(token-tree verification over the FP8 cache)")
+            raise NotImplementedError(f"{fn}: {name} is not supported on an FP8 cache (no FP8 ALiBi or packed kernels yet); use a 16-bit "
                                       "cache with the call of that name")
     _check_query_seqlens(fn, query_seqlens, query)
     _check_group_limit(fn, query, k_cache)
@@ -933,7 +943,7 @@ def flash_attention_n_kvcache_fp8_rope(
     :return: as flash_attention_n_kvcache_fp8. `query`, `k_new`, `cache_seqlens` are not modified.
 
     Nothing is read on the host: a captured graph follows `cache_seqlens`, `query_seqlens` and the scales. No ALiBi, no packed queries,
-    no token tree, no gradient.
+    no gradient; a token tree with rotary embedding is flash_attention_n_kvcache_fp8_tree's.
     """
     fn = "flash_attention_n_kvcache_fp8_rope"
     if window is not None:
@@ -1055,11 +1065,100 @@ def flash_attention_n_kvcache_tree_commit(
     skips that move: a malformed path gives unspecified rows and never touches memory outside the cache; accepted[b, k] == k moves nothing.
     Rotated keys need no re-rotation: node k of a path has depth k and lands at the position it was rotated for. Nothing is read on the
     host: the launch depends on shapes only and replays in a captured graph."""
-    fn = "flash_attention_n_kvcache_tree_commit"
+    _commit("flash_attention_n_kvcache_tree_commit", False, k_cache, v_cache, cache_seqlens, accepted, accepted_lens, block_table)
+
+
+def flash_attention_n_kvcache_fp8_tree(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        k_scale,
+        v_scale,
+        tree_mask: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        query_seqlens: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        return_lse: bool = False,
+        window: Optional[int] = None,
+        rotary_cos: Optional[Tensor] = None,
+        rotary_sin: Optional[Tensor] = None,
+        rotary_interleaved: bool = False):
+    """softmax_n attention of a TREE of draft tokens against an FP8 K/V CACHE, on MI355X: the verification step of speculative decoding
+    (EAGLE, Medusa, SpecInfer) over flash_attention_n_kvcache_fp8's cache, without dequantising it.
+
+    Visibility, the nodes' rows and positions (base_b, the depth from the popcount of the mask word), `tree_mask`, `window` and its memory
+    contract, rotary embedding at depth positions, `query_seqlens`, padding rows and the choice of kernels by shapes alone are
+    flash_attention_n_kvcache_tree's; the cache, `k_scale` / `v_scale`, the values, the quantisation of `k_new` / `v_new`, the caches' rules
+    and the refusals are flash_attention_n_kvcache_fp8's. With power-of-two scales the result is, bit for bit,
+    flash_attention_n_kvcache_tree on `k_cache.to(query.dtype)`; the chain mask is flash_attention_n_kvcache_fp8(is_causal=True) (with a
+    window: flash_attention_n_kvcache_fp8_window), bit for bit.
+
+    :param query: [B, H, Sq, D] fp16 / bf16 with Sq <= 64, D in {64, 128}.
+    :param k_new, v_new: optional [B, Hkv, Sq, D]: node i < qlen_b is quantised and written to cache row cache_seqlens[b] + i, then attended
+                  to as the mask says.
+    :param rotary_cos, rotary_sin, rotary_interleaved: both tables or neither. ONE launch rotates node i of k_new at cache_seqlens[b] + d_i,
+                  rounds it once to query's dtype, quantises that value with k_scale and writes the codes to row cache_seqlens[b] + i;
+                  quantises v_new beside it; and rotates the query node at p_i. The call equals "rotate `query` and `k_new` at the depth
+                  positions in eager torch, then this call without tables" bit for bit.
+    :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32), as flash_attention_n_kvcache_tree.
+
+    After acceptance flash_attention_n_kvcache_fp8_tree_commit moves the accepted path's code rows behind the prefix. Nothing is read on
+    the host: the launches - those of flash_attention_n_kvcache_tree for the same shapes and window - follow shapes, the capacity and
+    `window` only, so one captured graph serves every step while `tree_mask`, `cache_seqlens`, the scales and the cache change in place.
+    Always causal; no ALiBi, no packed queries, no gradient."""
+    fn = "flash_attention_n_kvcache_fp8_tree"
+    if window is not None:
+        _check_window(fn, window, or_none="None or ")
+    tree_mask = _check_tree_mask(fn, tree_mask, query)
+    if (rotary_cos is None) != (rotary_sin is None):
+        raise ValueError(f"{fn}: rotary_cos and rotary_sin come together (both tables, or neither)")
+    rotary = rotary_cos is not None
+    if rotary:
+        _check_rotary_tables(fn, rotary_cos, rotary_sin, query)
+    _check_query_seqlens(fn, query_seqlens, query)
+    _check_group_limit(fn, query, k_cache)
+    if rotary:
+        _check_rotary_fit(fn, rotary_cos, rotary_sin, query, k_cache, block_table)
+    scales = _fp8_scales(fn, k_scale, v_scale, query, k_cache)
+    c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, True,
+                 return_lse, query_seqlens=query_seqlens, by_shape=True, fp8=True)
+    return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query) if rotary else None, tree_mask=tree_mask,
+                fp8_scales=scales)
+
+
+def flash_attention_n_kvcache_fp8_tree_commit(
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        accepted: Tensor,
+        accepted_lens: Tensor,
+        block_table: Optional[Tensor] = None) -> None:
+    """flash_attention_n_kvcache_tree_commit on an FP8 K/V CACHE, on MI355X: the code rows of the accepted path of a tree verified by
+    flash_attention_n_kvcache_fp8_tree move behind the prefix, in place, through the block table. The scales are per (batch element, K/V
+    head), so a moved code keeps its value.
+
+    :param k_cache, v_cache: torch.float8_e4m3fn, D in {64, 128}, under the alignment rules of flash_attention_n_kvcache_fp8 (strides in
+                  multiples of 16 codes).
+    Every other parameter, the moves, the skip rules for a malformed path and the checks are flash_attention_n_kvcache_tree_commit's.
+    `cache_seqlens` is not modified. Nothing is read on the host: the launch depends on shapes only and replays in a captured graph."""
+    _commit("flash_attention_n_kvcache_fp8_tree_commit", True, k_cache, v_cache, cache_seqlens, accepted, accepted_lens, block_table)
+
+
+def _commit(fn, fp8, k_cache, v_cache, cache_seqlens, accepted, accepted_lens, block_table) -> None:
+    """the checks, the block and the one launch of both commits; `fp8`: the caches hold e4m3fn codes and the strides count them"""
     if k_cache.dim() != 4 or v_cache.dim() != 4:
         raise ValueError(f"{fn}: the caches must be [num_pages, page_size, Hkv, D] (paged) or [B, capacity, Hkv, D] (dense)")
-    if k_cache.dtype not in _KV_DTYPES or v_cache.dtype != k_cache.dtype:
-        raise TypeError(f"{fn}: k_cache and v_cache must share one dtype, fp16 or bf16; got {k_cache.dtype} and {v_cache.dtype}")
+    if fp8:
+        if k_cache.dtype != torch.float8_e4m3fn or v_cache.dtype != torch.float8_e4m3fn:
+            raise TypeError(f"{fn}: k_cache and v_cache must be torch.float8_e4m3fn (OCP e4m3fn codes; e5m2 and fnuz caches are not supported); "
+                            f"got {k_cache.dtype} and {v_cache.dtype}. A 16-bit cache is flash_attention_n_kvcache_tree_commit's")
+    elif k_cache.dtype not in _KV_DTYPES or v_cache.dtype != k_cache.dtype:
+        raise TypeError(f"{fn}: k_cache and v_cache must share one dtype, fp16 or bf16; got {k_cache.dtype} and {v_cache.dtype}"
+                        + (". An FP8 cache is flash_attention_n_kvcache_fp8_tree_commit's" if k_cache.dtype == torch.float8_e4m3fn else ""))
     dev = k_cache.device
     tensors = {"v_cache": v_cache, "cache_seqlens": cache_seqlens, "accepted": accepted, "accepted_lens": accepted_lens, "block_table": block_table}
     for name, t in tensors.items():
@@ -1071,6 +1170,8 @@ def flash_attention_n_kvcache_tree_commit(
     page_size, Hkv, D = k_cache.shape[1], k_cache.shape[2], k_cache.shape[3]
     if D not in _KV_HEAD_DIMS:
         raise ValueError(f"{fn}: head dim {D} is not supported (supported: {_KV_HEAD_DIMS})")
+    if fp8 and D not in _FP8_HEAD_DIMS:
+        raise ValueError(f"{fn}: head dim {D} is not supported on an FP8 cache (supported: {_FP8_HEAD_DIMS}; 32 and 256 have 16-bit kernels only)")
     if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or not cache_seqlens.is_contiguous():
         raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [B] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
     B = cache_seqlens.shape[0]
@@ -1114,7 +1215,8 @@ def flash_attention_n_kvcache_tree_commit(
     a.accepted, a.accepted_stride, a.accepted_lens = accepted.data_ptr(), accepted.stride(0) if B > 1 else A, accepted_lens.data_ptr()
     a.nodes, a.reserved = _MAX_NODES, 0
     lib = _lib.load()
-    _on_device(dev, lambda: _lib.check(lib.fasn_kvcache_tree_commit(a, _stream_ptr(dev)), "fasn_kvcache_tree_commit"))
+    entry = "fasn_kvcache_fp8_tree_commit" if fp8 else "fasn_kvcache_tree_commit"
+    _on_device(dev, lambda: _lib.check(getattr(lib, entry)(a, _stream_ptr(dev)), entry))
 
 
 def _rows(t: Tensor) -> Tensor:

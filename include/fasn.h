@@ -542,7 +542,7 @@ typedef struct fasn_kv_tree_commit {
     const int32_t* seqlens;      /* DEVICE [B]: base_b, the prefix length */
     int32_t B;
     int32_t Hkv;                 /* K/V heads */
-    int32_t D;                   /* 32, 64, 128, 256; 16-bit elements */
+    int32_t D;                   /* 32, 64, 128, 256; 16-bit elements (fasn_kvcache_fp8_tree_commit: 64, 128; codes) */
     int32_t A;                   /* columns of accepted, 1 .. 64 */
     const int32_t* accepted;     /* DEVICE, node (b, k) at accepted[b * accepted_stride + k] */
     int64_t accepted_stride;     /* elements, >= A */
@@ -585,7 +585,8 @@ int fasn_kvcache_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t st
  *              the base call's: fasn_fwd_kv{cache,prefill}_fp8_workspace_bytes, the *_fp8_plan calls write the launches as text.
  * Every rule and error code of the base call holds and is checked first; then fp8 == NULL, a NULL scale or reserved != 0 is FASN_EINVAL,
  * D other than 64 / 128 FASN_EHEADDIM, a scale pointer off 4 bytes or a cache stride that is not a multiple of 16 (bytes) FASN_EALIGN, a
- * negative or overflowing scale stride FASN_EINVAL. Not here: ALiBi, windows, rotary appends, packed queries, trees, e5m2, gradients.
+ * negative or overflowing scale stride FASN_EINVAL. Not here: ALiBi, packed queries, e5m2, gradients; windows, rotary appends and trees
+ * have calls of their own below.
  */
 typedef struct fasn_kv_fp8 {
     const float* k_scale;        /* DEVICE */
@@ -623,7 +624,8 @@ int fasn_kvprefill_fp8_append(const fasn_kvprefill_args* args, const fasn_kv_fp8
  *              -448, 448)), NaN -> a NaN code - so the call equals "rotate in eager fp32 arithmetic, round to dtype, fasn_kv*_fp8_append"
  *              byte for byte. Features at or beyond rotary_dim are quantised unrotated; v_new is quantised with v_scale. Positions,
  *              dropped rows, padding rows and the table-row clamp are the 16-bit call's. k_new == v_new == NULL: queries only.
- *              Checks: the base call's, then the FP8 operand's, then the rope operand's (as fasn_kv*_rope_append). No tree variant.
+ *              Checks: the base call's, then the FP8 operand's, then the rope operand's (as fasn_kv*_rope_append). The tree variant
+ *              is fasn_kv{cache,prefill}_fp8_tree_rope_append below.
  */
 size_t fasn_fwd_kvcache_fp8_window_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window);
 int fasn_fwd_kvcache_fp8_window(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_window* window, void* workspace,
@@ -641,6 +643,42 @@ int fasn_kvcache_fp8_rope_append_plan(const fasn_kvcache_args* args, const fasn_
                                       const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
 int fasn_kvprefill_fp8_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
                                         const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
+
+/*
+ * FP8 K/V CACHE, TOKEN TREES (additions within ABI 6; no struct is new or changed): the token-tree calls above over the FP8 cache -
+ * speculative-decoding verification without dequantising the cache. Decode and prefill blocks only.
+ *
+ *   forward    fasn_fwd_kv{cache,prefill}_fp8_tree: fasn_fwd_kv{cache,prefill}_tree's rows, mask, visibility, positions, window and memory
+ *              contract with the FP8 call's values and scales. The plan is the 16-bit tree call's of the same shape and window - same
+ *              grids, same split counts, same workspace - with the FP8 kernels' LDS and combine kernels. The append without rotary is
+ *              fasn_kv{cache,prefill}_fp8_append.
+ *   rope       fasn_kv{cache,prefill}_fp8_tree_rope_append: fasn_kv{cache,prefill}_fp8_rope_append at DEPTH positions, ONE launch on the
+ *              grid of fasn_kv{cache,prefill}_tree_rope_append. Node i of k_new is written to cache row seqlens[b] + i but rotated at
+ *              seqlens[b] + d_i, rounded once to `dtype` and quantised with k_scale; v_new is quantised beside it; the query node is
+ *              rotated at p_i. tree->window takes no part. The *_fp8_tree_rope_append_plan calls write the launch as text.
+ *   commit     fasn_kvcache_fp8_tree_commit: fasn_kvcache_tree_commit over code rows, with the same fasn_kv_tree_commit block. D is 64
+ *              or 128 (anything else: FASN_EHEADDIM), k_stride / v_stride count codes and are multiples of 16 (FASN_EALIGN), the pools
+ *              are 16-byte aligned, reserved is 0; every other rule and code is that call's.
+ * Checks, in this order: the base call's, the FP8 operand's (as fasn_fwd_kv*_fp8), the tree operand's (as fasn_fwd_kv*_tree, the same
+ * codes), and on the rope calls the rope operand's. Not here: packed trees, ALiBi, D = 32 / 256, e5m2, gradients.
+ */
+size_t fasn_fwd_kvcache_fp8_tree_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_tree* tree);
+int fasn_fwd_kvcache_fp8_tree(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_tree* tree, void* workspace,
+                              size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvcache_fp8_tree_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_tree* tree, char* buf, size_t cap);
+size_t fasn_fwd_kvprefill_fp8_tree_workspace_bytes(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_tree* tree);
+int fasn_fwd_kvprefill_fp8_tree(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_tree* tree, void* workspace,
+                                size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kvprefill_fp8_tree_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_tree* tree, char* buf, size_t cap);
+int fasn_kvcache_fp8_tree_rope_append(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
+                                      const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvprefill_fp8_tree_rope_append(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
+                                        const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);
+int fasn_kvcache_fp8_tree_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
+                                           const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
+int fasn_kvprefill_fp8_tree_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
+                                             const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
+int fasn_kvcache_fp8_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t stream);
 
 /*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
