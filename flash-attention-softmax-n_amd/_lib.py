@@ -154,58 +154,67 @@ class FasnError(RuntimeError):
 _lib = None
 
 
+# The K/V-cache ABI (include/fasn.h) in one description, which _kv_bindings(), the *_plan helpers below and kvcache.py's _forward / _append
+# share. A name is the stem of its block plus a suffix made of the operands present: fasn_fwd_{stem}{suffix}[_workspace_bytes] and
+# fasn_{stem}{suffix}_plan for a forward - suffix _fp8, then one of _tree / _window / _alibi - and fasn_{stem}{suffix}_append[_plan] for an
+# append - suffix _fp8, _tree, then _rope. The operands follow the block in ABI order: a forward's in suffix order, an append's as
+# fp8, rope, tree - so the 16-bit tree rope append takes (rope, tree) and the FP8 one (fp8, rope, tree). The one irregularity: there is no
+# *_alibi_workspace_bytes, the ALiBi forward uses the base call's.
+_KV_BLOCK = {"kvcache": KvCacheArgs, "kvprefill": KvPrefillArgs, "kvvarlen": KvVarlenArgs}
+_KV_OPERAND = {"fp8": KvFp8, "tree": KvTree, "window": KvWindow, "alibi": AlibiSlopes, "rope": KvRope}
+_KV_FORWARD_SETS = ((), ("alibi",), ("window",), ("tree",), ("fp8",), ("fp8", "window"), ("fp8", "tree"))   # packed: the first and ("window",)
+_KV_APPENDS = (((), False), (("rope",), True), (("tree", "rope"), False), (("fp8",), False), (("fp8", "rope"), True),
+               (("fp8", "tree", "rope"), True))   # (operands in suffix order, has a *_plan); packed: the first two
+
+
+def kv_stem(args):
+    """the stem of the entry points that take the block `args`"""
+    return next((stem for stem, block in _KV_BLOCK.items() if isinstance(args, block)), "kvcache")
+
+
+def kv_forward_call(stem, fp8=None, tree=None, window=None, alibi=None):
+    """(workspace-bytes name, its operands, forward name, plan name, their operands in ABI order) of the forward of `stem` under the
+    operands that are not None: the FP8 operand, then the first there is of tree, window and ALiBi slopes"""
+    one = ("_tree", tree) if tree is not None else ("_window", window) if window is not None else ("_alibi", alibi) if alibi is not None else ("", None)
+    sfx = ("_fp8" if fp8 is not None else "") + one[0]
+    operands = tuple(o for o in (fp8, one[1]) if o is not None)
+    ws = (f"fasn_fwd_{stem}_workspace_bytes", ()) if sfx == "_alibi" else (f"fasn_fwd_{stem}{sfx}_workspace_bytes", operands)
+    return (*ws, f"fasn_fwd_{stem}{sfx}", f"fasn_{stem}{sfx}_plan", operands)
+
+
+def kv_append_call(stem, fp8=None, tree=None, rope=None):
+    """(name, operands in ABI order: fp8, rope, tree) of the append of `stem` under the operands that are not None; the tree counts under
+    rope only"""
+    tree = tree if rope is not None else None
+    sfx = ("_fp8" if fp8 is not None else "") + ("_tree" if tree is not None else "") + ("_rope" if rope is not None else "")
+    return f"fasn_{stem}{sfx}_append", tuple(o for o in (fp8, rope, tree) if o is not None)
+
+
 def _kv_bindings():
-    """(name, restype, argtypes) of the 69 K/V-cache entry points: each name for the decode block (fasn_kvcache_args) and for the prefill
-    block (fasn_kvprefill_args), `operands` come between the block and the tail; then the nine of the packed block (fasn_kvvarlen_args)
-    and the two commits of a token tree (16-bit and FP8 cache), which have a block of their own"""
+    """(name, restype, argtypes) of the 69 K/V-cache entry points, from the description above: per block the supported operand sets x
+    {workspace_bytes, forward, plan} and the append kinds x {call, plan where there is one}; then the two commits of a token tree (16-bit
+    and FP8 cache), which have a block of their own"""
     view, text = POINTER(View4), [c_char_p, c_size_t]
     launch = [c_void_p]                          # the stream
     forward = [c_void_p, c_size_t, c_void_p]     # workspace, its bytes, the stream
-    rope = [POINTER(KvRope), view, view, view]
-    for stem, block in (("kvcache", POINTER(KvCacheArgs)), ("kvprefill", POINTER(KvPrefillArgs))):
-        for name, restype, operands, tail in (
-                (f"fasn_fwd_{stem}_workspace_bytes", c_size_t, [], []),
-                (f"fasn_fwd_{stem}_window_workspace_bytes", c_size_t, [POINTER(KvWindow)], []),
-                (f"fasn_fwd_{stem}", c_int32, [], forward),
-                (f"fasn_fwd_{stem}_alibi", c_int32, [POINTER(AlibiSlopes)], forward),
-                (f"fasn_fwd_{stem}_window", c_int32, [POINTER(KvWindow)], forward),
-                (f"fasn_{stem}_append", c_int32, [view, view], launch),
-                (f"fasn_{stem}_rope_append", c_int32, rope, launch),
-                (f"fasn_{stem}_plan", c_int32, [], text),
-                (f"fasn_{stem}_alibi_plan", c_int32, [POINTER(AlibiSlopes)], text),
-                (f"fasn_{stem}_window_plan", c_int32, [POINTER(KvWindow)], text),
-                (f"fasn_{stem}_rope_append_plan", c_int32, rope, text),
-                (f"fasn_fwd_{stem}_tree_workspace_bytes", c_size_t, [POINTER(KvTree)], []),
-                (f"fasn_fwd_{stem}_tree", c_int32, [POINTER(KvTree)], forward),
-                (f"fasn_{stem}_tree_plan", c_int32, [POINTER(KvTree)], text),
-                (f"fasn_{stem}_tree_rope_append", c_int32, [POINTER(KvRope), POINTER(KvTree), view, view, view], launch),
-                (f"fasn_fwd_{stem}_fp8_workspace_bytes", c_size_t, [POINTER(KvFp8)], []),
-                (f"fasn_fwd_{stem}_fp8", c_int32, [POINTER(KvFp8)], forward),
-                (f"fasn_{stem}_fp8_plan", c_int32, [POINTER(KvFp8)], text),
-                (f"fasn_{stem}_fp8_append", c_int32, [POINTER(KvFp8), view, view], launch),
-                (f"fasn_fwd_{stem}_fp8_window_workspace_bytes", c_size_t, [POINTER(KvFp8), POINTER(KvWindow)], []),
-                (f"fasn_fwd_{stem}_fp8_window", c_int32, [POINTER(KvFp8), POINTER(KvWindow)], forward),
-                (f"fasn_{stem}_fp8_window_plan", c_int32, [POINTER(KvFp8), POINTER(KvWindow)], text),
-                (f"fasn_{stem}_fp8_rope_append", c_int32, [POINTER(KvFp8)] + rope, launch),
-                (f"fasn_{stem}_fp8_rope_append_plan", c_int32, [POINTER(KvFp8)] + rope, text),
-                (f"fasn_fwd_{stem}_fp8_tree_workspace_bytes", c_size_t, [POINTER(KvFp8), POINTER(KvTree)], []),
-                (f"fasn_fwd_{stem}_fp8_tree", c_int32, [POINTER(KvFp8), POINTER(KvTree)], forward),
-                (f"fasn_{stem}_fp8_tree_plan", c_int32, [POINTER(KvFp8), POINTER(KvTree)], text),
-                (f"fasn_{stem}_fp8_tree_rope_append", c_int32, [POINTER(KvFp8), POINTER(KvRope), POINTER(KvTree), view, view, view], launch),
-                (f"fasn_{stem}_fp8_tree_rope_append_plan", c_int32, [POINTER(KvFp8), POINTER(KvRope), POINTER(KvTree), view, view, view], text)):
-            yield name, restype, [block] + operands + tail
-    packed = [POINTER(KvVarlenArgs)]
-    yield "fasn_fwd_kvvarlen_workspace_bytes", c_size_t, packed
-    yield "fasn_fwd_kvvarlen", c_int32, packed + forward
-    yield "fasn_kvvarlen_append", c_int32, packed + [view, view] + launch
-    yield "fasn_kvvarlen_plan", c_int32, packed + text
-    yield "fasn_fwd_kvvarlen_window_workspace_bytes", c_size_t, packed + [POINTER(KvWindow)]
-    yield "fasn_fwd_kvvarlen_window", c_int32, packed + [POINTER(KvWindow)] + forward
-    yield "fasn_kvvarlen_window_plan", c_int32, packed + [POINTER(KvWindow)] + text
-    yield "fasn_kvvarlen_rope_append", c_int32, packed + rope + launch
-    yield "fasn_kvvarlen_rope_append_plan", c_int32, packed + rope + text
-    yield "fasn_kvcache_tree_commit", c_int32, [POINTER(KvTreeCommit)] + launch
-    yield "fasn_kvcache_fp8_tree_commit", c_int32, [POINTER(KvTreeCommit)] + launch
+    types = {o: POINTER(t) for o, t in _KV_OPERAND.items()}
+    for stem, block in _KV_BLOCK.items():
+        packed = stem == "kvvarlen"
+        for ops in (s for s in _KV_FORWARD_SETS if not packed or s in ((), ("window",))):
+            ws, _, fwd, plan, operands = kv_forward_call(stem, **{o: types[o] for o in ops})
+            head = [POINTER(block), *operands]
+            if ops != ("alibi",):   # (the base call's, yielded with it)
+                yield ws, c_size_t, head
+            yield fwd, c_int32, head + forward
+            yield plan, c_int32, head + text
+        for ops, has_plan in _KV_APPENDS[:2] if packed else _KV_APPENDS:
+            name, operands = kv_append_call(stem, **{o: types[o] for o in ops})
+            head = [POINTER(block), *operands] + [view] * (3 if "rope" in ops else 2)   # (q_out,) k_new, v_new
+            yield name, c_int32, head + launch
+            if has_plan:
+                yield f"{name}_plan", c_int32, head + text
+    for name in ("fasn_kvcache_tree_commit", "fasn_kvcache_fp8_tree_commit"):
+        yield name, c_int32, [POINTER(KvTreeCommit)] + launch
 
 
 def load():
@@ -318,85 +327,91 @@ def _kv_plan(what, *operands):
     return _plan_lines(buf)
 
 
+def _kv_forward_plan(stem, args, **operands):
+    *_, plan, ops = kv_forward_call(stem, **operands)
+    return _kv_plan(plan, args, *ops)
+
+
+def _kv_append_plan(args, q_out, k_new, v_new, **operands):
+    name, ops = kv_append_call(kv_stem(args), **operands)
+    return _kv_plan(f"{name}_plan", args, *ops, q_out, k_new, v_new)
+
+
 def kvcache_plan(args, alibi=None):
     """The kernels fasn_fwd_kvcache would launch for `args` (a KvCacheArgs), as launch_plan returns them; with `alibi` (an AlibiSlopes)
     those of fasn_fwd_kvcache_alibi. Nothing is launched."""
-    return _kv_plan("fasn_kvcache_plan", args) if alibi is None else _kv_plan("fasn_kvcache_alibi_plan", args, alibi)
+    return _kv_forward_plan("kvcache", args, alibi=alibi)
 
 
 def kvprefill_plan(args, alibi=None):
     """The kernels fasn_fwd_kvprefill would launch for `args` (a KvPrefillArgs), as launch_plan returns them; with `alibi` (an AlibiSlopes)
     those of fasn_fwd_kvprefill_alibi. Nothing is launched."""
-    return _kv_plan("fasn_kvprefill_plan", args) if alibi is None else _kv_plan("fasn_kvprefill_alibi_plan", args, alibi)
+    return _kv_forward_plan("kvprefill", args, alibi=alibi)
 
 
 def kvvarlen_plan(args):
     """The kernels fasn_fwd_kvvarlen would launch for `args` (a KvVarlenArgs), as launch_plan returns them. Nothing is launched."""
-    return _kv_plan("fasn_kvvarlen_plan", args)
+    return _kv_forward_plan("kvvarlen", args)
 
 
 def kvvarlen_window_plan(args, win):
     """The kernels fasn_fwd_kvvarlen_window would launch for `args` (a KvVarlenArgs) under `win` (a KvWindow), as launch_plan returns
     them. Nothing is launched."""
-    return _kv_plan("fasn_kvvarlen_window_plan", args, win)
+    return _kv_forward_plan("kvvarlen", args, window=win)
 
 
 def kvcache_window_plan(args, win):
     """The kernels fasn_fwd_kvcache_window would launch for `args` (a KvCacheArgs) under `win` (a KvWindow), as launch_plan returns them.
     Nothing is launched."""
-    return _kv_plan("fasn_kvcache_window_plan", args, win)
+    return _kv_forward_plan("kvcache", args, window=win)
 
 
 def kvprefill_window_plan(args, win):
     """The kernels fasn_fwd_kvprefill_window would launch for `args` (a KvPrefillArgs) under `win` (a KvWindow), as launch_plan returns
     them. Nothing is launched."""
-    return _kv_plan("fasn_kvprefill_window_plan", args, win)
+    return _kv_forward_plan("kvprefill", args, window=win)
 
 
 def kvtree_plan(args, tree):
     """The kernels fasn_fwd_kvcache_tree (`args` a KvCacheArgs) or fasn_fwd_kvprefill_tree (a KvPrefillArgs) would launch under `tree` (a
     KvTree), as launch_plan returns them. Nothing is launched."""
-    return _kv_plan("fasn_kvprefill_tree_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_tree_plan", args, tree)
+    return _kv_forward_plan(kv_stem(args), args, tree=tree)
 
 
 def kvfp8_plan(args, fp8):
     """The kernels fasn_fwd_kvcache_fp8 (`args` a KvCacheArgs) or fasn_fwd_kvprefill_fp8 (a KvPrefillArgs) would launch under `fp8` (a
     KvFp8), as launch_plan returns them. Nothing is launched."""
-    return _kv_plan("fasn_kvprefill_fp8_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_plan", args, fp8)
+    return _kv_forward_plan(kv_stem(args), args, fp8=fp8)
 
 
 def kvfp8_window_plan(args, fp8, win):
     """The kernels fasn_fwd_kvcache_fp8_window (`args` a KvCacheArgs) or fasn_fwd_kvprefill_fp8_window (a KvPrefillArgs) would launch under
     `fp8` (a KvFp8) and `win` (a KvWindow), as launch_plan returns them. Nothing is launched."""
-    return _kv_plan("fasn_kvprefill_fp8_window_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_window_plan", args, fp8, win)
+    return _kv_forward_plan(kv_stem(args), args, fp8=fp8, window=win)
 
 
 def kvfp8_rope_plan(args, fp8, rope, q_out, k_new=None, v_new=None):
     """The one launch of fasn_kvcache_fp8_rope_append (`args` a KvCacheArgs) or fasn_kvprefill_fp8_rope_append (a KvPrefillArgs) under `fp8`
     (a KvFp8) and `rope` (a KvRope), as launch_plan returns it. Nothing is launched."""
-    what = "fasn_kvprefill_fp8_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_rope_append_plan"
-    return _kv_plan(what, args, fp8, rope, q_out, k_new, v_new)
+    return _kv_append_plan(args, q_out, k_new, v_new, fp8=fp8, rope=rope)
 
 
 def kvfp8_tree_plan(args, fp8, tree):
     """The kernels fasn_fwd_kvcache_fp8_tree (`args` a KvCacheArgs) or fasn_fwd_kvprefill_fp8_tree (a KvPrefillArgs) would launch under `fp8`
     (a KvFp8) and `tree` (a KvTree), as launch_plan returns them. Nothing is launched."""
-    return _kv_plan("fasn_kvprefill_fp8_tree_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_tree_plan", args, fp8, tree)
+    return _kv_forward_plan(kv_stem(args), args, fp8=fp8, tree=tree)
 
 
 def kvfp8_tree_rope_plan(args, fp8, rope, tree, q_out, k_new=None, v_new=None):
     """The one launch of fasn_kvcache_fp8_tree_rope_append (`args` a KvCacheArgs) or fasn_kvprefill_fp8_tree_rope_append (a KvPrefillArgs)
     under `fp8` (a KvFp8), `rope` (a KvRope) and `tree` (a KvTree), as launch_plan returns it. Nothing is launched."""
-    what = "fasn_kvprefill_fp8_tree_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_fp8_tree_rope_append_plan"
-    return _kv_plan(what, args, fp8, rope, tree, q_out, k_new, v_new)
+    return _kv_append_plan(args, q_out, k_new, v_new, fp8=fp8, rope=rope, tree=tree)
 
 
 def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):
     """The one launch of fasn_kvcache_rope_append (`args` a KvCacheArgs), fasn_kvprefill_rope_append (a KvPrefillArgs) or
     fasn_kvvarlen_rope_append (a KvVarlenArgs) under `rope` (a KvRope), as launch_plan returns it. Nothing is launched."""
-    what = ("fasn_kvvarlen_rope_append_plan" if isinstance(args, KvVarlenArgs) else
-            "fasn_kvprefill_rope_append_plan" if isinstance(args, KvPrefillArgs) else "fasn_kvcache_rope_append_plan")
-    return _kv_plan(what, args, rope, q_out, k_new, v_new)
+    return _kv_append_plan(args, q_out, k_new, v_new, rope=rope)
 
 
 def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):

@@ -1,8 +1,8 @@
 // fasn_kv_host.h — the ONE host layer of the K/V-cache family (decode, prefill, packed prefill, rotary append): argument checks, parameter
-// packing, the launch plan, the workspace rule, the launch recorder and the dtype x head-dim dispatch. fasn_kvcache.hip defines what is
-// declared here; fasn_kvcache.hip, fasn_kvprefill.hip, fasn_kvvarlen.hip, fasn_kvrope.hip and fasn_kvfp8.hip each instantiate and launch the
-// kernels of their own header (fasn_kvrope.hip: also the packed rotary append, fasn_kvvarlen.hip: also the packed window forward,
-// fasn_kvfp8.hip: the decode and the prefill call over an FP8 cache).
+// packing, the operand set of a call (KvOps) with its one check order and its table of supported sets, the launch plan, the workspace
+// rule, the one forward / plan / workspace path, the token-tree commit, the launch recorder and the dtype x head-dim dispatch.
+// fasn_kvcache.hip defines what is declared here, but for the forward launchers: fasn_kvcache.hip, fasn_kvprefill.hip, fasn_kvvarlen.hip
+// and fasn_kvfp8.hip each define the launcher of the kernels they instantiate (fasn_kvrope.hip: the rotary appends of every call).
 #pragma once
 #include <type_traits>
 #include "fasn.h"
@@ -26,26 +26,47 @@ inline KvArgs kv_args(const fasn_kvcache_args* a) { return {a, nullptr, KV_DECOD
 inline KvArgs kv_args(const fasn_kvprefill_args* pa) { return {pa != nullptr ? &pa->kv : nullptr, pa != nullptr ? pa->q_seqlens : nullptr, KV_PREFILL, nullptr}; }
 inline KvArgs kv_args(const fasn_kvvarlen_args* va) { return {va != nullptr ? &va->pf.kv : nullptr, va != nullptr ? va->pf.q_seqlens : nullptr, KV_VARLEN, va}; }
 
-// what a forward launches with: the parameters, the variant and its operand
+// The operands of a call beside its block, as a set. `takes` says which operands the entry point HAS; a NULL pointer of an operand it
+// takes is refused by that operand's own rule, never read as "none". kv_ops(typed pointers...) builds one from what an entry point got.
+enum : unsigned { KV_OP_ALIBI = 1, KV_OP_WINDOW = 2, KV_OP_TREE = 4, KV_OP_FP8 = 8 };
+struct KvOps {
+    unsigned takes;
+    const fasn_alibi_slopes* alibi;
+    const fasn_kv_window* window;
+    const fasn_kv_tree* tree;
+    const fasn_kv_fp8* fp8;
+};
+inline void kv_op(KvOps& o, const fasn_alibi_slopes* p) { o.takes |= KV_OP_ALIBI, o.alibi = p; }
+inline void kv_op(KvOps& o, const fasn_kv_window* p) { o.takes |= KV_OP_WINDOW, o.window = p; }
+inline void kv_op(KvOps& o, const fasn_kv_tree* p) { o.takes |= KV_OP_TREE, o.tree = p; }
+inline void kv_op(KvOps& o, const fasn_kv_fp8* p) { o.takes |= KV_OP_FP8, o.fp8 = p; }
+template <typename... P>
+KvOps kv_ops(const P*... p) {
+    KvOps o{};
+    (kv_op(o, p), ...);
+    return o;
+}
+
+// The operand sets a forward has kernels for, stated once: every other set is FASN_EUNSUPPORTED, behind the base checks. Decode and
+// prefill have the sets of kKvOpSets; the packed call (KV_VARLEN) has the base and the window kernels only.
+constexpr unsigned kKvOpSets[] = {0, KV_OP_ALIBI, KV_OP_WINDOW, KV_OP_TREE, KV_OP_FP8, KV_OP_FP8 | KV_OP_WINDOW, KV_OP_FP8 | KV_OP_TREE};
+constexpr bool kv_ops_supported(KvCall call, unsigned takes) {
+    if (call == KV_VARLEN) return takes == 0 || takes == KV_OP_WINDOW;
+    for (unsigned s : kKvOpSets)
+        if (s == takes) return true;
+    return false;
+}
+
+// what a forward launches with: the parameters, the operand set (KvOps::takes) and the operands as the kernels take them
 struct KvFwd {
     KvPrefillParams pp;
-    KvVariant variant;
-    KvAlibi al;
-    KvWindow kw;
+    unsigned ops;
+    int dtype, D;         // the block's: what the launchers dispatch on
+    KvAlibi al;           // KV_OP_ALIBI
+    KvWindow kw;          // KV_OP_WINDOW
     KvPacked pk;          // KV_VARLEN only
-    KvTree kt;            // KV_TREE and KV_FP8_TREE
-    KvFp8 f8;             // KV_FP8, KV_FP8_WINDOW (which fills kw too) and KV_FP8_TREE (which fills kt too)
-};
-// the operand of KV_FP8_WINDOW: the two operands its entry points take, checked in this order
-struct KvFp8Window {
-    const fasn_kv_fp8* fp8;
-    const fasn_kv_window* window;
-};
-
-// the operand of KV_FP8_TREE, likewise: the FP8 operand's checks, then the tree operand's
-struct KvFp8Tree {
-    const fasn_kv_fp8* fp8;
-    const fasn_kv_tree* tree;
+    KvTree kt;            // KV_OP_TREE
+    KvFp8 f8;             // KV_OP_FP8
 };
 
 inline bool kv_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
@@ -54,7 +75,6 @@ int kv_check_view(const fasn_view4& v);                                     // t
 int kv_build(const KvArgs& in, KvPrefillParams& pp, KvPacked* pk = nullptr);
 int kv_pack_new(const fasn_view4& k_new, const fasn_view4& v_new, KvParams& p);   // the views' checks, then p.kn / vn / kns / vns
 int kv_build_append(const KvArgs& in, const fasn_view4* k_new, const fasn_view4* v_new, KvPrefillParams& pp, KvPacked* pk = nullptr);
-size_t kv_workspace_bytes(const KvArgs& in, KvVariant variant, const void* operand);
 // the token-tree operand's checks, behind the base arguments' (the tree forwards and the tree rotary appends share them): `kt` with the
 // window as the kernels take it - capacity + 1 when there is none
 int kv_check_tree(const fasn_kvcache_args* a, const fasn_kv_tree* t, int capacity, KvTree& kt);
@@ -64,9 +84,23 @@ int kv_check_fp8(const fasn_kvcache_args* a, const fasn_kv_fp8* o, KvFp8& f8);
 // the checks of a fasn_kv_tree_commit block and the kernel's parameters (no HIP call). `fp8`: the cache holds codes - strides count bytes
 // and follow the FP8 calls' 16-byte rule, D is 64 or 128
 int kv_build_commit(const fasn_kv_tree_commit* a, bool fp8, KvCommit& c);
-// everything a forward does before its launches: base checks, the variant's operand (nothing, a fasn_alibi_slopes, a fasn_kv_window, a
-// fasn_kv_tree, a fasn_kv_fp8), then the workspace
-int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, KvFwd& f);
+// The one forward path. Behind the base checks the operands are checked in ONE order, each at most once - FP8, tree, window, ALiBi - then
+// the workspace; then the launcher of the call's translation unit runs. kv_forward_plan is the same call under the launch recorder.
+size_t kv_workspace_bytes(const KvArgs& in, const KvOps& ops);
+int kv_forward(const KvArgs& in, const KvOps& ops, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int kv_forward_plan(const KvArgs& in, const KvOps& ops, char* buf, size_t cap);
+// The launchers, each defined beside the kernels it instantiates: it picks the kernel of f.ops among those its translation unit holds
+// and adds the combine (decode: always; prefill and packed: when there is more than one split).
+int kv_launch_decode(const KvFwd& f, hipStream_t s);        // fasn_kvcache.hip
+int kv_launch_prefill(const KvFwd& f, hipStream_t s);       // fasn_kvprefill.hip
+int kv_launch_packed(const KvFwd& f, hipStream_t s);        // fasn_kvvarlen.hip
+int kv_launch_fp8_decode(const KvFwd& f, hipStream_t s);    // fasn_kvfp8.hip
+int kv_launch_fp8_prefill(const KvFwd& f, hipStream_t s);   // fasn_kvfp8.hip
+// fasn_kvcache_tree_commit / fasn_kvcache_fp8_tree_commit: kv_build_commit, the grid (a thread per 16-byte chunk of a row: D / 8 elements,
+// D / 16 codes), then the one launch from the kernel's translation unit
+int kv_commit(const fasn_kv_tree_commit* a, bool fp8, fasn_stream_t stream);
+int kv_launch_commit(const KvCommit& c, int D, unsigned grid, hipStream_t s);       // fasn_kvcache.hip
+int kv_launch_fp8_commit(const KvCommit& c, int D, unsigned grid, hipStream_t s);   // fasn_kvfp8.hip
 
 // dtype x head dim -> f(tag, std::integral_constant<int, D>) (kv_build let only these four head dims through)
 template <typename F>
@@ -84,27 +118,18 @@ int kv_dispatch(int dtype, int D, F f) {
     return kv_dispatch_d(D, [&](auto d) { return f(f16_tag{}, d); });
 }
 
-// The forward kernel of f.variant - the base kernel, or its ALiBi or window sibling on the same grid and LDS. `p` is what the kernels
-// take first: f.pp.kv (decode) or f.pp (prefill).
-template <auto Base, auto Alibi, auto Window, typename P>
-void kv_launch_variant(const KvFwd& f, const P& p, unsigned grid, int smem, hipStream_t s) {
-    if (f.variant == KV_WINDOW) {
-        ensure_smem<Window>(smem);
-        FASN_LAUNCH(Window, dim3(grid), dim3(256), smem, s, p, f.kw);
-    } else if (f.variant == KV_ALIBI) {
-        ensure_smem<Alibi>(smem);
-        FASN_LAUNCH(Alibi, dim3(grid), dim3(256), smem, s, p, f.al);
-    } else {
-        ensure_smem<Base>(smem);
-        FASN_LAUNCH(Base, dim3(grid), dim3(256), smem, s, p);
-    }
+// dtype x the two head dims the FP8 kernels are built for (kv_check_fp8 let only these through)
+template <typename F>
+int kv8_dispatch(int dtype, int D, F f) {
+    if (dtype == FASN_DTYPE_BF16) return D == 64 ? f(bf16_tag{}, std::integral_constant<int, 64>{}) : f(bf16_tag{}, std::integral_constant<int, 128>{});
+    return D == 64 ? f(f16_tag{}, std::integral_constant<int, 64>{}) : f(f16_tag{}, std::integral_constant<int, 128>{});
 }
 
-// ... and its token-tree sibling (KV_TREE), on the same grid and LDS: no packed call has one, so it stays out of the list above
-template <auto Tree, typename P>
-void kv_launch_tree(const KvFwd& f, const P& p, unsigned grid, int smem, hipStream_t s) {
-    ensure_smem<Tree>(smem);
-    FASN_LAUNCH(Tree, dim3(grid), dim3(256), smem, s, p, f.kt);
+// the one launch of the family's kernels with their trailing arguments: workgroups of 256, the dynamic-LDS attribute where it is needed
+template <auto Kern, typename... A>
+void kv_launch(unsigned grid, int smem, hipStream_t s, const A&... a) {
+    ensure_smem<Kern>(smem);
+    FASN_LAUNCH(Kern, dim3(grid), dim3(256), smem, s, a...);
 }
 
 // A call's launches as text: the call itself under the launch recorder (nothing is launched, no device is touched). The forwards are

@@ -141,10 +141,6 @@ struct KvFp8 {
     int vsb, vsh;
 };
 constexpr bool kv_fp8_head_dim_ok(int D) { return D == 64 || D == 128; }
-// which forward kernel a call launches; its operand is nothing, a fasn_alibi_slopes, a fasn_kv_window, a fasn_kv_tree, a fasn_kv_fp8 or
-// (KV_FP8_WINDOW: the sliding window over an FP8 cache) the pair of a fasn_kv_fp8 and a fasn_kv_window (fasn_kv_host.h: KvFp8Window) or
-// (KV_FP8_TREE: the token tree over an FP8 cache) the pair of a fasn_kv_fp8 and a fasn_kv_tree (fasn_kv_host.h: KvFp8Tree)
-enum KvVariant { KV_BASE, KV_ALIBI, KV_WINDOW, KV_TREE, KV_FP8, KV_FP8_WINDOW, KV_FP8_TREE };
 
 // fasn_kvcache_fwd_kernel<Tag, D>(KvParams), fasn_kvcache_fwd_alibi_kernel<Tag, D>(KvParams, KvAlibi) and
 // fasn_kvcache_fwd_window_kernel<Tag, D>(KvParams, KvWindow): one text, compiled three times.

@@ -1,8 +1,9 @@
 // K/V-cache forward (include/fasn.h: fasn_fwd_kvcache[_alibi|_window|_tree], fasn_kvcache_append, fasn_kvcache[_alibi|_window|_tree]_plan,
 // fasn_kvcache_tree_commit), in two parts:
-//   1. the host layer of the whole K/V-cache family (fasn_kv_host.h declares it; fasn_kvprefill.hip, fasn_kvvarlen.hip and fasn_kvrope.hip call it): argument
-//      checks, parameter packing, the launch plan - which depends on shapes and capacity only, never on the lengths in device memory -
-//      the operand checks of the ALiBi, window, tree and FP8 variants and the workspace rule;
+//   1. the host layer of the whole K/V-cache family (fasn_kv_host.h declares it; fasn_kvprefill.hip, fasn_kvvarlen.hip, fasn_kvfp8.hip and
+//      fasn_kvrope.hip call it): argument checks, parameter packing, the launch plan - which depends on shapes and capacity only, never on
+//      the lengths in device memory - the check of a call's operand set (kv_build_ops: FP8, tree, window, ALiBi, in this order), the
+//      workspace rule, the one forward / plan path of every call and the token-tree commit;
 //   2. the decode entry points and the launches of fasn_kvcache.h.
 #include <limits.h>
 #include <math.h>
@@ -201,40 +202,23 @@ int kv_build_window(const fasn_kvcache_args* a, const fasn_kv_window* w, int64_t
     return FASN_OK;
 }
 
-int kv_build_variant(const KvArgs& in, KvVariant variant, const void* operand, KvFwd& f) {
+// Behind the base checks: is there a kernel for this operand set (kv_ops_supported), then each operand the entry point takes, at most
+// once and in ONE order - FP8, tree, window, ALiBi. The window's and the tree's plan count the same blocks.
+int kv_build_ops(const KvArgs& in, const KvOps& o, KvFwd& f) {
     f.pk = KvPacked{};
     int rc = kv_build(in, f.pp, &f.pk);
     if (rc) return rc;
-    f.variant = variant;
+    f.ops = o.takes, f.dtype = in.a->dtype, f.D = in.a->D;
     f.al = KvAlibi{};
     f.kw = KvWindow{};
     f.kt = KvTree{};
     f.f8 = KvFp8{};
-    if (variant == KV_FP8) {   // (decode and prefill only: there is no packed FP8 call)
-        if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
-        return kv_check_fp8(in.a, static_cast<const fasn_kv_fp8*>(operand), f.f8);
-    }
-    if (variant == KV_FP8_WINDOW) {   // the FP8 operand's checks, then the window's rule and its plan: the 16-bit window call's
-        if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
-        const KvFp8Window* const o = static_cast<const KvFp8Window*>(operand);
-        if ((rc = kv_check_fp8(in.a, o->fp8, f.f8))) return rc;
-        return kv_build_window(in.a, o->window, (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kw);
-    }
-    if (variant == KV_FP8_TREE) {   // the FP8 operand's checks, then the tree operand's and its plan: the 16-bit tree call's
-        if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
-        const KvFp8Tree* const o = static_cast<const KvFp8Tree*>(operand);
-        if ((rc = kv_check_fp8(in.a, o->fp8, f.f8))) return rc;
-        return kv_build_tree(in.a, o->tree, (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kt);
-    }
-    if (variant == KV_TREE) {   // (decode and prefill only: there is no packed tree call)
-        if (in.call == KV_VARLEN) return FASN_EUNSUPPORTED;
-        return kv_build_tree(in.a, static_cast<const fasn_kv_tree*>(operand), (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb, f.pp, f.kt);
-    }
-    if (variant == KV_ALIBI) return kv_build_alibi(in.a, static_cast<const fasn_alibi_slopes*>(operand), f.al);
-    if (variant == KV_WINDOW) {
-        const int64_t blocks = in.call == KV_VARLEN ? (int64_t)f.pk.items_max * f.pp.kv.Hkv : (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb;
-        return kv_build_window(in.a, static_cast<const fasn_kv_window*>(operand), blocks, f.pp, f.kw);
-    }
+    if (!kv_ops_supported(in.call, o.takes)) return FASN_EUNSUPPORTED;
+    const int64_t blocks = in.call == KV_VARLEN ? (int64_t)f.pk.items_max * f.pp.kv.Hkv : (int64_t)f.pp.kv.B * f.pp.kv.Hkv * f.pp.nrb;
+    if ((o.takes & KV_OP_FP8) && (rc = kv_check_fp8(in.a, o.fp8, f.f8))) return rc;
+    if ((o.takes & KV_OP_TREE) && (rc = kv_build_tree(in.a, o.tree, blocks, f.pp, f.kt))) return rc;
+    if ((o.takes & KV_OP_WINDOW) && (rc = kv_build_window(in.a, o.window, blocks, f.pp, f.kw))) return rc;
+    if ((o.takes & KV_OP_ALIBI) && (rc = kv_build_alibi(in.a, o.alibi, f.al))) return rc;
     return FASN_OK;
 }
 
@@ -251,16 +235,9 @@ size_t kv_ws_bytes(KvCall call, const KvFwd& f, int D) {
     return kv_sched_bytes(call, f) + kv_part_elems(call, f) * (size_t)(D + 2) * sizeof(float);
 }
 
-}  // namespace
-
-size_t kv_workspace_bytes(const KvArgs& in, KvVariant variant, const void* operand) {
-    KvFwd f;
-    if (kv_build_variant(in, variant, operand, f) != FASN_OK) return 0;
-    return kv_ws_bytes(in.call, f, in.a->D);
-}
-
-int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, KvFwd& f) {
-    const int rc = kv_build_variant(in, variant, operand, f);
+// everything a forward does before its launches: base checks, the operands, then the workspace
+int kv_build_forward(const KvArgs& in, const KvOps& ops, void* workspace, size_t workspace_bytes, KvFwd& f) {
+    const int rc = kv_build_ops(in, ops, f);
     if (rc) return rc;
     const size_t need = kv_ws_bytes(in.call, f, in.a->D);
     if (need > 0) {   // (nothing to write beside o / lse: a NULL workspace is fine)
@@ -272,6 +249,29 @@ int kv_build_forward(const KvArgs& in, KvVariant variant, const void* operand, v
         f.pp.kv.part_ml = f.pp.kv.part_o + kv_part_elems(in.call, f) * in.a->D;
     }
     return FASN_OK;
+}
+
+}  // namespace
+
+size_t kv_workspace_bytes(const KvArgs& in, const KvOps& ops) {
+    KvFwd f;
+    if (kv_build_ops(in, ops, f) != FASN_OK) return 0;
+    return kv_ws_bytes(in.call, f, in.a->D);
+}
+
+int kv_forward(const KvArgs& in, const KvOps& ops, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    KvFwd f;
+    const int rc = kv_build_forward(in, ops, workspace, workspace_bytes, f);
+    if (rc) return rc;
+    const hipStream_t s = (hipStream_t)stream;
+    const bool fp8 = (f.ops & KV_OP_FP8) != 0;
+    if (in.call == KV_VARLEN) return kv_launch_packed(f, s);
+    if (in.call == KV_PREFILL) return fp8 ? kv_launch_fp8_prefill(f, s) : kv_launch_prefill(f, s);
+    return fp8 ? kv_launch_fp8_decode(f, s) : kv_launch_decode(f, s);
+}
+
+int kv_forward_plan(const KvArgs& in, const KvOps& ops, char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kv_forward(in, ops, kv_plan_workspace(), ~size_t(0), nullptr); });
 }
 
 // fasn_kvcache_tree_commit / fasn_kvcache_fp8_tree_commit: the cache's rules as kv_build states them for the members this block has (an FP8
@@ -315,16 +315,26 @@ int kv_build_commit(const fasn_kv_tree_commit* a, bool fp8, KvCommit& c) {
     return FASN_OK;
 }
 
+int kv_commit(const fasn_kv_tree_commit* a, bool fp8, fasn_stream_t stream) {
+    KvCommit c{};
+    const int rc = kv_build_commit(a, fp8, c);
+    if (rc) return rc;
+    const int64_t nthr = (int64_t)c.B * c.Hkv * (a->D / (fp8 ? 16 : 8));
+    if ((nthr + 255) / 256 > INT_MAX) return FASN_EINVAL;
+    const unsigned grid = (unsigned)((nthr + 255) / 256);
+    return fp8 ? kv_launch_fp8_commit(c, a->D, grid, (hipStream_t)stream) : kv_launch_commit(c, a->D, grid, (hipStream_t)stream);
+}
+
 namespace {
 
 template <typename Tag, int D>
-int kv_launch_fwd(const KvFwd& f, hipStream_t s) {
+int kv_launch_decode_as(const KvFwd& f, hipStream_t s) {
     const KvParams& p = f.pp.kv;
-    if (f.variant == KV_TREE)
-        kv_launch_tree<&fasn_kvcache_fwd_tree_kernel<Tag, D>>(f, p, (unsigned)(p.B * p.Hkv * p.nsplit), kv_smem(D), s);
-    else
-        kv_launch_variant<&fasn_kvcache_fwd_kernel<Tag, D>, &fasn_kvcache_fwd_alibi_kernel<Tag, D>, &fasn_kvcache_fwd_window_kernel<Tag, D>>(
-            f, p, (unsigned)(p.B * p.Hkv * p.nsplit), kv_smem(D), s);
+    const unsigned grid = (unsigned)(p.B * p.Hkv * p.nsplit);
+    if (f.ops == KV_OP_TREE) kv_launch<&fasn_kvcache_fwd_tree_kernel<Tag, D>>(grid, kv_smem(D), s, p, f.kt);
+    else if (f.ops == KV_OP_WINDOW) kv_launch<&fasn_kvcache_fwd_window_kernel<Tag, D>>(grid, kv_smem(D), s, p, f.kw);
+    else if (f.ops == KV_OP_ALIBI) kv_launch<&fasn_kvcache_fwd_alibi_kernel<Tag, D>>(grid, kv_smem(D), s, p, f.al);
+    else kv_launch<&fasn_kvcache_fwd_kernel<Tag, D>>(grid, kv_smem(D), s, p);
     const int64_t nthr = (int64_t)p.B * p.Hkv * p.R * (D / 4);
     FASN_LAUNCH((fasn_kvcache_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
@@ -335,88 +345,75 @@ int kv_launch_append(const KvParams& p, hipStream_t s) {
     FASN_LAUNCH((fasn_kvcache_append_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
 }
-
-int kv_forward(const fasn_kvcache_args* args, KvVariant variant, const void* operand, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    KvFwd f;
-    const int rc = kv_build_forward(kv_args(args), variant, operand, workspace, workspace_bytes, f);
-    if (rc) return rc;
-    return kv_dispatch(args->dtype, args->D, [&](auto tag, auto d) { return kv_launch_fwd<decltype(tag), decltype(d)::value>(f, (hipStream_t)stream); });
-}
 int kv_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
     KvPrefillParams pp;
     const int rc = kv_build_append(kv_args(args), k_new, v_new, pp);
     if (rc) return rc;
     return kv_dispatch_d(args->D, [&](auto d) { return kv_launch_append<decltype(d)::value>(pp.kv, (hipStream_t)stream); });
 }
-int kv_forward_plan(const fasn_kvcache_args* args, KvVariant variant, const void* operand, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kv_forward(args, variant, operand, kv_plan_workspace(), ~size_t(0), nullptr); });
-}
-
-template <int D>
-int kv_launch_commit(const KvCommit& c, hipStream_t s) {
-    const int64_t nthr = (int64_t)c.B * c.Hkv * (D / 8);
-    if ((nthr + 255) / 256 > INT_MAX) return FASN_EINVAL;
-    FASN_LAUNCH((fasn_kvcache_tree_commit_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, c);
-    return launch_rc();
-}
-int kv_commit(const fasn_kv_tree_commit* a, fasn_stream_t stream) {
-    KvCommit c{};
-    const int rc = kv_build_commit(a, false, c);
-    if (rc) return rc;
-    return kv_dispatch_d(a->D, [&](auto d) { return kv_launch_commit<decltype(d)::value>(c, (hipStream_t)stream); });
-}
 
 }  // namespace
+
+int kv_launch_decode(const KvFwd& f, hipStream_t s) {
+    return kv_dispatch(f.dtype, f.D, [&](auto tag, auto d) { return kv_launch_decode_as<decltype(tag), decltype(d)::value>(f, s); });
+}
+int kv_launch_commit(const KvCommit& c, int D, unsigned grid, hipStream_t s) {
+    return kv_dispatch_d(D, [&](auto d) {
+        kv_launch<&fasn_kvcache_tree_commit_kernel<decltype(d)::value>>(grid, 0, s, c);
+        return launch_rc();
+    });
+}
+
 }  // namespace fasn
 
 using namespace fasn;
 
 extern "C" {
 
-size_t fasn_fwd_kvcache_workspace_bytes(const fasn_kvcache_args* args) { return kv_workspace_bytes(kv_args(args), KV_BASE, nullptr); }
+size_t fasn_fwd_kvcache_workspace_bytes(const fasn_kvcache_args* args) { return kv_workspace_bytes(kv_args(args), kv_ops()); }
 
 int fasn_fwd_kvcache(const fasn_kvcache_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kv_forward(args, KV_BASE, nullptr, workspace, workspace_bytes, stream);
+    return kv_forward(kv_args(args), kv_ops(), workspace, workspace_bytes, stream);
 }
 
 int fasn_fwd_kvcache_alibi(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kv_forward(args, KV_ALIBI, alibi, workspace, workspace_bytes, stream);
+    return kv_forward(kv_args(args), kv_ops(alibi), workspace, workspace_bytes, stream);
 }
 
 size_t fasn_fwd_kvcache_window_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_window* window) {
-    return kv_workspace_bytes(kv_args(args), KV_WINDOW, window);
+    return kv_workspace_bytes(kv_args(args), kv_ops(window));
 }
 
 int fasn_fwd_kvcache_window(const fasn_kvcache_args* args, const fasn_kv_window* window, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kv_forward(args, KV_WINDOW, window, workspace, workspace_bytes, stream);
+    return kv_forward(kv_args(args), kv_ops(window), workspace, workspace_bytes, stream);
 }
 
 int fasn_kvcache_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
     return kv_append(args, k_new, v_new, stream);
 }
 
-int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) { return kv_forward_plan(args, KV_BASE, nullptr, buf, cap); }
+int fasn_kvcache_plan(const fasn_kvcache_args* args, char* buf, size_t cap) { return kv_forward_plan(kv_args(args), kv_ops(), buf, cap); }
 
 int fasn_kvcache_alibi_plan(const fasn_kvcache_args* args, const fasn_alibi_slopes* alibi, char* buf, size_t cap) {
-    return kv_forward_plan(args, KV_ALIBI, alibi, buf, cap);
+    return kv_forward_plan(kv_args(args), kv_ops(alibi), buf, cap);
 }
 
 int fasn_kvcache_window_plan(const fasn_kvcache_args* args, const fasn_kv_window* window, char* buf, size_t cap) {
-    return kv_forward_plan(args, KV_WINDOW, window, buf, cap);
+    return kv_forward_plan(kv_args(args), kv_ops(window), buf, cap);
 }
 
 size_t fasn_fwd_kvcache_tree_workspace_bytes(const fasn_kvcache_args* args, const fasn_kv_tree* tree) {
-    return kv_workspace_bytes(kv_args(args), KV_TREE, tree);
+    return kv_workspace_bytes(kv_args(args), kv_ops(tree));
 }
 
 int fasn_fwd_kvcache_tree(const fasn_kvcache_args* args, const fasn_kv_tree* tree, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return kv_forward(args, KV_TREE, tree, workspace, workspace_bytes, stream);
+    return kv_forward(kv_args(args), kv_ops(tree), workspace, workspace_bytes, stream);
 }
 
 int fasn_kvcache_tree_plan(const fasn_kvcache_args* args, const fasn_kv_tree* tree, char* buf, size_t cap) {
-    return kv_forward_plan(args, KV_TREE, tree, buf, cap);
+    return kv_forward_plan(kv_args(args), kv_ops(tree), buf, cap);
 }
 
-int fasn_kvcache_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t stream) { return kv_commit(commit, stream); }
+int fasn_kvcache_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t stream) { return kv_commit(commit, false, stream); }
 
 }  // extern "C"

@@ -1,10 +1,9 @@
-// Rotary rotate-and-append on the K/V-cache calls (include/fasn.h: fasn_kvcache_rope_append, fasn_kvprefill_rope_append,
-// fasn_kvvarlen_rope_append and their *_plan siblings, fasn_kvcache_tree_rope_append / fasn_kvprefill_tree_rope_append, and
-// fasn_kvcache_fp8_rope_append / fasn_kvprefill_fp8_rope_append with their *_plan siblings - the rotate-quantise-append in front of an FP8
-// cache, whose FP8 operand is checked behind the base arguments and in front of the rope operand - and fasn_kvcache_fp8_tree_rope_append /
-// fasn_kvprefill_fp8_tree_rope_append, the same at the depth positions of a token tree: base, FP8 operand, tree operand, rope operand): the base call's argument checks first
-// (the family's, fasn_kv_host.h), then the operand's, which live here, and the one launch of fasn_kvrope.h (the FP8 sibling: of
-// fasn_kvfp8.h) - whose grid depends on shapes only, never on the lengths in device memory.
+// Rotary rotate-and-append on the K/V-cache calls (include/fasn.h: fasn_{kvcache,kvprefill,kvvarlen}_rope_append, the decode and prefill
+// calls' *_tree_rope_append - the rotation at the depth positions of a token tree - and their *_fp8_rope_append / *_fp8_tree_rope_append,
+// the rotate-quantise-append in front of an FP8 cache; with the *_plan siblings they have): ONE call path, kvr_call, which takes the
+// operand set (FP8 and / or tree) beside the rope operand. The base call's argument checks and the FP8 and tree operands' checks are the
+// family's (fasn_kv_host.h), the rope operand's live here, and the one launch is of fasn_kvrope.h or, over an FP8 cache, of fasn_kvfp8.h -
+// its grid depends on shapes only, never on the lengths in device memory.
 #include <limits.h>
 #include "fasn_kv_host.h"
 #include "fasn_kvrope.h"
@@ -48,89 +47,50 @@ int kvr_build(const fasn_kvcache_args* a, bool prefill, int64_t rows, const fasn
     return FASN_OK;
 }
 
-template <typename Tag, int D>
-int kvr_launch(const KvRopeParams& rp, hipStream_t s) {
-    FASN_LAUNCH((fasn_kvrope_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp);
-    return launch_rc();
-}
-template <typename Tag, int D>
-int kvr_launch_tree(const KvRopeParams& rp, const KvTree& kt, hipStream_t s) {
-    FASN_LAUNCH((fasn_kvrope_tree_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, kt);
-    return launch_rc();
-}
-template <typename Tag, int D>
-int kvr_launch_packed(const KvRopeParams& rp, const KvPacked& pk, hipStream_t s) {
-    FASN_LAUNCH((fasn_kvvarlen_rope_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, pk);
-    return launch_rc();
-}
-
-// the rotate-quantise-append of fasn_kvfp8.h, at the two head dims the FP8 kernels are built for (kv_check_fp8 let only these through)
-template <typename Tag, int D>
-int kvr_launch_fp8(const KvRopeParams& rp, const KvFp8& f8, hipStream_t s) {
-    FASN_LAUNCH((fasn_kvrope_fp8_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, f8);
-    return launch_rc();
-}
-template <typename Tag>
-int kvr_launch_fp8_d(int D, const KvRopeParams& rp, const KvFp8& f8, hipStream_t s) {
-    return D == 64 ? kvr_launch_fp8<Tag, 64>(rp, f8, s) : kvr_launch_fp8<Tag, 128>(rp, f8, s);
-}
-
-template <typename Tag, int D>
-int kvr_launch_fp8_tree(const KvRopeParams& rp, const KvFp8& f8, const KvTree& kt, hipStream_t s) {
-    FASN_LAUNCH((fasn_kvrope_fp8_tree_kernel<Tag, D>), dim3((unsigned)((rp.nkv + rp.nq + 255) / 256)), dim3(256), 0, s, rp, f8, kt);
-    return launch_rc();
-}
-template <typename Tag>
-int kvr_launch_fp8_tree_d(int D, const KvRopeParams& rp, const KvFp8& f8, const KvTree& kt, hipStream_t s) {
-    return D == 64 ? kvr_launch_fp8_tree<Tag, 64>(rp, f8, kt, s) : kvr_launch_fp8_tree<Tag, 128>(rp, f8, kt, s);
-}
-
-// `tree`: the *_tree_rope_append calls (the rotation at depth positions); its operand is checked behind the rope operand
-int kvr_call(const KvArgs& in, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream,
-             bool tree = false, const fasn_kv_tree* tree_operand = nullptr) {
+// One call path for every rotary append. `ops`: the operands beside the rope operand - FP8 and / or tree; decode and prefill only, the
+// packed call has neither. THE CHECK ORDER is decided here and differs between the two families: a 16-bit cache checks base -> rope ->
+// tree, an FP8 cache base -> FP8 -> tree -> rope. Both orders are ABI behaviour that tests pin (tests/test_kvtree_cpu.py,
+// tests/test_kvfp8_tree_cpu.py, tests/golden/kvfp8_tree_plans.txt): keep them.
+int kvr_call(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
+             fasn_stream_t stream) {
     KvPrefillParams pp;
     KvPacked pk{};
     int rc = kv_build(in, pp, &pk);
     if (rc) return rc;
+    const bool packed = in.call == KV_VARLEN, fp8 = (ops.takes & KV_OP_FP8) != 0, tree = (ops.takes & KV_OP_TREE) != 0;
+    if (packed && ops.takes != 0) return FASN_EUNSUPPORTED;
+    KvFp8 f8{};
+    KvTree kt{};
+    if (fp8 && (rc = kv_check_fp8(in.a, ops.fp8, f8))) return rc;
+    if (fp8 && tree && (rc = kv_check_tree(in.a, ops.tree, pp.kv.capacity, kt))) return rc;
     KvRopeParams rp{};
     rp.kv = pp.kv;
     rp.qlens = pp.qlens;
-    const bool packed = in.call == KV_VARLEN;
     const int64_t rows = packed ? (int64_t)pk.T : (int64_t)pp.kv.B * pp.kv.Sq;
     if ((rc = kvr_build(in.a, in.call != KV_DECODE, rows, rope, q_out, k_new, v_new, rp))) return rc;
-    if (tree) {
-        KvTree kt{};
-        if (packed) return FASN_EUNSUPPORTED;
-        if ((rc = kv_check_tree(in.a, tree_operand, pp.kv.capacity, kt))) return rc;
-        return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch_tree<decltype(tag), decltype(d)::value>(rp, kt, (hipStream_t)stream); });
-    }
-    if (packed)
-        return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch_packed<decltype(tag), decltype(d)::value>(rp, pk, (hipStream_t)stream); });
-    return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) { return kvr_launch<decltype(tag), decltype(d)::value>(rp, (hipStream_t)stream); });
+    if (!fp8 && tree && (rc = kv_check_tree(in.a, ops.tree, pp.kv.capacity, kt))) return rc;
+    const unsigned grid = (unsigned)((rp.nkv + rp.nq + 255) / 256);
+    const hipStream_t s = (hipStream_t)stream;
+    if (fp8)
+        return kv8_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) {
+            using Tag = decltype(tag);
+            constexpr int D = decltype(d)::value;
+            if (tree) kv_launch<&fasn_kvrope_fp8_tree_kernel<Tag, D>>(grid, 0, s, rp, f8, kt);
+            else kv_launch<&fasn_kvrope_fp8_kernel<Tag, D>>(grid, 0, s, rp, f8);
+            return launch_rc();
+        });
+    return kv_dispatch(in.a->dtype, in.a->D, [&](auto tag, auto d) {
+        using Tag = decltype(tag);
+        constexpr int D = decltype(d)::value;
+        if (tree) kv_launch<&fasn_kvrope_tree_kernel<Tag, D>>(grid, 0, s, rp, kt);
+        else if (packed) kv_launch<&fasn_kvvarlen_rope_kernel<Tag, D>>(grid, 0, s, rp, pk);
+        else kv_launch<&fasn_kvrope_kernel<Tag, D>>(grid, 0, s, rp);
+        return launch_rc();
+    });
 }
-
-// the *_fp8_rope_append calls: the base checks, the FP8 operand's (kv_check_fp8), the rope operand's (kvr_build), one launch on the grid
-// of the 16-bit rope append. Decode and prefill only. `tree`: the *_fp8_tree_rope_append calls (the rotation at depth positions); their
-// tree operand is checked behind the FP8 operand and in front of the rope operand, and the one launch is on the 16-bit tree rope grid.
-int kvr_call_fp8(const KvArgs& in, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
-                 fasn_stream_t stream, bool tree = false, const fasn_kv_tree* tree_operand = nullptr) {
-    KvPrefillParams pp;
-    int rc = kv_build(in, pp);
-    if (rc) return rc;
-    KvFp8 f8{};
-    if ((rc = kv_check_fp8(in.a, fp8, f8))) return rc;
-    KvTree kt{};
-    if (tree && (rc = kv_check_tree(in.a, tree_operand, pp.kv.capacity, kt))) return rc;
-    KvRopeParams rp{};
-    rp.kv = pp.kv;
-    rp.qlens = pp.qlens;
-    if ((rc = kvr_build(in.a, in.call != KV_DECODE, (int64_t)pp.kv.B * pp.kv.Sq, rope, q_out, k_new, v_new, rp))) return rc;
-    if (tree) {
-        if (in.a->dtype == FASN_DTYPE_BF16) return kvr_launch_fp8_tree_d<bf16_tag>(in.a->D, rp, f8, kt, (hipStream_t)stream);
-        return kvr_launch_fp8_tree_d<f16_tag>(in.a->D, rp, f8, kt, (hipStream_t)stream);
-    }
-    if (in.a->dtype == FASN_DTYPE_BF16) return kvr_launch_fp8_d<bf16_tag>(in.a->D, rp, f8, (hipStream_t)stream);
-    return kvr_launch_fp8_d<f16_tag>(in.a->D, rp, f8, (hipStream_t)stream);
+int kvr_plan(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
+             char* buf, size_t cap) {
+    return kv_plan(buf, cap, [&] { return kvr_call(in, ops, rope, q_out, k_new, v_new, nullptr); });
 }
 
 }  // namespace
@@ -142,82 +102,82 @@ extern "C" {
 
 int fasn_kvcache_rope_append(const fasn_kvcache_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                              const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream);
+    return kvr_call(kv_args(args), kv_ops(), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvprefill_rope_append(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                                const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream);
+    return kvr_call(kv_args(args), kv_ops(), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvcache_tree_rope_append(const fasn_kvcache_args* args, const fasn_kv_rope* rope, const fasn_kv_tree* tree, const fasn_view4* q_out,
                                   const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream, true, tree);
+    return kvr_call(kv_args(args), kv_ops(tree), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvprefill_tree_rope_append(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_kv_tree* tree, const fasn_view4* q_out,
                                     const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream, true, tree);
+    return kvr_call(kv_args(args), kv_ops(tree), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvcache_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                                   const fasn_view4* v_new, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvr_call(kv_args(args), rope, q_out, k_new, v_new, nullptr); });
+    return kvr_plan(kv_args(args), kv_ops(), rope, q_out, k_new, v_new, buf, cap);
 }
 
 int fasn_kvprefill_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                                     const fasn_view4* v_new, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvr_call(kv_args(args), rope, q_out, k_new, v_new, nullptr); });
+    return kvr_plan(kv_args(args), kv_ops(), rope, q_out, k_new, v_new, buf, cap);
 }
 
 int fasn_kvvarlen_rope_append(const fasn_kvvarlen_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                               const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call(kv_args(args), rope, q_out, k_new, v_new, stream);
+    return kvr_call(kv_args(args), kv_ops(), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvvarlen_rope_append_plan(const fasn_kvvarlen_args* args, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                                    const fasn_view4* v_new, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvr_call(kv_args(args), rope, q_out, k_new, v_new, nullptr); });
+    return kvr_plan(kv_args(args), kv_ops(), rope, q_out, k_new, v_new, buf, cap);
 }
 
 int fasn_kvcache_fp8_rope_append(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
                                  const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, stream);
+    return kvr_call(kv_args(args), kv_ops(fp8), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvprefill_fp8_rope_append(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
                                    const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, stream);
+    return kvr_call(kv_args(args), kv_ops(fp8), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvcache_fp8_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
                                       const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr); });
+    return kvr_plan(kv_args(args), kv_ops(fp8), rope, q_out, k_new, v_new, buf, cap);
 }
 
 int fasn_kvprefill_fp8_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_view4* q_out,
                                         const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr); });
+    return kvr_plan(kv_args(args), kv_ops(fp8), rope, q_out, k_new, v_new, buf, cap);
 }
 
 int fasn_kvcache_fp8_tree_rope_append(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
                                       const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, stream, true, tree);
+    return kvr_call(kv_args(args), kv_ops(fp8, tree), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvprefill_fp8_tree_rope_append(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
                                         const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
-    return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, stream, true, tree);
+    return kvr_call(kv_args(args), kv_ops(fp8, tree), rope, q_out, k_new, v_new, stream);
 }
 
 int fasn_kvcache_fp8_tree_rope_append_plan(const fasn_kvcache_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
                                            const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr, true, tree); });
+    return kvr_plan(kv_args(args), kv_ops(fp8, tree), rope, q_out, k_new, v_new, buf, cap);
 }
 
 int fasn_kvprefill_fp8_tree_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
                                              const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvr_call_fp8(kv_args(args), fp8, rope, q_out, k_new, v_new, nullptr, true, tree); });
+    return kvr_plan(kv_args(args), kv_ops(fp8, tree), rope, q_out, k_new, v_new, buf, cap);
 }
 
 }  // extern "C"

@@ -292,53 +292,27 @@ def _on_device(dev, launch) -> None:
 def _append(lib, c, stream, rope=None, q_rot=None, tree=None, fp8=None) -> None:
     """k_new / v_new -> the cache rows behind the lengths; with `rope` the one launch that rotates them on the way and the queries into
     `q_rot`, which the forward then reads - under `tree` at the nodes' depth positions; with `fp8` the launch that quantises them; with
-    `fp8` and `rope` the one launch that rotates, then quantises - under `tree` at the nodes' depth positions too"""
-    if fp8 is not None and rope is not None:   # the rotate-quantise-append; without k_new / v_new it rotates the queries only
-        name = f"fasn_{c.stem}_fp8_rope_append" if tree is None else f"fasn_{c.stem}_fp8_tree_rope_append"
-        kn_view = None if c.k_new is None else _view4(c.k_new)
-        vn_view = None if c.v_new is None else _view4(c.v_new)
-        operand = (fp8, rope) if tree is None else (fp8, rope, tree)
-        _lib.check(getattr(lib, name)(c.args, *operand, _view4(q_rot), kn_view, vn_view, stream), name)
+    `fp8` and `rope` the one launch that rotates, then quantises - under `tree` at the nodes' depth positions too. The entry point's
+    name and its operands in ABI order follow from the operands present (_lib.kv_append_call)."""
+    if rope is None and c.k_new is None:
+        return
+    name, operands = _lib.kv_append_call(c.stem, fp8=fp8, tree=tree, rope=rope)
+    views = [None if t is None else _view4(t) for t in (c.k_new, c.v_new)]   # (a rope call without them rotates the queries only)
+    if rope is not None:
+        views.insert(0, _view4(q_rot))
+    _lib.check(getattr(lib, name)(c.args, *operands, *views, stream), name)
+    if rope is not None:
         c.kv.q = _view4(q_rot)
-    elif fp8 is not None:
-        if c.k_new is not None:
-            name = f"fasn_{c.stem}_fp8_append"
-            _lib.check(getattr(lib, name)(c.args, fp8, _view4(c.k_new), _view4(c.v_new), stream), name)
-    elif rope is not None:
-        name = f"fasn_{c.stem}_rope_append" if tree is None else f"fasn_{c.stem}_tree_rope_append"
-        kn_view = None if c.k_new is None else _view4(c.k_new)
-        vn_view = None if c.v_new is None else _view4(c.v_new)
-        operand = (rope,) if tree is None else (rope, tree)
-        _lib.check(getattr(lib, name)(c.args, *operand, _view4(q_rot), kn_view, vn_view, stream), name)
-        c.kv.q = _view4(q_rot)
-    elif c.k_new is not None:
-        name = f"fasn_{c.stem}_append"
-        _lib.check(getattr(lib, name)(c.args, _view4(c.k_new), _view4(c.v_new), stream), name)
 
 
 def _forward(lib, c, stream, win=None, tree=None, fp8=None) -> None:
-    """workspace bytes -> allocate -> the forward of the base kernels, of their ALiBi siblings (c.alibi), of their window siblings (`win`),
-    of their token-tree siblings (`tree`, which carries its window), of their FP8-cache siblings (`fp8`), of the FP8 window siblings
-    (`fp8` and `win`) or of the FP8 token-tree siblings (`fp8` and `tree`)"""
+    """workspace bytes -> allocate -> the forward of the base kernels or of their siblings under the operands present: ALiBi slopes
+    (c.alibi), a window (`win`), a token tree (`tree`, which carries its window), an FP8 cache (`fp8`), or `fp8` with `win` or `tree`.
+    The names and the operands in ABI order follow from the operands present (_lib.kv_forward_call: the ALiBi forward has the base
+    call's workspace)."""
     stem = c.stem
-    if fp8 is not None and tree is not None:
-        name, operand = f"fasn_fwd_{stem}_fp8_tree", (fp8, tree)
-        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_fp8_tree_workspace_bytes")(c.args, fp8, tree)
-    elif fp8 is not None and win is not None:
-        name, operand = f"fasn_fwd_{stem}_fp8_window", (fp8, win)
-        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_fp8_window_workspace_bytes")(c.args, fp8, win)
-    elif fp8 is not None:
-        name, operand = f"fasn_fwd_{stem}_fp8", (fp8,)
-        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_fp8_workspace_bytes")(c.args, fp8)
-    elif tree is not None:
-        name, operand = f"fasn_fwd_{stem}_tree", (tree,)
-        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_tree_workspace_bytes")(c.args, tree)
-    elif win is not None:
-        name, operand = f"fasn_fwd_{stem}_window", (win,)
-        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_window_workspace_bytes")(c.args, win)
-    else:   # (the ALiBi kernels: the base call's workspace)
-        name, operand = (f"fasn_fwd_{stem}_alibi", (c.alibi,)) if c.alibi is not None else (f"fasn_fwd_{stem}", ())
-        ws_bytes = getattr(lib, f"fasn_fwd_{stem}_workspace_bytes")(c.args)
+    ws_name, ws_operand, name, _plan, operand = _lib.kv_forward_call(stem, fp8=fp8, tree=tree, window=win, alibi=c.alibi)
+    ws_bytes = getattr(lib, ws_name)(c.args, *ws_operand)
     # torch's caching allocator: capturable, as _launch_fwd's. Decode always combines its split partials and a packed call always has its
     # item table: both always pass a pointer; a prefill of one split has no partials and takes no workspace
     if stem != "kvprefill":

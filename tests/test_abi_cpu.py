@@ -40,6 +40,23 @@ def test_library_exports_nothing_but_the_header(pkg):
     assert "getenv" not in und
 
 
+def test_kv_binding_table_is_a_census_of_the_kv_entry_points(pkg):
+    """_lib._kv_bindings() derives its rows from a description of the ABI: the names it yields are exactly the K/V-cache subset of EXPORTS
+    (69 entry points), each once, and every one of them is bound and callable - a NULL argument block, every other argument NULL / 0, is
+    refused with FASN_EINVAL (-1) by the int calls and answered with 0 bytes by the *_workspace_bytes calls, before any HIP call."""
+    lib = pkg._lib.load()
+    rows = list(pkg._lib._kv_bindings())
+    names = [name for name, _restype, _argtypes in rows]
+    assert len(names) == 69 and len(set(names)) == 69
+    assert set(names) == {e for e in pkg._lib.EXPORTS if re.search(r"kvcache|kvprefill|kvvarlen", e)}
+    for name, restype, argtypes in rows:
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+        assert restype is (ctypes.c_size_t if name.endswith("_workspace_bytes") else ctypes.c_int32), name
+        rc = fn(*(None if issubclass(t, (ctypes._Pointer, ctypes.c_void_p, ctypes.c_char_p)) else 0 for t in argtypes))
+        assert rc == (0 if name.endswith("_workspace_bytes") else -1), f"{name}(NULL, ...) returned {rc}"
+
+
 def test_abi_version_and_strerror(pkg):
     lib = pkg._lib.load()
     assert lib.fasn_abi_version() == 6
