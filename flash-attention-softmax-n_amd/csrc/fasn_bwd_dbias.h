@@ -307,7 +307,7 @@ __global__ void __launch_bounds__(256, 1) fasn_bwd_dbias_kernel(const DbiasParam
                 qf[ks] = E::cvt8(f);
                 __builtin_memcpy(&dof[ks], &da, 16);
             }
-            nlse2 = (cur.l == -INFINITY || cur.l == INFINITY) ? -INFINITY : -cur.l * kLog2e;   // a row without weights: P = 0
+            nlse2 = lse_no_weights(cur.l) ? -INFINITY : -cur.l * kLog2e;   // a row without weights: P = 0
             ndlt = -cur.x;
             if (STAGE && nt == 1 && more_bh) {   // one tile per (b,h): the row images are re-requested within the step
                 __syncthreads();   // every wave has its fragments

@@ -353,7 +353,7 @@ __global__ void __launch_bounds__(512, 2) fasn_bwd_dbias_ws_kernel(const DbwPara
             }
             retire_loads(nstat);
             const float l = __uint_as_float(nstat);
-            stat = (row >= p.Sq || l == -INFINITY || l == INFINITY) ? -INFINITY : -l * kLog2e;   // a row without weights: P = 0
+            stat = (row >= p.Sq || lse_no_weights(l)) ? -INFINITY : -l * kLog2e;   // a row without weights: P = 0
             retire_loads(nmk[0]);
             retire_loads(nmk[1]);
             if (p.mask != nullptr) {

@@ -207,7 +207,7 @@ __global__ void __launch_bounds__(512, 2) fasn_bwd_dkdv_ws_kernel(const BwdParam
                 l = lsebase[gr];
                 x = dltbase[gr];
             }
-            stL = (l == -INFINITY || l == INFINITY) ? -INFINITY : -l * kLog2e;   // a row without weights: every P = exp2(-inf) = 0
+            stL = lse_no_weights(l) ? -INFINITY : -l * kLog2e;   // a row without weights: every P = exp2(-inf) = 0
             stX = -x;
         }
     };

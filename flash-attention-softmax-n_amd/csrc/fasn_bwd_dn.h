@@ -2,7 +2,8 @@
 //
 //   Z_i = n + sum_j exp(x_ij) = exp(lse_i),  O_i = sum_j exp(x_ij) v_j / Z_i   ->   dO_i/dn = -O_i / Z_i
 //   dL/dn_(b,h) = - sum_i delta_i exp(-lse_i),   delta_i = dO_i . O_i
-// (under dropout O is the dropped output and the identity holds unchanged). A row with lse = -inf (no visible key, n = 0) adds 0.
+// (under dropout O is the dropped output and the identity holds unchanged). A row with lse = -inf (no visible key, n = 0) adds 0,
+// and so does a row whose delta is exactly 0, whatever its lse (0 * exp(+big) would be NaN).
 // Bandwidth-bound: O and dO are read once, plus lse. Deterministic: a fixed-order two-stage reduction, no atomics -
 // stage 1 writes one partial sum per (b, h, row chunk), stage 2 sums them per output element (over batch and / or heads when the
 // output broadcasts there).

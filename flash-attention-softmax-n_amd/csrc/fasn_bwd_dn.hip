@@ -72,7 +72,9 @@ __global__ void __launch_bounds__(kDnThreads) fasn_bwd_dn_partial_kernel(const D
         for (int o = cpr >> 1; o > 0; o >>= 1) d += __shfl_xor(d, o);   // delta of the row (the group's lanes are one wave's)
         if (sub == 0 && row < p.Sq) {
             const float l = p.lse[(int64_t)bh * p.Sq + row];
-            acc += l == -INFINITY ? 0.f : d * expf(-l);
+            // (a row whose delta is exactly 0 - dO = 0, a pad row no loss reads - adds 0 even where exp(-lse) overflows: under an additive mask
+            // such a row of a head with n = 0 has lse = -V, and 0 * inf would be NaN)
+            acc += (l < -kLseFloor || d == 0.f) ? 0.f : d * expf(-l);
         }
     }
     const float t = block_sum(acc, red);

@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(512, 2) fasn_bwd_dq_ws_kernel(const BwdParams 
         }
         if (role == 0) {
             const float l = ok ? p.lse[(int64_t)bh * p.Sq + row] : INFINITY;
-            stat = (l == -INFINITY || l == INFINITY) ? -INFINITY : -l * kLog2e;   // start value of S: a row without weights gets P = 0
+            stat = lse_no_weights(l) ? -INFINITY : -l * kLog2e;   // start value of S: a row without weights gets P = 0
         } else {
             stat = ok ? -bp.delta[(int64_t)bh * p.Sq + row] : 0.f;               // start value of dP
         }

@@ -239,7 +239,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams b
             __builtin_memcpy(&dof[qb][s], &d, 16);
         }
         float l = ok ? p.lse[(int64_t)bh * p.Sq + row] : 0.f;
-        lse2[qb] = (l == -INFINITY) ? INFINITY : l * kLog2e;
+        lse2[qb] = (l < -kLseFloor) ? INFINITY : l * kLog2e;   // (-inf, or below the floor: a row without weights, fasn_common.h)
         if (!FUSE_DELTA) dlt[qb] = ok ? bp.delta[(int64_t)bh * p.Sq + row] : 0.f;
     }
 
@@ -762,7 +762,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
                 x = dltbase[gr];
             }
             // seeded kernels keep the NEGATED statistics in LDS: they are the start values of the S / dP accumulators
-            stL = (l == -INFINITY) ? INFINITY : l * kLog2e;
+            stL = (l < -kLseFloor) ? INFINITY : l * kLog2e;   // (-inf, or below the floor: a row without weights, fasn_common.h)
             if (SEED_S) stL = -stL;
             stX = SEED_P ? -x : x;
         }

@@ -121,7 +121,7 @@ __global__ void __launch_bounds__(256, 2) fasn_bwd_dkdv_pipe_kernel(const BwdPar
                 l = lsebase[gr];
                 x = dltbase[gr];
             }
-            stL = (l == -INFINITY || l == INFINITY) ? -INFINITY : -l * kLog2e;   // a row without weights: every P = exp2(-inf) = 0
+            stL = lse_no_weights(l) ? -INFINITY : -l * kLog2e;   // a row without weights: every P = exp2(-inf) = 0
             stX = -x;
         }
     };
@@ -471,7 +471,7 @@ __global__ void __launch_bounds__(256, 2) fasn_bwd_dq_pipe_kernel(const BwdParam
             __builtin_memcpy(&dof[s], &d, 16);
         }
         const float l = ok ? p.lse[(int64_t)bh * p.Sq + row] : 0.f;
-        lse2 = (l == -INFINITY || l == INFINITY) ? INFINITY : l * kLog2e;   // a row without weights: every P = exp2(-inf) = 0
+        lse2 = lse_no_weights(l) ? INFINITY : l * kLog2e;   // a row without weights: every P = exp2(-inf) = 0
     }
     auto tile_dma = [&](int t, int buf) {
         tdK.dma(krw, ldsK_w + buf * TILEB, t * KT, p.ks[2]);

@@ -136,7 +136,7 @@ __global__ void __launch_bounds__(512, 2) fasn_bwd_dkdv_ws256_kernel(const BwdPa
                 l = lsebase[(int64_t)st_g * p.Sq + gr];
                 x = dltbase[(int64_t)st_g * p.Sq + gr];
             }
-            stL = (l == -INFINITY || l == INFINITY) ? -INFINITY : -l * kLog2e;
+            stL = lse_no_weights(l) ? -INFINITY : -l * kLog2e;
             stX = -x;
         }
         if (++st_u == nu1) { st_u = 0; if (st_g + 1 < G) ++st_g; }   // (uniform: every thread advances the walker)
@@ -461,7 +461,7 @@ __global__ void __launch_bounds__(512, 2) fasn_bwd_dq_ws256_kernel(const BwdPara
         }
         if (role == 0) {
             const float l = row_ok ? p.lse[(int64_t)bh * p.Sq + row] : INFINITY;
-            stat = (l == -INFINITY || l == INFINITY) ? -INFINITY : -l * kLog2e;
+            stat = lse_no_weights(l) ? -INFINITY : -l * kLog2e;
         } else {
             stat = row_ok ? -bp.delta[(int64_t)bh * p.Sq + row] : 0.f;
         }

@@ -24,6 +24,12 @@ typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;
 
 constexpr float kLog2e = 1.4426950408889634f;
 constexpr float kLn2 = 0.6931471805599453f;
+// A row whose lse lies below -2^22 nats has no weights in the backward, like a row with lse = -inf: fp32 is spaced half a nat and more
+// apart there, so P = exp2(x' - lse*log2e) cannot be recomputed from it (at lse = -1e9, spacing 64 nats, P came out up to 2^90 off,
+// overflowed fp16, and inf * dO made dV NaN for the whole K/V head). No q.k reaches that range; only an additive mask does: the row saw
+// masked keys only and no sink - a pad row - and its gradients are 0, as they are when the mask is written with -inf.
+constexpr float kLseFloor = 4194304.0f;
+FASN_DEV bool lse_no_weights(float l) { return l < -kLseFloor || l == INFINITY; }
 
 struct bf16_tag {};
 struct f16_tag {};

@@ -91,6 +91,12 @@ constexpr int KT = 64;  // keys per tile
 constexpr int kFwdKpMaxTiles = 512;
 // fast-path guard: a lane's partial row sum over one tile (32 values) must stay <= 2^8; any single p > 2^8 trips it
 constexpr float kSumLimit = 256.0f;
+// seed floor of the vector bias modes (log2 units): a row whose running max lies at or below -kSeedFloor still counts as unseeded - its
+// scores start from bias*log2e alone (mref = 0) and its wave stays on the exact path. An additive mask of -1e9 leaves a row without a
+// sink at m = -1.44e9; seeded from +1.44e9 (fp32 spacing 128) the next tile's q.k would be rounded away. No start value then exceeds
+// max(|row max|, kSeedFloor): rounding point (9) of tests/attn_witness.py, whose cap (D / 16 + 2) 2^-24 F ln2 <= 2^-12 nats at D = 128
+// gives F <= 590.
+constexpr float kSeedFloor = 512.0f;
 
 // Visibility words of a key-padding mask row: words[t] bit j = key 64t + j is visible (mask byte != 0 and key < Sk), for tiles
 // [0, ntiles). Thread `tid` of `nthreads` turns 16 mask bytes into 16 bits per step (one 16-byte load; a row that is not dword
@@ -470,6 +476,8 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     f32x16 mseed[(SEED && !VEC) ? QB : 1];   // the vector general modes build their start values per element from -m
     float n_p = (KPAIR && pass) ? n_item1 : n_item0;
     bool unseeded = !(n_p > 0.f && split == 0);
+    // a row with a finite max that is no use as a seed: only a bias can put one there (kSeedFloor); every other kernel keeps the plain test
+    auto no_seed = [](float m) { return (VEC && VBIAS) ? !(m > -kSeedFloor) : (m == -INFINITY); };
 #pragma unroll
     for (int qb = 0; qb < ((SEED && !VEC) ? QB : 1); ++qb)
 #pragma unroll
@@ -765,7 +773,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
                 // (S' = add + q.k, y = c*S'): from here on the tile is handled exactly like a plain one
 #pragma unroll
                 for (int qb = QLO; qb < QHI; ++qb) {
-                    const float mneg = (SEED && m_run[qb] != -INFINITY) ? -m_run[qb] : 0.f;
+                    const float mneg = (SEED && !no_seed(m_run[qb])) ? -m_run[qb] : 0.f;
 #pragma unroll
                     for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -958,7 +966,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
                         }
                     }
                     mx = max_across_halves(mx);
-                    const float mref = (SEED && m_run[qb] != -INFINITY) ? m_run[qb] : 0.f;   // SEED: what the scores are relative to
+                    const float mref = (SEED && !no_seed(m_run[qb])) ? m_run[qb] : 0.f;   // SEED: what the scores are relative to
                     const float m_new = fmaxf(m_run[qb], mx + mref);
                     const float m_use = (m_new == -INFINITY) ? 0.f : m_new;  // fully hidden so far
                     const float alpha = fast_exp2(m_run[qb] - m_use);
@@ -999,7 +1007,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
             if (SEED && unseeded) {   // rows that saw only hidden keys so far keep the wave on the exact path
                 bool u = false;
 #pragma unroll
-                for (int qb = 0; qb < QB; ++qb) u |= (m_run[qb] == -INFINITY);
+                for (int qb = 0; qb < QB; ++qb) u |= no_seed(m_run[qb]);
                 unseeded = __any(u);
             }
 

@@ -110,7 +110,8 @@ typedef struct fasn_fwd_args {
  */
 #define FASN_BWD_ONE_PASS 1 /* fasn_bwd_args.flags: reserved (the one-pass backward, no longer built); ignored by libfasn.so */
 typedef struct fasn_bwd_args {
-    fasn_fwd_args fwd; /* same views as forward; o and lse are inputs here */
+    fasn_fwd_args fwd; /* same views as forward; o and lse are inputs here. A row with lse = -inf or lse < -2^22 (a row that saw only
+                          keys under an additive mask such as -1e9, and no sink) has no weights: it adds 0 to every gradient */
     fasn_view4 dout;   /* [B,H,Sq,Dv] */
     fasn_view4 dq;     /* [B,H,Sq,D]  out */
     fasn_view4 dk;     /* [B,H/kv_group,Sk,D]  out (summed over the query heads of a GQA group inside the kernel) */
@@ -180,7 +181,7 @@ int fasn_fwd_n(const fasn_fwd_args* args, const float* n, int64_t n_stride_b, in
 /*
  * Gradient of that n (no counterpart in the reference, whose n carries none). With lse_i = log(n + sum_j exp(x_ij)) and
  * delta_i = sum_d dO_id O_id:
- *     dL/dn_(b,h) = - sum_i delta_i exp(-lse_i)        (rows with lse = -inf add 0; unchanged under dropout: O is the dropped output)
+ *     dL/dn_(b,h) = - sum_i delta_i exp(-lse_i)        (rows with lse = -inf or lse < -2^22, and rows with delta_i = 0, add 0; unchanged under dropout: O is the dropped output)
  * Reads args->fwd.o, args->fwd.lse and args->dout (the views of the fasn_bwd call; nothing else of args is read beyond validation,
  * args->fwd.softmax_n is ignored), WRITES dn[b * dn_stride_b + h * dn_stride_h] as fp32. A stride of 0 asks for the sum over that
  * dimension (dn_stride_b = 0: sum over the batch, e.g. an n of shape [H]). Deterministic: a fixed-order two-stage reduction through

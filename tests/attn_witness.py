@@ -38,6 +38,16 @@ DESIGN 4.1 and 4.4 and the kernel sources name:
       dS = rd(P) (dP - delta) from it: dS carries P's rounding as well as its own.
   (8) fp16 underflows gradually: below 2^-14 a rounding is off by up to ua = 2^-25 absolutely, not by u relatively (bf16: ua = 0). That
       matters where a weight far below the row's maximum meets a large factor: rd(P) |dP - delta| in (7), rd(P f) |dO| in dV, rd(P) |v|.
+  (9) the seed (DESIGN 4.1 "Seeded accumulators"; gated by tests/bias_witness.py, not by witness C's own cases, whose biases are N(0, 1)
+      and whose row maxima stay near 0): the score accumulates in fp32 onto a start value of magnitude at most max(|m_i| log2e, F), and
+      bias * log2e is formed in fp32. The vector bias modes of fasn_fwd_kernel start a tile's accumulator from fma(bias, log2e, -m_run)
+      and add q'.k onto it in D / 16 MFMAs; each of these `steps` = D / 16 + 2 roundings (the fma, the MFMAs, the subtraction of the
+      moved maximum) is off by at most 2^-24 of the running value, which is below |x_ij| log2e + max(|m_i| log2e, F) with m_i the row's
+      true maximum. In nats: eps_ij += steps 2^-24 (|x_ij| log2e + max(|m_i| log2e, F)) ln 2. F is the seed floor, a design constant of
+      the kernels (kSeedFloor in csrc/fasn_fwd_kernel.h, F_SEED in bias_witness.py): a row whose running maximum lies at or below -F
+      counts as unseeded (start value bias log2e alone, exact path), so no start value exceeds max(|m_i| log2e, F). The F part is capped:
+      (128 / 16 + 2) 2^-24 F ln 2 <= 2^-12 nats at D = 128, so F <= 590; F = 512. Without the floor a row that had seen only keys at
+      -1e9 was seeded from +1.44e9, where fp32 is spaced 128 apart, and the next tile's q.k was rounded away.
 To first order a logit perturbation eps moves out_id by sum_j Pf_ij eps_ij |v_jd - o_id|, bounded here by E1 + |o_id| E0 with
 E1 = sum_j Pf_ij eps_ij |v_jd|, E0 = sum_j Pf_ij eps_ij (the same sums without the [L, S, D] tensor), and lse_i by lam0_i = sum_j P_ij eps_ij.
     out    3 u A + E1 + |o| E0 + ua sum_j w_ij |v_jd| / l_i + 1e-6      A = sum_j Pf_ij |v_jd|: (2) weights, (2) l, (3), (8); l_i relative to the row's maximum
@@ -49,8 +59,9 @@ E1 = sum_j Pf_ij eps_ij |v_jd|, E0 = sum_j Pf_ij eps_ij (the same sums without t
     dK     |scale| sum_i bdS_ij |q_id| + u |dK_jd| + 1e-6     (6), summed over the query heads of the K/V head
     dbias  sum of bdS over the broadcast dimensions + u |dbias| + 1e-6
     dn     sum_i (eta_i + |delta_i| lam_i) exp(-lse_i) + 2^-20 sum_i |delta_i| exp(-lse_i) + 1e-6
-No constant comes from a GPU run. tests/test_attnwitness_cpu.py emulates exactly these roundings on the CPU and asserts that every
-result stays at or below 0.5 of its gate.
+No constant comes from a GPU run. tests/attn_emulate.py emulates exactly these roundings on the CPU - (1) to (8) with absolute fp32
+scores, and with (9) the seeded start value and the step-wise fp32 accumulation - and tests/test_attnwitness_cpu.py and
+tests/test_biaswitness_cpu.py assert that every result stays at or below 0.5 of its gate.
 
 Witness B's bound on dQ, dK, dn (bounded code). The winner t has P_it = 1 in fp32, so O_i = f_it V_t: exact without dropout, one rounding
 (u) with it. dS_it = P_it (dP_it - delta_i) is the difference of two fp32 evaluations of the same sum dO_i . O_i over D terms, in different
@@ -207,15 +218,29 @@ def attend(q, k, v, w, n, scale, bias=None, keep=None, p_eff=0.0, do=None, row_w
     r["dQ"], r["dQ_abs"] = scale * (dS @ k), abs(scale) * (dS.abs() @ k.abs())
     r["dK"], r["dK_abs"] = scale * (dS.transpose(1, 2) @ (rows * q)), abs(scale) * (dS.abs().transpose(1, 2) @ (rows * q.abs()))
     einv = torch.where(has, torch.exp(-lse), torch.zeros_like(lse))
+    einv = torch.where((do == 0).all(-1), torch.zeros_like(einv), einv)   # a row without dO adds 0 to dn, also where exp(-lse) overflows (bias_witness: pad rows at lse = -V)
     r["einv"] = einv
     r["dn"], r["dn_abs"] = -(delta * einv).sum(-1), (delta.abs() * einv).sum(-1)
     return r
 
 
-def bounds_c(r, q, k, v, do, scale, u, ua=0.0, p_rounded=False):
+def seed_eps(r, steps, F):
+    """rounding point (9) in nats, [N, L, S]: steps 2^-24 (|x_ij| log2e + max(|m_i| log2e, F)) ln 2 with x, m of the attend() result r;
+    0 where the key is hidden outright (x = -inf: its weight is exactly 0 whatever the score's rounding)"""
+    x, m = r["x"], r["m"]
+    fin = torch.isfinite(x)
+    xa = torch.where(fin, x.abs(), torch.zeros_like(x))
+    e = steps * 2.0 ** -24 * (xa * LOG2E + (m.abs() * LOG2E).clamp_min(F).unsqueeze(-1)) * math.log(2.0)
+    return torch.where(fin, e, torch.zeros_like(e))
+
+
+def bounds_c(r, q, k, v, do, scale, u, ua=0.0, p_rounded=False, eps_add=None):
     """Witness C's per-element gates of one attend() result (module docstring): a dict with out, lse and, when the result carries
-    gradients, dV, dQ, dK, dS (the bound on dS, from which a bias gradient's gate is summed) and dn"""
+    gradients, dV, dQ, dK, dS (the bound on dS, from which a bias gradient's gate is summed) and dn. eps_add [L, S]: further terms of
+    eps_ij (seed_eps: rounding point 9)"""
     eps = u * abs(scale) * (q.abs() @ k.abs().transpose(1, 2))
+    if eps_add is not None:
+        eps = eps + eps_add
     P, f = r["P"], r["f"]
     Pf = P * f
     Pe = Pf * eps
@@ -485,13 +510,15 @@ def group_sum(case, t):
     return t.view(case.ub, case.uhk, case.G, *t.shape[2:]).sum(2)
 
 
-def with_bounds(case, inp, r, u, ua=0.0):
-    """bounds_c of every distinct problem: dict of [ub, uh, ...]; dK already summed over the group with its result rounding"""
+def with_bounds(case, inp, r, u, ua=0.0, seed=None):
+    """bounds_c of every distinct problem: dict of [ub, uh, ...]; dK already summed over the group with its result rounding.
+    seed = (steps, F): add rounding point (9) to eps (tests/bias_witness.py)"""
     q, k, v, do = r["_ops"]
     gs = []
     for b in range(case.ub):
         rb = {key: val[b] for key, val in r.items() if not key.startswith("_")}
-        gs.append(bounds_c(rb, q[b], k[b], v[b], None if do is None else do[b], inp["scale"], u, ua, case.p_rounded))
+        gs.append(bounds_c(rb, q[b], k[b], v[b], None if do is None else do[b], inp["scale"], u, ua, case.p_rounded,
+                           None if seed is None else seed_eps(rb, *seed)))
     g = {key: torch.stack([x[key] for x in gs]) for key in gs[0]}
     if "dK" in g:
         g["dK"] = group_sum(case, g["dK"]) + u * group_sum(case, r["dK"]).abs() + 1e-6
@@ -694,6 +721,14 @@ def plan_text(pkg, case, dtype):
 
 
 # ---------------------------------------------------------------- the call on the GPU
+def _leaf_like(t):
+    """a leaf that requires grad with t's values AND strides (clone() makes a view with padded rows contiguous, which moves a bias
+    whose rows are aligned only through their padding to the element loads)"""
+    leaf = torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=t.device)
+    leaf.copy_(t.detach())
+    return leaf.requires_grad_()
+
+
 def run(pkg, case, inp, seed=1, backward=None):
     """the case's call through flash_attention_n (and its backward with inp["do"]), and once more through flash_attn._launch_fwd, which
     returns lse and must give the same output bit for bit. Returns a dict: out, lse (None for the regrouped decode), dq, dk, dv, dn,
@@ -707,7 +742,7 @@ def run(pkg, case, inp, seed=1, backward=None):
     if backward:
         qq, kk, vv = (t.detach().clone().requires_grad_() for t in (q, k, v))
         nn = n.detach().clone().requires_grad_() if torch.is_tensor(n) else n
-        bb = None if inp["bias"] is None else inp["bias"].detach().clone().requires_grad_()
+        bb = None if inp["bias"] is None else _leaf_like(inp["bias"])
         out = pkg.flash_attention_n(qq, kk, vv, softmax_n_param=nn, attn_bias=bb, **kwargs)
         state = flash_attn.last_dropout_state()
         out.backward(inp["do"])

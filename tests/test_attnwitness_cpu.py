@@ -28,8 +28,9 @@ Which witness is claimed to catch which mutant (dtype in brackets where only one
      other (length-paired) batch element
   11 bias of the neighbouring head                              C: out [fp16]
 
-The unmutated reference, rounded to the output type, passes every gate; an emulation of the kernels' arithmetic with exactly the rounding
-points of the derivation (attn_witness docstring) stays at or below 0.5 of every gate of witness C; the fp64 reference and its closed-form
+The unmutated reference, rounded to the output type, passes every gate; an emulation of the kernels' arithmetic with the rounding
+points (1) to (8) of the derivation (attn_witness docstring; tests/attn_emulate.py in its absolute-score model - the seed, rounding point
+(9), is the business of tests/test_biaswitness_cpu.py) stays at or below 0.5 of every gate of witness C; the fp64 reference and its closed-form
 gradients agree with oracle.ref_attention.ref_attention_n and autograd on the suite's ordinary data; and the launch plans of every case of
 attn_witness.SHAPES match tests/golden/attn_witness_plans.txt and have the property the case is named for."""
 import math
@@ -409,70 +410,7 @@ def test_11_bias_of_the_neighbouring_head():
 
 
 # ---------------------------------------------------------------- witness C's derivation: the kernels' arithmetic stays inside it
-def _emulate(w):
-    """the kernels' arithmetic on the CPU with exactly the rounding points of the derivation: the prescaled Q (forward, dQ) or K (dK / dV)
-    rounded to the operand type, fp32 scores in the log2 domain, an online softmax over 64-key tiles, P rounded for the P.V product and
-    l summed from the rounded weights, fp32 accumulation, O rounded once; fp32 lse; the backward recomputes P = exp2(x' - lse log2e),
-    rounds P for dV and (as the two-wave kernels do) before dS, rounds dS for dQ / dK, reads delta from the rounded O, and rounds each result once."""
-    case, inp, dt = w.case, w.inp, w.dt
-    q, k, v, do, un, ubias = aw.unique_operands(case, inp)
-    c = inp["scale"] * aw.LOG2E
-    rd = lambda t: t.to(dt).float()   # noqa: E731
-    wt = aw.weights(case, inp["um"])
-    res = {key: [] for key in ("out", "lse", "dQ", "dK", "dV", "dS", "dn")}
-    for b in range(case.ub):
-        qf, kf, vf, dof = q[b].float(), k[b].float(), v[b].float(), do[b].float()
-        vis = (wt[b] > 0).expand(case.uh, -1, -1)
-        n = un[b].float().view(-1, 1)
-        bias2 = None if ubias is None else (ubias[b if ubias.shape[0] > 1 else 0].float() * aw.LOG2E)
-        f = torch.ones(case.uh, case.L, case.S) if w.keep is None else (w.keep[b] / (1 - w.p_eff)).float()
-        qs, ks = rd(qf * c), rd(kf * c)
-        m = torch.where(n > 0, 0.0, -math.inf).expand(case.uh, case.L).clone()
-        l = n.expand(case.uh, case.L).clone()
-        acc = torch.zeros(case.uh, case.L, case.D)
-        for k0 in range(0, case.S, aw.KT):
-            sl = slice(k0, k0 + aw.KT)
-            s = qs @ kf[:, sl].transpose(1, 2)
-            if bias2 is not None:
-                s = s + bias2[..., sl]
-            s = torch.where(vis[..., sl], s, torch.full_like(s, -math.inf))
-            m_new = torch.maximum(m, s.amax(-1))
-            m_use = torch.where(torch.isfinite(m_new), m_new, torch.zeros_like(m_new))
-            alpha = torch.exp2(m - m_use)
-            p = rd(torch.exp2(s - m_use.unsqueeze(-1)))
-            l = l * alpha + p.sum(-1)
-            acc = acc * alpha.unsqueeze(-1) + rd(p * f[..., sl]) @ vf[:, sl]
-            m = m_new
-        has = l > 0
-        safe = torch.where(has, l, torch.ones_like(l))
-        o = rd(acc / safe.unsqueeze(-1))
-        m0 = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
-        lse2 = torch.where(has, m0 + torch.log2(safe), torch.full_like(m, math.inf))   # log2 domain; rows without anything: P = 0
-        res["out"].append(o.double())
-        res["lse"].append(torch.where(has, lse2 / aw.LOG2E, torch.full_like(m, -math.inf)).double())
-        delta = (dof * o).sum(-1)
-        grads = {}
-        for side, s in (("q", qs @ kf.transpose(1, 2)), ("k", qf @ ks.transpose(1, 2))):
-            if bias2 is not None:
-                s = s + bias2
-            s = torch.where(vis, s, torch.full_like(s, -math.inf))
-            P = torch.exp2(s - lse2.unsqueeze(-1))
-            dP = f * (dof @ vf.transpose(1, 2))
-            dS = rd((rd(P) if case.p_rounded else P) * (dP - delta.unsqueeze(-1)))   # (rounding point 7: the two-wave kernels' P arrives rounded)
-            if side == "q":
-                grads["dQ"] = rd(inp["scale"] * (dS @ kf))
-                grads["dS"] = dS
-            else:
-                grads["dK"] = inp["scale"] * (dS.transpose(1, 2) @ qf)
-                grads["dV"] = rd(P * f).transpose(1, 2) @ dof
-        for key in ("dQ", "dK", "dV", "dS"):
-            res[key].append(grads[key].double())
-        res["dn"].append(-(delta * torch.where(has, torch.exp(-lse2 / aw.LOG2E), torch.zeros_like(l))).sum(-1).double())
-    r = {key: torch.stack(val) for key, val in res.items()}
-    out = aw.as_result(case, r, dt)
-    for key, full in (("dk", r["dK"]), ("dv", r["dV"])):   # (the group's sum is rounded once)
-        out[key] = aw._tile(case, aw.group_sum(case, full), "kv").to(dt)
-    return out
+from attn_emulate import emulate as _emulate   # noqa: E402  (shared with tests/test_biaswitness_cpu.py; here: the absolute-score model)
 
 
 @pytest.mark.parametrize("std", [4, 8])
