@@ -1,5 +1,5 @@
 // fasn_common.h — device-side building blocks shared by the forward and backward kernels.
-// gfx950 (CDNA4) only: wave64, v_mfma_f32_32x32x16_{bf16,f16}, ds_read_b64_tr_b16, v_permlane32_swap.
+// gfx950 (CDNA4) only: wave64, v_mfma_f32_32x32x16_{bf16,f16} (and 16x16x32), ds_read_b64_tr_b16, v_permlane32_swap / v_permlane16_swap.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,6 +45,10 @@ struct ET<bf16_tag> {
     static FASN_DEV f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
     }
+    // 16x16x32: lane l holds A[row l&15][k = 8(l>>4) + j], B[k = 8(l>>4) + j][col l&15]; C/D col = l&15, row = 4(l>>4) + register
+    static FASN_DEV f32x4 mfma16(vec8 a, vec8 b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
     static FASN_DEV vec8 cvt8(f32x8 x) { return __builtin_convertvector(x, bf16x8); }
     // acc + lo + hi of one packed pair (v_dot2c_f32_bf16 against {1, 1}): a row sum costs one VALU issue per TWO weights
     static FASN_DEV float pair_sum(uint32_t pk, float acc) {
@@ -63,6 +67,9 @@ struct ET<f16_tag> {
     typedef f16x4 vec4;
     static FASN_DEV f32x16 mfma(vec8 a, vec8 b, f32x16 c) {
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+    }
+    static FASN_DEV f32x4 mfma16(vec8 a, vec8 b, f32x4 c) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
     }
     static FASN_DEV vec8 cvt8(f32x8 x) { return __builtin_convertvector(x, f16x8); }
     static FASN_DEV float pair_sum(uint32_t pk, float acc) {
@@ -191,6 +198,16 @@ FASN_DEV float max_across_halves(float x) {
 FASN_DEV float sum_across_halves(float x) {
     auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(x), __float_as_uint(x), false, false);
     return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+
+// the same over the four 16-lane rows of the wave (the 16x16x32 tiles: a query row lives in lanes l, l^16, l^32, l^48)
+FASN_DEV float max_across_rows16(float x) {
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return max_across_halves(fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1])));
+}
+FASN_DEV float sum_across_rows16(float x) {
+    auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(x), __float_as_uint(x), false, false);
+    return sum_across_halves(__uint_as_float(r[0]) + __uint_as_float(r[1]));
 }
 
 // Retire the global loads that filled loop-invariant register operands BEFORE a pipelined loop. Without this, hipcc's
@@ -428,6 +445,21 @@ FASN_DEV void store_block_narrow(char* blk, const f32x16& acc, float sc, int hi)
         __builtin_memcpy(&raw, &y, 8);
         gstore8(blk + (8 * g + 4 * hi) * 2, raw);
     }
+}
+
+// Two 16-column blocks (fc, fc + 1) of a row that FOUR lanes own (16x16x32 accumulators: lane (l&15, g = l>>4) holds columns 16 fc + 4 g .. + 3
+// of its row in the four registers of block fc): scaled, rounded and written as ONE 16-byte store per lane - v_permlane16_swap pairs the
+// lanes g and g^1, after which even g holds columns 16 fc + 4 g .. + 7 and odd g columns 16 (fc + 1) + 4 (g - 1) .. + 7. `blk` = the row's
+// address + the column offset of block fc; all four lanes of the row must be active.
+template <typename E>
+FASN_DEV void store_block16_pair(char* blk, const f32x4& a, const f32x4& b, float sc, int g) {
+    typename E::vec4 ya = E::cvt4(a * sc), yb = E::cvt4(b * sc);
+    u32x2 pa, pb;
+    __builtin_memcpy(&pa, &ya, 8);
+    __builtin_memcpy(&pb, &yb, 8);
+    const auto r0 = __builtin_amdgcn_permlane16_swap(pa[0], pb[0], false, false);
+    const auto r1 = __builtin_amdgcn_permlane16_swap(pa[1], pb[1], false, false);
+    gstore16(blk + (16 * (g & 1) + 8 * (g >> 1)) * 2, u32x4{r0[0], r1[0], r0[1], r1[1]});
 }
 
 // XCD-aware block -> (batch*head, q-block) map. Blocks are dispatched round-robin over the 8 XCDs

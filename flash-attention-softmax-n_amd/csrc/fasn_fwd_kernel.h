@@ -15,6 +15,8 @@
 //   P^T: those same registers, exponentiated and packed to 16 bit, ARE the B operand of the next MFMA
 //   O^T[d][q] += mfma(A = V^T (ds_read_b64_tr_b16 with the matching key permutation), B = P^T)
 // so there is no LDS round trip and no cross-lane shuffle for P, and alpha/l/m are per-lane scalars.
+// (The plain / key-padding D = 64 kernel of the big-grid tuning point tiles the same products with 16x16x32 MFMAs - T16 below: a row in
+// four lanes, per-lane partial row sums, still no shuffle on the fast path.)
 //
 // Work decomposition: workgroup = 4 waves = BM = 4*QB*32 query rows of one (b,h); each wave owns
 // QB 32-row blocks and reuses every K / V fragment it reads from LDS for all of them. K/V tiles of 64
@@ -89,7 +91,7 @@ constexpr int KT = 64;  // keys per tile
 // key-padding modes: visibility words (one per K/V tile) kept in LDS by the forward kernels: 4 KiB, Sk <= 32768. Longer key
 // sequences take the dense-mask general mode of the same mask (fasn_api.hip).
 constexpr int kFwdKpMaxTiles = 512;
-// fast-path guard: a lane's partial row sum over one tile (32 values) must stay <= 2^8; any single p > 2^8 trips it
+// fast-path guard: a lane's partial row sum over one tile (32 values; T16: 16) must stay <= 2^8; any single p > 2^8 trips it
 constexpr float kSumLimit = 256.0f;
 // seed floor of the vector bias modes (log2 units): a row whose running max lies at or below -kSeedFloor still counts as unseeded - its
 // scores start from bias*log2e alone (mref = 0) and its wave stays on the exact path. An additive mask of -1e9 leaves a row without a
@@ -228,6 +230,13 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     constexpr int CPR = D / 8;   // 16-B chunks per row
     constexpr int NLD = (KT * CPR) / NT;  // staging loads per thread per tensor
     static_assert(NLD >= 1, "tile too small for this workgroup size");
+    // T16: the plain / key-padding D = 64 kernel of the big-grid tuning point computes its scores and its output with v_mfma_f32_16x16x32
+    // instead of 32x32x16 - same wave tile (64 keys x 64 rows), same matrix-pipe cycles, same LDS bytes; DESIGN 4.1. Lane (l15 = lane & 15,
+    // g = lane >> 4): a query row lives in FOUR lanes, row chunk rc = rows 16 rc + l15 of the wave; register r of key chunk c = key 16 c + 4 g + r.
+    // Same box, three alternations against the 32x32x16 tiling (profiles/r07_m0_forward_mfma_16x16x32_ab.log): M0 forward 0.4852 -> 0.4673 ms at
+    // 2166 -> 2288 MHz under load - the cycles are the same, the chip holds a higher clock on this shape.
+    constexpr bool T16 = D == 64 && QB == 2 && NW == 4 && OCC == 2 && RING == 2 && SEED == 2 && (MODE == MODE_PLAIN || MODE == MODE_KEYPAD) &&
+                         !PRIO && !DROP && !SPLIT && VH == 1 && !FOLD && !BF32;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NBUF = RING == 2 ? 3 : 2;
@@ -392,8 +401,25 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
 
     // ---- Q fragments (B operand: col = q = lane&31, k = 8*hi..8*hi+7 of each 16-wide step)
     vec8 qf[QB][KS];
+    // T16: the same eight fragments hold (row chunk rc, 32-feature step s) at qf[rc >> 1][2 (rc & 1) + s]: B operand col = row l15 of the
+    // chunk, k = features 32 s + 8 g .. + 7
+    const int l15 = lane & 15, g16 = lane >> 4;
+    auto q16 = [&](int rc, int s) -> vec8& { return qf[rc >> 1][2 * (rc & 1) + s]; };
+    if constexpr (T16) {
 #pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
+        for (int rc = 0; rc < 4; ++rc) {
+            const int row = qw0 + 16 * rc + l15;
+            const char* rp = qbase + (int64_t)row * p.qs[2] * 2 + g16 * 16;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                u32x4 raw = {0u, 0u, 0u, 0u};
+                if (row < p.Sq) raw = gload16(rp + s * 64);
+                __builtin_memcpy(&q16(rc, s), &raw, 16);
+            }
+        }
+    }
+#pragma unroll
+    for (int qb = 0; qb < (T16 ? 0 : QB); ++qb) {
         const int row = rowb(qb) + l31;
         const bool ok = row < p.Sq;
         const char* rp = qbase + (int64_t)row * p.qs[2] * 2 + hi * 16;
@@ -421,7 +447,11 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
         // lane (MFMA rows (r&3) + 8(r>>2) + 4hi) are the 16 CONSECUTIVE keys 16hi + r: bias / mask rows are then read
         // 32 / 16 contiguous bytes per lane. K and V use the same order, the PV contraction does not see it.
         const int grow = KPERM ? ((row & ~31) | (((row >> 2) & 1) << 4) | (((row >> 3) & 3) << 2) | (row & 3)) : row;
-        kvoff[i] = (unsigned)(grow * (int)p.ks[2] * 2 + ch * 16);
+        // T16: the K image takes chunk' = chunk ^ ((row >> 1) & 7), under which the 16-row operand read (row = l15, chunk 4 s + g) is free of
+        // bank conflicts: a 16-lane service group of ds_read_b128 holds rows {0-3, 12-15} with one g and rows {4-11} with g ^ 1, and per row
+        // parity the slots (row >> 1) ^ g over them are eight different ones. The V image and its transposed reads stay as they are.
+        const int chk = T16 ? ((ci % CPR) ^ ((row >> 1) & 7)) : ch;
+        kvoff[i] = (unsigned)(grow * (int)p.ks[2] * 2 + chk * 16);
         vvoff[i] = (unsigned)(grow * (int)p.vs[2] * 2 + ch * 16);
         ldsoff[i] = tile_off<D>(row, ch);
     }
@@ -484,8 +514,24 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
         for (int r = 0; r < 16; ++r) mseed[qb][r] = 0.f;
     const int hi_p = FOLD ? (fresh_lane_id() >> 5) : hi;
     if constexpr (FOLD) asm volatile("" : "+s"(n_p));   // (per pass: not hoisted in front of the pass loop and parked in scratch)
+    // T16 state, per row chunk: m is the same in the four lanes of a row, l is the LANE's partial sum (its 16 keys of every tile; the sink in
+    // lane g = 0), combined once in the epilogue; O^T[feature 16 fc + 4 g + r][row l15] in register r of oacc16[rc][fc]
+    constexpr int RC = T16 ? 4 : 1;
+    float m16[RC], l16[RC];
+    f32x4 oacc16[RC][RC], mseed16[RC];
+    if constexpr (T16) {
+        const bool sink = n_p > 0.f;
 #pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
+        for (int rc = 0; rc < RC; ++rc) {
+            m16[rc] = sink ? 0.f : -INFINITY;
+            l16[rc] = (sink && g16 == 0) ? n_p : 0.f;
+            mseed16[rc] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int fc = 0; fc < RC; ++fc) oacc16[rc][fc] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
+#pragma unroll
+    for (int qb = 0; qb < (T16 ? 0 : QB); ++qb) {
         const bool sink = n_p > 0.f && split == 0;
         m_run[qb] = sink ? 0.f : -INFINITY;
         l_run[qb] = (sink && hi_p == 0) ? n_p : 0.f;  // the two half-lanes' partial sums are added at the end
@@ -1033,7 +1079,144 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
                     }
             }
         };
-        if constexpr (FOLD && DIAG) {
+        if constexpr (T16) {
+            if (!skip) {
+                const char* tK = ldsK + buf * TILEB;
+                const char* tV = ldsV + buf * TILEB;
+                // ---- S^T = K Q^T: sacc[rc][c] = 16 keys (chunk c) x 16 rows (chunk rc); a K fragment (one ds_read_b128: row l15 of the
+                // chunk, features 32 s + 8 g .. + 7) serves the four row chunks. The first k-step takes the -m tuple as an untied C operand.
+                f32x4 sacc[4][4];
+                auto qk16 = [&](auto PRESET_) {
+#pragma unroll
+                    for (int c = 0; c < 4; ++c)
+#pragma unroll
+                        for (int s = 0; s < 2; ++s) {
+                            const u32x4 raw = *LDS_PTR(const u32x4, tK + (16 * c + l15) * ROWB + (((4 * s + g16) ^ (l15 >> 1)) << 4));
+                            vec8 kf;
+                            __builtin_memcpy(&kf, &raw, 16);
+#pragma unroll
+                            for (int rc = 0; rc < 4; ++rc)
+                                sacc[rc][c] = E::mfma16(kf, q16(rc, s), (s == 0 && !decltype(PRESET_)::value) ? mseed16[rc] : sacc[rc][c]);
+                        }
+                };
+                if (KP && kp_bits != ~0ull) {   // boundary tile of a key-padding mask: hidden keys start at -inf
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        const uint32_t w = (uint32_t)(kp_bits >> (16 * c)) >> (4 * g16);   // bit r = key 16 c + 4 g + r
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+#pragma unroll
+                            for (int rc = 0; rc < 4; ++rc) sacc[rc][c][r] = ((w >> r) & 1u) ? mseed16[rc][r] : -INFINITY;
+                    }
+                    qk16(std::true_type{});
+                } else {
+                    qk16(std::false_type{});
+                }
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll
+                for (int rc = 0; rc < 4; ++rc) asm volatile("" ::"v"(mseed16[rc]));   // (the -m tuples stay where they are: untied C operands)
+#endif
+                // ---- softmax_n: pf[rc][kp] = the lane's 8 weights of key chunks 2 kp and 2 kp + 1 = keys 32 kp + 4 g .. + 3 and 32 kp + 16 + 4 g .. + 3,
+                // which is the B fragment (k = 8 g + j) of one k = 32 step of the PV product
+                vec8 pf[4][2];
+#pragma unroll
+                for (int qb = 0; qb < 2; ++qb) {   // (guard and exact path per 32 rows, as in the 32x32 tiling)
+                    bool exact = need_mask || unseeded;
+                    if (!exact) {
+                        float rsv[2];
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const int rc = 2 * qb + h;
+                            f32x2 rs2 = {0.f, 0.f};
+#pragma unroll
+                            for (int kp = 0; kp < 2; ++kp) {
+                                f32x8 x;
+#pragma unroll
+                                for (int e = 0; e < 8; ++e) x[e] = fast_exp2(sacc[rc][2 * kp + (e >> 2)][e & 3]);
+                                pf[rc][kp] = E::cvt8(x);
+                                uint32_t w[4];   // row sum of the ROUNDED weights, two per instruction
+                                __builtin_memcpy(w, &pf[rc][kp], 16);
+                                rs2[0] = E::pair_sum(w[0], rs2[0]);
+                                rs2[1] = E::pair_sum(w[1], rs2[1]);
+                                rs2[0] = E::pair_sum(w[2], rs2[0]);
+                                rs2[1] = E::pair_sum(w[3], rs2[1]);
+                            }
+                            rsv[h] = rs2[0] + rs2[1];
+                        }
+                        // the lane's partial over its 16 keys of the tile: any single p > 2^8, an unset max or a NaN trips it
+                        if (__any(!(rsv[0] <= kSumLimit) || !(rsv[1] <= kSumLimit))) exact = true;
+                        else {
+                            l16[2 * qb] += rsv[0];
+                            l16[2 * qb + 1] += rsv[1];
+                        }
+                    }
+                    if (exact) {
+#pragma unroll
+                        for (int h = 0; h < 2; ++h) {
+                            const int rc = 2 * qb + h;
+                            const int vis = causal ? (qw0 + 16 * rc + l15 + coff) : 0x7fffffff;
+                            float mx = -INFINITY;
+#pragma unroll
+                            for (int c = 0; c < 4; ++c)
+#pragma unroll
+                                for (int r = 0; r < 4; ++r) {
+                                    const int key = k0 + 16 * c + 4 * g16 + r;
+                                    const float y = ((key < p.Sk) && (key <= vis)) ? sacc[rc][c][r] : -INFINITY;   // (already y - mref)
+                                    sacc[rc][c][r] = y;
+                                    mx = fmaxf(mx, y);
+                                }
+                            mx = max_across_rows16(mx);   // over the four lanes of the row: m, alpha stay row-uniform
+                            const float mref = (m16[rc] == -INFINITY) ? 0.f : m16[rc];
+                            const float m_new = fmaxf(m16[rc], mx + mref);
+                            const float m_use = (m_new == -INFINITY) ? 0.f : m_new;
+                            const float alpha = fast_exp2(m16[rc] - m_use);
+                            const float m_sub = m_use - mref;
+                            float rs = 0.f;
+#pragma unroll
+                            for (int kp = 0; kp < 2; ++kp) {
+                                f32x8 x;
+#pragma unroll
+                                for (int e = 0; e < 8; ++e) {
+                                    x[e] = fast_exp2(sacc[rc][2 * kp + (e >> 2)][e & 3] - m_sub);
+                                    rs += x[e];
+                                }
+                                pf[rc][kp] = E::cvt8(x);
+                            }
+                            l16[rc] = l16[rc] * alpha + rs;
+                            m16[rc] = m_new;
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) mseed16[rc][r] = -m_use;
+                            if (!__all(alpha == 1.0f)) {
+#pragma unroll
+                                for (int fc = 0; fc < 4; ++fc) oacc16[rc][fc] *= alpha;
+                            }
+                        }
+                    }
+                }
+                if (unseeded) {
+                    bool u = false;
+#pragma unroll
+                    for (int rc = 0; rc < 4; ++rc) u |= (m16[rc] == -INFINITY);
+                    unseeded = __any(u);
+                }
+                // ---- O^T += V^T P^T: A = V^T (row = feature 16 fc + l15, k = 8 g + j = the keys of pf's element j): two ds_read_b64_tr_b16, the
+                // 4-key runs 32 kp + 4 g and 32 kp + 16 + 4 g of the 16 columns of fc; a fragment serves the four row chunks
+#pragma unroll
+                for (int kp = 0; kp < 2; ++kp)
+#pragma unroll
+                    for (int fc = 0; fc < 4; ++fc) {
+                        const int r0 = 32 * kp + 4 * g16 + (l15 >> 2);
+                        const int off = tile_off<D>(r0, 2 * fc + ((l15 & 3) >> 1)) + (l15 & 1) * 8;   // (swz_f<64> does not see row bit 4)
+                        const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, tV + off));
+                        const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16(LDS_PTR(s16x4, tV + off + 16 * ROWB));
+                        const s16x8 ab = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
+                        vec8 vf;
+                        __builtin_memcpy(&vf, &ab, 16);
+#pragma unroll
+                        for (int rc = 0; rc < 4; ++rc) oacc16[rc][fc] = E::mfma16(vf, pf[rc][kp], oacc16[rc][fc]);
+                    }
+            }
+        } else if constexpr (FOLD && DIAG) {
             if (!skipq[0]) compute(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
             if (!skipq[QB - 1]) compute(std::integral_constant<int, QB - 1>{}, std::integral_constant<int, QB>{});
         } else {
@@ -1117,8 +1300,25 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     // (where the compiler hoists them: they are loop invariant) they would be live across both tile loops, and 13 registers went to scratch
     const int lane_e = FOLD ? fresh_lane_id() : lane;   // (v_mbcnt: not even the lane id has to stay live)
     const int l31e = FOLD ? (lane_e & 31) : l31, hie = FOLD ? (lane_e >> 5) : hi;
+    if constexpr (T16) {   // the four lanes of a row add their partial sums; a lane stores 8 features of two feature chunks (16 bytes)
 #pragma unroll
-    for (int qb = 0; qb < QB; ++qb) {
+        for (int rc = 0; rc < 4; ++rc) {
+            const int row = qw0 + 16 * rc + l15;
+            const float l_tot = sum_across_rows16(l16[rc]);
+            const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+            if (row < p.Sq) {
+                if (p.lse != nullptr && g16 == 0) {
+                    const float m_use = (m16[rc] == -INFINITY) ? 0.f : m16[rc];
+                    p.lse[(int64_t)bh * p.Sq + row] = l_tot > 0.f ? (m_use + __builtin_log2f(l_tot)) * kLn2 : -INFINITY;
+                }
+                char* rp = obase + (int64_t)row * p.os[2] * 2;
+#pragma unroll
+                for (int fc = 0; fc < 4; fc += 2) store_block16_pair<E>(rp + fc * 32, oacc16[rc][fc], oacc16[rc][fc + 1], inv, g16);
+            }
+        }
+    }
+#pragma unroll
+    for (int qb = 0; qb < (T16 ? 0 : QB); ++qb) {
         const int row = rowb(qb) + l31e;
         const float l_tot = sum_across_halves(l_run[qb]);
         const float inv = l_tot > 0.f ? (DROP ? p.drop_scale : 1.0f) / l_tot : 0.f;
