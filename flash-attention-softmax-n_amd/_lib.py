@@ -46,6 +46,7 @@ EXPORTS = (
     "fasn_fwd_kvprefill_fp8_tree_workspace_bytes", "fasn_fwd_kvprefill_fp8_tree", "fasn_kvprefill_fp8_tree_plan",
     "fasn_kvcache_fp8_tree_rope_append", "fasn_kvprefill_fp8_tree_rope_append", "fasn_kvcache_fp8_tree_rope_append_plan",
     "fasn_kvprefill_fp8_tree_rope_append_plan", "fasn_kvcache_fp8_tree_commit",
+    "fasn_kv_forward_workspace_bytes", "fasn_kv_forward", "fasn_kv_forward_plan", "fasn_kv_append", "fasn_kv_append_plan",
 )
 
 
@@ -134,6 +135,16 @@ class KvFp8(Structure):
                 ("reserved", c_int32)]
 
 
+FASN_KV_CALL_DECODE, FASN_KV_CALL_PREFILL, FASN_KV_CALL_PACKED = 0, 1, 2
+
+
+class KvCall(Structure):
+    """fasn_kv_call (include/fasn.h): a cache call as data - the kind of its block, the block, and the operands present (NULL: not part of
+    the call) - for the operand-set entry points fasn_kv_forward* / fasn_kv_append*; reserved = 0"""
+    _fields_ = [("kind", c_int32), ("reserved", c_int32), ("block", c_void_p), ("fp8", POINTER(KvFp8)), ("tree", POINTER(KvTree)),
+                ("window", POINTER(KvWindow)), ("alibi", POINTER(AlibiSlopes))]
+
+
 class KvTreeCommit(Structure):
     """fasn_kv_tree_commit (include/fasn.h): the cache and the accepted path of fasn_kvcache_tree_commit"""
     _fields_ = [
@@ -165,6 +176,10 @@ _KV_OPERAND = {"fp8": KvFp8, "tree": KvTree, "window": KvWindow, "alibi": AlibiS
 _KV_FORWARD_SETS = ((), ("alibi",), ("window",), ("tree",), ("fp8",), ("fp8", "window"), ("fp8", "tree"))   # packed: the first and ("window",)
 _KV_APPENDS = (((), False), (("rope",), True), (("tree", "rope"), False), (("fp8",), False), (("fp8", "rope"), True),
                (("fp8", "tree", "rope"), True))   # (operands in suffix order, has a *_plan); packed: the first two
+# "packed: the first ..." counts NAMES. The packed block also has the forward sets ("fp8",) and ("fp8", "window") and the appends ("fp8",)
+# and ("fp8", "rope"): they have no names and are reached through the operand-set entry points (KvCall, _kv_call_bindings(), kv_call()
+# below), which serve every named set as well.
+_KV_KIND = {"kvcache": FASN_KV_CALL_DECODE, "kvprefill": FASN_KV_CALL_PREFILL, "kvvarlen": FASN_KV_CALL_PACKED}
 
 
 def kv_stem(args):
@@ -215,6 +230,28 @@ def _kv_bindings():
                 yield f"{name}_plan", c_int32, head + text
     for name in ("fasn_kvcache_tree_commit", "fasn_kvcache_fp8_tree_commit"):
         yield name, c_int32, [POINTER(KvTreeCommit)] + launch
+
+
+def _kv_call_bindings():
+    """(name, restype, argtypes) of the five operand-set entry points: the call, then what the named entry points take behind their
+    operands"""
+    call, view, text = POINTER(KvCall), POINTER(View4), [c_char_p, c_size_t]
+    append = [call, POINTER(KvRope), view, view, view]   # the call, rope, q_out, k_new, v_new
+    yield "fasn_kv_forward_workspace_bytes", c_size_t, [call]
+    yield "fasn_kv_forward", c_int32, [call, c_void_p, c_size_t, c_void_p]
+    yield "fasn_kv_forward_plan", c_int32, [call] + text
+    yield "fasn_kv_append", c_int32, append + [c_void_p]
+    yield "fasn_kv_append_plan", c_int32, append + text
+
+
+def kv_call(args, fp8=None, tree=None, window=None, alibi=None):
+    """the KvCall of the block `args` under the operands that are not None. The block and the operands live as long as the KvCall does."""
+    c = KvCall(kind=_KV_KIND[kv_stem(args)], reserved=0, block=ctypes.cast(ctypes.pointer(args), c_void_p))
+    for name, operand in (("fp8", fp8), ("tree", tree), ("window", window), ("alibi", alibi)):
+        if operand is not None:
+            setattr(c, name, ctypes.pointer(operand))
+    c._block = args   # (the operands are kept by their pointer members; the block's address is a plain integer)
+    return c
 
 
 def load():
@@ -269,7 +306,7 @@ def load():
     lib.fasn_softmax_n_plan.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int32, c_char_p, c_size_t]
     lib.fasn_moments_plan.restype = c_int32
     lib.fasn_moments_plan.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_char_p, c_size_t]
-    for name, restype, argtypes in _kv_bindings():
+    for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     ver = lib.fasn_abi_version()
@@ -406,6 +443,30 @@ def kvfp8_tree_rope_plan(args, fp8, rope, tree, q_out, k_new=None, v_new=None):
     """The one launch of fasn_kvcache_fp8_tree_rope_append (`args` a KvCacheArgs) or fasn_kvprefill_fp8_tree_rope_append (a KvPrefillArgs)
     under `fp8` (a KvFp8), `rope` (a KvRope) and `tree` (a KvTree), as launch_plan returns it. Nothing is launched."""
     return _kv_append_plan(args, q_out, k_new, v_new, fp8=fp8, rope=rope, tree=tree)
+
+
+def kv_call_plan(call):
+    """The kernels fasn_kv_forward would launch for `call` (a KvCall), as launch_plan returns them: for a set a named entry point serves,
+    that entry point's plan. Nothing is launched."""
+    return _kv_plan("fasn_kv_forward_plan", call)
+
+
+def kv_call_append_plan(call, rope=None, q_out=None, k_new=None, v_new=None):
+    """The one launch of fasn_kv_append for `call` (a KvCall) - with `rope` (a KvRope) the rotary append into `q_out` - as launch_plan
+    returns it. Nothing is launched."""
+    return _kv_plan("fasn_kv_append_plan", call, rope, q_out, k_new, v_new)
+
+
+def kvfp8_varlen_plan(args, fp8, win=None):
+    """The kernels of the packed forward over an FP8 cache - `args` a KvVarlenArgs, `fp8` a KvFp8, `win` a KvWindow or None - as
+    launch_plan returns them (fasn_kv_forward_plan: the set has no named entry point). Nothing is launched."""
+    return kv_call_plan(kv_call(args, fp8=fp8, window=win))
+
+
+def kvfp8_varlen_append_plan(args, fp8, k_new, v_new, rope=None, q_out=None):
+    """The one launch of the packed quantising append (`rope` None) or of the packed rotate-quantise-append (`rope` a KvRope, `q_out` the
+    rotated queries' view) over an FP8 cache, as launch_plan returns it (fasn_kv_append_plan). Nothing is launched."""
+    return kv_call_append_plan(kv_call(args, fp8=fp8), rope, q_out, k_new, v_new)
 
 
 def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):

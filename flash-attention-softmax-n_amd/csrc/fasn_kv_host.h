@@ -48,10 +48,10 @@ KvOps kv_ops(const P*... p) {
 }
 
 // The operand sets a forward has kernels for, stated once: every other set is FASN_EUNSUPPORTED, behind the base checks. Decode and
-// prefill have the sets of kKvOpSets; the packed call (KV_VARLEN) has the base and the window kernels only.
+// prefill have the sets of kKvOpSets; the packed call (KV_VARLEN) has the base and the window kernels, over a 16-bit and an FP8 cache.
 constexpr unsigned kKvOpSets[] = {0, KV_OP_ALIBI, KV_OP_WINDOW, KV_OP_TREE, KV_OP_FP8, KV_OP_FP8 | KV_OP_WINDOW, KV_OP_FP8 | KV_OP_TREE};
 constexpr bool kv_ops_supported(KvCall call, unsigned takes) {
-    if (call == KV_VARLEN) return takes == 0 || takes == KV_OP_WINDOW;
+    if (call == KV_VARLEN) return (takes & ~(KV_OP_FP8 | KV_OP_WINDOW)) == 0;
     for (unsigned s : kKvOpSets)
         if (s == takes) return true;
     return false;
@@ -96,6 +96,16 @@ int kv_launch_prefill(const KvFwd& f, hipStream_t s);       // fasn_kvprefill.hi
 int kv_launch_packed(const KvFwd& f, hipStream_t s);        // fasn_kvvarlen.hip
 int kv_launch_fp8_decode(const KvFwd& f, hipStream_t s);    // fasn_kvfp8.hip
 int kv_launch_fp8_prefill(const KvFwd& f, hipStream_t s);   // fasn_kvfp8.hip
+int kv_launch_fp8_packed(const KvFwd& f, hipStream_t s);    // fasn_kvfp8.hip
+// The appends, each defined beside the kernels it launches: the plain appends of the three blocks, the quantising append of any block
+// (base checks, the new rows' views, then kv_check_fp8) and the one path of every rotary append - `ops`: FP8 and / or tree (fasn_kvrope.hip).
+// fasn_kv_append (fasn_kvcall.hip) picks among them as the named entry points do.
+int kv_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);      // fasn_kvcache.hip
+int kvp_append(const fasn_kvprefill_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);   // fasn_kvprefill.hip
+int kvv_append(const fasn_kvvarlen_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);    // fasn_kvvarlen.hip
+int kv8_append(const KvArgs& in, const fasn_kv_fp8* fp8, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream);   // fasn_kvfp8.hip
+int kvr_call(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
+             fasn_stream_t stream);
 // fasn_kvcache_tree_commit / fasn_kvcache_fp8_tree_commit: kv_build_commit, the grid (a thread per 16-byte chunk of a row: D / 8 elements,
 // D / 16 codes), then the one launch from the kernel's translation unit
 int kv_commit(const fasn_kv_tree_commit* a, bool fp8, fasn_stream_t stream);

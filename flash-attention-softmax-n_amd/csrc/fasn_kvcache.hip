@@ -265,7 +265,7 @@ int kv_forward(const KvArgs& in, const KvOps& ops, void* workspace, size_t works
     if (rc) return rc;
     const hipStream_t s = (hipStream_t)stream;
     const bool fp8 = (f.ops & KV_OP_FP8) != 0;
-    if (in.call == KV_VARLEN) return kv_launch_packed(f, s);
+    if (in.call == KV_VARLEN) return fp8 ? kv_launch_fp8_packed(f, s) : kv_launch_packed(f, s);
     if (in.call == KV_PREFILL) return fp8 ? kv_launch_fp8_prefill(f, s) : kv_launch_prefill(f, s);
     return fp8 ? kv_launch_fp8_decode(f, s) : kv_launch_decode(f, s);
 }
@@ -345,14 +345,15 @@ int kv_launch_append(const KvParams& p, hipStream_t s) {
     FASN_LAUNCH((fasn_kvcache_append_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
 }
+
+}  // namespace
+
 int kv_append(const fasn_kvcache_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
     KvPrefillParams pp;
     const int rc = kv_build_append(kv_args(args), k_new, v_new, pp);
     if (rc) return rc;
     return kv_dispatch_d(args->D, [&](auto d) { return kv_launch_append<decltype(d)::value>(pp.kv, (hipStream_t)stream); });
 }
-
-}  // namespace
 
 int kv_launch_decode(const KvFwd& f, hipStream_t s) {
     return kv_dispatch(f.dtype, f.D, [&](auto tag, auto d) { return kv_launch_decode_as<decltype(tag), decltype(d)::value>(f, s); });

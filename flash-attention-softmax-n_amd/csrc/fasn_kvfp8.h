@@ -1,4 +1,4 @@
-// fasn_kvfp8.h — the cache calls over an FP8 cache: decode and prefill on a paged or dense cache of OCP e4m3fn codes with one fp32 scale per
+// fasn_kvfp8.h — the cache calls over an FP8 cache: decode, prefill and token-packed prefill on a paged or dense cache of OCP e4m3fn codes with one fp32 scale per
 // (batch element, K/V head) in device memory (fasn_kvcache.h: KvFp8). The 16-bit kernels of fasn_kvcache.h / fasn_kvprefill.h are not
 // touched; these are their siblings on the same grid and split rule.
 //
@@ -10,6 +10,9 @@
 //   fasn_kvcache_fwd_fp8_tree_kernel / fasn_kvprefill_fwd_fp8_tree_kernel   the token-tree siblings: FASN_KV_FP8 with FASN_KV_TREE
 //   fasn_kvrope_fp8_tree_kernel   fasn_kvrope_fp8_kernel at the depth positions of a token tree
 //   fasn_kvcache_fp8_tree_commit_kernel   the commit of an accepted path over code rows
+//   fasn_kvvarlen_fwd_fp8_kernel / fasn_kvvarlen_fwd_window_fp8_kernel   the token-packed siblings: FASN_KV_FP8 with FASN_KV_PACKED (and FASN_KV_WINDOW)
+//   fasn_kvvarlen_fp8_combine_kernel / fasn_kvvarlen_fp8_append_kernel / fasn_kvvarlen_rope_fp8_kernel   their combine, quantising append and
+//                                         rotate-quantise-append: the kernels of fasn_kvvarlen.h / fasn_kvrope.h in front of this cache
 //
 // Semantics. value(code) = up(code) * scale[b, hkv], up() the exact upcast. All 254 finite codes are bf16 AND fp16 numbers, so the operands
 // of the 16-bit MFMAs are the codes themselves and the scales act in fp32:
@@ -27,6 +30,11 @@
 #include "fasn_kvrope.h"
 
 namespace fasn {
+
+// The packed kernels of this file carry FASN_KV_LOCAL: their host-side handles stay out of the library's dynamic symbol table (on the
+// device a kernel is raised to protected visibility whatever it is given, so the code objects hold them as they hold every other kernel).
+// The library exports its C entry points; no packed FP8 name is among them, and none shows up beside them.
+#define FASN_KV_LOCAL __attribute__((visibility("hidden")))
 
 constexpr int kv_fp8_smem(int D) { return 2 * kv_nbuf(D) * KV_KT * D + 2 * KV_KT * D * 2; }   // staged codes + one 16-bit image per operand
 
@@ -76,6 +84,17 @@ FASN_DEV void kv_fp8_widen(const char* src, char* img, int tid) {
 #include "fasn_kvcache_fwd.inc"
 #include "fasn_kvprefill_fwd.inc"
 #undef FASN_KV_TREE
+// fasn_kvvarlen_fwd_fp8_kernel(..., KvPacked, KvFp8) / fasn_kvvarlen_fwd_window_fp8_kernel(..., KvPacked, KvFp8, KvWindow): the token-packed
+// siblings (fasn_kvvarlen.h), the product of FASN_KV_FP8 and FASN_KV_PACKED, without and with FASN_KV_WINDOW. From the packed kernels: the
+// item of the schedule kernel's table, the token rows, lse [H, T], the partial slot (item, hkv, split). From the FP8 kernels: everything
+// above, the scales read at the item's b. Same LDS as the FP8 prefill, same grid and split rule as the 16-bit packed call of the same
+// shape; fasn_kvvarlen_schedule_kernel serves them as it is, fasn_kvvarlen_fp8_combine_kernel below merges their partials.
+#define FASN_KV_PACKED 1
+#include "fasn_kvprefill_fwd.inc"
+#define FASN_KV_WINDOW 1
+#include "fasn_kvprefill_fwd.inc"
+#undef FASN_KV_WINDOW
+#undef FASN_KV_PACKED
 #undef FASN_KV_FP8
 
 // fasn_kvcache_combine_kernel with v_scale[b, hkv] on the normalised fp32 row, in front of its one rounding
@@ -158,6 +177,48 @@ __global__ void __launch_bounds__(256) fasn_kvprefill_fp8_combine_kernel(const K
     if (lat != nullptr) *lat = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
 }
 
+// fasn_kvvarlen_combine_kernel with v_scale[b, hkv], likewise: b is the item's
+template <typename Tag, int D>
+FASN_KV_LOCAL __global__ void __launch_bounds__(256) fasn_kvvarlen_fp8_combine_kernel(const KvPrefillParams pp, const KvPacked pk, const KvFp8 f8) {
+    using E = ET<Tag>;
+    const KvParams& p = pp.kv;
+    constexpr int TPR = D / 4;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t slot = gid / TPR;   // ((item * Hkv + hkv), r)
+    const int c4 = (int)(gid % TPR) * 4;
+    if (slot >= (int64_t)pk.items_max * p.Hkv * KVP_ROWS) return;
+    const int64_t blk = slot / KVP_ROWS;
+    const int r = (int)(slot % KVP_ROWS);
+    const int item = (int)(blk / p.Hkv), hkv = (int)(blk % p.Hkv);
+    if (item >= pk.sched[0]) return;
+    const int4 it = *reinterpret_cast<const int4*>(pk.sched + KVV_HEAD + (int64_t)item * KVV_ITEM);   // b, rb, token0, qlen
+    const int g = r / pp.PB, pos = it.y * pp.PB + r % pp.PB;
+    if (g >= p.G || pos >= it.w) return;
+    const int h = hkv * p.G + g;
+    const int64_t tok = (int64_t)it.z + pos;
+    char* const oat = p.o + (h * p.os[1] + tok * p.os[2] + c4) * 2;
+    float mstar = -INFINITY;
+    for (int s = 0; s < p.nsplit; ++s) mstar = fmaxf(mstar, p.part_ml[((blk * p.nsplit + s) * KVP_ROWS + r) * 2]);
+    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
+    float l = 0.f;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < p.nsplit; ++s) {
+        const int64_t base = (blk * p.nsplit + s) * KVP_ROWS + r;
+        const float ms = p.part_ml[base * 2], ls = p.part_ml[base * 2 + 1];
+        if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
+        const float w = fast_exp2(ms - m_use);
+        l += ls * w;
+        const f32x4 a = *reinterpret_cast<const f32x4*>(p.part_o + base * D + c4);
+        acc += a * w;
+    }
+    const float inv = l > 0.f ? 1.0f / l : 0.f;
+    typename E::vec4 y = E::cvt4(acc * inv * f8.vs[it.x * f8.vsb + hkv * f8.vsh]);
+    u32x2 raw;
+    __builtin_memcpy(&raw, &y, 8);
+    gstore8(oat, raw);
+    if (p.lse != nullptr && c4 == 0) p.lse[(int64_t)h * pk.T + tok] = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
+}
+
 // ---- quantising append
 // code = rne_e4m3(clamp(float(x) / s, -448, 448)); a NaN stays a NaN code. The division is the correctly rounded fp32 division (this build
 // has no fast-math). The clamp makes the saturation explicit - whatever the conversion instruction's mode does beyond 448 is never asked -
@@ -221,6 +282,40 @@ __global__ void __launch_bounds__(256) fasn_kvcache_fp8_append_kernel(const KvPa
 template <typename Tag, int D>
 __global__ void __launch_bounds__(256) fasn_kvprefill_fp8_append_kernel(const KvPrefillParams pp, const KvFp8 f8) {
     kv_fp8_append<Tag, D, true>(pp.kv, pp.qlens, f8);
+}
+// fasn_kvvarlen_append_kernel (fasn_kvvarlen.h) in front of an FP8 cache: its lanes - one thread per (token t < T, K/V head, chunk), here a
+// chunk of 16 codes - its binary search in cu and its skip rules (a token of no sequence, beyond its sequence's clamped length, a row
+// outside the capacity), with the arithmetic and the byte addressing of kv_fp8_append: token t of k_new / v_new, quantised with the scales
+// of its sequence's (b, hkv) -> cache row seqlens[b] + (t - cu[b]).
+template <typename Tag, int D>
+FASN_KV_LOCAL __global__ void __launch_bounds__(256) fasn_kvvarlen_fp8_append_kernel(const KvPrefillParams pp, const KvPacked pk, const KvFp8 f8) {
+    using E = ET<Tag>;
+    const KvParams& p = pp.kv;
+    constexpr int CPR = D / 16;
+    const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= (int64_t)pk.T * p.Hkv * CPR) return;
+    const int ch = (int)(gid % CPR);
+    const int64_t rest = gid / CPR;
+    const int hkv = (int)(rest % p.Hkv), t = (int)(rest / p.Hkv);
+    int lo = 0, hi = p.B + 1;   // the first index of cu[0 .. B] whose offset is beyond t
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pk.cu[mid] <= t) lo = mid + 1;
+        else hi = mid;
+    }
+    const int b = lo - 1;
+    if (b < 0 || b >= p.B) return;   // a token at or beyond cu[B] (or in front of cu[0])
+    const int64_t c0 = pk.cu[b];
+    const int64_t i = t - c0;        // >= 0: cu[b] <= t
+    if (i >= min(max((int64_t)pk.cu[b + 1] - c0, (int64_t)0), (int64_t)p.Sq)) return;
+    const int64_t key = (int64_t)p.seqlens[b] + i;
+    if (key < 0 || key >= p.capacity) return;
+    const int slot = (int)(key / p.page_size), rip = (int)(key % p.page_size);
+    const int64_t page = p.bt != nullptr ? p.bt[(int64_t)b * p.bts + slot] : b;
+    const u32x4 kx = kv_fp8_quant16<E>(p.kn + (hkv * p.kns[1] + (int64_t)t * p.kns[2]) * 2 + ch * 32, f8.ks[b * f8.ksb + hkv * f8.ksh]);
+    const u32x4 vx = kv_fp8_quant16<E>(p.vn + (hkv * p.vns[1] + (int64_t)t * p.vns[2]) * 2 + ch * 32, f8.vs[b * f8.vsb + hkv * f8.vsh]);
+    gstore16(p.k + page * p.kps + (int64_t)rip * p.krs + (int64_t)hkv * p.khs + ch * 16, kx);
+    gstore16(p.v + page * p.vps + (int64_t)rip * p.vrs + (int64_t)hkv * p.vhs + ch * 16, vx);
 }
 
 // ---- rotate-quantise-append
@@ -347,6 +442,62 @@ __global__ void __launch_bounds__(256) fasn_kvrope_fp8_tree_kernel(const KvRopeP
         pos = (int64_t)depth + len - qlen;
         src = p.q + (b * p.qs[0] + h * p.qs[1] + (int64_t)i * p.qs[2]) * 2;
         dst = rp.qo + (b * rp.qos[0] + h * rp.qos[1] + (int64_t)i * rp.qos[2]) * 2;
+    }
+#include "fasn_kvrope_unit.inc"
+}
+
+// fasn_kvvarlen_rope_kernel (fasn_kvrope.h) in front of an FP8 cache, as fasn_kvrope_fp8_kernel relates to fasn_kvrope_kernel: one lane per
+// (token t < T, head, unit), the K/V units first, the token's sequence from the binary search in cu, qlen_b with the schedule kernel's
+// clamps, the same unit text. A K/V unit rotates its 16 key elements, rounds them once to the 16-bit type, quantises them with the
+// k_scale of the token's (b, hkv) and writes the codes - rows addressed in bytes - and quantises v_new beside it; a query unit is the
+// 16-bit kernel's.
+template <typename Tag, int D>
+FASN_KV_LOCAL __global__ void __launch_bounds__(256) fasn_kvvarlen_rope_fp8_kernel(const KvRopeParams rp, const KvPacked pk, const KvFp8 f8) {
+    using E = ET<Tag>;
+    const KvParams& p = rp.kv;
+    constexpr int UPR = D / 16;   // units per row
+    int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (gid >= rp.nkv + rp.nq) return;
+    const bool isq = gid >= rp.nkv;
+    if (isq) gid -= rp.nkv;
+    const int u = (int)(gid % UPR);
+    const int64_t rest = gid / UPR;
+    const int heads = isq ? p.H : p.Hkv;
+    const int h = (int)(rest % heads), t = (int)(rest / heads);   // t < T: nkv / nq count T tokens
+    int lo = 0, hi = p.B + 1;   // the first index of cu[0 .. B] whose offset is beyond t
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (pk.cu[mid] <= t) lo = mid + 1;
+        else hi = mid;
+    }
+    const int b = lo - 1;
+    if (b < 0 || b >= p.B) return;   // a token at or beyond cu[B] (or in front of cu[0])
+    const int64_t c0 = pk.cu[b];
+    const int64_t i = t - c0;        // >= 0: cu[b] <= t
+    const int token0 = (int)min(max(c0, (int64_t)0), (int64_t)pk.T);
+    int qlen = (int)min(max((int64_t)pk.cu[b + 1] - c0, (int64_t)0), (int64_t)p.Sq);
+    qlen = min(qlen, pk.T - token0);
+    if (i >= qlen) return;
+    int64_t pos;
+    const char* src;
+    char* dst = nullptr;    // a query unit's row of q_out (16-bit)
+    char* dst8 = nullptr;   // a K/V unit's row of the code cache
+    float ksc = 1.f;
+    if (!isq) {
+        pos = (int64_t)p.seqlens[b] + i;
+        if (pos < 0 || pos >= p.capacity) return;   // dropped: the host does not know the lengths
+        const int slot = (int)(pos / p.page_size), rip = (int)(pos % p.page_size);
+        const int64_t page = p.bt != nullptr ? p.bt[(int64_t)b * p.bts + slot] : b;
+        src = p.kn + (h * p.kns[1] + (int64_t)t * p.kns[2]) * 2;
+        dst8 = p.k + page * p.kps + (int64_t)rip * p.krs + (int64_t)h * p.khs;
+        ksc = f8.ks[b * f8.ksb + h * f8.ksh];
+        const u32x4 vx = kv_fp8_quant16<E>(p.vn + (h * p.vns[1] + (int64_t)t * p.vns[2]) * 2 + u * 32, f8.vs[b * f8.vsb + h * f8.vsh]);
+        gstore16(p.v + page * p.vps + (int64_t)rip * p.vrs + (int64_t)h * p.vhs + u * 16, vx);
+    } else {
+        const int len = (int)min(max((int64_t)p.seqlens[b] + (rp.add_qlen ? qlen : 0), (int64_t)0), (int64_t)p.capacity);
+        pos = i + len - qlen;
+        src = p.q + (h * p.qs[1] + (int64_t)t * p.qs[2]) * 2;
+        dst = rp.qo + (h * rp.qos[1] + (int64_t)t * rp.qos[2]) * 2;
     }
 #include "fasn_kvrope_unit.inc"
 }

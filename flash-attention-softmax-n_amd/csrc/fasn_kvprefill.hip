@@ -30,14 +30,15 @@ int kvp_launch_append(const KvPrefillParams& pp, hipStream_t s) {
     FASN_LAUNCH((fasn_kvprefill_append_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, pp);
     return launch_rc();
 }
+
+}  // namespace
+
 int kvp_append(const fasn_kvprefill_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
     KvPrefillParams pp;
     const int rc = kv_build_append(kv_args(args), k_new, v_new, pp);
     if (rc) return rc;
     return kv_dispatch_d(args->kv.D, [&](auto d) { return kvp_launch_append<decltype(d)::value>(pp, (hipStream_t)stream); });
 }
-
-}  // namespace
 
 int kv_launch_prefill(const KvFwd& f, hipStream_t s) {
     return kv_dispatch(f.dtype, f.D, [&](auto tag, auto d) { return kv_launch_prefill_as<decltype(tag), decltype(d)::value>(f, s); });

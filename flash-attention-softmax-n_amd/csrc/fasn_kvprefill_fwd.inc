@@ -13,13 +13,20 @@
 // above are what they were. FASN_KV_FP8 = 1 with FASN_KV_WINDOW = 1 (fasn_kvfp8.h) is the sliding-window sibling over the FP8 cache: the
 // window blocks of the body are orthogonal to the FP8 blocks. FASN_KV_SC is the score factor's one name (fasn_kvcache_fwd.inc).
 // FASN_KV_FP8 = 1 with FASN_KV_TREE = 1 (fasn_kvfp8.h) is the token-tree sibling over the FP8 cache, by the same orthogonality.
+// FASN_KV_FP8 = 1 with FASN_KV_PACKED = 1 (fasn_kvfp8.h; FASN_KV_WINDOW = 0 / 1) are the token-packed siblings over the FP8 cache: the
+// packed blocks say where the item, the rows and the partial slot come from, the FP8 blocks what is staged, widened and scaled - the
+// scales are read at the item's b. No block of the text carries both switches.
 #if FASN_KV_FP8
 #define FASN_KV_SC c8
 #else
 #define FASN_KV_SC p.c
 #endif
 template <typename Tag, int D>
-#if FASN_KV_FP8 && FASN_KV_TREE
+#if FASN_KV_FP8 && FASN_KV_PACKED && FASN_KV_WINDOW
+FASN_KV_LOCAL __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvvarlen_fwd_window_fp8_kernel(const KvPrefillParams pp, const KvPacked pk, const KvFp8 f8, const KvWindow win) {
+#elif FASN_KV_FP8 && FASN_KV_PACKED
+FASN_KV_LOCAL __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvvarlen_fwd_fp8_kernel(const KvPrefillParams pp, const KvPacked pk, const KvFp8 f8) {
+#elif FASN_KV_FP8 && FASN_KV_TREE
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_fp8_tree_kernel(const KvPrefillParams pp, const KvFp8 f8, const KvTree tree) {
 #elif FASN_KV_FP8 && FASN_KV_WINDOW
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvprefill_fwd_fp8_window_kernel(const KvPrefillParams pp, const KvFp8 f8, const KvWindow win) {

@@ -47,8 +47,10 @@ int kvr_build(const fasn_kvcache_args* a, bool prefill, int64_t rows, const fasn
     return FASN_OK;
 }
 
-// One call path for every rotary append. `ops`: the operands beside the rope operand - FP8 and / or tree; decode and prefill only, the
-// packed call has neither. THE CHECK ORDER is decided here and differs between the two families: a 16-bit cache checks base -> rope ->
+}  // namespace
+
+// One call path for every rotary append. `ops`: the operands beside the rope operand - FP8 and / or tree; the packed call has the FP8
+// operand only. THE CHECK ORDER is decided here and differs between the two families: a 16-bit cache checks base -> rope ->
 // tree, an FP8 cache base -> FP8 -> tree -> rope. Both orders are ABI behaviour that tests pin (tests/test_kvtree_cpu.py,
 // tests/test_kvfp8_tree_cpu.py, tests/golden/kvfp8_tree_plans.txt): keep them.
 int kvr_call(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
@@ -58,7 +60,7 @@ int kvr_call(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const
     int rc = kv_build(in, pp, &pk);
     if (rc) return rc;
     const bool packed = in.call == KV_VARLEN, fp8 = (ops.takes & KV_OP_FP8) != 0, tree = (ops.takes & KV_OP_TREE) != 0;
-    if (packed && ops.takes != 0) return FASN_EUNSUPPORTED;
+    if (packed && (ops.takes & ~KV_OP_FP8) != 0) return FASN_EUNSUPPORTED;
     KvFp8 f8{};
     KvTree kt{};
     if (fp8 && (rc = kv_check_fp8(in.a, ops.fp8, f8))) return rc;
@@ -76,6 +78,7 @@ int kvr_call(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const
             using Tag = decltype(tag);
             constexpr int D = decltype(d)::value;
             if (tree) kv_launch<&fasn_kvrope_fp8_tree_kernel<Tag, D>>(grid, 0, s, rp, f8, kt);
+            else if (packed) kv_launch<&fasn_kvvarlen_rope_fp8_kernel<Tag, D>>(grid, 0, s, rp, pk, f8);
             else kv_launch<&fasn_kvrope_fp8_kernel<Tag, D>>(grid, 0, s, rp, f8);
             return launch_rc();
         });
@@ -88,6 +91,7 @@ int kvr_call(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const
         return launch_rc();
     });
 }
+namespace {
 int kvr_plan(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
              char* buf, size_t cap) {
     return kv_plan(buf, cap, [&] { return kvr_call(in, ops, rope, q_out, k_new, v_new, nullptr); });

@@ -28,6 +28,9 @@ int kvv_launch_append(const KvPrefillParams& pp, const KvPacked& pk, hipStream_t
     FASN_LAUNCH((fasn_kvvarlen_append_kernel<D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, pp, pk);
     return launch_rc();
 }
+
+}  // namespace
+
 int kvv_append(const fasn_kvvarlen_args* args, const fasn_view4* k_new, const fasn_view4* v_new, fasn_stream_t stream) {
     KvPrefillParams pp;
     KvPacked pk;
@@ -35,8 +38,6 @@ int kvv_append(const fasn_kvvarlen_args* args, const fasn_view4* k_new, const fa
     if (rc) return rc;
     return kv_dispatch_d(args->pf.kv.D, [&](auto d) { return kvv_launch_append<decltype(d)::value>(pp, pk, (hipStream_t)stream); });
 }
-
-}  // namespace
 
 int kv_launch_packed(const KvFwd& f, hipStream_t s) {
     return kv_dispatch(f.dtype, f.D, [&](auto tag, auto d) { return kv_launch_packed_as<decltype(tag), decltype(d)::value>(f, s); });

@@ -24,6 +24,8 @@ flash_attention_n_kvcache_fp8_window is the sliding-window layer on that cache (
 the rotary call (fasn_kv*_fp8_rope_append: rotate, round to the 16-bit type, quantise, append - one launch), with or without a window.
 flash_attention_n_kvcache_fp8_tree verifies a tree of draft tokens on that cache (fasn_fwd_kv*_fp8_tree, fasn_kv*_fp8_tree_rope_append) and
 flash_attention_n_kvcache_fp8_tree_commit moves the accepted path's code rows behind the prefix (fasn_kvcache_fp8_tree_commit).
+flash_attention_n_kvcache_fp8_varlen, _fp8_varlen_window and _fp8_varlen_rope are the token-packed calls over that cache: the packed FP8
+operand sets have no named entry points and go through the operand-set calls (fasn_kv_forward, fasn_kv_append: a fasn_kv_call).
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -296,11 +298,15 @@ def _append(lib, c, stream, rope=None, q_rot=None, tree=None, fp8=None) -> None:
     name and its operands in ABI order follow from the operands present (_lib.kv_append_call)."""
     if rope is None and c.k_new is None:
         return
-    name, operands = _lib.kv_append_call(c.stem, fp8=fp8, tree=tree, rope=rope)
     views = [None if t is None else _view4(t) for t in (c.k_new, c.v_new)]   # (a rope call without them rotates the queries only)
-    if rope is not None:
-        views.insert(0, _view4(q_rot))
-    _lib.check(getattr(lib, name)(c.args, *operands, *views, stream), name)
+    if c.packed and fp8 is not None:   # the packed FP8 sets have no named entry points: the operand-set call
+        call = _lib.kv_call(c.args, fp8=fp8)
+        _lib.check(lib.fasn_kv_append(call, rope, None if rope is None else _view4(q_rot), *views, stream), "fasn_kv_append")
+    else:
+        name, operands = _lib.kv_append_call(c.stem, fp8=fp8, tree=tree, rope=rope)
+        if rope is not None:
+            views.insert(0, _view4(q_rot))
+        _lib.check(getattr(lib, name)(c.args, *operands, *views, stream), name)
     if rope is not None:
         c.kv.q = _view4(q_rot)
 
@@ -311,6 +317,12 @@ def _forward(lib, c, stream, win=None, tree=None, fp8=None) -> None:
     The names and the operands in ABI order follow from the operands present (_lib.kv_forward_call: the ALiBi forward has the base
     call's workspace)."""
     stem = c.stem
+    if c.packed and fp8 is not None:   # the packed FP8 sets have no named entry points: the operand-set calls (a packed call has its table)
+        call = _lib.kv_call(c.args, fp8=fp8, window=win)
+        ws_bytes = lib.fasn_kv_forward_workspace_bytes(call)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=c.dev)
+        _lib.check(lib.fasn_kv_forward(call, ws.data_ptr(), ws_bytes, stream), "fasn_kv_forward")
+        return
     ws_name, ws_operand, name, _plan, operand = _lib.kv_forward_call(stem, fp8=fp8, tree=tree, window=win, alibi=c.alibi)
     ws_bytes = getattr(lib, ws_name)(c.args, *ws_operand)
     # torch's caching allocator: capturable, as _launch_fwd's. Decode always combines its split partials and a packed call always has its
@@ -802,8 +814,8 @@ def flash_attention_n_kvcache_fp8(
                   correctly rounded in fp32, saturating, NaN -> a NaN code - and then attended to. `cache_seqlens` is not modified.
     :param alibi_slopes, window, rotary_cos, rotary_sin, cu_seqlens_q, tree_mask: anything but None is refused here. A sliding window
                   and rotary embedding on an FP8 cache are calls of their own: flash_attention_n_kvcache_fp8_window,
-                  flash_attention_n_kvcache_fp8_rope; a token tree is flash_attention_n_kvcache_fp8_tree's. ALiBi and packed queries
-                  have 16-bit kernels only.
+                  flash_attention_n_kvcache_fp8_rope; a token tree is flash_attention_n_kvcache_fp8_tree's; token-packed queries are
+                  flash_attention_n_kvcache_fp8_varlen's (this call keeps its [B, H, Sq, D] query). ALiBi has 16-bit kernels only.
     :return: [B, H, Sq, D] in query's dtype (and lse [B, H, Sq] fp32).
     """
     fn = "flash_attention_n_kvcache_fp8"
@@ -931,6 +943,157 @@ def flash_attention_n_kvcache_fp8_rope(
     scales = _fp8_scales(fn, k_scale, v_scale, query, k_cache)
     c = _prepare(fn, "kvprefill", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
                  return_lse, query_seqlens=query_seqlens, by_shape=True, fp8=True)
+    return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query), fp8_scales=scales)
+
+
+def _refuse_fp8_packed(fn, alibi_slopes, tree_mask) -> None:
+    """what the packed FP8 calls have no kernels for, named with the call that has"""
+    if alibi_slopes is not None:
+        raise NotImplementedError(f"{fn}: alibi_slopes is not supported (there are no ALiBi kernels on an FP8 cache or on token-packed "
+                                  "queries); flash_attention_n_kvcache_prefill takes alibi_slopes on a 16-bit cache and a padded step")
+    if tree_mask is not None:
+        raise NotImplementedError(f"{fn}: tree_mask is not supported (there are no token-tree kernels on token-packed queries); "
+                                  "flash_attention_n_kvcache_fp8_tree verifies a tree on the FP8 cache, one [B, H, Sq, D] step")
+
+
+def flash_attention_n_kvcache_fp8_varlen(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        k_scale,
+        v_scale,
+        cu_seqlens_q: Tensor,
+        max_seqlen_q: int,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False,
+        alibi_slopes=None,
+        tree_mask=None):
+    """softmax_n attention of a CONTINUOUS-BATCHING step against an FP8 K/V CACHE, on MI355X: the token-packed buffers of
+    flash_attention_n_kvcache_varlen over the cache of flash_attention_n_kvcache_fp8 - the grid follows the tokens AND a key costs one byte.
+
+    The product of the two calls. From flash_attention_n_kvcache_varlen: `query` [T, H, D], `cu_seqlens_q` (int32 [B + 1] on the device,
+    never read on the host), `max_seqlen_q`, qlen_b, len_b, visibility, `softmax_n_param`, `scale`, `is_causal`, the outputs ([T, H, D], lse
+    [H, T]; rows at or beyond cu[B] are neither read nor written) and the safety under malformed offsets. From
+    flash_attention_n_kvcache_fp8: the cache (torch.float8_e4m3fn, D in {64, 128}, strides in multiples of 16 bytes), the value of a code,
+    the scales, the quantisation of `k_new` / `v_new` and the stale-memory rules. With power-of-two scales the result is, bit for bit,
+    flash_attention_n_kvcache_varlen on `k_cache.to(query.dtype)`. What is particular to the product:
+
+    :param k_scale, v_scale: a Python float, or a floating tensor on the query's device that broadcasts to [B, Hkv] with
+                  B = cu_seqlens_q.shape[0] - 1: one scale per SEQUENCE and K/V head, read by the kernels at the token's sequence.
+    :param k_new, v_new: optional [T, Hkv, D] in query's dtype, token-packed like `query`: token cu[b] + i is quantised with the scales of
+                  (b, hkv) and written to the cache position cache_seqlens[b] + i first, then attended to.
+    :param alibi_slopes, tree_mask: anything but None is refused: no kernels.
+    :return: [T, H, D] in query's dtype (and lse [H, T] fp32).
+
+    Nothing is read on the host; the launches are those of flash_attention_n_kvcache_varlen for the same shapes, so one captured graph
+    serves every step and follows `cu_seqlens_q`, `cache_seqlens` and the scales.
+    """
+    fn = "flash_attention_n_kvcache_fp8_varlen"
+    _refuse_fp8_packed(fn, alibi_slopes, tree_mask)
+    _B, _T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    scales = _fp8_scales(fn, k_scale, v_scale, q4, k_cache)
+    c = _prepare(fn, "kvvarlen", q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
+                 return_lse, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, fp8=True)
+    return _run(c, fp8_scales=scales)
+
+
+def flash_attention_n_kvcache_fp8_varlen_window(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        k_scale,
+        v_scale,
+        cu_seqlens_q: Tensor,
+        max_seqlen_q: int,
+        window: int,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        return_lse: bool = False,
+        alibi_slopes=None,
+        tree_mask=None):
+    """softmax_n attention of a SLIDING-WINDOW layer on a CONTINUOUS-BATCHING step against an FP8 K/V CACHE, on MI355X:
+    flash_attention_n_kvcache_varlen_window's visibility and per-sequence memory contract over flash_attention_n_kvcache_fp8_varlen's
+    buffers and cache.
+
+    Always causal: token cu[b] + i sees key j iff j < len_b and p_i - window < j <= p_i, p_i = i + len_b - qlen_b. Everything else is
+    flash_attention_n_kvcache_fp8_varlen's. With power-of-two scales the result is, bit for bit, flash_attention_n_kvcache_varlen_window on
+    `k_cache.to(query.dtype)`.
+
+    :param window: a Python int >= 1, a constant of the layer and part of a captured graph.
+
+    Memory contract, per sequence: with first_b = 64 * floor(max(0, len_b - qlen_b - window + 1) / 64), cache rows j < first_b and the
+    block-table entries of pages wholly below first_b are never read and may hold any byte. The launches are those of
+    flash_attention_n_kvcache_varlen_window for the same shapes and window.
+    """
+    fn = "flash_attention_n_kvcache_fp8_varlen_window"
+    _refuse_fp8_packed(fn, alibi_slopes, tree_mask)
+    _check_window(fn, window)
+    _B, _T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    scales = _fp8_scales(fn, k_scale, v_scale, q4, k_cache)
+    c = _prepare(fn, "kvvarlen", q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, True,
+                 return_lse, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, fp8=True)
+    return _run(c, window=window, fp8_scales=scales)
+
+
+def flash_attention_n_kvcache_fp8_varlen_rope(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        k_scale,
+        v_scale,
+        cu_seqlens_q: Tensor,
+        max_seqlen_q: int,
+        rotary_cos: Tensor,
+        rotary_sin: Tensor,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False,
+        window: Optional[int] = None,
+        rotary_interleaved: bool = False,
+        alibi_slopes=None,
+        tree_mask=None):
+    """softmax_n attention of a CONTINUOUS-BATCHING step against an FP8 K/V CACHE with ROTARY POSITION EMBEDDING applied to `query` and
+    `k_new` on the way, on MI355X: one layer step of a served Llama / Mistral / GPT-OSS over the FP8 cache - rotate, quantise, append,
+    attend - on token-packed buffers.
+
+    ONE launch rotates token cu[b] + i of k_new at position cache_seqlens[b] + i, rounds it once to query's dtype - the key
+    flash_attention_n_kvcache_varlen_rope would have stored - quantises THAT value with k_scale[b, hkv] and writes the codes; quantises
+    v_new beside it; and rotates the query token at p_i into a [T, H, D] temporary the forward reads. The call equals "rotate `query`
+    and `k_new` in eager torch, then flash_attention_n_kvcache_fp8_varlen (or _varlen_window)" bit for bit. The tables, layouts and the
+    rotation's arithmetic are flash_attention_n_kvcache_rope's; tokens, offsets and outputs flash_attention_n_kvcache_fp8_varlen's.
+
+    :param k_new, v_new: optional [T, Hkv, D]. Without them only `query` is rotated, at p_i over the cache as it is.
+    :param window: None: flash_attention_n_kvcache_fp8_varlen's attention; a Python int >= 1: flash_attention_n_kvcache_fp8_varlen_window's
+                  (needs is_causal=True).
+    :return: [T, H, D] (and lse [H, T]). `query`, `k_new`, `cache_seqlens` are not modified.
+    """
+    fn = "flash_attention_n_kvcache_fp8_varlen_rope"
+    _refuse_fp8_packed(fn, alibi_slopes, tree_mask)
+    if window is not None:
+        _check_window(fn, window, or_none="None or ")
+        if not is_causal:
+            raise ValueError(f"{fn}: a sliding window is always causal; window={window} needs is_causal=True")
+    _B, _T, q4 = _packed_query(fn, query, k_cache, cache_seqlens, cu_seqlens_q, max_seqlen_q)
+    _check_rotary_tables(fn, rotary_cos, rotary_sin, query)
+    _check_rotary_fit(fn, rotary_cos, rotary_sin, q4, k_cache, block_table)
+    scales = _fp8_scales(fn, k_scale, v_scale, q4, k_cache)
+    c = _prepare(fn, "kvvarlen", q4, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
+                 return_lse, cu_seqlens_q=cu_seqlens_q, max_seqlen_q=max_seqlen_q, fp8=True)
     return _run(c, window=window, rope=_rope_operand(rotary_cos, rotary_sin, rotary_interleaved, query), fp8_scales=scales)
 
 

@@ -586,8 +586,8 @@ int fasn_kvcache_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t st
  *              the base call's: fasn_fwd_kv{cache,prefill}_fp8_workspace_bytes, the *_fp8_plan calls write the launches as text.
  * Every rule and error code of the base call holds and is checked first; then fp8 == NULL, a NULL scale or reserved != 0 is FASN_EINVAL,
  * D other than 64 / 128 FASN_EHEADDIM, a scale pointer off 4 bytes or a cache stride that is not a multiple of 16 (bytes) FASN_EALIGN, a
- * negative or overflowing scale stride FASN_EINVAL. Not here: ALiBi, packed queries, e5m2, gradients; windows, rotary appends and trees
- * have calls of their own below.
+ * negative or overflowing scale stride FASN_EINVAL. Not here: ALiBi, e5m2, gradients; windows, rotary appends and trees have calls of
+ * their own below, packed queries the operand-set calls at the end of the cache section.
  */
 typedef struct fasn_kv_fp8 {
     const float* k_scale;        /* DEVICE */
@@ -612,7 +612,8 @@ int fasn_kvprefill_fp8_append(const fasn_kvprefill_args* args, const fasn_kv_fp8
 
 /*
  * FP8 K/V CACHE, THE LAYER (additions within ABI 6; no struct is new or changed): the sliding window and the rotary append over the FP8
- * cache above - what a GPT-OSS / Mistral / Llama layer needs of it. Decode and prefill blocks only; a packed block has no such call.
+ * cache above - what a GPT-OSS / Mistral / Llama layer needs of it. Decode and prefill blocks only; a packed block has no such NAMED call
+ * (fasn_kv_forward / fasn_kv_append below take it).
  *
  *   window     fasn_fwd_kv{cache,prefill}_fp8_window: fasn_fwd_kv{cache,prefill}_window's visibility, tile walk and memory contract (rows
  *              and block-table entries below the window's first tile are never read) with the FP8 call's values and scales. The plan
@@ -680,6 +681,58 @@ int fasn_kvcache_fp8_tree_rope_append_plan(const fasn_kvcache_args* args, const 
 int fasn_kvprefill_fp8_tree_rope_append_plan(const fasn_kvprefill_args* args, const fasn_kv_fp8* fp8, const fasn_kv_rope* rope, const fasn_kv_tree* tree,
                                              const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new, char* buf, size_t cap);
 int fasn_kvcache_fp8_tree_commit(const fasn_kv_tree_commit* commit, fasn_stream_t stream);
+
+/*
+ * THE CACHE CALLS BY OPERAND SET (additions within ABI 6; no struct above is changed): the one host path below every named cache entry
+ * point - argument block, then the operands present - as five entry points that take the operand set as data. A call is its block and
+ * the non-NULL operand pointers; every named entry point above is one such call and keeps its name, its behaviour and its plan.
+ *
+ *   kind       which block `block` points at: FASN_KV_CALL_DECODE a fasn_kvcache_args, FASN_KV_CALL_PREFILL a fasn_kvprefill_args,
+ *              FASN_KV_CALL_PACKED a fasn_kvvarlen_args. reserved = 0.
+ *   operands   fp8, tree, window, alibi: NULL means "not part of the call". A forward reads all four. An append reads fp8, reads tree only
+ *              when `rope` is given, and never reads window or alibi.
+ *   checks     call == NULL, block == NULL, kind outside 0 .. 2 or reserved != 0 is FASN_EINVAL (fasn_kv_forward_workspace_bytes: 0).
+ *              Everything else is the named calls' path: the block's rules first, then - a set without kernels is FASN_EUNSUPPORTED -
+ *              the operands' rules in the family's one order (FP8, tree, window, ALiBi; a rotary append: as fasn_kv*_rope_append states).
+ *              For a set a named entry point serves, the code, the workspace bytes and the plan text are that entry point's.
+ *   forward    fasn_kv_forward_workspace_bytes / fasn_kv_forward / fasn_kv_forward_plan: fasn_fwd_kv*_workspace_bytes / fasn_fwd_kv* /
+ *              fasn_kv*_plan of the set.
+ *   append     fasn_kv_append: with `rope` the set's fasn_kv*_rope_append (q_out needed; k_new == v_new == NULL rotates the queries only),
+ *              without it fasn_kv*_fp8_append when fp8 is given and fasn_kv*_append otherwise (q_out is not read). fasn_kv_append_plan
+ *              writes its one launch as text.
+ *
+ * FP8 CACHE ON PACKED QUERIES. The sets a packed block has beside those of the named packed calls, reached through these entry points only:
+ *   {fp8}, {fp8, window}   fasn_fwd_kvvarlen[_window] over the FP8 cache of fasn_fwd_kvprefill_fp8[_window]: the packed call's tokens,
+ *              offsets, item table, outputs ([1, H, total_tokens, D] views, lse [H, total_tokens]), safety and - under a window - per-sequence
+ *              memory contract, with the FP8 call's values; scale (b, hkv) is read at the token's sequence b. The launches are the schedule
+ *              kernel, the forward and, with several splits, a combine kernel: grids, split count and workspace are those of the 16-bit
+ *              packed call of the same shape (and window), the LDS is the FP8 prefill's. Checks: the block's, the packed operands', the
+ *              FP8 operand's, the window's. D is 64 or 128.
+ *   append     {fp8}: token t of k_new / v_new ([1, H / kv_group, total_tokens, D] views) quantised as fasn_kvprefill_fp8_append quantises
+ *              a row, with the scales of its sequence, to cache row seqlens[b] + t - cu[b] under the rules of fasn_kvvarlen_append; one
+ *              launch of ceil(total_tokens * (H / kv_group) * (D / 16) / 256) workgroups. {fp8} with `rope`: fasn_kvvarlen_rope_append in
+ *              front of the FP8 cache - rotate, round once to `dtype`, quantise with k_scale, write the codes; v_new quantised beside it;
+ *              the query token rotated into q_out - on that call's grid, as fasn_kvprefill_fp8_rope_append defines the values.
+ * A packed block with a tree or with ALiBi slopes, and the FP8 cache with ALiBi slopes, are FASN_EUNSUPPORTED.
+ */
+enum { FASN_KV_CALL_DECODE = 0, FASN_KV_CALL_PREFILL = 1, FASN_KV_CALL_PACKED = 2 };
+typedef struct fasn_kv_call {
+    int32_t kind;                    /* FASN_KV_CALL_* */
+    int32_t reserved;                /* 0 */
+    const void* block;               /* fasn_kvcache_args / fasn_kvprefill_args / fasn_kvvarlen_args, by kind */
+    const fasn_kv_fp8* fp8;          /* NULL: not part of the call */
+    const fasn_kv_tree* tree;
+    const fasn_kv_window* window;
+    const fasn_alibi_slopes* alibi;
+} fasn_kv_call;
+
+size_t fasn_kv_forward_workspace_bytes(const fasn_kv_call* call);
+int fasn_kv_forward(const fasn_kv_call* call, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_kv_forward_plan(const fasn_kv_call* call, char* buf, size_t cap);
+int fasn_kv_append(const fasn_kv_call* call, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
+                   fasn_stream_t stream);
+int fasn_kv_append_plan(const fasn_kv_call* call, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
+                        const fasn_view4* v_new, char* buf, size_t cap);
 
 /*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
