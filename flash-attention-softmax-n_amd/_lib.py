@@ -316,62 +316,50 @@ def load():
     return lib
 
 
+_PLAN_BYTES = 8192   # the one buffer size of every plan read here (the longest plan text of the library is a fraction of it)
+
+
+def _plan(what, *operands, described=False):
+    """The launches the entry point `what` records for `operands`, as (kernel name with template arguments, grid, block, lds bytes): the one
+    reader of the plan lines "name grid=G block=T lds=L cfg=C". `described`: the kernel as family<cfg>, where the line has a cfg."""
+    buf = ctypes.create_string_buffer(_PLAN_BYTES)
+    rc = getattr(load(), what)(*operands, buf, len(buf))
+    if rc < 0:
+        check(rc, what)
+    out = []
+    for line in buf.value.decode().splitlines():
+        name, g, b, l, cfg = line.rsplit(" ", 4)
+        cfg = cfg.split("=", 1)[1]
+        if described and cfg != "-":
+            name = f"{name.split('<', 1)[0]}<{cfg}>"
+        out.append((name, int(g.split("=")[1]), int(b.split("=")[1]), int(l.split("=")[1])))
+    return out
+
+
+_kv_plan = _plan   # (the name the cache tests' support module, tests/kv_layout.py, reads plans by)
+
 def launch_plan(args, which):
     """The kernels fasn_fwd (FASN_PLAN_FWD), fasn_bwd (FASN_PLAN_BWD) or fasn_fwd_ws (FASN_PLAN_FWD_WS) would launch for `args` (a BwdArgs;
     the forward plans read only its .fwd part): a list of (kernel name with template arguments, grid, block, lds bytes). Nothing is
     launched and no device is touched (include/fasn.h: fasn_launch_plan)."""
-    buf = ctypes.create_string_buffer(8192)
-    rc = load().fasn_launch_plan(args, which, buf, len(buf))
-    if rc < 0:
-        check(rc, "fasn_launch_plan")
-    out = []
-    for line in buf.value.decode().splitlines():
-        name, g, b, l, _cfg = line.rsplit(" ", 4)
-        out.append((name, int(g.split("=")[1]), int(b.split("=")[1]), int(l.split("=")[1])))
-    return out
+    return _plan("fasn_launch_plan", args, which)
 
 
 def launch_plan_described(args, which):
     """The same plan as (kernel family<named template arguments>, grid, block, lds bytes): the `cfg` field of the plan lines (ABI 6) names the
     positional template arguments - fasn_fwd_kernel<bf16,D=64,QB=2,plain,OCC=2,NW=4,RING=2,SEED=2> instead of
     fasn_fwd_kernel<fasn::bf16_tag, 64, 2, 0, 2, 4, 0, 0, 2, 0, 2, 1, 0, 0>. What bench.py prints as roofline.kernels."""
-    buf = ctypes.create_string_buffer(8192)
-    rc = load().fasn_launch_plan(args, which, buf, len(buf))
-    if rc < 0:
-        check(rc, "fasn_launch_plan")
-    out = []
-    for line in buf.value.decode().splitlines():
-        name, g, b, l, cfg = line.rsplit(" ", 4)
-        cfg = cfg.split("=", 1)[1]
-        shown = name if cfg == "-" else f"{name.split('<', 1)[0]}<{cfg}>"
-        out.append((shown, int(g.split("=")[1]), int(b.split("=")[1]), int(l.split("=")[1])))
-    return out
-
-
-def _plan_lines(buf):
-    out = []
-    for line in buf.value.decode().splitlines():
-        name, g, b, l, _cfg = line.rsplit(" ", 4)
-        out.append((name, int(g.split("=")[1]), int(b.split("=")[1]), int(l.split("=")[1])))
-    return out
-
-
-def _kv_plan(what, *operands):
-    buf = ctypes.create_string_buffer(4096)
-    rc = getattr(load(), what)(*operands, buf, len(buf))
-    if rc < 0:
-        check(rc, what)
-    return _plan_lines(buf)
+    return _plan("fasn_launch_plan", args, which, described=True)
 
 
 def _kv_forward_plan(stem, args, **operands):
     *_, plan, ops = kv_forward_call(stem, **operands)
-    return _kv_plan(plan, args, *ops)
+    return _plan(plan, args, *ops)
 
 
 def _kv_append_plan(args, q_out, k_new, v_new, **operands):
     name, ops = kv_append_call(kv_stem(args), **operands)
-    return _kv_plan(f"{name}_plan", args, *ops, q_out, k_new, v_new)
+    return _plan(f"{name}_plan", args, *ops, q_out, k_new, v_new)
 
 
 def kvcache_plan(args, alibi=None):
@@ -448,13 +436,13 @@ def kvfp8_tree_rope_plan(args, fp8, rope, tree, q_out, k_new=None, v_new=None):
 def kv_call_plan(call):
     """The kernels fasn_kv_forward would launch for `call` (a KvCall), as launch_plan returns them: for a set a named entry point serves,
     that entry point's plan. Nothing is launched."""
-    return _kv_plan("fasn_kv_forward_plan", call)
+    return _plan("fasn_kv_forward_plan", call)
 
 
 def kv_call_append_plan(call, rope=None, q_out=None, k_new=None, v_new=None):
     """The one launch of fasn_kv_append for `call` (a KvCall) - with `rope` (a KvRope) the rotary append into `q_out` - as launch_plan
     returns it. Nothing is launched."""
-    return _kv_plan("fasn_kv_append_plan", call, rope, q_out, k_new, v_new)
+    return _plan("fasn_kv_append_plan", call, rope, q_out, k_new, v_new)
 
 
 def kvfp8_varlen_plan(args, fp8, win=None):
@@ -479,13 +467,13 @@ def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype
     """The one launch of fasn_softmax_n_fwd (`which` = FASN_ROW_FWD: a, b = the addresses of x and y, c is not read) or fasn_softmax_n_bwd
     (FASN_ROW_BWD: y, dy, dx) for these rows, columns, row strides (in elements) and FASN_DTYPE_*, as launch_plan returns it. Only the
     alignment of the addresses is read. Nothing is launched."""
-    return _kv_plan("fasn_softmax_n_plan", which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype)
+    return _plan("fasn_softmax_n_plan", which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype)
 
 
 def moments_plan(x, sums, rows, cols, row_stride, dtype):
     """The one launch of fasn_moments for these arguments (x, sums: addresses), as launch_plan returns it; the grid is the number of
     chunks a row is cut into. Nothing is launched."""
-    return _kv_plan("fasn_moments_plan", x, sums, rows, cols, row_stride, dtype)
+    return _plan("fasn_moments_plan", x, sums, rows, cols, row_stride, dtype)
 
 
 def check(rc, what):

@@ -7,7 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "fasn.h"
-#include "fasn_launch.h"
+#include "fasn_plan.h"
 #include "fasn_bwd_launch.h"
 #include "fasn_bwd_dn.h"
 
@@ -116,7 +116,7 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
 
 void log_launch(const char* tag_name, unsigned grid, unsigned block, int smem) {
     LaunchLog* const g = t_launch_log;
-    if (g == nullptr) return;
+    if (g == nullptr || g->buf == nullptr) return;   // (no buffer: the launch site has recorded the mode, and that is all such a log asks)
     int st = 0;
     char* dm = abi::__cxa_demangle(tag_name, nullptr, nullptr, &st);
     const char* b = dm ? strstr(dm, "&(void ") : nullptr;
@@ -394,12 +394,9 @@ int fasn_fwd_path(const fasn_fwd_args* args) {
     const int rc = build_fwd(args, p, l);
     if (rc) return rc;
     if (l.dtype == FASN_DTYPE_F32) return FASN_PATH_FP32;
-    int mode = l.mode;
-    if (l.D > 128 && (p.drop_thr || mode == MODE_BIAS_KEYPAD)) {            // D = 256: dropout and bias + key padding through the general modes (launch_fwd_d256)
-        if (mode == MODE_KEYPAD || mode == MODE_BIAS_KEYPAD) mode = p.keypad_fallback;
-        if (p.drop_thr) return mode == MODE_GENERAL_SLOW ? FASN_PATH_ELEMENT : FASN_PATH_VECTOR;
-    }
-    switch (mode) {
+    // The family of the call's MODE, not of the kernel that serves it: a 16-bit bias alone at D = 128 runs the bias + key-padding kernel
+    // with every key kept and is FASN_PATH_VECTOR all the same. D = 256 has modes it serves through others: the launcher's own rule.
+    switch (l.D > 128 ? fwd_d256_mode(p, l.mode) : l.mode) {
         case MODE_PLAIN: case MODE_CAUSAL: return FASN_PATH_PLAIN;
         case MODE_KEYPAD: return FASN_PATH_KEYPAD;
         case MODE_BIAS_KEYPAD: return FASN_PATH_BIAS_KEYPAD;
@@ -602,32 +599,26 @@ int fasn_bwd_dn(const fasn_bwd_args* args, float* dn, int64_t dn_stride_b, int64
 }
 
 int fasn_launch_plan(const fasn_bwd_args* args, int32_t which, char* buf, size_t cap) {
-    if (args == nullptr || buf == nullptr || cap == 0 || which < FASN_PLAN_FWD || which > FASN_PLAN_FWD_WS) return FASN_EINVAL;
-    LaunchLog log{buf, cap, 0};
-    buf[0] = 0;
-    LaunchLog* const outer = t_launch_log;
-    t_launch_log = &log;
-    int rc;
-    if (which == FASN_PLAN_FWD) rc = fasn_fwd(&args->fwd, nullptr);
-    else if (which == FASN_PLAN_BWD) rc = fasn_bwd(args, nullptr);
-    else rc = fasn_fwd_ws(&args->fwd, reinterpret_cast<void*>(uintptr_t(256)), ~size_t(0), nullptr);   // (nothing is launched: any aligned address stands for the workspace)
-    t_launch_log = outer;
-    if (rc) return rc;
-    return log.len > cap ? FASN_EINVAL : (int)log.len;
+    if (args == nullptr || which < FASN_PLAN_FWD || which > FASN_PLAN_FWD_WS) return FASN_EINVAL;
+    return record_plan(buf, cap, [&] {
+        if (which == FASN_PLAN_FWD) return fasn_fwd(&args->fwd, nullptr);
+        if (which == FASN_PLAN_BWD) return fasn_bwd(args, nullptr);
+        return fasn_fwd_ws(&args->fwd, plan_workspace(), ~size_t(0), nullptr);
+    });
 }
 
-
-// The family the BACKWARD of a call is routed to: asked of the launch tables themselves (a recorded plan whose dQ / dK/dV kernels are
-// element-load instantiations), so it cannot drift from them. Differs from fasn_fwd_path at head dim 256, where masks other than key padding
-// and every bias have vector kernels in the forward only.
+// The family the BACKWARD of a call is routed to: the forward's, or FASN_PATH_ELEMENT when the backward's own launch record (LaunchLog::modes
+// of the call under the recorder, no text) holds an element-load instantiation - asked of the launch tables themselves, so it cannot drift
+// from them. Differs from fasn_fwd_path at head dim 256, where masks other than key padding and every bias have vector kernels in the
+// forward only.
 int fasn_bwd_path(const fasn_bwd_args* args) {
     if (args == nullptr) return FASN_EINVAL;
     const int fp = fasn_fwd_path(&args->fwd);
     if (fp < 0 || fp == FASN_PATH_FP32 || fp == FASN_PATH_ELEMENT) return fp;
-    char buf[2048];
-    const int n = fasn_launch_plan(args, FASN_PLAN_BWD, buf, sizeof buf);
-    if (n < 0) return n;
-    return strstr(buf, "element-load") != nullptr ? FASN_PATH_ELEMENT : fp;
+    LaunchLog log{};
+    const int rc = record_plan(log, [&] { return fasn_bwd(args, nullptr); });
+    if (rc < 0) return rc;
+    return (log.modes & (1u << MODE_GENERAL_SLOW)) ? FASN_PATH_ELEMENT : fp;
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@ static int launch_ws256(BwdParams p, hipStream_t s) {
         p.nblk = (p.f.Sq + 127) / 128;
         constexpr auto kern = &fasn_bwd_dq_ws256_kernel<Tag, MODE>;
         ensure_smem<kern>(smem);
-        FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
+        FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
     }
     if (p.f.kvg > 1) {   // grouped K/V (plain / causal): one workgroup per K/V head and key block walks the query heads of its group
         constexpr int smem = bwd_ws256_smem_bytes();
@@ -31,11 +31,11 @@ static int launch_ws256(BwdParams p, hipStream_t s) {
         if (MODE == MODE_CAUSAL) {
             constexpr auto kern = &fasn_bwd_dkdv_ws256_kernel<Tag, MODE_CAUSAL, 1>;
             ensure_smem<kern>(smem);
-            FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * (nbh / p.f.kvg))), dim3(512), smem, s, p);
+            FASN_LAUNCH_MODE(MODE_CAUSAL, kern, dim3((unsigned)(p.nblk * (nbh / p.f.kvg))), dim3(512), smem, s, p);
         } else {
             constexpr auto kern = &fasn_bwd_dkdv_ws256_kernel<Tag, MODE_PLAIN, 1>;
             ensure_smem<kern>(smem);
-            FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * (nbh / p.f.kvg))), dim3(512), smem, s, p);
+            FASN_LAUNCH_MODE(MODE_PLAIN, kern, dim3((unsigned)(p.nblk * (nbh / p.f.kvg))), dim3(512), smem, s, p);
         }
     } else {
         constexpr int smem = bwd_ws256_smem_bytes();
@@ -43,11 +43,11 @@ static int launch_ws256(BwdParams p, hipStream_t s) {
         if (MODE == MODE_CAUSAL || (MODE == MODE_KEYPAD && p.f.causal)) {
             constexpr auto kern = &fasn_bwd_dkdv_ws256_kernel<Tag, MODE_CAUSAL>;
             ensure_smem<kern>(smem);
-            FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
+            FASN_LAUNCH_MODE(MODE_CAUSAL, kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
         } else {
             constexpr auto kern = &fasn_bwd_dkdv_ws256_kernel<Tag, MODE_PLAIN>;
             ensure_smem<kern>(smem);
-            FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
+            FASN_LAUNCH_MODE(MODE_PLAIN, kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
         }
     }
     return launch_rc();
@@ -79,7 +79,7 @@ static int go(const BwdParams& p, int mode, hipStream_t s) {
                 q.nblk = (p.f.Sq + 127) / 128;
                 constexpr auto kern = &fasn_bwd_dq_ws256_kernel<Tag, MODE_GENERAL>;
                 ensure_smem<kern>(smem);
-                FASN_LAUNCH(kern, dim3((unsigned)(q.nblk * nbh)), dim3(512), smem, s, q);
+                FASN_LAUNCH_MODE(MODE_GENERAL, kern, dim3((unsigned)(q.nblk * nbh)), dim3(512), smem, s, q);
                 BwdParams r = p;
                 r.skip |= 2 | 4;   // dQ and delta are launched
                 return launch_bwd_one<Tag, 256, 1, 1, MODE_GENERAL, 1, 1, 0, 0, 2>(r, s);

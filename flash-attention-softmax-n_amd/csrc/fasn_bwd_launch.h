@@ -46,7 +46,7 @@ int launch_bwd_one(BwdParams p, hipStream_t s) {
             p.nblk = (p.f.Sq + 127) / 128;
             constexpr auto kern = &fasn_bwd_dq_ws_kernel<Tag, D, MODE, DROP>;
             ensure_smem<kern>(smem);
-            FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
+            FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
             dq_done = true;
         }
     }
@@ -60,7 +60,7 @@ int launch_bwd_one(BwdParams p, hipStream_t s) {
         // causal: block r and block nblk-1-r in one workgroup (equal workgroups for the in-order dispatcher, see fasn_fwd_kernel.h)
         constexpr bool VEC_PAIR = D <= 128 && mode_is_vector(MODE) && !mode_has_keypad(MODE);   // (the vector modes of a causal call pair their blocks too, fasn_launch.h)
         p.f.pair = ((MODE == MODE_CAUSAL || (VEC_PAIR && p.f.causal)) && (!DROP || MODE == MODE_CAUSAL) && p.nblk > 1 && pair_wanted((long)p.nblk * nbh, wg_slots(OCC_Q, 4, smem), true)) ? 1 : 0;
-        FASN_LAUNCH(kern, dim3((unsigned)((p.f.pair ? (p.nblk + 1) / 2 : p.nblk) * nbh)), dim3(256), smem, s, p);
+        FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)((p.f.pair ? (p.nblk + 1) / 2 : p.nblk) * nbh)), dim3(256), smem, s, p);
         p.f.pair = 0;
     }
     }
@@ -72,14 +72,14 @@ int launch_bwd_one(BwdParams p, hipStream_t s) {
                 if (p.f.kvg > 1) {   // grouped-query attention: one workgroup per K/V head walks the query heads of its group
                     constexpr auto kern = &fasn_bwd_dkdv_ws_kernel<Tag, D, MODE, 1>;
                     ensure_smem<kern>(smem);
-                    FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * (nbh / p.f.kvg))), dim3(512), smem, s, p);
+                    FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(p.nblk * (nbh / p.f.kvg))), dim3(512), smem, s, p);
                     return launch_rc();
                 }
             }
             {
                 constexpr auto kern = &fasn_bwd_dkdv_ws_kernel<Tag, D, MODE, 0, DROP>;
                 ensure_smem<kern>(smem);
-                FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
+                FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(p.nblk * nbh)), dim3(512), smem, s, p);
             }
             return launch_rc();
         }
@@ -95,7 +95,7 @@ int launch_bwd_one(BwdParams p, hipStream_t s) {
         if (p.f.kvg > 1) {
             constexpr auto kern = &fasn_bwd_dkdv_kernel<Tag, D, KB, MODE, OCC_K, DROP, 1, DH, BF32>;
             ensure_smem<kern>(smem);
-            FASN_LAUNCH(kern, dim3((unsigned)(p.nblk * (nbh / p.f.kvg) * DH)), dim3(256), smem, s, p);
+            FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(p.nblk * (nbh / p.f.kvg) * DH)), dim3(256), smem, s, p);
         } else if constexpr (GROUPED_ONLY) {
             return -7;   // FASN_EUNSUPPORTED: a caller broke the rule above
         } else {
@@ -103,7 +103,7 @@ int launch_bwd_one(BwdParams p, hipStream_t s) {
             ensure_smem<kern>(smem);
             constexpr bool VEC_PAIRK = mode_is_vector(MODE) && !mode_has_keypad(MODE);
             p.f.pair = ((MODE == MODE_CAUSAL || (VEC_PAIRK && p.f.causal)) && (!DROP || MODE == MODE_CAUSAL) && DH == 1 && p.nblk > 1 && pair_wanted((long)p.nblk * nbh, wg_slots(OCC_K, 4, smem), true)) ? 1 : 0;
-            FASN_LAUNCH(kern, dim3((unsigned)((p.f.pair ? (p.nblk + 1) / 2 : p.nblk) * nbh * DH)), dim3(256), smem, s, p);
+            FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)((p.f.pair ? (p.nblk + 1) / 2 : p.nblk) * nbh * DH)), dim3(256), smem, s, p);
         }
     }
     return launch_rc();

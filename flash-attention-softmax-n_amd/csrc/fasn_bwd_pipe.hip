@@ -12,7 +12,7 @@ static int launch_dkdv_pipe(BwdParams p, hipStream_t s) {
     constexpr auto kern = &fasn_bwd_dkdv_pipe_kernel<Tag, MODE, DROP>;
     ensure_smem<kern>(smem);
     p.f.pair = (MODE == MODE_CAUSAL && p.nblk > 1 && pair_wanted((long)p.nblk * nbh, wg_slots(2, 4, smem), true)) ? 1 : 0;
-    FASN_LAUNCH(kern, dim3((unsigned)((p.f.pair ? (p.nblk + 1) / 2 : p.nblk) * nbh)), dim3(256), smem, s, p);
+    FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)((p.f.pair ? (p.nblk + 1) / 2 : p.nblk) * nbh)), dim3(256), smem, s, p);
     return launch_rc();
 }
 
@@ -25,7 +25,7 @@ static int launch_dq_pipe(BwdParams p, hipStream_t s) {
     constexpr auto kern = &fasn_bwd_dq_pipe_kernel<Tag, MODE, DROP>;
     ensure_smem<kern>(smem);
     p.f.pair = (MODE == MODE_CAUSAL && p.nblk > 1 && pair_wanted((long)p.nblk * nbh, wg_slots(2, 4, smem), true)) ? 1 : 0;
-    FASN_LAUNCH(kern, dim3((unsigned)((p.f.pair ? (p.nblk + 1) / 2 : p.nblk) * nbh)), dim3(256), smem, s, p);
+    FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)((p.f.pair ? (p.nblk + 1) / 2 : p.nblk) * nbh)), dim3(256), smem, s, p);
     return launch_rc();
 }
 

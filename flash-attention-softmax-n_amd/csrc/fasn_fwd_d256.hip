@@ -15,17 +15,16 @@ static int launch_ws256(FwdParams p, hipStream_t s) {
     p.nqblk = (p.Sq + 127) / 128;
     constexpr auto kern = &fasn_fwd_ws256_kernel<Tag, MODE, DROP>;
     ensure_smem<kern>(smem);
-    FASN_LAUNCH(kern, dim3((unsigned)(p.nqblk * p.B * p.H)), dim3(512), smem, s, p);
+    FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(p.nqblk * p.B * p.H)), dim3(512), smem, s, p);
     return launch_rc();
 }
 template <typename Tag>
 static int go(const FwdParams& p, const FwdLaunch& l, hipStream_t s) {
+    const int mode = fwd_d256_mode(p, l.mode);   // (fasn_launch.h: the routing fasn_fwd_path reports)
     if (p.drop_thr) {   // dropout (round 6): the vector general instantiation whenever the call's mask / bias rows move as vectors (or there is no operand)
-        const int md = (l.mode == MODE_BIAS_KEYPAD || l.mode == MODE_KEYPAD) ? p.keypad_fallback : l.mode;
-        if (md == MODE_GENERAL_SLOW) return launch_fwd_one<Tag, 256, 1, MODE_GENERAL_SLOW, 1, 4, 0, 0, 1, 2>(p, s);   // the element-load kernel
+        if (mode == MODE_GENERAL_SLOW) return launch_fwd_one<Tag, 256, 1, MODE_GENERAL_SLOW, 1, 4, 0, 0, 1, 2>(p, s);   // the element-load kernel
         return launch_ws256<Tag, MODE_GENERAL, 1>(p, s);   // the two-wave kernel (per-wave images; keep bits on the packed weights)
     }
-    const int mode = l.mode == MODE_BIAS_KEYPAD ? p.keypad_fallback : l.mode;   // bias + key padding: the dense-mask view of the same mask
     switch (mode) {
         case MODE_PLAIN: return launch_ws256<Tag, MODE_PLAIN>(p, s);
         case MODE_CAUSAL: return launch_ws256<Tag, MODE_CAUSAL>(p, s);

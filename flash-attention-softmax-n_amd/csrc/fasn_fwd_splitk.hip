@@ -19,7 +19,7 @@ int launch_splitk_one(FwdParams p, hipStream_t s) {
     // kernels recompute P from - with the scale applied in fp32 here, lse and the backward's logits differed by up to u |x|
     constexpr auto kern = &fasn_fwd_kernel<Tag, D, 1, MODE, OCC, 4, 0, 0, RING, 1, 2>;
     ensure_smem<kern>(smem);
-    FASN_LAUNCH(kern, dim3((unsigned)(p.nqblk * p.nsplit * p.B * p.H)), dim3(256), smem, s, p);
+    FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(p.nqblk * p.nsplit * p.B * p.H)), dim3(256), smem, s, p);
     const int64_t nthr = (int64_t)p.B * p.H * p.Sq * (D / 4);
     FASN_LAUNCH((fasn_fwd_combine_kernel<Tag, D>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();

@@ -19,7 +19,7 @@
 // private ring of two images of its [32 rows][32 keys] - 2 KiB of bias, 1 KiB of mask bytes, three LDS-DMA requests, asked for two blocks
 // ahead right after the block's image has been read into registers - and starts its score accumulator at bias*log2e (-inf where the mask
 // byte is clear) instead of zero; nothing else changes, wave B does not know. The 24 KiB of images are paid for with the fourth V slot
-// (V is then requested one block ahead of the block wave B is working on). Dropout stays on the feature-half kernels.
+// (V is then requested one block ahead of the block wave B is working on). Dropout: this mode's DROP = 1 instantiation (below); element-load operands only stay on the feature-half kernel.
 #pragma once
 #include "fasn_fwd_kernel.h"
 

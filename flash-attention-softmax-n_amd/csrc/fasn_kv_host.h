@@ -1,13 +1,13 @@
 // fasn_kv_host.h — the ONE host layer of the K/V-cache family (decode, prefill, packed prefill, rotary append): argument checks, parameter
 // packing, the operand set of a call (KvOps) with its one check order and its table of supported sets, the launch plan, the workspace
-// rule, the one forward / plan / workspace path, the token-tree commit, the launch recorder and the dtype x head-dim dispatch.
+// rule, the one forward / plan / workspace path, the token-tree commit and the dtype x head-dim dispatch.
 // fasn_kvcache.hip defines what is declared here, but for the forward launchers: fasn_kvcache.hip, fasn_kvprefill.hip, fasn_kvvarlen.hip
 // and fasn_kvfp8.hip each define the launcher of the kernels they instantiate (fasn_kvrope.hip: the rotary appends of every call).
 #pragma once
 #include <type_traits>
 #include "fasn.h"
 #include "fasn_kvvarlen.h"
-#include "fasn_launch.h"
+#include "fasn_plan.h"
 
 namespace fasn {
 
@@ -85,7 +85,8 @@ int kv_check_fp8(const fasn_kvcache_args* a, const fasn_kv_fp8* o, KvFp8& f8);
 // and follow the FP8 calls' 16-byte rule, D is 64 or 128
 int kv_build_commit(const fasn_kv_tree_commit* a, bool fp8, KvCommit& c);
 // The one forward path. Behind the base checks the operands are checked in ONE order, each at most once - FP8, tree, window, ALiBi - then
-// the workspace; then the launcher of the call's translation unit runs. kv_forward_plan is the same call under the launch recorder.
+// the workspace; then the launcher of the call's translation unit runs. kv_forward_plan is the same call under the launch recorder
+// (record_plan, fasn_plan.h), with plan_workspace() and a size of ~size_t(0) standing for the workspace.
 size_t kv_workspace_bytes(const KvArgs& in, const KvOps& ops);
 int kv_forward(const KvArgs& in, const KvOps& ops, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
 int kv_forward_plan(const KvArgs& in, const KvOps& ops, char* buf, size_t cap);
@@ -140,22 +141,6 @@ template <auto Kern, typename... A>
 void kv_launch(unsigned grid, int smem, hipStream_t s, const A&... a) {
     ensure_smem<Kern>(smem);
     FASN_LAUNCH(Kern, dim3(grid), dim3(256), smem, s, a...);
-}
-
-// A call's launches as text: the call itself under the launch recorder (nothing is launched, no device is touched). The forwards are
-// recorded with kv_plan_workspace() and a size of ~size_t(0) standing for the workspace: any aligned address will do.
-inline void* kv_plan_workspace() { return reinterpret_cast<void*>(uintptr_t(256)); }
-template <typename Call>
-int kv_plan(char* buf, size_t cap, Call call) {
-    if (buf == nullptr || cap == 0) return FASN_EINVAL;
-    LaunchLog log{buf, cap, 0};
-    buf[0] = 0;
-    LaunchLog* const outer = t_launch_log;
-    t_launch_log = &log;
-    const int rc = call();
-    t_launch_log = outer;
-    if (rc) return rc;
-    return log.len > cap ? FASN_EINVAL : (int)log.len;
 }
 
 }  // namespace fasn

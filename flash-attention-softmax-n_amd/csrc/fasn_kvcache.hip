@@ -271,7 +271,7 @@ int kv_forward(const KvArgs& in, const KvOps& ops, void* workspace, size_t works
 }
 
 int kv_forward_plan(const KvArgs& in, const KvOps& ops, char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kv_forward(in, ops, kv_plan_workspace(), ~size_t(0), nullptr); });
+    return record_plan(buf, cap, [&] { return kv_forward(in, ops, plan_workspace(), ~size_t(0), nullptr); });
 }
 
 // fasn_kvcache_tree_commit / fasn_kvcache_fp8_tree_commit: the cache's rules as kv_build states them for the members this block has (an FP8

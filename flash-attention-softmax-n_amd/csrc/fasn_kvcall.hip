@@ -78,7 +78,7 @@ int fasn_kv_append(const fasn_kv_call* call, const fasn_kv_rope* rope, const fas
 int fasn_kv_append_plan(const fasn_kv_call* call, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new,
                         const fasn_view4* v_new, char* buf, size_t cap) {
     if (!kvc_ok(call)) return FASN_EINVAL;
-    return kv_plan(buf, cap, [&] { return kvc_append(call, rope, q_out, k_new, v_new, nullptr); });
+    return record_plan(buf, cap, [&] { return kvc_append(call, rope, q_out, k_new, v_new, nullptr); });
 }
 
 }  // extern "C"

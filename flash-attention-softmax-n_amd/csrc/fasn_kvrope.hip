@@ -94,7 +94,7 @@ int kvr_call(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const
 namespace {
 int kvr_plan(const KvArgs& in, const KvOps& ops, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_new, const fasn_view4* v_new,
              char* buf, size_t cap) {
-    return kv_plan(buf, cap, [&] { return kvr_call(in, ops, rope, q_out, k_new, v_new, nullptr); });
+    return record_plan(buf, cap, [&] { return kvr_call(in, ops, rope, q_out, k_new, v_new, nullptr); });
 }
 
 }  // namespace

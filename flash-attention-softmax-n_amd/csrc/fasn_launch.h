@@ -19,13 +19,24 @@ int launch_fwd_d128(const FwdParams& p, const FwdLaunch& l, hipStream_t s);
 int launch_fwd_d256(const FwdParams& p, const FwdLaunch& l, hipStream_t s);
 int launch_fwd_splitk(const FwdParams& p, const FwdLaunch& l, hipStream_t s);   // p.nsplit > 1, partial buffers set
 
+// The mode a D = 256 forward runs in (launch_fwd_d256 launches it, fasn_fwd_path reports its family): bias + key padding is the dense-mask
+// view of the same mask; under dropout so is key padding, and then ONE vector instantiation (MODE_GENERAL, two-wave kernel) serves every
+// call whose mask / bias rows move as vectors, no operand at all included - FASN_PATH_VECTOR where D <= 128 says FASN_PATH_PLAIN.
+inline int fwd_d256_mode(const FwdParams& p, int mode) {
+    if (mode == MODE_BIAS_KEYPAD || (p.drop_thr && mode == MODE_KEYPAD)) mode = p.keypad_fallback;
+    return (p.drop_thr && mode != MODE_GENERAL_SLOW) ? MODE_GENERAL : mode;
+}
+
 // Launch recorder (fasn_launch_plan, include/fasn.h): while the calling thread has a log installed, every launch site of the library
 // (FASN_LAUNCH) writes "kernel<template arguments> grid=G block=T lds=L" into it INSTEAD of launching, and no HIP call is made - the
 // host side of fasn_fwd / fasn_bwd then runs to its end exactly as for a real call, so the record is the launch table itself, not a
 // description of it (bench.py prints it as roofline.kernels; tests/test_spill_gate.py looks the names up in the code objects).
+// `modes` is the same record as data: bit MODE_* for every launch of a kernel that has a mode, set by the launch site from the template
+// argument itself (FASN_LAUNCH_MODE). A log without a buffer records that alone - what fasn_fwd_path / fasn_bwd_path ask (fasn_plan.h).
 struct LaunchLog {
     char* buf;
     size_t cap, len;
+    unsigned modes;
 };
 extern thread_local LaunchLog* t_launch_log;
 void log_launch(const char* pretty, unsigned grid, unsigned block, int smem);
@@ -37,6 +48,11 @@ const char* kernel_pretty_name() { return typeid(KernelTag<Kern>).name(); }   //
     do {                                                                                                                       \
         if (::fasn::t_launch_log != nullptr) ::fasn::log_launch(::fasn::kernel_pretty_name<(kern)>(), (grid).x, (block).x, (int)(smem)); \
         else hipLaunchKernelGGL(kern, grid, block, smem, stream, __VA_ARGS__);                                                \
+    } while (0)
+#define FASN_LAUNCH_MODE(mode, ...)   /* a kernel whose template arguments include MODE_* `mode` */                          \
+    do {                                                                                                                       \
+        if (::fasn::t_launch_log != nullptr) ::fasn::t_launch_log->modes |= 1u << (mode);                                      \
+        FASN_LAUNCH(__VA_ARGS__);                                                                                              \
     } while (0)
 
 // A kernel that needs more than 48 KiB of dynamic LDS must be told so once per (kernel, device). The attribute is per
@@ -105,14 +121,14 @@ int launch_fwd_one(FwdParams p, hipStream_t s) {
             // items: such a launch takes the static deal below instead
             const bool zeroed = t_launch_log != nullptr || hipMemsetAsync(p.xq, 0, 8 * sizeof(int), s) == hipSuccess;
             if (zeroed) {
-                FASN_LAUNCH(kern, dim3((unsigned)(blocks * p.B * p.H + 8 * kXqSurplus)), dim3(NW * 64), smem, s, p);
+                FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(blocks * p.B * p.H + 8 * kXqSurplus)), dim3(NW * 64), smem, s, p);
                 return launch_rc();
             }
             (void)hipGetLastError();
         }
     }
     p.xq = nullptr;   // (every other instantiation: static deal)
-    FASN_LAUNCH(kern, dim3((unsigned)(blocks * p.B * p.H * VH)), dim3(NW * 64), smem, s, p);
+    FASN_LAUNCH_MODE(MODE, kern, dim3((unsigned)(blocks * p.B * p.H * VH)), dim3(NW * 64), smem, s, p);
     return launch_rc();
 }
 

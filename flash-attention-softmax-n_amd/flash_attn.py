@@ -329,8 +329,10 @@ class _FlashAttentionSoftmaxN(torch.autograd.Function):
         else:
             a.dbias.ptr = None
         if pl.bwd_path is None:   # once per cached call signature
-            pl.bwd_path = lib.fasn_bwd_path(a)
-            if pl.bwd_path == _lib.FASN_PATH_ELEMENT and pl.path != _lib.FASN_PATH_ELEMENT:
+            path = lib.fasn_bwd_path(a)
+            if path >= 0:   # (a refusal is no answer: the fasn_bwd below reports the same code, and the next backward asks again)
+                pl.bwd_path = path
+            if path == _lib.FASN_PATH_ELEMENT and pl.path != _lib.FASN_PATH_ELEMENT:
                 why = ("bwd", _sig(mask), _sig(bias), D)
                 if why not in _WARNED_SLOW:
                     _WARNED_SLOW.add(why)

@@ -85,7 +85,8 @@ typedef struct fasn_fwd_args {
     int32_t causal;     /* bottom-right aligned: key j visible to row i iff j <= i + Sk - Sq */
     float dropout_p;    /* in [0,1): attention-weight dropout; realised as thr/65536 with thr = round(65536 p) in [1,65535] */
     uint64_t seed, offset; /* dropout stream: the keep bit of (b,h,row,key) is a pure function of (seed, offset, indices);
-                              pass the SAME values to fasn_bwd (see flash-attention-softmax-n_amd/dropout.py) */
+                              pass the SAME values to fasn_bwd (see flash-attention-softmax-n_amd/dropout.py). The function is part
+                              of FASN_ABI_VERSION - it changed in ABI 6 - so a mask is reproducible within one ABI version only */
     int32_t kv_group;      /* grouped-query attention (ABI 2): query head h reads K/V head h / kv_group, i.e. k and v are
                               [B, H / kv_group, Sk, D] addressed through their head stride; 0 or 1 = one K/V head per query
                               head. fasn_bwd writes dk / dv per K/V head, [B, H / kv_group, Sk, D]: each dK/dV workgroup walks the
@@ -143,7 +144,12 @@ int fasn_fwd(const fasn_fwd_args* args, fasn_stream_t stream);
  * differ in speed. FASN_PATH_ELEMENT is the one to know about: masks / biases whose rows cannot be moved in aligned vector
  * pieces (unaligned or strided rows, key stride != 1; an fp32 bias next to 16-bit q at head dim 256, under dropout, or with rows
  * that are not 16-byte aligned - at head dims <= 128 an aligned fp32 bias takes the vector family since ABI 5), scale <= 0 with a bias, fp16 with
- * scale*log2(e) > 8 take per-element loads and run 3-5 x slower than the vector path (ABI 6: dropout at head dim 256 no longer does - it runs the vector general kernels, and reports FASN_PATH_VECTOR, whenever the call's operands allow). Nothing is launched. (The reference has no counterpart: its SDPA backends are picked inside torch.)
+ * scale*log2(e) > 8 take per-element loads and run 3-5 x slower than the vector path. Nothing is launched. (The reference has no
+ * counterpart: its SDPA backends are picked inside torch.)
+ * The value names the family of the call's operands, except at head dim 256 UNDER DROPOUT (ABI 6), where one vector instantiation serves
+ * every call whose mask / bias rows move as vectors: such a call reports FASN_PATH_VECTOR - also with a key-padding mask, with a bias next to
+ * one, and with no mask or bias at all (FASN_PATH_PLAIN at head dims <= 128) - and FASN_PATH_ELEMENT otherwise. Without dropout, bias + key
+ * padding at head dim 256 reports the family of the dense view of its mask (FASN_PATH_VECTOR or FASN_PATH_ELEMENT).
  */
 #define FASN_PATH_PLAIN 0       /* no mask / bias (causal or not) */
 #define FASN_PATH_KEYPAD 1      /* key-padding mask as per-tile visibility bits */
@@ -225,8 +231,11 @@ int fasn_launch_plan(const fasn_bwd_args* args, int32_t which, char* buf, size_t
 
 /*
  * Which kernel family the BACKWARD of a call takes (ABI 6): the value fasn_fwd_path gives for args->fwd, except that FASN_PATH_ELEMENT is
- * returned whenever the recorded backward plan contains an element-load kernel - today the two only differ through operands the backward's kernels cannot move as vectors although the forward's can (none known: since round 6 the head dim 256 backward
- * has vector instantiations for dense masks and 16-bit biases too); kept so that the front end's slow-path warning follows the backward's launch table, not an assumption about it. Same argument rules as fasn_launch_plan; nothing is launched.
+ * returned whenever the backward launches an element-load kernel. The question is put to the launch record itself (fasn_bwd under the
+ * recorder of fasn_launch_plan, read as data: no plan text is written, so no length can make it fail), so that the front end's slow-path
+ * warning follows the backward's launch table, not an assumption about it. Today the two only differ through operands the backward's kernels
+ * cannot move as vectors although the forward's can (none known: since round 6 the head dim 256 backward has vector instantiations for dense
+ * masks and 16-bit biases too). Argument rules and FASN_E* codes of fasn_bwd; nothing is launched.
  */
 int fasn_bwd_path(const fasn_bwd_args* args);
 

@@ -178,7 +178,8 @@ def test_fwd_path_query(pkg):
     assert lib.fasn_fwd_path(with_views(bias=(0, 64, 8, 1), bias_dtype=1)) == 2                    # aligned 16-bit bias
     assert lib.fasn_fwd_path(with_views(mask=(8, 0, 0, 1), bias=(0, 64, 8, 1), bias_dtype=1)) == 3
     # fp32 bias next to bf16 q (round 5): rows movable in 16-byte pieces take the vector path at head dims <= 128 (fp32 image instantiations),
-    # with a key-padding mask the visibility-bit family; head dim 256, 8-byte-only alignment and dropout keep the element loads
+    # with a key-padding mask the visibility-bit family; an fp32 bias at head dim 256, with 8-byte-only alignment or under dropout keeps the element loads
+    # (dropout as such does not: at head dim 256 too it runs vector kernels and reports FASN_PATH_VECTOR, include/fasn.h)
     assert lib.fasn_fwd_path(with_views(bias=(0, 64, 8, 1), bias_dtype=2)) == 2
     assert lib.fasn_fwd_path(with_views(mask=(8, 0, 0, 1), bias=(0, 64, 8, 1), bias_dtype=2)) == 3
     assert lib.fasn_fwd_path(with_views(bias=(0, 64, 8, 1), bias_dtype=2, D=128, Dv=128)) == 2
