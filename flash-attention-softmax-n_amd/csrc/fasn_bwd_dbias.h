@@ -101,7 +101,9 @@ __global__ void __launch_bounds__(256, 1) fasn_bwd_dbias_kernel(const DbiasParam
         // thread `tid` fills slots tid + 256 i: 16-byte chunk c of row r <- global chunk c ^ swz(r); rows / keys past the end of the
         // (b,h) slice read back as zeros (range-checked descriptor), keys past Sk inside it are discarded by the visibility test
         const char* bbase = p.bias + ((int64_t)bb * p.bs[0] + (int64_t)hb * p.bs[1] + key0) * besz;
-        const u32x4 brw = make_rsrc_words(bbase, (uint32_t)(p.bias_bytes * (besz / 2)) - (uint32_t)(key0 * besz));
+        // (bias_bytes is in BYTES at the bias's own element size, build_fwd: scaling it by besz / 2 once more doubled the range of an fp32
+        // bias, and rows past Sq of the buffer's last (b,h) slice were fetched from beyond the allocation instead of reading back as zeros)
+        const u32x4 brw = make_rsrc_words(bbase, (uint32_t)p.bias_bytes - (uint32_t)(key0 * besz));
         const int cpr = 128 * besz / 16;   // chunks per row: 16 or 32
         const uint32_t dst = lds_addr(ldsS) + wave * 1024;
         for (int i = 0; i < (128 * cpr) / 256; ++i) {

@@ -58,7 +58,7 @@ struct FwdParams {
     int mask_vec;   // mask key stride 1 and every row 4-byte aligned: 4 keys per load
     int batch_inner;  // bias/mask broadcast over batch: schedule the batch innermost so a head's bias tile is reused from L2
     unsigned kbytes, vbytes;  // byte extent of one (b,h) K / V matrix: Sk * row_stride * 2 (buffer descriptor range)
-    unsigned bias_bytes, mask_bytes;  // byte extent of one (b,h) bias / mask slice: (Sq-1)*row_stride + Sk elements
+    unsigned bias_bytes, mask_bytes;  // byte extent of one (b,h) bias / mask slice: ((Sq-1)*row_stride + Sk) elements x the element size (4 for an fp32 bias)
     unsigned drop_thr;        // dropout: drop an attention weight iff its 16-bit hash field < drop_thr (0 = no dropout)
     unsigned seed_lo, seed_hi;
     const uint64_t* rng;      // optional device {seed, offset}: replaces seed_lo / seed_hi (graph-safe dropout state)

@@ -47,10 +47,23 @@ def _rows_ok(t: Tensor) -> bool:
     return all(t.stride(i) % q == 0 or t.size(i) == 1 for i in range(t.dim() - 1))
 
 
+def _span_ok(t: Tensor) -> bool:
+    """The span rule of the C ABI (include/fasn.h): one (batch, head) matrix - the last row's start plus one row - spans less than 2^31
+    bytes. fasn_fwd refuses a K or V beyond it and fasn_bwd a Q or dO as well (the forward reads Q by 64-bit addresses), so a packed
+    buffer at a very long context would run its forward and fail its backward with a bare FASN_EINVAL."""
+    return ((t.size(-2) - 1) * t.stride(-2) + t.size(-1)) * t.element_size() < (1 << 31)
+
+
 def _canon(t: Tensor) -> Tensor:
+    """the operand as the kernels take it: itself, or a contiguous copy where its rows break the alignment rule or its (b, h) span the
+    span rule (a contiguous tensor beyond the span rule stays as it is: the call reports it)"""
     if t.is_contiguous() and t.data_ptr() % 16 == 0 and (t.shape[-1] * t.element_size()) % 16 == 0:
         return t   # the common case, one C++ call instead of a stride walk
-    return t if _rows_ok(t) else t.contiguous()
+    if _rows_ok(t) and _span_ok(t):
+        return t
+    c = t.contiguous()
+    # a contiguous tensor whose base is off the 16-byte alignment (a slice of a flat buffer) is its own .contiguous(): only a clone moves it
+    return c.clone() if c.data_ptr() % 16 else c
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)   # the current stream's handle without building a torch.cuda.Stream object (6 us of host time per launch)

@@ -21,7 +21,23 @@
  * Tensor layout: 4-D (batch, head, seq, feature) addressed by element strides; the feature stride
  * must be 1 and base pointers / other strides must keep every row 16-byte aligned (strides % 8 elements for the 16-bit
  * types, % 4 for fp32). A stride of 0 is
- * a broadcast dimension (mask, bias, and the head dimension of K/V for shared-KV layouts).
+ * a broadcast dimension (mask, bias, and the head dimension of K/V for shared-KV layouts). The rule holds for the inputs (q, k, v,
+ * dout, mask, bias) and for the outputs (o, dq, dk, dv, dbias) alike: each is addressed by its own strides, none has to be contiguous,
+ * and no two have to share a layout; batch and head strides are 64-bit and unbounded. lse and delta are contiguous [B, H, Sq].
+ *
+ * The span rule. The span of one (batch, head) matrix of an operand with `rows` rows of `width` elements is
+ * ((rows - 1) * row_stride + width) * element_size bytes - the last row's start plus one row. The vector kernels address such a matrix
+ * through a 32-bit buffer descriptor, so:
+ *   - K and V (rows = Sk): a span of 2^31 bytes or more is FASN_EINVAL in every call that takes a fasn_fwd_args (fasn_fwd, fasn_fwd_ws,
+ *     fasn_fwd_n, fasn_bwd, fasn_bwd_dn, the workspace and path queries).
+ *   - Q and dout (rows = Sq): a span of 2^31 bytes or more is FASN_EINVAL in fasn_bwd only. The forward reads Q by 64-bit addresses and
+ *     has no such bound - a call may therefore pass fasn_fwd and be refused by fasn_bwd; a caller that differentiates copies such a Q
+ *     (or dout) into a denser buffer first (flash_attn._canon does).
+ *   - mask and bias (rows = Sq, width = Sk): a span of 2^31 bytes or more is no error; the call takes the element-load kernels
+ *     (FASN_PATH_ELEMENT), which address every element in 64 bits.
+ *   - o, dq, dk, dv, dbias: written through 64-bit addresses, no bound.
+ * With a 16-bit type and 65 rows the largest legal row stride is therefore (2^31 - 2 width) / 128 elements rounded down to a
+ * multiple of 8; the kernels' 32-bit tile and lane offsets (rows * row_stride * element_size) are sized for exactly that bound.
  */
 #ifndef FASN_H_
 #define FASN_H_
