@@ -47,6 +47,7 @@ EXPORTS = (
     "fasn_kvcache_fp8_tree_rope_append", "fasn_kvprefill_fp8_tree_rope_append", "fasn_kvcache_fp8_tree_rope_append_plan",
     "fasn_kvprefill_fp8_tree_rope_append_plan", "fasn_kvcache_fp8_tree_commit",
     "fasn_kv_forward_workspace_bytes", "fasn_kv_forward", "fasn_kv_forward_plan", "fasn_kv_append", "fasn_kv_append_plan",
+    "fasn_fwd_varlen", "fasn_bwd_varlen", "fasn_varlen_plan",
 )
 
 
@@ -77,6 +78,13 @@ class BwdArgs(Structure):
         ("flags", c_int32),
         ("dbias_dtype", c_int32),
     ]
+
+
+class Varlen(Structure):
+    """fasn_varlen (include/fasn.h): the packed variable-length training call - the two offset tables in device memory, the number of
+    sequences and the host bounds of the lengths; reserved = 0"""
+    _fields_ = [("cu_seqlens_q", c_void_p), ("cu_seqlens_k", c_void_p), ("num_seqs", c_int32), ("max_seqlen_q", c_int32),
+                ("max_seqlen_k", c_int32), ("reserved", c_int32)]
 
 
 class KvCacheArgs(Structure):
@@ -306,6 +314,12 @@ def load():
     lib.fasn_softmax_n_plan.argtypes = [c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int32, c_char_p, c_size_t]
     lib.fasn_moments_plan.restype = c_int32
     lib.fasn_moments_plan.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int32, c_char_p, c_size_t]
+    lib.fasn_fwd_varlen.restype = c_int32
+    lib.fasn_fwd_varlen.argtypes = [POINTER(FwdArgs), POINTER(Varlen), c_void_p, c_int64, c_void_p]
+    lib.fasn_bwd_varlen.restype = c_int32
+    lib.fasn_bwd_varlen.argtypes = [POINTER(BwdArgs), POINTER(Varlen), c_void_p]
+    lib.fasn_varlen_plan.restype = c_int32
+    lib.fasn_varlen_plan.argtypes = [POINTER(BwdArgs), POINTER(Varlen), c_int32, c_char_p, c_size_t]
     for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -360,6 +374,12 @@ def _kv_forward_plan(stem, args, **operands):
 def _kv_append_plan(args, q_out, k_new, v_new, **operands):
     name, ops = kv_append_call(kv_stem(args), **operands)
     return _plan(f"{name}_plan", args, *ops, q_out, k_new, v_new)
+
+
+def varlen_plan(args, varlen, which):
+    """The kernels fasn_fwd_varlen (FASN_PLAN_FWD) or fasn_bwd_varlen (FASN_PLAN_BWD) would launch for `args` (a BwdArgs that describes the
+    packed operands) under `varlen` (a Varlen), as launch_plan returns them. Nothing is launched."""
+    return _plan("fasn_varlen_plan", args, varlen, which)
 
 
 def kvcache_plan(args, alibi=None):

@@ -65,6 +65,7 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
         {"fasn_kvprefill_fwd_fp8_tree_kernel", "T D"},
         {"fasn_kvrope_fp8_tree_kernel", "T D"},
         {"fasn_kvcache_fp8_tree_commit_kernel", "D"},
+        {"fasn_varlen_tail_kernel", "TOK"},
     };
     static const char* const modes[] = {"plain", "causal", "bias+mask", "element-load", "bias", "mask", "keypad", "bias+keypad"};
     if (cap == 0) return 0;
@@ -99,7 +100,7 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
         const long num = strtol(val, nullptr, 10);
         char item[96];
         int in = 0;
-        if (*pn == 'T' && pe - pn == 1) in = snprintf(item, sizeof item, "%s", strstr(val, "bf16") ? "bf16" : "f16");
+        if (*pn == 'T' && pe - pn == 1) in = snprintf(item, sizeof item, "%s%s", strstr(val, "bf16") ? "bf16" : "f16", strstr(val, "varlen") ? ",varlen" : "");   // (*_varlen_tag: packed variable-length items)
         else if (*pn == 'M' && pe - pn == 1) in = snprintf(item, sizeof item, "%s", (num >= 0 && num < 8) ? modes[num] : val);
         else if (*pn == '!') { if (strcmp(val, "0") != 0 && strcmp(val, "false") != 0) in = snprintf(item, sizeof item, "%.*s=%s", (int)(pe - pn - 1), pn + 1, val); }
         else if (*pn == '1') { if (num != 1) in = snprintf(item, sizeof item, "%.*s=%s", (int)(pe - pn - 1), pn + 1, val); }

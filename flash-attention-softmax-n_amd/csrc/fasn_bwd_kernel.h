@@ -40,6 +40,37 @@ struct BwdParams {
     int skip;          // host side only (launch_bwd_one): bit 1 = dQ, bit 2 = delta are launched by the caller (fasn_bwd_d256.hip)
 };
 
+// Packed variable-length work items (fasn_fwd_kernel.h, fasn_common.h): the backward's launch block `l` patched into `bp` for sequence b -
+// operands, gradients, lengths and descriptor ranges - and, per query head (the dK/dV kernel of grouped K/V walks several per item), the
+// lse / delta rows. lse and delta are [H, Sq] of the packed call.
+template <int D>
+FASN_DEV void varlen_enter_bwd(const BwdParams& l, BwdParams& bp, int b) {
+    int q0, q1, k0, k1;
+    varlen_range(varlen_cu_q(l.f), b, l.f.Sq, q0, q1);
+    varlen_range(varlen_cu_k(l.f), b, l.f.Sk, k0, k1);
+    FwdParams& p = bp.f;
+    p.Sq = q1 - q0;
+    p.Sk = k1 - k0;
+    p.q = l.f.q + (int64_t)q0 * l.f.qs[2] * 2;
+    p.o = l.f.o + (int64_t)q0 * l.f.os[2] * 2;
+    p.k = l.f.k + (int64_t)k0 * l.f.ks[2] * 2;
+    p.v = l.f.v + (int64_t)k0 * l.f.vs[2] * 2;
+    bp.dout = l.dout + (int64_t)q0 * l.dos[2] * 2;
+    bp.dq = l.dq + (int64_t)q0 * l.dqs[2] * 2;
+    bp.dk = l.dk + (int64_t)k0 * l.dks[2] * 2;
+    bp.dv = l.dv + (int64_t)k0 * l.dvs[2] * 2;
+    p.kbytes = varlen_bytes(p.Sk, l.f.ks[2], D);
+    p.vbytes = varlen_bytes(p.Sk, l.f.vs[2], D);
+    bp.qbytes = varlen_bytes(p.Sq, l.f.qs[2], D);
+    bp.dobytes = varlen_bytes(p.Sq, l.dos[2], D);
+}
+FASN_DEV void varlen_head_bwd(const BwdParams& l, BwdParams& bp, int b, int h) {   // (after varlen_enter_bwd: bp.f.Sq is the item's length)
+    int q0, q1;
+    varlen_range(varlen_cu_q(l.f), b, l.f.Sq, q0, q1);
+    bp.f.lse = varlen_stat(l.f.lse, b, h, l.f.H, l.f.Sq, q0, q1 - q0);
+    bp.delta = varlen_stat(l.delta, b, h, l.f.H, l.f.Sq, q0, q1 - q0);
+}
+
 // ---------------------------------------------------------------------------------------------
 // delta[b,h,i] = sum_d O[i][d] * dO[i][d]      (D/8 lanes per row, 16-byte loads)
 template <typename Tag, int D>
@@ -159,7 +190,8 @@ struct TileDma {
 constexpr int dq_seed(int D) { return D == 64 ? 3 : 2; }   // DQ_SEED of the shipped instantiations (bit 0 = S, bit 1 = dP seeded; measurements: LABNOTES.md)
 // BF32 (round 5): fp32 bias image next to 16-bit q / k / v, as in the forward (fasn_fwd_kernel.h)
 template <typename Tag, int D, int QB, int MODE, int OCC, int DROP = 0, int DQ_SEED = dq_seed(D), int BF32 = 0>
-__global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams bp) {
+__global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams FASN_KERNARG(bp)) {
+    FASN_ITEM_PARAMS(BwdParams, bp)
     static_assert(!BF32 || mode_has_vbias(MODE), "fp32 bias image: the vector bias modes");
     constexpr int IMGB = BF32 ? 8192 : 4096, IMGM = mode_has_vmask(MODE) ? 2048 : 0, BPC = BF32 ? 16 : 8, BW = BF32 ? 16 : 8;   // (fasn_fwd_kernel.h)
     using E = ET<Tag>;
@@ -197,6 +229,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams b
     const int qblk = causal ? (pass == 0 ? bp.nblk - 1 - qi : qi) : qi;
     const int b = bh / p.H, h = bh % p.H;
     const int q0 = qblk * BM;
+    FASN_ITEM_ENTER_DQ(D, b, h, q0)
     const int qw0 = q0 + wave * (QB * 32);
     const int coff = p.Sk - p.Sq;
 
@@ -628,7 +661,8 @@ constexpr int QT = 64;  // query rows per tile
 // (bias, or -inf where the mask byte is clear), moved in 16-byte pieces (4 keys), and a lane reads the 16 rows of ITS key column with plain
 // ds_read_b32 (consecutive lanes, consecutive dwords: no bank conflict) instead of the 16-bit transposing read
 template <typename Tag, int D, int KB, int MODE, int OCC, int DROP = 0, int GQA = 0, int DH = 1, int BF32 = 0>
-__global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams bp) {
+__global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams FASN_KERNARG(bp)) {
+    FASN_ITEM_PARAMS(BwdParams, bp)
     static_assert(!BF32 || mode_has_vbias(MODE), "fp32 additive tile: the vector bias modes");
     using E = ET<Tag>;
     using vec8 = typename E::vec8;
@@ -669,6 +703,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
     const int kblk = pass == 0 ? kblk0 : bp.nblk - 1 - kblk0;
     const bool causal = (MODE == MODE_CAUSAL) || (MODE >= MODE_GENERAL && p.causal);
     const int b = bhk / Hkv, hk = bhk % Hkv;
+    FASN_ITEM_ENTER_DKDV(D, b, kblk * BN)
     const int kw0 = kblk * BN + wave * (KB * 32);  // first key of this wave
     const int coff = p.Sk - p.Sq;
 
@@ -685,6 +720,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
 
     for (int g = 0; g < kvg; ++g) {   // the query heads of this K/V head (one trip without grouping)
     const int h = hk * kvg + g, bh = b * p.H + h;
+    FASN_ITEM_HEAD(b, h)
     const char* qbase = p.q + (b * p.qs[0] + h * p.qs[1]) * 2;
     const char* kbase = p.k + (b * p.ks[0] + (h / p.kvg) * p.ks[1]) * 2;
     const char* vbase = p.v + (b * p.vs[0] + (h / p.kvg) * p.vs[1]) * 2;

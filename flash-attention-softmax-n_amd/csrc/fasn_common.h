@@ -86,6 +86,50 @@ struct ET<f16_tag> {
     }
 };
 
+// Packed variable-length calls (fasn_attnvarlen.hip). Their kernels are the text of the rectangular kernels, compiled ONCE
+// more in that translation unit alone, which defines FASN_VARLEN_ITEMS in front of the kernel headers: there the kernel argument is the
+// LAUNCH's parameter block, `p` / `bp` a local copy of it (FASN_ITEM_PARAMS), and the FASN_ITEM_* hooks in the kernel text patch the copy
+// to the work item's sequence (offsets and lengths from device memory: varlen_enter_* in the kernel headers). In every other translation
+// unit the macros expand to the plain parameter name and to nothing, so the rectangular kernels are compiled from the token stream they
+// always had. The packed kernels are instantiated on element tags of their own, which gives them names of their own and nothing else: the
+// arithmetic is the base tag's.
+struct bf16_varlen_tag {};
+struct f16_varlen_tag {};
+template <>
+struct ET<bf16_varlen_tag> : ET<bf16_tag> {};
+template <>
+struct ET<f16_varlen_tag> : ET<f16_tag> {};
+template <typename Tag>
+struct TagVarlen { static constexpr bool value = false; };
+template <>
+struct TagVarlen<bf16_varlen_tag> { static constexpr bool value = true; };
+template <>
+struct TagVarlen<f16_varlen_tag> { static constexpr bool value = true; };
+#ifdef FASN_VARLEN_ITEMS
+#define FASN_KERNARG(p) p##_launch
+#define FASN_ITEM_PARAMS(T, p)                                                                                          \
+    static_assert(TagVarlen<Tag>::value, "this translation unit compiles the packed variable-length kernels only");     \
+    T p = p##_launch;
+#define FASN_ITEM_ENTER_FWD(D, b, h, row0)   /* forward: the item's sequence; a block beyond it leaves (no barrier yet) */ \
+    varlen_enter_fwd<D>(p_launch, p, b, h);                                                                             \
+    if ((row0) >= p.Sq) return;
+#define FASN_ITEM_ENTER_DQ(D, b, h, row0)                                                                               \
+    varlen_enter_bwd<D>(bp_launch, bp, b);                                                                              \
+    varlen_head_bwd(bp_launch, bp, b, h);                                                                               \
+    if ((row0) >= bp.f.Sq) return;
+#define FASN_ITEM_ENTER_DKDV(D, b, key0)                                                                                \
+    varlen_enter_bwd<D>(bp_launch, bp, b);                                                                              \
+    if ((key0) >= bp.f.Sk) return;
+#define FASN_ITEM_HEAD(b, h) varlen_head_bwd(bp_launch, bp, b, h);   /* lse / delta rows of one query head */
+#else
+#define FASN_KERNARG(p) p
+#define FASN_ITEM_PARAMS(T, p)
+#define FASN_ITEM_ENTER_FWD(D, b, h, row0)
+#define FASN_ITEM_ENTER_DQ(D, b, h, row0)
+#define FASN_ITEM_ENTER_DKDV(D, b, key0)
+#define FASN_ITEM_HEAD(b, h)
+#endif
+
 // ---- LDS tile image -------------------------------------------------------------------------
 // A tile is [rows][D] 16-bit elements, row-major, with the 16-byte chunks of each row XOR-permuted
 // so that BOTH access patterns below are bank-conflict free (bank = (addr/4) mod 64):

@@ -87,6 +87,45 @@ FASN_DEV float item_n(const FwdParams& p, int b, int h) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, p.nt[i])));
 }
 
+// ---- packed variable-length work items (kernels instantiated on a *_varlen_tag; fasn_attnvarlen.hip) ----
+// The launch parameters describe the packed operands: B = number of sequences, Sq / Sk = token rows of the query / key side, batch strides
+// 0, row stride = token stride, lse [H, Sq]. The two device offset tables ride in the split-K pointers, which these instantiations never
+// read otherwise (no struct member is added: the kernel arguments of every other instantiation stay where they are).
+FASN_DEV const int* varlen_cu_q(const FwdParams& p) { return reinterpret_cast<const int*>(p.part_o); }
+FASN_DEV const int* varlen_cu_k(const FwdParams& p) { return reinterpret_cast<const int*>(p.part_ml); }
+// token range [t0, t1) of sequence b, wave-uniform (two scalar loads), clamped into the `rows` of the operand: offsets that break the
+// caller's contract (decreasing, beyond the buffer) shorten a sequence, they never move an access outside the operands
+FASN_DEV void varlen_range(const int* cu, int b, int rows, int& t0, int& t1) {
+    const int a = __builtin_amdgcn_readfirstlane(cu[b]), e = __builtin_amdgcn_readfirstlane(cu[b + 1]);
+    t0 = min(max(a, 0), rows);
+    t1 = min(max(e, t0), rows);
+}
+// byte extent of `rows` rows of D 16-bit features, `stride` elements apart: the range of the item's buffer descriptor - rows of the next
+// sequence lie behind it and read back as zeros, as rows beyond Sk do in a rectangular call
+FASN_DEV unsigned varlen_bytes(int rows, int64_t stride, int D) { return rows > 0 ? (unsigned)(((int64_t)(rows - 1) * stride + D) * 2) : 0u; }
+// the [H, T] statistics row of head h, addressed as the kernels do ([b * H + h][len] + row) for an item of `len` rows that starts at token t0
+template <typename T>
+FASN_DEV T* varlen_stat(T* base, int b, int h, int H, int T_rows, int t0, int len) {
+    return base == nullptr ? nullptr : base + ((int64_t)h * T_rows + t0 - (int64_t)(b * H + h) * len);
+}
+// the launch's block `l` patched into `p` for the item (sequence b, head h): base pointers, lengths, descriptor ranges, lse base - the
+// rest of the kernel text reads `p` as it always did (FASN_ITEM_ENTER_FWD, fasn_common.h)
+template <int D>
+FASN_DEV void varlen_enter_fwd(const FwdParams& l, FwdParams& p, int b, int h) {
+    int q0, q1, k0, k1;
+    varlen_range(varlen_cu_q(l), b, l.Sq, q0, q1);
+    varlen_range(varlen_cu_k(l), b, l.Sk, k0, k1);
+    p.Sq = q1 - q0;
+    p.Sk = k1 - k0;
+    p.q = l.q + (int64_t)q0 * l.qs[2] * 2;
+    p.o = l.o + (int64_t)q0 * l.os[2] * 2;
+    p.k = l.k + (int64_t)k0 * l.ks[2] * 2;
+    p.v = l.v + (int64_t)k0 * l.vs[2] * 2;
+    p.kbytes = varlen_bytes(p.Sk, l.ks[2], D);
+    p.vbytes = varlen_bytes(p.Sk, l.vs[2], D);
+    p.lse = varlen_stat(l.lse, b, h, l.H, l.Sq, q0, p.Sq);
+}
+
 constexpr int KT = 64;  // keys per tile
 // key-padding modes: visibility words (one per K/V tile) kept in LDS by the forward kernels: 4 KiB, Sk <= 32768. Longer key
 // sequences take the dense-mask general mode of the same mask (fasn_api.hip).
@@ -208,7 +247,8 @@ constexpr int kXqSurplus = 16;   // surplus workgroups per XCD of such a launch 
 // like a D = 128 tile), moved by the same coalesced 16-byte LDS-DMA pieces, read 64 bytes per 32-key block and lane, and the start value of a
 // score is one fma on the fp32 value - no 16-bit unpack. Round 4 sent these calls through the element-load kernels (3-5 x slower).
 template <typename Tag, int D, int QB, int MODE, int OCC, int NW = 4, int PRIO = 0, int DROP = 0, int RING = 0, int SPLIT = 0, int SEED = 0, int VH = 1, int FOLD = 0, int BF32 = 0>
-__global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams p) {
+__global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams FASN_KERNARG(p)) {
+    FASN_ITEM_PARAMS(FwdParams, p)
     static_assert(!BF32 || (mode_has_vbias(MODE) && !SPLIT), "fp32 bias image: the vector bias modes");
     static_assert(!FOLD || (MODE == MODE_CAUSAL && QB == 2 && RING == 2 && !SPLIT && !DROP && VH == 1 && D <= 64), "folded two-phase walk: the causal 64-rows-per-wave kernel");
     static_assert(!SEED || MODE != MODE_GENERAL_SLOW, "seeded accumulators: not for the element-load kernels");
@@ -346,6 +386,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
     const int qblk = (MODE != MODE_PLAIN && p.causal) ? (pass == 0 ? p.nqblk - 1 - qi : qi) : qi;
     const int b = bh / p.H, h = bh % p.H;
     const int q0 = qblk * BM;
+    FASN_ITEM_ENTER_FWD(D, b, h, q0)
     const int qw0 = q0 + wave * (QB * 32);  // first row of this wave
     // first row of the wave's 32-row block qb: contiguous, or (FOLD) block `wave` and block `2 NW - 1 - wave` of the workgroup's 2 NW blocks
     auto rowb = [&](int qb) { return FOLD ? q0 + (qb == 0 ? wave : 2 * NW - 1 - wave) * 32 : qw0 + qb * 32; };

@@ -656,3 +656,196 @@ def slow_attention_n(query: Tensor, key: Tensor, value: Tensor, attn_mask: Optio
     p = dropout_p if train else 0.0
     out = _attention(query, key, value, softmax_n_param, scale, p, mask, bias, is_causal)
     return out.squeeze(1) if squeeze else out
+
+
+# ---- packed variable-length training attention (include/fasn.h: fasn_fwd_varlen / fasn_bwd_varlen) -----------------
+_VARLEN_D = (64,)   # the head dims fasn_fwd_varlen serves in this build (any other: FASN_EUNSUPPORTED)
+
+
+def _view_packed(t: Tensor) -> View4:
+    """a packed [T, heads, E] operand as the [1, heads, T, E] view of the C ABI: stride[1] between heads, stride[2] between tokens"""
+    v = View4()
+    v.ptr = t.data_ptr()
+    v.stride[0], v.stride[1], v.stride[2], v.stride[3] = 0, t.stride(1), t.stride(0), 1
+    return v
+
+
+def _packed_ok(t: Tensor) -> bool:
+    return t.stride(2) == 1 and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
+
+
+def _varlen_block(cu_q, cu_k, max_q, max_k):
+    vl = _lib.Varlen()
+    vl.cu_seqlens_q, vl.cu_seqlens_k = cu_q.data_ptr(), cu_k.data_ptr()
+    vl.num_seqs, vl.max_seqlen_q, vl.max_seqlen_k, vl.reserved = cu_q.numel() - 1, max_q, max_k, 0
+    return vl
+
+
+def _fill_fwd_varlen(a: FwdArgs, q, k, v, o, lse, n, scale, causal):
+    a.q, a.k, a.v, a.o = _view_packed(q), _view_packed(k), _view_packed(v), _view_packed(o)
+    a.lse = lse.data_ptr()
+    a.mask.ptr = a.bias.ptr = None
+    a.bias_dtype = _lib.FASN_BIAS_NONE
+    a.dtype = _DTYPES[q.dtype]
+    a.B, a.H, a.Sq, a.Sk, a.D, a.Dv = 1, q.shape[1], q.shape[0], k.shape[0], q.shape[2], v.shape[2]
+    a.kv_group = q.shape[1] // k.shape[1] if k.shape[1] != q.shape[1] else 0
+    a.scale, a.softmax_n, a.causal, a.dropout_p = scale, n, 1 if causal else 0, 0.0
+    a.seed = a.offset = 0
+    a.rng_state = None
+
+
+def _launch_fwd_varlen(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, causal):
+    """out [Tq, H, E] and lse [H, Tq]: every row is written by the call (rows at or beyond cu_q[B]: 0 / -inf, by its tail kernel)"""
+    lib = _lib.load()
+    dev = q.device
+    o = torch.empty((q.shape[0], q.shape[1], q.shape[2]), dtype=q.dtype, device=dev)
+    lse = torch.empty((q.shape[1], q.shape[0]), dtype=torch.float32, device=dev)
+    a = FwdArgs()
+    tensor_n = isinstance(n, Tensor)
+    _fill_fwd_varlen(a, q, k, v, o, lse, 0.0 if tensor_n else n, scale, causal)
+    vl = _varlen_block(cu_q, cu_k, max_q, max_k)
+    with torch.cuda.device(dev):
+        rc = lib.fasn_fwd_varlen(a, vl, n.data_ptr() if tensor_n else None, (n.stride(1) if n.shape[1] > 1 else 0) if tensor_n else 0, _stream_ptr(dev))
+    if rc:
+        _lib.check(rc, "fasn_fwd_varlen")
+    return o, lse
+
+
+class _FlashAttentionSoftmaxNVarlen(torch.autograd.Function):
+    """autograd glue of flash_attention_n_varlen, beside _FlashAttentionSoftmaxN: dq / dk / dv through fasn_bwd_varlen, the gradient of a
+    tensor n through fasn_bwd_dn on the [1, H, Tq] view of out, lse and dout (rows behind the last sequence are 0 / -inf: no term)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q: int, max_k: int, n, scale: float, causal: bool):
+        o, lse = _launch_fwd_varlen(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, causal)
+        ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
+        ctx.n_shape = tuple(n.shape) if isinstance(n, Tensor) else None
+        ctx.n = 0.0 if isinstance(n, Tensor) else n
+        ctx.max_q, ctx.max_k, ctx.scale, ctx.causal = max_q, max_k, scale, causal
+        ctx.mark_non_differentiable(lse)
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, dout, _dlse):
+        lib = _lib.load()
+        q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
+        dev = q.device
+        if not _packed_ok(dout):
+            dout = dout.contiguous()
+            if dout.data_ptr() % 16:
+                dout = dout.clone()
+        dq = torch.empty(q.shape, dtype=q.dtype, device=dev)
+        dk = torch.empty(k.shape, dtype=q.dtype, device=dev)
+        dv = torch.empty(v.shape, dtype=q.dtype, device=dev)
+        delta = torch.empty(lse.shape, dtype=torch.float32, device=dev)
+        a = BwdArgs()
+        _fill_fwd_varlen(a.fwd, q, k, v, o, lse, ctx.n, ctx.scale, ctx.causal)
+        a.dout, a.dq, a.dk, a.dv = _view_packed(dout), _view_packed(dq), _view_packed(dk), _view_packed(dv)
+        a.delta = delta.data_ptr()
+        a.workspace, a.workspace_bytes, a.flags, a.dbias_dtype = None, 0, 0, 0
+        a.dbias.ptr = None
+        vl = _varlen_block(cu_q, cu_k, ctx.max_q, ctx.max_k)
+        dn = None
+        with torch.cuda.device(dev):
+            rc = lib.fasn_bwd_varlen(a, vl, _stream_ptr(dev))
+            if rc:
+                _lib.check(rc, "fasn_bwd_varlen")
+            if ctx.n_shape is not None and ctx.needs_input_grad[7]:
+                # dL/dn_h = -sum_t delta_t exp(-lse_t): the rectangular call's kernel on B = 1, Sq = Tq (views [1, H, Tq, E] as filled above)
+                dn = torch.empty(ctx.n_shape, dtype=torch.float32, device=dev)
+                a.fwd.softmax_n = 0.0
+                ws_bytes = lib.fasn_bwd_dn_workspace_bytes(a)
+                ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+                _lib.check(lib.fasn_bwd_dn(a, dn.data_ptr(), 0, dn.stride(1) if dn.shape[1] > 1 else 0, ws.data_ptr(), ws_bytes, _stream_ptr(dev)),
+                           "fasn_bwd_dn")
+        return dq, dk, dv, None, None, None, None, dn, None, None
+
+
+def _n_tensor_varlen(n: Tensor, query: Tensor) -> Tensor:
+    """softmax_n as a tensor for the packed call: one n per query head ([H], [1, H] or 0-d), read as the fp32 [1, 1 or H] view"""
+    H = query.shape[1]
+    if not n.is_floating_point():
+        raise TypeError(f"softmax_n_param as a tensor must be floating point; got {n.dtype}")
+    if n.device != query.device:
+        raise ValueError(f"softmax_n_param is on {n.device}, query on {query.device}: pass n on the query's device")
+    shape = tuple(n.shape)
+    if not (n.dim() == 0 or (n.dim() == 1 and shape[0] in (1, H)) or (n.dim() == 2 and shape[0] == 1 and shape[1] in (1, H))):
+        raise ValueError(f"softmax_n_param must broadcast to [H] = [{H}] (0-d, [H] or [1, H]); got {shape}: a per-sequence n is not built "
+                         "(the kernels read one n per head)")
+    return n.float().reshape((1,) * (2 - n.dim()) + shape)
+
+
+def flash_attention_n_varlen(query: Tensor, key: Tensor, value: Tensor, cu_seqlens_q: Tensor, max_seqlen_q: int,
+                             cu_seqlens_k: Optional[Tensor] = None, max_seqlen_k: Optional[int] = None, softmax_n_param=1, scale: Optional[float] = None,
+                             is_causal: bool = False, return_lse: bool = False):
+    """flash_attention_n on packed variable-length sequences, forward and backward (flash_attn_varlen_func for softmax_n): sequence b is
+    flash_attention_n on query[cu_q[b]:cu_q[b+1]] against key, value[cu_k[b]:cu_k[b+1]]; nothing is padded and nothing is read on the host.
+
+    :param query: [Tq, H, E] fp16 / bf16 device tensor; E = 64 in this build. Any token and head strides with unit feature stride and 16-byte
+                  aligned rows (slices of one packed [T, H + 2 Hkv, E] buffer go in without a copy; anything else is copied).
+    :param key, value: [Tk, Hkv, E], H % Hkv == 0 (grouped-query attention).
+    :param cu_seqlens_q, cu_seqlens_k: int32 [B + 1] on the query's device: cu[0] = 0, non-decreasing, cu[B] <= T. cu_seqlens_k = None: the same
+                  tensor as cu_seqlens_q (self-attention). Sequences of length 0 on either side are legal.
+    :param max_seqlen_q, max_seqlen_k: Python ints that bound every length (the grid's size); max_seqlen_k = None: max_seqlen_q. Rows of a longer
+                  sequence beyond the bound are not computed (the caller's error; no access leaves the operands).
+    :param softmax_n_param: a float >= 0, or a floating tensor on the query's device that broadcasts to [H] (0-d, [H], [1, H]), differentiated
+                  when it requires grad. A tensor filled with c gives the float c's results bit for bit. A per-sequence n is refused.
+    :param is_causal: bottom-right aligned per sequence: key j visible to row i iff j <= i + (sk_b - sq_b).
+    :return: out [Tq, H, E]; with return_lse also lse, fp32 [H, Tq]. Rows at or beyond cu_q[B] are 0 with lse -inf, their dq rows and the
+             dk / dv rows at or beyond cu_k[B] exactly 0. A row that sees no key is 0 with lse log n (-inf at n = 0), its gradients 0.
+    Capturable: one captured graph serves any contents of the cu_seqlens tensors with the same B, T and max_seqlen.
+    There is no attn_mask, attn_bias or dropout_p on packed operands."""
+    if not isinstance(query, Tensor) or not query.is_cuda:
+        raise RuntimeError("flash_attention_n_varlen runs on MI355X device tensors only; got a CPU tensor (there is deliberately no CPU fallback)")
+    if query.dtype not in (torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"flash_attention_n_varlen: dtype {query.dtype} is not served; packed operands are torch.float16 or torch.bfloat16")
+    if key.dtype != query.dtype or value.dtype != query.dtype:
+        raise TypeError("query, key and value must share one dtype")
+    if query.dim() != 3 or key.dim() != 3 or value.dim() != 3:
+        raise ValueError("packed operands: query must be [Tq, H, E], key and value [Tk, Hkv, E]")
+    if key.device != query.device or value.device != query.device:
+        raise ValueError("query, key and value must be on one device")
+    Tq, H, E = query.shape
+    Tk, Hkv, Ek = key.shape
+    if Ek != E or value.shape[0] != Tk or value.shape[1] != Hkv:
+        raise ValueError("key must be [Tk, Hkv, E] and value [Tk, Hkv, Ev]")
+    if value.shape[2] != E:
+        raise NotImplementedError(f"flash_attention_n_varlen: E != Ev ({E} != {value.shape[2]}) is not served on packed operands")
+    if E not in _VARLEN_D:
+        raise NotImplementedError(f"flash_attention_n_varlen: head dim {E} is not served on packed operands; head dims served: {list(_VARLEN_D)} "
+                                  "(no feature padding here)")
+    if Hkv < 1 or H % Hkv != 0:
+        raise ValueError(f"key / value have {Hkv} heads: must divide the {H} query heads (grouped-query attention)")
+    if Tq < 1 or Tk < 1:
+        raise ValueError("packed operands must hold at least one token row per side")
+    cu_k = cu_seqlens_q if cu_seqlens_k is None else cu_seqlens_k
+    for name, cu in (("cu_seqlens_q", cu_seqlens_q), ("cu_seqlens_k", cu_k)):
+        if not isinstance(cu, Tensor) or cu.dtype != torch.int32:
+            raise TypeError(f"{name} must be an int32 tensor [B + 1]; got {getattr(cu, 'dtype', type(cu))}")
+        if cu.device != query.device:
+            raise ValueError(f"{name} is on {cu.device}, query on {query.device}: the offsets are read on the device")
+        if cu.dim() != 1 or cu.numel() < 2 or not cu.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous [B + 1] tensor with B >= 1")
+    if cu_k.numel() != cu_seqlens_q.numel():
+        raise ValueError("cu_seqlens_q and cu_seqlens_k must describe the same number of sequences")
+    max_q = int(max_seqlen_q)
+    max_k = max_q if max_seqlen_k is None else int(max_seqlen_k)
+    if max_q < 1 or max_k < 1:
+        raise ValueError("max_seqlen_q and max_seqlen_k must be >= 1")
+    if isinstance(softmax_n_param, Tensor):
+        n = _n_tensor_varlen(softmax_n_param, query)
+    else:
+        n = 0.0 if softmax_n_param is None else float(softmax_n_param)
+        if n < 0:
+            raise ValueError("softmax_n_param must be >= 0")
+    scale = (1.0 / sqrt(E)) if scale is None else float(scale)
+    if scale < 0:
+        query, scale = -query, -scale
+    q, k, v = (t if _packed_ok(t) else t.contiguous() for t in (query, key, value))
+    q, k, v = (t.clone() if t.data_ptr() % 16 else t for t in (q, k, v))
+    needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (isinstance(n, Tensor) and n.requires_grad))
+    if needs_grad:
+        out, lse = _FlashAttentionSoftmaxNVarlen.apply(q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale, bool(is_causal))
+    else:   # nothing to differentiate: no autograd node
+        out, lse = _launch_fwd_varlen(q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale, bool(is_causal))
+    return (out, lse) if return_lse else out

@@ -804,6 +804,50 @@ int fasn_softmax_n_plan(int32_t which, const void* a, const void* b, const void*
 int fasn_moments_plan(const void* x, const double* sums, int64_t rows, int64_t cols, int64_t row_stride, int32_t dtype, char* buf,
                       size_t cap);
 
+/*
+ * PACKED VARIABLE-LENGTH TRAINING ATTENTION (flash_attn_varlen_func for softmax_n; additions within ABI 6, the argument blocks above keep
+ * their layouts): the sequences of a batch lie behind each other in one token buffer per side, and two tables of B + 1 int32 offsets in
+ * DEVICE memory - cu[0] = 0, non-decreasing, cu[B] <= rows of the side - say where each sequence starts. Sequence b is fasn_fwd / fasn_bwd
+ * on q[cu_q[b] : cu_q[b + 1]] against k, v[cu_k[b] : cu_k[b + 1]]: causal is bottom-right aligned per sequence (j <= i + sk_b - sq_b), a
+ * row that sees no key gives 0 with lse = log n (-inf at n = 0) and zero gradients, a sequence may be empty on either side.
+ *
+ *   args      the forward / backward block describes the PACKED operands: B = 1, Sq / Sk = the token rows of the query / key side, every
+ *             view [1, heads, rows, D] with stride[1] between heads, stride[2] between tokens, stride[0] unused; lse and delta
+ *             [H, Sq] fp32 (lse must be given); kv_group as in fasn_fwd (dk / dv have H / kv_group heads, summed inside the kernel).
+ *             dtype fp16 / bf16, D == Dv == 64. mask, bias and dbias NULL, dropout_p 0.
+ *   varlen    cu_seqlens_q / cu_seqlens_k (the same pointer for self-attention), num_seqs = B >= 1, and max_seqlen_q / max_seqlen_k >= 1:
+ *             host bounds of every length, constants of a captured graph. The grids are functions of num_seqs, max_seqlen_*, the heads
+ *             and the rows alone; nothing is read on the host. A sequence longer than its bound is the caller's error: its rows beyond the
+ *             bound are not computed. Whatever the tables hold, no kernel touches memory outside the operands: offsets are clamped to
+ *             [0, rows] and made non-decreasing.
+ *   n         NULL: args->softmax_n. Else a DEVICE fp32 value per query head, head h at n[h * n_stride_h] (stride 0: one value); an entry
+ *             that is not > 0 acts as 0. Its gradient: fasn_bwd_dn on the [1, H, Sq] view of o, lse and dout.
+ *   tail      rows at or beyond cu_q[B] come back as o = 0, lse = -inf, dq = 0; dk / dv rows at or beyond cu_k[B] as 0 (a small kernel of
+ *             its own writes them); no byte between the rows of a strided view is written.
+ *
+ * fasn_fwd_varlen launches the tail kernel and the forward on num_seqs * H * ceil(max_seqlen_q / 128) workgroups; fasn_bwd_varlen the tail
+ * kernel, the dQ kernel on the same grid (it publishes delta) and the dK/dV kernel on num_seqs * (H / kv_group) * ceil(max_seqlen_k / 128)
+ * workgroups: deterministic, no atomics, no workspace. A workgroup reads its sequence's two offset pairs once and leaves at once when its
+ * block lies beyond the sequence. fasn_varlen_plan writes the launches of the forward (FASN_PLAN_FWD) or the backward (FASN_PLAN_BWD) as
+ * text, in the line format of fasn_launch_plan, with no HIP call.
+ * Codes, checked in this order before any HIP call: a NULL block, NULL offsets, sizes < 1, B != 1, a bad enum, kv_group that does not
+ * divide H, n_stride_h < 0 FASN_EINVAL; D != Dv FASN_EHEADDIM; fp32, a head dim other than 64, a mask, a bias, dropout or dbias
+ * FASN_EUNSUPPORTED; then the views (FASN_EINVAL / FASN_ESTRIDE / FASN_EALIGN as in fasn_fwd, a side of 2^31 bytes or more FASN_EINVAL),
+ * offsets or n off 4 bytes FASN_EALIGN.
+ */
+typedef struct fasn_varlen {
+    const int32_t* cu_seqlens_q; /* DEVICE [num_seqs + 1] token offsets of the query side */
+    const int32_t* cu_seqlens_k; /* DEVICE [num_seqs + 1] token offsets of the key / value side */
+    int32_t num_seqs;
+    int32_t max_seqlen_q;
+    int32_t max_seqlen_k;
+    int32_t reserved;            /* 0 */
+} fasn_varlen;
+
+int fasn_fwd_varlen(const fasn_fwd_args* args, const fasn_varlen* varlen, const float* n, int64_t n_stride_h, fasn_stream_t stream);
+int fasn_bwd_varlen(const fasn_bwd_args* args, const fasn_varlen* varlen, fasn_stream_t stream);
+int fasn_varlen_plan(const fasn_bwd_args* args, const fasn_varlen* varlen, int32_t which, char* buf, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
