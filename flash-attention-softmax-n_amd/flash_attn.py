@@ -660,6 +660,8 @@ def slow_attention_n(query: Tensor, key: Tensor, value: Tensor, attn_mask: Optio
 
 # ---- packed variable-length training attention (include/fasn.h: fasn_fwd_varlen / fasn_bwd_varlen) -----------------
 _VARLEN_D = (64,)   # the head dims fasn_fwd_varlen serves in this build (any other: FASN_EUNSUPPORTED)
+_VARLEN_LOG2E = 1.4426950408889634
+_VARLEN_F16_MAX_PRESCALE = 8.0   # float16: |scale * log2e| beyond this is FASN_EUNSUPPORTED (build_varlen, csrc/fasn_attnvarlen.hip)
 
 
 def _view_packed(t: Tensor) -> View4:
@@ -790,6 +792,8 @@ def flash_attention_n_varlen(query: Tensor, key: Tensor, value: Tensor, cu_seqle
                   sequence beyond the bound are not computed (the caller's error; no access leaves the operands).
     :param softmax_n_param: a float >= 0, or a floating tensor on the query's device that broadcasts to [H] (0-d, [H], [1, H]), differentiated
                   when it requires grad. A tensor filled with c gives the float c's results bit for bit. A per-sequence n is refused.
+    :param scale: the logits are scale * q . k; default 1 / sqrt(E). A negative scale negates the query. float16 serves |scale| * log2(e) <= 8
+                  (NotImplementedError beyond it).
     :param is_causal: bottom-right aligned per sequence: key j visible to row i iff j <= i + (sk_b - sq_b).
     :return: out [Tq, H, E]; with return_lse also lse, fp32 [H, Tq]. Rows at or beyond cu_q[B] are 0 with lse -inf, their dq rows and the
              dk / dv rows at or beyond cu_k[B] exactly 0. A row that sees no key is 0 with lse log n (-inf at n = 0), its gradients 0.
@@ -841,6 +845,11 @@ def flash_attention_n_varlen(query: Tensor, key: Tensor, value: Tensor, cu_seqle
     scale = (1.0 / sqrt(E)) if scale is None else float(scale)
     if scale < 0:
         query, scale = -query, -scale
+    # (in fp32, as build_varlen forms it: a scale within a rounding of the limit gets the same answer here and there)
+    if query.dtype == torch.float16 and float(torch.tensor(scale, dtype=torch.float32) * torch.tensor(_VARLEN_LOG2E, dtype=torch.float32)) > _VARLEN_F16_MAX_PRESCALE:
+        raise NotImplementedError(f"flash_attention_n_varlen: float16 with |scale| = {scale:g} is not served on packed operands: the kernels round "
+                                  f"query * scale * log2(e) to float16 and serve |scale| * log2(e) <= {_VARLEN_F16_MAX_PRESCALE:g}, that is |scale| <= "
+                                  f"{_VARLEN_F16_MAX_PRESCALE / _VARLEN_LOG2E:.4f}; use bfloat16 or fold the scale into the query")
     q, k, v = (t if _packed_ok(t) else t.contiguous() for t in (query, key, value))
     q, k, v = (t.clone() if t.data_ptr() % 16 else t for t in (q, k, v))
     needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (isinstance(n, Tensor) and n.requires_grad))

@@ -115,7 +115,7 @@ class Case:
     want: properties of the launch plans this case is named for (tests/test_attnwitness_cpu.py asserts them)."""
 
     def __init__(self, B, H, L, S, D, Hkv=None, causal=False, mask=None, bias=None, p=0.0, lens=None, nshape="H", ub=None, uh=None,
-                 dtypes=("fp16", "bf16"), bwd=True, want=(), wit="ABC", a_dtypes=None, hide_from=None):
+                 dtypes=("fp16", "bf16"), bwd=True, want=(), wit="ABC", a_dtypes=None, hide_from=None, n_pos=None):
         self.B, self.H, self.L, self.S, self.D, self.Hkv = B, H, L, S, D, Hkv or H
         self.G = H // self.Hkv
         self.causal, self.mask, self.bias, self.p, self.nshape = causal, mask, bias, p, nshape
@@ -124,6 +124,7 @@ class Case:
         self.uh = uh or H
         self.dtypes, self.bwd, self.want, self.wit = tuple(dtypes), bwd, tuple(want), wit
         self.hide_from = hide_from   # a dense mask hides every key from this one on
+        self.n_pos = n_pos           # the n > 0 of a caller that hands its own n to inputs_* (tests/attn_varlen_witness.py: one n for a whole pack); pow2_n answers from it
         self.a_dtypes = tuple(a_dtypes) if a_dtypes is not None else self.dtypes
         assert H % self.Hkv == 0 and self.uh % self.G == 0 and H % self.uh == 0 and B % self.ub == 0
         assert (mask == "keypad") == (lens is not None) and (lens is None or len(lens) == self.ub)
@@ -276,9 +277,13 @@ def _tile(case, t, heads="q"):
     return t[case.bidx.to(t.device)][:, hid.to(t.device)].contiguous()
 
 
-def n_values(case, dev, pos=None):
-    """(n as the call gets it, un [ub, uh] fp64 on the CPU). Zeros next to positive entries; `pos` replaces the positive value."""
+def n_values(case, dev, pos=None, given=None):
+    """(n as the call gets it, un [ub, uh] fp64 on the CPU). Zeros next to positive entries; `pos` replaces the positive value.
+    given: an [H] tensor handed in instead of drawn (a case with ub = 1, uh = H: the packed call's one n per head)"""
     ub, uh = case.ub, case.uh
+    if given is not None:
+        assert case.nshape == "H" and ub == 1 and uh == case.H and tuple(given.shape) == (case.H,)
+        return given.float().to(dev), given.detach().double().cpu().view(1, uh)
     if case.nshape == "float":
         val = 1.5 if pos is None else pos
         return val, torch.full((ub, uh), val, dtype=torch.float64)
@@ -358,11 +363,14 @@ def pow2_n(case):
     """the n > 0 that makes Z = n + S a power of two (non-causal, no mask: every row sees S keys), or None"""
     if case.causal or case.mask is not None or case.nshape == "float":
         return None
+    if case.n_pos is not None:   # a handed-in n: Z is a power of two only at the key lengths it was chosen for
+        z = case.n_pos + case.S
+        return float(case.n_pos) if z == 2.0 ** round(math.log2(z)) else None
     z = 1 << case.S.bit_length()
     return float(z - case.S)
 
 
-def inputs_a(case, dtype, dev, seed):
+def inputs_a(case, dtype, dev, seed, n=None):
     """query = 0. V[j, d] = 1 for d = j mod (D/2) and for d = D/2 + (j // granule) mod (D/2 - 1): the key's place within its half tile and
     its tile (bf16: half tile, as kv_witness.inputs_a). The last feature is the spare class: (hkv + 1) 2^-k for every key of K/V head hkv.
     K is the same indicator (the logits stay 0). dO[i] is the indicator of row i's class, the same in every head. A zero bias where the
@@ -377,7 +385,7 @@ def inputs_a(case, dtype, dev, seed):
         shift += 1
     v[:, :, :, D - 1] = ((torch.arange(Hkv, device=dev) % case.uhk + 1).float() * 2.0 ** -shift).view(1, Hkv, 1)
     do = _indicator(L, D, KT // 2, dev).view(1, 1, L, D).repeat(B, H, 1, 1)
-    n, un = n_values(case, dev, pos=pow2_n(case))
+    n, un = n_values(case, dev, pos=pow2_n(case), given=n)
     mask, um = masks(case, dev, seed)
     bias, ubias = _bias(case, "zero", dtype, dev, seed)
     return dict(q=q, k=k.to(dtype), v=v.to(dtype), do=do.to(dtype), n=n, un=un, mask=mask, um=um, bias=bias, ubias=ubias, scale=1.0 / math.sqrt(D))
@@ -396,7 +404,7 @@ def ladder_params(dtype, S):
     return 1.0, 4, 32.0
 
 
-def inputs_b(case, form, dtype, dev, seed):
+def inputs_b(case, form, dtype, dev, seed, n=None):
     """ascending / descending / sink: q_d = g 16^d for d < digits, k_jd = base-16 digit d of j (descending: 15 - digit), feature `digits`
     is g and 1; the MFMA sum is the integer g (j + 1), every operand exact, neighbouring logits scale g = 32 nats apart. sink: q negated.
     code / code_sink: k_jd = +-1 by bit d of j for 12 bits, q_i = g k_t(i) with t(i) the last visible key of row i (without causal: the last
@@ -441,12 +449,12 @@ def inputs_b(case, form, dtype, dev, seed):
     uv = torch.where(uv.abs() < 2.0 ** -12, torch.ones_like(uv), uv)   # (no zeros, and f V, f dO stay clear of fp16's gradual underflow, where 2 u |x| does not hold)
     udo = _counter_normal((case.ub, case.uh, L, D), seed + 2, 1.0, dtype, dev)
     udo = torch.where(udo.abs() < 2.0 ** -12, torch.ones_like(udo), udo)
-    n, un = n_values(case, dev)
+    n, un = n_values(case, dev, given=n)
     bias, ubias = _bias(case, "small", dtype, dev, seed + 3)
     return dict(q=q.to(dtype), k=k, v=_tile(case, uv, "kv"), do=_tile(case, udo), n=n, un=un, mask=mask, um=um, bias=bias, ubias=ubias, scale=scale)
 
 
-def inputs_c(case, std, dtype, dev, seed):
+def inputs_c(case, std, dtype, dev, seed, n=None):
     """q, k ~ N(0, 0.5^2), v, dO ~ N(0, 1) in the operand type; scale so that the logits have the standard deviation `std` (q.k has
     0.25 sqrt(D)); a bias ~ N(0, 1) where the case has one"""
     L, S, D = case.L, case.S, case.D
@@ -454,7 +462,7 @@ def inputs_c(case, std, dtype, dev, seed):
     uk = _counter_normal((case.ub, case.uhk, S, D), seed + 1, 0.5, dtype, dev)
     uv = _counter_normal((case.ub, case.uhk, S, D), seed + 2, 1.0, dtype, dev)
     udo = _counter_normal((case.ub, case.uh, L, D), seed + 3, 1.0, dtype, dev)
-    n, un = n_values(case, dev)
+    n, un = n_values(case, dev, given=n)
     mask, um = masks(case, dev, seed)
     bias, ubias = _bias(case, "random", dtype, dev, seed + 4)
     return dict(q=_tile(case, uq), k=_tile(case, uk, "kv"), v=_tile(case, uv, "kv"), do=_tile(case, udo), n=n, un=un, mask=mask, um=um,
