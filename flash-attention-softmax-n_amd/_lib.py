@@ -48,6 +48,7 @@ EXPORTS = (
     "fasn_kvprefill_fp8_tree_rope_append_plan", "fasn_kvcache_fp8_tree_commit",
     "fasn_kv_forward_workspace_bytes", "fasn_kv_forward", "fasn_kv_forward_plan", "fasn_kv_append", "fasn_kv_append_plan",
     "fasn_fwd_varlen", "fasn_bwd_varlen", "fasn_varlen_plan",
+    "fasn_fwd_varlen_window", "fasn_bwd_varlen_window", "fasn_varlen_window_plan",
 )
 
 
@@ -320,6 +321,12 @@ def load():
     lib.fasn_bwd_varlen.argtypes = [POINTER(BwdArgs), POINTER(Varlen), c_void_p]
     lib.fasn_varlen_plan.restype = c_int32
     lib.fasn_varlen_plan.argtypes = [POINTER(BwdArgs), POINTER(Varlen), c_int32, c_char_p, c_size_t]
+    lib.fasn_fwd_varlen_window.restype = c_int32
+    lib.fasn_fwd_varlen_window.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvWindow), c_void_p, c_int64, c_void_p]
+    lib.fasn_bwd_varlen_window.restype = c_int32
+    lib.fasn_bwd_varlen_window.argtypes = [POINTER(BwdArgs), POINTER(Varlen), POINTER(KvWindow), c_void_p]
+    lib.fasn_varlen_window_plan.restype = c_int32
+    lib.fasn_varlen_window_plan.argtypes = [POINTER(BwdArgs), POINTER(Varlen), POINTER(KvWindow), c_int32, c_char_p, c_size_t]
     for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -380,6 +387,12 @@ def varlen_plan(args, varlen, which):
     """The kernels fasn_fwd_varlen (FASN_PLAN_FWD) or fasn_bwd_varlen (FASN_PLAN_BWD) would launch for `args` (a BwdArgs that describes the
     packed operands) under `varlen` (a Varlen), as launch_plan returns them. Nothing is launched."""
     return _plan("fasn_varlen_plan", args, varlen, which)
+
+
+def varlen_window_plan(args, varlen, win, which):
+    """The kernels fasn_fwd_varlen_window (FASN_PLAN_FWD) or fasn_bwd_varlen_window (FASN_PLAN_BWD) would launch for `args` and `varlen`
+    under `win` (a KvWindow), as launch_plan returns them; varlen_plan's with a window >= max_seqlen_k. Nothing is launched."""
+    return _plan("fasn_varlen_window_plan", args, varlen, win, which)
 
 
 def kvcache_plan(args, alibi=None):

@@ -1,7 +1,9 @@
 // Packed variable-length training attention (include/fasn.h: fasn_fwd_varlen, fasn_bwd_varlen, fasn_varlen_plan): the
 // argument checks, the parameter blocks, the launches and the tail kernel. The forward, dQ and dK/dV kernels are instantiations of the
 // rectangular kernels' text on the *_varlen_tag element tags (fasn_common.h): a work item is (sequence, head, block) on a grid sized from
-// num_seqs and max_seqlen_*, and takes its offsets and lengths from the two tables in device memory.
+// num_seqs and max_seqlen_*, and takes its offsets and lengths from the two tables in device memory. The *_window entry points
+// (fasn_fwd_varlen_window, fasn_bwd_varlen_window, fasn_varlen_window_plan) launch the same kernels on the *_varlen_window_tag
+// tags, which walk only the tiles of a sliding window, on the same grids.
 #define FASN_VARLEN_ITEMS 1   // the kernel headers compile the packed variable-length form of their kernels here (fasn_common.h)
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -178,10 +180,23 @@ int launch_bwd_varlen(BwdParams p, int nqblk, int nkblk, hipStream_t s) {
     return launch_rc();
 }
 
-int fwd_varlen(const fasn_fwd_args* a, const fasn_varlen* vl, const float* n, int64_t n_stride_h, hipStream_t s) {
+// The window operand of the *_window entry points, checked behind every rule of the base call (the rule of the cache's *_window calls).
+// Returns the window the kernels walk under, 0 for none: with window >= max_seqlen_k no key of any sequence lies below a row's window, and
+// the call is the causal packed call - its launches, its plan text, its bits.
+int check_window(const fasn_fwd_args* a, const fasn_varlen* vl, const fasn_kv_window* win, int& window) {
+    if (win == nullptr || win->window < 1 || win->reserved != 0) return FASN_EINVAL;
+    if (!a->causal) return FASN_EUNSUPPORTED;
+    window = win->window >= vl->max_seqlen_k ? 0 : win->window;
+    return FASN_OK;
+}
+
+// windowed: the call came through a *_window entry point (win is its operand, checked here)
+int fwd_varlen(const fasn_fwd_args* a, const fasn_varlen* vl, const float* n, int64_t n_stride_h, bool windowed, const fasn_kv_window* win, hipStream_t s) {
     VarlenCall c;
     int rc = build_varlen(a, vl, n, n_stride_h, c);
     if (rc) return rc;
+    int window = 0;
+    if (windowed && (rc = check_window(a, vl, win, window))) return rc;
     VarlenTail t{};
     t.cu_q = vl->cu_seqlens_q;
     t.cu_k = vl->cu_seqlens_k;
@@ -196,12 +211,17 @@ int fwd_varlen(const fasn_fwd_args* a, const fasn_varlen* vl, const float* n, in
     t.qs_t = a->o.stride[2];
     t.lse = a->lse;
     if ((rc = launch_tail(t, s))) return rc;
+    if (window > 0) {   // (the window rides in tps: split-K is off in the packed instantiations, which never read it)
+        c.p.tps = window;
+        return c.dtype == FASN_DTYPE_BF16 ? launch_fwd_varlen<bf16_varlen_window_tag, MODE_CAUSAL>(c.p, c.nqblk, s)
+                                          : launch_fwd_varlen<f16_varlen_window_tag, MODE_CAUSAL>(c.p, c.nqblk, s);
+    }
     if (c.dtype == FASN_DTYPE_BF16)
         return c.mode == MODE_CAUSAL ? launch_fwd_varlen<bf16_varlen_tag, MODE_CAUSAL>(c.p, c.nqblk, s) : launch_fwd_varlen<bf16_varlen_tag, MODE_PLAIN>(c.p, c.nqblk, s);
     return c.mode == MODE_CAUSAL ? launch_fwd_varlen<f16_varlen_tag, MODE_CAUSAL>(c.p, c.nqblk, s) : launch_fwd_varlen<f16_varlen_tag, MODE_PLAIN>(c.p, c.nqblk, s);
 }
 
-int bwd_varlen(const fasn_bwd_args* a, const fasn_varlen* vl, hipStream_t s) {
+int bwd_varlen(const fasn_bwd_args* a, const fasn_varlen* vl, bool windowed, const fasn_kv_window* win, hipStream_t s) {
     if (a == nullptr) return FASN_EINVAL;
     fasn_fwd_args f = a->fwd;
     f.softmax_n = 0.f;   // (the backward reads n through lse alone)
@@ -215,6 +235,8 @@ int bwd_varlen(const fasn_bwd_args* a, const fasn_varlen* vl, hipStream_t s) {
     if ((rc = check_packed(a->dk, f.Sk, f.D))) return rc;
     if ((rc = check_packed(a->dv, f.Sk, f.D))) return rc;
     if (reinterpret_cast<uintptr_t>(a->delta) % 4) return FASN_EALIGN;
+    int window = 0;
+    if (windowed && (rc = check_window(&f, vl, win, window))) return rc;
     BwdParams p{};
     p.f = c.p;
     p.dout = (const char*)a->dout.ptr;
@@ -248,6 +270,11 @@ int bwd_varlen(const fasn_bwd_args* a, const fasn_varlen* vl, hipStream_t s) {
     t.ks_h[1] = a->dv.stride[1];
     t.ks_t[1] = a->dv.stride[2];
     if ((rc = launch_tail(t, s))) return rc;
+    if (window > 0) {
+        p.f.tps = window;
+        return c.dtype == FASN_DTYPE_BF16 ? launch_bwd_varlen<bf16_varlen_window_tag, MODE_CAUSAL>(p, c.nqblk, c.nkblk, s)
+                                          : launch_bwd_varlen<f16_varlen_window_tag, MODE_CAUSAL>(p, c.nqblk, c.nkblk, s);
+    }
     if (c.dtype == FASN_DTYPE_BF16)
         return c.mode == MODE_CAUSAL ? launch_bwd_varlen<bf16_varlen_tag, MODE_CAUSAL>(p, c.nqblk, c.nkblk, s)
                                      : launch_bwd_varlen<bf16_varlen_tag, MODE_PLAIN>(p, c.nqblk, c.nkblk, s);
@@ -263,17 +290,33 @@ using namespace fasn;
 extern "C" {
 
 int fasn_fwd_varlen(const fasn_fwd_args* args, const fasn_varlen* varlen, const float* n, int64_t n_stride_h, fasn_stream_t stream) {
-    return fwd_varlen(args, varlen, n, n_stride_h, (hipStream_t)stream);
+    return fwd_varlen(args, varlen, n, n_stride_h, false, nullptr, (hipStream_t)stream);
 }
 
 int fasn_bwd_varlen(const fasn_bwd_args* args, const fasn_varlen* varlen, fasn_stream_t stream) {
-    return bwd_varlen(args, varlen, (hipStream_t)stream);
+    return bwd_varlen(args, varlen, false, nullptr, (hipStream_t)stream);
 }
 
 int fasn_varlen_plan(const fasn_bwd_args* args, const fasn_varlen* varlen, int32_t which, char* buf, size_t cap) {
     if (args == nullptr || (which != FASN_PLAN_FWD && which != FASN_PLAN_BWD)) return FASN_EINVAL;
     return record_plan(buf, cap, [&] {
-        return which == FASN_PLAN_FWD ? fwd_varlen(&args->fwd, varlen, nullptr, 0, nullptr) : bwd_varlen(args, varlen, nullptr);
+        return which == FASN_PLAN_FWD ? fwd_varlen(&args->fwd, varlen, nullptr, 0, false, nullptr, nullptr) : bwd_varlen(args, varlen, false, nullptr, nullptr);
+    });
+}
+
+int fasn_fwd_varlen_window(const fasn_fwd_args* args, const fasn_varlen* varlen, const fasn_kv_window* window, const float* n, int64_t n_stride_h,
+                           fasn_stream_t stream) {
+    return fwd_varlen(args, varlen, n, n_stride_h, true, window, (hipStream_t)stream);
+}
+
+int fasn_bwd_varlen_window(const fasn_bwd_args* args, const fasn_varlen* varlen, const fasn_kv_window* window, fasn_stream_t stream) {
+    return bwd_varlen(args, varlen, true, window, (hipStream_t)stream);
+}
+
+int fasn_varlen_window_plan(const fasn_bwd_args* args, const fasn_varlen* varlen, const fasn_kv_window* window, int32_t which, char* buf, size_t cap) {
+    if (args == nullptr || (which != FASN_PLAN_FWD && which != FASN_PLAN_BWD)) return FASN_EINVAL;
+    return record_plan(buf, cap, [&] {
+        return which == FASN_PLAN_FWD ? fwd_varlen(&args->fwd, varlen, nullptr, 0, true, window, nullptr) : bwd_varlen(args, varlen, true, window, nullptr);
     });
 }
 

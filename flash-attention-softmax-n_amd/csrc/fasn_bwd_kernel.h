@@ -487,6 +487,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams F
             skip = k0 > wave_last_vis;
             need_mask = (k0 + KT - 1) > wave_first_vis;
         }
+        FASN_ITEM_WINDOW_KTILE(k0, qw0, QB * 32, coff, skip, need_mask)
         if (k0 + KT > p.Sk) need_mask = true;
         if (MODE == MODE_GENERAL_SLOW) need_mask = true;
         if (KP && kp_bits == 0) skip = true;
@@ -541,7 +542,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dq_kernel(const BwdParams F
                             bool show = true;
                             if (decltype(MASKED)::value) {
                                 const int key = k0 + kb * 32 + (VEC ? 16 * hi + r : (r & 3) + 8 * (r >> 2) + 4 * hi);
-                                show = (key < p.Sk) && (key <= vis);
+                                show = (key < p.Sk) && (key <= vis) FASN_ITEM_WINDOW_SHOW(key, vis);
                                 if (MODE == MODE_GENERAL_SLOW) {
                                     const bool inb = show && (row < p.Sq);
                                     if (p.bias != nullptr && inb) {
@@ -736,6 +737,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
         const int first_row = kblk * BN - coff;
         tq0 = first_row <= 0 ? 0 : first_row / QT;
     }
+    FASN_ITEM_WINDOW_NTQ(ntq, kblk * BN, BN, coff)
     if (mode_has_keypad(MODE)) {   // a workgroup none of whose keys is visible (the padded tail of a batch element) walks no q-tile at all
         bool any = false;
 #pragma unroll
@@ -954,6 +956,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
             skip = (r0 + QT - 1 + coff) < kw0;                       // even the last row sees none of my keys
             need_mask = (r0 + coff) < (kw0 + KB * 32 - 1);           // the first row does not see all my keys
         }
+        FASN_ITEM_WINDOW_QTILE(r0, kw0, KB * 32, coff, skip, need_mask)
         if (r0 + QT > p.Sq || kw0 + KB * 32 > p.Sk) need_mask = true;
         if (MODE == MODE_GENERAL_SLOW) need_mask = true;
         if (KPD && kp_none) skip = true;   // none of this wave's keys is visible to anybody
@@ -1030,7 +1033,7 @@ __global__ void __launch_bounds__(256, OCC) fasn_bwd_dkdv_kernel(const BwdParams
                         bool show = true;
                         if (decltype(MASKED)::value) {
                             const int row = r0 + qb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                            show = (key < p.Sk) && (row < p.Sq) && (!causal || key <= row + coff);
+                            show = (key < p.Sk) && (row < p.Sq) && (!causal || key <= row + coff) FASN_ITEM_WINDOW_SHOW(key, row + coff);
                             if (MODE == MODE_GENERAL_SLOW) {
                                 if (p.bias != nullptr && show) {
                                     const int64_t bo = b * p.bs[0] + h * p.bs[1] + (int64_t)row * p.bs[2] + (int64_t)key * p.bs[3];

@@ -105,6 +105,25 @@ template <>
 struct TagVarlen<bf16_varlen_tag> { static constexpr bool value = true; };
 template <>
 struct TagVarlen<f16_varlen_tag> { static constexpr bool value = true; };
+// The packed kernels under a sliding window (fasn_*_varlen_window): a third and fourth tag, packed tags with TagWindow set. The
+// window - keys a row sees, its own position included - rides in FwdParams::tps, which no packed instantiation reads otherwise (split-K is
+// off there). The FASN_ITEM_WINDOW_* hooks are `if constexpr` on the tag: the packed kernels without a window compile what they always did.
+struct bf16_varlen_window_tag {};
+struct f16_varlen_window_tag {};
+template <>
+struct ET<bf16_varlen_window_tag> : ET<bf16_tag> {};
+template <>
+struct ET<f16_varlen_window_tag> : ET<f16_tag> {};
+template <>
+struct TagVarlen<bf16_varlen_window_tag> { static constexpr bool value = true; };
+template <>
+struct TagVarlen<f16_varlen_window_tag> { static constexpr bool value = true; };
+template <typename Tag>
+struct TagWindow { static constexpr bool value = false; };
+template <>
+struct TagWindow<bf16_varlen_window_tag> { static constexpr bool value = true; };
+template <>
+struct TagWindow<f16_varlen_window_tag> { static constexpr bool value = true; };
 #ifdef FASN_VARLEN_ITEMS
 #define FASN_KERNARG(p) p##_launch
 #define FASN_ITEM_PARAMS(T, p)                                                                                          \
@@ -112,15 +131,39 @@ struct TagVarlen<f16_varlen_tag> { static constexpr bool value = true; };
     T p = p##_launch;
 #define FASN_ITEM_ENTER_FWD(D, b, h, row0)   /* forward: the item's sequence; a block beyond it leaves (no barrier yet) */ \
     varlen_enter_fwd<D>(p_launch, p, b, h);                                                                             \
-    if ((row0) >= p.Sq) return;
+    if ((row0) >= p.Sq) return;                                                                                         \
+    if constexpr (TagWindow<Tag>::value) varlen_window_rebase<D>(p_launch, p, row0);
 #define FASN_ITEM_ENTER_DQ(D, b, h, row0)                                                                               \
     varlen_enter_bwd<D>(bp_launch, bp, b);                                                                              \
     varlen_head_bwd(bp_launch, bp, b, h);                                                                               \
-    if ((row0) >= bp.f.Sq) return;
+    if ((row0) >= bp.f.Sq) return;                                                                                      \
+    if constexpr (TagWindow<Tag>::value) varlen_window_rebase<D>(bp_launch.f, bp.f, row0);
 #define FASN_ITEM_ENTER_DKDV(D, b, key0)                                                                                \
     varlen_enter_bwd<D>(bp_launch, bp, b);                                                                              \
     if ((key0) >= bp.f.Sk) return;
 #define FASN_ITEM_HEAD(b, h) varlen_head_bwd(bp_launch, bp, b, h);   /* lse / delta rows of one query head */
+// the lower edge of a window, beside the causal upper edge (`p`: the item's FwdParams; the row at position pos sees key j iff j > pos - tps)
+//   row-owning kernels (forward, dQ), wave rows [qw0, qw0 + rows) against tile [k0, k0 + KT): hidden when its last key lies below the
+//   first row's window, element path when its first key lies below the last row's
+#define FASN_ITEM_WINDOW_KTILE(k0, qw0, rows, coff, skip, need_mask)                                                    \
+    if constexpr (TagWindow<Tag>::value) {                                                                              \
+        skip = skip || ((k0) + KT - 1 <= (qw0) + (coff) - p.tps);                                                       \
+        need_mask = need_mask || ((k0) <= (qw0) + (rows) - 1 + (coff) - p.tps);                                         \
+    }
+//   `vis` = row + coff, the row's last visible key
+#define FASN_ITEM_WINDOW_SHOW(key, vis) &&(!TagWindow<Tag>::value || (key) > (vis) - p.tps)
+//   dK/dV, key block [key0, key0 + BN): no query tile beyond the last row that sees the block's last key
+#define FASN_ITEM_WINDOW_NTQ(ntq, key0, BN, coff)                                                                       \
+    if constexpr (TagWindow<Tag>::value) {                                                                              \
+        const int last_row_w = min((key0) + (BN), p.Sk) - 1 - (coff) + p.tps - 1;                                       \
+        ntq = min(ntq, last_row_w < 0 ? 0 : last_row_w / QT + 1);                                                       \
+    }
+//   dK/dV, wave keys [kw0, kw0 + keys) against query tile [r0, r0 + QT)
+#define FASN_ITEM_WINDOW_QTILE(r0, kw0, keys, coff, skip, need_mask)                                                    \
+    if constexpr (TagWindow<Tag>::value) {                                                                              \
+        skip = skip || ((kw0) + (keys) - 1 <= (r0) + (coff) - p.tps);                                                   \
+        need_mask = need_mask || ((kw0) <= (r0) + QT - 1 + (coff) - p.tps);                                             \
+    }
 #else
 #define FASN_KERNARG(p) p
 #define FASN_ITEM_PARAMS(T, p)
@@ -128,6 +171,10 @@ struct TagVarlen<f16_varlen_tag> { static constexpr bool value = true; };
 #define FASN_ITEM_ENTER_DQ(D, b, h, row0)
 #define FASN_ITEM_ENTER_DKDV(D, b, key0)
 #define FASN_ITEM_HEAD(b, h)
+#define FASN_ITEM_WINDOW_KTILE(k0, qw0, rows, coff, skip, need_mask)
+#define FASN_ITEM_WINDOW_SHOW(key, vis)
+#define FASN_ITEM_WINDOW_NTQ(ntq, key0, BN, coff)
+#define FASN_ITEM_WINDOW_QTILE(r0, kw0, keys, coff, skip, need_mask)
 #endif
 
 // ---- LDS tile image -------------------------------------------------------------------------

@@ -127,6 +127,19 @@ FASN_DEV void varlen_enter_fwd(const FwdParams& l, FwdParams& p, int b, int h) {
 }
 
 constexpr int KT = 64;  // keys per tile
+// Sliding window on a packed item (FASN_ITEM_ENTER_FWD / _DQ on a window tag, after varlen_enter_*): the query block that starts
+// at row0 sees no key below row0 + coff - window + 1, so the item's K / V begin at the tile that holds that key - bases klo rows up, Sk and the
+// descriptor ranges klo shorter. coff = Sk - Sq shifts with Sk: the causal walk and the lower-edge tests run on the rebased keys as they
+// stand, and no K / V row below klo is within a descriptor. row0 < Sq, so klo <= row0 + coff < Sk: at least one key row stays.
+template <int D>
+FASN_DEV void varlen_window_rebase(const FwdParams& l, FwdParams& p, int row0) {
+    const int klo = KT * (max(0, row0 + (p.Sk - p.Sq) - p.tps + 1) / KT);
+    p.k += (int64_t)klo * l.ks[2] * 2;
+    p.v += (int64_t)klo * l.vs[2] * 2;
+    p.Sk -= klo;
+    p.kbytes = varlen_bytes(p.Sk, l.ks[2], D);
+    p.vbytes = varlen_bytes(p.Sk, l.vs[2], D);
+}
 // key-padding modes: visibility words (one per K/V tile) kept in LDS by the forward kernels: 4 KiB, Sk <= 32768. Longer key
 // sequences take the dense-mask general mode of the same mask (fasn_api.hip).
 constexpr int kFwdKpMaxTiles = 512;
@@ -778,6 +791,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
             skip = k0 > wave_last_vis;
             need_mask = (k0 + KT - 1) > wave_first_vis;
         }
+        FASN_ITEM_WINDOW_KTILE(k0, qw0, QB * 32, coff, skip, need_mask)
         if (k0 + KT > p.Sk && !(FOLD && !DIAG)) need_mask = true;   // (a FOLD kernel's main walk ends in front of the diagonal: every key below Sk)
         // per 32-row block (FOLD, diagonal tiles): hidden altogether / needs the element-wise path
         bool skipq[QB], maskq[QB];
@@ -996,7 +1010,7 @@ __global__ void __launch_bounds__(NW * 64, OCC) fasn_fwd_kernel(const FwdParams 
 #pragma unroll
                             for (int r = 0; r < 16; ++r) {
                                 const int key = k0 + kb * 32 + (KPERM ? 16 * hi + r : (r & 3) + 8 * (r >> 2) + 4 * hi);
-                                const bool show = (key < p.Sk) && (key <= vis);
+                                const bool show = (key < p.Sk) && (key <= vis) FASN_ITEM_WINDOW_SHOW(key, vis);
                                 const float y = show ? (SEED ? sacc[qb][kb][r] : sacc[qb][kb][r] * p.c) : -INFINITY;   // SEED: already y - mref
                                 sacc[qb][kb][r] = y;
                                 mx = fmaxf(mx, y);

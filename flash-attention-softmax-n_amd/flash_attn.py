@@ -696,8 +696,15 @@ def _fill_fwd_varlen(a: FwdArgs, q, k, v, o, lse, n, scale, causal):
     a.rng_state = None
 
 
-def _launch_fwd_varlen(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, causal):
-    """out [Tq, H, E] and lse [H, Tq]: every row is written by the call (rows at or beyond cu_q[B]: 0 / -inf, by its tail kernel)"""
+def _window_block(window):
+    w = _lib.KvWindow()
+    w.window, w.reserved = min(window, 2 ** 31 - 1), 0
+    return w
+
+
+def _launch_fwd_varlen(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, causal, window=None):
+    """out [Tq, H, E] and lse [H, Tq]: every row is written by the call (rows at or beyond cu_q[B]: 0 / -inf, by its tail kernel).
+    window: None - fasn_fwd_varlen - or the sliding window of fasn_fwd_varlen_window"""
     lib = _lib.load()
     dev = q.device
     o = torch.empty((q.shape[0], q.shape[1], q.shape[2]), dtype=q.dtype, device=dev)
@@ -706,24 +713,29 @@ def _launch_fwd_varlen(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, causal):
     tensor_n = isinstance(n, Tensor)
     _fill_fwd_varlen(a, q, k, v, o, lse, 0.0 if tensor_n else n, scale, causal)
     vl = _varlen_block(cu_q, cu_k, max_q, max_k)
+    n_ptr, n_stride = (n.data_ptr(), n.stride(1) if n.shape[1] > 1 else 0) if tensor_n else (None, 0)
     with torch.cuda.device(dev):
-        rc = lib.fasn_fwd_varlen(a, vl, n.data_ptr() if tensor_n else None, (n.stride(1) if n.shape[1] > 1 else 0) if tensor_n else 0, _stream_ptr(dev))
+        if window is None:
+            rc = lib.fasn_fwd_varlen(a, vl, n_ptr, n_stride, _stream_ptr(dev))
+        else:
+            rc = lib.fasn_fwd_varlen_window(a, vl, _window_block(window), n_ptr, n_stride, _stream_ptr(dev))
     if rc:
-        _lib.check(rc, "fasn_fwd_varlen")
+        _lib.check(rc, "fasn_fwd_varlen" if window is None else "fasn_fwd_varlen_window")
     return o, lse
 
 
 class _FlashAttentionSoftmaxNVarlen(torch.autograd.Function):
-    """autograd glue of flash_attention_n_varlen, beside _FlashAttentionSoftmaxN: dq / dk / dv through fasn_bwd_varlen, the gradient of a
-    tensor n through fasn_bwd_dn on the [1, H, Tq] view of out, lse and dout (rows behind the last sequence are 0 / -inf: no term)."""
+    """autograd glue of flash_attention_n_varlen, beside _FlashAttentionSoftmaxN: dq / dk / dv through fasn_bwd_varlen (under a window:
+    fasn_bwd_varlen_window), the gradient of a tensor n through fasn_bwd_dn on the [1, H, Tq] view of out, lse and dout (rows behind the
+    last sequence are 0 / -inf: no term; lse carries the window, so the kernel is the same)."""
 
     @staticmethod
-    def forward(ctx, q, k, v, cu_q, cu_k, max_q: int, max_k: int, n, scale: float, causal: bool):
-        o, lse = _launch_fwd_varlen(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, causal)
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q: int, max_k: int, n, scale: float, causal: bool, window=None):
+        o, lse = _launch_fwd_varlen(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, causal, window)
         ctx.save_for_backward(q, k, v, o, lse, cu_q, cu_k)
         ctx.n_shape = tuple(n.shape) if isinstance(n, Tensor) else None
         ctx.n = 0.0 if isinstance(n, Tensor) else n
-        ctx.max_q, ctx.max_k, ctx.scale, ctx.causal = max_q, max_k, scale, causal
+        ctx.max_q, ctx.max_k, ctx.scale, ctx.causal, ctx.window = max_q, max_k, scale, causal, window
         ctx.mark_non_differentiable(lse)
         return o, lse
 
@@ -749,9 +761,12 @@ class _FlashAttentionSoftmaxNVarlen(torch.autograd.Function):
         vl = _varlen_block(cu_q, cu_k, ctx.max_q, ctx.max_k)
         dn = None
         with torch.cuda.device(dev):
-            rc = lib.fasn_bwd_varlen(a, vl, _stream_ptr(dev))
+            if ctx.window is None:
+                rc = lib.fasn_bwd_varlen(a, vl, _stream_ptr(dev))
+            else:
+                rc = lib.fasn_bwd_varlen_window(a, vl, _window_block(ctx.window), _stream_ptr(dev))
             if rc:
-                _lib.check(rc, "fasn_bwd_varlen")
+                _lib.check(rc, "fasn_bwd_varlen" if ctx.window is None else "fasn_bwd_varlen_window")
             if ctx.n_shape is not None and ctx.needs_input_grad[7]:
                 # dL/dn_h = -sum_t delta_t exp(-lse_t): the rectangular call's kernel on B = 1, Sq = Tq (views [1, H, Tq, E] as filled above)
                 dn = torch.empty(ctx.n_shape, dtype=torch.float32, device=dev)
@@ -760,7 +775,7 @@ class _FlashAttentionSoftmaxNVarlen(torch.autograd.Function):
                 ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
                 _lib.check(lib.fasn_bwd_dn(a, dn.data_ptr(), 0, dn.stride(1) if dn.shape[1] > 1 else 0, ws.data_ptr(), ws_bytes, _stream_ptr(dev)),
                            "fasn_bwd_dn")
-        return dq, dk, dv, None, None, None, None, dn, None, None
+        return dq, dk, dv, None, None, None, None, dn, None, None, None
 
 
 def _n_tensor_varlen(n: Tensor, query: Tensor) -> Tensor:
@@ -779,7 +794,7 @@ def _n_tensor_varlen(n: Tensor, query: Tensor) -> Tensor:
 
 def flash_attention_n_varlen(query: Tensor, key: Tensor, value: Tensor, cu_seqlens_q: Tensor, max_seqlen_q: int,
                              cu_seqlens_k: Optional[Tensor] = None, max_seqlen_k: Optional[int] = None, softmax_n_param=1, scale: Optional[float] = None,
-                             is_causal: bool = False, return_lse: bool = False):
+                             is_causal: bool = False, return_lse: bool = False, window: Optional[int] = None):
     """flash_attention_n on packed variable-length sequences, forward and backward (flash_attn_varlen_func for softmax_n): sequence b is
     flash_attention_n on query[cu_q[b]:cu_q[b+1]] against key, value[cu_k[b]:cu_k[b+1]]; nothing is padded and nothing is read on the host.
 
@@ -795,10 +810,22 @@ def flash_attention_n_varlen(query: Tensor, key: Tensor, value: Tensor, cu_seqle
     :param scale: the logits are scale * q . k; default 1 / sqrt(E). A negative scale negates the query. float16 serves |scale| * log2(e) <= 8
                   (NotImplementedError beyond it).
     :param is_causal: bottom-right aligned per sequence: key j visible to row i iff j <= i + (sk_b - sq_b).
+    :param window: None, or a Python int >= 1 - a sliding window, the constant of a layer (Hugging Face's sliding_window; with is_causal only):
+                  row i of sequence b sits at p_i = i + (sk_b - sq_b) and sees key j iff p_i - window < j <= p_i and 0 <= j < sk_b - its own
+                  position counts, `window` keys. A workgroup walks only the window's tiles; a window >= max_seqlen_k is the causal call,
+                  bit for bit. Part of a captured graph.
     :return: out [Tq, H, E]; with return_lse also lse, fp32 [H, Tq]. Rows at or beyond cu_q[B] are 0 with lse -inf, their dq rows and the
              dk / dv rows at or beyond cu_k[B] exactly 0. A row that sees no key is 0 with lse log n (-inf at n = 0), its gradients 0.
     Capturable: one captured graph serves any contents of the cu_seqlens tensors with the same B, T and max_seqlen.
     There is no attn_mask, attn_bias or dropout_p on packed operands."""
+    if window is not None:   # (a constant of the layer: refused before anything is read from the operands)
+        if isinstance(window, bool) or not isinstance(window, int):
+            raise TypeError(f"window must be None or a Python int >= 1; got {type(window).__name__}")
+        if window < 1:
+            raise ValueError(f"window must be >= 1 (a row's own position counts); got {window}")
+        if not is_causal:
+            raise ValueError("window needs is_causal=True: the window is causal and bottom-right aligned (row i at position i + sk_b - sq_b "
+                             "sees the `window` keys that end at its own position); there is no two-sided window")
     if not isinstance(query, Tensor) or not query.is_cuda:
         raise RuntimeError("flash_attention_n_varlen runs on MI355X device tensors only; got a CPU tensor (there is deliberately no CPU fallback)")
     if query.dtype not in (torch.float16, torch.bfloat16):
@@ -854,7 +881,7 @@ def flash_attention_n_varlen(query: Tensor, key: Tensor, value: Tensor, cu_seqle
     q, k, v = (t.clone() if t.data_ptr() % 16 else t for t in (q, k, v))
     needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (isinstance(n, Tensor) and n.requires_grad))
     if needs_grad:
-        out, lse = _FlashAttentionSoftmaxNVarlen.apply(q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale, bool(is_causal))
+        out, lse = _FlashAttentionSoftmaxNVarlen.apply(q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale, bool(is_causal), window)
     else:   # nothing to differentiate: no autograd node
-        out, lse = _launch_fwd_varlen(q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale, bool(is_causal))
+        out, lse = _launch_fwd_varlen(q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale, bool(is_causal), window)
     return (out, lse) if return_lse else out

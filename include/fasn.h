@@ -848,6 +848,33 @@ int fasn_fwd_varlen(const fasn_fwd_args* args, const fasn_varlen* varlen, const 
 int fasn_bwd_varlen(const fasn_bwd_args* args, const fasn_varlen* varlen, fasn_stream_t stream);
 int fasn_varlen_plan(const fasn_bwd_args* args, const fasn_varlen* varlen, int32_t which, char* buf, size_t cap);
 
+/*
+ * SLIDING WINDOW ON THE PACKED TRAINING CALL (additions within ABI 6; no struct is new: the operand is the cache calls' fasn_kv_window).
+ * The positions are those of the cache calls: row i of sequence b sits at p_i = i + (sk_b - sq_b) and sees key j iff 0 <= j < sk_b and
+ * p_i - window < j <= p_i - its own position counts, so `window` keys (the Hugging Face sliding_window rule). A row that sees no key gives
+ * 0 with lse = log n (-inf at n = 0) and zero gradients. Everything else is the base call's: the tail rows, a device n, grouped K/V, strided
+ * views, the grids - functions of num_seqs, max_seqlen_* and the heads; the window changes the walk inside a work item, not the items.
+ *
+ * fasn_fwd_varlen_window / fasn_bwd_varlen_window are fasn_fwd_varlen / fasn_bwd_varlen with the operand: the tail kernel, then forward / dQ
+ * and dK/dV kernels of their own (the packed kernels compiled once more, under names of their own). fasn_varlen_window_plan is
+ * fasn_varlen_plan for these launches. With window >= max_seqlen_k no key of any sequence can lie below a row's window: the three calls
+ * then take the launches of the causal packed call - its plan text, its results bit for bit.
+ * Codes: every rule and code of fasn_fwd_varlen / fasn_bwd_varlen holds and is checked first, in its order; then window == NULL,
+ * window->window < 1 or reserved != 0 is FASN_EINVAL; then args->causal == 0 is FASN_EUNSUPPORTED (the window is causal, bottom-right
+ * aligned). Any window >= 1 is legal.
+ *
+ * Memory contract (what "only the window's tiles" means). With coff_b = sk_b - sq_b, for the 128-row query block of sequence b that starts
+ * at row q0, the forward and the dQ kernel read no K / V row of the sequence below 64 * floor(max(0, q0 + coff_b - window + 1) / 64): such
+ * rows may hold anything. For a 128-key block, the dK/dV kernel uses no Q / dO / lse / delta row of a 64-row tile beyond tile
+ * floor((last key of the block - coff_b + window - 1) / 64) (no tile at all when that is negative: dk / dv of the block are 0). A row that
+ * a prefetch loads and no MFMA consumes is within the contract.
+ */
+int fasn_fwd_varlen_window(const fasn_fwd_args* args, const fasn_varlen* varlen, const fasn_kv_window* window, const float* n,
+                           int64_t n_stride_h, fasn_stream_t stream);
+int fasn_bwd_varlen_window(const fasn_bwd_args* args, const fasn_varlen* varlen, const fasn_kv_window* window, fasn_stream_t stream);
+int fasn_varlen_window_plan(const fasn_bwd_args* args, const fasn_varlen* varlen, const fasn_kv_window* window, int32_t which, char* buf,
+                            size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
