@@ -3,6 +3,7 @@
 Public surface = flash_attention_softmax_n/__init__.py:3-9 of the reference:
     flash_attention_n, softmax_n, slow_attention_n, flash_attention_n_triton (+ TRITON_INSTALLED for source compat)
     flash_attention_n_varlen  (training attention on packed variable-length sequences, forward and backward; no counterpart in the reference)
+    flash_attention_n_varlen_rope  (the same call with rotary position embedding at per-sequence positions: one launch rotates q and k)
     flash_attention_n_kvcache  (inference over a paged / dense K/V cache with device-side lengths; no counterpart in the reference)
     flash_attention_n_kvcache_prefill  (the same cache, any number of query positions, ragged query lengths on the device)
     flash_attention_n_kvcache_window  (a sliding-window layer on the same cache: decode or prefill, only the window's pages are read)
@@ -25,7 +26,7 @@ Every function runs on device tensors through libfasn.so; importing the package 
 library raises ImportError (no silent fallback).
 """
 from . import _lib, dropout, statistics, surgery
-from .flash_attn import flash_attention_n, flash_attention_n_triton, flash_attention_n_varlen, slow_attention_n
+from .flash_attn import flash_attention_n, flash_attention_n_triton, flash_attention_n_varlen, flash_attention_n_varlen_rope, slow_attention_n
 from .kvcache import (flash_attention_n_kvcache, flash_attention_n_kvcache_fp8, flash_attention_n_kvcache_fp8_rope, flash_attention_n_kvcache_fp8_tree,
                       flash_attention_n_kvcache_fp8_tree_commit, flash_attention_n_kvcache_fp8_varlen, flash_attention_n_kvcache_fp8_varlen_rope,
                       flash_attention_n_kvcache_fp8_varlen_window, flash_attention_n_kvcache_fp8_window,
@@ -39,4 +40,4 @@ _lib.load()  # fail loudly at import if the HIP extension is missing
 TRITON_INSTALLED = False  # kept for source compatibility: the Triton path is replaced by the HIP kernel
 HIP_NATIVE = True
 
-__all__ = ["flash_attention_n", "flash_attention_n_varlen", "flash_attention_n_kvcache", "flash_attention_n_kvcache_prefill", "flash_attention_n_kvcache_window", "flash_attention_n_kvcache_rope", "flash_attention_n_kvcache_varlen", "flash_attention_n_kvcache_varlen_window", "flash_attention_n_kvcache_varlen_rope", "flash_attention_n_kvcache_tree", "flash_attention_n_kvcache_tree_commit", "flash_attention_n_kvcache_fp8", "flash_attention_n_kvcache_fp8_window", "flash_attention_n_kvcache_fp8_rope", "flash_attention_n_kvcache_fp8_tree", "flash_attention_n_kvcache_fp8_tree_commit", "flash_attention_n_kvcache_fp8_varlen", "flash_attention_n_kvcache_fp8_varlen_window", "flash_attention_n_kvcache_fp8_varlen_rope", "flash_attention_n_triton", "slow_attention_n", "softmax_n", "TRITON_INSTALLED", "HIP_NATIVE"]
+__all__ = ["flash_attention_n", "flash_attention_n_varlen", "flash_attention_n_varlen_rope", "flash_attention_n_kvcache", "flash_attention_n_kvcache_prefill", "flash_attention_n_kvcache_window", "flash_attention_n_kvcache_rope", "flash_attention_n_kvcache_varlen", "flash_attention_n_kvcache_varlen_window", "flash_attention_n_kvcache_varlen_rope", "flash_attention_n_kvcache_tree", "flash_attention_n_kvcache_tree_commit", "flash_attention_n_kvcache_fp8", "flash_attention_n_kvcache_fp8_window", "flash_attention_n_kvcache_fp8_rope", "flash_attention_n_kvcache_fp8_tree", "flash_attention_n_kvcache_fp8_tree_commit", "flash_attention_n_kvcache_fp8_varlen", "flash_attention_n_kvcache_fp8_varlen_window", "flash_attention_n_kvcache_fp8_varlen_rope", "flash_attention_n_triton", "slow_attention_n", "softmax_n", "TRITON_INSTALLED", "HIP_NATIVE"]

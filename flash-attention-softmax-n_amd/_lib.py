@@ -49,6 +49,7 @@ EXPORTS = (
     "fasn_kv_forward_workspace_bytes", "fasn_kv_forward", "fasn_kv_forward_plan", "fasn_kv_append", "fasn_kv_append_plan",
     "fasn_fwd_varlen", "fasn_bwd_varlen", "fasn_varlen_plan",
     "fasn_fwd_varlen_window", "fasn_bwd_varlen_window", "fasn_varlen_window_plan",
+    "fasn_varlen_rope", "fasn_varlen_rope_plan",
 )
 
 
@@ -327,6 +328,10 @@ def load():
     lib.fasn_bwd_varlen_window.argtypes = [POINTER(BwdArgs), POINTER(Varlen), POINTER(KvWindow), c_void_p]
     lib.fasn_varlen_window_plan.restype = c_int32
     lib.fasn_varlen_window_plan.argtypes = [POINTER(BwdArgs), POINTER(Varlen), POINTER(KvWindow), c_int32, c_char_p, c_size_t]
+    lib.fasn_varlen_rope.restype = c_int32
+    lib.fasn_varlen_rope.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvRope), POINTER(View4), POINTER(View4), c_int32, c_void_p]
+    lib.fasn_varlen_rope_plan.restype = c_int32
+    lib.fasn_varlen_rope_plan.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvRope), POINTER(View4), POINTER(View4), c_int32, c_char_p, c_size_t]
     for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -393,6 +398,12 @@ def varlen_window_plan(args, varlen, win, which):
     """The kernels fasn_fwd_varlen_window (FASN_PLAN_FWD) or fasn_bwd_varlen_window (FASN_PLAN_BWD) would launch for `args` and `varlen`
     under `win` (a KvWindow), as launch_plan returns them; varlen_plan's with a window >= max_seqlen_k. Nothing is launched."""
     return _plan("fasn_varlen_window_plan", args, varlen, win, which)
+
+
+def varlen_rope_plan(args, varlen, rope, q_out, k_out, inverse=0):
+    """The one launch of fasn_varlen_rope for `args` (a FwdArgs that describes the packed operands; q and k are the sources) and `varlen`
+    under `rope` (a KvRope) into the views `q_out` / `k_out`, as launch_plan returns it. Nothing is launched."""
+    return _plan("fasn_varlen_rope_plan", args, varlen, rope, q_out, k_out, inverse)
 
 
 def kvcache_plan(args, alibi=None):

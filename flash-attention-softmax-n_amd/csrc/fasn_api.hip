@@ -66,6 +66,7 @@ static size_t describe_kernel(const char* name, size_t n, char* out, size_t cap)
         {"fasn_kvrope_fp8_tree_kernel", "T D"},
         {"fasn_kvcache_fp8_tree_commit_kernel", "D"},
         {"fasn_varlen_tail_kernel", "TOK"},
+        {"fasn_varlen_rope_kernel", "T D"},
     };
     static const char* const modes[] = {"plain", "causal", "bias+mask", "element-load", "bias", "mask", "keypad", "bias+keypad"};
     if (cap == 0) return 0;

@@ -3,13 +3,15 @@
 // rectangular kernels' text on the *_varlen_tag element tags (fasn_common.h): a work item is (sequence, head, block) on a grid sized from
 // num_seqs and max_seqlen_*, and takes its offsets and lengths from the two tables in device memory. The *_window entry points
 // (fasn_fwd_varlen_window, fasn_bwd_varlen_window, fasn_varlen_window_plan) launch the same kernels on the *_varlen_window_tag
-// tags, which walk only the tiles of a sliding window, on the same grids.
+// tags, which walk only the tiles of a sliding window, on the same grids. fasn_varlen_rope / fasn_varlen_rope_plan enter here
+// for the packed call's argument checks; the rope operand's checks, the kernel and its launch are fasn_varlen_rope.hip's.
 #define FASN_VARLEN_ITEMS 1   // the kernel headers compile the packed variable-length form of their kernels here (fasn_common.h)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "fasn.h"
 #include "fasn_plan.h"
 #include "fasn_bwd_launch.h"
+#include "fasn_varlen_rope.h"
 
 namespace fasn {
 namespace {
@@ -54,8 +56,10 @@ __global__ void __launch_bounds__(256) fasn_varlen_tail_kernel(const VarlenTail 
 }
 
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+}  // namespace
 // a packed operand [1, heads, rows, D] of 16-bit elements: unit feature stride, 16-byte rows, less than 2^31 bytes from its first row to
-// the end of its last (the kernels' descriptors and their 32-bit row offsets)
+// the end of its last (the kernels' descriptors and their 32-bit row offsets). (Named in fasn_varlen_rope.h: the rotary launch checks
+// its outputs under the same rules.)
 int check_packed(const fasn_view4& v, int rows, int D) {
     if (v.ptr == nullptr) return FASN_EINVAL;
     if (v.stride[3] != 1) return FASN_ESTRIDE;
@@ -64,6 +68,7 @@ int check_packed(const fasn_view4& v, int rows, int D) {
     if (((int64_t)(rows - 1) * v.stride[2] + D) * 2 >= (1ll << 31)) return FASN_EINVAL;
     return FASN_OK;
 }
+namespace {
 
 constexpr int kBlock = 128;   // query rows / keys of a work item: four waves x 32
 
@@ -73,7 +78,9 @@ struct VarlenCall {
     int nqblk, nkblk;
 };
 
-int build_varlen(const fasn_fwd_args* a, const fasn_varlen* vl, const float* n, int64_t n_stride_h, VarlenCall& c) {
+// qk_only: the rotary launch (fasn_varlen_rope), which reads q and k alone - the rules of v, o and lse do not apply to it, every other
+// rule and code does, in this order
+int build_varlen(const fasn_fwd_args* a, const fasn_varlen* vl, const float* n, int64_t n_stride_h, VarlenCall& c, bool qk_only = false) {
     if (a == nullptr || vl == nullptr) return FASN_EINVAL;
     if (vl->cu_seqlens_q == nullptr || vl->cu_seqlens_k == nullptr) return FASN_EINVAL;
     if (vl->num_seqs < 1 || vl->max_seqlen_q < 1 || vl->max_seqlen_k < 1 || vl->reserved != 0) return FASN_EINVAL;
@@ -91,11 +98,13 @@ int build_varlen(const fasn_fwd_args* a, const fasn_varlen* vl, const float* n, 
     int rc;
     if ((rc = check_packed(a->q, a->Sq, a->D))) return rc;
     if ((rc = check_packed(a->k, a->Sk, a->D))) return rc;
-    if ((rc = check_packed(a->v, a->Sk, a->D))) return rc;
-    if ((rc = check_packed(a->o, a->Sq, a->D))) return rc;
-    if (a->lse == nullptr) return FASN_EINVAL;
+    if (!qk_only) {
+        if ((rc = check_packed(a->v, a->Sk, a->D))) return rc;
+        if ((rc = check_packed(a->o, a->Sq, a->D))) return rc;
+        if (a->lse == nullptr) return FASN_EINVAL;
+    }
     if (reinterpret_cast<uintptr_t>(vl->cu_seqlens_q) % 4 || reinterpret_cast<uintptr_t>(vl->cu_seqlens_k) % 4) return FASN_EALIGN;
-    if (reinterpret_cast<uintptr_t>(a->lse) % 4 || reinterpret_cast<uintptr_t>(n) % 4) return FASN_EALIGN;
+    if (!qk_only && (reinterpret_cast<uintptr_t>(a->lse) % 4 || reinterpret_cast<uintptr_t>(n) % 4)) return FASN_EALIGN;
 
     c.nqblk = (vl->max_seqlen_q + kBlock - 1) / kBlock;
     c.nkblk = (vl->max_seqlen_k + kBlock - 1) / kBlock;
@@ -282,6 +291,16 @@ int bwd_varlen(const fasn_bwd_args* a, const fasn_varlen* vl, bool windowed, con
                                  : launch_bwd_varlen<f16_varlen_tag, MODE_PLAIN>(p, c.nqblk, c.nkblk, s);
 }
 
+// fasn_varlen_rope: the base call's rules on the block (q and k are the sources; v, o and lse are not touched), then the rope operand's
+// and the launch (fasn_varlen_rope.hip)
+int rope_varlen(const fasn_fwd_args* a, const fasn_varlen* vl, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_out, int32_t inverse,
+                hipStream_t s) {
+    VarlenCall c;
+    const int rc = build_varlen(a, vl, nullptr, 0, c, true);
+    if (rc) return rc;
+    return varlen_rope(a, vl, c.p.kvg, rope, q_out, k_out, inverse, s);
+}
+
 }  // namespace
 }  // namespace fasn
 
@@ -318,6 +337,16 @@ int fasn_varlen_window_plan(const fasn_bwd_args* args, const fasn_varlen* varlen
     return record_plan(buf, cap, [&] {
         return which == FASN_PLAN_FWD ? fwd_varlen(&args->fwd, varlen, nullptr, 0, true, window, nullptr) : bwd_varlen(args, varlen, true, window, nullptr);
     });
+}
+
+int fasn_varlen_rope(const fasn_fwd_args* args, const fasn_varlen* varlen, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_out,
+                     int32_t inverse, fasn_stream_t stream) {
+    return rope_varlen(args, varlen, rope, q_out, k_out, inverse, (hipStream_t)stream);
+}
+
+int fasn_varlen_rope_plan(const fasn_fwd_args* args, const fasn_varlen* varlen, const fasn_kv_rope* rope, const fasn_view4* q_out, const fasn_view4* k_out,
+                          int32_t inverse, char* buf, size_t cap) {
+    return record_plan(buf, cap, [&] { return rope_varlen(args, varlen, rope, q_out, k_out, inverse, nullptr); });
 }
 
 }  // extern "C"

@@ -7,6 +7,8 @@
 // FASN_KVROPE_FP8 = 1 (fasn_kvfp8.h: fasn_kvrope_fp8_kernel; undefined counts as 0): a K/V unit (!isq) stores chunk c - the 16-bit values
 // every other kernel stores - as their 8 e4m3fn codes under the scale `ksc` at byte 8 c of the code row `dst8`; E = ET<Tag> is in scope
 // too. The store has one name for that; with FASN_KVROPE_FP8 == 0 it is the 16-byte store it was, token for token.
+// FASN_KVROPE_INVERSE = 1 (fasn_varlen_rope.hip: the packed training call, whose backward rotates gradients; undefined counts as 0):
+// `rp.inverse` != 0 negates the sines behind the table read. With FASN_KVROPE_INVERSE == 0 no token is added.
 #if FASN_KVROPE_FP8
 #define FASN_KVROPE_STORE(c, x)                                        \
     do {                                                               \
@@ -29,6 +31,12 @@
     float c[8], s[8], e0[8], e1[8], x1[8], x2[8], y1[8], y2[8];
     kvrope_table<Tag>(rp.cos, trow * rp.trs + 8 * u, rp.tf32, c);
     kvrope_table<Tag>(rp.sin, trow * rp.trs + 8 * u, rp.tf32, s);
+#if FASN_KVROPE_INVERSE
+    if (rp.inverse) {   // the transpose rotation: sin negated, which is exact - y1 = x1 c + x2 s, y2 = x2 c - x1 s with the same roundings
+#pragma unroll
+        for (int j = 0; j < 8; ++j) s[j] = -s[j];
+    }
+#endif
     kvrope_widen<Tag>(a, e0);
     kvrope_widen<Tag>(bq, e1);
     if (rp.interleaved) {   // the 16 elements are the pairs (2 j, 2 j + 1)

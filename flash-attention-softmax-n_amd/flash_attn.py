@@ -741,41 +741,47 @@ class _FlashAttentionSoftmaxNVarlen(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _dlse):
-        lib = _lib.load()
         q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
-        dev = q.device
-        if not _packed_ok(dout):
-            dout = dout.contiguous()
-            if dout.data_ptr() % 16:
-                dout = dout.clone()
-        dq = torch.empty(q.shape, dtype=q.dtype, device=dev)
-        dk = torch.empty(k.shape, dtype=q.dtype, device=dev)
-        dv = torch.empty(v.shape, dtype=q.dtype, device=dev)
-        delta = torch.empty(lse.shape, dtype=torch.float32, device=dev)
-        a = BwdArgs()
-        _fill_fwd_varlen(a.fwd, q, k, v, o, lse, ctx.n, ctx.scale, ctx.causal)
-        a.dout, a.dq, a.dk, a.dv = _view_packed(dout), _view_packed(dq), _view_packed(dk), _view_packed(dv)
-        a.delta = delta.data_ptr()
-        a.workspace, a.workspace_bytes, a.flags, a.dbias_dtype = None, 0, 0, 0
-        a.dbias.ptr = None
-        vl = _varlen_block(cu_q, cu_k, ctx.max_q, ctx.max_k)
-        dn = None
-        with torch.cuda.device(dev):
-            if ctx.window is None:
-                rc = lib.fasn_bwd_varlen(a, vl, _stream_ptr(dev))
-            else:
-                rc = lib.fasn_bwd_varlen_window(a, vl, _window_block(ctx.window), _stream_ptr(dev))
-            if rc:
-                _lib.check(rc, "fasn_bwd_varlen" if ctx.window is None else "fasn_bwd_varlen_window")
-            if ctx.n_shape is not None and ctx.needs_input_grad[7]:
-                # dL/dn_h = -sum_t delta_t exp(-lse_t): the rectangular call's kernel on B = 1, Sq = Tq (views [1, H, Tq, E] as filled above)
-                dn = torch.empty(ctx.n_shape, dtype=torch.float32, device=dev)
-                a.fwd.softmax_n = 0.0
-                ws_bytes = lib.fasn_bwd_dn_workspace_bytes(a)
-                ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
-                _lib.check(lib.fasn_bwd_dn(a, dn.data_ptr(), 0, dn.stride(1) if dn.shape[1] > 1 else 0, ws.data_ptr(), ws_bytes, _stream_ptr(dev)),
-                           "fasn_bwd_dn")
+        dq, dk, dv, dn = _bwd_varlen(ctx, q, k, v, o, lse, cu_q, cu_k, dout)
         return dq, dk, dv, None, None, None, None, dn, None, None, None
+
+
+def _bwd_varlen(ctx, q, k, v, o, lse, cu_q, cu_k, dout):
+    """(dq, dk, dv, dn) of the packed call on the saved operands; ctx: the node's constants (n at input 7). Freshly allocated, contiguous."""
+    lib = _lib.load()
+    dev = q.device
+    if not _packed_ok(dout):
+        dout = dout.contiguous()
+        if dout.data_ptr() % 16:
+            dout = dout.clone()
+    dq = torch.empty(q.shape, dtype=q.dtype, device=dev)
+    dk = torch.empty(k.shape, dtype=q.dtype, device=dev)
+    dv = torch.empty(v.shape, dtype=q.dtype, device=dev)
+    delta = torch.empty(lse.shape, dtype=torch.float32, device=dev)
+    a = BwdArgs()
+    _fill_fwd_varlen(a.fwd, q, k, v, o, lse, ctx.n, ctx.scale, ctx.causal)
+    a.dout, a.dq, a.dk, a.dv = _view_packed(dout), _view_packed(dq), _view_packed(dk), _view_packed(dv)
+    a.delta = delta.data_ptr()
+    a.workspace, a.workspace_bytes, a.flags, a.dbias_dtype = None, 0, 0, 0
+    a.dbias.ptr = None
+    vl = _varlen_block(cu_q, cu_k, ctx.max_q, ctx.max_k)
+    dn = None
+    with torch.cuda.device(dev):
+        if ctx.window is None:
+            rc = lib.fasn_bwd_varlen(a, vl, _stream_ptr(dev))
+        else:
+            rc = lib.fasn_bwd_varlen_window(a, vl, _window_block(ctx.window), _stream_ptr(dev))
+        if rc:
+            _lib.check(rc, "fasn_bwd_varlen" if ctx.window is None else "fasn_bwd_varlen_window")
+        if ctx.n_shape is not None and ctx.needs_input_grad[7]:
+            # dL/dn_h = -sum_t delta_t exp(-lse_t): the rectangular call's kernel on B = 1, Sq = Tq (views [1, H, Tq, E] as filled above)
+            dn = torch.empty(ctx.n_shape, dtype=torch.float32, device=dev)
+            a.fwd.softmax_n = 0.0
+            ws_bytes = lib.fasn_bwd_dn_workspace_bytes(a)
+            ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)
+            _lib.check(lib.fasn_bwd_dn(a, dn.data_ptr(), 0, dn.stride(1) if dn.shape[1] > 1 else 0, ws.data_ptr(), ws_bytes, _stream_ptr(dev)),
+                       "fasn_bwd_dn")
+    return dq, dk, dv, dn
 
 
 def _n_tensor_varlen(n: Tensor, query: Tensor) -> Tensor:
@@ -818,6 +824,19 @@ def flash_attention_n_varlen(query: Tensor, key: Tensor, value: Tensor, cu_seqle
              dk / dv rows at or beyond cu_k[B] exactly 0. A row that sees no key is 0 with lse log n (-inf at n = 0), its gradients 0.
     Capturable: one captured graph serves any contents of the cu_seqlens tensors with the same B, T and max_seqlen.
     There is no attn_mask, attn_bias or dropout_p on packed operands."""
+    q, k, v, cu_q, cu_k, max_q, max_k, n, scale = _prepare_varlen(query, key, value, cu_seqlens_q, max_seqlen_q, cu_seqlens_k, max_seqlen_k,
+                                                                  softmax_n_param, scale, is_causal, window)
+    needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (isinstance(n, Tensor) and n.requires_grad))
+    if needs_grad:
+        out, lse = _FlashAttentionSoftmaxNVarlen.apply(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, bool(is_causal), window)
+    else:   # nothing to differentiate: no autograd node
+        out, lse = _launch_fwd_varlen(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, bool(is_causal), window)
+    return (out, lse) if return_lse else out
+
+
+def _prepare_varlen(query, key, value, cu_seqlens_q, max_seqlen_q, cu_seqlens_k, max_seqlen_k, softmax_n_param, scale, is_causal, window):
+    """every refusal of flash_attention_n_varlen, in its order and under its name (flash_attention_n_varlen_rope refuses the same calls with
+    the same words), then the operands as the launches take them: (q, k, v, cu_q, cu_k, max_q, max_k, n, scale)"""
     if window is not None:   # (a constant of the layer: refused before anything is read from the operands)
         if isinstance(window, bool) or not isinstance(window, int):
             raise TypeError(f"window must be None or a Python int >= 1; got {type(window).__name__}")
@@ -879,9 +898,119 @@ def flash_attention_n_varlen(query: Tensor, key: Tensor, value: Tensor, cu_seqle
                                   f"{_VARLEN_F16_MAX_PRESCALE / _VARLEN_LOG2E:.4f}; use bfloat16 or fold the scale into the query")
     q, k, v = (t if _packed_ok(t) else t.contiguous() for t in (query, key, value))
     q, k, v = (t.clone() if t.data_ptr() % 16 else t for t in (q, k, v))
+    return q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale
+
+
+# ---- rotary position embedding on the packed call (include/fasn.h: fasn_varlen_rope) ---------------------------------
+def _launch_varlen_rope(q, k, q_out, k_out, cu_q, cu_k, max_q, max_k, rope, inverse):
+    """the one rotary launch over packed q [Tq, H, E] and k [Tk, Hkv, E] into q_out / k_out (None: allocated here; rows at or beyond
+    cu[B] of a side are not written - no launch reads them). inverse: the transpose rotation. Returns (q_out, k_out)."""
+    lib = _lib.load()
+    dev = q.device
+    if q_out is None:
+        q_out = torch.empty(q.shape, dtype=q.dtype, device=dev)
+    if k_out is None:
+        k_out = torch.empty(k.shape, dtype=k.dtype, device=dev)
+    a = FwdArgs()
+    a.q, a.k = _view_packed(q), _view_packed(k)
+    a.v.ptr = a.o.ptr = a.lse = None   # (not touched by this launch)
+    a.mask.ptr = a.bias.ptr = None
+    a.bias_dtype = _lib.FASN_BIAS_NONE
+    a.dtype = _DTYPES[q.dtype]
+    a.B, a.H, a.Sq, a.Sk, a.D, a.Dv = 1, q.shape[1], q.shape[0], k.shape[0], q.shape[2], q.shape[2]
+    a.kv_group = q.shape[1] // k.shape[1] if k.shape[1] != q.shape[1] else 0
+    a.scale, a.softmax_n, a.causal, a.dropout_p = 1.0, 0.0, 0, 0.0
+    a.seed = a.offset = 0
+    a.rng_state = None
+    vl = _varlen_block(cu_q, cu_k, max_q, max_k)
+    with torch.cuda.device(dev):
+        rc = lib.fasn_varlen_rope(a, vl, rope, _view_packed(q_out), _view_packed(k_out), 1 if inverse else 0, _stream_ptr(dev))
+    if rc:
+        _lib.check(rc, "fasn_varlen_rope")
+    return q_out, k_out
+
+
+class _FlashAttentionSoftmaxNVarlenRope(torch.autograd.Function):
+    """autograd glue of flash_attention_n_varlen_rope: the rotary launch, then _FlashAttentionSoftmaxNVarlen's forward on the rotated q / k,
+    which are what is saved; the backward is that class's on the saved operands, then the transpose rotation of dq / dk in place."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, cu_q, cu_k, max_q: int, max_k: int, n, scale: float, causal: bool, window, cos, sin, interleaved: bool):
+        from .kvcache import _rope_operand
+        qr, kr = _launch_varlen_rope(q, k, None, None, cu_q, cu_k, max_q, max_k, _rope_operand(cos, sin, interleaved, q), False)
+        o, lse = _launch_fwd_varlen(qr, kr, v, cu_q, cu_k, max_q, max_k, n, scale, causal, window)
+        ctx.save_for_backward(qr, kr, v, o, lse, cu_q, cu_k, cos, sin)
+        ctx.n_shape = tuple(n.shape) if isinstance(n, Tensor) else None
+        ctx.n = 0.0 if isinstance(n, Tensor) else n
+        ctx.max_q, ctx.max_k, ctx.scale, ctx.causal, ctx.window, ctx.interleaved = max_q, max_k, scale, causal, window, interleaved
+        ctx.mark_non_differentiable(lse)
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, dout, _dlse):
+        from .kvcache import _rope_operand
+        qr, kr, v, o, lse, cu_q, cu_k, cos, sin = ctx.saved_tensors
+        dq, dk, dv, dn = _bwd_varlen(ctx, qr, kr, v, o, lse, cu_q, cu_k, dout)
+        _launch_varlen_rope(dq, dk, dq, dk, cu_q, cu_k, ctx.max_q, ctx.max_k, _rope_operand(cos, sin, ctx.interleaved, qr), True)
+        return dq, dk, dv, None, None, None, None, dn, None, None, None, None, None, None
+
+
+def flash_attention_n_varlen_rope(query: Tensor, key: Tensor, value: Tensor, cu_seqlens_q: Tensor, max_seqlen_q: int, rotary_cos: Tensor,
+                                  rotary_sin: Tensor, cu_seqlens_k: Optional[Tensor] = None, max_seqlen_k: Optional[int] = None,
+                                  softmax_n_param=1, scale: Optional[float] = None, is_causal: bool = False, return_lse: bool = False,
+                                  window: Optional[int] = None, rotary_interleaved: bool = False):
+    """flash_attention_n_varlen with rotary position embedding (RoPE) at per-sequence positions, forward and backward: ONE launch rotates the
+    packed query and key rows - positions from the offset tables in device memory, nothing read on the host -, then the packed call runs on
+    the rotated operands (flash-attn's apply_rotary_emb(..., cu_seqlens=, max_seqlen=) in front of flash_attn_varlen_func).
+
+    Positions: key token cu_k[b] + j sits at j, query token cu_q[b] + i at p_i = i + (sk_b - sq_b) - the position of the causal mask and of
+    `window`; self-attention gives p_i = i, and every sequence restarts at 0. The table row read is clamp(position, 0, rows - 1).
+
+    :param rotary_cos, rotary_sin: [rows, rotary_dim / 2] device tensors, float32 or the query's dtype, unit column stride, 16-byte aligned
+                  rows; 16 <= rotary_dim <= E, rotary_dim % 16 == 0 (features beyond rotary_dim pass through); rows >= max_seqlen_k
+                  (max_seqlen_q when cu_seqlens_k is None). Scaling rules (YaRN, NTK) live in the tables. A table that requires grad is
+                  refused: there is no table gradient.
+    :param rotary_interleaved: False: the half-split layout (GPT-NeoX / Llama / GPT-OSS, rotate_half) - the pair of feature d is
+                  (d, d + rotary_dim / 2); True: GPT-J pairs (2 d, 2 d + 1).
+    Every other parameter, the result and every refusal are flash_attention_n_varlen's (the refusals come first, with its messages).
+
+    out, lse and the gradient of a tensor n are, bit for bit, flash_attention_n_varlen on rot(query), rot(key), value, with rot evaluated in
+    fp32 - every product and the sum / difference rounded on its own - and rounded once to the operand type; query.grad and key.grad are,
+    bit for bit, eager autograd's for that rot in front of the call: the transpose rotation of the rotated operands' gradients in fp32,
+    rounded once. The rotated query and key are allocated once and are what the backward keeps; the unrotated ones are not kept here.
+    Capturable as flash_attention_n_varlen is."""
+    q, k, v, cu_q, cu_k, max_q, max_k, n, scale = _prepare_varlen(query, key, value, cu_seqlens_q, max_seqlen_q, cu_seqlens_k, max_seqlen_k,
+                                                                  softmax_n_param, scale, is_causal, window)
+    fn = "flash_attention_n_varlen_rope"
+    from .kvcache import _check_rotary_tables, _rope_operand
+    if not isinstance(rotary_interleaved, bool):
+        raise TypeError(f"{fn}: rotary_interleaved must be a bool; got {type(rotary_interleaved).__name__}")
+    _check_rotary_tables(fn, rotary_cos, rotary_sin, q)
+    E = q.shape[2]
+    rows, rd = rotary_cos.shape[0], 2 * rotary_cos.shape[1]
+    esize = rotary_cos.element_size()
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if t.device != q.device:
+            raise RuntimeError(f"{name} is on {t.device}, query on {q.device}: every operand must live on the query's device "
+                               "(the tables are read by the kernels, never on the host)")
+    if rd < 16 or rd > E or rd % 16 != 0:
+        raise ValueError(f"{fn}: rotary_dim = 2 x {rotary_cos.shape[1]} = {rd} is not supported: 16 <= rotary_dim <= head dim {E} and "
+                         "rotary_dim % 16 == 0 (a lane rotates 8 pairs)")
+    if rows < max_k:
+        raise ValueError(f"{fn}: the rotary tables cover {rows} positions but max_seqlen_k is {max_k}: rows >= max_seqlen_k, so that "
+                         "no position the offsets in device memory can name lies outside the tables")
+    for name, t in (("rotary_cos", rotary_cos), ("rotary_sin", rotary_sin)):
+        if t.stride(1) != 1 or t.data_ptr() % 16 != 0 or (rows > 1 and ((t.stride(0) * esize) % 16 != 0 or t.stride(0) < rd // 2)):
+            raise ValueError(f"{fn}: {name}: rows must be 16-byte aligned, apart and with unit column stride (base pointer % 16 == 0, row "
+                             f"stride x {esize} bytes % 16 == 0, row stride >= rotary_dim / 2 = {rd // 2}); got strides {tuple(t.stride())}. "
+                             "A table is never copied here")
+        if t.requires_grad:
+            raise ValueError(f"{fn}: {name} requires grad: there is no gradient with respect to the rotary tables; pass it detached")
     needs_grad = torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad or (isinstance(n, Tensor) and n.requires_grad))
     if needs_grad:
-        out, lse = _FlashAttentionSoftmaxNVarlen.apply(q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale, bool(is_causal), window)
+        out, lse = _FlashAttentionSoftmaxNVarlenRope.apply(q, k, v, cu_q, cu_k, max_q, max_k, n, scale, bool(is_causal), window, rotary_cos,
+                                                           rotary_sin, rotary_interleaved)
     else:   # nothing to differentiate: no autograd node
-        out, lse = _launch_fwd_varlen(q, k, v, cu_seqlens_q, cu_k, max_q, max_k, n, scale, bool(is_causal), window)
+        qr, kr = _launch_varlen_rope(q, k, None, None, cu_q, cu_k, max_q, max_k, _rope_operand(rotary_cos, rotary_sin, rotary_interleaved, q), False)
+        out, lse = _launch_fwd_varlen(qr, kr, v, cu_q, cu_k, max_q, max_k, n, scale, bool(is_causal), window)
     return (out, lse) if return_lse else out

@@ -875,6 +875,38 @@ int fasn_bwd_varlen_window(const fasn_bwd_args* args, const fasn_varlen* varlen,
 int fasn_varlen_window_plan(const fasn_bwd_args* args, const fasn_varlen* varlen, const fasn_kv_window* window, int32_t which, char* buf,
                             size_t cap);
 
+/*
+ * ROTARY POSITION EMBEDDING ON THE PACKED TRAINING CALL (additions within ABI 6; no struct is new: the operand is the cache calls'
+ * fasn_kv_rope, with `rows` >= max_seqlen_k in the place of the capacity). ONE launch in front of fasn_fwd_varlen / fasn_fwd_varlen_window
+ * that rotates the packed q and k rows at per-sequence positions, read from the two offset tables in device memory - a replayed graph
+ * follows them. With [q0, q1) / [k0, k1) the token ranges of sequence b as the attention kernels clamp them, sq_b = q1 - q0, sk_b = k1 - k0:
+ *   k       key token k0 + j, j < sk_b, of args->k is rotated at position j and written to the same row of k_out
+ *   q       query token q0 + i, i < sq_b, of args->q is rotated at p_i = i + (sk_b - sq_b) - the p_i of the causal mask and of the window -
+ *           and written to the same row of q_out. Self-attention: p_i = i; every sequence restarts at 0.
+ * The table row read is clamp(pos, 0, rows - 1): the clamp acts on the negative p_i of rows that see no key. Layouts, tables and
+ * rounding are those of the cache's rotary calls above (the kernels share the rotation's text): bit for bit (x1 c - x2 s), (x2 c + x1 s)
+ * evaluated in fp32 step by step and rounded once. inverse = 1 applies the transpose rotation - the sines negated, which is exact:
+ * y1 = x1 c + x2 s, y2 = x2 c - x1 s - and is what the backward applies to dq / dk where fasn_bwd_varlen left them.
+ *
+ *   args      the block of fasn_fwd_varlen; args->q and args->k are the SOURCES. v, o and lse are not touched and may be NULL here; every
+ *             other member is checked as fasn_fwd_varlen checks it (one block serves both calls).
+ *   q_out / k_out   [1, heads, rows, D] views under the rules of q / k. Each may be its source exactly (same pointer, same strides: in
+ *             place); otherwise it must not overlap it.
+ *   rows nobody owns - tokens at or beyond cu[B] of their side - are neither read nor written, and no byte between the rows of a strided
+ *   view is written. Whatever the offset tables hold, no access leaves the operands and the tables.
+ *
+ * The launch runs ceil(Sq / 16) + ceil(Sk / 16) workgroups of 256 lanes - a function of the token rows alone, not of num_seqs or
+ * max_seqlen_*, and never of the offsets. fasn_varlen_rope_plan writes it as text, in the line format of fasn_launch_plan, with no HIP call.
+ * Codes, all before any HIP call: every rule and code of fasn_fwd_varlen that applies (all but those of v, o and lse), in its order;
+ * then rope, cos, sin, q_out or k_out NULL, rotary_dim outside [16, D] or not a multiple of 16, rows < max_seqlen_k, interleaved not 0 or 1,
+ * row_stride < rotary_dim / 2 FASN_EINVAL; table_dtype neither FASN_DTYPE_F32 nor args->dtype FASN_EDTYPE; a table base off 16 bytes or a
+ * row stride that is no multiple of 16 bytes FASN_EALIGN; q_out, then k_out, with the codes of q; then inverse not 0 or 1 FASN_EINVAL.
+ */
+int fasn_varlen_rope(const fasn_fwd_args* args, const fasn_varlen* varlen, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                     const fasn_view4* k_out, int32_t inverse, fasn_stream_t stream);
+int fasn_varlen_rope_plan(const fasn_fwd_args* args, const fasn_varlen* varlen, const fasn_kv_rope* rope, const fasn_view4* q_out,
+                          const fasn_view4* k_out, int32_t inverse, char* buf, size_t cap);
+
 #ifdef __cplusplus
 }
 #endif
