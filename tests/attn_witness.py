@@ -76,6 +76,24 @@ reference is computed once per distinct problem while EVERY (batch, head, row) o
 block served with the data of batch b + ub or head h + uh (a multiple of the period) is bit-identical to the right answer. The period is
 1 x 2 at the forward-only large grids; the cases with ub = B and uh = H (the small grids, dropout) witness every such mix-up.
 
+Witness C in fp32. The fp32 kernels (fasn_f32_kernels.h) keep P and dS in fp32 and round nothing to a 16-bit type: rounding points (2), (3),
+(5), (6), (7) and (8) shrink to fp32's own 2^-24 and what is left is the error of their sums, at most S + D terms each. The gates are the
+formulas above, unchanged, at u = unit(case, fp32) = (S + D) 2^-24 and ua = 0. tests/test_attnwitness_cpu.py shows on every fp32 case that
+an independent evaluation in torch fp32 - the online softmax and every sum over keys in tile order - stays at or below 0.5 of every gate
+(out, lse, dQ, dK, dV, dbias, dn: it is below 0.03), so no result's gate is left out in fp32.
+
+The instantiations (NEW). SHAPES' first part reaches every kernel template once; its second part, NEW, the modes of each template that
+the first leaves to tests/test_gpu_parity.py: the 8-wave forward kernels of large grids (D = 128 plain / causal, D = 64 bias / mask /
+bias + mask / bias + key padding), key padding at D = 32, 128, 256 and under causal at D = 64, dropout away from D = 64 and the backward
+of the 64-rows-per-wave dropout kernel, grouped K/V at D = 32 and 128, split-K under key padding, and the fp32 kernels at D = 64 and 128,
+in their mask / bias / dropout mode and with grouped K/V. Three shapes differ from the obvious ones because the dispatch does:
+  * at D = 128 the two-wave backward kernels have dropout instantiations and take every dropout call with one query head per K/V head;
+    the one-wave fasn_bwd_dq_kernel / fasn_bwd_dkdv_kernel run under dropout with grouped K/V only (launch_bwd_one, fasn_bwd_launch.h).
+    "d128 drop" and "d128 drop causal keypad" are therefore grouped (H = 8, Hkv = 2), and "... two-wave" are their ungrouped twins;
+  * a key-padding row of S = 4090 bytes is no run of aligned 4-byte vectors, takes the element loads and is never split: the split-K
+    key-padding cases have S = 4092. Their forward is the general (bias+mask) SPLIT=1 instantiation - split-K has no key-padding one;
+  * "d64 drop 64 rows bwd" needs ceil(L / 256) B H >= 512 under ub = B, uh = H: 512 distinct problems, witness A only.
+
 This is a helper module (no test is collected from it). tests/test_attnwitness_cpu.py is the test of these tests;
 tests/test_gpu_attnwitness.py runs the kernels."""
 import math
@@ -960,10 +978,58 @@ SHAPES = {
     "gqa decode regroup": Case(2, 8, 1, 420, 64, Hkv=2, nshape="float", bwd=False, want=("D=64,QB=1,plain",)),
     # the element-load kernels: a dense mask whose rows are no aligned vectors
     "element loads": Case(2, 4, 130, 200, 64, mask="misaligned", want=("element-load",)),
-    # fp32 kernels: A and B
-    "fp32": Case(2, 2, 130, 96, 32, dtypes=("fp32",), wit="AB", want=("fasn_f32_",)),
-    "fp32 causal": Case(2, 2, 130, 96, 32, causal=True, dtypes=("fp32",), nshape="BH", wit="AB", want=("fasn_f32_",)),
+    # fp32 kernels: A, B (the ladder) and C at u = unit(case, fp32)
+    "fp32": Case(2, 2, 130, 96, 32, dtypes=("fp32",), want=("fasn_f32_",)),
+    "fp32 causal": Case(2, 2, 130, 96, 32, causal=True, dtypes=("fp32",), nshape="BH", want=("fasn_f32_",)),
 }
+
+# ---------------------------------------------------------------- the instantiations: the modes of each family that the cases above leave out
+# (NEW names them: tests/test_attnwitness_cpu.py runs the emulation bound on every 16-bit one of them)
+RAGGED16 = [512, 300, 448, 77, 512, 5, 64, 511, 129, 512, 200, 333, 1, 450, 65, 512]
+_NEW = {
+    # D = 128, 8 waves: the kernel of every large D = 128 launch (512 row blocks of 256 rows and more)
+    "d128 8-wave plain": Case(16, 32, 256, 320, 128, ub=1, uh=2, bwd=False, want=("D=128,QB=1,plain", "NW=8")),
+    "d128 8-wave causal": Case(16, 32, 512, 512, 128, causal=True, ub=1, uh=2, bwd=False, want=("D=128,QB=1,causal", "NW=8")),
+    # D = 128: key padding (two-wave backward), with causal and grouped K/V; dropout keeps the one-wave backward
+    "d128 keypad": Case(4, 4, 300, 420, 128, mask="keypad", lens=[420, 300, 64, 5], want=("D=128", "keypad", "_ws_")),
+    "d128 keypad causal gqa": Case(2, 8, 300, 420, 128, Hkv=2, mask="keypad", lens=[420, 100], causal=True, want=("keypad", "GQA=1", "_ws_")),
+    # (the two-wave kernels have dropout instantiations of their own and take every dropout call with one query head per K/V head: only grouped
+    # K/V under dropout is left to the one-wave dQ and dK / dV kernels at this head dim, launch_bwd_one of fasn_bwd_launch.h)
+    "d128 drop": Case(2, 8, 300, 420, 128, Hkv=2, p=0.1, want=("D=128", "DROP=1", "GQA=1", "fasn_bwd_dq_kernel", "fasn_bwd_dkdv_kernel")),
+    "d128 drop causal keypad": Case(2, 8, 300, 420, 128, Hkv=2, p=0.25, causal=True, mask="keypad", lens=[420, 100], nshape="BH", want=("DROP=1", "keypad", "GQA=1", "fasn_bwd_dq_kernel", "fasn_bwd_dkdv_kernel")),
+    "d128 drop two-wave": Case(2, 4, 300, 420, 128, p=0.1, want=("D=128", "DROP=1", "fasn_bwd_dq_ws_kernel", "fasn_bwd_dkdv_ws_kernel")),
+    "d128 drop causal keypad two-wave": Case(2, 4, 300, 420, 128, p=0.25, causal=True, mask="keypad", lens=[420, 100], nshape="BH", want=("DROP=1", "keypad", "fasn_bwd_dq_ws_kernel", "fasn_bwd_dkdv_ws_kernel")),
+    # D = 256: key padding, the general instantiation (dense mask), dropout
+    "d256 keypad": Case(2, 4, 200, 200, 256, mask="keypad", lens=[200, 70], want=("_ws256_", "keypad")),
+    "d256 dense mask": Case(2, 4, 200, 200, 256, mask="dense", causal=True, nshape="BH", want=("_ws256_", "bias+mask")),
+    "d256 drop": Case(2, 4, 200, 200, 256, p=0.1, want=("_ws256_", "DROP=1")),
+    # D = 32
+    "d32 keypad causal": Case(2, 4, 300, 420, 32, mask="keypad", lens=[420, 100], causal=True, want=("D=32", "keypad")),
+    "d32 drop": Case(2, 4, 300, 420, 32, p=0.1, want=("D=32", "DROP=1")),
+    "d32 gqa": Case(2, 8, 300, 420, 32, Hkv=2, nshape="BH", want=("D=32", "GQA=1")),
+    # D = 64: key padding under causal; the 64-rows-per-wave dropout kernel with its backward
+    "d64 keypad causal": Case(2, 4, 300, 420, 64, mask="keypad", lens=[420, 100], causal=True, nshape="B1", want=("D=64,QB=1,keypad",)),
+    "d64 drop 64 rows bwd": Case(32, 16, 256, 192, 64, p=0.1, wit="A", want=("QB=2", "DROP=1", "_pipe_")),
+    # D = 64, 8 waves: the general kernels of large grids
+    "d64 8-wave bias": Case(8, 32, 512, 520, 64, bias="hls", ub=1, uh=2, bwd=False, wit="AC", want=("D=64,QB=2,bias,", "NW=8")),
+    "d64 8-wave dense mask": Case(8, 32, 512, 520, 64, mask="dense", ub=1, uh=2, bwd=False, want=("QB=2,mask", "NW=8")),
+    "d64 8-wave bias+mask": Case(8, 32, 512, 520, 64, bias="hls", mask="dense", ub=1, uh=2, bwd=False, wit="AC", want=("QB=2,bias+mask", "NW=8")),
+    "d64 8-wave bias keypad": Case(16, 32, 512, 512, 64, bias="hls", mask="keypad", lens=RAGGED16, ub=16, uh=2, bwd=False, wit="AC", want=("bias+keypad", "NW=8")),
+    "d64 8-wave bias causal": Case(16, 32, 512, 512, 64, bias="hls", causal=True, ub=1, uh=2, bwd=False, wit="AC", want=("QB=2", "NW=8")),
+    # split-K under key padding: the last splits see no key (S = 4092: a key-padding row of 4090 bytes is no run of aligned 4-byte vectors, and
+    # such a mask takes the element loads, which do not split)
+    "split keypad": Case(1, 16, 130, 4092, 64, mask="keypad", lens=[700], uh=2, want=("D=64,QB=1,bias+mask", "SPLIT=1", "keypad", "fasn_fwd_combine_kernel")),
+    "split keypad d128": Case(1, 16, 130, 4092, 128, mask="keypad", lens=[700], uh=2, want=("D=128", "SPLIT=1", "keypad", "fasn_fwd_combine_kernel", "_ws_")),
+    "split keypad d32": Case(1, 16, 130, 4092, 32, mask="keypad", lens=[700], uh=2, a_dtypes=("fp16",), want=("D=32", "SPLIT=1", "keypad", "fasn_fwd_combine_kernel")),
+    # fp32 kernels: the other head dims, the mask / bias / dropout mode, grouped K/V
+    "fp32 d64": Case(2, 2, 130, 96, 64, dtypes=("fp32",), want=("fasn_f32_", "D=64")),
+    "fp32 d128 causal": Case(1, 2, 130, 96, 128, causal=True, dtypes=("fp32",), want=("fasn_f32_", "D=128")),
+    "fp32 mask bias": Case(2, 2, 130, 96, 32, mask="dense", bias="bhls", dtypes=("fp32",), want=("fasn_f32_",)),
+    "fp32 drop": Case(2, 2, 130, 96, 32, p=0.1, dtypes=("fp32",), want=("fasn_f32_",)),
+    "fp32 gqa": Case(2, 4, 130, 96, 32, Hkv=2, dtypes=("fp32",), want=("fasn_f32_",)),
+}
+NEW = tuple(_NEW)
+SHAPES.update(_NEW)
 
 
 def seed_of(name):

@@ -28,6 +28,12 @@ Which witness is claimed to catch which mutant (dtype in brackets where only one
      other (length-paired) batch element
   11 bias of the neighbouring head                              C: out [fp16]
 
+Mutants 2, 4, 6 and 10 are shown caught again on cases of attn_witness.NEW, cut down to their distinct problems (distinct()): the
+key-padding words on "d128 keypad", the keep bits on "d128 drop" (one-wave backward, grouped) and "d128 drop two-wave", the tiles on
+"d64 8-wave dense mask", the K/V head map on "d32 gqa". Every 16-bit case of NEW passes the emulation bound below at both logit standard
+deviations; every fp32 case passes it with an fp32 evaluation in tile order (witness C in fp32); witness A's class-count condition and
+the rounded reference's pass through every gate are asserted for each case of NEW from the reference alone.
+
 The unmutated reference, rounded to the output type, passes every gate; an emulation of the kernels' arithmetic with the rounding
 points (1) to (8) of the derivation (attn_witness docstring; tests/attn_emulate.py in its absolute-score model - the seed, rounding point
 (9), is the business of tests/test_biaswitness_cpu.py) stays at or below 0.5 of every gate of witness C; the fp64 reference and its closed-form
@@ -101,10 +107,20 @@ class World:
 _WORLDS = {}
 
 
+def distinct(case):
+    """a case of attn_witness.SHAPES cut down to its ub x uh distinct problems (2 x 2 of them where it has more than 64): the reference, the
+    gates and the kernels' arithmetic are those of one (batch, head) problem and know nothing of the grid the problems are tiled over"""
+    if case.ub * case.uh > 64:
+        assert case.G == 1 and case.lens is None
+        return case.but(B=2, H=2, Hkv=2, ub=2, uh=2)
+    return case.but(B=case.ub, H=case.uh, Hkv=case.uhk)
+
+
 def world(case_name, wit, dtype, form=None, std=None):
+    """case_name: one of CASES, or one of attn_witness.SHAPES (its distinct problems)"""
     key = (case_name, wit, dtype, form, std)
     if key not in _WORLDS:
-        _WORLDS[key] = World(CASES[case_name], wit, dtype, form, std)
+        _WORLDS[key] = World(CASES[case_name] if case_name in CASES else distinct(aw.SHAPES[case_name]), wit, dtype, form, std)
     return _WORLDS[key]
 
 
@@ -409,6 +425,61 @@ def test_11_bias_of_the_neighbouring_head():
         assert_caught(w, w.ref(ubias=w.inp["ubias"].roll(1, 1)), ("out",), 10, f"11 C std {std} bias of the neighbouring head fp16", kv=False)
 
 
+# ---------------------------------------------------------------- the same mutants on the instantiations of attn_witness.NEW
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_new_key_padding_words_d128(dtype):
+    """mutant 10 on "d128 keypad" (four lengths: 420, 300, 64, 5)"""
+    w = world("d128 keypad", "A", dtype)
+    wt = aw.weights(w.case, w.inp["um"])
+    shifted = torch.cat([wt[..., aw.KT:], torch.zeros_like(wt[..., :aw.KT])], -1)
+    for wm, what in ((shifted, "of the neighbouring tile"), (wt.flip(0), "of the length-paired batch element")):
+        mut = w.ref(w=wm)
+        assert_caught(w, mut, ("exp(lse)",), 10, f"10 A d128 keypad: visibility words {what} {dtype} exp(lse)", kv=False)
+        assert_caught(w, mut, ("out Z",), 4, f"10 A d128 keypad: visibility words {what} {dtype} out Z", kv=False, exact=True)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("case_name", ["d128 drop", "d128 drop two-wave"])
+def test_new_keep_bits_d128(case_name, dtype):
+    """mutant 6 on the D = 128 dropout cases: the one-wave kernels' (grouped K/V) and the two-wave kernels'. The backward's integer gate
+    on dV Z runs in fp16, and in bf16 with one query head per K/V head (test_unmutated_reference_passes says why): claimed there"""
+    w = world(case_name, "A", dtype)
+    flip = w.keep.clone()
+    flip[:, :, 7::RB, 100] = 1 - flip[:, :, 7::RB, 100]
+    for keep, what in ((flip, "one keep bit flipped"), (w.keep.roll(1, 2), "keep bits of the neighbouring row"),
+                       (w.keep.roll(16, 3), "keep bits of the neighbouring 16-key group")):
+        mut = w.ref(keep=keep)
+        assert_caught(w, mut, ("out Z",), 4, f"6 A {case_name}: {what} {dtype} in the forward", kv=False, exact=True)
+        if dtype == "fp16":
+            assert_caught(w, mut, ("dV Z", "dV"), 4, f"6 A {case_name}: {what} {dtype} in the backward only", fwd=False, exact=True)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_new_tiles_d64_8wave(dtype):
+    """mutant 2 on "d64 8-wave dense mask" (forward only: a tile dropped, counted twice, the partial last tile taken as full)"""
+    w = world("d64 8-wave dense mask", "A", dtype)
+    for factor, what in ((0.0, "dropped"), (2.0, "counted twice")):
+        mut = w.ref(w=_tile_w(w.case, w.inp["um"], factor))
+        assert_caught(w, mut, ("exp(lse)",), 10, f"2 A d64 8-wave dense mask: tile {what} {dtype} exp(lse)", kv=False)
+        assert_caught(w, mut, ("out Z",), 4, f"2 A d64 8-wave dense mask: tile {what} {dtype} out Z", kv=False, exact=True)
+    mut = w.ref(un=w.inp["un"] + (aw.KT - w.case.S % aw.KT))
+    assert_caught(w, mut, ("exp(lse)",), 10, f"2 A d64 8-wave dense mask: last tile full {dtype}", kv=False)
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+def test_new_kv_heads_d32(dtype):
+    """mutant 4 on "d32 gqa": the forward's K/V head map, and dK / dV without one query head of the group"""
+    for wit, form, std, keys, thr in (("A", None, None, ("out Z",), 4), ("B", "code", None, ("out",), 10), ("C", None, 4, ("out",), 10)):
+        w = world("d32 gqa", wit, dtype, form, std)
+        assert_caught(w, w.ref(swap_kv=True), keys, thr, f"4 {wit} d32 gqa: neighbouring K/V head {dtype}", kv=False)
+    if dtype == "fp16":
+        w = world("d32 gqa", "A", dtype)
+        mut = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in w.clean.items()}
+        for key, full in (("dk", w.r["dK"]), ("dv", w.r["dV"])):
+            mut[key] = aw._tile(w.case, aw.group_sum(w.case, full) - full[:, ::w.case.G], "kv").to(w.dt)
+        assert_caught(w, mut, ("dV Z", "dV"), 4, f"4 A d32 gqa: dK / dV without one query head {dtype}", fwd=False)
+
+
 # ---------------------------------------------------------------- witness C's derivation: the kernels' arithmetic stays inside it
 from attn_emulate import emulate as _emulate   # noqa: E402  (shared with tests/test_biaswitness_cpu.py; here: the absolute-score model)
 
@@ -421,6 +492,55 @@ def test_c_gates_hold_for_the_kernels_arithmetic(case_name, dtype, std):
     rat = aw.judge_c(w.case, w.dt, _emulate(w), w.r, w.g)
     print(f"C {case_name} std {std} {dtype}: emulated kernel arithmetic at {rat} of the gates")
     assert rat.worst() <= 0.5, dict(rat)
+
+
+NEW16 = [n for n in aw.NEW if "fp32" not in aw.SHAPES[n].dtypes]
+FP32 = [n for n, c in aw.SHAPES.items() if c.dtypes == ("fp32",)]
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("name", NEW16)
+def test_c_gates_hold_for_the_new_instantiations(name, dtype):
+    """every 16-bit case of attn_witness.NEW, at both logit standard deviations, whatever witnesses it runs on the GPU (witness A reads the
+    same gates for dQ, dV, dn and dbias); the absolute-score model: no case of NEW draws a bias beyond N(0, 1)"""
+    assert dtype in aw.SHAPES[name].dtypes
+    for std in (4, 8):
+        w = world(name, "C", dtype, None, std)
+        rat = aw.judge_c(w.case, w.dt, _emulate(w), w.r, w.g)
+        print(f"C {name} std {std} {dtype}: emulated kernel arithmetic at {rat} of the gates")
+        assert rat.worst() <= 0.5, (std, dict(rat))
+
+
+@pytest.mark.parametrize("std", [4, 8])
+@pytest.mark.parametrize("name", FP32)
+def test_c_gates_hold_in_fp32(name, std):
+    """witness C in fp32, u = unit(case, fp32) = (S + D) 2^-24: an independent fp32 evaluation of the closed forms - torch fp32, the online
+    softmax and every sum over keys in tile order, no rounding point but fp32's own - stays at or below 0.5 of every gate"""
+    w = world(name, "C", "fp32", None, std)
+    assert w.u == (w.case.S + w.case.D) * 2.0 ** -24
+    rat = aw.judge_c(w.case, w.dt, _emulate(w), w.r, w.g)
+    print(f"C {name} std {std} fp32: fp32 evaluation at {rat} of the gates")
+    assert rat.worst() <= 0.5, dict(rat)
+    assert {"out", "lse", "dQ", "dK", "dV", "dn"} <= set(rat)
+
+
+@pytest.mark.parametrize("name", list(aw.NEW))
+def test_new_cases_on_the_reference_alone(name):
+    """witness A's class-count condition holds in every type the case runs A in, from the reference alone; the rounded reference passes the
+    gates of every witness the case runs"""
+    case = aw.SHAPES[name]
+    for dtype in case.a_dtypes if "A" in case.wit else ():
+        w = world(name, "A", dtype)
+        aw.condition_a(w.case, w.r, w.dt, w.p_eff)
+        rat = w.judge(w.clean)
+        assert "refused" not in rat and rat.worst() <= 0.8 + 1e-9, (dtype, dict(rat))
+    for dtype in case.dtypes:
+        for form in (aw.B_FORMS if "B" in case.wit else ()):
+            if form.startswith("code") and (dtype == "fp32" or not case.bwd):
+                continue
+            w = world(name, "B", dtype, form)
+            rat, kinds = aw.judge_b(w.case, form, w.dt, w.clean, w.r, w.g, w.inp)
+            assert rat.worst() <= 1.0 and (1 in kinds or form == "code_sink") and (2 in kinds or "sink" not in form), (dtype, form, dict(rat), kinds)
 
 
 # ---------------------------------------------------------------- the fp64 reference against the suite's oracle and autograd

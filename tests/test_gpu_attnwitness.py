@@ -7,7 +7,10 @@ Every expectation comes from the fp64 CPU reference of attn_witness.py and is co
      it decides which shapes run in fp16 only.
   B  |out - f V[t]| <= 2 u |V[t]| + 1e-30 where key t decides the row, |out| <= 1e-12 where the sink does, exactly 0 where nothing is
      visible; the bounded code also dV[t] = dO within 2 u |dO| and dQ, dK, dn = 0 up to the derived fp32 summation error.
-  C  every result within its first-order bound (attn_witness docstring), at logit standard deviations of 4 and 8.
+  C  every result within its first-order bound (attn_witness docstring), at logit standard deviations of 4 and 8; the fp32 cases at
+     u = unit(case, fp32).
+attn_witness.NEW adds the instantiations of each family that the first cases leave out (8-wave forwards, key padding and dropout at every
+head dim, grouped K/V at D = 32 / 128, split-K under key padding, the fp32 kernels' other head dims and modes).
 Each test prints its largest ratios before it asserts <= 1. tests/test_attnwitness_cpu.py shows what each gate catches and that an
 emulation of the kernels' arithmetic stays at or below 0.5 of witness C's gates."""
 import os

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
 """Launch tables of a build of libfasn.so over a grid of calls, without a GPU:  tools/plan_sweep.py [REPO_ROOT] [OUT.txt]
+(tools/plan_sweep.py [REPO_ROOT] --witness lists instead the flash_attention_n kernels that no witness plan file under tests/golden names.)
 One block per call: fasn_fwd_path, fasn_bwd_path, fasn_fwd_workspace_bytes and the fasn_launch_plan text of the forward, the forward with its
 workspace and the backward (dummy aligned addresses, as tests/baseline_plans.py; nothing is launched). Two trees launch the same kernels with
 the same grids iff their outputs are byte-identical - run it with REPO_ROOT = an export of the other commit, built. Also lists the kernels of
@@ -8,8 +9,9 @@ The token-packed sliding-window and rotary K/V-cache calls (fasn_kvvarlen_window
 library has them: every head dim and dtype, one split and several, with and without new rows; their kernels count as families that must be reached."""
 import ctypes, hashlib, itertools, os, re, sys
 
-ROOT = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = sys.argv[2] if len(sys.argv) > 2 else None
+ARGV = [a for a in sys.argv[1:] if not a.startswith("--")]
+ROOT = os.path.abspath(ARGV[0]) if ARGV else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+OUT = ARGV[1] if len(ARGV) > 1 else None
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests"), os.path.dirname(os.path.abspath(__file__))]
 import flash_attention_softmax_n_amd as pkg
 import baseline_plans
@@ -120,7 +122,35 @@ def kv_packed_calls():
         yield f"{hdr} rope", lib.fasn_kvvarlen_rope_append_plan, (block(False), rope, qo, None, None)
 
 
+def library_attention_kernels():
+    table = spill_map.kernel_table(os.path.join(ROOT, "flash-attention-softmax-n_amd", "libfasn.so"))
+    names = {re.sub(r"\(fasn::\w+(, fasn::\w+)*\)$", "", d).replace("void fasn::", "") for d in spill_map.demangle(list(table)).values()}
+    return names, {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel", n)}
+
+
+def witness_main():
+    """tools/plan_sweep.py [REPO_ROOT] --witness: the flash_attention_n kernels of the library (fasn_fwd_ / fasn_bwd_ / fasn_f32_) that no
+    witness plan file under tests/golden names (attn_witness_plans.txt, bias_witness_plans.txt and their siblings) - what the witnesses
+    do not reach. No sweep is run."""
+    gold = os.path.join(ROOT, "tests", "golden")
+    named = set()
+    files = sorted(f for f in os.listdir(gold) if f.endswith("witness_plans.txt"))
+    for f in files:
+        for line in open(os.path.join(gold, f)):
+            if line.startswith("    fasn_"):
+                named.add(line.strip().split(" grid=")[0])
+    _, att = library_attention_kernels()
+    att = {n for n in att if re.match(r"fasn_(fwd|bwd|f32)_", n)}
+    miss = sorted(att - named)
+    print(f"witness plan files {', '.join(files)}: {len(att & named)} of {len(att)} flash_attention_n kernels named, {len(miss)} not")
+    for n in miss:
+        print("   ", n)
+    return 0
+
+
 def main():
+    if "--witness" in sys.argv:
+        return witness_main()
     out, named, ncalls = [], set(), 0
     buf = ctypes.create_string_buffer(1 << 15)
     for hdr, plan, operands in kv_packed_calls():
@@ -143,9 +173,7 @@ def main():
     if OUT:
         open(OUT, "w").write(text)
     print(f"{ncalls} calls, {len(out)} lines, sha256 {hashlib.sha256(text.encode()).hexdigest()}")
-    table = spill_map.kernel_table(os.path.join(ROOT, "flash-attention-softmax-n_amd", "libfasn.so"))
-    names = {re.sub(r"\(fasn::\w+(, fasn::\w+)*\)$", "", d).replace("void fasn::", "") for d in spill_map.demangle(list(table)).values()}
-    att = {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel", n)}
+    names, att = library_attention_kernels()
     miss = sorted(att - named)
     print(f"library kernels {len(names)}, attention families {len(att)}, named by the sweep {len(att & named)}, named but not in the library {len(named - names)}, never named {len(miss)}")
     for n in miss:
