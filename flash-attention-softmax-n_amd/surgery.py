@@ -130,7 +130,28 @@ def _hf_attention(module: Module, query: torch.Tensor, key: torch.Tensor, value:
     Attention sinks (`s_aux`, GPT-OSS: one learned logit s_h per query head, a softmax column that is dropped after the softmax) are
     softmax_n with n_h = exp(s_h): they add to a surgery n (n_h = softmax_n_param + exp(s_h)) and their gradient reaches the sink
     parameter. Causality follows transformers' SDPA integration: the `is_causal` kwarg, else the module's `is_causal` attribute, and
-    only for more than one query row and no mask (a mask, when given, already holds the causal pattern)."""
+    only for more than one query row and no mask (a mask, when given, already holds the causal pattern).
+
+    Padding-free batches: with `cu_seq_lens_q` among the keywords - what `DataCollatorWithFlattening(
+    return_flash_attn_kwargs=True)` adds to a flattened [1, T] batch - the call goes to `flash_attention_n_varlen` on the
+    [T, H, E] views of query, key and value (no copy, no repeat_kv): `cu_seq_lens_q / _k` are the offsets (int32 on the query's device
+    goes in as the same object; int64 or CPU offsets are converted on the way), `max_length_q / _k` the bounds (Python ints as they are;
+    a 0-d tensor becomes int(x), ONE HOST READ per call - pass ints), `sliding_window` the call's `window`, causality the `is_causal`
+    kwarg, else the module's attribute (the conditions "more than one row" and "no mask" do not apply: the offsets replace the mask).
+    `attention_mask` is NOT READ on this route: the offsets must describe every token, which is the contract of transformers' own
+    flash-attention path. The result is the packed call's [T, H, E] output as [1, T, H, E], no transpose and no copy. The route needs
+    batch 1, fp16 / bf16, E == Ev in flash_attn._VARLEN_D, no active dropout, no head_mask, a sliding window only on a causal call
+    and, for fp16, |scaling| * log2(e) <= 8; anything else takes the dense route below exactly as without the packed keywords, after
+    one warning per reason and process. The device is not tested: on CPU tensors flash_attention_n_varlen raises its own error.
+    With HF_PACKED_FROM_POSITION_IDS set and no `cu_seq_lens_q`, the offsets are derived from a [1, T] `position_ids`
+    (_offsets_from_position_ids: one host read per forward, shared by the layers)."""
+    packed = _hf_packed_operands(module, query, key, value, scaling, dropout, kwargs)
+    if packed is not None:
+        from .flash_attn import flash_attention_n_varlen
+        cu_q, cu_k, max_q, max_k, n, is_causal, window = packed
+        out = flash_attention_n_varlen(query[0].transpose(0, 1), key[0].transpose(0, 1), value[0].transpose(0, 1), cu_q, max_q, cu_k, max_k,
+                                       softmax_n_param=n, scale=scaling, is_causal=is_causal, window=window)
+        return out.unsqueeze(0), None
     from .flash_attn import flash_attention_n
     n = float(getattr(module, "softmax_n_param", 0.0))
     s_aux = kwargs.get("s_aux")
@@ -158,6 +179,129 @@ def _hf_attention(module: Module, query: torch.Tensor, key: torch.Tensor, value:
     out = flash_attention_n(query, key, value, softmax_n_param=n, scale=scaling, dropout_p=dropout if module.training else 0.0,
                             attn_mask=mask, attn_bias=bias, is_causal=is_causal)
     return out.transpose(1, 2).contiguous(), None
+
+
+# ---- padding-free (packed) batches: transformers' flash-attention keywords -> flash_attention_n_varlen
+# transformers hands every layer `position_ids`, so deriving the offsets from them cannot be automatic: it would change the bits of
+# every existing batch-1 call and add a host read. Set this to True to route a [1, T] batch whose `position_ids` restart (and that comes
+# without `cu_seq_lens_q`) through the packed call: a sequence starts at token 0 and wherever a position is not its predecessor's + 1.
+HF_PACKED_FROM_POSITION_IDS = False
+
+_PACKED_WARNED = set()      # the reasons a packed batch took the dense route, each logged once per process
+_POSITION_IDS_CACHE = None  # (weakref of the position_ids tensor, its _version, device, (cu, max_len)): the layers of one forward share it
+
+
+def _packed_fallback(reason: str) -> None:
+    if reason not in _PACKED_WARNED:
+        _PACKED_WARNED.add(reason)
+        log.warning("packed-batch keywords (cu_seq_lens_q / position_ids) are not routed to flash_attention_n_varlen: %s; the call takes "
+                    "the dense route, where only attention_mask separates the documents", reason)
+
+
+def _packed_refusal(module, query, key, value, scaling, dropout, kwargs) -> Optional[str]:
+    """why this call cannot go to flash_attention_n_varlen, or None (the conditions of the packed route, nothing read on the host)"""
+    from . import flash_attn
+    if query.dim() != 4 or query.shape[0] != 1:
+        return "query is not [1, H, T, E] (batch greater than 1)"
+    if key.dim() != 4 or value.dim() != 4 or key.shape[0] != 1 or value.shape[0] != 1:
+        return "key / value are not [1, Hkv, T, E] (batch greater than 1)"
+    if query.dtype not in (torch.float16, torch.bfloat16):
+        return f"dtype {query.dtype} (the packed kernels serve float16 and bfloat16)"
+    E, Ev = query.shape[-1], value.shape[-1]
+    if E != Ev or key.shape[-1] != E or E not in flash_attn._VARLEN_D:
+        return f"head dim {E} / {Ev} (the packed kernels serve E == Ev in {list(flash_attn._VARLEN_D)})"
+    if dropout and module.training:
+        return "attention dropout in training (there is no dropout on packed operands)"
+    if kwargs.get("head_mask") is not None:
+        return "head_mask is given"
+    window = kwargs.get("sliding_window")
+    if window is not None:
+        if isinstance(window, bool) or not isinstance(window, int) or window < 1:
+            return f"sliding_window {window!r} is not an int >= 1"
+        if not _packed_is_causal(module, kwargs):
+            return "sliding_window on a call that is not causal (the packed window is causal)"
+    if query.dtype == torch.float16:
+        scale = E ** -0.5 if scaling is None else abs(float(scaling))
+        # (in fp32, as flash_attention_n_varlen forms it: a scale within a rounding of the limit gets the same answer here and there)
+        if float(torch.tensor(scale, dtype=torch.float32) * torch.tensor(flash_attn._VARLEN_LOG2E, dtype=torch.float32)) > flash_attn._VARLEN_F16_MAX_PRESCALE:
+            return f"float16 with |scaling| = {scale:g} (|scaling| * log2(e) must be <= {flash_attn._VARLEN_F16_MAX_PRESCALE:g})"
+    return None
+
+
+def _packed_is_causal(module, kwargs) -> bool:
+    is_causal = kwargs.get("is_causal")
+    return bool(getattr(module, "is_causal", False) if is_causal is None else is_causal)
+
+
+def _packed_offsets(cu: torch.Tensor, device) -> torch.Tensor:
+    """an offset table as the packed call reads it: int32 on the query's device (such a tensor is returned as it is)"""
+    if cu.device != device:
+        cu = cu.to(device)
+    return cu if cu.dtype == torch.int32 else cu.to(torch.int32)
+
+
+def _offsets_from_position_ids(position_ids: torch.Tensor):
+    """(cu_seqlens int32 [B + 1] on position_ids' device, longest length as a Python int) of a flattened [1, T] batch, by the boundary
+    rule of transformers' packed masks: a sequence starts at token 0 and wherever a position is not its predecessor's plus one.
+    Torch ops on the device and ONE host read (B and the longest length together)."""
+    pos = position_ids.reshape(-1)
+    T = pos.numel()
+    start = torch.ones(T, dtype=torch.bool, device=pos.device)
+    start[1:] = pos[1:] != pos[:-1] + 1
+    at = torch.arange(T + 1, device=pos.device)
+    # the starts in order, then T for every token that starts nothing and once more as cu[B]: no nonzero(), whose size is a host read
+    table = torch.where(torch.cat([start, start.new_zeros(1)]), at, at.new_full((), T)).sort().values
+    B, longest = torch.stack([start.sum(), (table[1:] - table[:-1]).max()]).tolist()
+    return table[:B + 1].to(torch.int32), int(longest)
+
+
+def _cached_offsets_from_position_ids(position_ids: torch.Tensor, device):
+    """_offsets_from_position_ids once per tensor OBJECT and version (a weakref compared with `is`, plus `_version`; never an address -
+    see _as_key_padding_mask): the layers of one forward get the same position_ids and share the derivation and its host read."""
+    global _POSITION_IDS_CACHE
+    import weakref
+    c = _POSITION_IDS_CACHE
+    if c is not None and c[0]() is position_ids and c[1] == position_ids._version and c[2] == device:
+        return c[3]
+    cu, longest = _offsets_from_position_ids(position_ids)
+    got = (_packed_offsets(cu, device), longest)
+    _POSITION_IDS_CACHE = (weakref.ref(position_ids), position_ids._version, device, got)
+    return got
+
+
+def _hf_packed_operands(module, query, key, value, scaling, dropout, kwargs):
+    """(cu_q, cu_k, max_q, max_k, n, is_causal, window) of the packed route of _hf_attention, or None: not a packed batch, or one of the
+    route's conditions fails (logged once per reason)."""
+    cu_q = kwargs.get("cu_seq_lens_q")
+    position_ids = None
+    if cu_q is None:
+        position_ids = kwargs.get("position_ids") if HF_PACKED_FROM_POSITION_IDS else None
+        if (not torch.is_tensor(position_ids) or query.dim() != 4 or key.dim() != 4
+                or tuple(position_ids.shape) != (1, query.shape[2]) or key.shape[2] != query.shape[2]):
+            return None
+    reason = _packed_refusal(module, query, key, value, scaling, dropout, kwargs)
+    if reason is not None:
+        _packed_fallback(reason)
+        return None
+    if cu_q is None:
+        cu_q, max_q = _cached_offsets_from_position_ids(position_ids, query.device)
+        cu_k, max_k = cu_q, max_q
+    else:
+        given_k = kwargs.get("cu_seq_lens_k")
+        cu_q_in, cu_q = cu_q, _packed_offsets(cu_q, query.device)
+        cu_k = cu_q if given_k is None or given_k is cu_q_in else _packed_offsets(given_k, query.device)
+        max_q, max_k = kwargs.get("max_length_q"), kwargs.get("max_length_k")
+        if max_q is None:
+            raise ValueError("cu_seq_lens_q came without max_length_q: the packed call needs a bound of the sequence lengths (the collator "
+                             "passes both, as transformers' flash-attention path requires)")
+        max_q = int(max_q)   # a Python int as it is; a 0-d tensor: one host read
+        max_k = max_q if max_k is None else int(max_k)
+    n = float(getattr(module, "softmax_n_param", 0.0))
+    s_aux = kwargs.get("s_aux")
+    if s_aux is not None:
+        n = torch.exp(s_aux.float()) + n   # [H]: one n per query head
+    window = kwargs.get("sliding_window")
+    return cu_q, cu_k, max_q, max_k, n, _packed_is_causal(module, kwargs), None if window is None else int(window)
 
 
 # transformers' extended attention mask is (1 - mask) * finfo.min: 0 / min for the binary masks tokenizers produce. A float mask
