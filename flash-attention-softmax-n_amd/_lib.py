@@ -50,6 +50,7 @@ EXPORTS = (
     "fasn_fwd_varlen", "fasn_bwd_varlen", "fasn_varlen_plan",
     "fasn_fwd_varlen_window", "fasn_bwd_varlen_window", "fasn_varlen_window_plan",
     "fasn_varlen_rope", "fasn_varlen_rope_plan",
+    "fasn_fwd_shared_prefix_workspace_bytes", "fasn_fwd_shared_prefix", "fasn_shared_prefix_plan",
 )
 
 
@@ -168,6 +169,12 @@ class KvTreeCommit(Structure):
     ]
 
 
+class SharedPrefix(Structure):
+    """fasn_shared_prefix (include/fasn.h): the shared prefix of fasn_fwd_shared_prefix - its length (one int32) and its page ids
+    ([max_prefix_pages] int32), both in device memory; reserved = 0"""
+    _fields_ = [("prefix_len", c_void_p), ("prefix_table", c_void_p), ("max_prefix_pages", c_int32), ("reserved", c_int32)]
+
+
 class FasnError(RuntimeError):
     pass
 
@@ -254,6 +261,15 @@ def _kv_call_bindings():
     yield "fasn_kv_append_plan", c_int32, append + text
 
 
+def _shared_prefix_bindings():
+    """(name, restype, argtypes) of the three entry points of the shared-prefix decode: a decode block and the prefix operand. They are
+    no part of the K/V-cache description above - the operand belongs to no operand set - and have a list of their own."""
+    head = [POINTER(KvCacheArgs), POINTER(SharedPrefix)]
+    yield "fasn_fwd_shared_prefix_workspace_bytes", c_size_t, head
+    yield "fasn_fwd_shared_prefix", c_int32, head + [c_void_p, c_size_t, c_void_p]
+    yield "fasn_shared_prefix_plan", c_int32, head + [c_char_p, c_size_t]
+
+
 def kv_call(args, fp8=None, tree=None, window=None, alibi=None):
     """the KvCall of the block `args` under the operands that are not None. The block and the operands live as long as the KvCall does."""
     c = KvCall(kind=_KV_KIND[kv_stem(args)], reserved=0, block=ctypes.cast(ctypes.pointer(args), c_void_p))
@@ -332,7 +348,7 @@ def load():
     lib.fasn_varlen_rope.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvRope), POINTER(View4), POINTER(View4), c_int32, c_void_p]
     lib.fasn_varlen_rope_plan.restype = c_int32
     lib.fasn_varlen_rope_plan.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvRope), POINTER(View4), POINTER(View4), c_int32, c_char_p, c_size_t]
-    for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings()):
+    for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings(), *_shared_prefix_bindings()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     ver = lib.fasn_abi_version()
@@ -505,6 +521,12 @@ def kvrope_plan(args, rope, q_out, k_new=None, v_new=None):
     """The one launch of fasn_kvcache_rope_append (`args` a KvCacheArgs), fasn_kvprefill_rope_append (a KvPrefillArgs) or
     fasn_kvvarlen_rope_append (a KvVarlenArgs) under `rope` (a KvRope), as launch_plan returns it. Nothing is launched."""
     return _kv_append_plan(args, q_out, k_new, v_new, rope=rope)
+
+
+def shared_prefix_plan(args, prefix):
+    """The three launches of fasn_fwd_shared_prefix for `args` (a KvCacheArgs) behind `prefix` (a SharedPrefix) - the prefix pass, the
+    suffix pass, the combine - as launch_plan returns them. Nothing is launched."""
+    return _plan("fasn_shared_prefix_plan", args, prefix)
 
 
 def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):

@@ -11,13 +11,22 @@
 // c8 under FASN_KV_FP8, p.c otherwise (a macro, so that the kernels that were there keep their tokens).
 // FASN_KV_FP8 is orthogonal to FASN_KV_TREE in the same way: both at 1 (fasn_kvfp8.h) is the token-tree sibling over the FP8 cache - the tree's
 // tile range, full-tile test and per-lane visibility word around the FP8 staging and widening, FASN_KV_SC in both arms of the masked loop.
+// FASN_KV_SHARED = 1 / 2 (fasn_kvshared.h, with the other four at 0; undefined counts as 0) are the two passes of the shared-prefix call:
+// 1 is the prefix pass - a workgroup is (K/V head, 128-row block of the row space b * R + r of ALL batch elements, split), walks the tiles of
+// the prefix pages [0, ceil(P / 64)), every lane carries the b of its own row and the limit min(P - 1, its base limit), no sink - and 2 the
+// suffix pass - the base walk over the tiles [P / 64, ceil(len_b / 64)) of the batch element's own pages, keys below P hidden in the first
+// tile. With FASN_KV_SHARED == 0 the eight kernels above are what they were.
 #if FASN_KV_FP8
 #define FASN_KV_SC c8
 #else
 #define FASN_KV_SC p.c
 #endif
 template <typename Tag, int D>
-#if FASN_KV_FP8 && FASN_KV_TREE
+#if FASN_KV_SHARED == 1
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvshared_prefix_kernel(const KvParams p, const KvShared sh) {
+#elif FASN_KV_SHARED == 2
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvshared_suffix_kernel(const KvParams p, const KvShared sh) {
+#elif FASN_KV_FP8 && FASN_KV_TREE
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_tree_kernel(const KvParams p, const KvFp8 f8, const KvTree tree) {
 #elif FASN_KV_FP8 && FASN_KV_WINDOW
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_window_kernel(const KvParams p, const KvFp8 f8, const KvWindow win) {
@@ -68,14 +77,35 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     const int hi = lane >> 5;
 
     const int wg = (int)blockIdx.x;
+#if FASN_KV_SHARED == 1
+    // (K/V head, row block, split); the lane's row of the row space rho = b * R + r decides its b. `len` is what the walk covers: P
+    const int split = wg % sh.nsplit;
+    const int bk = wg / sh.nsplit;         // hkv * nrb + row block
+    const int hkv = bk / sh.nrb;
+    const int rho = (bk - hkv * sh.nrb) * KVS_ROWS + (tid >> 6) * 32 + (tid & 31);
+    const int rows_all = p.B * p.R;
+    const int b = rho < rows_all ? rho / p.R : 0;
+    const int len = kvs_prefix_len(sh);
+#else
     const int split = wg % p.nsplit;
     const int bk = wg / p.nsplit;          // b * Hkv + hkv
     const int b = bk / p.Hkv, hkv = bk % p.Hkv;
 
     // ---- this split's tile range, from the length in device memory
     const int len = kv_len(p, b);
+#endif
     const int tiles_b = (len + KV_KT - 1) / KV_KT;
-#if FASN_KV_TREE
+#if FASN_KV_SHARED == 1
+    const int tps = (tiles_b + sh.nsplit - 1) / sh.nsplit;
+    const int t0 = min(split * tps, tiles_b);
+#elif FASN_KV_SHARED == 2
+    // the walk starts at the tile that holds key P: the base call's split rule over [tlo, tiles_b), the base call's ranges at P = 0. Tiles
+    // below tlo get no request and no table read: their slots may be unset
+    const int P = kvs_prefix_len(sh);
+    const int tlo = min(P / KV_KT, tiles_b);
+    const int tps = (tiles_b - tlo + p.nsplit - 1) / p.nsplit;
+    const int t0 = min(tlo + split * tps, tiles_b);
+#elif FASN_KV_TREE
     // node i sits in cache row base + i; the walk starts at the tile of the first key a node at depth 0 can see under the window (no
     // window: tree.w is beyond the capacity and tlo is 0, the base kernel's split of [0, tiles_b))
     const int base = len - p.Sq;
@@ -95,6 +125,16 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     const int t1 = min(t0 + tps, tiles_b);
 
     // ---- the lane's row: query head of the group, position, softmax_n, causal limit
+#if FASN_KV_SHARED == 1
+    const bool row_ok = rho < rows_all;
+    const int r_b = row_ok ? rho - b * p.R : 0;   // the row inside the lane's own batch element
+    const int g = r_b / p.Sq;
+    const int pos = r_b - g * p.Sq;
+    const int h = hkv * p.G + g;
+    // the lane's own len_b: a vector load, retired in front of the tile loop (a lane without a row reads nothing)
+    int len_l = 0;
+    if (row_ok) len_l = p.seqlens[b];
+#else
     const int row = wave * 32 + l31;
     const bool row_ok = row < p.R;
     const int g = row_ok ? row / p.Sq : 0;
@@ -102,13 +142,18 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     const int h = hkv * p.G + g;
     float n_row = p.n;
     if (p.nt != nullptr) n_row = p.nt[b * p.nsb + h * p.nsh];
+#endif
 #if FASN_KV_ALIBI
     float nslope2 = al.slopes[b * al.sb + h * al.sh] * -kLog2e;   // -slope * log2(e) of the row's query head: lane-private, read once, like n
 #endif
 #if FASN_KV_FP8
     float c8 = p.c * f8.ks[b * f8.ksb + hkv * f8.ksh];   // k_scale acts on the fp32 scores: one uniform load in front of the tile loop, like n
 #endif
+#if FASN_KV_SHARED == 1
+    const bool wave_rows = (bk - hkv * sh.nrb) * KVS_ROWS + wave * 32 < rows_all;   // the last row block may be mostly idle
+#else
     const bool wave_rows = wave * 32 < p.R;   // a wave without rows only helps staging
+#endif
 
     vec8 qf[KS];
     {
@@ -145,12 +190,21 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     // Page ids are wave-uniform and the table does not change while the kernel runs: read through the constant address space they are
     // scalar loads whose wait the compiler places at the first use - the NEXT tile's request - instead of vector loads whose wait
     // would drain the K/V requests just issued. Entries of tiles outside the range are never read.
+#if FASN_KV_SHARED == 1
+    // the prefix pages: one table for every batch element; entries at or beyond ceil(P / page_size) belong to no tile of the range
+    const __attribute__((address_space(4))) int* const bt_row = (const __attribute__((address_space(4))) int*)sh.ptab;
+    auto page_of = [&](int tile, int slot) -> int {
+        if (tile >= t1) return 0;
+        return bt_row[slot];
+    };
+#else
     const __attribute__((address_space(4))) int* const bt_row = (const __attribute__((address_space(4))) int*)(p.bt + (int64_t)b * p.bts);
     const bool paged = p.bt != nullptr;
     auto page_of = [&](int tile, int slot) -> int {
         if (tile >= t1) return 0;
         return paged ? bt_row[slot] : b;
     };
+#endif
     int u_page = page_of(u, u_slot);
     auto request_next = [&](int buf) {
         const int nvis = u < t1 ? min(KV_KT, len - u * KV_KT) : 0;   // rows of the tile below len_b (>= 1 inside the range)
@@ -159,11 +213,23 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
         const uint32_t kbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.krs * EB + SROWB) : 0u;
         const uint32_t vbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.vrs * EB + SROWB) : 0u;
         const u32x4 krw = make_rsrc_words(kpool + koff, kbytes), vrw = make_rsrc_words(vpool + voff, vbytes);
+#if FASN_KV_SHARED == 2
+        // the tile that holds key P: its rows below P are the batch element's own rows of a partially shared page and may hold anything.
+        // Their lanes ask beyond every range a descriptor can have (kv_build: a tile spans less than 2^31 bytes) and get zeros
+        const int lo = u == tlo ? P - tlo * KV_KT : 0;
+#pragma unroll
+        for (int i = 0; i < SNLD; ++i) {
+            const bool below = (tid + i * NT) / SCPR < lo;
+            kv_dma16(krw, __builtin_amdgcn_readfirstlane(ldsK_w + buf * STILEB + i * NT * 16), below ? 0x80000000u : kvoff[i]);
+            kv_dma16(vrw, __builtin_amdgcn_readfirstlane(ldsV_w + buf * STILEB + i * NT * 16), below ? 0x80000000u : vvoff[i]);
+        }
+#else
 #pragma unroll
         for (int i = 0; i < SNLD; ++i) {
             kv_dma16(krw, __builtin_amdgcn_readfirstlane(ldsK_w + buf * STILEB + i * NT * 16), kvoff[i]);
             kv_dma16(vrw, __builtin_amdgcn_readfirstlane(ldsV_w + buf * STILEB + i * NT * 16), vvoff[i]);
         }
+#endif
         ++u;
         if (++u_tip == p.tpp) {
             u_tip = 0;
@@ -173,22 +239,34 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     };
 
     // ---- online-softmax state of the row (log2 domain); the sink (+n) belongs to split 0
+#if FASN_KV_SHARED == 1
+    float m_run = -INFINITY;   // (no sink here: it belongs to split 0 of the suffix pass)
+    float l_run = 0.f;
+#else
     const bool sink = n_row > 0.f && split == 0;
     float m_run = sink ? 0.f : -INFINITY;
     float l_run = (sink && hi == 0) ? n_row : 0.f;   // the two half-lanes' partial sums are added at the end
+#endif
     f32x16 oacc[DB];
 #pragma unroll
     for (int d = 0; d < DB; ++d)
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
-#if !FASN_KV_TREE
+#if FASN_KV_SHARED == 1
+    // last visible key of the row: the base call's limit under the lane's own len_b, and below P
+    len_l = min(max(len_l + p.seqlen_add, 0), p.capacity);
+    int vis = !row_ok ? -1 : min(len - 1, p.causal ? pos + len_l - p.Sq : len_l - 1);
+    retire_loads(vis);
+#elif !FASN_KV_TREE
     const int vis = !row_ok ? -1 : (p.causal ? pos + len - p.Sq : len - 1);   // last visible key of the row
     const int all_vis = p.causal ? len - p.Sq : len - 1;                          // every row sees the keys up to here
 #endif
 
 #pragma unroll
     for (int s = 0; s < KS; ++s) retire_loads(qf[s]);
+#if FASN_KV_SHARED != 1
     retire_loads(n_row);
+#endif
 #if FASN_KV_ALIBI
     retire_loads(nslope2);
     const int qpos = pos + len - p.Sq;   // absolute position of the row's query
@@ -245,7 +323,13 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
             // the bias is part of the score before the maximum is taken; k0 is the absolute key index in every split
             const float dk0 = (float)(k0 + 4 * hi - qpos);
 #endif
-#if FASN_KV_TREE
+#if FASN_KV_SHARED == 1
+            // every lane that has a row sees the whole tile (the rows of a wave belong to several batch elements: a vote, wave-uniform)
+            if (__all(!row_ok || k0 + KV_KT - 1 <= vis)) {
+#elif FASN_KV_SHARED == 2
+            // ... and the tile holds no key below P
+            if (k0 + KV_KT - 1 <= all_vis && k0 >= P) {
+#elif FASN_KV_TREE
             // the tile lies wholly in the prefix and wholly inside the window of the deepest position a node can have, base + Sq - 1:
             // conservative for every depth, every row sees the whole tile
             if (k0 + KV_KT - 1 < base && k0 > len - 1 - tree.w) {
@@ -295,7 +379,9 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-#if FASN_KV_TREE
+#if FASN_KV_SHARED == 2
+                        const float y = key <= vis && key >= P ? sacc[kb][r] * FASN_KV_SC : -INFINITY;
+#elif FASN_KV_TREE
                         const float y = ((vm >> (kb * 32 + (r & 3) + 8 * (r >> 2))) & 1ull) != 0ull ? sacc[kb][r] * FASN_KV_SC : -INFINITY;
 #elif FASN_KV_ALIBI
                         const float y = key <= vis ? __builtin_fmaf(sacc[kb][r], p.c, kv_alibi_term(nslope2, dk0, kb, r)) : -INFINITY;
@@ -350,8 +436,15 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     // ---- partial result of this key range: un-normalised accumulator + (m, l) per row
+#if FASN_KV_SHARED == 1
+    // the prefix partials: [Hkv][nsplit][B * R rows of the row space][D] and [...][2]; `row` becomes the row of that space
+    float* po = sh.part_o + ((int64_t)hkv * sh.nsplit + split) * rows_all * D;
+    float* pml = sh.part_ml + ((int64_t)hkv * sh.nsplit + split) * rows_all * 2;
+    const int row = rho;
+#else
     float* po = p.part_o + ((int64_t)bk * p.nsplit + split) * p.R * D;
     float* pml = p.part_ml + ((int64_t)bk * p.nsplit + split) * p.R * 2;
+#endif
     const float l_tot = sum_across_halves(l_run);
     if (row_ok) {
         if (hi == 0) {

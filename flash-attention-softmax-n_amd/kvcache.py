@@ -26,6 +26,8 @@ flash_attention_n_kvcache_fp8_tree verifies a tree of draft tokens on that cache
 flash_attention_n_kvcache_fp8_tree_commit moves the accepted path's code rows behind the prefix (fasn_kvcache_fp8_tree_commit).
 flash_attention_n_kvcache_fp8_varlen, _fp8_varlen_window and _fp8_varlen_rope are the token-packed calls over that cache: the packed FP8
 operand sets have no named entry points and go through the operand-set calls (fasn_kv_forward, fasn_kv_append: a fasn_kv_call).
+flash_attention_n_kvcache_shared_prefix is the decode call for a batch behind ONE shared prefix (fasn_fwd_shared_prefix): `prefix_table` names
+the prefix pages and `prefix_len` - on the device - how many keys they hold; the prefix is attended to once per K/V head for all sequences.
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -35,7 +37,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import AlibiSlopes, KvCacheArgs, KvFp8, KvPrefillArgs, KvRope, KvTree, KvTreeCommit, KvVarlenArgs, KvWindow
+from ._lib import AlibiSlopes, KvCacheArgs, KvFp8, KvPrefillArgs, KvRope, KvTree, KvTreeCommit, KvVarlenArgs, KvWindow, SharedPrefix
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
@@ -482,6 +484,87 @@ def flash_attention_n_kvcache(
     """
     return _run(_prepare("flash_attention_n_kvcache", "kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new,
                          softmax_n_param, scale, is_causal, return_lse, alibi_slopes=alibi_slopes))
+
+
+_SHARED_PREFIX_HEAD_DIMS = (64, 128)   # the head dims the shared-prefix kernels are built for
+
+
+def flash_attention_n_kvcache_shared_prefix(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        block_table: Tensor,
+        prefix_table: Tensor,
+        prefix_len: Tensor,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """flash_attention_n_kvcache for a batch that decodes behind ONE SHARED PREFIX (a system prompt, a few-shot header, N samples of one
+    prompt), on MI355X: the prefix pages are attended to once per K/V head for the rows of all batch elements - packed into full 128-row
+    blocks - each batch element's own keys as flash_attention_n_kvcache walks them, and the two are merged (fasn_fwd_shared_prefix).
+
+    With P = clamp(prefix_len, 0, min(max_prefix_pages * page_size, capacity)), computed in the kernels, every batch element b has the
+    virtual cache whose key row j < P is row j % page_size of page prefix_table[j // page_size] and whose key row j >= P is the row
+    block_table[b] names. The result is exactly flash_attention_n_kvcache's on that cache: len_b, the positions, causal visibility,
+    n (counted once per row) and lse do not depend on P. A batch element shorter than the prefix sees prefix keys up to its own limit; P
+    need not be a multiple of the page size (a partially shared last page, copy on write). `query`, the paged 16-bit caches,
+    `cache_seqlens`, `block_table`, `k_new` / `v_new`, `softmax_n_param`, `scale`, `is_causal`, `return_lse`, alignment rules and refusals
+    are those of flash_attention_n_kvcache, with (H // Hkv) * Sq <= 128. What differs:
+
+    :param block_table: required (a shared prefix is a set of pages; a dense cache is refused). Slots wholly below P are never read.
+    :param prefix_table: contiguous int32 [max_prefix_pages] on the device: the page ids of the shared prefix, in order.
+    :param prefix_len: int32 tensor of ONE element on the device; never read on the host, so one captured graph serves every step and
+                  every prefix length.
+    :param k_new, v_new: appended to the batch element's OWN pages at cache_seqlens[b] + i, as in flash_attention_n_kvcache; rows that
+                  land below P are never read.
+    Head dims 64 and 128, fp16 / bf16 caches; an FP8 cache, ALiBi, a window, rotary embedding, a token tree and packed queries are not
+    served by this call.
+
+    Memory contract. For keys below P, block_table[b] entries and the batch element's own cache rows are never read. Prefix-page rows at
+    or beyond P and prefix_table entries at or beyond ceil(P / page_size) are never read. Rows at or beyond len_b may hold anything.
+    """
+    fn = "flash_attention_n_kvcache_shared_prefix"
+    if block_table is None:
+        raise ValueError(f"{fn}: a dense cache (block_table=None) is not supported: a shared prefix is a set of pages that several block "
+                         "tables name (paged caches only)")
+    if isinstance(k_cache, Tensor) and k_cache.dtype == torch.float8_e4m3fn:
+        raise TypeError(f"{fn}: a float8 cache is not supported (fp16 and bf16 caches only; the FP8 call is flash_attention_n_kvcache_fp8, "
+                        "without a shared prefix)")
+    if query.dim() == 4 and query.shape[3] in _KV_HEAD_DIMS and query.shape[3] not in _SHARED_PREFIX_HEAD_DIMS:
+        raise ValueError(f"{fn}: head dim {query.shape[3]} is not supported behind a shared prefix (supported: {_SHARED_PREFIX_HEAD_DIMS}; "
+                         "32 and 256 have the kernels of flash_attention_n_kvcache only)")
+    if (not isinstance(prefix_table, Tensor) or prefix_table.dtype != torch.int32 or prefix_table.dim() != 1 or prefix_table.shape[0] < 1
+            or not prefix_table.is_contiguous()):
+        got = f"{prefix_table.dtype} {tuple(prefix_table.shape)}" if isinstance(prefix_table, Tensor) else type(prefix_table).__name__
+        raise ValueError(f"{fn}: prefix_table must be a contiguous int32 tensor of shape [max_prefix_pages] on the device (at least one "
+                         f"page); got {got}")
+    if not isinstance(prefix_len, Tensor) or prefix_len.dtype != torch.int32 or prefix_len.numel() != 1:
+        got = f"{prefix_len.dtype} {tuple(prefix_len.shape)}" if isinstance(prefix_len, Tensor) else type(prefix_len).__name__
+        raise ValueError(f"{fn}: prefix_len must be an int32 tensor of one element on the device (it is read by the kernels, never on "
+                         f"the host; not a Python int); got {got}")
+    for name, t in (("prefix_table", prefix_table), ("prefix_len", prefix_len)):
+        if t.device != query.device:
+            raise RuntimeError(f"{name} is on {t.device}, query on {query.device}: every operand must live on the query's device "
+                               "(the prefix length and its page ids are read by the kernels, never on the host)")
+    c = _prepare(fn, "kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
+                 return_lse)
+    lib = _lib.load()
+    prefix = SharedPrefix(prefix_len=prefix_len.data_ptr(), prefix_table=prefix_table.data_ptr(),
+                          max_prefix_pages=min(prefix_table.shape[0], _INT_MAX), reserved=0)
+
+    def launch():
+        stream = _stream_ptr(c.dev)
+        _append(lib, c, stream)
+        ws_bytes = lib.fasn_fwd_shared_prefix_workspace_bytes(c.args, prefix)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=c.dev)   # (torch's caching allocator: capturable)
+        _lib.check(lib.fasn_fwd_shared_prefix(c.args, prefix, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_shared_prefix")
+
+    _on_device(c.dev, launch)
+    return c.out if c.lse is None else (c.out, c.lse)
 
 
 def flash_attention_n_kvcache_prefill(

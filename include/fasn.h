@@ -760,6 +760,47 @@ int fasn_kv_append_plan(const fasn_kv_call* call, const fasn_kv_rope* rope, cons
                         const fasn_view4* v_new, char* buf, size_t cap);
 
 /*
+ * DECODE BEHIND A SHARED PREFIX (additions within ABI 6; no struct or function above is changed): fasn_fwd_kvcache on a paged 16-bit cache
+ * whose first P keys are the same physical pages for every batch element (a system prompt, a few-shot header, N samples of one prompt).
+ * The prefix is walked once per K/V head for the rows of ALL batch elements, each batch element's own keys as fasn_fwd_kvcache walks them.
+ *
+ *   the virtual cache   P = clamp(*prefix_len, 0, min(max_prefix_pages * page_size, capacity)), read inside the kernels (never on the
+ *              host: one captured graph serves every step and every prefix length). For every batch element b, key row j < P is row
+ *              j % page_size of page prefix_table[j / page_size]; key row j >= P is the row block_table[b] names, as in fasn_fwd_kvcache.
+ *              The result is exactly fasn_fwd_kvcache's on that cache: len_b, the positions p_i, what a row sees, softmax_n (counted
+ *              once per row) and lse do not depend on P. A batch element with len_b < P sees prefix keys up to its own limit; P need
+ *              not be a multiple of page_size or of 64 (a partially shared last page, copy on write).
+ *   never read block_table[b] entries and the batch element's own cache rows for keys below P (slots wholly below P may be unset or
+ *              point anywhere); prefix-page rows at or beyond P; prefix_table entries at or beyond ceil(P / page_size); rows at or
+ *              beyond len_b. All of them may hold anything, NaN included.
+ *   append     fasn_kvcache_append on the same block: k_new / v_new land in the batch element's OWN pages at seqlens[b] + i. Rows that
+ *              land below P are never read.
+ *   launches   three: the prefix pass - Hkv * ceil(B * R / 128) * nsplit_p workgroups of 256, R = kv_group * Sq, a workgroup holding
+ *              128 rows of the row space b * R + r - the suffix pass - fasn_fwd_kvcache's grid B * Hkv * nsplit - and the combine,
+ *              ceil(B * Hkv * R * (D / 4) / 256) workgroups. Grids, split counts and workspace depend on shapes, max_prefix_pages and
+ *              capacity only.
+ *   splits     nsplit is fasn_fwd_kvcache's for the block; split s of the suffix pass owns ceil((ceil(len_b / 64) - tlo) / nsplit) tiles
+ *              from tlo = min(P / 64, ceil(len_b / 64)) on, the base call's ranges at P = 0. nsplit_p is the same rule over
+ *              Hkv * ceil(B * R / 128) blocks and the ceil(min(max_prefix_pages * page_size, capacity) / 64) tiles a prefix can have, at
+ *              least 16 tiles per split.
+ *   workspace  (B * Hkv * nsplit * R + Hkv * nsplit_p * B * R) * (D + 2) * 4 bytes, 16-byte aligned.
+ *   checks     the block's rules with fasn_fwd_kvcache's codes and order; then block_table == NULL (a dense cache) and D outside
+ *              {64, 128}: FASN_EUNSUPPORTED; prefix == NULL, a NULL member, max_prefix_pages < 1 or reserved != 0: FASN_EINVAL; prefix_len
+ *              or prefix_table not 4-byte aligned: FASN_EALIGN; then the workspace. args == NULL is FASN_EINVAL (workspace query: 0)
+ *              before any HIP call. An FP8 cache, ALiBi, a window, a tree and packed queries have no shared-prefix kernels.
+ */
+typedef struct fasn_shared_prefix {
+    const int32_t* prefix_len;     /* device, one int32 */
+    const int32_t* prefix_table;   /* device, int32 [max_prefix_pages]: the page ids of the prefix, in order */
+    int32_t max_prefix_pages;      /* >= 1 */
+    int32_t reserved;              /* 0 */
+} fasn_shared_prefix;
+
+size_t fasn_fwd_shared_prefix_workspace_bytes(const fasn_kvcache_args* args, const fasn_shared_prefix* prefix);
+int fasn_fwd_shared_prefix(const fasn_kvcache_args* args, const fasn_shared_prefix* prefix, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_shared_prefix_plan(const fasn_kvcache_args* args, const fasn_shared_prefix* prefix, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).

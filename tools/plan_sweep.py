@@ -6,7 +6,8 @@ workspace and the backward (dummy aligned addresses, as tests/baseline_plans.py;
 the same grids iff their outputs are byte-identical - run it with REPO_ROOT = an export of the other commit, built. Also lists the kernels of
 the library's attention families that no plan named: an instantiation no call can reach, or an axis this sweep lacks.
 The token-packed sliding-window and rotary K/V-cache calls (fasn_kvvarlen_window_plan, fasn_kvvarlen_rope_append_plan) are swept too, where the
-library has them: every head dim and dtype, one split and several, with and without new rows; their kernels count as families that must be reached."""
+library has them: every head dim and dtype, one split and several, with and without new rows; their kernels count as families that must be reached.
+So is the shared-prefix decode (fasn_shared_prefix_plan) and its three kernels."""
 import ctypes, hashlib, itertools, os, re, sys
 
 ARGV = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -122,10 +123,31 @@ def kv_packed_calls():
         yield f"{hdr} rope", lib.fasn_kvvarlen_rope_append_plan, (block(False), rope, qo, None, None)
 
 
+def shared_prefix_calls():
+    """(header, plan function, its operands) of the shared-prefix decode: a fasn_kvcache_args over dummy addresses and the prefix operand -
+    both head dims and dtypes, one row block and several, a prefix of one split and of several"""
+    if not hasattr(lib, "fasn_shared_prefix_plan"):   # (a tree from before this call)
+        return
+    for D, dt, (H, Hkv), (B, Sq, pages, ppages) in itertools.product((64, 128), (0, 1), ((8, 8), (64, 8), (6, 2)),
+                                                                    ((64, 1, 40, 32), (1, 1, 40, 32), (10, 5, 8, 3), (4, 16, 32, 48))):
+        a = L.KvCacheArgs()
+        for v in (a.q, a.o):
+            view(v, (H * Sq * D, Sq * D, D, 1))
+        a.lse = a.k_cache = a.v_cache = a.block_table = a.seqlens = DUMMY
+        for i, st in enumerate((256 * Hkv * D, Hkv * D, D)):
+            a.k_stride[i] = a.v_stride[i] = st
+        a.block_table_stride = a.max_pages = pages
+        a.seqlen_add, a.page_size = 0, 256
+        a.B, a.H, a.kv_group, a.Sq, a.D, a.dtype = B, H, H // Hkv, Sq, D, dt
+        a.scale, a.softmax_n, a.causal = D ** -0.5, 1.0, 1
+        yield (f"shared_prefix D={D} dt={dt} heads={H}/{Hkv} B={B} Sq={Sq} pages={pages} prefix_pages={ppages}", lib.fasn_shared_prefix_plan,
+               (a, L.SharedPrefix(prefix_len=DUMMY, prefix_table=DUMMY, max_prefix_pages=ppages, reserved=0)))
+
+
 def library_attention_kernels():
     table = spill_map.kernel_table(os.path.join(ROOT, "flash-attention-softmax-n_amd", "libfasn.so"))
     names = {re.sub(r"\(fasn::\w+(, fasn::\w+)*\)$", "", d).replace("void fasn::", "") for d in spill_map.demangle(list(table)).values()}
-    return names, {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel", n)}
+    return names, {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel|fasn_kvshared_", n)}
 
 
 def witness_main():
@@ -153,7 +175,7 @@ def main():
         return witness_main()
     out, named, ncalls = [], set(), 0
     buf = ctypes.create_string_buffer(1 << 15)
-    for hdr, plan, operands in kv_packed_calls():
+    for hdr, plan, operands in itertools.chain(kv_packed_calls(), shared_prefix_calls()):
         ncalls += 1
         rc = plan(*operands, buf, len(buf))
         out.append(f"{hdr} rc={rc}")
