@@ -22,6 +22,7 @@ Public surface = flash_attention_softmax_n/__init__.py:3-9 of the reference:
     flash_attention_n_kvcache_fp8_varlen_window  (a sliding-window layer on the token-packed step over the FP8 cache)
     flash_attention_n_kvcache_fp8_varlen_rope  (rotary position embedding fused into the quantising append of the token-packed step)
     flash_attention_n_kvcache_shared_prefix  (decode behind one shared prefix: its pages are attended to once per K/V head for the whole batch)
+    flash_attention_n_kvcache_prefix_groups  (decode behind several shared prefixes in one call: prefix_group[b] on the device names the prefix of b, or none)
     surgery.apply_attention_softmax_n / surgery.policy_registry  (flash_attention_softmax_n/surgery, composer-free)
 Every function runs on device tensors through libfasn.so; importing the package without the built
 library raises ImportError (no silent fallback).
@@ -31,7 +32,7 @@ from .flash_attn import flash_attention_n, flash_attention_n_triton, flash_atten
 from .kvcache import (flash_attention_n_kvcache, flash_attention_n_kvcache_fp8, flash_attention_n_kvcache_fp8_rope, flash_attention_n_kvcache_fp8_tree,
                       flash_attention_n_kvcache_fp8_tree_commit, flash_attention_n_kvcache_fp8_varlen, flash_attention_n_kvcache_fp8_varlen_rope,
                       flash_attention_n_kvcache_fp8_varlen_window, flash_attention_n_kvcache_fp8_window,
-                      flash_attention_n_kvcache_prefill, flash_attention_n_kvcache_rope, flash_attention_n_kvcache_shared_prefix, flash_attention_n_kvcache_tree,
+                      flash_attention_n_kvcache_prefill, flash_attention_n_kvcache_prefix_groups, flash_attention_n_kvcache_rope, flash_attention_n_kvcache_shared_prefix, flash_attention_n_kvcache_tree,
                       flash_attention_n_kvcache_tree_commit, flash_attention_n_kvcache_varlen,
                       flash_attention_n_kvcache_varlen_rope, flash_attention_n_kvcache_varlen_window, flash_attention_n_kvcache_window)
 from .softmax import softmax_n
@@ -41,4 +42,4 @@ _lib.load()  # fail loudly at import if the HIP extension is missing
 TRITON_INSTALLED = False  # kept for source compatibility: the Triton path is replaced by the HIP kernel
 HIP_NATIVE = True
 
-__all__ = ["flash_attention_n", "flash_attention_n_varlen", "flash_attention_n_varlen_rope", "flash_attention_n_kvcache", "flash_attention_n_kvcache_prefill", "flash_attention_n_kvcache_window", "flash_attention_n_kvcache_rope", "flash_attention_n_kvcache_varlen", "flash_attention_n_kvcache_varlen_window", "flash_attention_n_kvcache_varlen_rope", "flash_attention_n_kvcache_tree", "flash_attention_n_kvcache_tree_commit", "flash_attention_n_kvcache_fp8", "flash_attention_n_kvcache_fp8_window", "flash_attention_n_kvcache_fp8_rope", "flash_attention_n_kvcache_fp8_tree", "flash_attention_n_kvcache_fp8_tree_commit", "flash_attention_n_kvcache_fp8_varlen", "flash_attention_n_kvcache_fp8_varlen_window", "flash_attention_n_kvcache_fp8_varlen_rope", "flash_attention_n_kvcache_shared_prefix", "flash_attention_n_triton", "slow_attention_n", "softmax_n", "TRITON_INSTALLED", "HIP_NATIVE"]
+__all__ = ["flash_attention_n", "flash_attention_n_varlen", "flash_attention_n_varlen_rope", "flash_attention_n_kvcache", "flash_attention_n_kvcache_prefill", "flash_attention_n_kvcache_window", "flash_attention_n_kvcache_rope", "flash_attention_n_kvcache_varlen", "flash_attention_n_kvcache_varlen_window", "flash_attention_n_kvcache_varlen_rope", "flash_attention_n_kvcache_tree", "flash_attention_n_kvcache_tree_commit", "flash_attention_n_kvcache_fp8", "flash_attention_n_kvcache_fp8_window", "flash_attention_n_kvcache_fp8_rope", "flash_attention_n_kvcache_fp8_tree", "flash_attention_n_kvcache_fp8_tree_commit", "flash_attention_n_kvcache_fp8_varlen", "flash_attention_n_kvcache_fp8_varlen_window", "flash_attention_n_kvcache_fp8_varlen_rope", "flash_attention_n_kvcache_shared_prefix", "flash_attention_n_kvcache_prefix_groups", "flash_attention_n_triton", "slow_attention_n", "softmax_n", "TRITON_INSTALLED", "HIP_NATIVE"]

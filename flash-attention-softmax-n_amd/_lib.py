@@ -51,6 +51,7 @@ EXPORTS = (
     "fasn_fwd_varlen_window", "fasn_bwd_varlen_window", "fasn_varlen_window_plan",
     "fasn_varlen_rope", "fasn_varlen_rope_plan",
     "fasn_fwd_shared_prefix_workspace_bytes", "fasn_fwd_shared_prefix", "fasn_shared_prefix_plan",
+    "fasn_fwd_prefix_groups_workspace_bytes", "fasn_fwd_prefix_groups", "fasn_prefix_groups_plan",
 )
 
 
@@ -175,6 +176,16 @@ class SharedPrefix(Structure):
     _fields_ = [("prefix_len", c_void_p), ("prefix_table", c_void_p), ("max_prefix_pages", c_int32), ("reserved", c_int32)]
 
 
+class PrefixGroups(Structure):
+    """fasn_prefix_groups (include/fasn.h): the prefixes of fasn_fwd_prefix_groups - their lengths ([num_groups] int32), their page ids
+    ([num_groups, max_prefix_pages] int32) and the group of every batch element ([B] int32), all in device memory; reserved = 0"""
+    _fields_ = [("prefix_lens", c_void_p), ("prefix_tables", c_void_p), ("prefix_group", c_void_p),
+                ("num_groups", c_int32), ("max_prefix_pages", c_int32), ("reserved", c_int32)]
+
+
+FASN_PREFIX_GROUPS_MAX = 1024   # include/fasn.h
+
+
 class FasnError(RuntimeError):
     pass
 
@@ -270,6 +281,15 @@ def _shared_prefix_bindings():
     yield "fasn_shared_prefix_plan", c_int32, head + [c_char_p, c_size_t]
 
 
+def _prefix_groups_bindings():
+    """(name, restype, argtypes) of the three entry points of the prefix-groups decode: a decode block and the groups operand, beside
+    the shared-prefix call's and, like them, no part of the K/V-cache description above."""
+    head = [POINTER(KvCacheArgs), POINTER(PrefixGroups)]
+    yield "fasn_fwd_prefix_groups_workspace_bytes", c_size_t, head
+    yield "fasn_fwd_prefix_groups", c_int32, head + [c_void_p, c_size_t, c_void_p]
+    yield "fasn_prefix_groups_plan", c_int32, head + [c_char_p, c_size_t]
+
+
 def kv_call(args, fp8=None, tree=None, window=None, alibi=None):
     """the KvCall of the block `args` under the operands that are not None. The block and the operands live as long as the KvCall does."""
     c = KvCall(kind=_KV_KIND[kv_stem(args)], reserved=0, block=ctypes.cast(ctypes.pointer(args), c_void_p))
@@ -348,7 +368,7 @@ def load():
     lib.fasn_varlen_rope.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvRope), POINTER(View4), POINTER(View4), c_int32, c_void_p]
     lib.fasn_varlen_rope_plan.restype = c_int32
     lib.fasn_varlen_rope_plan.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvRope), POINTER(View4), POINTER(View4), c_int32, c_char_p, c_size_t]
-    for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings(), *_shared_prefix_bindings()):
+    for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings(), *_shared_prefix_bindings(), *_prefix_groups_bindings()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     ver = lib.fasn_abi_version()
@@ -527,6 +547,12 @@ def shared_prefix_plan(args, prefix):
     """The three launches of fasn_fwd_shared_prefix for `args` (a KvCacheArgs) behind `prefix` (a SharedPrefix) - the prefix pass, the
     suffix pass, the combine - as launch_plan returns them. Nothing is launched."""
     return _plan("fasn_shared_prefix_plan", args, prefix)
+
+
+def prefix_groups_plan(args, groups):
+    """The four launches of fasn_fwd_prefix_groups for `args` (a KvCacheArgs) behind `groups` (a PrefixGroups) - the schedule kernel, the
+    prefix pass, the suffix pass, the combine - as launch_plan returns them. Nothing is launched."""
+    return _plan("fasn_prefix_groups_plan", args, groups)
 
 
 def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):

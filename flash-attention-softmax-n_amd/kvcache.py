@@ -28,6 +28,8 @@ flash_attention_n_kvcache_fp8_varlen, _fp8_varlen_window and _fp8_varlen_rope ar
 operand sets have no named entry points and go through the operand-set calls (fasn_kv_forward, fasn_kv_append: a fasn_kv_call).
 flash_attention_n_kvcache_shared_prefix is the decode call for a batch behind ONE shared prefix (fasn_fwd_shared_prefix): `prefix_table` names
 the prefix pages and `prefix_len` - on the device - how many keys they hold; the prefix is attended to once per K/V head for all sequences.
+flash_attention_n_kvcache_prefix_groups is that call behind SEVERAL prefixes at once (fasn_fwd_prefix_groups): `prefix_group[b]` - on the
+device - names the prefix of batch element b or none, so one call and one captured graph serve every mix of prompts in a batch.
 Forward only: the training entry point is flash_attention_n.
 """
 from math import sqrt
@@ -37,7 +39,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import AlibiSlopes, KvCacheArgs, KvFp8, KvPrefillArgs, KvRope, KvTree, KvTreeCommit, KvVarlenArgs, KvWindow, SharedPrefix
+from ._lib import AlibiSlopes, KvCacheArgs, KvFp8, KvPrefillArgs, KvRope, KvTree, KvTreeCommit, KvVarlenArgs, KvWindow, PrefixGroups, SharedPrefix
 from .flash_attn import _current_device, _n_strides, _n_tensor, _stream_ptr, _view4
 
 _KV_DTYPES = {torch.float16: _lib.FASN_DTYPE_F16, torch.bfloat16: _lib.FASN_DTYPE_BF16}
@@ -562,6 +564,104 @@ def flash_attention_n_kvcache_shared_prefix(
         ws_bytes = lib.fasn_fwd_shared_prefix_workspace_bytes(c.args, prefix)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=c.dev)   # (torch's caching allocator: capturable)
         _lib.check(lib.fasn_fwd_shared_prefix(c.args, prefix, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_shared_prefix")
+
+    _on_device(c.dev, launch)
+    return c.out if c.lse is None else (c.out, c.lse)
+
+
+def flash_attention_n_kvcache_prefix_groups(
+        query: Tensor,
+        k_cache: Tensor,
+        v_cache: Tensor,
+        cache_seqlens: Tensor,
+        block_table: Tensor,
+        prefix_tables: Tensor,
+        prefix_lens: Tensor,
+        prefix_group: Tensor,
+        k_new: Optional[Tensor] = None,
+        v_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        scale: Optional[float] = None,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """flash_attention_n_kvcache for a batch that decodes behind SEVERAL SHARED PREFIXES (a server that holds a few system prompts, N
+    samples of each of M prompts, sequences that share nothing), on MI355X, in one call: flash_attention_n_kvcache_shared_prefix with one
+    prefix per GROUP of batch elements. A schedule kernel sorts the batch by group on the device; the pages of every prefix that has a
+    member are attended to once per K/V head for the rows of its members - packed into 128-row blocks that never mix groups - each batch
+    element's own keys as flash_attention_n_kvcache walks them, and the two are merged (fasn_fwd_prefix_groups).
+
+    For a batch element b with g = prefix_group[b] in [0, G): P_b = clamp(prefix_lens[g], 0, min(max_prefix_pages * page_size, capacity)),
+    key row j < P_b is row j % page_size of page prefix_tables[g, j // page_size] and key row j >= P_b is the row block_table[b] names.
+    For every other b, P_b = 0: its cache is the one flash_attention_n_kvcache sees. The result is exactly flash_attention_n_kvcache's on
+    that virtual cache: len_b, the positions, causal visibility, n (counted once per row) and lse do not depend on P_b; P_b need not be a
+    multiple of the page size or of 64; a batch element shorter than its prefix sees prefix keys up to its own limit. With every entry of
+    prefix_group out of range the result is flash_attention_n_kvcache's bit for bit, with G = 1 and every entry 0
+    flash_attention_n_kvcache_shared_prefix's. Operands, append, alignment rules and refusals are those of
+    flash_attention_n_kvcache_shared_prefix. What differs:
+
+    :param prefix_tables: contiguous int32 [G, max_prefix_pages] on the device: row g holds the page ids of prefix g, in order.
+                  1 <= G <= 1024 (the schedule kernel keeps its counters per group in LDS).
+    :param prefix_lens: contiguous int32 [G] on the device.
+    :param prefix_group: contiguous int32 [B] on the device: the prefix of batch element b; any value outside [0, G) - -1, say - means
+                  "no shared prefix".
+    None of the three is read on the host, so one captured graph serves every assignment of sequences to prefixes, every prefix length
+    and every step.
+
+    Memory contract. For keys below P_b, block_table[b] entries and the batch element's own cache rows are never read. Rows of a prefix
+    page at or beyond that prefix's P and prefix_tables[g] entries at or beyond ceil(P_g / page_size) are never read, nor are the whole
+    table row and every page of a group that has no member. Rows at or beyond len_b may hold anything. Whatever prefix_group and
+    prefix_lens hold, no access leaves the operands.
+    """
+    fn = "flash_attention_n_kvcache_prefix_groups"
+    if block_table is None:
+        raise ValueError(f"{fn}: a dense cache (block_table=None) is not supported: a shared prefix is a set of pages that several block "
+                         "tables name (paged caches only)")
+    if isinstance(k_cache, Tensor) and k_cache.dtype == torch.float8_e4m3fn:
+        raise TypeError(f"{fn}: a float8 cache is not supported (fp16 and bf16 caches only; the FP8 call is flash_attention_n_kvcache_fp8, "
+                        "without shared prefixes)")
+    if query.dim() == 4 and query.shape[3] in _KV_HEAD_DIMS and query.shape[3] not in _SHARED_PREFIX_HEAD_DIMS:
+        raise ValueError(f"{fn}: head dim {query.shape[3]} is not supported behind shared prefixes (supported: {_SHARED_PREFIX_HEAD_DIMS}; "
+                         "32 and 256 have the kernels of flash_attention_n_kvcache only)")
+
+    def got(t):
+        return f"{t.dtype} {tuple(t.shape)}" if isinstance(t, Tensor) else type(t).__name__
+
+    def int32(t, dims):
+        return isinstance(t, Tensor) and t.dtype == torch.int32 and t.dim() == dims and t.is_contiguous()
+    if not int32(prefix_tables, 2) or prefix_tables.shape[0] < 1 or prefix_tables.shape[1] < 1:
+        raise ValueError(f"{fn}: prefix_tables must be a contiguous int32 tensor of shape [G, max_prefix_pages] on the device (at least one "
+                         f"group and one page); got {got(prefix_tables)}")
+    G = prefix_tables.shape[0]
+    if G > _lib.FASN_PREFIX_GROUPS_MAX:
+        raise ValueError(f"{fn}: {G} prefix groups exceed the {_lib.FASN_PREFIX_GROUPS_MAX} of one call (the schedule kernel keeps its "
+                         "counters per group in LDS)")
+    if not int32(prefix_lens, 1):
+        raise ValueError(f"{fn}: prefix_lens must be a contiguous int32 tensor of shape [G] on the device (it is read by the kernels, never "
+                         f"on the host); got {got(prefix_lens)}")
+    if prefix_lens.shape[0] != G:
+        raise ValueError(f"{fn}: prefix_lens has {prefix_lens.shape[0]} entries, prefix_tables {G} rows: one length per prefix")
+    if not int32(prefix_group, 1):
+        raise ValueError(f"{fn}: prefix_group must be a contiguous int32 tensor of shape [B] on the device (it is read by the kernels, never "
+                         f"on the host); got {got(prefix_group)}")
+    if query.dim() == 4 and prefix_group.shape[0] != query.shape[0]:
+        raise ValueError(f"{fn}: prefix_group has {prefix_group.shape[0]} entries, the batch {query.shape[0]} elements: one group per batch "
+                         "element (any value outside [0, G) for none)")
+    for name, t in (("prefix_tables", prefix_tables), ("prefix_lens", prefix_lens), ("prefix_group", prefix_group)):
+        if t.device != query.device:
+            raise RuntimeError(f"{name} is on {t.device}, query on {query.device}: every operand must live on the query's device "
+                               "(the prefixes, their lengths and the groups are read by the kernels, never on the host)")
+    c = _prepare(fn, "kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
+                 return_lse)
+    lib = _lib.load()
+    groups = PrefixGroups(prefix_lens=prefix_lens.data_ptr(), prefix_tables=prefix_tables.data_ptr(), prefix_group=prefix_group.data_ptr(),
+                          num_groups=G, max_prefix_pages=min(prefix_tables.shape[1], _INT_MAX), reserved=0)
+
+    def launch():
+        stream = _stream_ptr(c.dev)
+        _append(lib, c, stream)
+        ws_bytes = lib.fasn_fwd_prefix_groups_workspace_bytes(c.args, groups)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=c.dev)   # (torch's caching allocator: capturable)
+        _lib.check(lib.fasn_fwd_prefix_groups(c.args, groups, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_prefix_groups")
 
     _on_device(c.dev, launch)
     return c.out if c.lse is None else (c.out, c.lse)

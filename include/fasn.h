@@ -801,6 +801,57 @@ int fasn_fwd_shared_prefix(const fasn_kvcache_args* args, const fasn_shared_pref
 int fasn_shared_prefix_plan(const fasn_kvcache_args* args, const fasn_shared_prefix* prefix, char* buf, size_t cap);
 
 /*
+ * DECODE BEHIND SEVERAL SHARED PREFIXES: PREFIX GROUPS (additions within ABI 6; no struct or function above is changed): the call above
+ * with one prefix per GROUP of batch elements - a server that holds a few system prompts, N samples of each of M prompts, sequences that
+ * share nothing - in one launch set and one captured graph. Membership is device data: prefix_group[b] names the prefix of batch
+ * element b, any value outside [0, num_groups) means "no shared prefix".
+ *
+ *   the virtual cache   for g = prefix_group[b] in [0, num_groups): P_b = clamp(prefix_lens[g], 0, min(max_prefix_pages * page_size,
+ *              capacity)); key row j < P_b is row j % page_size of page prefix_tables[g * max_prefix_pages + j / page_size], key row
+ *              j >= P_b the row block_table[b] names. For every other b, P_b = 0. The result is exactly fasn_fwd_kvcache's on that
+ *              cache, as above: with every prefix_group entry out of range it is fasn_fwd_kvcache's bit for bit, with num_groups = 1
+ *              and every entry 0 fasn_fwd_shared_prefix's.
+ *   never read what fasn_fwd_shared_prefix never reads, per batch element and per group; and the prefix_tables row and every page of a
+ *              group that has no member. Whatever prefix_group and prefix_lens hold, no access leaves the operands.
+ *   append     fasn_kvcache_append on the same block, as above.
+ *   launches   four: the schedule kernel (one workgroup of 256: prefix_group -> the table below), the prefix pass -
+ *              Hkv * items_max * nsplit_p workgroups of 256, a workgroup holding one ITEM: 128 rows of one group - the suffix pass -
+ *              fasn_fwd_kvcache's grid - and the combine. items_max = ceil(B * R / 128) + min(num_groups, B) - 1, R = kv_group * Sq.
+ *              Grids, split counts and workspace depend on shapes, num_groups, max_prefix_pages and capacity only.
+ *   splits     nsplit as above; nsplit_p is the same rule over Hkv * items_max blocks and the tiles a prefix can have, at least 16 tiles
+ *              per split.
+ *   workspace  partials of (B * Hkv * nsplit * R + Hkv * nsplit_p * B * R) * (D + 2) * 4 bytes, laid out as above; then, at the next
+ *              multiple of 16 bytes - FASN_PREFIX_GROUPS_TABLE_OFFSET(partial bytes) - the schedule table of
+ *              (4 + ceil(3 * B / 4) * 4 + 4 * items_max) int32. 16-byte aligned.
+ *   the table  the grouped batch elements in a STABLE order - by group, inside a group by batch index - own the rows slot * R + r of the
+ *              prefix partials. int32:
+ *                [0] the item count, [1] the number of grouped batch elements, [2] [3] 0
+ *                [4 + s]            order: the batch element of slot s; -1 at and beyond [1]            (s < B)
+ *                [4 + B + b]        the slot of batch element b; -1: no prefix                            (b < B)
+ *                [4 + 2 B + b]      P_b                                                                   (b < B)
+ *                [4 + ceil(3 * B / 4) * 4 + 4 * i ..]  item i: group, first row, the row at which the group's rows end, P_g; a group
+ *                                   of c members has ceil(c * R / 128) items of 128 rows from first row on; (-1, 0, 0, 0) at and beyond [0]
+ *              Every entry is written by every call, and the same operands give the same table. It is output for inspection only.
+ *   checks     the block's rules with fasn_fwd_kvcache's codes and order; then block_table == NULL and D outside {64, 128}:
+ *              FASN_EUNSUPPORTED; groups == NULL, a NULL member, num_groups < 1 or > FASN_PREFIX_GROUPS_MAX, max_prefix_pages < 1 or
+ *              reserved != 0: FASN_EINVAL; prefix_lens, prefix_tables or prefix_group not 4-byte aligned: FASN_EALIGN; then the workspace.
+ */
+#define FASN_PREFIX_GROUPS_MAX 1024   /* three LDS counters per group in the schedule kernel */
+#define FASN_PREFIX_GROUPS_TABLE_OFFSET(partial_bytes) (((size_t)(partial_bytes) + 15) / 16 * 16)
+typedef struct fasn_prefix_groups {
+    const int32_t* prefix_lens;     /* device, int32 [num_groups] */
+    const int32_t* prefix_tables;   /* device, int32 [num_groups][max_prefix_pages], contiguous: the page ids of prefix g, in order */
+    const int32_t* prefix_group;    /* device, int32 [B]: the prefix of batch element b; outside [0, num_groups): none */
+    int32_t num_groups;             /* 1 .. FASN_PREFIX_GROUPS_MAX */
+    int32_t max_prefix_pages;       /* >= 1 */
+    int32_t reserved;               /* 0 */
+} fasn_prefix_groups;
+
+size_t fasn_fwd_prefix_groups_workspace_bytes(const fasn_kvcache_args* args, const fasn_prefix_groups* groups);
+int fasn_fwd_prefix_groups(const fasn_kvcache_args* args, const fasn_prefix_groups* groups, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_prefix_groups_plan(const fasn_kvcache_args* args, const fasn_prefix_groups* groups, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).

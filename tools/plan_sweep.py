@@ -7,7 +7,8 @@ the same grids iff their outputs are byte-identical - run it with REPO_ROOT = an
 the library's attention families that no plan named: an instantiation no call can reach, or an axis this sweep lacks.
 The token-packed sliding-window and rotary K/V-cache calls (fasn_kvvarlen_window_plan, fasn_kvvarlen_rope_append_plan) are swept too, where the
 library has them: every head dim and dtype, one split and several, with and without new rows; their kernels count as families that must be reached.
-So is the shared-prefix decode (fasn_shared_prefix_plan) and its three kernels."""
+So is the shared-prefix decode (fasn_shared_prefix_plan) and its three kernels, and the prefix-groups decode (fasn_prefix_groups_plan)
+and its four."""
 import ctypes, hashlib, itertools, os, re, sys
 
 ARGV = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -144,10 +145,21 @@ def shared_prefix_calls():
                (a, L.SharedPrefix(prefix_len=DUMMY, prefix_table=DUMMY, max_prefix_pages=ppages, reserved=0)))
 
 
+def prefix_groups_calls():
+    """the blocks of shared_prefix_calls() behind 1, 4 and 64 prefix groups (fasn_prefix_groups_plan)"""
+    if not hasattr(lib, "fasn_prefix_groups_plan"):   # (a tree from before this call)
+        return
+    for hdr, _plan, (a, sp) in shared_prefix_calls():
+        for G in (1, 4, 64):
+            yield (hdr.replace("shared_prefix", "prefix_groups") + f" groups={G}", lib.fasn_prefix_groups_plan,
+                   (a, L.PrefixGroups(prefix_lens=DUMMY, prefix_tables=DUMMY, prefix_group=DUMMY, num_groups=G,
+                                      max_prefix_pages=sp.max_prefix_pages, reserved=0)))
+
+
 def library_attention_kernels():
     table = spill_map.kernel_table(os.path.join(ROOT, "flash-attention-softmax-n_amd", "libfasn.so"))
     names = {re.sub(r"\(fasn::\w+(, fasn::\w+)*\)$", "", d).replace("void fasn::", "") for d in spill_map.demangle(list(table)).values()}
-    return names, {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel|fasn_kvshared_", n)}
+    return names, {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel|fasn_kvshared_|fasn_kvgroups_", n)}
 
 
 def witness_main():
@@ -175,7 +187,7 @@ def main():
         return witness_main()
     out, named, ncalls = [], set(), 0
     buf = ctypes.create_string_buffer(1 << 15)
-    for hdr, plan, operands in itertools.chain(kv_packed_calls(), shared_prefix_calls()):
+    for hdr, plan, operands in itertools.chain(kv_packed_calls(), shared_prefix_calls(), prefix_groups_calls()):
         ncalls += 1
         rc = plan(*operands, buf, len(buf))
         out.append(f"{hdr} rc={rc}")
