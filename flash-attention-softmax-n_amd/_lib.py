@@ -272,22 +272,21 @@ def _kv_call_bindings():
     yield "fasn_kv_append_plan", c_int32, append + text
 
 
+def _prefix_bindings(stem, operand):
+    """(name, restype, argtypes) of the three entry points of a decode behind shared prefixes: a decode block and the prefix operand.
+    They are no part of the K/V-cache description above - the operand belongs to no operand set - and have lists of their own."""
+    head = [POINTER(KvCacheArgs), POINTER(operand)]
+    yield f"fasn_fwd_{stem}_workspace_bytes", c_size_t, head
+    yield f"fasn_fwd_{stem}", c_int32, head + [c_void_p, c_size_t, c_void_p]
+    yield f"fasn_{stem}_plan", c_int32, head + [c_char_p, c_size_t]
+
+
 def _shared_prefix_bindings():
-    """(name, restype, argtypes) of the three entry points of the shared-prefix decode: a decode block and the prefix operand. They are
-    no part of the K/V-cache description above - the operand belongs to no operand set - and have a list of their own."""
-    head = [POINTER(KvCacheArgs), POINTER(SharedPrefix)]
-    yield "fasn_fwd_shared_prefix_workspace_bytes", c_size_t, head
-    yield "fasn_fwd_shared_prefix", c_int32, head + [c_void_p, c_size_t, c_void_p]
-    yield "fasn_shared_prefix_plan", c_int32, head + [c_char_p, c_size_t]
+    return _prefix_bindings("shared_prefix", SharedPrefix)
 
 
 def _prefix_groups_bindings():
-    """(name, restype, argtypes) of the three entry points of the prefix-groups decode: a decode block and the groups operand, beside
-    the shared-prefix call's and, like them, no part of the K/V-cache description above."""
-    head = [POINTER(KvCacheArgs), POINTER(PrefixGroups)]
-    yield "fasn_fwd_prefix_groups_workspace_bytes", c_size_t, head
-    yield "fasn_fwd_prefix_groups", c_int32, head + [c_void_p, c_size_t, c_void_p]
-    yield "fasn_prefix_groups_plan", c_int32, head + [c_char_p, c_size_t]
+    return _prefix_bindings("prefix_groups", PrefixGroups)
 
 
 def kv_call(args, fp8=None, tree=None, window=None, alibi=None):

@@ -129,7 +129,8 @@ int kv_dispatch(int dtype, int D, F f) {
     return kv_dispatch_d(D, [&](auto d) { return f(f16_tag{}, d); });
 }
 
-// dtype x the two head dims the FP8 kernels are built for (kv_check_fp8 let only these through)
+// dtype x the two head dims the FP8 kernels and the kernels behind shared prefixes (fasn_kvprefix.hip) are built for (kv_check_fp8 and
+// the prefix calls' builder let only these through)
 template <typename F>
 int kv8_dispatch(int dtype, int D, F f) {
     if (dtype == FASN_DTYPE_BF16) return D == 64 ? f(bf16_tag{}, std::integral_constant<int, 64>{}) : f(bf16_tag{}, std::integral_constant<int, 128>{});

@@ -169,8 +169,83 @@ constexpr bool kv_fp8_head_dim_ok(int D) { return D == 64 || D == 128; }
 #undef FASN_KV_WINDOW
 #undef FASN_KV_ALIBI
 
-// Merge the partials of a row (the arithmetic of fasn_fwd_combine_kernel: m* = max_s m_s, l = sum_s l_s 2^(m_s - m*),
-// O = sum_s acc_s 2^(m_s - m*) / l) and scatter it: row r of (b, hkv) is o[b, hkv * G + r / Sq, r % Sq, :]. One thread per (row, 4 features).
+// ---- the split merge of the K/V-cache family: the eight combine kernels (here, fasn_kvprefill.h, fasn_kvvarlen.h, fasn_kvfp8.h,
+// fasn_kvprefix.h) compute their row and where its partials lie, call kv_merge, then kv_store_row and kv_lse (decode rows:
+// kv_store_decode_row). One thread per (row, 4 features).
+//
+// A partial set is (part_o, part_ml, nsplit, at): the nsplit un-normalised partials of one row, split s at row `at(s)` of part_o [..][D]
+// and part_ml [..][2]; `at` is the kernel's own index expression, so the three layouts in use stay as they are.
+struct KvMerged {
+    f32x4 acc;           // sum_s acc_s 2^(m_s - m*), features c4 .. c4 + 3
+    float l, m_use;      // sum_s l_s 2^(m_s - m*);  m* (0 when every partial is neutral)
+};
+struct KvNoParts {   // the index of a set that is not there
+    FASN_DEV int64_t operator()(int) const { return 0; }
+};
+// The merge of one set or two (the arithmetic of fasn_fwd_combine_kernel): m* = max_s m_s over the sets in the order given, then
+// l = sum_s l_s 2^(m_s - m*) and acc = sum_s acc_s 2^(m_s - m*) over the sets in the same order.
+template <int D, typename At1, typename At2 = KvNoParts>
+FASN_DEV KvMerged kv_merge(int c4, const float* part_o1, const float* part_ml1, int nsplit1, At1 at1, const float* part_o2 = nullptr,
+                           const float* part_ml2 = nullptr, int nsplit2 = 0, At2 at2 = {}) {
+    float mstar = -INFINITY;
+    auto take_max = [&](const float* part_ml, int nsplit, auto at) {
+        for (int s = 0; s < nsplit; ++s) mstar = fmaxf(mstar, part_ml[at(s) * 2]);
+    };
+    take_max(part_ml1, nsplit1, at1);
+    take_max(part_ml2, nsplit2, at2);
+    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
+    float l = 0.f;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    auto add = [&](const float* part_o, const float* part_ml, int nsplit, auto at) {
+        for (int s = 0; s < nsplit; ++s) {
+            const int64_t base = at(s);
+            const float ms = part_ml[base * 2], ls = part_ml[base * 2 + 1];
+            if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
+            const float w = fast_exp2(ms - m_use);
+            l += ls * w;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(part_o + base * D + c4);
+            acc += a * w;
+        }
+    };
+    add(part_o1, part_ml1, nsplit1, at1);
+    add(part_o2, part_ml2, nsplit2, at2);
+    return {acc, l, m_use};
+}
+// The store of a merged row: O = acc / l (zeros where nothing was visible) and its one rounding to oat ...
+FASN_DEV f32x4 kv_merged_row(const KvMerged& m) {
+    const float inv = m.l > 0.f ? 1.0f / m.l : 0.f;
+    return m.acc * inv;
+}
+template <typename E>
+FASN_DEV void kv_store_rounded(char* oat, f32x4 y4) {
+    typename E::vec4 y = E::cvt4(y4);
+    u32x2 raw;
+    __builtin_memcpy(&raw, &y, 8);
+    gstore8(oat, raw);
+}
+template <typename E>
+FASN_DEV void kv_store_row(char* oat, const KvMerged& m) {
+    kv_store_rounded<E>(oat, kv_merged_row(m));
+}
+// ... with v_scale (the FP8 cache's) on the normalised fp32 row, in front of the rounding
+template <typename E>
+FASN_DEV void kv_store_row(char* oat, const KvMerged& m, float v_scale) {
+    kv_store_rounded<E>(oat, kv_merged_row(m) * v_scale);
+}
+// ... and the row's lse = ln(sum), which the thread of the row's first four features writes where the call has an lse
+FASN_DEV float kv_lse(const KvMerged& m) { return m.l > 0.f ? (m.m_use + __builtin_log2f(m.l)) * kLn2 : -INFINITY; }
+// where a decode row goes: row r of (b, hkv) is o[b, hkv * G + r / Sq, r % Sq, :] / lse[b, h, pos]
+template <typename E>
+FASN_DEV void kv_store_decode_row(const KvParams& p, int b, int h, int pos, int c4, const KvMerged& m) {
+    kv_store_row<E>(p.o + (b * p.os[0] + h * p.os[1] + (int64_t)pos * p.os[2] + c4) * 2, m);
+    if (p.lse != nullptr && c4 == 0) p.lse[((int64_t)b * p.H + h) * p.Sq + pos] = kv_lse(m);
+}
+template <typename E>
+FASN_DEV void kv_store_decode_row(const KvParams& p, int b, int h, int pos, int c4, const KvMerged& m, float v_scale) {
+    kv_store_row<E>(p.o + (b * p.os[0] + h * p.os[1] + (int64_t)pos * p.os[2] + c4) * 2, m, v_scale);
+    if (p.lse != nullptr && c4 == 0) p.lse[((int64_t)b * p.H + h) * p.Sq + pos] = kv_lse(m);
+}
+
 template <typename Tag, int D>
 __global__ void __launch_bounds__(256) fasn_kvcache_combine_kernel(const KvParams p) {
     using E = ET<Tag>;
@@ -181,26 +256,8 @@ __global__ void __launch_bounds__(256) fasn_kvcache_combine_kernel(const KvParam
     if (rowg >= (int64_t)p.B * p.Hkv * p.R) return;
     const int bk = (int)(rowg / p.R), r = (int)(rowg % p.R);
     const int b = bk / p.Hkv, h = (bk % p.Hkv) * p.G + r / p.Sq, pos = r % p.Sq;
-    float mstar = -INFINITY;
-    for (int s = 0; s < p.nsplit; ++s) mstar = fmaxf(mstar, p.part_ml[(((int64_t)bk * p.nsplit + s) * p.R + r) * 2]);
-    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
-    float l = 0.f;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.nsplit; ++s) {
-        const int64_t base = ((int64_t)bk * p.nsplit + s) * p.R + r;
-        const float ms = p.part_ml[base * 2], ls = p.part_ml[base * 2 + 1];
-        if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
-        const float w = fast_exp2(ms - m_use);
-        l += ls * w;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p.part_o + base * D + c4);
-        acc += a * w;
-    }
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    typename E::vec4 y = E::cvt4(acc * inv);
-    u32x2 raw;
-    __builtin_memcpy(&raw, &y, 8);
-    gstore8(p.o + (b * p.os[0] + h * p.os[1] + (int64_t)pos * p.os[2] + c4) * 2, raw);
-    if (p.lse != nullptr && c4 == 0) p.lse[((int64_t)b * p.H + h) * p.Sq + pos] = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
+    const KvMerged m = kv_merge<D>(c4, p.part_o, p.part_ml, p.nsplit, [&](int s) { return ((int64_t)bk * p.nsplit + s) * p.R + r; });
+    kv_store_decode_row<E>(p, b, h, pos, c4, m);
 }
 
 // k_new / v_new row i of (b, hkv) -> cache row seqlens[b] + i, 16 bytes per thread and tensor. Rows that would land at or beyond the

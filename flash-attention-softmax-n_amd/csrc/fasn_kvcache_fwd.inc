@@ -11,32 +11,29 @@
 // c8 under FASN_KV_FP8, p.c otherwise (a macro, so that the kernels that were there keep their tokens).
 // FASN_KV_FP8 is orthogonal to FASN_KV_TREE in the same way: both at 1 (fasn_kvfp8.h) is the token-tree sibling over the FP8 cache - the tree's
 // tile range, full-tile test and per-lane visibility word around the FP8 staging and widening, FASN_KV_SC in both arms of the masked loop.
-// FASN_KV_SHARED = 1 / 2 (fasn_kvshared.h, with the other four at 0; undefined counts as 0) are the two passes of the shared-prefix call:
-// 1 is the prefix pass - a workgroup is (K/V head, 128-row block of the row space b * R + r of ALL batch elements, split), walks the tiles of
-// the prefix pages [0, ceil(P / 64)), every lane carries the b of its own row and the limit min(P - 1, its base limit), no sink - and 2 the
-// suffix pass - the base walk over the tiles [P / 64, ceil(len_b / 64)) of the batch element's own pages, keys below P hidden in the first
-// tile. With FASN_KV_SHARED == 0 the eight kernels above are what they were.
-// FASN_KV_SHARED = 3 / 4 (fasn_kvgroups.h) are the two passes of the prefix-groups call, the passes above with one prefix per GROUP of batch
-// elements: 3 is the prefix pass with a workgroup per (K/V head, item of the schedule table, split) - the item names the group, its 128 rows
-// of the SORTED row space and P_g, the lane's b comes from the order table - and 4 the suffix pass with P = P_b from the table. Where 3 / 4
-// share the text of 1 / 2 they do so under FASN_KV_PREFIX_PASS / FASN_KV_SUFFIX_PASS; with FASN_KV_SHARED <= 2 the ten kernels above are
-// what they were.
-#define FASN_KV_PREFIX_PASS (FASN_KV_SHARED == 1 || FASN_KV_SHARED == 3)
-#define FASN_KV_SUFFIX_PASS (FASN_KV_SHARED == 2 || FASN_KV_SHARED == 4)
+// FASN_KV_PASS = FASN_KV_PASS_PREFIX / FASN_KV_PASS_SUFFIX (fasn_kvprefix.h, with the other four at 0; undefined counts as 0: no pass) are the
+// two passes of the calls behind shared prefixes: the prefix pass walks the tiles [0, ceil(P / 64)) of the prefix pages for 128 rows of a row
+// space of ALL batch elements, every lane with the b of its own row and the limit min(P - 1, its base limit), no sink; the suffix pass is the
+// base walk over the tiles [P / 64, ceil(len_b / 64)) of the batch element's own pages, keys below P hidden in the first tile.
+// FASN_KV_GROUPS is orthogonal to FASN_KV_PASS: at 1 the prefix is the one of the batch element's GROUP - the prefix pass takes its rows,
+// its pages and P_g from an item of the schedule table, the suffix pass P_b from the table. With FASN_KV_PASS == 0 the eight kernels above
+// are what they were.
+#define FASN_KV_PASS_PREFIX 1
+#define FASN_KV_PASS_SUFFIX 2
 #if FASN_KV_FP8
 #define FASN_KV_SC c8
 #else
 #define FASN_KV_SC p.c
 #endif
 template <typename Tag, int D>
-#if FASN_KV_SHARED == 1
-__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvshared_prefix_kernel(const KvParams p, const KvShared sh) {
-#elif FASN_KV_SHARED == 2
-__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvshared_suffix_kernel(const KvParams p, const KvShared sh) {
-#elif FASN_KV_SHARED == 3
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX && FASN_KV_GROUPS
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvgroups_prefix_kernel(const KvParams p, const KvGroups gr) {
-#elif FASN_KV_SHARED == 4
+#elif FASN_KV_PASS == FASN_KV_PASS_SUFFIX && FASN_KV_GROUPS
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvgroups_suffix_kernel(const KvParams p, const KvGroups gr) {
+#elif FASN_KV_PASS == FASN_KV_PASS_PREFIX
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvshared_prefix_kernel(const KvParams p, const KvShared sh) {
+#elif FASN_KV_PASS == FASN_KV_PASS_SUFFIX
+__global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvshared_suffix_kernel(const KvParams p, const KvShared sh) {
 #elif FASN_KV_FP8 && FASN_KV_TREE
 __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_fp8_tree_kernel(const KvParams p, const KvFp8 f8, const KvTree tree) {
 #elif FASN_KV_FP8 && FASN_KV_WINDOW
@@ -88,16 +85,8 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     const int hi = lane >> 5;
 
     const int wg = (int)blockIdx.x;
-#if FASN_KV_SHARED == 1
-    // (K/V head, row block, split); the lane's row of the row space rho = b * R + r decides its b. `len` is what the walk covers: P
-    const int split = wg % sh.nsplit;
-    const int bk = wg / sh.nsplit;         // hkv * nrb + row block
-    const int hkv = bk / sh.nrb;
-    const int rho = (bk - hkv * sh.nrb) * KVS_ROWS + (tid >> 6) * 32 + (tid & 31);
-    const int rows_all = p.B * p.R;
-    const int b = rho < rows_all ? rho / p.R : 0;
-    const int len = kvs_prefix_len(sh);
-#elif FASN_KV_SHARED == 3
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX
+#if FASN_KV_GROUPS
     // (K/V head, item, split); an item beyond the table's count leaves before it reads anything else. The item names the group, the first
     // of its 128 rows of the sorted row space, where the group's rows end and P_g; the lane's row decides its slot, the order table its b.
     // From here on the workgroup is a prefix pass behind ONE prefix: `sh` is that call's operand, `len` is what the walk covers, P_g
@@ -119,6 +108,16 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     if (row_ok) b = kvg_order(gr)[slot];
     const int len = item.P;
 #else
+    // (K/V head, row block, split); the lane's row of the row space rho = b * R + r decides its b. `len` is what the walk covers: P
+    const int split = wg % sh.nsplit;
+    const int bk = wg / sh.nsplit;         // hkv * nrb + row block
+    const int hkv = bk / sh.nrb;
+    const int rho = (bk - hkv * sh.nrb) * KVS_ROWS + (tid >> 6) * 32 + (tid & 31);
+    const int rows_all = p.B * p.R;
+    const int b = rho < rows_all ? rho / p.R : 0;
+    const int len = kvs_prefix_len(sh);
+#endif
+#else
     const int split = wg % p.nsplit;
     const int bk = wg / p.nsplit;          // b * Hkv + hkv
     const int b = bk / p.Hkv, hkv = bk % p.Hkv;
@@ -127,13 +126,13 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     const int len = kv_len(p, b);
 #endif
     const int tiles_b = (len + KV_KT - 1) / KV_KT;
-#if FASN_KV_PREFIX_PASS
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX
     const int tps = (tiles_b + sh.nsplit - 1) / sh.nsplit;
     const int t0 = min(split * tps, tiles_b);
-#elif FASN_KV_SUFFIX_PASS
+#elif FASN_KV_PASS == FASN_KV_PASS_SUFFIX
     // the walk starts at the tile that holds key P: the base call's split rule over [tlo, tiles_b), the base call's ranges at P = 0. Tiles
     // below tlo get no request and no table read: their slots may be unset
-#if FASN_KV_SHARED == 4
+#if FASN_KV_GROUPS
     const int P = kvg_prefix_len(gr, p.B, b);   // P_b: the schedule kernel's clamp of the length of the batch element's group, 0 without one
 #else
     const int P = kvs_prefix_len(sh);
@@ -161,8 +160,8 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     const int t1 = min(t0 + tps, tiles_b);
 
     // ---- the lane's row: query head of the group, position, softmax_n, causal limit
-#if FASN_KV_PREFIX_PASS
-#if FASN_KV_SHARED == 3
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX
+#if FASN_KV_GROUPS
     const int r_b = row_ok ? rho - slot * p.R : 0;   // the row inside the lane's own batch element
 #else
     const bool row_ok = rho < rows_all;
@@ -189,10 +188,10 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
 #if FASN_KV_FP8
     float c8 = p.c * f8.ks[b * f8.ksb + hkv * f8.ksh];   // k_scale acts on the fp32 scores: one uniform load in front of the tile loop, like n
 #endif
-#if FASN_KV_SHARED == 1
-    const bool wave_rows = (bk - hkv * sh.nrb) * KVS_ROWS + wave * 32 < rows_all;   // the last row block may be mostly idle
-#elif FASN_KV_SHARED == 3
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX && FASN_KV_GROUPS
     const bool wave_rows = item.row0 + wave * 32 < item.rend;   // the last item of a group may be mostly idle
+#elif FASN_KV_PASS == FASN_KV_PASS_PREFIX
+    const bool wave_rows = (bk - hkv * sh.nrb) * KVS_ROWS + wave * 32 < rows_all;   // the last row block may be mostly idle
 #else
     const bool wave_rows = wave * 32 < p.R;   // a wave without rows only helps staging
 #endif
@@ -232,7 +231,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     // Page ids are wave-uniform and the table does not change while the kernel runs: read through the constant address space they are
     // scalar loads whose wait the compiler places at the first use - the NEXT tile's request - instead of vector loads whose wait
     // would drain the K/V requests just issued. Entries of tiles outside the range are never read.
-#if FASN_KV_PREFIX_PASS
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX
     // the prefix pages: one table for every batch element; entries at or beyond ceil(P / page_size) belong to no tile of the range
     const __attribute__((address_space(4))) int* const bt_row = (const __attribute__((address_space(4))) int*)sh.ptab;
     auto page_of = [&](int tile, int slot) -> int {
@@ -255,7 +254,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
         const uint32_t kbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.krs * EB + SROWB) : 0u;
         const uint32_t vbytes = nvis > 0 ? (uint32_t)((nvis - 1) * (int)p.vrs * EB + SROWB) : 0u;
         const u32x4 krw = make_rsrc_words(kpool + koff, kbytes), vrw = make_rsrc_words(vpool + voff, vbytes);
-#if FASN_KV_SUFFIX_PASS
+#if FASN_KV_PASS == FASN_KV_PASS_SUFFIX
         // the tile that holds key P: its rows below P are the batch element's own rows of a partially shared page and may hold anything.
         // Their lanes ask beyond every range a descriptor can have (kv_build: a tile spans less than 2^31 bytes) and get zeros
         const int lo = u == tlo ? P - tlo * KV_KT : 0;
@@ -281,7 +280,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     };
 
     // ---- online-softmax state of the row (log2 domain); the sink (+n) belongs to split 0
-#if FASN_KV_PREFIX_PASS
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX
     float m_run = -INFINITY;   // (no sink here: it belongs to split 0 of the suffix pass)
     float l_run = 0.f;
 #else
@@ -294,7 +293,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     for (int d = 0; d < DB; ++d)
 #pragma unroll
         for (int r = 0; r < 16; ++r) oacc[d][r] = 0.f;
-#if FASN_KV_PREFIX_PASS
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX
     // last visible key of the row: the base call's limit under the lane's own len_b, and below P
     len_l = min(max(len_l + p.seqlen_add, 0), p.capacity);
     int vis = !row_ok ? -1 : min(len - 1, p.causal ? pos + len_l - p.Sq : len_l - 1);
@@ -306,7 +305,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
 
 #pragma unroll
     for (int s = 0; s < KS; ++s) retire_loads(qf[s]);
-#if !FASN_KV_PREFIX_PASS
+#if FASN_KV_PASS != FASN_KV_PASS_PREFIX
     retire_loads(n_row);
 #endif
 #if FASN_KV_ALIBI
@@ -365,10 +364,10 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
             // the bias is part of the score before the maximum is taken; k0 is the absolute key index in every split
             const float dk0 = (float)(k0 + 4 * hi - qpos);
 #endif
-#if FASN_KV_PREFIX_PASS
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX
             // every lane that has a row sees the whole tile (the rows of a wave belong to several batch elements: a vote, wave-uniform)
             if (__all(!row_ok || k0 + KV_KT - 1 <= vis)) {
-#elif FASN_KV_SUFFIX_PASS
+#elif FASN_KV_PASS == FASN_KV_PASS_SUFFIX
             // ... and the tile holds no key below P
             if (k0 + KV_KT - 1 <= all_vis && k0 >= P) {
 #elif FASN_KV_TREE
@@ -421,7 +420,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-#if FASN_KV_SUFFIX_PASS
+#if FASN_KV_PASS == FASN_KV_PASS_SUFFIX
                         const float y = key <= vis && key >= P ? sacc[kb][r] * FASN_KV_SC : -INFINITY;
 #elif FASN_KV_TREE
                         const float y = ((vm >> (kb * 32 + (r & 3) + 8 * (r >> 2))) & 1ull) != 0ull ? sacc[kb][r] * FASN_KV_SC : -INFINITY;
@@ -478,7 +477,7 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
     // ---- partial result of this key range: un-normalised accumulator + (m, l) per row
-#if FASN_KV_PREFIX_PASS
+#if FASN_KV_PASS == FASN_KV_PASS_PREFIX
     // the prefix partials: [Hkv][nsplit][B * R rows of the row space][D] and [...][2]; `row` becomes the row of that space
     float* po = sh.part_o + ((int64_t)hkv * sh.nsplit + split) * rows_all * D;
     float* pml = sh.part_ml + ((int64_t)hkv * sh.nsplit + split) * rows_all * 2;
@@ -505,5 +504,5 @@ __global__ void __launch_bounds__(256, kv_wg_per_cu(D)) fasn_kvcache_fwd_kernel(
     }
 }
 #undef FASN_KV_SC
-#undef FASN_KV_PREFIX_PASS
-#undef FASN_KV_SUFFIX_PASS
+#undef FASN_KV_PASS_PREFIX
+#undef FASN_KV_PASS_SUFFIX

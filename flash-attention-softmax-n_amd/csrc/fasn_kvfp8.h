@@ -108,26 +108,8 @@ __global__ void __launch_bounds__(256) fasn_kvcache_fp8_combine_kernel(const KvP
     if (rowg >= (int64_t)p.B * p.Hkv * p.R) return;
     const int bk = (int)(rowg / p.R), r = (int)(rowg % p.R);
     const int b = bk / p.Hkv, hkv = bk % p.Hkv, h = hkv * p.G + r / p.Sq, pos = r % p.Sq;
-    float mstar = -INFINITY;
-    for (int s = 0; s < p.nsplit; ++s) mstar = fmaxf(mstar, p.part_ml[(((int64_t)bk * p.nsplit + s) * p.R + r) * 2]);
-    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
-    float l = 0.f;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.nsplit; ++s) {
-        const int64_t base = ((int64_t)bk * p.nsplit + s) * p.R + r;
-        const float ms = p.part_ml[base * 2], ls = p.part_ml[base * 2 + 1];
-        if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
-        const float w = fast_exp2(ms - m_use);
-        l += ls * w;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p.part_o + base * D + c4);
-        acc += a * w;
-    }
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    typename E::vec4 y = E::cvt4(acc * inv * f8.vs[b * f8.vsb + hkv * f8.vsh]);
-    u32x2 raw;
-    __builtin_memcpy(&raw, &y, 8);
-    gstore8(p.o + (b * p.os[0] + h * p.os[1] + (int64_t)pos * p.os[2] + c4) * 2, raw);
-    if (p.lse != nullptr && c4 == 0) p.lse[((int64_t)b * p.H + h) * p.Sq + pos] = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
+    const KvMerged m = kv_merge<D>(c4, p.part_o, p.part_ml, p.nsplit, [&](int s) { return ((int64_t)bk * p.nsplit + s) * p.R + r; });
+    kv_store_decode_row<E>(p, b, h, pos, c4, m, f8.vs[b * f8.vsb + hkv * f8.vsh]);
 }
 
 // fasn_kvprefill_combine_kernel with v_scale[b, hkv], likewise
@@ -155,26 +137,9 @@ __global__ void __launch_bounds__(256) fasn_kvprefill_fp8_combine_kernel(const K
         if (lat != nullptr) *lat = -INFINITY;
         return;
     }
-    float mstar = -INFINITY;
-    for (int s = 0; s < p.nsplit; ++s) mstar = fmaxf(mstar, p.part_ml[((blk * p.nsplit + s) * KVP_ROWS + r) * 2]);
-    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
-    float l = 0.f;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.nsplit; ++s) {
-        const int64_t base = (blk * p.nsplit + s) * KVP_ROWS + r;
-        const float ms = p.part_ml[base * 2], ls = p.part_ml[base * 2 + 1];
-        if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
-        const float w = fast_exp2(ms - m_use);
-        l += ls * w;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p.part_o + base * D + c4);
-        acc += a * w;
-    }
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    typename E::vec4 y = E::cvt4(acc * inv * f8.vs[b * f8.vsb + hkv * f8.vsh]);
-    u32x2 raw;
-    __builtin_memcpy(&raw, &y, 8);
-    gstore8(oat, raw);
-    if (lat != nullptr) *lat = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
+    const KvMerged m = kv_merge<D>(c4, p.part_o, p.part_ml, p.nsplit, [&](int s) { return (blk * p.nsplit + s) * KVP_ROWS + r; });
+    kv_store_row<E>(oat, m, f8.vs[b * f8.vsb + hkv * f8.vsh]);
+    if (lat != nullptr) *lat = kv_lse(m);
 }
 
 // fasn_kvvarlen_combine_kernel with v_scale[b, hkv], likewise: b is the item's
@@ -197,26 +162,9 @@ FASN_KV_LOCAL __global__ void __launch_bounds__(256) fasn_kvvarlen_fp8_combine_k
     const int h = hkv * p.G + g;
     const int64_t tok = (int64_t)it.z + pos;
     char* const oat = p.o + (h * p.os[1] + tok * p.os[2] + c4) * 2;
-    float mstar = -INFINITY;
-    for (int s = 0; s < p.nsplit; ++s) mstar = fmaxf(mstar, p.part_ml[((blk * p.nsplit + s) * KVP_ROWS + r) * 2]);
-    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
-    float l = 0.f;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.nsplit; ++s) {
-        const int64_t base = (blk * p.nsplit + s) * KVP_ROWS + r;
-        const float ms = p.part_ml[base * 2], ls = p.part_ml[base * 2 + 1];
-        if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
-        const float w = fast_exp2(ms - m_use);
-        l += ls * w;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p.part_o + base * D + c4);
-        acc += a * w;
-    }
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    typename E::vec4 y = E::cvt4(acc * inv * f8.vs[it.x * f8.vsb + hkv * f8.vsh]);
-    u32x2 raw;
-    __builtin_memcpy(&raw, &y, 8);
-    gstore8(oat, raw);
-    if (p.lse != nullptr && c4 == 0) p.lse[(int64_t)h * pk.T + tok] = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
+    const KvMerged m = kv_merge<D>(c4, p.part_o, p.part_ml, p.nsplit, [&](int s) { return (blk * p.nsplit + s) * KVP_ROWS + r; });
+    kv_store_row<E>(oat, m, f8.vs[it.x * f8.vsb + hkv * f8.vsh]);
+    if (p.lse != nullptr && c4 == 0) p.lse[(int64_t)h * pk.T + tok] = kv_lse(m);
 }
 
 // ---- quantising append

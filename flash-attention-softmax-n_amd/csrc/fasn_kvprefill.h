@@ -101,26 +101,9 @@ __global__ void __launch_bounds__(256) fasn_kvprefill_combine_kernel(const KvPre
         if (lat != nullptr) *lat = -INFINITY;
         return;
     }
-    float mstar = -INFINITY;
-    for (int s = 0; s < p.nsplit; ++s) mstar = fmaxf(mstar, p.part_ml[((blk * p.nsplit + s) * KVP_ROWS + r) * 2]);
-    const float m_use = (mstar == -INFINITY) ? 0.f : mstar;
-    float l = 0.f;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < p.nsplit; ++s) {
-        const int64_t base = (blk * p.nsplit + s) * KVP_ROWS + r;
-        const float ms = p.part_ml[base * 2], ls = p.part_ml[base * 2 + 1];
-        if (ms == -INFINITY) continue;   // an empty or fully hidden range: nothing to add
-        const float w = fast_exp2(ms - m_use);
-        l += ls * w;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p.part_o + base * D + c4);
-        acc += a * w;
-    }
-    const float inv = l > 0.f ? 1.0f / l : 0.f;
-    typename E::vec4 y = E::cvt4(acc * inv);
-    u32x2 raw;
-    __builtin_memcpy(&raw, &y, 8);
-    gstore8(oat, raw);
-    if (lat != nullptr) *lat = l > 0.f ? (m_use + __builtin_log2f(l)) * kLn2 : -INFINITY;
+    const KvMerged m = kv_merge<D>(c4, p.part_o, p.part_ml, p.nsplit, [&](int s) { return (blk * p.nsplit + s) * KVP_ROWS + r; });
+    kv_store_row<E>(oat, m);
+    if (lat != nullptr) *lat = kv_lse(m);
 }
 
 // fasn_kvcache_append_kernel plus the i < qlen_b test: padding rows of k_new / v_new are neither read nor written.

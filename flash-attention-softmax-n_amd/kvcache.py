@@ -491,6 +491,49 @@ def flash_attention_n_kvcache(
 _SHARED_PREFIX_HEAD_DIMS = (64, 128)   # the head dims the shared-prefix kernels are built for
 
 
+def _refuse_not_behind_prefix(fn, what, query, k_cache, block_table) -> None:
+    """what the calls behind shared prefixes refuse in front of their operands' checks; `what`: "a shared prefix" / "shared prefixes" """
+    if block_table is None:
+        raise ValueError(f"{fn}: a dense cache (block_table=None) is not supported: a shared prefix is a set of pages that several block "
+                         "tables name (paged caches only)")
+    if isinstance(k_cache, Tensor) and k_cache.dtype == torch.float8_e4m3fn:
+        raise TypeError(f"{fn}: a float8 cache is not supported (fp16 and bf16 caches only; the FP8 call is flash_attention_n_kvcache_fp8, "
+                        f"without {what})")
+    if query.dim() == 4 and query.shape[3] in _KV_HEAD_DIMS and query.shape[3] not in _SHARED_PREFIX_HEAD_DIMS:
+        raise ValueError(f"{fn}: head dim {query.shape[3]} is not supported behind {what} (supported: {_SHARED_PREFIX_HEAD_DIMS}; "
+                         "32 and 256 have the kernels of flash_attention_n_kvcache only)")
+
+
+def _is_int32(t, dims) -> bool:
+    return isinstance(t, Tensor) and t.dtype == torch.int32 and t.dim() == dims and t.is_contiguous()
+
+
+def _got(t) -> str:
+    return f"{t.dtype} {tuple(t.shape)}" if isinstance(t, Tensor) else type(t).__name__
+
+
+def _check_on_query_device(query, read, **operands) -> None:
+    for name, t in operands.items():
+        if t.device != query.device:
+            raise RuntimeError(f"{name} is on {t.device}, query on {query.device}: every operand must live on the query's device "
+                               f"({read} are read by the kernels, never on the host)")
+
+
+def _run_behind_prefix(c, operand, ws_fn, fwd_fn):
+    """append -> workspace bytes -> allocate -> the forward `fwd_fn` of the prefix operand, under the query's device"""
+    lib = _lib.load()
+
+    def launch():
+        stream = _stream_ptr(c.dev)
+        _append(lib, c, stream)
+        ws_bytes = getattr(lib, ws_fn)(c.args, operand)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=c.dev)   # (torch's caching allocator: capturable)
+        _lib.check(getattr(lib, fwd_fn)(c.args, operand, ws.data_ptr(), ws_bytes, stream), fwd_fn)
+
+    _on_device(c.dev, launch)
+    return c.out if c.lse is None else (c.out, c.lse)
+
+
 def flash_attention_n_kvcache_shared_prefix(
         query: Tensor,
         k_cache: Tensor,
@@ -530,43 +573,19 @@ def flash_attention_n_kvcache_shared_prefix(
     or beyond P and prefix_table entries at or beyond ceil(P / page_size) are never read. Rows at or beyond len_b may hold anything.
     """
     fn = "flash_attention_n_kvcache_shared_prefix"
-    if block_table is None:
-        raise ValueError(f"{fn}: a dense cache (block_table=None) is not supported: a shared prefix is a set of pages that several block "
-                         "tables name (paged caches only)")
-    if isinstance(k_cache, Tensor) and k_cache.dtype == torch.float8_e4m3fn:
-        raise TypeError(f"{fn}: a float8 cache is not supported (fp16 and bf16 caches only; the FP8 call is flash_attention_n_kvcache_fp8, "
-                        "without a shared prefix)")
-    if query.dim() == 4 and query.shape[3] in _KV_HEAD_DIMS and query.shape[3] not in _SHARED_PREFIX_HEAD_DIMS:
-        raise ValueError(f"{fn}: head dim {query.shape[3]} is not supported behind a shared prefix (supported: {_SHARED_PREFIX_HEAD_DIMS}; "
-                         "32 and 256 have the kernels of flash_attention_n_kvcache only)")
-    if (not isinstance(prefix_table, Tensor) or prefix_table.dtype != torch.int32 or prefix_table.dim() != 1 or prefix_table.shape[0] < 1
-            or not prefix_table.is_contiguous()):
-        got = f"{prefix_table.dtype} {tuple(prefix_table.shape)}" if isinstance(prefix_table, Tensor) else type(prefix_table).__name__
+    _refuse_not_behind_prefix(fn, "a shared prefix", query, k_cache, block_table)
+    if not _is_int32(prefix_table, 1) or prefix_table.shape[0] < 1:
         raise ValueError(f"{fn}: prefix_table must be a contiguous int32 tensor of shape [max_prefix_pages] on the device (at least one "
-                         f"page); got {got}")
+                         f"page); got {_got(prefix_table)}")
     if not isinstance(prefix_len, Tensor) or prefix_len.dtype != torch.int32 or prefix_len.numel() != 1:
-        got = f"{prefix_len.dtype} {tuple(prefix_len.shape)}" if isinstance(prefix_len, Tensor) else type(prefix_len).__name__
         raise ValueError(f"{fn}: prefix_len must be an int32 tensor of one element on the device (it is read by the kernels, never on "
-                         f"the host; not a Python int); got {got}")
-    for name, t in (("prefix_table", prefix_table), ("prefix_len", prefix_len)):
-        if t.device != query.device:
-            raise RuntimeError(f"{name} is on {t.device}, query on {query.device}: every operand must live on the query's device "
-                               "(the prefix length and its page ids are read by the kernels, never on the host)")
+                         f"the host; not a Python int); got {_got(prefix_len)}")
+    _check_on_query_device(query, "the prefix length and its page ids", prefix_table=prefix_table, prefix_len=prefix_len)
     c = _prepare(fn, "kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
                  return_lse)
-    lib = _lib.load()
     prefix = SharedPrefix(prefix_len=prefix_len.data_ptr(), prefix_table=prefix_table.data_ptr(),
                           max_prefix_pages=min(prefix_table.shape[0], _INT_MAX), reserved=0)
-
-    def launch():
-        stream = _stream_ptr(c.dev)
-        _append(lib, c, stream)
-        ws_bytes = lib.fasn_fwd_shared_prefix_workspace_bytes(c.args, prefix)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=c.dev)   # (torch's caching allocator: capturable)
-        _lib.check(lib.fasn_fwd_shared_prefix(c.args, prefix, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_shared_prefix")
-
-    _on_device(c.dev, launch)
-    return c.out if c.lse is None else (c.out, c.lse)
+    return _run_behind_prefix(c, prefix, "fasn_fwd_shared_prefix_workspace_bytes", "fasn_fwd_shared_prefix")
 
 
 def flash_attention_n_kvcache_prefix_groups(
@@ -613,58 +632,32 @@ def flash_attention_n_kvcache_prefix_groups(
     prefix_lens hold, no access leaves the operands.
     """
     fn = "flash_attention_n_kvcache_prefix_groups"
-    if block_table is None:
-        raise ValueError(f"{fn}: a dense cache (block_table=None) is not supported: a shared prefix is a set of pages that several block "
-                         "tables name (paged caches only)")
-    if isinstance(k_cache, Tensor) and k_cache.dtype == torch.float8_e4m3fn:
-        raise TypeError(f"{fn}: a float8 cache is not supported (fp16 and bf16 caches only; the FP8 call is flash_attention_n_kvcache_fp8, "
-                        "without shared prefixes)")
-    if query.dim() == 4 and query.shape[3] in _KV_HEAD_DIMS and query.shape[3] not in _SHARED_PREFIX_HEAD_DIMS:
-        raise ValueError(f"{fn}: head dim {query.shape[3]} is not supported behind shared prefixes (supported: {_SHARED_PREFIX_HEAD_DIMS}; "
-                         "32 and 256 have the kernels of flash_attention_n_kvcache only)")
-
-    def got(t):
-        return f"{t.dtype} {tuple(t.shape)}" if isinstance(t, Tensor) else type(t).__name__
-
-    def int32(t, dims):
-        return isinstance(t, Tensor) and t.dtype == torch.int32 and t.dim() == dims and t.is_contiguous()
-    if not int32(prefix_tables, 2) or prefix_tables.shape[0] < 1 or prefix_tables.shape[1] < 1:
+    _refuse_not_behind_prefix(fn, "shared prefixes", query, k_cache, block_table)
+    if not _is_int32(prefix_tables, 2) or prefix_tables.shape[0] < 1 or prefix_tables.shape[1] < 1:
         raise ValueError(f"{fn}: prefix_tables must be a contiguous int32 tensor of shape [G, max_prefix_pages] on the device (at least one "
-                         f"group and one page); got {got(prefix_tables)}")
+                         f"group and one page); got {_got(prefix_tables)}")
     G = prefix_tables.shape[0]
     if G > _lib.FASN_PREFIX_GROUPS_MAX:
         raise ValueError(f"{fn}: {G} prefix groups exceed the {_lib.FASN_PREFIX_GROUPS_MAX} of one call (the schedule kernel keeps its "
                          "counters per group in LDS)")
-    if not int32(prefix_lens, 1):
+    if not _is_int32(prefix_lens, 1):
         raise ValueError(f"{fn}: prefix_lens must be a contiguous int32 tensor of shape [G] on the device (it is read by the kernels, never "
-                         f"on the host); got {got(prefix_lens)}")
+                         f"on the host); got {_got(prefix_lens)}")
     if prefix_lens.shape[0] != G:
         raise ValueError(f"{fn}: prefix_lens has {prefix_lens.shape[0]} entries, prefix_tables {G} rows: one length per prefix")
-    if not int32(prefix_group, 1):
+    if not _is_int32(prefix_group, 1):
         raise ValueError(f"{fn}: prefix_group must be a contiguous int32 tensor of shape [B] on the device (it is read by the kernels, never "
-                         f"on the host); got {got(prefix_group)}")
+                         f"on the host); got {_got(prefix_group)}")
     if query.dim() == 4 and prefix_group.shape[0] != query.shape[0]:
         raise ValueError(f"{fn}: prefix_group has {prefix_group.shape[0]} entries, the batch {query.shape[0]} elements: one group per batch "
                          "element (any value outside [0, G) for none)")
-    for name, t in (("prefix_tables", prefix_tables), ("prefix_lens", prefix_lens), ("prefix_group", prefix_group)):
-        if t.device != query.device:
-            raise RuntimeError(f"{name} is on {t.device}, query on {query.device}: every operand must live on the query's device "
-                               "(the prefixes, their lengths and the groups are read by the kernels, never on the host)")
+    _check_on_query_device(query, "the prefixes, their lengths and the groups", prefix_tables=prefix_tables, prefix_lens=prefix_lens,
+                           prefix_group=prefix_group)
     c = _prepare(fn, "kvcache", query, k_cache, v_cache, cache_seqlens, block_table, k_new, v_new, softmax_n_param, scale, is_causal,
                  return_lse)
-    lib = _lib.load()
     groups = PrefixGroups(prefix_lens=prefix_lens.data_ptr(), prefix_tables=prefix_tables.data_ptr(), prefix_group=prefix_group.data_ptr(),
                           num_groups=G, max_prefix_pages=min(prefix_tables.shape[1], _INT_MAX), reserved=0)
-
-    def launch():
-        stream = _stream_ptr(c.dev)
-        _append(lib, c, stream)
-        ws_bytes = lib.fasn_fwd_prefix_groups_workspace_bytes(c.args, groups)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=c.dev)   # (torch's caching allocator: capturable)
-        _lib.check(lib.fasn_fwd_prefix_groups(c.args, groups, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_prefix_groups")
-
-    _on_device(c.dev, launch)
-    return c.out if c.lse is None else (c.out, c.lse)
+    return _run_behind_prefix(c, groups, "fasn_fwd_prefix_groups_workspace_bytes", "fasn_fwd_prefix_groups")
 
 
 def flash_attention_n_kvcache_prefill(

@@ -1,13 +1,15 @@
-"""What the prefix-groups decode tests share (flash_attention_n_kvcache_prefix_groups / fasn_fwd_prefix_groups): the builder of the virtual
-cache behind G prefixes - kv_shared.Shared extended to groups - its gather to dense per-sequence K / V, the runners of the parity and the
-witness cases, the integer model of the schedule table and - for the suite without a GPU - the groups operand over fake pointers, the
-named plan cases and the plan rule restated in Python. A plain module: no tests, importable without a GPU. It imports kv_shared,
-kv_support and kv_witness and edits none of them.
+"""What the tests of the decodes behind shared prefixes share (flash_attention_n_kvcache_shared_prefix / fasn_fwd_shared_prefix and
+flash_attention_n_kvcache_prefix_groups / fasn_fwd_prefix_groups): the builder of the virtual cache behind G prefixes - `Groups`, and
+`Shared`, its case of ONE prefix that every batch element is behind - its gather to dense per-sequence K / V, the runners of the parity
+and the witness cases, the integer model of the schedule table and - for the suites without a GPU - the operands over fake pointers, the
+named plan cases and the plan rules restated in Python. A plain module: no tests, importable without a GPU. It imports kv_support and
+kv_witness and edits neither.
 
 The virtual cache of batch element b with g = group[b] in [0, G) under P_g: key row j < P_g is row j % page of page
 prefix_tables[g, j // page], key row j >= P_g is the row block_table[b] names; any other group value: the own rows alone. `Groups` builds
 it from a dense picture kd / vd [B, Hkv, capacity, D]: the keys of prefix g are those of its FIRST member in batch order, which the dense
-picture of every other member is overwritten with, so `kd` / `vd` of the object are what every batch element sees.
+picture of every other member is overwritten with, so `kd` / `vd` of the object are what every batch element sees and the references
+are computed on them.
 
 What the memory contract lets hold anything does: the own slots of a member that lie wholly below P_g point at the poison page (NaN), its
 own rows below P_g in the page that holds key P_g are NaN, the prefix pages' rows at or beyond P_g are NaN, a prefix table row's entries at
@@ -20,11 +22,10 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import kv_args as ka        # noqa: E402
-import kv_shared as sp      # noqa: E402
 import kv_support as ks     # noqa: E402
 import kv_witness as kw     # noqa: E402
 
-NAN = sp.NAN
+NAN = float("nan")
 GROUPS_MAX = 1024   # include/fasn.h: FASN_PREFIX_GROUPS_MAX
 
 
@@ -33,8 +34,8 @@ def effective(group, plens):
     return [plens[g] if 0 <= g < len(plens) else 0 for g in group]
 
 
-class Groups(sp.Shared):
-    """kv_shared.Shared behind G prefixes: pool k / v, `table` [B, max_pages], `lens` [B], `prefix_tables` [G, prefix_pages], `plens` [G]
+class Groups:
+    """pool k / v, `table` [B, max_pages], `lens` [B], `prefix_tables` [G, prefix_pages], `plens` [G]
     and `group` [B] (device), and the dense virtual picture kd / vd. `plens`: the EFFECTIVE lengths (what the kernels clamp prefix_lens
     to); `group`: any integers, those outside [0, G) mean no prefix. `share`: the own tables name the prefix pages below P_b (page
     multiples) instead of the poison page - tables the base call can walk too."""
@@ -105,18 +106,60 @@ class Groups(sp.Shared):
         return res
 
 
-data = sp.data
-check = sp.check   # (kv_support's gates on gr.gather(): the object has what kv_shared.check reads)
+class Shared(Groups):
+    """Groups with G = 1 and every batch element in group 0: `prefix_table` [prefix_pages], `plen` [1] (device) and `P`, the effective
+    prefix length, are the group fields of that one prefix - read-only views: a test that wants another table, length tensor or P
+    writes into them in place (`sh.prefix_table[:] = ...`, `sh.plen.fill_(...)`) or builds another object; assigning to them raises."""
+
+    def __init__(self, kd, vd, lens, P, page, max_pages, seed, prefix_pages=None, alloc_all=False, share=False):
+        super().__init__(kd, vd, lens, [0] * kd.shape[0], [P], page, max_pages, seed, prefix_pages, alloc_all, share)
+
+    prefix_table = property(lambda self: self.prefix_tables[0])
+    plen = property(lambda self: self.plens)
+    P = property(lambda self: self.plens_list[0])
 
 
-def call(pkg, gr, q, n, causal=True, prefix_lens=None, prefix_group=None, **kw):
+def data(dev, B, H, Hkv, Sq, D, dtype, page, max_pages, seed):
+    q = ks._rand((B, H, Sq, D), dtype, dev, seed)
+    kd = ks._rand((B, Hkv, page * max_pages, D), dtype, dev, seed + 1)
+    vd = ks._rand((B, Hkv, page * max_pages, D), dtype, dev, seed + 2, std=1.0)
+    return q, kd, vd
+
+
+def check(pkg, sh, out, lse, q, n, causal, dtype, what, lens=None, scale=None):
+    """kv_support's gates on the gathered virtual cache, with flash_attention_n as second witness (ks._check_all)"""
+    lens = sh.lens_list if lens is None else lens
+    kg, vg = sh.gather(lens)
+    return ks._check_all(pkg, out, lse, q, kg, vg, lens, [q.shape[2]] * q.shape[0], n, causal, dtype, what, True, scale)
+
+
+def shared_call(pkg, sh, q, n, causal=True, prefix_len=None, **kw):
+    return pkg.flash_attention_n_kvcache_shared_prefix(q, sh.k, sh.v, sh.lens, sh.table, sh.prefix_table, sh.plen if prefix_len is None else prefix_len,
+                                                       softmax_n_param=n, is_causal=causal, return_lse=True, **kw)
+
+
+def groups_call(pkg, gr, q, n, causal=True, prefix_lens=None, prefix_group=None, **kw):
     return pkg.flash_attention_n_kvcache_prefix_groups(q, gr.k, gr.v, gr.lens, gr.table, gr.prefix_tables,
                                                        gr.plens if prefix_lens is None else prefix_lens,
                                                        gr.group if prefix_group is None else prefix_group,
                                                        softmax_n_param=n, is_causal=causal, return_lse=True, **kw)
 
 
-def witness_run(pkg, case, inp, group, plens, seed=1):
+# ---------------------------------------------------------------- the witnesses of kv_witness behind shared prefixes
+def witness_case(H, Hkv, D, Sq, lens, page=64, causal=True, max_pages=None):
+    return kw.Case("decode", H, Hkv, D, Sq, lens, page=page, causal=causal, max_pages=max_pages)
+
+
+def shared_witness_run(pkg, case, inp, P, seed=1):
+    """kv_witness.run_decode behind a prefix of P keys: (the per-sequence rows, the inputs as every batch element sees them - the dense
+    picture with the prefix of batch element 0 - for kv_witness.reference)"""
+    sh = Shared(inp["kd"], inp["vd"], case.lens, P, case.page, case.max_pages, seed)
+    out, lse = pkg.flash_attention_n_kvcache_shared_prefix(inp["q"], sh.k, sh.v, sh.lens, sh.table, sh.prefix_table, sh.plen,
+                                                           softmax_n_param=inp["n"], scale=inp["scale"], is_causal=case.causal, return_lse=True)
+    return kw._rows_of(case, out, lse, False), dict(inp, kd=sh.kd, vd=sh.vd)
+
+
+def groups_witness_run(pkg, case, inp, group, plens, seed=1):
     """kv_witness.run_decode behind the prefixes `plens` with the batch elements assigned by `group`: (the per-sequence rows, the inputs as
     every batch element sees them, for kv_witness.reference)"""
     gr = Groups(inp["kd"], inp["vd"], case.lens, group, plens, case.page, case.max_pages, seed)
@@ -170,14 +213,28 @@ def read_table(ws, partial_bytes, B, R, G):
             [it[3] for it in items[:n_items]])
 
 
-# ---------------------------------------------------------------- without a GPU: the operand over fake pointers, plan cases, the plan rule
+# ---------------------------------------------------------------- without a GPU: the operands over fake pointers, plan cases, the plan rules
+def _prefix(pkg, pages=8, plen=ka.DUMMY + 256, table=ka.DUMMY + 512, reserved=0):
+    return pkg._lib.SharedPrefix(prefix_len=plen, prefix_table=table, max_prefix_pages=pages, reserved=reserved)
+
+
 def _groups(pkg, G=4, pages=8, lens=ka.DUMMY + 256, tables=ka.DUMMY + 512, group=ka.DUMMY + 1024, reserved=0):
     return pkg._lib.PrefixGroups(prefix_lens=lens, prefix_tables=tables, prefix_group=group, num_groups=G, max_prefix_pages=pages,
                                  reserved=reserved)
 
 
+# name -> (the decode block's shape, max_prefix_pages)
+SHARED_PLAN_CASES = {
+    "gqa8_long_prefix": (dict(B=64, H=64, Hkv=8, Sq=1, page=256, max_pages=40), 32),
+    "mha_long_prefix": (dict(B=64, H=16, Hkv=16, Sq=1, page=256, max_pages=40), 32),
+    "gqa8_short_prefix": (dict(B=64, H=64, Hkv=8, Sq=1, page=256, max_pages=20), 4),
+    "one_sequence": (dict(B=1, H=64, Hkv=8, Sq=1, page=256, max_pages=40), 32),
+    "straddle": (dict(B=10, H=6, Hkv=2, Sq=5, page=64, max_pages=8), 3),
+    "prefix_beyond_capacity": (dict(B=4, H=8, Hkv=2, Sq=4, page=64, max_pages=32), 48),
+    "full_rows": (dict(B=3, H=64, Hkv=2, Sq=4, page=128, max_pages=64), 64),
+}
 # name -> (the decode block's shape, num_groups, max_prefix_pages)
-PLAN_CASES = {
+GROUPS_PLAN_CASES = {
     "four_prompts_gqa8": (dict(B=64, H=64, Hkv=8, Sq=1, page=256, max_pages=40), 4, 32),
     "four_prompts_mha": (dict(B=64, H=16, Hkv=16, Sq=1, page=256, max_pages=40), 4, 32),
     "one_group": (dict(B=64, H=64, Hkv=8, Sq=1, page=256, max_pages=40), 1, 32),
@@ -189,19 +246,31 @@ PLAN_CASES = {
 }
 
 
-def plan_rule(B, H, Hkv, Sq, D, page, max_pages, G, prefix_pages):
-    """(grid of the prefix pass, of the suffix pass, of the combine, bytes of the partials, workspace bytes) as include/fasn.h states them;
-    the schedule kernel is one workgroup"""
+def _plan(B, H, Hkv, Sq, D, page, max_pages, prefix_pages, units):
+    """what the two rules share, `units` being the 128-row units the prefix pass has workgroups for: (grid of the prefix pass, of the
+    suffix pass, of the combine, bytes of the partials) as include/fasn.h states them"""
     R = (H // Hkv) * Sq
     cap = page * max_pages
     target = 1024
     nsplit = max(1, min(-(-target // (B * Hkv)), -(-cap // 64) // max(4, R // 8)))
-    imax = items_max(B, R, G)
     pcap = min(prefix_pages * page, cap)
-    nsplit_p = max(1, min(-(-target // (Hkv * imax)), -(-pcap // 64) // 16))
+    nsplit_p = max(1, min(-(-target // (Hkv * units)), -(-pcap // 64) // 16))
     partials = (B * Hkv * nsplit * R + Hkv * nsplit_p * B * R) * (D + 2) * 4
-    ws = (partials + 15) // 16 * 16 + 4 * table_ints(B, R, G)
-    return Hkv * imax * nsplit_p, B * Hkv * nsplit, -(-B * Hkv * R * (D // 4) // 256), partials, ws
+    return Hkv * units * nsplit_p, B * Hkv * nsplit, -(-B * Hkv * R * (D // 4) // 256), partials
 
 
-lds_bytes = sp.lds_bytes
+def shared_plan_rule(B, H, Hkv, Sq, D, page, max_pages, prefix_pages):
+    """(grid of the prefix pass, of the suffix pass, of the combine, workspace bytes): the units are the blocks of the row space"""
+    return _plan(B, H, Hkv, Sq, D, page, max_pages, prefix_pages, -(-B * (H // Hkv) * Sq // ROWS))
+
+
+def groups_plan_rule(B, H, Hkv, Sq, D, page, max_pages, G, prefix_pages):
+    """(grid of the prefix pass, of the suffix pass, of the combine, bytes of the partials, workspace bytes): the units are the most items
+    a table can hold, the table lies behind the partials; the schedule kernel is one workgroup"""
+    R = (H // Hkv) * Sq
+    plan = _plan(B, H, Hkv, Sq, D, page, max_pages, prefix_pages, items_max(B, R, G))
+    return (*plan, (plan[3] + 15) // 16 * 16 + 4 * table_ints(B, R, G))
+
+
+def lds_bytes(D):
+    return 2 * (3 if D <= 64 else 2) * 64 * D * 2

@@ -1,5 +1,5 @@
 """flash_attention_n_kvcache_prefix_groups on the GPU: decode behind several shared prefixes in one call equals flash_attention_n_kvcache
-on the virtual cache (tests/kv_groups.py) - parity with two witnesses over interleaved groups, groups without members, a group whose rows
+on the virtual cache (tests/kv_prefix.py) - parity with two witnesses over interleaved groups, groups without members, a group whose rows
 fill more than one item; bit equality with the shared-prefix call (G = 1) and with the base call (nobody grouped); prefix_lens clamped per
 group; the memory contract; every key once and the sink once (kv_witness A), one key decides (kv_witness B); the schedule table against
 its integer model; the append; one captured graph for every assignment; and the refusals. Page 64, at most 512 keys, B at most 40 - but
@@ -12,8 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import kv_groups as kg      # noqa: E402
-import kv_shared as sp      # noqa: E402
+import kv_prefix as kg      # noqa: E402
 import kv_support as ks     # noqa: E402
 import kv_witness as kw     # noqa: E402
 
@@ -36,7 +35,7 @@ def _n(kind, B, H, dev, seed):
 
 def _both(pkg, gr, q, n, dtype, what):
     for causal in (True, False):
-        out, lse = kg.call(pkg, gr, q, n, causal)
+        out, lse = kg.groups_call(pkg, gr, q, n, causal)
         kg.check(pkg, gr, out, lse, q, n, causal, dtype, f"{what} causal={causal}")
 
 
@@ -96,12 +95,12 @@ def test_parity_a_group_of_33(pkg, dev, D, dt):
 def test_one_group_is_the_shared_prefix_call(pkg, dev, D, dt, Sq):
     dtype, P = DTYPES[dt], 2 * PAGE + 37
     lens = [3 * PAGE + 1, P, 37, 0, 2 * PAGE, 5 * PAGE]
-    q, kd, vd = sp.data(dev, 6, 8, 2, Sq, D, dtype, PAGE, 5, 301)
-    sh = sp.Shared(kd, vd, lens, P, PAGE, 5, 7, prefix_pages=3)
+    q, kd, vd = kg.data(dev, 6, 8, 2, Sq, D, dtype, PAGE, 5, 301)
+    sh = kg.Shared(kd, vd, lens, P, PAGE, 5, 7, prefix_pages=3)
     n = ks._n_values((6, 8), dev, 6)
     zeros = torch.zeros(6, dtype=torch.int32, device=dev)
     for causal in (True, False):
-        want, want_lse = sp.call(pkg, sh, q, n, causal)
+        want, want_lse = kg.shared_call(pkg, sh, q, n, causal)
         out, lse = pkg.flash_attention_n_kvcache_prefix_groups(q, sh.k, sh.v, sh.lens, sh.table, sh.prefix_table.view(1, -1), sh.plen, zeros,
                                                                softmax_n_param=n, is_causal=causal, return_lse=True)
         assert torch.equal(out, want) and torch.equal(lse, want_lse), f"G = 1 is not the shared-prefix call bit for bit (causal={causal})"
@@ -118,7 +117,7 @@ def test_nobody_grouped_is_the_base_call(pkg, dev, D, dt, Sq):
     lens_junk = torch.tensor([2 ** 31 - 1, -5, 77], dtype=torch.int32, device=dev)
     for causal in (True, False):
         want, want_lse = pkg.flash_attention_n_kvcache(q, gr.k, gr.v, gr.lens, block_table=gr.table, softmax_n_param=n, is_causal=causal, return_lse=True)
-        out, lse = kg.call(pkg, gr, q, n, causal, prefix_lens=lens_junk)
+        out, lse = kg.groups_call(pkg, gr, q, n, causal, prefix_lens=lens_junk)
         assert torch.equal(out, want) and torch.equal(lse, want_lse), f"nobody grouped is not the base call bit for bit (causal={causal})"
 
 
@@ -128,13 +127,13 @@ def test_out_of_range_groups_are_no_group_and_runs_repeat(pkg, dev):
     q, kd, vd = kg.data(dev, 7, 8, 2, 3, 64, dtype, PAGE, 5, 321)
     gr = kg.Groups(kd, vd, MIXED_LENS, MIXED, MIXED_PLENS, PAGE, 5, 17, prefix_pages=4)
     n = ks._n_values((7, 8), dev, 5)
-    want, want_lse = kg.call(pkg, gr, q, n)
+    want, want_lse = kg.groups_call(pkg, gr, q, n)
     kg.check(pkg, gr, want, want_lse, q, n, True, dtype, "the -1 run")
     for other in (3, -7, 2 ** 31 - 1):
         group = torch.tensor([g if g != -1 else other for g in MIXED], dtype=torch.int32, device=dev)
-        out, lse = kg.call(pkg, gr, q, n, prefix_group=group)
+        out, lse = kg.groups_call(pkg, gr, q, n, prefix_group=group)
         assert torch.equal(out, want) and torch.equal(lse, want_lse), f"prefix_group = {other} is not 'no shared prefix'"
-    again, again_lse = kg.call(pkg, gr, q, n)
+    again, again_lse = kg.groups_call(pkg, gr, q, n)
     assert torch.equal(again, want) and torch.equal(again_lse, want_lse), "a second run differs"
 
 
@@ -146,7 +145,7 @@ def test_prefix_lens_are_clamped_per_group(pkg, dev):
     gr = kg.Groups(kd, vd, lens, group, (0, 2 * PAGE, 0, 2 * PAGE), PAGE, 5, 3, prefix_pages=2)
     n = ks._n_values((8, 8), dev, 9)
     raw = torch.tensor([-5, 10000, -2 ** 31, 2 ** 31 - 1], dtype=torch.int32, device=dev)
-    out, lse = kg.call(pkg, gr, q, n, True, prefix_lens=raw)
+    out, lse = kg.groups_call(pkg, gr, q, n, True, prefix_lens=raw)
     kg.check(pkg, gr, out, lse, q, n, True, torch.bfloat16, "prefix_lens clamped per group")
 
 
@@ -176,7 +175,7 @@ def test_memory_contract(pkg, dev, D, dt):
     assert torch.isnan(gr.k[int(tab[0, 3]), 1:]).all()                                # rows at or beyond len_b
     n = ks._n_values((7, 8), dev, 4)
     for causal in (True, False):
-        out, lse = kg.call(pkg, gr, q, n, causal)
+        out, lse = kg.groups_call(pkg, gr, q, n, causal)
         assert torch.isfinite(out).all() and not torch.isnan(lse).any()
         kg.check(pkg, gr, out, lse, q, n, causal, dtype, f"contract D={D} {dt} causal={causal}")
 
@@ -193,14 +192,14 @@ def test_every_key_once_and_the_sink_once(pkg, dev, D, dt, Sq, nkind):
     dtype = DTYPES[dt]
     lens = [40, 62, 63, 64, 65, 66, 130, 200, 0, 64, 65, 63]
     group = [0, 1, 2, 0, 1, 2, 0, 1, 2, -1, 0, 1]
-    case = sp.witness_case(8, 2, D, Sq, lens)
+    case = kg.witness_case(8, 2, D, Sq, lens)
     inp = kw.inputs_a(case, dtype, dev, 68)
     if nkind == "tensor":
         inp["n"] = ks._n_values((case.B, case.H), dev, 17)
         assert (inp["n"] == 0).any() and (inp["n"] > 0).any()
     else:
         inp["n"] = torch.tensor(0.0 if nkind == "zero" else 1.0, device=dev)
-    got, seen = kg.witness_run(pkg, case, inp, group, WITNESS_PLENS)
+    got, seen = kg.groups_witness_run(pkg, case, inp, group, WITNESS_PLENS)
     refs = kw.reference(case, seen)
     kw.condition_a(refs, dtype)
     ratios = [kw.gate_a(o, lse, r) for (o, lse), r in zip(got, refs)]
@@ -218,9 +217,9 @@ def test_one_key_decides(pkg, dev, D, dt, Sq, form):
     dtype = DTYPES[dt]
     lens = [40, 63, 66, 62, 64, 65, 130, 200, 3, 0, 64, 67]
     group = [0, 1, 2, 0, 1, 2, -1, 1, 2, 0, 0, 1]
-    case = sp.witness_case(8, 2, D, Sq, lens)
+    case = kg.witness_case(8, 2, D, Sq, lens)
     inp = kw.inputs_b(case, form, dtype, dev, 23)
-    got, seen = kg.witness_run(pkg, case, inp, group, WITNESS_PLENS)
+    got, seen = kg.groups_witness_run(pkg, case, inp, group, WITNESS_PLENS)
     refs = kw.reference(case, seen)
     ratios, kinds = [], set()
     for b, ((o, lse), r) in enumerate(zip(got, refs)):
@@ -246,7 +245,7 @@ def _table_of(pkg, dev, H, Hkv, Sq, group, G, plens, seed):
     ops = pkg._lib.PrefixGroups(prefix_lens=gr.plens.data_ptr(), prefix_tables=gr.prefix_tables.data_ptr(), prefix_group=gr.group.data_ptr(),
                                 num_groups=G, max_prefix_pages=2, reserved=0)
     need = lib.fasn_fwd_prefix_groups_workspace_bytes(c.args, ops)
-    rule = kg.plan_rule(B, H, Hkv, Sq, D, PAGE, max_pages, G, 2)
+    rule = kg.groups_plan_rule(B, H, Hkv, Sq, D, PAGE, max_pages, G, 2)
     assert need == rule[4]
     ws = torch.full((need,), 0xA5, dtype=torch.uint8, device=dev)
     pkg._lib.check(lib.fasn_fwd_prefix_groups(c.args, ops, ws.data_ptr(), need, pkg.kvcache._stream_ptr(dev)), "fasn_fwd_prefix_groups")
@@ -282,7 +281,7 @@ def test_append(pkg, dev, D, dt):
     kn = torch.stack([gr.kd[b, :, old[b]:old[b] + Sq] for b in range(B)])
     vn = torch.stack([gr.vd[b, :, old[b]:old[b] + Sq] for b in range(B)])
     n = ks._n_values((B, 8), dev, 2)
-    out, lse = kg.call(pkg, gr, q, n, True, k_new=kn, v_new=vn)
+    out, lse = kg.groups_call(pkg, gr, q, n, True, k_new=kn, v_new=vn)
     new = [ln + Sq for ln in old]
     kgath, vgath = gr.gather(new)
     assert torch.equal(kgath, ks._visible_dense(gr.kd, new)[:, :, :kgath.shape[2]]) and torch.equal(vgath, ks._visible_dense(gr.vd, new)[:, :, :vgath.shape[2]])
@@ -316,7 +315,7 @@ def test_one_graph_serves_every_assignment(pkg, dev):
             static[a].copy_(getattr(gr, a))
         g.replay()
         torch.cuda.synchronize()
-        want, want_lse = kg.call(pkg, gr, q, n, True)
+        want, want_lse = kg.groups_call(pkg, gr, q, n, True)
         assert torch.equal(out, want) and torch.equal(lse, want_lse), f"replay differs from the eager call for groups {gr.group_list}"
         kg.check(pkg, gr, out, lse, q, n, True, dtype, f"graph groups={gr.group_list}")
 

@@ -1,5 +1,5 @@
 """flash_attention_n_kvcache_shared_prefix on the GPU: decode behind a shared prefix equals flash_attention_n_kvcache on the virtual cache
-(tests/kv_shared.py) - parity with two witnesses, rows of one sequence in two row blocks, P between the limits of one sequence's rows,
+(tests/kv_prefix.py) - parity with two witnesses, rows of one sequence in two row blocks, P between the limits of one sequence's rows,
 the memory contract, every key once and the sink once (kv_witness A), one key decides (kv_witness B), the base call on truly shared
 tables, the append, one captured graph for every prefix, and the refusals. Page 64 unless said."""
 import os
@@ -9,7 +9,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import kv_shared as sp      # noqa: E402
+import kv_prefix as sp      # noqa: E402
 import kv_support as ks     # noqa: E402
 import kv_witness as kw     # noqa: E402
 
@@ -35,7 +35,7 @@ def test_parity_on_the_virtual_cache(pkg, dev, i):
     sh = sp.Shared(kd, vd, lens, P, PAGE, 5, 7 + i, prefix_pages=3)
     n = _n(i, 5, H, dev, 50 + i)
     for causal in (True, False):
-        out, lse = sp.call(pkg, sh, q, n, causal)
+        out, lse = sp.shared_call(pkg, sh, q, n, causal)
         sp.check(pkg, sh, out, lse, q, n, causal, dtype, f"D={D} {dt} H={H}/{Hkv} Sq={Sq} P={P} causal={causal}")
 
 
@@ -46,7 +46,7 @@ def test_prefix_len_is_clamped(pkg, dev, plen, P):
     q, kd, vd = sp.data(dev, 5, 8, 2, 4, 64, torch.bfloat16, PAGE, 5, 31)
     sh = sp.Shared(kd, vd, lens, P, PAGE, 5, 3, prefix_pages=2)
     n = ks._n_values((5, 8), dev, 9)
-    out, lse = sp.call(pkg, sh, q, n, True, prefix_len=torch.tensor([plen], dtype=torch.int32, device=dev))
+    out, lse = sp.shared_call(pkg, sh, q, n, True, prefix_len=torch.tensor([plen], dtype=torch.int32, device=dev))
     sp.check(pkg, sh, out, lse, q, n, True, torch.bfloat16, f"prefix_len={plen}")
 
 
@@ -59,7 +59,7 @@ def test_rows_of_one_sequence_in_two_row_blocks(pkg, dev, D, dt):
     sh = sp.Shared(kd, vd, lens, 100, PAGE, 4, 5, prefix_pages=2)
     n = ks._n_values((10, 6), dev, 8)
     for causal in (True, False):
-        out, lse = sp.call(pkg, sh, q, n, causal)
+        out, lse = sp.shared_call(pkg, sh, q, n, causal)
         sp.check(pkg, sh, out, lse, q, n, causal, dtype, f"straddle D={D} {dt} causal={causal}")
 
 
@@ -70,7 +70,7 @@ def test_prefix_ends_between_the_limits_of_one_sequences_rows(pkg, dev, D, causa
     q, kd, vd = sp.data(dev, 2, 8, 2, 4, D, torch.float16, PAGE, 3, 71)
     sh = sp.Shared(kd, vd, [70, 70], 68, PAGE, 3, 11)
     for n in (1.0, 0.0):
-        out, lse = sp.call(pkg, sh, q, n, causal)
+        out, lse = sp.shared_call(pkg, sh, q, n, causal)
         sp.check(pkg, sh, out, lse, q, n, causal, torch.float16, f"P=68 len=70 D={D} causal={causal} n={n}")
 
 
@@ -94,7 +94,7 @@ def test_memory_contract(pkg, dev, D, dt):
     assert torch.isnan(sh.k[own, 1:]).all()                                          # rows at or beyond len_b
     n = ks._n_values((6, 8), dev, 4)
     for causal in (True, False):
-        out, lse = sp.call(pkg, sh, q, n, causal)
+        out, lse = sp.shared_call(pkg, sh, q, n, causal)
         assert torch.isfinite(out).all() and not torch.isnan(lse).any()
         sp.check(pkg, sh, out, lse, q, n, causal, dtype, f"contract D={D} {dt} causal={causal}")
 
@@ -112,7 +112,7 @@ def test_every_key_once_and_the_sink_once(pkg, dev, D, dt, Sq, P, nkind):
         assert (inp["n"] == 0).any() and (inp["n"] > 0).any()
     else:
         inp["n"] = torch.tensor(0.0 if nkind == "zero" else 1.0, device=dev)
-    got, seen = sp.witness_run(pkg, case, inp, P)
+    got, seen = sp.shared_witness_run(pkg, case, inp, P)
     refs = kw.reference(case, seen)
     kw.condition_a(refs, dtype)
     ratios = [kw.gate_a(o, lse, r) for (o, lse), r in zip(got, refs)]
@@ -131,7 +131,7 @@ def test_one_key_decides(pkg, dev, D, dt, Sq, P, form):
     dtype = DTYPES[dt]
     case = sp.witness_case(8, 2, D, Sq, [40, P - 1, P, P + 1, P + 2, 130, 200, 3, 0])
     inp = kw.inputs_b(case, form, dtype, dev, 23)
-    got, seen = sp.witness_run(pkg, case, inp, P)
+    got, seen = sp.shared_witness_run(pkg, case, inp, P)
     refs = kw.reference(case, seen)
     ratios, kinds = [], set()
     for b, ((o, lse), r) in enumerate(zip(got, refs)):
@@ -155,11 +155,11 @@ def test_against_the_base_call(pkg, dev, D, dt, Sq):
     n = ks._n_values((6, 8), dev, 6)
     for causal in (True, False):
         base, base_lse = pkg.flash_attention_n_kvcache(q, sh.k, sh.v, sh.lens, block_table=sh.table, softmax_n_param=n, is_causal=causal, return_lse=True)
-        out, lse = sp.call(pkg, sh, q, n, causal)
+        out, lse = sp.shared_call(pkg, sh, q, n, causal)
         ks._check(out, base.float(), dtype, f"vs base D={D} causal={causal} out")
         ks._check_lse(lse, base_lse, f"vs base D={D} causal={causal} lse")
         print(f"max |shared - base| = {(out.float() - base.float()).abs().max().item():.3e}")
-        out0, lse0 = sp.call(pkg, sh, q, n, causal, prefix_len=torch.zeros(1, dtype=torch.int32, device=dev))
+        out0, lse0 = sp.shared_call(pkg, sh, q, n, causal, prefix_len=torch.zeros(1, dtype=torch.int32, device=dev))
         assert torch.equal(out0, base) and torch.equal(lse0, base_lse), "prefix_len = 0 is not the base call bit for bit"
 
 
@@ -174,7 +174,7 @@ def test_append(pkg, dev, D, dt):
     kn = torch.stack([sh.kd[b, :, old[b]:old[b] + Sq] for b in range(B)])
     vn = torch.stack([sh.vd[b, :, old[b]:old[b] + Sq] for b in range(B)])
     n = ks._n_values((B, 8), dev, 2)
-    out, lse = sp.call(pkg, sh, q, n, True, k_new=kn, v_new=vn)
+    out, lse = sp.shared_call(pkg, sh, q, n, True, k_new=kn, v_new=vn)
     new = [ln + Sq for ln in old]
     kg, vg = sh.gather(new)
     assert torch.equal(kg, ks._visible_dense(sh.kd, new)[:, :, :kg.shape[2]]) and torch.equal(vg, ks._visible_dense(sh.vd, new)[:, :, :vg.shape[2]])
@@ -204,7 +204,7 @@ def test_one_graph_serves_every_prefix(pkg, dev):
             static[a].copy_(getattr(sh, a))
         g.replay()
         torch.cuda.synchronize()
-        want, want_lse = sp.call(pkg, sh, q, n, True)
+        want, want_lse = sp.shared_call(pkg, sh, q, n, True)
         assert torch.equal(out, want) and torch.equal(lse, want_lse), f"replay differs from the eager call at P = {sh.P}"
         sp.check(pkg, sh, out, lse, q, n, True, dtype, f"graph P={sh.P}")
 

@@ -1,6 +1,6 @@
 """Decode behind several shared prefixes (fasn_fwd_prefix_groups), without a GPU: the operand's layout, the exports against the header and
 the bindings, the validation codes and their order behind the base checks (fake, aligned pointers: validation comes before any HIP call),
-the launch plans - equal to tests/golden/kvgroups_plans.txt and to the rule restated in tests/kv_groups.py, at G = 1 the shared-prefix
+the launch plans - equal to tests/golden/kvgroups_plans.txt and to the rule restated in tests/kv_prefix.py, at G = 1 the shared-prefix
 call's plus the schedule launch and the table's bytes - the integer model of the schedule table, the register tables of the new kernels
 and the front end's refusals."""
 import ctypes
@@ -18,8 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import kv_args as ka     # noqa: E402
-import kv_groups as kg   # noqa: E402
-import kv_shared as sp   # noqa: E402
+import kv_prefix as kg   # noqa: E402
 
 DUMMY, BIG = ka.DUMMY, ka.BIG
 NEW = ("fasn_fwd_prefix_groups_workspace_bytes", "fasn_fwd_prefix_groups", "fasn_prefix_groups_plan")
@@ -133,15 +132,15 @@ def _expected_plan(tag, D, rule):
 
 @pytest.mark.parametrize("dtype", [0, 1])
 @pytest.mark.parametrize("D", DIMS)
-@pytest.mark.parametrize("case", sorted(kg.PLAN_CASES))
+@pytest.mark.parametrize("case", sorted(kg.GROUPS_PLAN_CASES))
 def test_plan_and_workspace_follow_the_rule(pkg, case, D, dtype):
     """four launches; the grids, the LDS and the workspace as include/fasn.h states them, recomputed in Python; the suffix pass and the
     combine have the base call's grids"""
-    shape, G, pages = kg.PLAN_CASES[case]
+    shape, G, pages = kg.GROUPS_PLAN_CASES[case]
     lib = pkg._lib.load()
     args = lambda **kw: ka._args_decode(pkg, dtype=dtype, D=D, **dict(shape, **kw))   # noqa: E731
     plan = pkg._lib.prefix_groups_plan(args(), _groups(pkg, G=G, pages=pages))
-    rule = kg.plan_rule(D=D, G=G, prefix_pages=pages, **shape)
+    rule = kg.groups_plan_rule(D=D, G=G, prefix_pages=pages, **shape)
     assert plan == _expected_plan("%s, %d" % (TAGS[dtype], D), D, rule)
     base = pkg._lib.kvcache_plan(args())
     assert plan[2][1:] == base[0][1:] and plan[3][1:] == base[1][1:]
@@ -150,30 +149,30 @@ def test_plan_and_workspace_follow_the_rule(pkg, case, D, dtype):
 
 
 @pytest.mark.parametrize("D", DIMS)
-@pytest.mark.parametrize("case", sorted(sp.PLAN_CASES))
+@pytest.mark.parametrize("case", sorted(kg.SHARED_PLAN_CASES))
 def test_one_group_plans_as_the_shared_prefix_call(pkg, case, D):
-    """G = 1: kv_shared.plan_rule's grids and partial bytes, plus the schedule launch and the table's bytes"""
-    shape, pages = sp.PLAN_CASES[case]
+    """G = 1: kv_prefix.shared_plan_rule's grids and partial bytes, plus the schedule launch and the table's bytes"""
+    shape, pages = kg.SHARED_PLAN_CASES[case]
     lib = pkg._lib.load()
     a = ka._args_decode(pkg, D=D, **shape)
-    gp, gs, gc, partials = sp.plan_rule(D=D, prefix_pages=pages, **shape)
-    rule = kg.plan_rule(D=D, G=1, prefix_pages=pages, **shape)
+    gp, gs, gc, partials = kg.shared_plan_rule(D=D, prefix_pages=pages, **shape)
+    rule = kg.groups_plan_rule(D=D, G=1, prefix_pages=pages, **shape)
     assert rule[:4] == (gp, gs, gc, partials)
     one = pkg._lib.prefix_groups_plan(a, _groups(pkg, G=1, pages=pages))
-    shared = pkg._lib.shared_prefix_plan(a, sp._prefix(pkg, pages=pages))
+    shared = pkg._lib.shared_prefix_plan(a, kg._prefix(pkg, pages=pages))
     assert one[0] == ("fasn_kvgroups_schedule_kernel<256>", 1, 256, 0)
     assert [k[1:] for k in one[1:]] == [k[1:] for k in shared]
     assert [k[0].replace("kvgroups", "kvshared") for k in one[1:]] == [k[0] for k in shared]
     R = (shape["H"] // shape["Hkv"]) * shape["Sq"]
     table = 4 * (4 + -(-3 * shape["B"] // 4) * 4 + 4 * -(-shape["B"] * R // 128))
     assert lib.fasn_fwd_prefix_groups_workspace_bytes(a, _groups(pkg, G=1, pages=pages)) == (partials + 15) // 16 * 16 + table
-    assert lib.fasn_fwd_shared_prefix_workspace_bytes(a, sp._prefix(pkg, pages=pages)) == partials
+    assert lib.fasn_fwd_shared_prefix_workspace_bytes(a, kg._prefix(pkg, pages=pages)) == partials
 
 
 def test_grids_do_not_depend_on_device_memory(pkg):
     """other lengths, another block table, other prefix tables, lengths and groups (other device pointers), an append: the same launches"""
     lib = pkg._lib.load()
-    for case, (shape, G, pages) in kg.PLAN_CASES.items():
+    for case, (shape, G, pages) in kg.GROUPS_PLAN_CASES.items():
         a = ka._args_decode(pkg, **shape)
         plan = pkg._lib.prefix_groups_plan(a, _groups(pkg, G=G, pages=pages))
         other = ka._args_decode(pkg, seqlens=DUMMY + 4096, **shape)
@@ -190,8 +189,8 @@ def _plan_text(pkg):
     got = []
     for D in DIMS:
         for dtype in (0, 1):
-            for name in sorted(kg.PLAN_CASES):
-                shape, G, pages = kg.PLAN_CASES[name]
+            for name in sorted(kg.GROUPS_PLAN_CASES):
+                shape, G, pages = kg.GROUPS_PLAN_CASES[name]
                 buf = ctypes.create_string_buffer(4096)
                 rc = lib.fasn_prefix_groups_plan(ka._args_decode(pkg, dtype=dtype, D=D, **shape), _groups(pkg, G=G, pages=pages), buf, len(buf))
                 assert rc > 0, (name, D, dtype, rc)
@@ -256,7 +255,7 @@ def test_new_kernels_do_not_spill(pkg):
     wanted = set()
     for D in DIMS:
         for dtype in (0, 1):
-            shape, G, pages = kg.PLAN_CASES["straddle"]
+            shape, G, pages = kg.GROUPS_PLAN_CASES["straddle"]
             wanted |= {k[0] for k in pkg._lib.prefix_groups_plan(ka._args_decode(pkg, dtype=dtype, D=D, **shape), _groups(pkg, G=G, pages=pages))}
     assert len(wanted) == 13, wanted
     for name in sorted(wanted):

@@ -1,6 +1,6 @@
 """Decode behind a shared prefix (fasn_fwd_shared_prefix), without a GPU: the operand's layout, the exports against the header and the
 bindings, the validation codes and their order behind the base checks (fake, aligned pointers: validation comes before any HIP call), the
-launch plans - equal to tests/golden/kvshared_plans.txt and to the rule restated in tests/kv_shared.py - the workspace formula, the
+launch plans - equal to tests/golden/kvshared_plans.txt and to the rule restated in tests/kv_prefix.py - the workspace formula, the
 register tables of the new kernels and the front end's refusals."""
 import ctypes
 import inspect
@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import kv_args as ka     # noqa: E402
-import kv_shared as sp   # noqa: E402
+import kv_prefix as sp   # noqa: E402
 
 DUMMY, BIG = ka.DUMMY, ka.BIG
 NEW = ("fasn_fwd_shared_prefix_workspace_bytes", "fasn_fwd_shared_prefix", "fasn_shared_prefix_plan")
@@ -112,16 +112,16 @@ def test_validation_codes_and_their_order(pkg):
 # ---------------------------------------------------------------- plans
 @pytest.mark.parametrize("dtype", [0, 1])
 @pytest.mark.parametrize("D", DIMS)
-@pytest.mark.parametrize("case", sorted(sp.PLAN_CASES))
+@pytest.mark.parametrize("case", sorted(sp.SHARED_PLAN_CASES))
 def test_plan_and_workspace_follow_the_rule(pkg, case, D, dtype):
     """three launches; the grids, the LDS and the workspace as include/fasn.h states them, recomputed in Python; the suffix pass has the
     base call's grid"""
-    shape, pages = sp.PLAN_CASES[case]
+    shape, pages = sp.SHARED_PLAN_CASES[case]
     lib = pkg._lib.load()
     tag = "%s, %d" % (TAGS[dtype], D)
     args = lambda **kw: ka._args_decode(pkg, dtype=dtype, D=D, **dict(shape, **kw))   # noqa: E731
     plan = pkg._lib.shared_prefix_plan(args(), _prefix(pkg, pages=pages))
-    gp, gs, gc, ws = sp.plan_rule(D=D, prefix_pages=pages, **shape)
+    gp, gs, gc, ws = sp.shared_plan_rule(D=D, prefix_pages=pages, **shape)
     assert plan == [(f"fasn_kvshared_prefix_kernel<{tag}>", gp, 256, sp.lds_bytes(D)), (f"fasn_kvshared_suffix_kernel<{tag}>", gs, 256, sp.lds_bytes(D)),
                     (f"fasn_kvshared_combine_kernel<{tag}>", gc, 256, 0)]
     base = pkg._lib.kvcache_plan(args())
@@ -133,7 +133,7 @@ def test_plan_and_workspace_follow_the_rule(pkg, case, D, dtype):
 
 def test_grids_do_not_depend_on_device_memory(pkg):
     """other lengths, another block table, another prefix table and length (other device pointers), an append: the same launches"""
-    for case, (shape, pages) in sp.PLAN_CASES.items():
+    for case, (shape, pages) in sp.SHARED_PLAN_CASES.items():
         a = ka._args_decode(pkg, **shape)
         plan = pkg._lib.shared_prefix_plan(a, _prefix(pkg, pages=pages))
         other = ka._args_decode(pkg, seqlens=DUMMY + 4096, **shape)
@@ -151,8 +151,8 @@ def _plan_text(pkg):
     got = []
     for D in DIMS:
         for dtype in (0, 1):
-            for name in sorted(sp.PLAN_CASES):
-                shape, pages = sp.PLAN_CASES[name]
+            for name in sorted(sp.SHARED_PLAN_CASES):
+                shape, pages = sp.SHARED_PLAN_CASES[name]
                 buf = ctypes.create_string_buffer(4096)
                 rc = lib.fasn_shared_prefix_plan(ka._args_decode(pkg, dtype=dtype, D=D, **shape), _prefix(pkg, pages=pages), buf, len(buf))
                 assert rc > 0, (name, D, dtype, rc)
@@ -178,7 +178,7 @@ def test_new_kernels_do_not_spill(pkg):
     wanted = set()
     for D in DIMS:
         for dtype in (0, 1):
-            shape, pages = sp.PLAN_CASES["straddle"]
+            shape, pages = sp.SHARED_PLAN_CASES["straddle"]
             wanted |= {k[0] for k in pkg._lib.shared_prefix_plan(ka._args_decode(pkg, dtype=dtype, D=D, **shape), _prefix(pkg, pages=pages))}
     assert len(wanted) == 12, wanted
     for name in sorted(wanted):
