@@ -52,6 +52,7 @@ EXPORTS = (
     "fasn_varlen_rope", "fasn_varlen_rope_plan",
     "fasn_fwd_shared_prefix_workspace_bytes", "fasn_fwd_shared_prefix", "fasn_shared_prefix_plan",
     "fasn_fwd_prefix_groups_workspace_bytes", "fasn_fwd_prefix_groups", "fasn_prefix_groups_plan",
+    "fasn_mla_workspace_bytes", "fasn_fwd_mla", "fasn_mla_append", "fasn_mla_plan",
 )
 
 
@@ -186,6 +187,22 @@ class PrefixGroups(Structure):
 FASN_PREFIX_GROUPS_MAX = 1024   # include/fasn.h
 
 
+class MlaArgs(Structure):
+    """fasn_mla_args (include/fasn.h): decode over a compressed latent K/V cache - one 576-feature row per token, the first 512 the value"""
+    _fields_ = [
+        ("q", View4), ("o", View4),
+        ("lse", c_void_p),
+        ("kv_cache", c_void_p),
+        ("kv_stride", c_int64 * 2),
+        ("block_table", c_void_p), ("block_table_stride", c_int64), ("max_pages", c_int32),
+        ("seqlens", c_void_p), ("seqlen_add", c_int32), ("page_size", c_int32),
+        ("B", c_int32), ("H", c_int32), ("Sq", c_int32), ("D", c_int32), ("Dv", c_int32),
+        ("dtype", c_int32),
+        ("scale", c_float), ("softmax_n", c_float), ("causal", c_int32), ("reserved", c_int32),
+        ("n", c_void_p), ("n_stride_b", c_int64), ("n_stride_h", c_int64),
+    ]
+
+
 class FasnError(RuntimeError):
     pass
 
@@ -289,6 +306,15 @@ def _prefix_groups_bindings():
     return _prefix_bindings("prefix_groups", PrefixGroups)
 
 
+def _mla_bindings():
+    """(name, restype, argtypes) of the four entry points of the MLA decode: a block of its own, no part of the K/V-cache description"""
+    head = [POINTER(MlaArgs)]
+    yield "fasn_mla_workspace_bytes", c_size_t, head
+    yield "fasn_fwd_mla", c_int32, head + [c_void_p, c_size_t, c_void_p]
+    yield "fasn_mla_append", c_int32, head + [POINTER(View4), c_void_p]
+    yield "fasn_mla_plan", c_int32, head + [c_char_p, c_size_t]
+
+
 def kv_call(args, fp8=None, tree=None, window=None, alibi=None):
     """the KvCall of the block `args` under the operands that are not None. The block and the operands live as long as the KvCall does."""
     c = KvCall(kind=_KV_KIND[kv_stem(args)], reserved=0, block=ctypes.cast(ctypes.pointer(args), c_void_p))
@@ -367,7 +393,7 @@ def load():
     lib.fasn_varlen_rope.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvRope), POINTER(View4), POINTER(View4), c_int32, c_void_p]
     lib.fasn_varlen_rope_plan.restype = c_int32
     lib.fasn_varlen_rope_plan.argtypes = [POINTER(FwdArgs), POINTER(Varlen), POINTER(KvRope), POINTER(View4), POINTER(View4), c_int32, c_char_p, c_size_t]
-    for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings(), *_shared_prefix_bindings(), *_prefix_groups_bindings()):
+    for name, restype, argtypes in (*_kv_bindings(), *_kv_call_bindings(), *_shared_prefix_bindings(), *_prefix_groups_bindings(), *_mla_bindings()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     ver = lib.fasn_abi_version()
@@ -552,6 +578,12 @@ def prefix_groups_plan(args, groups):
     """The four launches of fasn_fwd_prefix_groups for `args` (a KvCacheArgs) behind `groups` (a PrefixGroups) - the schedule kernel, the
     prefix pass, the suffix pass, the combine - as launch_plan returns them. Nothing is launched."""
     return _plan("fasn_prefix_groups_plan", args, groups)
+
+
+def mla_plan(args):
+    """The two launches of fasn_fwd_mla for `args` (an MlaArgs) - the forward on B * ceil(H * Sq / 64) * nsplit workgroups, the combine -
+    as launch_plan returns them. Nothing is launched."""
+    return _plan("fasn_mla_plan", args)
 
 
 def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):

@@ -1,0 +1,123 @@
+// MLA decode over a compressed latent K/V cache (include/fasn.h: fasn_fwd_mla, fasn_mla_append, fasn_mla_workspace_bytes, fasn_mla_plan):
+// the argument checks - all of them in front of any HIP call -, the launch plan, which depends on shapes and capacity only, and the
+// launches of fasn_mla.h. The call sits beside the K/V-cache family and is no operand set of it: a block of its own, kernels of its own.
+#include <limits.h>
+#include <math.h>
+#include "fasn_kv_host.h"
+#include "fasn_mla.h"
+
+namespace fasn {
+namespace {
+
+// Check order: sizes, enums and NULL members; what this build does not serve; the views; the remaining alignment rules.
+int mla_build(const fasn_mla_args* a, MlaParams& p) {
+    if (a == nullptr) return FASN_EINVAL;
+    if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->D <= 0 || a->Dv <= 0 || a->page_size <= 0 || a->reserved != 0) return FASN_EINVAL;
+    if (a->dtype != FASN_DTYPE_F16 && a->dtype != FASN_DTYPE_BF16) return FASN_EDTYPE;
+    if (a->D != MLA_E || a->Dv != MLA_EV) return FASN_EHEADDIM;
+    if (!(a->softmax_n >= 0.f) || !isfinite(a->scale)) return FASN_EINVAL;
+    if (a->seqlens == nullptr || a->kv_cache == nullptr) return FASN_EINVAL;
+    const bool paged = a->block_table != nullptr;
+    if (paged && (a->max_pages <= 0 || a->block_table_stride < a->max_pages)) return FASN_EINVAL;
+    const int64_t capacity = paged ? (int64_t)a->max_pages * a->page_size : (int64_t)a->page_size;
+    if (capacity > INT_MAX - 2 * KV_KT || (int64_t)a->seqlen_add + capacity > INT_MAX || a->seqlen_add < 0) return FASN_EINVAL;
+    if (a->kv_stride[0] < 0 || a->kv_stride[1] < MLA_E) return FASN_EINVAL;
+    if (a->n != nullptr && (a->n_stride_b < 0 || a->n_stride_h < 0 || (a->B - 1) * a->n_stride_b + (a->H - 1) * a->n_stride_h >= (1ll << 31))) return FASN_EINVAL;
+    // served: H * Sq <= 256 rows, pages of whole 64-key tiles, a tile whose descriptor range and lane offsets are 32-bit, and - the queries are
+    // prescaled by scale * log2(e) in the element type - |scale * log2(e)| <= 8 in fp16
+    if ((int64_t)a->H * a->Sq > MLA_MAX_ROWS) return FASN_EUNSUPPORTED;
+    if (paged && a->page_size % KV_KT != 0) return FASN_EUNSUPPORTED;
+    if ((int64_t)KV_KT * a->kv_stride[1] * 2 >= (1ll << 31)) return FASN_EUNSUPPORTED;
+    if (a->dtype == FASN_DTYPE_F16 && !(fabsf(a->scale * kLog2e) <= 8.0f)) return FASN_EUNSUPPORTED;
+    int rc;
+    if ((rc = kv_check_view(a->q))) return rc;
+    if ((rc = kv_check_view(a->o))) return rc;
+    if (!kv_aligned16(a->kv_cache) || a->kv_stride[0] % 8 != 0 || a->kv_stride[1] % 8 != 0) return FASN_EALIGN;
+    if (reinterpret_cast<uintptr_t>(a->seqlens) % 4 || reinterpret_cast<uintptr_t>(a->block_table) % 4 || reinterpret_cast<uintptr_t>(a->n) % 4) return FASN_EALIGN;
+    p = MlaParams{};
+    p.q = static_cast<const char*>(a->q.ptr);
+    p.o = static_cast<char*>(a->o.ptr);
+    p.lse = a->lse;
+    p.kv = static_cast<char*>(a->kv_cache);
+    for (int i = 0; i < 3; ++i) {
+        p.qs[i] = a->q.stride[i];
+        p.os[i] = a->o.stride[i];
+    }
+    p.kps = a->kv_stride[0], p.krs = a->kv_stride[1];
+    p.bt = a->block_table;
+    p.bts = a->block_table_stride;
+    p.seqlens = a->seqlens;
+    p.seqlen_add = a->seqlen_add;
+    p.page_size = a->page_size;
+    p.tpp = paged ? a->page_size / KV_KT : INT_MAX;
+    p.capacity = (int)capacity;
+    p.B = a->B, p.H = a->H, p.Sq = a->Sq;
+    p.R = a->H * a->Sq;
+    p.nrb = (p.R + MLA_RB - 1) / MLA_RB;
+    p.causal = a->causal ? 1 : 0;
+    p.c = a->scale * kLog2e;
+    p.n = a->softmax_n;
+    p.nt = a->n;
+    p.nsb = (int)a->n_stride_b, p.nsh = (int)a->n_stride_h;
+    // the plan: one workgroup per (batch element, 64-row block, split)
+    const int64_t base = (int64_t)p.B * p.nrb;
+    p.nsplit = (int)mla_nsplit(base, (capacity + KV_KT - 1) / KV_KT, p.R);
+    if (base * p.nsplit > INT_MAX / MLA_MAX_ROWS) return FASN_EINVAL;
+    return FASN_OK;
+}
+
+size_t mla_ws_bytes(const MlaParams& p) { return (size_t)p.B * p.nsplit * p.R * (size_t)(MLA_EV + 2) * sizeof(float); }
+
+template <typename Tag>
+int mla_launch_as(const MlaParams& p, hipStream_t s) {
+    kv_launch<&fasn_mla_fwd_kernel<Tag>>((unsigned)(p.B * p.nrb * p.nsplit), MLA_SMEM, s, p);
+    const int64_t nthr = (int64_t)p.B * p.R * (MLA_EV / 4);
+    FASN_LAUNCH((fasn_mla_combine_kernel<Tag>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
+    return launch_rc();
+}
+
+int mla_forward(const fasn_mla_args* a, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    MlaParams p;
+    const int rc = mla_build(a, p);
+    if (rc) return rc;
+    if (workspace == nullptr || workspace_bytes < mla_ws_bytes(p)) return FASN_EWORKSPACE;
+    if (!kv_aligned16(workspace)) return FASN_EALIGN;
+    p.part_o = static_cast<float*>(workspace);
+    p.part_ml = p.part_o + (size_t)p.B * p.nsplit * p.R * MLA_EV;
+    return a->dtype == FASN_DTYPE_BF16 ? mla_launch_as<bf16_tag>(p, s) : mla_launch_as<f16_tag>(p, s);
+}
+
+}  // namespace
+}  // namespace fasn
+
+using namespace fasn;
+
+extern "C" {
+
+size_t fasn_mla_workspace_bytes(const fasn_mla_args* args) {
+    MlaParams p;
+    return mla_build(args, p) == FASN_OK ? mla_ws_bytes(p) : 0;
+}
+
+int fasn_fwd_mla(const fasn_mla_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return mla_forward(args, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int fasn_mla_append(const fasn_mla_args* args, const fasn_view4* kv_new, fasn_stream_t stream) {
+    MlaParams p;
+    int rc = mla_build(args, p);
+    if (rc) return rc;
+    if (kv_new == nullptr) return FASN_EINVAL;
+    if ((rc = kv_check_view(*kv_new))) return rc;
+    p.kn = static_cast<const char*>(kv_new->ptr);
+    p.kns[0] = kv_new->stride[0], p.kns[1] = kv_new->stride[1];
+    const int64_t nthr = (int64_t)p.B * p.Sq * MLA_CPR;   // (at most 256 rows per batch element: the grid fits)
+    FASN_LAUNCH(fasn_mla_append_kernel, dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
+    return launch_rc();
+}
+
+int fasn_mla_plan(const fasn_mla_args* args, char* buf, size_t cap) {
+    return record_plan(buf, cap, [&] { return mla_forward(args, plan_workspace(), ~size_t(0), nullptr); });
+}
+
+}  // extern "C"

@@ -1,0 +1,148 @@
+"""MLA decode: attention over a compressed latent K/V cache (multi-head latent attention in its absorbed form: DeepSeek-V2 / V3 / R1,
+Kimi K2). Host side of fasn_fwd_mla / fasn_mla_append in include/fasn.h.
+
+The cache holds ONE row of 576 features per token, shared by every query head: a 512-wide latent and a 64-wide rotated key part. The logit
+of head h is q_h[0:576] . row[0:576] and the value is the latent itself, out_h = sum_j p_hj row_j[0:512] - so K and V are one tensor, read
+once. The call sits beside the K/V-cache family (kvcache.py) and shares its contract: lengths and block table are read by the kernels only,
+the launches depend on shapes and capacity alone, one captured graph serves every step. Forward only.
+"""
+from typing import Optional
+
+import torch
+from torch import Tensor
+
+from . import _lib
+from ._lib import MlaArgs
+from .flash_attn import _n_strides, _n_tensor, _stream_ptr, _view4
+from .kvcache import _KV_DTYPES, _check_cache, _on_device, _rows
+
+MLA_HEAD_DIM, MLA_VALUE_DIM, MLA_MAX_ROWS = 576, 512, 256
+_LOG2E = 1.4426950408889634
+_F16_MAX_PRESCALE = 8.0   # float16: |scale * log2e| beyond this is FASN_EUNSUPPORTED (mla_build, csrc/fasn_mla.hip)
+_SERVED = (f"served: a latent cache of head dims exactly {MLA_VALUE_DIM} + 64 = {MLA_HEAD_DIM} in fp16 / bf16, H * Sq <= {MLA_MAX_ROWS}, "
+           "causal or not, softmax_n; not served: an FP8 cache, a window, ALiBi, trees, packed queries, shared prefixes")
+
+
+def flash_attention_n_mla(
+        query: Tensor,
+        kv_cache: Tensor,
+        cache_seqlens: Tensor,
+        scale: float,
+        block_table: Optional[Tensor] = None,
+        kv_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """softmax_n attention of a few new query positions against a compressed latent K/V cache (absorbed MLA decode), on MI355X.
+
+    :param query: [B, H, Sq, 576] fp16 / bf16 device tensor: W_UK is absorbed into the first 512 features, the last 64 are rotated.
+                  H * Sq <= 256 (DeepSeek-V3's 128 heads with one MTP draft position).
+    :param kv_cache: paged [num_pages, page_size, 1, 576] with `block_table` (page_size a multiple of 64), or dense [B, capacity, 1, 576]
+                  with block_table=None; a 3-D cache without the head axis is a view of the same thing. Query's dtype, feature stride 1,
+                  16-byte aligned rows; never copied.
+    :param cache_seqlens: int32 [B] ON THE DEVICE: valid rows per batch element before this call; clamped to [0, capacity] in the kernel,
+                  never read on the host, not modified.
+    :param scale: multiplies q . row. REQUIRED: an MLA model's scale is (128 + 64) ** -0.5 times its YaRN factor, not 576 ** -0.5, so there
+                  is no default. float16 serves |scale| * log2(e) <= 8 (the queries are prescaled in the element type).
+    :param block_table: int32 [B, max_pages] on the device. Entries beyond the pages a batch element needs are never read; cache rows at
+                  or beyond its length may hold anything (NaN included).
+    :param kv_new: optional [B, Sq, 1, 576]: written to the cache positions cache_seqlens[b] .. + Sq - 1 first (positions at or beyond
+                  the capacity are dropped in the kernel) and then attended to: batch element b sees len_b = cache_seqlens[b] + Sq rows.
+    :param softmax_n_param: n >= 0, or a floating tensor that broadcasts to [B, H]; no gradient. n = 0 is the models as they ship.
+    :param is_causal: position i sees key j iff j < len_b and j <= i + len_b - Sq. False: every position sees all len_b keys.
+    :param return_lse: also return lse [B, H, Sq] fp32 = log(n + sum_j exp(x_ij)).
+    :return: [B, H, Sq, 512] in query's dtype (and lse). Rows that see no key give exactly 0 and lse = log n (-inf for n = 0).
+    """
+    fn = "flash_attention_n_mla"
+    if not isinstance(query, Tensor) or query.dim() != 4 or not isinstance(kv_cache, Tensor) or kv_cache.dim() not in (3, 4):
+        raise ValueError(f"{fn}: query must be [B, H, Sq, {MLA_HEAD_DIM}] and kv_cache [num_pages, page_size, 1, {MLA_HEAD_DIM}] (paged) or "
+                         f"[B, capacity, 1, {MLA_HEAD_DIM}] (dense); {_SERVED}")
+    if kv_cache.dim() == 3:
+        kv_cache = kv_cache.unsqueeze(2)
+    if kv_cache.dtype in (torch.float8_e4m3fn, torch.float8_e5m2, torch.float8_e4m3fnuz, torch.float8_e5m2fnuz):
+        raise TypeError(f"{fn}: an FP8 latent cache ({kv_cache.dtype}) has no kernel; {_SERVED}")
+    B, H, Sq, D = query.shape
+    if D != MLA_HEAD_DIM or kv_cache.shape[3] != MLA_HEAD_DIM or kv_cache.shape[2] != 1:
+        raise ValueError(f"{fn}: query is {tuple(query.shape)} and kv_cache {tuple(kv_cache.shape)}: not a latent cache; {_SERVED}. "
+                         "Separate K and V of one head dim are flash_attention_n_kvcache's")
+    if query.dtype not in _KV_DTYPES:
+        raise ValueError(f"{fn}: dtype {query.dtype} is not supported; {_SERVED}")
+    if kv_cache.dtype != query.dtype:
+        raise TypeError(f"{fn}: query and kv_cache must share one dtype; got {query.dtype} and {kv_cache.dtype}")
+    if H * Sq > MLA_MAX_ROWS:
+        raise ValueError(f"{fn}: H * Sq = {H} x {Sq} = {H * Sq} rows exceed {MLA_MAX_ROWS}; {_SERVED}")
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)):
+        raise TypeError(f"{fn}: scale must be a Python float (required: MLA models use (128 + 64) ** -0.5 times their YaRN factor, never "
+                        f"{MLA_HEAD_DIM} ** -0.5); got {type(scale).__name__}")
+    scale = float(scale)
+    if query.dtype == torch.float16 and not abs(scale) * _LOG2E <= _F16_MAX_PRESCALE:
+        raise ValueError(f"{fn}: float16 serves |scale| * log2(e) <= {_F16_MAX_PRESCALE:g} (the queries are prescaled in float16); got scale "
+                         f"{scale}. Use bfloat16, or fold the factor into the queries")
+    dev = query.device
+    for name, t in (("kv_cache", kv_cache), ("cache_seqlens", cache_seqlens), ("block_table", block_table), ("kv_new", kv_new)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}, query on {dev}: every operand must live on the query's device "
+                               "(the lengths and the block table are read by the kernels, never on the host)")
+    if torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in (query, kv_cache, kv_new))
+                                    or (isinstance(softmax_n_param, Tensor) and softmax_n_param.requires_grad)):
+        raise RuntimeError(f"{fn} is forward only (inference): an input requires grad. Call it under torch.no_grad()")
+    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B or not cache_seqlens.is_contiguous():
+        raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
+    page_size = kv_cache.shape[1]
+    paged = block_table is not None
+    if paged:
+        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.stride(1) != 1 or block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"block_table must be an int32 tensor [B, max_pages] = [{B}, >= 1] with unit column stride; got {block_table.dtype} {tuple(block_table.shape)}")
+        if page_size % 64 != 0:
+            raise ValueError(f"page_size {page_size} is not supported: a paged cache needs page_size % 64 == 0 (a 64-key tile never straddles a page)")
+    elif kv_cache.shape[0] != B:
+        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, 1, {MLA_HEAD_DIM}] with B = {B}; got {tuple(kv_cache.shape)}")
+    _check_cache("kv_cache", kv_cache, paged, MLA_HEAD_DIM)
+    if kv_new is not None:
+        if kv_new.dtype != query.dtype or tuple(kv_new.shape) != (B, Sq, 1, MLA_HEAD_DIM):
+            raise ValueError(f"kv_new must be [B, Sq, 1, {MLA_HEAD_DIM}] = [{B}, {Sq}, 1, {MLA_HEAD_DIM}] in {query.dtype}; got {tuple(kv_new.shape)} {kv_new.dtype}")
+        kv_new = _rows(kv_new)
+    query = _rows(query)
+    if isinstance(softmax_n_param, Tensor):
+        nt, n = _n_tensor(softmax_n_param.detach(), query).contiguous(), 0.0
+    else:
+        nt, n = None, 0.0 if softmax_n_param is None else float(softmax_n_param)
+        if n < 0:
+            raise ValueError("softmax_n_param must be >= 0")
+    # (the argument checks above need no device; everything below does)
+    if not query.is_cuda:
+        raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
+                           "(there is deliberately no CPU fallback)")
+    out = torch.empty((B, H, Sq, MLA_VALUE_DIM), dtype=query.dtype, device=dev)
+    lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
+    a = MlaArgs()
+    a.q, a.o = _view4(query), _view4(out)
+    a.lse = None if lse is None else lse.data_ptr()
+    a.kv_cache = kv_cache.data_ptr()
+    a.kv_stride[0] = kv_cache.stride(0) if kv_cache.size(0) > 1 else 0
+    a.kv_stride[1] = kv_cache.stride(1) if kv_cache.size(1) > 1 else MLA_HEAD_DIM
+    if paged:
+        a.block_table, a.block_table_stride, a.max_pages = block_table.data_ptr(), block_table.stride(0) if B > 1 else block_table.shape[1], block_table.shape[1]
+    else:
+        a.block_table, a.block_table_stride, a.max_pages = None, 0, 1
+    a.seqlens = cache_seqlens.data_ptr()
+    a.seqlen_add = Sq if kv_new is not None else 0
+    a.page_size = page_size
+    a.B, a.H, a.Sq, a.D, a.Dv = B, H, Sq, MLA_HEAD_DIM, MLA_VALUE_DIM
+    a.dtype = _KV_DTYPES[query.dtype]
+    a.scale, a.softmax_n, a.causal, a.reserved = scale, n, 1 if is_causal else 0, 0
+    if nt is not None:
+        a.n = nt.data_ptr()
+        a.n_stride_b, a.n_stride_h = _n_strides(nt)
+    lib = _lib.load()
+
+    def launch():
+        stream = _stream_ptr(dev)
+        if kv_new is not None:
+            _lib.check(lib.fasn_mla_append(a, _view4(kv_new), stream), "fasn_mla_append")
+        ws_bytes = lib.fasn_mla_workspace_bytes(a)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # torch's caching allocator: capturable
+        _lib.check(lib.fasn_fwd_mla(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_mla")
+
+    _on_device(dev, launch)
+    return out if lse is None else (out, lse)

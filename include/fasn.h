@@ -852,6 +852,69 @@ int fasn_fwd_prefix_groups(const fasn_kvcache_args* args, const fasn_prefix_grou
 int fasn_prefix_groups_plan(const fasn_kvcache_args* args, const fasn_prefix_groups* groups, char* buf, size_t cap);
 
 /*
+ * MLA DECODE: attention over a COMPRESSED LATENT K/V cache (additions within ABI 6; no struct or function above is changed): multi-head
+ * latent attention in its absorbed decode form (DeepSeek-V2 / V3 / R1, Kimi K2). The cache holds ONE row of 576 features per token, shared
+ * by every query head: a 512-wide latent and a 64-wide rotated key part. For query head h, position i and key j
+ *     x_ij = scale * q_hi[0:576] . row_j[0:576],      o_hi = sum_j p_ij row_j[0:512]
+ * - multi-query attention with one K/V head, D = 576, Dv = 512 and V aliased onto K's first 512 features. The caller has absorbed W_UK
+ * into the queries and rotated their last 64 features. softmax_n is the start state of a row, (m, l) = (0, n); n = 0 is plain softmax.
+ *
+ *   cache     key j of batch element b is row j % page_size of page block_table[b * block_table_stride + j / page_size]; feature d of
+ *             (page, row) sits at kv_cache + (page * kv_stride[0] + row * kv_stride[1] + d) elements (feature stride 1, both strides % 8
+ *             and kv_stride[1] >= 576, base 16-byte aligned). block_table == NULL is the dense cache, as in fasn_fwd_kvcache.
+ *   lengths   len_b = clamp(seqlens[b] + seqlen_add, 0, capacity), read in the kernel; capacity = max_pages * page_size (dense:
+ *             page_size). Rows at or beyond len_b and pages no visible tile points to may hold anything, NaN included; block-table
+ *             entries that are not needed are not read.
+ *   rows      the H * Sq rows of a batch element (row = h * Sq + i) are cut into blocks of 64; a workgroup owns (batch element, row
+ *             block, key split), so the cache is read once per 64 rows. Each row uses the softmax_n of its own query head (`n`, as in
+ *             fasn_fwd_kvcache).
+ *   causal    bottom-right aligned per batch element: position i sees key j iff j < len_b and j <= i + len_b - Sq. Rows that see no key
+ *             give 0 and lse = log n (-inf for n = 0). The output is rounded once.
+ *   served    D = 576 and Dv = 512 exactly (FASN_EHEADDIM), fp16 / bf16 (FASN_EDTYPE), H * Sq <= 256, paged: page_size % 64 == 0, and in
+ *             fp16 |scale * log2(e)| <= 8 - the queries are prescaled in the element type (each FASN_EUNSUPPORTED). `scale` has no
+ *             default anywhere: an MLA model's scale is (128 + 64)^-1/2 times its YaRN factor, not 576^-1/2.
+ *   checks    in this order, all before any HIP call: args == NULL, a non-positive size, reserved != 0 (FASN_EINVAL); dtype; head dims;
+ *             a NULL member, a negative n, seqlen_add or stride, kv_stride[1] < 576, a capacity beyond 2^31 (FASN_EINVAL); what is not
+ *             served (above); the views q and o with the codes of fasn_fwd (FASN_EINVAL / FASN_ESTRIDE / FASN_EALIGN); the cache's
+ *             16-byte rule and seqlens / block_table / n off 4 bytes (FASN_EALIGN); then the workspace.
+ *
+ * fasn_fwd_mla needs fasn_mla_workspace_bytes(args) = B * nsplit * H * Sq * 514 * 4 bytes of 16-byte aligned device memory (the split
+ * partials; FASN_EWORKSPACE when missing or too small; 0 for a block that is refused) and launches two kernels: the forward on
+ * B * ceil(H * Sq / 64) * nsplit workgroups of 256 with 144 KiB of LDS, and the combine. nsplit brings the grid to ~512 workgroups with at
+ * least 8 (below 64 rows: 4) of the capacity's tiles per split; it depends on shapes and capacity only, so one captured graph serves
+ * every step. fasn_mla_append writes the Sq rows of kv_new (a [B, Sq, 1, 576] view) to the cache positions seqlens[b] .. seqlens[b] +
+ * Sq - 1 (positions at or beyond the capacity are dropped inside the kernel; `seqlens` is not modified); a forward that is to see them
+ * passes seqlen_add = Sq. fasn_mla_plan writes the launches of fasn_fwd_mla as text, in the line format of fasn_launch_plan, without
+ * touching a device. Not here: an FP8 cache, a window, ALiBi, trees, packed queries, shared prefixes, gradients.
+ */
+typedef struct fasn_mla_args {
+    fasn_view4 q;          /* [B,H,Sq,576] */
+    fasn_view4 o;          /* [B,H,Sq,512] out */
+    float* lse;            /* [B,H,Sq] fp32 contiguous, out; may be NULL */
+    void* kv_cache;
+    int64_t kv_stride[2];  /* element strides (page, row) */
+    const int32_t* block_table;  /* DEVICE [B, max_pages] page ids, or NULL (dense cache) */
+    int64_t block_table_stride;
+    int32_t max_pages;
+    const int32_t* seqlens;      /* DEVICE [B] */
+    int32_t seqlen_add;
+    int32_t page_size;
+    int32_t B, H, Sq, D, Dv;     /* D = 576, Dv = 512 */
+    int32_t dtype;         /* FASN_DTYPE_F16 / FASN_DTYPE_BF16 */
+    float scale;
+    float softmax_n;
+    int32_t causal;
+    int32_t reserved;      /* 0 */
+    const float* n;        /* DEVICE per-(batch, query head) softmax_n, or NULL */
+    int64_t n_stride_b, n_stride_h;
+} fasn_mla_args;
+
+size_t fasn_mla_workspace_bytes(const fasn_mla_args* args);
+int fasn_fwd_mla(const fasn_mla_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_mla_append(const fasn_mla_args* args, const fasn_view4* kv_new, fasn_stream_t stream);
+int fasn_mla_plan(const fasn_mla_args* args, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).

@@ -1,0 +1,104 @@
+"""MLA decode over a compressed latent cache: flash_attention_n_mla (B) against the route it replaces (A), same box, same process.
+
+  A = torch ops, fully captured: gather the pages through the block table, torch.matmul(q, rows^T) * scale, the length mask, the sink
+      column written by hand, softmax, torch.matmul(p, rows[..., :512]). Sq = 1 shapes need no causal mask beyond the lengths; for Sq = 2
+      the causal offset is part of the mask.
+  B = flash_attention_n_mla on the same pool and table.
+
+Both are captured in a HIP graph of REPS calls so that host time is out of the picture; the graphs are replayed alternating A / B / A / B
+and timed with device events. Reported: microseconds per call for every alternation, A / B, A's own spread between its alternations (the
+margin B is judged against), max |A - B| and B's TB/s of VISIBLE cache bytes (B * len * 1152: the cache is read once per 64 rows, so the
+bytes moved are ceil(H * Sq / 64) times that).
+usage: python tools/bench_mla.py [--rounds N] [--iters N] [--only I]"""
+import argparse
+import sys
+
+import torch
+
+sys.path.insert(0, ".")
+import flash_attention_softmax_n_amd as fa   # noqa: E402
+
+PAGE = 256
+REPS = 5
+E, EV = 576, 512
+SCALE = (128 + 64) ** -0.5
+SHAPES = [(64, 128, 1, 8192), (64, 16, 1, 8192), (1, 128, 2, 32768)]   # (B, H, Sq, len); the second is the TP-8 shard
+
+
+def graph_of(fn):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(REPS):
+            out = fn()
+    return g, out
+
+
+def time_graph(g, iters):
+    for _ in range(2):
+        g.replay()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(iters):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / (iters * REPS)   # microseconds per call
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--only", type=int, default=None)
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "bench_mla needs a GPU"
+    dev, dtype = torch.device("cuda:0"), torch.bfloat16
+    print(f"device: {torch.cuda.get_device_name(0)}; {REPS} calls per graph, {args.iters} replays per timing, {args.rounds} alternations A/B; bf16, page {PAGE}, n = 1")
+    print(f"{'shape (B,H,Sq,len)':24s} {'A us':>26s} {'B us':>26s} {'A/B':>6s} {'A spread':>9s} {'max|A-B|':>9s} {'B TB/s visible':>15s}")
+    for idx, (B, H, Sq, ln) in enumerate(SHAPES):
+        if args.only is not None and idx != args.only:
+            continue
+        torch.manual_seed(0)
+        max_pages = (ln + PAGE - 1) // PAGE
+        q = torch.randn(B, H, Sq, E, device=dev, dtype=dtype) * 0.5
+        pool = torch.randn(B * max_pages, PAGE, 1, E, device=dev, dtype=dtype) * 0.5
+        table = torch.randperm(B * max_pages, device=dev).to(torch.int32).view(B, max_pages)
+        sl = torch.full((B,), ln, dtype=torch.int32, device=dev)
+        pos = torch.arange(max_pages * PAGE, device=dev).view(1, 1, 1, -1)
+        qi = torch.arange(Sq, device=dev).view(1, 1, Sq, 1)
+
+        def run_a():
+            rows = pool[table.long()].view(B, max_pages * PAGE, E)                       # gather the pages
+            x = torch.matmul(q.view(B, H * Sq, E), rows.transpose(1, 2)).view(B, H, Sq, -1).float() * SCALE
+            x = x.masked_fill(pos > qi + sl.view(B, 1, 1, 1) - Sq, float("-inf"))
+            x = torch.cat([torch.zeros(B, H, Sq, 1, device=dev), x], -1)                  # the sink column: logit 0, weight n = 1
+            p = torch.softmax(x, -1)[..., 1:].to(dtype)
+            return torch.matmul(p.view(B, H * Sq, -1), rows[..., :EV]).view(B, H, Sq, EV)
+
+        def run_b():
+            return fa.flash_attention_n_mla(q, pool, sl, SCALE, block_table=table)
+
+        with torch.no_grad():
+            ga, oa = graph_of(run_a)
+            gb, ob = graph_of(run_b)
+            ta, tb = [], []
+            for _ in range(args.rounds):
+                ta.append(time_graph(ga, args.iters))
+                tb.append(time_graph(gb, args.iters))
+            diff = (oa.float() - ob.float()).abs().max().item()
+        a_med, b_med = sorted(ta)[len(ta) // 2], sorted(tb)[len(tb) // 2]
+        fmt = lambda ts: "/".join(f"{t:.1f}" for t in ts)   # noqa: E731
+        tbs = B * ln * E * 2 / (b_med * 1e-6) / 1e12
+        print(f"{str((B, H, Sq, ln)):24s} {fmt(ta):>26s} {fmt(tb):>26s} {a_med / b_med:6.2f} {max(ta) / min(ta):9.3f} {diff:9.2e} {tbs:15.2f}", flush=True)
+        del ga, gb, pool
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
