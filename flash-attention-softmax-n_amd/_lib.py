@@ -53,6 +53,7 @@ EXPORTS = (
     "fasn_fwd_shared_prefix_workspace_bytes", "fasn_fwd_shared_prefix", "fasn_shared_prefix_plan",
     "fasn_fwd_prefix_groups_workspace_bytes", "fasn_fwd_prefix_groups", "fasn_prefix_groups_plan",
     "fasn_mla_workspace_bytes", "fasn_fwd_mla", "fasn_mla_append", "fasn_mla_plan",
+    "fasn_mla_fp8_workspace_bytes", "fasn_fwd_mla_fp8", "fasn_mla_fp8_append", "fasn_mla_fp8_plan",
 )
 
 
@@ -203,6 +204,11 @@ class MlaArgs(Structure):
     ]
 
 
+class MlaFp8(Structure):
+    """fasn_mla_fp8 (include/fasn.h): the scale of an FP8 latent cache, one fp32 value per batch element in device memory"""
+    _fields_ = [("kv_scale", c_void_p), ("sb", c_int64), ("reserved", c_int32)]
+
+
 class FasnError(RuntimeError):
     pass
 
@@ -313,6 +319,11 @@ def _mla_bindings():
     yield "fasn_fwd_mla", c_int32, head + [c_void_p, c_size_t, c_void_p]
     yield "fasn_mla_append", c_int32, head + [POINTER(View4), c_void_p]
     yield "fasn_mla_plan", c_int32, head + [c_char_p, c_size_t]
+    head = head + [POINTER(MlaFp8)]   # ... and the four over an FP8 latent cache
+    yield "fasn_mla_fp8_workspace_bytes", c_size_t, head
+    yield "fasn_fwd_mla_fp8", c_int32, head + [c_void_p, c_size_t, c_void_p]
+    yield "fasn_mla_fp8_append", c_int32, head + [POINTER(View4), c_void_p]
+    yield "fasn_mla_fp8_plan", c_int32, head + [c_char_p, c_size_t]
 
 
 def kv_call(args, fp8=None, tree=None, window=None, alibi=None):
@@ -584,6 +595,12 @@ def mla_plan(args):
     """The two launches of fasn_fwd_mla for `args` (an MlaArgs) - the forward on B * ceil(H * Sq / 64) * nsplit workgroups, the combine -
     as launch_plan returns them. Nothing is launched."""
     return _plan("fasn_mla_plan", args)
+
+
+def mla_fp8_plan(args, fp8):
+    """The two launches of fasn_fwd_mla_fp8 for `args` (an MlaArgs over a cache of codes) and `fp8` (an MlaFp8): mla_plan's grid and LDS
+    with the FP8 kernels' names. Nothing is launched."""
+    return _plan("fasn_mla_fp8_plan", args, fp8)
 
 
 def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):

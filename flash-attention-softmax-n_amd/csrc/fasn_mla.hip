@@ -1,16 +1,20 @@
 // MLA decode over a compressed latent K/V cache (include/fasn.h: fasn_fwd_mla, fasn_mla_append, fasn_mla_workspace_bytes, fasn_mla_plan):
 // the argument checks - all of them in front of any HIP call -, the launch plan, which depends on shapes and capacity only, and the
 // launches of fasn_mla.h. The call sits beside the K/V-cache family and is no operand set of it: a block of its own, kernels of its own.
+// The same block over a latent cache of e4m3fn codes (fasn_fwd_mla_fp8, fasn_mla_fp8_append, fasn_mla_fp8_workspace_bytes, fasn_mla_fp8_plan;
+// kernels in fasn_mla_fp8.h) goes through the same checks with the cache's element size at 1 and the operand's checks behind them.
 #include <limits.h>
 #include <math.h>
 #include "fasn_kv_host.h"
 #include "fasn_mla.h"
+#include "fasn_mla_fp8.h"
 
 namespace fasn {
 namespace {
 
-// Check order: sizes, enums and NULL members; what this build does not serve; the views; the remaining alignment rules.
-int mla_build(const fasn_mla_args* a, MlaParams& p) {
+// Check order: sizes, enums and NULL members; what this build does not serve; the views; the remaining alignment rules. `eb`: bytes of a
+// cache element (2; 1 for the cache of codes), which enters the 32-bit range of a tile and the 16-byte rule of the cache strides.
+int mla_build(const fasn_mla_args* a, MlaParams& p, int eb = 2) {
     if (a == nullptr) return FASN_EINVAL;
     if (a->B <= 0 || a->H <= 0 || a->Sq <= 0 || a->D <= 0 || a->Dv <= 0 || a->page_size <= 0 || a->reserved != 0) return FASN_EINVAL;
     if (a->dtype != FASN_DTYPE_F16 && a->dtype != FASN_DTYPE_BF16) return FASN_EDTYPE;
@@ -27,12 +31,12 @@ int mla_build(const fasn_mla_args* a, MlaParams& p) {
     // prescaled by scale * log2(e) in the element type - |scale * log2(e)| <= 8 in fp16
     if ((int64_t)a->H * a->Sq > MLA_MAX_ROWS) return FASN_EUNSUPPORTED;
     if (paged && a->page_size % KV_KT != 0) return FASN_EUNSUPPORTED;
-    if ((int64_t)KV_KT * a->kv_stride[1] * 2 >= (1ll << 31)) return FASN_EUNSUPPORTED;
+    if ((int64_t)KV_KT * a->kv_stride[1] * eb >= (1ll << 31)) return FASN_EUNSUPPORTED;
     if (a->dtype == FASN_DTYPE_F16 && !(fabsf(a->scale * kLog2e) <= 8.0f)) return FASN_EUNSUPPORTED;
     int rc;
     if ((rc = kv_check_view(a->q))) return rc;
     if ((rc = kv_check_view(a->o))) return rc;
-    if (!kv_aligned16(a->kv_cache) || a->kv_stride[0] % 8 != 0 || a->kv_stride[1] % 8 != 0) return FASN_EALIGN;
+    if (!kv_aligned16(a->kv_cache) || a->kv_stride[0] % (16 / eb) != 0 || a->kv_stride[1] % (16 / eb) != 0) return FASN_EALIGN;
     if (reinterpret_cast<uintptr_t>(a->seqlens) % 4 || reinterpret_cast<uintptr_t>(a->block_table) % 4 || reinterpret_cast<uintptr_t>(a->n) % 4) return FASN_EALIGN;
     p = MlaParams{};
     p.q = static_cast<const char*>(a->q.ptr);
@@ -68,23 +72,44 @@ int mla_build(const fasn_mla_args* a, MlaParams& p) {
 
 size_t mla_ws_bytes(const MlaParams& p) { return (size_t)p.B * p.nsplit * p.R * (size_t)(MLA_EV + 2) * sizeof(float); }
 
+// the FP8 operand behind the block's checks: NULL, a NULL scale, reserved, a stride that is negative or leaves the 32-bit range
+// (FASN_EINVAL); a scale pointer off 4 bytes (FASN_EALIGN)
+int mla_build_fp8(const fasn_mla_args* a, const fasn_mla_fp8* f, MlaParams& p, MlaFp8& f8) {
+    const int rc = mla_build(a, p, 1);
+    if (rc) return rc;
+    if (f == nullptr || f->kv_scale == nullptr || f->reserved != 0 || f->sb < 0 || f->sb >= (1ll << 31) || (a->B - 1) * f->sb >= (1ll << 31))
+        return FASN_EINVAL;
+    if (reinterpret_cast<uintptr_t>(f->kv_scale) % 4) return FASN_EALIGN;
+    f8 = MlaFp8{f->kv_scale, f->sb};
+    return FASN_OK;
+}
+
+// f8 == nullptr: the 16-bit cache
 template <typename Tag>
-int mla_launch_as(const MlaParams& p, hipStream_t s) {
-    kv_launch<&fasn_mla_fwd_kernel<Tag>>((unsigned)(p.B * p.nrb * p.nsplit), MLA_SMEM, s, p);
+int mla_launch_as(const MlaParams& p, const MlaFp8* f8, hipStream_t s) {
     const int64_t nthr = (int64_t)p.B * p.R * (MLA_EV / 4);
+    if (f8 != nullptr) {
+        kv_launch<&fasn_mla_fwd_fp8_kernel<Tag>>((unsigned)(p.B * p.nrb * p.nsplit), MLA8_SMEM, s, p, *f8);
+        FASN_LAUNCH((fasn_mla_fp8_combine_kernel<Tag>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p, *f8);
+        return launch_rc();
+    }
+    kv_launch<&fasn_mla_fwd_kernel<Tag>>((unsigned)(p.B * p.nrb * p.nsplit), MLA_SMEM, s, p);
     FASN_LAUNCH((fasn_mla_combine_kernel<Tag>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
     return launch_rc();
 }
 
-int mla_forward(const fasn_mla_args* a, void* workspace, size_t workspace_bytes, hipStream_t s) {
+// f == nullptr with fp8 == false: fasn_fwd_mla; fp8: fasn_fwd_mla_fp8, whose operand may be NULL only to be refused
+int mla_forward(const fasn_mla_args* a, bool fp8, const fasn_mla_fp8* f, void* workspace, size_t workspace_bytes, hipStream_t s) {
     MlaParams p;
-    const int rc = mla_build(a, p);
+    MlaFp8 f8;
+    const int rc = fp8 ? mla_build_fp8(a, f, p, f8) : mla_build(a, p);
     if (rc) return rc;
     if (workspace == nullptr || workspace_bytes < mla_ws_bytes(p)) return FASN_EWORKSPACE;
     if (!kv_aligned16(workspace)) return FASN_EALIGN;
     p.part_o = static_cast<float*>(workspace);
     p.part_ml = p.part_o + (size_t)p.B * p.nsplit * p.R * MLA_EV;
-    return a->dtype == FASN_DTYPE_BF16 ? mla_launch_as<bf16_tag>(p, s) : mla_launch_as<f16_tag>(p, s);
+    const MlaFp8* const f8p = fp8 ? &f8 : nullptr;
+    return a->dtype == FASN_DTYPE_BF16 ? mla_launch_as<bf16_tag>(p, f8p, s) : mla_launch_as<f16_tag>(p, f8p, s);
 }
 
 }  // namespace
@@ -100,7 +125,7 @@ size_t fasn_mla_workspace_bytes(const fasn_mla_args* args) {
 }
 
 int fasn_fwd_mla(const fasn_mla_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
-    return mla_forward(args, workspace, workspace_bytes, (hipStream_t)stream);
+    return mla_forward(args, false, nullptr, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int fasn_mla_append(const fasn_mla_args* args, const fasn_view4* kv_new, fasn_stream_t stream) {
@@ -117,7 +142,37 @@ int fasn_mla_append(const fasn_mla_args* args, const fasn_view4* kv_new, fasn_st
 }
 
 int fasn_mla_plan(const fasn_mla_args* args, char* buf, size_t cap) {
-    return record_plan(buf, cap, [&] { return mla_forward(args, plan_workspace(), ~size_t(0), nullptr); });
+    return record_plan(buf, cap, [&] { return mla_forward(args, false, nullptr, plan_workspace(), ~size_t(0), nullptr); });
+}
+
+size_t fasn_mla_fp8_workspace_bytes(const fasn_mla_args* args, const fasn_mla_fp8* fp8) {
+    MlaParams p;
+    MlaFp8 f8;
+    return mla_build_fp8(args, fp8, p, f8) == FASN_OK ? mla_ws_bytes(p) : 0;
+}
+
+int fasn_fwd_mla_fp8(const fasn_mla_args* args, const fasn_mla_fp8* fp8, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return mla_forward(args, true, fp8, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int fasn_mla_fp8_append(const fasn_mla_args* args, const fasn_mla_fp8* fp8, const fasn_view4* kv_new, fasn_stream_t stream) {
+    MlaParams p;
+    MlaFp8 f8;
+    int rc = mla_build_fp8(args, fp8, p, f8);
+    if (rc) return rc;
+    if (kv_new == nullptr) return FASN_EINVAL;
+    if ((rc = kv_check_view(*kv_new))) return rc;
+    p.kn = static_cast<const char*>(kv_new->ptr);
+    p.kns[0] = kv_new->stride[0], p.kns[1] = kv_new->stride[1];
+    const int64_t nthr = (int64_t)p.B * p.Sq * (MLA_E / 16);
+    const dim3 grid((unsigned)((nthr + 255) / 256));
+    if (args->dtype == FASN_DTYPE_BF16) FASN_LAUNCH((fasn_mla_fp8_append_kernel<bf16_tag>), grid, dim3(256), 0, (hipStream_t)stream, p, f8);
+    else FASN_LAUNCH((fasn_mla_fp8_append_kernel<f16_tag>), grid, dim3(256), 0, (hipStream_t)stream, p, f8);
+    return launch_rc();
+}
+
+int fasn_mla_fp8_plan(const fasn_mla_args* args, const fasn_mla_fp8* fp8, char* buf, size_t cap) {
+    return record_plan(buf, cap, [&] { return mla_forward(args, true, fp8, plan_workspace(), ~size_t(0), nullptr); });
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 """MLA decode: attention over a compressed latent K/V cache (multi-head latent attention in its absorbed form: DeepSeek-V2 / V3 / R1,
-Kimi K2). Host side of fasn_fwd_mla / fasn_mla_append in include/fasn.h.
+Kimi K2). Host side of fasn_fwd_mla / fasn_mla_append and of fasn_fwd_mla_fp8 / fasn_mla_fp8_append in include/fasn.h: one call path,
+with the scale of an FP8 latent cache as an optional operand.
 
 The cache holds ONE row of 576 features per token, shared by every query head: a 512-wide latent and a 64-wide rotated key part. The logit
 of head h is q_h[0:576] . row[0:576] and the value is the latent itself, out_h = sum_j p_hj row_j[0:512] - so K and V are one tensor, read
@@ -12,15 +13,17 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import MlaArgs
+from ._lib import MlaArgs, MlaFp8
 from .flash_attn import _n_strides, _n_tensor, _stream_ptr, _view4
-from .kvcache import _KV_DTYPES, _check_cache, _on_device, _rows
+from .kvcache import _KV_DTYPES, _check_cache, _on_device, _rows, _scale_tensor
 
 MLA_HEAD_DIM, MLA_VALUE_DIM, MLA_MAX_ROWS = 576, 512, 256
 _LOG2E = 1.4426950408889634
 _F16_MAX_PRESCALE = 8.0   # float16: |scale * log2e| beyond this is FASN_EUNSUPPORTED (mla_build, csrc/fasn_mla.hip)
-_SERVED = (f"served: a latent cache of head dims exactly {MLA_VALUE_DIM} + 64 = {MLA_HEAD_DIM} in fp16 / bf16, H * Sq <= {MLA_MAX_ROWS}, "
-           "causal or not, softmax_n; not served: an FP8 cache, a window, ALiBi, trees, packed queries, shared prefixes")
+_SERVED = (f"served: a latent cache of head dims exactly {MLA_VALUE_DIM} + 64 = {MLA_HEAD_DIM} in fp16 / bf16 (flash_attention_n_mla) or in "
+           f"e4m3fn codes with kv_scale (flash_attention_n_mla_fp8), H * Sq <= {MLA_MAX_ROWS}, causal or not, softmax_n; not served: e5m2 and "
+           "the fnuz codes, a window, ALiBi, trees, packed queries, shared prefixes")
+_FP8_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2, torch.float8_e4m3fnuz, torch.float8_e5m2fnuz)
 
 
 def flash_attention_n_mla(
@@ -53,21 +56,58 @@ def flash_attention_n_mla(
     :param return_lse: also return lse [B, H, Sq] fp32 = log(n + sum_j exp(x_ij)).
     :return: [B, H, Sq, 512] in query's dtype (and lse). Rows that see no key give exactly 0 and lse = log n (-inf for n = 0).
     """
-    fn = "flash_attention_n_mla"
+    return _mla("flash_attention_n_mla", query, kv_cache, cache_seqlens, scale, None, block_table, kv_new, softmax_n_param, is_causal, return_lse)
+
+
+def flash_attention_n_mla_fp8(
+        query: Tensor,
+        kv_cache: Tensor,
+        cache_seqlens: Tensor,
+        scale: float,
+        kv_scale,
+        block_table: Optional[Tensor] = None,
+        kv_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """flash_attention_n_mla over a latent cache of FP8 codes: 576 bytes per token instead of 1152. Everything flash_attention_n_mla says
+    of shapes, lengths, the block table, stale rows, `scale`, softmax_n, causality and lse holds here; what differs:
+
+    :param query: fp16 / bf16, which is also the dtype of the output and of `kv_new`. Neither the queries nor the weights are quantised.
+    :param kv_cache: torch.float8_e4m3fn (OCP e4m3fn codes), paged [num_pages, page_size, 1, 576] or dense [B, capacity, 1, 576] (or 3-D);
+                  feature stride 1, row and page strides multiples of 16 bytes, base 16-byte aligned; never copied.
+    :param kv_scale: the value of a code is up(code) * kv_scale[b]: a Python float (becomes a one-element device tensor), or a floating
+                  tensor that broadcasts to [B] ([B], [B, 1], [1] or 0-d) ON THE DEVICE - read by the kernels only, so a captured graph
+                  follows its values. It multiplies the fp32 scores (with `scale`) and the fp32 output before its one rounding. One scale
+                  serves the whole row: a model whose rotated 64 features want another scale folds the ratio into the queries' last 64
+                  features. A non-positive or non-finite scale gives unspecified values.
+    :param kv_new: optional [B, Sq, 1, 576] in query's dtype: quantised as flash_attention_n_kvcache quantises k_new for an FP8 cache -
+                  code = rne_e4m3(clamp(float(x) / kv_scale[b], -448, 448)), NaN to a NaN code - written behind the lengths, then seen.
+    """
+    return _mla("flash_attention_n_mla_fp8", query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_new, softmax_n_param, is_causal,
+                return_lse, fp8=True)
+
+
+def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_new, softmax_n_param, is_causal, return_lse, fp8=False):
+    """the one call path of both functions; fp8: the cache holds e4m3fn codes and `kv_scale` is their scale"""
     if not isinstance(query, Tensor) or query.dim() != 4 or not isinstance(kv_cache, Tensor) or kv_cache.dim() not in (3, 4):
         raise ValueError(f"{fn}: query must be [B, H, Sq, {MLA_HEAD_DIM}] and kv_cache [num_pages, page_size, 1, {MLA_HEAD_DIM}] (paged) or "
                          f"[B, capacity, 1, {MLA_HEAD_DIM}] (dense); {_SERVED}")
     if kv_cache.dim() == 3:
         kv_cache = kv_cache.unsqueeze(2)
-    if kv_cache.dtype in (torch.float8_e4m3fn, torch.float8_e5m2, torch.float8_e4m3fnuz, torch.float8_e5m2fnuz):
-        raise TypeError(f"{fn}: an FP8 latent cache ({kv_cache.dtype}) has no kernel; {_SERVED}")
+    if not fp8 and kv_cache.dtype in _FP8_DTYPES:
+        raise TypeError(f"{fn}: an FP8 latent cache ({kv_cache.dtype}) is flash_attention_n_mla_fp8's (e4m3fn codes with kv_scale); {_SERVED}")
+    if fp8 and kv_cache.dtype != torch.float8_e4m3fn:
+        if kv_cache.dtype in _FP8_DTYPES:
+            raise TypeError(f"{fn}: the cache must hold torch.float8_e4m3fn codes; {kv_cache.dtype} has no kernel; {_SERVED}")
+        raise TypeError(f"{fn}: the cache must hold torch.float8_e4m3fn codes; a {kv_cache.dtype} cache is flash_attention_n_mla's")
     B, H, Sq, D = query.shape
     if D != MLA_HEAD_DIM or kv_cache.shape[3] != MLA_HEAD_DIM or kv_cache.shape[2] != 1:
         raise ValueError(f"{fn}: query is {tuple(query.shape)} and kv_cache {tuple(kv_cache.shape)}: not a latent cache; {_SERVED}. "
                          "Separate K and V of one head dim are flash_attention_n_kvcache's")
     if query.dtype not in _KV_DTYPES:
         raise ValueError(f"{fn}: dtype {query.dtype} is not supported; {_SERVED}")
-    if kv_cache.dtype != query.dtype:
+    if not fp8 and kv_cache.dtype != query.dtype:
         raise TypeError(f"{fn}: query and kv_cache must share one dtype; got {query.dtype} and {kv_cache.dtype}")
     if H * Sq > MLA_MAX_ROWS:
         raise ValueError(f"{fn}: H * Sq = {H} x {Sq} = {H * Sq} rows exceed {MLA_MAX_ROWS}; {_SERVED}")
@@ -103,6 +143,9 @@ def flash_attention_n_mla(
             raise ValueError(f"kv_new must be [B, Sq, 1, {MLA_HEAD_DIM}] = [{B}, {Sq}, 1, {MLA_HEAD_DIM}] in {query.dtype}; got {tuple(kv_new.shape)} {kv_new.dtype}")
         kv_new = _rows(kv_new)
     query = _rows(query)
+    if fp8 and isinstance(kv_scale, Tensor) and kv_scale.dim() == 1:   # the one K/V head has no axis here: a 1-D scale is [B]
+        kv_scale = kv_scale[:, None]
+    ks = _scale_tensor(fn, "kv_scale", kv_scale, query, 1) if fp8 else None   # [1 or B, 1] fp32
     if isinstance(softmax_n_param, Tensor):
         nt, n = _n_tensor(softmax_n_param.detach(), query).contiguous(), 0.0
     else:
@@ -135,14 +178,20 @@ def flash_attention_n_mla(
         a.n = nt.data_ptr()
         a.n_stride_b, a.n_stride_h = _n_strides(nt)
     lib = _lib.load()
+    # the entry points and the operands behind the block: the four of the 16-bit cache, or their _fp8 siblings with the scale
+    ops, suffix = (), ""
+    if fp8:
+        f8 = MlaFp8()
+        f8.kv_scale, f8.sb, f8.reserved = ks.data_ptr(), ks.stride(0) if ks.shape[0] > 1 else 0, 0
+        ops, suffix = (f8,), "_fp8"
 
     def launch():
         stream = _stream_ptr(dev)
         if kv_new is not None:
-            _lib.check(lib.fasn_mla_append(a, _view4(kv_new), stream), "fasn_mla_append")
-        ws_bytes = lib.fasn_mla_workspace_bytes(a)
+            _lib.check(getattr(lib, f"fasn_mla{suffix}_append")(a, *ops, _view4(kv_new), stream), f"fasn_mla{suffix}_append")
+        ws_bytes = getattr(lib, f"fasn_mla{suffix}_workspace_bytes")(a, *ops)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # torch's caching allocator: capturable
-        _lib.check(lib.fasn_fwd_mla(a, ws.data_ptr(), ws_bytes, stream), "fasn_fwd_mla")
+        _lib.check(getattr(lib, f"fasn_fwd_mla{suffix}")(a, *ops, ws.data_ptr(), ws_bytes, stream), f"fasn_fwd_mla{suffix}")
 
     _on_device(dev, launch)
     return out if lse is None else (out, lse)

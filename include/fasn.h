@@ -885,7 +885,8 @@ int fasn_prefix_groups_plan(const fasn_kvcache_args* args, const fasn_prefix_gro
  * every step. fasn_mla_append writes the Sq rows of kv_new (a [B, Sq, 1, 576] view) to the cache positions seqlens[b] .. seqlens[b] +
  * Sq - 1 (positions at or beyond the capacity are dropped inside the kernel; `seqlens` is not modified); a forward that is to see them
  * passes seqlen_add = Sq. fasn_mla_plan writes the launches of fasn_fwd_mla as text, in the line format of fasn_launch_plan, without
- * touching a device. Not here: an FP8 cache, a window, ALiBi, trees, packed queries, shared prefixes, gradients.
+ * touching a device. Not here: a window, ALiBi, trees, packed queries, shared prefixes, gradients. An FP8 latent cache has entry points of
+ * its own (MLA DECODE OVER AN FP8 LATENT CACHE, below); these four refuse nothing they served before.
  */
 typedef struct fasn_mla_args {
     fasn_view4 q;          /* [B,H,Sq,576] */
@@ -913,6 +914,38 @@ size_t fasn_mla_workspace_bytes(const fasn_mla_args* args);
 int fasn_fwd_mla(const fasn_mla_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
 int fasn_mla_append(const fasn_mla_args* args, const fasn_view4* kv_new, fasn_stream_t stream);
 int fasn_mla_plan(const fasn_mla_args* args, char* buf, size_t cap);
+
+/*
+ * MLA DECODE OVER AN FP8 LATENT CACHE (additions within ABI 6; no struct or function above is changed): the MLA decode above on a cache of
+ * OCP e4m3fn codes - 576 bytes per token instead of 1152 - with ONE fp32 scale per batch element in device memory, kv_scale[b * sb]
+ * (sb = 0 broadcasts). The semantics are those of FP8 K/V CACHE, reduced to the one tensor an MLA cache has:
+ *     value(code) = up(code) * kv_scale[b]                                   up() the exact upcast
+ *     x_ij  = scale * kv_scale[b] * (q_hi[0:576] . up(c_j[0:576]))            one fp32 factor on the scores
+ *     o_hi  = kv_scale[b] * sum_j p_ij up(c_j[0:512]) / (n + sum_j p_ij)      scaled in fp32, rounded once
+ * Neither Q nor P is quantised. The scale is read by the kernels only, so a captured graph follows it; a non-positive or non-finite scale
+ * gives unspecified values and touches no memory outside the buffers. There is one scale for the whole row: a model whose rotated 64
+ * features want another one folds the ratio into the queries' last 64 features. In fp16 the queries stay prescaled (|scale * log2(e)| <= 8)
+ * and kv_scale acts on the fp32 scores; in bf16 the scores are multiplied by scale * log2(e) * kv_scale[b] once.
+ *
+ * The block is fasn_mla_args with kv_cache pointing at the codes, kv_stride counting codes (= bytes; both multiples of 16, kv_stride[1] >=
+ * 576) and dtype that of q, o and kv_new. Every check of fasn_fwd_mla runs first, with its codes, the cache's 16-byte rule read in bytes;
+ * then fp8 == NULL, a NULL kv_scale, reserved != 0, a negative sb or (B - 1) * sb >= 2^31 (FASN_EINVAL) and a scale pointer off 4 bytes
+ * (FASN_EALIGN); the workspace last; all of it before any HIP call. Workspace, split rule, grid, the 144 KiB of LDS and everything else
+ * fasn_fwd_mla says of lengths, stale rows, unread table entries, the sink and lse hold here unchanged. fasn_mla_fp8_append quantises the
+ * rows of kv_new (16-bit, [B, Sq, 1, 576]) as fasn_kvcache_fp8_append quantises k_new - code = rne_e4m3(clamp(float(x) / kv_scale[b],
+ * -448, 448)), the division correctly rounded, NaN to a NaN code - and writes them at seqlens[b] .. seqlens[b] + Sq - 1, positions at or
+ * beyond the capacity dropped in the kernel. Not here: e5m2, per-token or per-block scales, FP8 MFMAs.
+ */
+typedef struct fasn_mla_fp8 {
+    const float* kv_scale; /* DEVICE */
+    int64_t sb;            /* element stride between batch elements; 0 broadcasts */
+    int32_t reserved;      /* 0 */
+} fasn_mla_fp8;
+
+size_t fasn_mla_fp8_workspace_bytes(const fasn_mla_args* args, const fasn_mla_fp8* fp8);
+int fasn_fwd_mla_fp8(const fasn_mla_args* args, const fasn_mla_fp8* fp8, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_mla_fp8_append(const fasn_mla_args* args, const fasn_mla_fp8* fp8, const fasn_view4* kv_new, fasn_stream_t stream);
+int fasn_mla_fp8_plan(const fasn_mla_args* args, const fasn_mla_fp8* fp8, char* buf, size_t cap);
 
 /*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,

@@ -9,7 +9,12 @@ Both are captured in a HIP graph of REPS calls so that host time is out of the p
 and timed with device events. Reported: microseconds per call for every alternation, A / B, A's own spread between its alternations (the
 margin B is judged against), max |A - B| and B's TB/s of VISIBLE cache bytes (B * len * 1152: the cache is read once per 64 rows, so the
 bytes moved are ceil(H * Sq / 64) times that).
-usage: python tools/bench_mla.py [--rounds N] [--iters N] [--only I]"""
+
+--fp8: the FP8 latent cache against the 16-bit one, same shapes, lengths and alternation.
+  A = flash_attention_n_mla on the pool of bf16 numbers that ARE the codes (pool8.to(bf16)),
+  B = flash_attention_n_mla_fp8 on the codes with kv_scale = 1 - so max |A - B| must be 0 - and both columns of TB/s count their own
+      visible cache bytes once (B * len * 1152 for A, B * len * 576 for B).
+usage: python tools/bench_mla.py [--fp8] [--rounds N] [--iters N] [--only I]"""
 import argparse
 import sys
 
@@ -56,11 +61,15 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--only", type=int, default=None)
+    ap.add_argument("--fp8", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_mla needs a GPU"
     dev, dtype = torch.device("cuda:0"), torch.bfloat16
     print(f"device: {torch.cuda.get_device_name(0)}; {REPS} calls per graph, {args.iters} replays per timing, {args.rounds} alternations A/B; bf16, page {PAGE}, n = 1")
-    print(f"{'shape (B,H,Sq,len)':24s} {'A us':>26s} {'B us':>26s} {'A/B':>6s} {'A spread':>9s} {'max|A-B|':>9s} {'B TB/s visible':>15s}")
+    if args.fp8:
+        print("A = flash_attention_n_mla (bf16 cache), B = flash_attention_n_mla_fp8 (e4m3fn cache, kv_scale = 1)")
+    print(f"{'shape (B,H,Sq,len)':24s} {'A us':>26s} {'B us':>26s} {'A/B':>6s} {'A spread':>9s} {'max|A-B|':>9s} "
+          + (f"{'A TB/s visible':>15s} " if args.fp8 else "") + f"{'B TB/s visible':>15s}")
     for idx, (B, H, Sq, ln) in enumerate(SHAPES):
         if args.only is not None and idx != args.only:
             continue
@@ -68,6 +77,9 @@ def main():
         max_pages = (ln + PAGE - 1) // PAGE
         q = torch.randn(B, H, Sq, E, device=dev, dtype=dtype) * 0.5
         pool = torch.randn(B * max_pages, PAGE, 1, E, device=dev, dtype=dtype) * 0.5
+        if args.fp8:   # the codes nearest to the same values, and the 16-bit pool of exactly those numbers
+            pool8 = pool.to(torch.float8_e4m3fn)
+            pool = pool8.to(dtype)
         table = torch.randperm(B * max_pages, device=dev).to(torch.int32).view(B, max_pages)
         sl = torch.full((B,), ln, dtype=torch.int32, device=dev)
         pos = torch.arange(max_pages * PAGE, device=dev).view(1, 1, 1, -1)
@@ -84,9 +96,12 @@ def main():
         def run_b():
             return fa.flash_attention_n_mla(q, pool, sl, SCALE, block_table=table)
 
+        def run_b8():
+            return fa.flash_attention_n_mla_fp8(q, pool8, sl, SCALE, 1.0, block_table=table)
+
         with torch.no_grad():
-            ga, oa = graph_of(run_a)
-            gb, ob = graph_of(run_b)
+            ga, oa = graph_of(run_b if args.fp8 else run_a)
+            gb, ob = graph_of(run_b8 if args.fp8 else run_b)
             ta, tb = [], []
             for _ in range(args.rounds):
                 ta.append(time_graph(ga, args.iters))
@@ -94,8 +109,9 @@ def main():
             diff = (oa.float() - ob.float()).abs().max().item()
         a_med, b_med = sorted(ta)[len(ta) // 2], sorted(tb)[len(tb) // 2]
         fmt = lambda ts: "/".join(f"{t:.1f}" for t in ts)   # noqa: E731
-        tbs = B * ln * E * 2 / (b_med * 1e-6) / 1e12
-        print(f"{str((B, H, Sq, ln)):24s} {fmt(ta):>26s} {fmt(tb):>26s} {a_med / b_med:6.2f} {max(ta) / min(ta):9.3f} {diff:9.2e} {tbs:15.2f}", flush=True)
+        tbs = B * ln * E * (1 if args.fp8 else 2) / (b_med * 1e-6) / 1e12
+        tas = f"{B * ln * E * 2 / (a_med * 1e-6) / 1e12:15.2f} " if args.fp8 else ""
+        print(f"{str((B, H, Sq, ln)):24s} {fmt(ta):>26s} {fmt(tb):>26s} {a_med / b_med:6.2f} {max(ta) / min(ta):9.3f} {diff:9.2e} {tas}{tbs:15.2f}", flush=True)
         del ga, gb, pool
         torch.cuda.empty_cache()
 
