@@ -54,6 +54,7 @@ EXPORTS = (
     "fasn_fwd_prefix_groups_workspace_bytes", "fasn_fwd_prefix_groups", "fasn_prefix_groups_plan",
     "fasn_mla_workspace_bytes", "fasn_fwd_mla", "fasn_mla_append", "fasn_mla_plan",
     "fasn_mla_fp8_workspace_bytes", "fasn_fwd_mla_fp8", "fasn_mla_fp8_append", "fasn_mla_fp8_plan",
+    "fasn_mla_sparse_workspace_bytes", "fasn_fwd_mla_sparse", "fasn_mla_sparse_plan",
 )
 
 
@@ -209,6 +210,11 @@ class MlaFp8(Structure):
     _fields_ = [("kv_scale", c_void_p), ("sb", c_int64), ("reserved", c_int32)]
 
 
+class MlaSparse(Structure):
+    """fasn_mla_sparse (include/fasn.h): the top-k index list of the sparse MLA decode, int32 [B, Sq, topk] in device memory"""
+    _fields_ = [("indices", c_void_p), ("stride_b", c_int64), ("stride_q", c_int64), ("topk", c_int32), ("reserved", c_int32)]
+
+
 class FasnError(RuntimeError):
     pass
 
@@ -324,6 +330,10 @@ def _mla_bindings():
     yield "fasn_fwd_mla_fp8", c_int32, head + [c_void_p, c_size_t, c_void_p]
     yield "fasn_mla_fp8_append", c_int32, head + [POINTER(View4), c_void_p]
     yield "fasn_mla_fp8_plan", c_int32, head + [c_char_p, c_size_t]
+    head = [POINTER(MlaArgs), POINTER(MlaSparse)]   # ... and the three behind an index list (the append is fasn_mla_append)
+    yield "fasn_mla_sparse_workspace_bytes", c_size_t, head
+    yield "fasn_fwd_mla_sparse", c_int32, head + [c_void_p, c_size_t, c_void_p]
+    yield "fasn_mla_sparse_plan", c_int32, head + [c_char_p, c_size_t]
 
 
 def kv_call(args, fp8=None, tree=None, window=None, alibi=None):
@@ -601,6 +611,12 @@ def mla_fp8_plan(args, fp8):
     """The two launches of fasn_fwd_mla_fp8 for `args` (an MlaArgs over a cache of codes) and `fp8` (an MlaFp8): mla_plan's grid and LDS
     with the FP8 kernels' names. Nothing is launched."""
     return _plan("fasn_mla_fp8_plan", args, fp8)
+
+
+def mla_sparse_plan(args, sparse):
+    """The two launches of fasn_fwd_mla_sparse for `args` (an MlaArgs) and `sparse` (an MlaSparse) - the gathering forward on
+    B * Sq * ceil(H / 64) * nsplit workgroups, the dense call's combine - as launch_plan returns them. Nothing is launched."""
+    return _plan("fasn_mla_sparse_plan", args, sparse)
 
 
 def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):

@@ -261,9 +261,13 @@ __global__ void __launch_bounds__(256, 1) fasn_mla_fwd_kernel(const MlaParams p)
                 // S^T, mask, softmax, O^T on the image in buffer `buf` (the text is shared with the FP8 sibling, fasn_mla_fp8.h)
 #define MLA_TILE_AT (buf * MLA_TILEB)
 #define MLA_SCORE(x) (PRESCALE ? (x) : (x) * p.c)
+#define MLA_TILE_ALL_VISIBLE (k0 + KV_KT - 1 <= all_vis)
+#define MLA_KEY_VISIBLE(kb, r) (k0 + (kb) * 32 + ((r) & 3) + 8 * ((r) >> 2) + 4 * hi <= vis)
 #include "fasn_mla_tile.inc"
 #undef MLA_TILE_AT
 #undef MLA_SCORE
+#undef MLA_TILE_ALL_VISIBLE
+#undef MLA_KEY_VISIBLE
             }
             buf ^= 1;
         }

@@ -8,6 +8,7 @@
 #include "fasn_kv_host.h"
 #include "fasn_mla.h"
 #include "fasn_mla_fp8.h"
+#include "fasn_mla_sparse.h"
 
 namespace fasn {
 namespace {
@@ -84,10 +85,39 @@ int mla_build_fp8(const fasn_mla_args* a, const fasn_mla_fp8* f, MlaParams& p, M
     return FASN_OK;
 }
 
-// f8 == nullptr: the 16-bit cache
+// the index list behind the block's checks: NULL, a NULL list, reserved, topk <= 0, a stride that is negative or leaves the 32-bit range
+// (FASN_EINVAL); a topk that is no multiple of the 64-key tile (FASN_EUNSUPPORTED); a list off 4 bytes (FASN_EALIGN). The plan: one
+// workgroup per (batch element, position, 64-head block, split), split s over the index tiles [s * tps, (s + 1) * tps).
+int mla_build_sparse(const fasn_mla_args* a, const fasn_mla_sparse* x, MlaParams& p, MlaSparse& sp) {
+    const int rc = mla_build(a, p);
+    if (rc) return rc;
+    if (x == nullptr || x->indices == nullptr || x->reserved != 0 || x->topk <= 0 || x->stride_b < 0 || x->stride_q < 0 ||
+        x->stride_b >= (1ll << 31) || x->stride_q >= (1ll << 31) || (a->B - 1) * x->stride_b + (a->Sq - 1) * x->stride_q + x->topk >= (1ll << 31))
+        return FASN_EINVAL;
+    if (x->topk % KV_KT != 0) return FASN_EUNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(x->indices) % 4) return FASN_EALIGN;
+    sp = MlaSparse{};
+    sp.idx = x->indices;
+    sp.sb = x->stride_b, sp.sq = x->stride_q;
+    sp.ntiles = x->topk / KV_KT;
+    sp.nhb = (p.H + MLA_RB - 1) / MLA_RB;
+    sp.ps_magic = (uint32_t)((1ull << 32) / (uint64_t)p.page_size);   // (a paged cache has page_size >= 64; a dense one does not divide)
+    const int64_t base = (int64_t)p.B * p.Sq * sp.nhb;
+    p.nsplit = (int)mla_nsplit(base, sp.ntiles, p.H < MLA_RB ? p.H : MLA_RB);
+    sp.tps = (sp.ntiles + p.nsplit - 1) / p.nsplit;
+    if (base * p.nsplit > INT_MAX / MLA_MAX_ROWS) return FASN_EINVAL;
+    return FASN_OK;
+}
+
+// f8 == nullptr: the 16-bit cache; sp != nullptr: behind an index list
 template <typename Tag>
-int mla_launch_as(const MlaParams& p, const MlaFp8* f8, hipStream_t s) {
+int mla_launch_as(const MlaParams& p, const MlaFp8* f8, const MlaSparse* sp, hipStream_t s) {
     const int64_t nthr = (int64_t)p.B * p.R * (MLA_EV / 4);
+    if (sp != nullptr) {
+        kv_launch<&fasn_mla_sparse_fwd_kernel<Tag>>((unsigned)(p.B * p.Sq * sp->nhb * p.nsplit), MLA_SMEM, s, p, *sp);
+        FASN_LAUNCH((fasn_mla_combine_kernel<Tag>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p);
+        return launch_rc();
+    }
     if (f8 != nullptr) {
         kv_launch<&fasn_mla_fwd_fp8_kernel<Tag>>((unsigned)(p.B * p.nrb * p.nsplit), MLA8_SMEM, s, p, *f8);
         FASN_LAUNCH((fasn_mla_fp8_combine_kernel<Tag>), dim3((unsigned)((nthr + 255) / 256)), dim3(256), 0, s, p, *f8);
@@ -98,18 +128,22 @@ int mla_launch_as(const MlaParams& p, const MlaFp8* f8, hipStream_t s) {
     return launch_rc();
 }
 
-// f == nullptr with fp8 == false: fasn_fwd_mla; fp8: fasn_fwd_mla_fp8, whose operand may be NULL only to be refused
-int mla_forward(const fasn_mla_args* a, bool fp8, const fasn_mla_fp8* f, void* workspace, size_t workspace_bytes, hipStream_t s) {
+// f == nullptr with fp8 == false: fasn_fwd_mla; fp8: fasn_fwd_mla_fp8, whose operand may be NULL only to be refused; sparse: fasn_fwd_mla_sparse,
+// likewise with x
+int mla_forward(const fasn_mla_args* a, bool fp8, const fasn_mla_fp8* f, void* workspace, size_t workspace_bytes, hipStream_t s,
+                bool sparse = false, const fasn_mla_sparse* x = nullptr) {
     MlaParams p;
     MlaFp8 f8;
-    const int rc = fp8 ? mla_build_fp8(a, f, p, f8) : mla_build(a, p);
+    MlaSparse sp;
+    const int rc = sparse ? mla_build_sparse(a, x, p, sp) : fp8 ? mla_build_fp8(a, f, p, f8) : mla_build(a, p);
     if (rc) return rc;
     if (workspace == nullptr || workspace_bytes < mla_ws_bytes(p)) return FASN_EWORKSPACE;
     if (!kv_aligned16(workspace)) return FASN_EALIGN;
     p.part_o = static_cast<float*>(workspace);
     p.part_ml = p.part_o + (size_t)p.B * p.nsplit * p.R * MLA_EV;
     const MlaFp8* const f8p = fp8 ? &f8 : nullptr;
-    return a->dtype == FASN_DTYPE_BF16 ? mla_launch_as<bf16_tag>(p, f8p, s) : mla_launch_as<f16_tag>(p, f8p, s);
+    const MlaSparse* const spp = sparse ? &sp : nullptr;
+    return a->dtype == FASN_DTYPE_BF16 ? mla_launch_as<bf16_tag>(p, f8p, spp, s) : mla_launch_as<f16_tag>(p, f8p, spp, s);
 }
 
 }  // namespace
@@ -173,6 +207,20 @@ int fasn_mla_fp8_append(const fasn_mla_args* args, const fasn_mla_fp8* fp8, cons
 
 int fasn_mla_fp8_plan(const fasn_mla_args* args, const fasn_mla_fp8* fp8, char* buf, size_t cap) {
     return record_plan(buf, cap, [&] { return mla_forward(args, true, fp8, plan_workspace(), ~size_t(0), nullptr); });
+}
+
+size_t fasn_mla_sparse_workspace_bytes(const fasn_mla_args* args, const fasn_mla_sparse* sparse) {
+    MlaParams p;
+    MlaSparse sp;
+    return mla_build_sparse(args, sparse, p, sp) == FASN_OK ? mla_ws_bytes(p) : 0;
+}
+
+int fasn_fwd_mla_sparse(const fasn_mla_args* args, const fasn_mla_sparse* sparse, void* workspace, size_t workspace_bytes, fasn_stream_t stream) {
+    return mla_forward(args, false, nullptr, workspace, workspace_bytes, (hipStream_t)stream, true, sparse);
+}
+
+int fasn_mla_sparse_plan(const fasn_mla_args* args, const fasn_mla_sparse* sparse, char* buf, size_t cap) {
+    return record_plan(buf, cap, [&] { return mla_forward(args, false, nullptr, plan_workspace(), ~size_t(0), nullptr, true, sparse); });
 }
 
 }  // extern "C"

@@ -221,9 +221,13 @@ __global__ void __launch_bounds__(256, 1) fasn_mla_fwd_fp8_kernel(const MlaParam
             if (wave_rows) {
 #define MLA_TILE_AT 0
 #define MLA_SCORE(x) ((x) * sc)
+#define MLA_TILE_ALL_VISIBLE (k0 + KV_KT - 1 <= all_vis)
+#define MLA_KEY_VISIBLE(kb, r) (k0 + (kb) * 32 + ((r) & 3) + 8 * ((r) >> 2) + 4 * hi <= vis)
 #include "fasn_mla_tile.inc"
 #undef MLA_TILE_AT
 #undef MLA_SCORE
+#undef MLA_TILE_ALL_VISIBLE
+#undef MLA_KEY_VISIBLE
             }
             cb ^= 1;
         }

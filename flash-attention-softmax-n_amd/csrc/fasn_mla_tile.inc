@@ -3,7 +3,10 @@
 // cache (fasn_mla_fp8.h), which differ in where the 16-bit tile image lies and in the factor on the scores:
 //   MLA_TILE_AT    byte offset of this tile's image behind the lane parts ka / va
 //   MLA_SCORE(x)   the fp32 score x of the MFMAs in the log2 domain
-// Everything else - t, the lane parts, qf, vis / all_vis, the row's (m_run, l_run) and oacc - is the including kernel's.
+// and, with the kernel over an index list (fasn_mla_sparse.h), in what a visible key is (k0 = t * 64 is this tile's first key of a walk):
+//   MLA_TILE_ALL_VISIBLE     every row sees every key of the tile (wave-uniform)
+//   MLA_KEY_VISIBLE(kb, r)   the lane's row sees the key of accumulator register r of key block kb: key kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi
+// Everything else - t, the lane parts, qf, the row's (m_run, l_run) and oacc - is the including kernel's.
 {
     // the lane parts inside this tile's buffer, opaque so that the literals stay literals (the instructions' offset fields)
     uint32_t kt[4], vt[2][2];
@@ -31,7 +34,7 @@
     }
     // hidden keys (beyond the row's causal limit, which is below len_b) at -inf
     float mx = -INFINITY;
-    if (k0 + KV_KT - 1 <= all_vis) {   // wave-uniform (lanes without a row carry zero queries; their state is never stored)
+    if (MLA_TILE_ALL_VISIBLE) {   // wave-uniform (lanes without a row carry zero queries; their state is never stored)
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -44,8 +47,7 @@
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int key = k0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi;
-                const float y = key <= vis ? MLA_SCORE(sacc[kb][r]) : -INFINITY;
+                const float y = MLA_KEY_VISIBLE(kb, r) ? MLA_SCORE(sacc[kb][r]) : -INFINITY;
                 sacc[kb][r] = y;
                 mx = fmaxf(mx, y);
             }

@@ -1,6 +1,7 @@
 """MLA decode: attention over a compressed latent K/V cache (multi-head latent attention in its absorbed form: DeepSeek-V2 / V3 / R1,
-Kimi K2). Host side of fasn_fwd_mla / fasn_mla_append and of fasn_fwd_mla_fp8 / fasn_mla_fp8_append in include/fasn.h: one call path,
-with the scale of an FP8 latent cache as an optional operand.
+Kimi K2). Host side of fasn_fwd_mla / fasn_mla_append, of fasn_fwd_mla_fp8 / fasn_mla_fp8_append and of fasn_fwd_mla_sparse in
+include/fasn.h: one call path, with the scale of an FP8 latent cache and the top-k index list of the sparse decode (DeepSeek-V3.2) as
+optional operands.
 
 The cache holds ONE row of 576 features per token, shared by every query head: a 512-wide latent and a 64-wide rotated key part. The logit
 of head h is q_h[0:576] . row[0:576] and the value is the latent itself, out_h = sum_j p_hj row_j[0:512] - so K and V are one tensor, read
@@ -13,7 +14,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import MlaArgs, MlaFp8
+from ._lib import MlaArgs, MlaFp8, MlaSparse
 from .flash_attn import _n_strides, _n_tensor, _stream_ptr, _view4
 from .kvcache import _KV_DTYPES, _check_cache, _on_device, _rows, _scale_tensor
 
@@ -21,8 +22,10 @@ MLA_HEAD_DIM, MLA_VALUE_DIM, MLA_MAX_ROWS = 576, 512, 256
 _LOG2E = 1.4426950408889634
 _F16_MAX_PRESCALE = 8.0   # float16: |scale * log2e| beyond this is FASN_EUNSUPPORTED (mla_build, csrc/fasn_mla.hip)
 _SERVED = (f"served: a latent cache of head dims exactly {MLA_VALUE_DIM} + 64 = {MLA_HEAD_DIM} in fp16 / bf16 (flash_attention_n_mla) or in "
-           f"e4m3fn codes with kv_scale (flash_attention_n_mla_fp8), H * Sq <= {MLA_MAX_ROWS}, causal or not, softmax_n; not served: e5m2 and "
-           "the fnuz codes, a window, ALiBi, trees, packed queries, shared prefixes")
+           f"e4m3fn codes with kv_scale (flash_attention_n_mla_fp8), H * Sq <= {MLA_MAX_ROWS}, causal or not, softmax_n; behind a top-k list "
+           "of logical positions (flash_attention_n_mla_sparse): the fp16 / bf16 cache, int32 indices [B, Sq, topk] on the device with "
+           "topk a multiple of 64; not served: e5m2 and the fnuz codes, a window, ALiBi, trees, packed queries, shared prefixes, an FP8 "
+           f"cache behind indices, physical (pool) indices, more than {MLA_MAX_ROWS} rows, gradients")
 _FP8_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2, torch.float8_e4m3fnuz, torch.float8_e5m2fnuz)
 
 
@@ -88,8 +91,40 @@ def flash_attention_n_mla_fp8(
                 return_lse, fp8=True)
 
 
-def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_new, softmax_n_param, is_causal, return_lse, fp8=False):
-    """the one call path of both functions; fp8: the cache holds e4m3fn codes and `kv_scale` is their scale"""
+def flash_attention_n_mla_sparse(
+        query: Tensor,
+        kv_cache: Tensor,
+        indices: Tensor,
+        cache_seqlens: Tensor,
+        scale: float,
+        block_table: Optional[Tensor] = None,
+        kv_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """flash_attention_n_mla over the cache rows that a top-k index list names (DeepSeek-V3.2's sparse attention: an indexer selects a
+    fixed budget of tokens per query position, the attention gathers their latent rows). Everything flash_attention_n_mla says of
+    `query` (H * Sq <= 256), the paged / dense / 3-D fp16 / bf16 cache, `cache_seqlens`, `block_table`, `scale`, `kv_new` (appended first,
+    then nameable), softmax_n, lse and the 512-wide output holds here; what differs:
+
+    :param indices: int32 [B, Sq, topk] ON THE DEVICE, last stride 1, topk a multiple of 64 (the call does not pad: a pad is a copy and
+                  a launch). Entry e of (b, i) names the LOGICAL position j = indices[b, i, e] of batch element b - the kernel
+                  translates it through the block table - and every head of position i shares the list. j is a key of position i iff
+                  0 <= j < len_b and, when is_causal, j <= i + len_b - Sq, with len_b = clamp(cache_seqlens[b] + (Sq if kv_new else 0),
+                  0, capacity). Every other value - -1 padding, positions at or beyond the length, causally hidden ones, garbage - is no
+                  key: it contributes nothing, and neither its block-table slot nor its cache row is read. A position named twice counts
+                  twice. Read by the kernels only: the launches depend on shapes, topk and capacity alone, so one captured graph
+                  serves every step.
+    :return: [B, H, Sq, 512] in query's dtype (and lse). Rows without a key give exactly 0 and lse = log n.
+    """
+    return _mla("flash_attention_n_mla_sparse", query, kv_cache, cache_seqlens, scale, None, block_table, kv_new, softmax_n_param, is_causal,
+                return_lse, indices=indices, sparse=True)
+
+
+def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_new, softmax_n_param, is_causal, return_lse, fp8=False,
+         indices=None, sparse=False):
+    """the one call path of the three functions; fp8: the cache holds e4m3fn codes and `kv_scale` is their scale; sparse: `indices` is the
+    top-k list of logical positions"""
     if not isinstance(query, Tensor) or query.dim() != 4 or not isinstance(kv_cache, Tensor) or kv_cache.dim() not in (3, 4):
         raise ValueError(f"{fn}: query must be [B, H, Sq, {MLA_HEAD_DIM}] and kv_cache [num_pages, page_size, 1, {MLA_HEAD_DIM}] (paged) or "
                          f"[B, capacity, 1, {MLA_HEAD_DIM}] (dense); {_SERVED}")
@@ -119,10 +154,19 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
         raise ValueError(f"{fn}: float16 serves |scale| * log2(e) <= {_F16_MAX_PRESCALE:g} (the queries are prescaled in float16); got scale "
                          f"{scale}. Use bfloat16, or fold the factor into the queries")
     dev = query.device
-    for name, t in (("kv_cache", kv_cache), ("cache_seqlens", cache_seqlens), ("block_table", block_table), ("kv_new", kv_new)):
+    if sparse:
+        if not isinstance(indices, Tensor) or indices.dtype != torch.int32 or tuple(indices.shape[:2]) != (B, Sq) or indices.dim() != 3 \
+                or indices.stride(2) != 1:
+            got = f"{indices.dtype} {tuple(indices.shape)}" if isinstance(indices, Tensor) else type(indices).__name__
+            raise ValueError(f"{fn}: indices must be an int32 tensor [B, Sq, topk] = [{B}, {Sq}, topk] of logical positions with unit last "
+                             f"stride; got {got}; {_SERVED}")
+        if indices.shape[2] < 64 or indices.shape[2] % 64 != 0:
+            raise ValueError(f"{fn}: topk = {indices.shape[2]} is not supported: topk % 64 == 0 and topk >= 64 (pad the list with -1 where "
+                             f"it is built: the call does not copy it); {_SERVED}")
+    for name, t in (("kv_cache", kv_cache), ("indices", indices), ("cache_seqlens", cache_seqlens), ("block_table", block_table), ("kv_new", kv_new)):
         if t is not None and t.device != dev:
             raise RuntimeError(f"{name} is on {t.device}, query on {dev}: every operand must live on the query's device "
-                               "(the lengths and the block table are read by the kernels, never on the host)")
+                               f"(the lengths, the block table and the index list are read by the kernels, never on the host); {_SERVED}")
     if torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in (query, kv_cache, kv_new))
                                     or (isinstance(softmax_n_param, Tensor) and softmax_n_param.requires_grad)):
         raise RuntimeError(f"{fn} is forward only (inference): an input requires grad. Call it under torch.no_grad()")
@@ -178,17 +222,25 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
         a.n = nt.data_ptr()
         a.n_stride_b, a.n_stride_h = _n_strides(nt)
     lib = _lib.load()
-    # the entry points and the operands behind the block: the four of the 16-bit cache, or their _fp8 siblings with the scale
-    ops, suffix = (), ""
+    # the entry points and the operands behind the block: the four of the 16-bit cache, their _fp8 siblings with the scale, or the
+    # _sparse ones with the index list (whose append is the 16-bit cache's)
+    ops, suffix, app = (), "", ()
     if fp8:
         f8 = MlaFp8()
         f8.kv_scale, f8.sb, f8.reserved = ks.data_ptr(), ks.stride(0) if ks.shape[0] > 1 else 0, 0
         ops, suffix = (f8,), "_fp8"
+        app = ops
+    if sparse:
+        sp = MlaSparse()
+        sp.indices, sp.topk, sp.reserved = indices.data_ptr(), indices.shape[2], 0
+        sp.stride_b, sp.stride_q = indices.stride(0) if B > 1 else 0, indices.stride(1) if Sq > 1 else 0
+        ops, suffix = (sp,), "_sparse"
+    app_name = "fasn_mla_fp8_append" if fp8 else "fasn_mla_append"
 
     def launch():
         stream = _stream_ptr(dev)
         if kv_new is not None:
-            _lib.check(getattr(lib, f"fasn_mla{suffix}_append")(a, *ops, _view4(kv_new), stream), f"fasn_mla{suffix}_append")
+            _lib.check(getattr(lib, app_name)(a, *app, _view4(kv_new), stream), app_name)
         ws_bytes = getattr(lib, f"fasn_mla{suffix}_workspace_bytes")(a, *ops)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # torch's caching allocator: capturable
         _lib.check(getattr(lib, f"fasn_fwd_mla{suffix}")(a, *ops, ws.data_ptr(), ws_bytes, stream), f"fasn_fwd_mla{suffix}")

@@ -948,6 +948,37 @@ int fasn_mla_fp8_append(const fasn_mla_args* args, const fasn_mla_fp8* fp8, cons
 int fasn_mla_fp8_plan(const fasn_mla_args* args, const fasn_mla_fp8* fp8, char* buf, size_t cap);
 
 /*
+ * SPARSE MLA DECODE: TOP-K TOKEN INDICES OVER THE LATENT CACHE (additions within ABI 6; no struct or function above is changed): the MLA
+ * decode above restricted, per query position, to the cache rows an index list names (DeepSeek-V3.2's sparse attention: an indexer picks a
+ * fixed budget of tokens, the attention gathers their latent rows). indices is int32 [B, Sq, topk] in DEVICE memory, entry e of (b, i) at
+ * indices[b * stride_b + i * stride_q + e]; every head of position i shares the list. An entry j is a LOGICAL position of batch element b
+ * (the kernel translates it through the block table, as the dense walk does) and is a key of position i iff
+ *     0 <= j < len_b   and, when causal,   j <= i + len_b - Sq            len_b = clamp(seqlens[b] + seqlen_add, 0, capacity)
+ * Every other value - -1 padding, positions at or beyond the length, causally hidden ones, garbage - is no key: it contributes nothing and
+ * NO ADDRESS IS FORMED FROM IT, neither its block-table slot nor its cache row is read. A position named twice counts twice. Rows without
+ * a key give exactly 0 and lse = log n. The list is read by the kernels only: launches depend on shapes, topk and capacity alone.
+ *
+ * The block is fasn_mla_args over the 16-bit cache, unchanged. Every check of fasn_fwd_mla runs first, with its codes and order; then
+ * sparse == NULL, a NULL indices, reserved != 0, topk <= 0, a negative stride or strides under which an entry's offset leaves the 32-bit
+ * range (FASN_EINVAL); topk % 64 != 0 (FASN_EUNSUPPORTED: the library does not pad); indices off 4 bytes (FASN_EALIGN); the workspace
+ * last; all of it before any HIP call. Two launches: fasn_mla_sparse_fwd_kernel on B * Sq * ceil(H / 64) * nsplit workgroups (a work item
+ * is a batch element, a position, a block of 64 heads and a split of the topk / 64 index tiles; 144 KiB of LDS) and the combine of
+ * fasn_fwd_mla. fasn_mla_sparse_workspace_bytes(args, sparse) = B * nsplit * H * Sq * 514 * 4 bytes, 16-byte aligned, with this call's
+ * nsplit (a function of B, H, Sq and topk). The append is fasn_mla_append with the same block; the caller then passes seqlen_add = Sq.
+ * Not here: an FP8 cache behind indices, physical (pool) indices, H * Sq > 256, gradients.
+ */
+typedef struct fasn_mla_sparse {
+    const int32_t* indices; /* DEVICE */
+    int64_t stride_b, stride_q; /* element strides between batch elements and between positions; the entry stride is 1 */
+    int32_t topk;           /* entries per list: a positive multiple of 64 */
+    int32_t reserved;       /* 0 */
+} fasn_mla_sparse;
+
+size_t fasn_mla_sparse_workspace_bytes(const fasn_mla_args* args, const fasn_mla_sparse* sparse);
+int fasn_fwd_mla_sparse(const fasn_mla_args* args, const fasn_mla_sparse* sparse, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_mla_sparse_plan(const fasn_mla_args* args, const fasn_mla_sparse* sparse, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).

@@ -14,7 +14,13 @@ bytes moved are ceil(H * Sq / 64) times that).
   A = flash_attention_n_mla on the pool of bf16 numbers that ARE the codes (pool8.to(bf16)),
   B = flash_attention_n_mla_fp8 on the codes with kv_scale = 1 - so max |A - B| must be 0 - and both columns of TB/s count their own
       visible cache bytes once (B * len * 1152 for A, B * len * 576 for B).
-usage: python tools/bench_mla.py [--fp8] [--rounds N] [--iters N] [--only I]"""
+
+--sparse: flash_attention_n_mla_sparse (B) at topk = 2048 entries per position, sampled without replacement from a context of 32768 that
+every position sees, same (B, H, Sq) and alternation A1 / B / A2:
+  A1 = flash_attention_n_mla on a dense cache that holds exactly those 2048 rows per (batch element, position), len = topk: the same bytes,
+       contiguous - the yardstick for "the gather costs nothing", judged within A1's own spread;
+  A2 = the torch route, fully captured: index-gather of the rows through the table, two matmuls, the sink column by hand.
+usage: python tools/bench_mla.py [--fp8 | --sparse] [--rounds N] [--iters N] [--only I]"""
 import argparse
 import sys
 
@@ -56,16 +62,72 @@ def time_graph(g, iters):
     return e0.elapsed_time(e1) * 1e3 / (iters * REPS)   # microseconds per call
 
 
+TOPK, CONTEXT = 2048, 32768
+
+
+def sparse_main(args):
+    dev, dtype = torch.device("cuda:0"), torch.bfloat16
+    print(f"A1 = flash_attention_n_mla on the {TOPK} rows made contiguous, B = flash_attention_n_mla_sparse (topk {TOPK} of {CONTEXT}), A2 = torch gather + matmuls")
+    print(f"{'shape (B,H,Sq)':16s} {'A1 us':>22s} {'B us':>22s} {'A2 us':>26s} {'A1/B':>6s} {'A2/B':>6s} {'A1 spread':>9s} {'max|A2-B|':>9s} {'max|A1-B|':>9s}")
+    for idx, (B, H, Sq, _) in enumerate(SHAPES):
+        if args.only is not None and idx != args.only:
+            continue
+        torch.manual_seed(0)
+        max_pages = CONTEXT // PAGE
+        q = torch.randn(B, H, Sq, E, device=dev, dtype=dtype) * 0.5
+        pool = torch.randn(B * max_pages, PAGE, 1, E, device=dev, dtype=dtype) * 0.5
+        table = torch.randperm(B * max_pages, device=dev).to(torch.int32).view(B, max_pages)
+        sl = torch.full((B,), CONTEXT, dtype=torch.int32, device=dev)
+        # without replacement, from the positions every query position sees (j <= len - Sq)
+        ind = torch.stack([torch.randperm(CONTEXT - Sq + 1, device=dev)[:TOPK] for _ in range(B * Sq)]).view(B, Sq, TOPK).to(torch.int32)
+        phys = (table.long().gather(1, (ind.long() // PAGE).view(B, -1)) * PAGE + (ind.long() % PAGE).view(B, -1)).view(B, Sq, TOPK)
+        flat = pool.view(-1, E)
+        compact = flat[phys.view(B * Sq, TOPK)].view(B * Sq, TOPK, 1, E).contiguous()    # A1's cache: the same rows, contiguous
+        q1 = q.transpose(1, 2).reshape(B * Sq, H, 1, E)
+        sl1 = torch.full((B * Sq,), TOPK, dtype=torch.int32, device=dev)
+
+        def run_a1():
+            return fa.flash_attention_n_mla(q1, compact, sl1, SCALE).view(B, Sq, H, EV).transpose(1, 2)
+
+        def run_a2():
+            rows = flat[phys]                                                             # [B, Sq, topk, 576]: the gather
+            x = torch.matmul(q.transpose(1, 2), rows.transpose(2, 3)).float() * SCALE      # [B, Sq, H, topk]
+            x = torch.cat([torch.zeros(B, Sq, H, 1, device=dev), x], -1)                   # the sink column: logit 0, weight n = 1
+            p = torch.softmax(x, -1)[..., 1:].to(dtype)
+            return torch.matmul(p, rows[..., :EV]).transpose(1, 2)
+
+        def run_b():
+            return fa.flash_attention_n_mla_sparse(q, pool, ind, sl, SCALE, block_table=table)
+
+        with torch.no_grad():
+            (g1, o1), (gb, ob), (g2, o2) = graph_of(run_a1), graph_of(run_b), graph_of(run_a2)
+            t1, tb, t2 = [], [], []
+            for _ in range(args.rounds):
+                t1.append(time_graph(g1, args.iters))
+                tb.append(time_graph(gb, args.iters))
+                t2.append(time_graph(g2, args.iters))
+            d2, d1 = (o2.float() - ob.float()).abs().max().item(), (o1.float() - ob.float()).abs().max().item()
+        med = lambda ts: sorted(ts)[len(ts) // 2]   # noqa: E731
+        fmt = lambda ts: "/".join(f"{t:.1f}" for t in ts)   # noqa: E731
+        print(f"{str((B, H, Sq)):16s} {fmt(t1):>22s} {fmt(tb):>22s} {fmt(t2):>26s} {med(t1) / med(tb):6.2f} {med(t2) / med(tb):6.2f} "
+              f"{max(t1) / min(t1):9.3f} {d2:9.2e} {d1:9.2e}", flush=True)
+        del g1, gb, g2, pool, compact
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--only", type=int, default=None)
     ap.add_argument("--fp8", action="store_true")
+    ap.add_argument("--sparse", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_mla needs a GPU"
     dev, dtype = torch.device("cuda:0"), torch.bfloat16
     print(f"device: {torch.cuda.get_device_name(0)}; {REPS} calls per graph, {args.iters} replays per timing, {args.rounds} alternations A/B; bf16, page {PAGE}, n = 1")
+    if args.sparse:
+        return sparse_main(args)
     if args.fp8:
         print("A = flash_attention_n_mla (bf16 cache), B = flash_attention_n_mla_fp8 (e4m3fn cache, kv_scale = 1)")
     print(f"{'shape (B,H,Sq,len)':24s} {'A us':>26s} {'B us':>26s} {'A/B':>6s} {'A spread':>9s} {'max|A-B|':>9s} "
