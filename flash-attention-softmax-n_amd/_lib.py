@@ -55,6 +55,7 @@ EXPORTS = (
     "fasn_mla_workspace_bytes", "fasn_fwd_mla", "fasn_mla_append", "fasn_mla_plan",
     "fasn_mla_fp8_workspace_bytes", "fasn_fwd_mla_fp8", "fasn_mla_fp8_append", "fasn_mla_fp8_plan",
     "fasn_mla_sparse_workspace_bytes", "fasn_fwd_mla_sparse", "fasn_mla_sparse_plan",
+    "fasn_mla_sparse_fp8_workspace_bytes", "fasn_fwd_mla_sparse_fp8", "fasn_mla_sparse_fp8_append", "fasn_mla_sparse_fp8_plan",
 )
 
 
@@ -334,6 +335,11 @@ def _mla_bindings():
     yield "fasn_mla_sparse_workspace_bytes", c_size_t, head
     yield "fasn_fwd_mla_sparse", c_int32, head + [c_void_p, c_size_t, c_void_p]
     yield "fasn_mla_sparse_plan", c_int32, head + [c_char_p, c_size_t]
+    # ... and the four over 656-byte FP8 rows behind an index list (the rows carry their scales: no operand beside the list)
+    yield "fasn_mla_sparse_fp8_workspace_bytes", c_size_t, head
+    yield "fasn_fwd_mla_sparse_fp8", c_int32, head + [c_void_p, c_size_t, c_void_p]
+    yield "fasn_mla_sparse_fp8_append", c_int32, [POINTER(MlaArgs), POINTER(View4), c_void_p]
+    yield "fasn_mla_sparse_fp8_plan", c_int32, head + [c_char_p, c_size_t]
 
 
 def kv_call(args, fp8=None, tree=None, window=None, alibi=None):
@@ -617,6 +623,12 @@ def mla_sparse_plan(args, sparse):
     """The two launches of fasn_fwd_mla_sparse for `args` (an MlaArgs) and `sparse` (an MlaSparse) - the gathering forward on
     B * Sq * ceil(H / 64) * nsplit workgroups, the dense call's combine - as launch_plan returns them. Nothing is launched."""
     return _plan("fasn_mla_sparse_plan", args, sparse)
+
+
+def mla_sparse_fp8_plan(args, sparse):
+    """The two launches of fasn_fwd_mla_sparse_fp8 for `args` (an MlaArgs over 656-byte FP8 rows) and `sparse` (an MlaSparse):
+    mla_sparse_plan's grid with the FP8 forward's name and its 157696 bytes of LDS, the dense call's combine. Nothing is launched."""
+    return _plan("fasn_mla_sparse_fp8_plan", args, sparse)
 
 
 def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):

@@ -1,7 +1,7 @@
 """MLA decode: attention over a compressed latent K/V cache (multi-head latent attention in its absorbed form: DeepSeek-V2 / V3 / R1,
-Kimi K2). Host side of fasn_fwd_mla / fasn_mla_append, of fasn_fwd_mla_fp8 / fasn_mla_fp8_append and of fasn_fwd_mla_sparse in
-include/fasn.h: one call path, with the scale of an FP8 latent cache and the top-k index list of the sparse decode (DeepSeek-V3.2) as
-optional operands.
+Kimi K2). Host side of fasn_fwd_mla / fasn_mla_append, of fasn_fwd_mla_fp8 / fasn_mla_fp8_append, of fasn_fwd_mla_sparse and of
+fasn_fwd_mla_sparse_fp8 / fasn_mla_sparse_fp8_append in include/fasn.h: one call path, with the scale of an FP8 latent cache, the top-k
+index list of the sparse decode (DeepSeek-V3.2) and the 656-byte FP8 row behind such a list as optional operands.
 
 The cache holds ONE row of 576 features per token, shared by every query head: a 512-wide latent and a 64-wide rotated key part. The logit
 of head h is q_h[0:576] . row[0:576] and the value is the latent itself, out_h = sum_j p_hj row_j[0:512] - so K and V are one tensor, read
@@ -19,14 +19,18 @@ from .flash_attn import _n_strides, _n_tensor, _stream_ptr, _view4
 from .kvcache import _KV_DTYPES, _check_cache, _on_device, _rows, _scale_tensor
 
 MLA_HEAD_DIM, MLA_VALUE_DIM, MLA_MAX_ROWS = 576, 512, 256
+MLA_FP8_ROW_BYTES, MLA_FP8_GROUP = 656, 128   # the FP8 row behind an index list: 512 codes, 4 fp32 scales (one per 128 features), 64 x 16-bit rope
+_FP8_E_MIN, _FP8_E_MAX = -30, 120             # the exponents a group's scale 2^e takes (csrc/fasn_mla_sparse_fp8.h)
 _LOG2E = 1.4426950408889634
 _F16_MAX_PRESCALE = 8.0   # float16: |scale * log2e| beyond this is FASN_EUNSUPPORTED (mla_build, csrc/fasn_mla.hip)
 _SERVED = (f"served: a latent cache of head dims exactly {MLA_VALUE_DIM} + 64 = {MLA_HEAD_DIM} in fp16 / bf16 (flash_attention_n_mla) or in "
            f"e4m3fn codes with kv_scale (flash_attention_n_mla_fp8), H * Sq <= {MLA_MAX_ROWS}, causal or not, softmax_n; behind a top-k list "
-           "of logical positions (flash_attention_n_mla_sparse): the fp16 / bf16 cache, int32 indices [B, Sq, topk] on the device with "
-           "topk a multiple of 64; not served: e5m2 and the fnuz codes, a window, ALiBi, trees, packed queries, shared prefixes, an FP8 "
-           f"cache behind indices, physical (pool) indices, more than {MLA_MAX_ROWS} rows, gradients")
+           "of logical positions: the fp16 / bf16 cache (flash_attention_n_mla_sparse) or 656-byte FP8 rows - 512 e4m3fn codes, four "
+           "fp32 scales, 64 16-bit rotated features - as uint8 / float8_e4m3fn bytes (flash_attention_n_mla_sparse_fp8), int32 indices "
+           "[B, Sq, topk] on the device with topk a multiple of 64; not served: e5m2 and the fnuz codes, a window, ALiBi, trees, packed "
+           f"queries, shared prefixes, the 656-byte rows without indices, physical (pool) indices, more than {MLA_MAX_ROWS} rows, gradients")
 _FP8_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2, torch.float8_e4m3fnuz, torch.float8_e5m2fnuz)
+_BYTE_DTYPES = (torch.uint8, torch.float8_e4m3fn)   # what a cache of 656-byte rows may be declared as: both mean bytes
 
 
 def flash_attention_n_mla(
@@ -121,28 +125,108 @@ def flash_attention_n_mla_sparse(
                 return_lse, indices=indices, sparse=True)
 
 
+def flash_attention_n_mla_sparse_fp8(
+        query: Tensor,
+        kv_cache: Tensor,
+        indices: Tensor,
+        cache_seqlens: Tensor,
+        scale: float,
+        block_table: Optional[Tensor] = None,
+        kv_new: Optional[Tensor] = None,
+        softmax_n_param=1,
+        is_causal: bool = True,
+        return_lse: bool = False):
+    """flash_attention_n_mla_sparse over the FP8 latent cache the top-k models are served from. Everything flash_attention_n_mla_sparse
+    says of `query` (H * Sq <= 256), `indices` (logical positions, topk % 64 == 0, no address formed from an entry that is no key, a
+    duplicate counts twice), `cache_seqlens`, `block_table`, `scale` (float16: |scale| * log2(e) <= 8), softmax_n, causality, lse and the
+    512-wide output holds here; what differs:
+
+    :param kv_cache: torch.uint8 or torch.float8_e4m3fn (both mean bytes), paged [num_pages, page_size, 1, 656] with `block_table`
+                  (page_size a multiple of 64), dense [B, capacity, 1, 656], or 3-D without the head axis; last stride 1, row and page
+                  strides multiples of 16 bytes, base 16-byte aligned; never copied. A row is 512 OCP e4m3fn codes of the latent, four
+                  fp32 scales (scale g for features 128 g .. 128 g + 127) and the 64 rotated features as 16-bit numbers IN QUERY'S DTYPE,
+                  not quantised (mla_fp8_rows_pack writes it, mla_fp8_rows_unpack reads it). Latent feature f of a row is
+                  (float32(code[f]) * scale[f // 128]) rounded once to query's dtype - dequantise to 16 bits, then attend - so the call
+                  gives, bit for bit, flash_attention_n_mla_sparse on mla_fp8_rows_unpack(kv_cache, query.dtype). There is no kv_scale
+                  operand and no factor on scores or output. Scales that are not finite and positive give unspecified values.
+    :param kv_new: optional [B, Sq, 1, 576] in query's dtype: quantised by the rule of mla_fp8_rows_pack, byte for byte, into the rows
+                  cache_seqlens[b] .. + Sq - 1 (positions at or beyond the capacity are dropped in the kernel), then nameable.
+    :return: [B, H, Sq, 512] in query's dtype (and lse). Rows without a key give exactly 0 and lse = log n.
+    """
+    return _mla("flash_attention_n_mla_sparse_fp8", query, kv_cache, cache_seqlens, scale, None, block_table, kv_new, softmax_n_param,
+                is_causal, return_lse, indices=indices, sparse=True, rows8=True)
+
+
+def _fp8_group_exponent(amax: Tensor) -> Tensor:
+    """int32 e per group from its fp32 amax >= 0: the smallest e with amax <= 448 * 2^e = 1.75 * 2^(e + 8), clamped to [-30, 120], read
+    from the exponent and mantissa bits as the append kernel reads it (amax = m * 2^E, 1 <= m < 2: e = E - 8, one more where m > 1.75;
+    zero and fp32's subnormals fall to the lower clamp)"""
+    bits = amax.contiguous().view(torch.int32)
+    e = (bits >> 23) - 127 - 8 + ((bits & 0x7FFFFF) > 0x600000).to(torch.int32)
+    return e.clamp(_FP8_E_MIN, _FP8_E_MAX)
+
+
+def mla_fp8_rows_pack(kv16: Tensor) -> Tensor:
+    """[..., 576] fp16 / bf16 latent rows -> uint8 [..., 656] rows of flash_attention_n_mla_sparse_fp8's cache (plain torch, any device),
+    by the rule its kv_new append follows byte for byte. Per row and group g of 128 latent features: a = max |x| over the finite
+    elements in fp32, scale = 2^e with e the smallest integer such that a <= 448 * 2^e, clamped to [-30, 120] (a = 0: e = -30),
+    code = rne_e4m3(clamp(x / scale, -448, 448)) - the division is exact, +-Inf clamps, NaN gives the NaN code 0x7f. The 64 rotated features
+    are copied bit for bit: the row's rope part has kv16's dtype."""
+    if not isinstance(kv16, Tensor) or kv16.dtype not in _KV_DTYPES or kv16.shape[-1] != MLA_HEAD_DIM:
+        raise ValueError(f"mla_fp8_rows_pack: rows must be [..., {MLA_HEAD_DIM}] in fp16 / bf16")
+    lead = kv16.shape[:-1]
+    x = kv16[..., :MLA_VALUE_DIM].float().reshape(*lead, MLA_VALUE_DIM // MLA_FP8_GROUP, MLA_FP8_GROUP)
+    amax = torch.where(torch.isfinite(x), x.abs(), torch.zeros_like(x)).amax(-1)
+    s = ((_fp8_group_exponent(amax) + 127) << 23).view(torch.float32)
+    codes = (x / s[..., None]).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    codes = torch.where(torch.isnan(x), torch.full_like(codes, 0x7F), codes).reshape(*lead, MLA_VALUE_DIM)   # one NaN code, whatever the sign
+    rope = kv16[..., MLA_VALUE_DIM:].contiguous().view(torch.uint8).reshape(*lead, 2 * (MLA_HEAD_DIM - MLA_VALUE_DIM))
+    return torch.cat([codes, s.contiguous().view(torch.uint8).reshape(*lead, 16), rope], -1)
+
+
+def mla_fp8_rows_unpack(rows656: Tensor, dtype: torch.dtype) -> Tensor:
+    """uint8 / float8_e4m3fn [..., 656] rows -> [..., 576] in `dtype` (fp16 / bf16; plain torch, any device): the 16-bit rows
+    flash_attention_n_mla_sparse_fp8 attends to - latent feature f = (float32(code[f]) * scale[f // 128]).to(dtype), the rope part
+    reinterpreted as `dtype`."""
+    if not isinstance(rows656, Tensor) or rows656.dtype not in _BYTE_DTYPES or rows656.shape[-1] != MLA_FP8_ROW_BYTES or dtype not in _KV_DTYPES:
+        raise ValueError(f"mla_fp8_rows_unpack: rows must be uint8 / float8_e4m3fn [..., {MLA_FP8_ROW_BYTES}] and dtype fp16 / bf16")
+    raw = rows656.view(torch.uint8).contiguous()
+    lead = raw.shape[:-1]
+    codes = raw[..., :MLA_VALUE_DIM].contiguous().view(torch.float8_e4m3fn).float().reshape(*lead, MLA_VALUE_DIM // MLA_FP8_GROUP, MLA_FP8_GROUP)
+    s = raw[..., MLA_VALUE_DIM:MLA_VALUE_DIM + 16].contiguous().view(torch.float32)
+    rope = raw[..., MLA_VALUE_DIM + 16:].contiguous().view(dtype)
+    return torch.cat([(codes * s[..., None]).to(dtype).reshape(*lead, MLA_VALUE_DIM), rope], -1)
+
+
 def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_new, softmax_n_param, is_causal, return_lse, fp8=False,
-         indices=None, sparse=False):
-    """the one call path of the three functions; fp8: the cache holds e4m3fn codes and `kv_scale` is their scale; sparse: `indices` is the
-    top-k list of logical positions"""
+         indices=None, sparse=False, rows8=False):
+    """the one call path of the four functions; fp8: the cache holds e4m3fn codes and `kv_scale` is their scale; sparse: `indices` is the
+    top-k list of logical positions; rows8 (with sparse): the cache holds 656-byte FP8 rows, which carry their scales"""
+    row = MLA_FP8_ROW_BYTES if rows8 else MLA_HEAD_DIM   # elements of a cache row
     if not isinstance(query, Tensor) or query.dim() != 4 or not isinstance(kv_cache, Tensor) or kv_cache.dim() not in (3, 4):
-        raise ValueError(f"{fn}: query must be [B, H, Sq, {MLA_HEAD_DIM}] and kv_cache [num_pages, page_size, 1, {MLA_HEAD_DIM}] (paged) or "
-                         f"[B, capacity, 1, {MLA_HEAD_DIM}] (dense); {_SERVED}")
+        raise ValueError(f"{fn}: query must be [B, H, Sq, {MLA_HEAD_DIM}] and kv_cache [num_pages, page_size, 1, {row}] (paged) or "
+                         f"[B, capacity, 1, {row}] (dense); {_SERVED}")
     if kv_cache.dim() == 3:
         kv_cache = kv_cache.unsqueeze(2)
-    if not fp8 and kv_cache.dtype in _FP8_DTYPES:
+    if rows8 and kv_cache.dtype not in _BYTE_DTYPES:
+        raise TypeError(f"{fn}: the cache must hold {MLA_FP8_ROW_BYTES}-byte rows as torch.uint8 or torch.float8_e4m3fn; a {kv_cache.dtype} "
+                        f"cache behind indices is flash_attention_n_mla_sparse's; {_SERVED}")
+    if sparse and not rows8 and kv_cache.dtype in (torch.uint8,) + _FP8_DTYPES:
+        raise TypeError(f"{fn}: an FP8 latent cache ({kv_cache.dtype}) behind indices is flash_attention_n_mla_sparse_fp8's "
+                        f"({MLA_FP8_ROW_BYTES}-byte rows); {_SERVED}")
+    if not fp8 and not rows8 and kv_cache.dtype in _FP8_DTYPES:
         raise TypeError(f"{fn}: an FP8 latent cache ({kv_cache.dtype}) is flash_attention_n_mla_fp8's (e4m3fn codes with kv_scale); {_SERVED}")
     if fp8 and kv_cache.dtype != torch.float8_e4m3fn:
         if kv_cache.dtype in _FP8_DTYPES:
             raise TypeError(f"{fn}: the cache must hold torch.float8_e4m3fn codes; {kv_cache.dtype} has no kernel; {_SERVED}")
         raise TypeError(f"{fn}: the cache must hold torch.float8_e4m3fn codes; a {kv_cache.dtype} cache is flash_attention_n_mla's")
     B, H, Sq, D = query.shape
-    if D != MLA_HEAD_DIM or kv_cache.shape[3] != MLA_HEAD_DIM or kv_cache.shape[2] != 1:
+    if D != MLA_HEAD_DIM or kv_cache.shape[3] != row or kv_cache.shape[2] != 1:
         raise ValueError(f"{fn}: query is {tuple(query.shape)} and kv_cache {tuple(kv_cache.shape)}: not a latent cache; {_SERVED}. "
                          "Separate K and V of one head dim are flash_attention_n_kvcache's")
     if query.dtype not in _KV_DTYPES:
         raise ValueError(f"{fn}: dtype {query.dtype} is not supported; {_SERVED}")
-    if not fp8 and kv_cache.dtype != query.dtype:
+    if not fp8 and not rows8 and kv_cache.dtype != query.dtype:
         raise TypeError(f"{fn}: query and kv_cache must share one dtype; got {query.dtype} and {kv_cache.dtype}")
     if H * Sq > MLA_MAX_ROWS:
         raise ValueError(f"{fn}: H * Sq = {H} x {Sq} = {H * Sq} rows exceed {MLA_MAX_ROWS}; {_SERVED}")
@@ -180,8 +264,8 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
         if page_size % 64 != 0:
             raise ValueError(f"page_size {page_size} is not supported: a paged cache needs page_size % 64 == 0 (a 64-key tile never straddles a page)")
     elif kv_cache.shape[0] != B:
-        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, 1, {MLA_HEAD_DIM}] with B = {B}; got {tuple(kv_cache.shape)}")
-    _check_cache("kv_cache", kv_cache, paged, MLA_HEAD_DIM)
+        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, 1, {row}] with B = {B}; got {tuple(kv_cache.shape)}")
+    _check_cache("kv_cache", kv_cache, paged, row)
     if kv_new is not None:
         if kv_new.dtype != query.dtype or tuple(kv_new.shape) != (B, Sq, 1, MLA_HEAD_DIM):
             raise ValueError(f"kv_new must be [B, Sq, 1, {MLA_HEAD_DIM}] = [{B}, {Sq}, 1, {MLA_HEAD_DIM}] in {query.dtype}; got {tuple(kv_new.shape)} {kv_new.dtype}")
@@ -207,7 +291,7 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
     a.lse = None if lse is None else lse.data_ptr()
     a.kv_cache = kv_cache.data_ptr()
     a.kv_stride[0] = kv_cache.stride(0) if kv_cache.size(0) > 1 else 0
-    a.kv_stride[1] = kv_cache.stride(1) if kv_cache.size(1) > 1 else MLA_HEAD_DIM
+    a.kv_stride[1] = kv_cache.stride(1) if kv_cache.size(1) > 1 else row
     if paged:
         a.block_table, a.block_table_stride, a.max_pages = block_table.data_ptr(), block_table.stride(0) if B > 1 else block_table.shape[1], block_table.shape[1]
     else:
@@ -223,7 +307,7 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
         a.n_stride_b, a.n_stride_h = _n_strides(nt)
     lib = _lib.load()
     # the entry points and the operands behind the block: the four of the 16-bit cache, their _fp8 siblings with the scale, or the
-    # _sparse ones with the index list (whose append is the 16-bit cache's)
+    # _sparse ones with the index list (whose append is the 16-bit cache's), or the _sparse_fp8 ones with the list and an append of their own
     ops, suffix, app = (), "", ()
     if fp8:
         f8 = MlaFp8()
@@ -234,8 +318,8 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
         sp = MlaSparse()
         sp.indices, sp.topk, sp.reserved = indices.data_ptr(), indices.shape[2], 0
         sp.stride_b, sp.stride_q = indices.stride(0) if B > 1 else 0, indices.stride(1) if Sq > 1 else 0
-        ops, suffix = (sp,), "_sparse"
-    app_name = "fasn_mla_fp8_append" if fp8 else "fasn_mla_append"
+        ops, suffix = (sp,), "_sparse_fp8" if rows8 else "_sparse"
+    app_name = "fasn_mla_sparse_fp8_append" if rows8 else "fasn_mla_fp8_append" if fp8 else "fasn_mla_append"
 
     def launch():
         stream = _stream_ptr(dev)

@@ -965,7 +965,7 @@ int fasn_mla_fp8_plan(const fasn_mla_args* args, const fasn_mla_fp8* fp8, char* 
  * is a batch element, a position, a block of 64 heads and a split of the topk / 64 index tiles; 144 KiB of LDS) and the combine of
  * fasn_fwd_mla. fasn_mla_sparse_workspace_bytes(args, sparse) = B * nsplit * H * Sq * 514 * 4 bytes, 16-byte aligned, with this call's
  * nsplit (a function of B, H, Sq and topk). The append is fasn_mla_append with the same block; the caller then passes seqlen_add = Sq.
- * Not here: an FP8 cache behind indices, physical (pool) indices, H * Sq > 256, gradients.
+ * Not here: physical (pool) indices, H * Sq > 256, gradients. An FP8 cache behind indices has entry points of its own (below).
  */
 typedef struct fasn_mla_sparse {
     const int32_t* indices; /* DEVICE */
@@ -977,6 +977,33 @@ typedef struct fasn_mla_sparse {
 size_t fasn_mla_sparse_workspace_bytes(const fasn_mla_args* args, const fasn_mla_sparse* sparse);
 int fasn_fwd_mla_sparse(const fasn_mla_args* args, const fasn_mla_sparse* sparse, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
 int fasn_mla_sparse_plan(const fasn_mla_args* args, const fasn_mla_sparse* sparse, char* buf, size_t cap);
+
+/*
+ * SPARSE MLA DECODE OVER THE FP8 LATENT CACHE, 656-BYTE ROWS (additions within ABI 6; no struct or function above is changed): the sparse
+ * decode above over the cache the top-k models are served from. One cache row is 656 bytes, little-endian:
+ *     [0, 512)     OCP e4m3fn codes of latent features 0 .. 511
+ *     [512, 528)   four fp32 scales; scale g belongs to features 128 g .. 128 g + 127
+ *     [528, 656)   the 64 rotated key features as 16-bit numbers in the dtype of q, not quantised
+ * and the value of latent feature f is rn_T(float(up(code[f])) * scale[f / 128]): one fp32 multiply, one rounding (to nearest even) to
+ * the dtype T of q. On the 576-feature row [latent | rope] so defined, the semantics are fasn_fwd_mla_sparse's word for word: the
+ * visibility rule, entries that are no key form no address, a duplicate counts twice, rows without a key give exactly 0 and lse = log n.
+ * There is no factor on the scores or on the output and no scale operand. Scales that are not finite and positive give unspecified values.
+ *
+ * The block is fasn_mla_args with kv_cache pointing at the bytes, kv_stride counting bytes (both multiples of 16, kv_stride[1] >= 656),
+ * D = 576, Dv = 512 and dtype that of q, o and kv_new; the list is fasn_mla_sparse. Every check of fasn_fwd_mla_sparse runs, with its
+ * codes and order, the cache's rules read in bytes. Two launches: fasn_mla_sparse_fp8_fwd_kernel on the grid and with the nsplit of
+ * fasn_fwd_mla_sparse for the same shapes (157696 bytes of LDS: two staged 64 x 656-byte tiles and one 16-bit image) and the combine of
+ * fasn_fwd_mla; the workspace is fasn_mla_sparse_workspace_bytes' for the same shapes. fasn_mla_sparse_fp8_append quantises the rows of
+ * kv_new (16-bit, [B, Sq, 1, 576]) into rows seqlens[b] .. seqlens[b] + Sq - 1, positions at or beyond the capacity dropped in the
+ * kernel: per group of 128 latent features a = max |x| over the finite elements, scale = 2^e with e the smallest integer such that
+ * a <= 448 * 2^e, clamped to [-30, 120] (a = 0: e = -30), code = rne_e4m3(clamp(x / scale, -448, 448)) - +-Inf clamps, NaN gives the NaN
+ * code 0x7f -, the rotated part copied bit for bit. Not here: a dense (non-sparse) call over this row, e5m2, physical (pool) indices,
+ * H * Sq > 256, gradients.
+ */
+size_t fasn_mla_sparse_fp8_workspace_bytes(const fasn_mla_args* args, const fasn_mla_sparse* sparse);
+int fasn_fwd_mla_sparse_fp8(const fasn_mla_args* args, const fasn_mla_sparse* sparse, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_mla_sparse_fp8_append(const fasn_mla_args* args, const fasn_view4* kv_new, fasn_stream_t stream);
+int fasn_mla_sparse_fp8_plan(const fasn_mla_args* args, const fasn_mla_sparse* sparse, char* buf, size_t cap);
 
 /*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,

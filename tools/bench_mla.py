@@ -20,7 +20,12 @@ every position sees, same (B, H, Sq) and alternation A1 / B / A2:
   A1 = flash_attention_n_mla on a dense cache that holds exactly those 2048 rows per (batch element, position), len = topk: the same bytes,
        contiguous - the yardstick for "the gather costs nothing", judged within A1's own spread;
   A2 = the torch route, fully captured: index-gather of the rows through the table, two matmuls, the sink column by hand.
-usage: python tools/bench_mla.py [--fp8 | --sparse] [--rounds N] [--iters N] [--only I]"""
+
+--sparse-fp8: flash_attention_n_mla_sparse_fp8 (B) over 656-byte FP8 rows, the lists and shapes of --sparse, alternation A / B / A2:
+  A  = flash_attention_n_mla_sparse on the bf16 pool mla_fp8_rows_unpack gives: the same numbers (max |A - B| must be 0), the yardstick;
+  A2 = the route B replaces, fully captured: torch gather of the 656-byte rows, mla_fp8_rows_unpack, flash_attention_n_mla on the compacted rows.
+Then the calls with kv_new, A + fasn_mla_append and B + fasn_mla_sparse_fp8_append, and graphs that launch the two append entry points alone.
+usage: python tools/bench_mla.py [--fp8 | --sparse | --sparse-fp8] [--rounds N] [--iters N] [--only I]"""
 import argparse
 import sys
 
@@ -115,6 +120,82 @@ def sparse_main(args):
         torch.cuda.empty_cache()
 
 
+def append_graph(name, q, pool, table, sl, kv_new):
+    """a captured graph that launches nothing but the append entry point `name` on the call's block (pool: 16-bit or 656-byte rows)"""
+    from flash_attention_softmax_n_amd import _lib
+    from flash_attention_softmax_n_amd.flash_attn import _stream_ptr, _view4
+    (B, H, Sq, _), lib = q.shape, _lib.load()
+    out = torch.empty(B, H, Sq, EV, device=q.device, dtype=q.dtype)
+    a = _lib.MlaArgs()
+    a.q, a.o, a.kv_cache, a.seqlens = _view4(q), _view4(out), pool.data_ptr(), sl.data_ptr()
+    a.kv_stride[0], a.kv_stride[1] = pool.stride(0), pool.stride(1)
+    a.block_table, a.block_table_stride, a.max_pages, a.page_size = table.data_ptr(), table.stride(0), table.shape[1], PAGE
+    a.B, a.H, a.Sq, a.D, a.Dv, a.dtype = B, H, Sq, E, EV, _lib.FASN_DTYPE_BF16
+    a.scale, a.softmax_n, a.causal = SCALE, 1.0, 1
+    view = _view4(kv_new)
+    return graph_of(lambda: _lib.check(getattr(lib, name)(a, view, _stream_ptr(q.device)), name))[0], (a, out, view)
+
+
+def sparse_fp8_main(args):
+    dev, dtype = torch.device("cuda:0"), torch.bfloat16
+    print(f"A = flash_attention_n_mla_sparse on the unpacked bf16 pool, B = flash_attention_n_mla_sparse_fp8 (topk {TOPK} of {CONTEXT}), "
+          "A2 = torch gather + unpack + flash_attention_n_mla; +new: the same call with kv_new")
+    print(f"{'shape (B,H,Sq)':16s} {'A us':>22s} {'B us':>22s} {'A2 us':>26s} {'B/A':>6s} {'B/A2':>6s} {'A spread':>9s} {'max|A-B|':>9s} {'max|A2-B|':>9s} "
+          f"{'A+new us':>9s} {'B+new us':>9s} {'append16':>9s} {'append8':>9s}")
+    for idx, (B, H, Sq, _) in enumerate(SHAPES):
+        if args.only is not None and idx != args.only:
+            continue
+        torch.manual_seed(0)
+        max_pages = CONTEXT // PAGE
+        q = torch.randn(B, H, Sq, E, device=dev, dtype=dtype) * 0.5
+        pool8 = torch.cat([fa.mla_fp8_rows_pack(torch.randn(max_pages, PAGE, 1, E, device=dev, dtype=dtype) * 0.5) for _ in range(B)])
+        pool = torch.cat([fa.mla_fp8_rows_unpack(pool8[b * max_pages:(b + 1) * max_pages], dtype) for b in range(B)])
+        table = torch.randperm(B * max_pages, device=dev).to(torch.int32).view(B, max_pages)
+        sl = torch.full((B,), CONTEXT, dtype=torch.int32, device=dev)
+        sl_new = sl - Sq   # with kv_new the same context, its last Sq rows rewritten every call
+        kv_new = torch.randn(B, Sq, 1, E, device=dev, dtype=dtype) * 0.5
+        ind = torch.stack([torch.randperm(CONTEXT - Sq + 1, device=dev)[:TOPK] for _ in range(B * Sq)]).view(B, Sq, TOPK).to(torch.int32)
+        phys = (table.long().gather(1, (ind.long() // PAGE).view(B, -1)) * PAGE + (ind.long() % PAGE).view(B, -1)).view(B * Sq, TOPK)
+        flat8 = pool8.view(-1, 656)
+        q1 = q.transpose(1, 2).reshape(B * Sq, H, 1, E)
+        sl1 = torch.full((B * Sq,), TOPK, dtype=torch.int32, device=dev)
+
+        def run_a(**kw):
+            return fa.flash_attention_n_mla_sparse(q, pool, ind, sl_new if kw else sl, SCALE, block_table=table, **kw)
+
+        def run_b(**kw):
+            return fa.flash_attention_n_mla_sparse_fp8(q, pool8, ind, sl_new if kw else sl, SCALE, block_table=table, **kw)
+
+        def run_a2():
+            rows = fa.mla_fp8_rows_unpack(flat8[phys], dtype).view(B * Sq, TOPK, 1, E)
+            return fa.flash_attention_n_mla(q1, rows, sl1, SCALE).view(B, Sq, H, EV).transpose(1, 2)
+
+        with torch.no_grad():
+            (ga, oa), (gb, ob), (g2, o2) = graph_of(run_a), graph_of(run_b), graph_of(run_a2)
+            ta, tb, t2 = [], [], []
+            for _ in range(args.rounds):
+                ta.append(time_graph(ga, args.iters))
+                tb.append(time_graph(gb, args.iters))
+                t2.append(time_graph(g2, args.iters))
+            da, d2 = (oa.float() - ob.float()).abs().max().item(), (o2.float() - ob.float()).abs().max().item()
+            del ga, gb, g2
+            gan, gbn = graph_of(lambda: run_a(kv_new=kv_new))[0], graph_of(lambda: run_b(kv_new=kv_new))[0]
+            (g16, keep16), (g8, keep8) = (append_graph("fasn_mla_append", q, pool, table, sl_new, kv_new),
+                                          append_graph("fasn_mla_sparse_fp8_append", q, pool8, table, sl_new, kv_new))   # the appends alone
+            tan, tbn, t16, t8 = [], [], [], []
+            for _ in range(args.rounds):
+                tan.append(time_graph(gan, args.iters))
+                tbn.append(time_graph(gbn, args.iters))
+                t16.append(time_graph(g16, args.iters))
+                t8.append(time_graph(g8, args.iters))
+        med = lambda ts: sorted(ts)[len(ts) // 2]   # noqa: E731
+        fmt = lambda ts: "/".join(f"{t:.1f}" for t in ts)   # noqa: E731
+        print(f"{str((B, H, Sq)):16s} {fmt(ta):>22s} {fmt(tb):>22s} {fmt(t2):>26s} {med(tb) / med(ta):6.2f} {med(tb) / med(t2):6.2f} "
+              f"{max(ta) / min(ta):9.3f} {da:9.2e} {d2:9.2e} {med(tan):9.1f} {med(tbn):9.1f} {med(t16):9.2f} {med(t8):9.2f}", flush=True)
+        del gan, gbn, g16, g8, pool, pool8, flat8
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=3)
@@ -122,12 +203,15 @@ def main():
     ap.add_argument("--only", type=int, default=None)
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--sparse", action="store_true")
+    ap.add_argument("--sparse-fp8", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_mla needs a GPU"
     dev, dtype = torch.device("cuda:0"), torch.bfloat16
     print(f"device: {torch.cuda.get_device_name(0)}; {REPS} calls per graph, {args.iters} replays per timing, {args.rounds} alternations A/B; bf16, page {PAGE}, n = 1")
     if args.sparse:
         return sparse_main(args)
+    if args.sparse_fp8:
+        return sparse_fp8_main(args)
     if args.fp8:
         print("A = flash_attention_n_mla (bf16 cache), B = flash_attention_n_mla_fp8 (e4m3fn cache, kv_scale = 1)")
     print(f"{'shape (B,H,Sq,len)':24s} {'A us':>26s} {'B us':>26s} {'A/B':>6s} {'A spread':>9s} {'max|A-B|':>9s} "
