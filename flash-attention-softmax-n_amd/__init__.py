@@ -27,6 +27,7 @@ Public surface = flash_attention_softmax_n/__init__.py:3-9 of the reference:
     flash_attention_n_mla_fp8  (the same decode over a latent cache of e4m3fn codes with one scale per batch element: 576 bytes per token)
     flash_attention_n_mla_sparse  (the same decode over the rows a top-k list of logical positions names, [B, Sq, topk] int32: DeepSeek-V3.2's sparse attention)
     flash_attention_n_mla_sparse_fp8  (the sparse decode over the FP8 latent cache of 656-byte rows - 512 e4m3fn codes, four fp32 scales, 16-bit rope; mla_fp8_rows_pack / mla_fp8_rows_unpack write and read that row)
+    flash_attention_n_mla_index  (the lightning indexer in front of the sparse decode: ReLU-weighted logits of 32 / 64 index heads over a paged cache of 128-feature index keys, the top-k positions per query as the int32 list the sparse calls take)
     surgery.apply_attention_softmax_n / surgery.policy_registry  (flash_attention_softmax_n/surgery, composer-free)
 Every function runs on device tensors through libfasn.so; importing the package without the built
 library raises ImportError (no silent fallback).
@@ -40,7 +41,7 @@ from .kvcache import (flash_attention_n_kvcache, flash_attention_n_kvcache_fp8, 
                       flash_attention_n_kvcache_tree_commit, flash_attention_n_kvcache_varlen,
                       flash_attention_n_kvcache_varlen_rope, flash_attention_n_kvcache_varlen_window, flash_attention_n_kvcache_window)
 from .mla import (flash_attention_n_mla, flash_attention_n_mla_fp8, flash_attention_n_mla_sparse, flash_attention_n_mla_sparse_fp8,
-                  mla_fp8_rows_pack, mla_fp8_rows_unpack)
+                  flash_attention_n_mla_index, mla_fp8_rows_pack, mla_fp8_rows_unpack)
 from .softmax import softmax_n
 
 _lib.load()  # fail loudly at import if the HIP extension is missing
@@ -48,4 +49,4 @@ _lib.load()  # fail loudly at import if the HIP extension is missing
 TRITON_INSTALLED = False  # kept for source compatibility: the Triton path is replaced by the HIP kernel
 HIP_NATIVE = True
 
-__all__ = ["flash_attention_n", "flash_attention_n_varlen", "flash_attention_n_varlen_rope", "flash_attention_n_kvcache", "flash_attention_n_kvcache_prefill", "flash_attention_n_kvcache_window", "flash_attention_n_kvcache_rope", "flash_attention_n_kvcache_varlen", "flash_attention_n_kvcache_varlen_window", "flash_attention_n_kvcache_varlen_rope", "flash_attention_n_kvcache_tree", "flash_attention_n_kvcache_tree_commit", "flash_attention_n_kvcache_fp8", "flash_attention_n_kvcache_fp8_window", "flash_attention_n_kvcache_fp8_rope", "flash_attention_n_kvcache_fp8_tree", "flash_attention_n_kvcache_fp8_tree_commit", "flash_attention_n_kvcache_fp8_varlen", "flash_attention_n_kvcache_fp8_varlen_window", "flash_attention_n_kvcache_fp8_varlen_rope", "flash_attention_n_kvcache_shared_prefix", "flash_attention_n_kvcache_prefix_groups", "flash_attention_n_mla", "flash_attention_n_mla_fp8", "flash_attention_n_mla_sparse", "flash_attention_n_mla_sparse_fp8", "mla_fp8_rows_pack", "mla_fp8_rows_unpack", "flash_attention_n_triton", "slow_attention_n", "softmax_n", "TRITON_INSTALLED", "HIP_NATIVE"]
+__all__ = ["flash_attention_n", "flash_attention_n_varlen", "flash_attention_n_varlen_rope", "flash_attention_n_kvcache", "flash_attention_n_kvcache_prefill", "flash_attention_n_kvcache_window", "flash_attention_n_kvcache_rope", "flash_attention_n_kvcache_varlen", "flash_attention_n_kvcache_varlen_window", "flash_attention_n_kvcache_varlen_rope", "flash_attention_n_kvcache_tree", "flash_attention_n_kvcache_tree_commit", "flash_attention_n_kvcache_fp8", "flash_attention_n_kvcache_fp8_window", "flash_attention_n_kvcache_fp8_rope", "flash_attention_n_kvcache_fp8_tree", "flash_attention_n_kvcache_fp8_tree_commit", "flash_attention_n_kvcache_fp8_varlen", "flash_attention_n_kvcache_fp8_varlen_window", "flash_attention_n_kvcache_fp8_varlen_rope", "flash_attention_n_kvcache_shared_prefix", "flash_attention_n_kvcache_prefix_groups", "flash_attention_n_mla", "flash_attention_n_mla_fp8", "flash_attention_n_mla_sparse", "flash_attention_n_mla_sparse_fp8", "flash_attention_n_mla_index", "mla_fp8_rows_pack", "mla_fp8_rows_unpack", "flash_attention_n_triton", "slow_attention_n", "softmax_n", "TRITON_INSTALLED", "HIP_NATIVE"]

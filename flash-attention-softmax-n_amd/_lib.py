@@ -56,6 +56,7 @@ EXPORTS = (
     "fasn_mla_fp8_workspace_bytes", "fasn_fwd_mla_fp8", "fasn_mla_fp8_append", "fasn_mla_fp8_plan",
     "fasn_mla_sparse_workspace_bytes", "fasn_fwd_mla_sparse", "fasn_mla_sparse_plan",
     "fasn_mla_sparse_fp8_workspace_bytes", "fasn_fwd_mla_sparse_fp8", "fasn_mla_sparse_fp8_append", "fasn_mla_sparse_fp8_plan",
+    "fasn_mla_index_workspace_bytes", "fasn_mla_index", "fasn_mla_index_append", "fasn_mla_index_plan",
 )
 
 
@@ -216,6 +217,22 @@ class MlaSparse(Structure):
     _fields_ = [("indices", c_void_p), ("stride_b", c_int64), ("stride_q", c_int64), ("topk", c_int32), ("reserved", c_int32)]
 
 
+class MlaIndexArgs(Structure):
+    """fasn_mla_index_args (include/fasn.h): the lightning indexer - ReLU-weighted logits over 128-feature index keys, top-k positions"""
+    _fields_ = [
+        ("q", View4),
+        ("w", c_void_p), ("w_stride", c_int64 * 3),
+        ("k_cache", c_void_p), ("k_stride", c_int64 * 2),
+        ("block_table", c_void_p), ("block_table_stride", c_int64), ("max_pages", c_int32),
+        ("seqlens", c_void_p), ("seqlen_add", c_int32), ("page_size", c_int32),
+        ("B", c_int32), ("Hi", c_int32), ("Sq", c_int32), ("D", c_int32),
+        ("dtype", c_int32), ("causal", c_int32), ("topk", c_int32),
+        ("indices", c_void_p), ("indices_stride", c_int64 * 2),
+        ("logits", c_void_p), ("logits_stride", c_int64 * 2),
+        ("reserved", c_int32),
+    ]
+
+
 class FasnError(RuntimeError):
     pass
 
@@ -340,6 +357,11 @@ def _mla_bindings():
     yield "fasn_fwd_mla_sparse_fp8", c_int32, head + [c_void_p, c_size_t, c_void_p]
     yield "fasn_mla_sparse_fp8_append", c_int32, [POINTER(MlaArgs), POINTER(View4), c_void_p]
     yield "fasn_mla_sparse_fp8_plan", c_int32, head + [c_char_p, c_size_t]
+    head = [POINTER(MlaIndexArgs)]   # ... and the four of the indexer that builds such a list: a block of its own
+    yield "fasn_mla_index_workspace_bytes", c_size_t, head
+    yield "fasn_mla_index", c_int32, head + [c_void_p, c_size_t, c_void_p]
+    yield "fasn_mla_index_append", c_int32, head + [POINTER(View4), c_void_p]
+    yield "fasn_mla_index_plan", c_int32, head + [c_char_p, c_size_t]
 
 
 def kv_call(args, fp8=None, tree=None, window=None, alibi=None):
@@ -629,6 +651,12 @@ def mla_sparse_fp8_plan(args, sparse):
     """The two launches of fasn_fwd_mla_sparse_fp8 for `args` (an MlaArgs over 656-byte FP8 rows) and `sparse` (an MlaSparse):
     mla_sparse_plan's grid with the FP8 forward's name and its 157696 bytes of LDS, the dense call's combine. Nothing is launched."""
     return _plan("fasn_mla_sparse_fp8_plan", args, sparse)
+
+
+def mla_index_plan(args):
+    """The two launches of fasn_mla_index for `args` (an MlaIndexArgs) - the logits kernel on B * Sq * ceil(tiles / tpw) workgroups, the
+    select on B * Sq workgroups of 1024 - as (kernel name with template arguments, grid, block, lds bytes). Nothing is launched."""
+    return _plan("fasn_mla_index_plan", args)
 
 
 def softmax_plan(which, a, b, c, rows, cols, a_stride, b_stride, c_stride, dtype):

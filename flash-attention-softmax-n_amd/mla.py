@@ -1,7 +1,8 @@
 """MLA decode: attention over a compressed latent K/V cache (multi-head latent attention in its absorbed form: DeepSeek-V2 / V3 / R1,
 Kimi K2). Host side of fasn_fwd_mla / fasn_mla_append, of fasn_fwd_mla_fp8 / fasn_mla_fp8_append, of fasn_fwd_mla_sparse and of
 fasn_fwd_mla_sparse_fp8 / fasn_mla_sparse_fp8_append in include/fasn.h: one call path, with the scale of an FP8 latent cache, the top-k
-index list of the sparse decode (DeepSeek-V3.2) and the 656-byte FP8 row behind such a list as optional operands.
+index list of the sparse decode (DeepSeek-V3.2) and the 656-byte FP8 row behind such a list as optional operands. Beside it
+flash_attention_n_mla_index, the indexer that builds such a list (fasn_mla_index / fasn_mla_index_append): a call path of its own.
 
 The cache holds ONE row of 576 features per token, shared by every query head: a 512-wide latent and a 64-wide rotated key part. The logit
 of head h is q_h[0:576] . row[0:576] and the value is the latent itself, out_h = sum_j p_hj row_j[0:512] - so K and V are one tensor, read
@@ -14,7 +15,7 @@ import torch
 from torch import Tensor
 
 from . import _lib
-from ._lib import MlaArgs, MlaFp8, MlaSparse
+from ._lib import MlaArgs, MlaFp8, MlaIndexArgs, MlaSparse
 from .flash_attn import _n_strides, _n_tensor, _stream_ptr, _view4
 from .kvcache import _KV_DTYPES, _check_cache, _on_device, _rows, _scale_tensor
 
@@ -331,3 +332,141 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
 
     _on_device(dev, launch)
     return out if lse is None else (out, lse)
+
+
+MLA_INDEX_DIM, MLA_INDEX_HEADS = 128, (32, 64)
+_INDEX_SERVED = (f"served: index queries [B, Hi, Sq, {MLA_INDEX_DIM}] with Hi = 32 or 64 and a cache of {MLA_INDEX_DIM}-feature index keys, both fp16 or "
+                 "both bf16, fp32 weights [B, Hi, Sq], causal or not, topk a multiple of 64, a paged cache with page_size % 64 == 0 or a dense "
+                 f"one; not served: FP8 index keys or queries, other head counts, feature sizes other than {MLA_INDEX_DIM}, packed queries, gradients")
+
+
+def flash_attention_n_mla_index(
+        q_index: Tensor,
+        weights: Tensor,
+        k_cache: Tensor,
+        cache_seqlens: Tensor,
+        topk: int,
+        block_table: Optional[Tensor] = None,
+        k_new: Optional[Tensor] = None,
+        is_causal: bool = True,
+        return_logits: bool = False):
+    """The lightning indexer in front of flash_attention_n_mla_sparse / flash_attention_n_mla_sparse_fp8 (DeepSeek-V3.2), on MI355X: per
+    batch element b and query position i the logit of cache position j is
+
+        logit[b, i, j] = sum_h weights[b, h, i] * relu(q_index[b, h, i, :] . k_b[j, :])
+
+    and the call returns the positions of the topk largest logits. There is no scale: the model folds its softmax scale and Hi ** -0.5
+    into `weights`. Lengths, block table and cache are read by the kernels only and the launches depend on shapes, topk and capacity
+    alone, so one captured graph serves every step.
+
+    :param q_index: [B, Hi, Sq, 128] fp16 / bf16 device tensor, Hi = 32 or 64; feature stride 1, rows 16-byte aligned, other strides
+                  free; never copied.
+    :param weights: fp32 [B, Hi, Sq], any non-negative strides (the model's [B, Sq, Hi] transposed is a legal view); may be negative.
+    :param k_cache: the index keys in q_index's dtype: paged [num_pages, page_size, 1, 128] with `block_table` (page_size a multiple of
+                  64), or dense [B, capacity, 1, 128]; a 3-D tensor without the head axis is the same thing. Never copied; rows at or
+                  beyond the length may hold anything (NaN included).
+    :param cache_seqlens: int32 [B] ON THE DEVICE: valid rows per batch element before this call; never read on the host, not modified.
+    :param topk: a Python int, topk % 64 == 0 and topk >= 64. topk > capacity is legal and only pads.
+    :param block_table: int32 [B, max_pages] on the device. Entries beyond the pages a row needs are never read.
+    :param k_new: optional [B, Sq, 1, 128]: written to the positions cache_seqlens[b] .. + Sq - 1 first (positions at or beyond the
+                  capacity are dropped in the kernel); the new rows are then visible.
+    :param is_causal: with len_b = clamp(cache_seqlens[b] + (Sq if k_new is given else 0), 0, capacity), position i sees the positions
+                  j < L, L = len_b - (Sq - 1 - i). False: L = len_b for every position.
+    :param return_logits: also return fp32 [B, Sq, capacity]: the logit where j < L, -inf elsewhere.
+    :return: int32 [B, Sq, topk], contiguous: the min(topk, L) positions of largest logit in ASCENDING position order, then -1 - directly
+                  the `indices` of both sparse calls. Among equal logits at the cut the lower position wins (-0.0 and +0.0 are equal):
+                  the list is the stable descending sort of logit[:L], cut at topk, sorted ascending. L <= 0 gives a row of -1.
+    """
+    fn = "flash_attention_n_mla_index"
+    if not isinstance(q_index, Tensor) or q_index.dim() != 4 or not isinstance(k_cache, Tensor) or k_cache.dim() not in (3, 4):
+        raise ValueError(f"{fn}: q_index must be [B, Hi, Sq, {MLA_INDEX_DIM}] and k_cache [num_pages, page_size, 1, {MLA_INDEX_DIM}] (paged) or "
+                         f"[B, capacity, 1, {MLA_INDEX_DIM}] (dense); {_INDEX_SERVED}")
+    if k_cache.dim() == 3:
+        k_cache = k_cache.unsqueeze(2)
+    if q_index.dtype in _FP8_DTYPES or k_cache.dtype in (torch.uint8,) + _FP8_DTYPES:
+        raise TypeError(f"{fn}: FP8 index keys or queries ({q_index.dtype}, {k_cache.dtype}) have no kernel; {_INDEX_SERVED}")
+    if q_index.dtype not in _KV_DTYPES:
+        raise ValueError(f"{fn}: dtype {q_index.dtype} is not supported; {_INDEX_SERVED}")
+    if k_cache.dtype != q_index.dtype:
+        raise TypeError(f"{fn}: q_index and k_cache must share one dtype; got {q_index.dtype} and {k_cache.dtype}")
+    B, Hi, Sq, D = q_index.shape
+    if D != MLA_INDEX_DIM or k_cache.shape[3] != MLA_INDEX_DIM or k_cache.shape[2] != 1:
+        raise ValueError(f"{fn}: q_index is {tuple(q_index.shape)} and k_cache {tuple(k_cache.shape)}: not an index-key cache of feature size "
+                         f"{MLA_INDEX_DIM}; {_INDEX_SERVED}")
+    if Hi not in MLA_INDEX_HEADS:
+        raise ValueError(f"{fn}: Hi = {Hi} index heads are not supported; {_INDEX_SERVED}")
+    if isinstance(topk, bool) or not isinstance(topk, int) or topk < 64 or topk % 64 != 0:
+        raise ValueError(f"{fn}: topk = {topk} is not supported: a Python int with topk % 64 == 0 and topk >= 64, as the sparse calls take "
+                         f"their lists; {_INDEX_SERVED}")
+    if not isinstance(weights, Tensor) or weights.dtype != torch.float32 or tuple(weights.shape) != (B, Hi, Sq) or any(s < 0 for s in weights.stride()):
+        got = f"{weights.dtype} {tuple(weights.shape)}" if isinstance(weights, Tensor) else type(weights).__name__
+        raise ValueError(f"{fn}: weights must be an fp32 tensor [B, Hi, Sq] = [{B}, {Hi}, {Sq}] (any non-negative strides); got {got}")
+    if q_index.stride(3) != 1 or q_index.data_ptr() % 16 != 0 or any(q_index.stride(i) % 8 != 0 for i in range(3) if q_index.size(i) > 1):
+        raise ValueError(f"{fn}: q_index needs feature stride 1 and 16-byte aligned rows (it is never copied); got strides {tuple(q_index.stride())}")
+    dev = q_index.device
+    for name, t in (("weights", weights), ("k_cache", k_cache), ("cache_seqlens", cache_seqlens), ("block_table", block_table), ("k_new", k_new)):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}, q_index on {dev}: every operand must live on the queries' device "
+                               f"(the lengths and the block table are read by the kernels, never on the host); {_INDEX_SERVED}")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q_index, weights, k_cache, k_new)):
+        raise RuntimeError(f"{fn} is forward only (inference): an input requires grad. Call it under torch.no_grad()")
+    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B or not cache_seqlens.is_contiguous():
+        raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
+    page_size = k_cache.shape[1]
+    paged = block_table is not None
+    if paged:
+        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.stride(1) != 1 or block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"block_table must be an int32 tensor [B, max_pages] = [{B}, >= 1] with unit column stride; got {block_table.dtype} {tuple(block_table.shape)}")
+        if page_size % 64 != 0:
+            raise ValueError(f"page_size {page_size} is not supported: a paged cache needs page_size % 64 == 0 (a 64-key tile never straddles a page)")
+    elif k_cache.shape[0] != B:
+        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, 1, {MLA_INDEX_DIM}] with B = {B}; got {tuple(k_cache.shape)}")
+    _check_cache("k_cache", k_cache, paged, MLA_INDEX_DIM)
+    if k_new is not None:
+        if k_new.dtype != q_index.dtype or tuple(k_new.shape) != (B, Sq, 1, MLA_INDEX_DIM):
+            raise ValueError(f"k_new must be [B, Sq, 1, {MLA_INDEX_DIM}] = [{B}, {Sq}, 1, {MLA_INDEX_DIM}] in {q_index.dtype}; got {tuple(k_new.shape)} {k_new.dtype}")
+        k_new = _rows(k_new)
+    # (the argument checks above need no device; everything below does)
+    if not q_index.is_cuda:
+        raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
+                           "(there is deliberately no CPU fallback)")
+    capacity = block_table.shape[1] * page_size if paged else page_size
+    weights = weights.detach()
+    a = MlaIndexArgs()
+    a.q = _view4(q_index)
+    a.w = weights.data_ptr()
+    for i in range(3):
+        a.w_stride[i] = weights.stride(i) if weights.size(i) > 1 else 0
+    a.k_cache = k_cache.data_ptr()
+    a.k_stride[0] = k_cache.stride(0) if k_cache.size(0) > 1 else 0
+    a.k_stride[1] = k_cache.stride(1) if k_cache.size(1) > 1 else MLA_INDEX_DIM
+    if paged:
+        a.block_table, a.block_table_stride, a.max_pages = block_table.data_ptr(), block_table.stride(0) if B > 1 else block_table.shape[1], block_table.shape[1]
+    else:
+        a.block_table, a.block_table_stride, a.max_pages = None, 0, 1
+    a.seqlens = cache_seqlens.data_ptr()
+    a.seqlen_add = Sq if k_new is not None else 0
+    a.page_size = page_size
+    a.B, a.Hi, a.Sq, a.D = B, Hi, Sq, MLA_INDEX_DIM
+    a.dtype, a.causal, a.topk, a.reserved = _KV_DTYPES[q_index.dtype], 1 if is_causal else 0, topk, 0
+    a.indices_stride[0], a.indices_stride[1] = Sq * topk, topk
+    a.logits_stride[0], a.logits_stride[1] = Sq * capacity, capacity
+    lib = _lib.load()
+    res = []
+
+    def launch():
+        stream = _stream_ptr(dev)
+        idx = torch.empty((B, Sq, topk), dtype=torch.int32, device=dev)
+        # the kernel writes -inf at the hidden positions of the tiles it works on only: the buffer starts as -inf
+        logits = torch.full((B, Sq, capacity), float("-inf"), dtype=torch.float32, device=dev) if return_logits else None
+        a.indices = idx.data_ptr()
+        a.logits = None if logits is None else logits.data_ptr()
+        if k_new is not None:
+            _lib.check(lib.fasn_mla_index_append(a, _view4(k_new), stream), "fasn_mla_index_append")
+        ws_bytes = lib.fasn_mla_index_workspace_bytes(a)
+        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # torch's caching allocator: capturable
+        _lib.check(lib.fasn_mla_index(a, ws.data_ptr(), ws_bytes, stream), "fasn_mla_index")
+        res.extend((idx, logits))
+
+    _on_device(dev, launch)
+    return (res[0], res[1]) if return_logits else res[0]

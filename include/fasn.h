@@ -1006,6 +1006,76 @@ int fasn_mla_sparse_fp8_append(const fasn_mla_args* args, const fasn_view4* kv_n
 int fasn_mla_sparse_fp8_plan(const fasn_mla_args* args, const fasn_mla_sparse* sparse, char* buf, size_t cap);
 
 /*
+ * LIGHTNING INDEXER FOR THE SPARSE MLA DECODE (additions within ABI 6; no struct or function above is changed): the operation that
+ * produces the `indices` of fasn_fwd_mla_sparse / fasn_fwd_mla_sparse_fp8 (DeepSeek-V3.2). For batch element b, position i and cache
+ * position j
+ *     logit[b, i, j] = sum_h w[b, h, i] * relu(q[b, h, i, 0:128] . k_b[j, 0:128])        h < Hi
+ * with k_b[j] the index-key row at logical position j of batch element b. There is no scale operand: the model folds its softmax scale
+ * and Hi^-1/2 into w, which may be negative. The products are exact in fp32, the sums are fp32.
+ *
+ *   cache     the index keys, one 128-feature row per token, addressed as fasn_fwd_mla addresses its cache: row j % page_size of page
+ *             block_table[b * block_table_stride + j / page_size], feature d at k_cache + (page * k_stride[0] + row * k_stride[1] + d)
+ *             elements (both strides % 8, k_stride[1] >= 128, base 16-byte aligned); block_table == NULL is the dense cache.
+ *   lengths   len_b = clamp(seqlens[b] + seqlen_add, 0, capacity), read in the kernels; capacity = max_pages * page_size (dense:
+ *             page_size). Row (b, i) sees the positions j < L, L = len_b - (Sq - 1 - i) when causal and len_b otherwise. Rows at or
+ *             beyond L and pages no visible position lies in may hold anything; no address is formed from a block-table slot at or
+ *             beyond the pages L needs.
+ *   list      indices[b * indices_stride[0] + i * indices_stride[1] + e], e < topk: the min(topk, L) positions of largest logit in
+ *             ASCENDING position order, then -1. Among equal logits at the cut the lower position wins; -0.0 and +0.0 are equal. The
+ *             list is the stable descending sort of logit[0:L], cut at topk, sorted ascending - a function of the logits alone. L <= topk
+ *             gives 0 .. L - 1 without reading a logit; L <= 0 gives -1 throughout. topk > capacity is legal and only pads. A NaN logit
+ *             has an unspecified rank; the list still holds distinct visible positions.
+ *   logits    optional fp32 out, logits[b * logits_stride[0] + i * logits_stride[1] + j], j < capacity: the logit where j < L. The kernel
+ *             writes -inf at the hidden positions of the 64-key tiles it works on and leaves the rest alone: a caller who wants -inf
+ *             everywhere else fills the buffer with -inf first. NULL: the logits live in the workspace.
+ *   served    D = 128 exactly (FASN_EHEADDIM), fp16 / bf16 for q, the cache and k_new (FASN_EDTYPE), Hi = 32 or 64, topk % 64 == 0,
+ *             paged: page_size % 64 == 0 (each FASN_EUNSUPPORTED).
+ *   checks    in this order, all before any HIP call: args == NULL, a non-positive size or topk, reserved != 0 (FASN_EINVAL); dtype; D;
+ *             a NULL seqlens, k_cache, w or indices, a negative stride or seqlen_add, k_stride[1] < 128, rows of indices or logits that
+ *             overlap, a capacity beyond 2^30 (FASN_EINVAL); what is not served; the view q with the codes of fasn_fwd (FASN_EINVAL /
+ *             FASN_ESTRIDE / FASN_EALIGN); the cache's 16-byte rule and seqlens / block_table / w / indices / logits off 4 bytes
+ *             (FASN_EALIGN); then the workspace.
+ *
+ * fasn_mla_index launches two kernels. fasn_mla_index_logits_kernel runs on B * Sq * ceil(tiles / tpw) workgroups of 256, tiles =
+ * ceil(capacity / 64) and tpw, the 64-key tiles of a workgroup, the even number >= 2 that brings the grid to ~2048 workgroups: the queries
+ * stay in registers, every key row goes from global memory straight into an MFMA operand, no LDS. fasn_mla_index_select_kernel runs on
+ * B * Sq workgroups of 1024: a radix select of the rank-topk logit and an ordered compaction. Both depend on shapes, topk and capacity
+ * alone, so one captured graph serves every step. fasn_mla_index_workspace_bytes(args) = B * Sq * roundup(capacity, 64) * 4 bytes of
+ * 16-byte aligned device memory when logits == NULL and 0 otherwise (FASN_EWORKSPACE when missing or too small; 0 for a block that is
+ * refused). fasn_mla_index_append writes the Sq rows of k_new (a [B, Sq, 1, 128] view) to the positions seqlens[b] .. seqlens[b] + Sq - 1
+ * (positions at or beyond the capacity are dropped inside the kernel; `seqlens` is not modified); a call that is to see them passes
+ * seqlen_add = Sq. fasn_mla_index_plan writes the launches of fasn_mla_index as text, in the line format of fasn_launch_plan, without
+ * touching a device. Not here: FP8 index keys or queries, other head counts or feature sizes, packed queries, gradients.
+ */
+typedef struct fasn_mla_index_args {
+    fasn_view4 q;          /* [B,Hi,Sq,128] */
+    const float* w;        /* DEVICE fp32 [B,Hi,Sq] */
+    int64_t w_stride[3];   /* element strides (batch, head, position); 0 broadcasts */
+    void* k_cache;
+    int64_t k_stride[2];   /* element strides (page, row) */
+    const int32_t* block_table;  /* DEVICE [B, max_pages] page ids, or NULL (dense cache) */
+    int64_t block_table_stride;
+    int32_t max_pages;
+    const int32_t* seqlens;      /* DEVICE [B] */
+    int32_t seqlen_add;
+    int32_t page_size;
+    int32_t B, Hi, Sq, D;  /* Hi = 32 or 64, D = 128 */
+    int32_t dtype;         /* FASN_DTYPE_F16 / FASN_DTYPE_BF16 */
+    int32_t causal;
+    int32_t topk;          /* entries per list: a positive multiple of 64 */
+    int32_t* indices;      /* DEVICE int32 [B,Sq,topk] out, entry stride 1 */
+    int64_t indices_stride[2];   /* element strides (batch, position) */
+    float* logits;         /* DEVICE fp32 [B,Sq,capacity] out, position stride 1; may be NULL */
+    int64_t logits_stride[2];
+    int32_t reserved;      /* 0 */
+} fasn_mla_index_args;
+
+size_t fasn_mla_index_workspace_bytes(const fasn_mla_index_args* args);
+int fasn_mla_index(const fasn_mla_index_args* args, void* workspace, size_t workspace_bytes, fasn_stream_t stream);
+int fasn_mla_index_append(const fasn_mla_index_args* args, const fasn_view4* k_new, fasn_stream_t stream);
+int fasn_mla_index_plan(const fasn_mla_index_args* args, char* buf, size_t cap);
+
+/*
  * Stand-alone softmax_n over the last dimension of a [rows, cols] matrix (row stride in elements,
  * col stride 1). Replaces flash_attention_softmax_n/core/functional.py:15-29 for device tensors.
  * dtype: FASN_DTYPE_F16 / FASN_DTYPE_BF16 / 2 (= fp32).

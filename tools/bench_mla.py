@@ -25,7 +25,13 @@ every position sees, same (B, H, Sq) and alternation A1 / B / A2:
   A  = flash_attention_n_mla_sparse on the bf16 pool mla_fp8_rows_unpack gives: the same numbers (max |A - B| must be 0), the yardstick;
   A2 = the route B replaces, fully captured: torch gather of the 656-byte rows, mla_fp8_rows_unpack, flash_attention_n_mla on the compacted rows.
 Then the calls with kv_new, A + fasn_mla_append and B + fasn_mla_sparse_fp8_append, and graphs that launch the two append entry points alone.
-usage: python tools/bench_mla.py [--fp8 | --sparse | --sparse-fp8] [--rounds N] [--iters N] [--only I]"""
+
+--index: flash_attention_n_mla_index (B), the indexer that builds such a list: Hi = 64, topk = 2048, context 32768, (B, Sq) = (64, 1), (1, 2), (8, 1).
+  A = the torch route, fully captured: gather of the index-key pages through the table, einsum over the 64 heads, relu, the weighted head
+      sum, the length and causal mask, torch.topk. Reported beside the times: the share of B's entries that A's list holds too (A's logits
+      are sums of bf16 matmul outputs, so the lists differ near the cut) and B's TB/s of key bytes (B * Sq * len * 256: every position
+      reads the keys once).
+usage: python tools/bench_mla.py [--fp8 | --sparse | --sparse-fp8 | --index] [--rounds N] [--iters N] [--only I]"""
 import argparse
 import sys
 
@@ -120,6 +126,51 @@ def sparse_main(args):
         torch.cuda.empty_cache()
 
 
+INDEX_SHAPES = [(64, 1), (1, 2), (8, 1)]   # (B, Sq)
+INDEX_HEADS, INDEX_D = 64, 128
+
+
+def index_main(args):
+    dev, dtype = torch.device("cuda:0"), torch.bfloat16
+    print(f"A = torch gather + einsum + relu + weighted sum + mask + topk, B = flash_attention_n_mla_index (Hi {INDEX_HEADS}, topk {TOPK} of {CONTEXT})")
+    print(f"{'shape (B,Sq)':14s} {'A us':>26s} {'B us':>26s} {'A/B':>6s} {'A spread':>9s} {'B entries in A list':>20s} {'B TB/s of key bytes':>20s}")
+    for idx, (B, Sq) in enumerate(INDEX_SHAPES):
+        if args.only is not None and idx != args.only:
+            continue
+        torch.manual_seed(0)
+        max_pages = CONTEXT // PAGE
+        q = torch.randn(B, INDEX_HEADS, Sq, INDEX_D, device=dev, dtype=dtype)
+        w = (torch.randn(B, Sq, INDEX_HEADS, device=dev) * INDEX_HEADS ** -0.5).transpose(1, 2)   # the model's [B, Sq, Hi], transposed
+        pool = torch.randn(B * max_pages, PAGE, 1, INDEX_D, device=dev, dtype=dtype)
+        table = torch.randperm(B * max_pages, device=dev).to(torch.int32).view(B, max_pages)
+        sl = torch.full((B,), CONTEXT, dtype=torch.int32, device=dev)
+        pos = torch.arange(CONTEXT, device=dev).view(1, 1, -1)
+        qi = torch.arange(Sq, device=dev).view(1, Sq, 1)
+
+        def run_a():
+            rows = pool[table.long()].view(B, CONTEXT, INDEX_D)                                        # gather the pages
+            s = torch.relu(torch.einsum("bhqd,bsd->bhqs", q, rows).float())
+            lg = (w[..., None] * s).sum(1).masked_fill(pos > qi + sl.view(B, 1, 1) - Sq, float("-inf"))
+            return lg.topk(TOPK, -1).indices
+
+        def run_b():
+            return fa.flash_attention_n_mla_index(q, w, pool, sl, TOPK, block_table=table)
+
+        with torch.no_grad():
+            (ga, oa), (gb, ob) = graph_of(run_a), graph_of(run_b)
+            ta, tb = [], []
+            for _ in range(args.rounds):
+                ta.append(time_graph(ga, args.iters))
+                tb.append(time_graph(gb, args.iters))
+            same = sum(int(torch.isin(b, a).sum()) for a, b in zip(oa.view(-1, TOPK), ob.view(-1, TOPK))) / (B * Sq * TOPK)
+        a_med, b_med = sorted(ta)[len(ta) // 2], sorted(tb)[len(tb) // 2]
+        fmt = lambda ts: "/".join(f"{t:.1f}" for t in ts)   # noqa: E731
+        tbs = B * Sq * CONTEXT * INDEX_D * 2 / (b_med * 1e-6) / 1e12
+        print(f"{str((B, Sq)):14s} {fmt(ta):>26s} {fmt(tb):>26s} {a_med / b_med:6.2f} {max(ta) / min(ta):9.3f} {same:20.4f} {tbs:20.2f}", flush=True)
+        del ga, gb, pool
+        torch.cuda.empty_cache()
+
+
 def append_graph(name, q, pool, table, sl, kv_new):
     """a captured graph that launches nothing but the append entry point `name` on the call's block (pool: 16-bit or 656-byte rows)"""
     from flash_attention_softmax_n_amd import _lib
@@ -204,6 +255,7 @@ def main():
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--sparse", action="store_true")
     ap.add_argument("--sparse-fp8", action="store_true")
+    ap.add_argument("--index", action="store_true")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "bench_mla needs a GPU"
     dev, dtype = torch.device("cuda:0"), torch.bfloat16
@@ -212,6 +264,8 @@ def main():
         return sparse_main(args)
     if args.sparse_fp8:
         return sparse_fp8_main(args)
+    if args.index:
+        return index_main(args)
     if args.fp8:
         print("A = flash_attention_n_mla (bf16 cache), B = flash_attention_n_mla_fp8 (e4m3fn cache, kv_scale = 1)")
     print(f"{'shape (B,H,Sq,len)':24s} {'A us':>26s} {'B us':>26s} {'A/B':>6s} {'A spread':>9s} {'max|A-B|':>9s} "
