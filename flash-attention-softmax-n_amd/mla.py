@@ -9,7 +9,7 @@ of head h is q_h[0:576] . row[0:576] and the value is the latent itself, out_h =
 once. The call sits beside the K/V-cache family (kvcache.py) and shares its contract: lengths and block table are read by the kernels only,
 the launches depend on shapes and capacity alone, one captured graph serves every step. Forward only.
 """
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 from torch import Tensor
@@ -64,7 +64,7 @@ def flash_attention_n_mla(
     :param return_lse: also return lse [B, H, Sq] fp32 = log(n + sum_j exp(x_ij)).
     :return: [B, H, Sq, 512] in query's dtype (and lse). Rows that see no key give exactly 0 and lse = log n (-inf for n = 0).
     """
-    return _mla("flash_attention_n_mla", query, kv_cache, cache_seqlens, scale, None, block_table, kv_new, softmax_n_param, is_causal, return_lse)
+    return _mla(_MLA, query, kv_cache, cache_seqlens, scale, None, block_table, kv_new, softmax_n_param, is_causal, return_lse)
 
 
 def flash_attention_n_mla_fp8(
@@ -92,8 +92,7 @@ def flash_attention_n_mla_fp8(
     :param kv_new: optional [B, Sq, 1, 576] in query's dtype: quantised as flash_attention_n_kvcache quantises k_new for an FP8 cache -
                   code = rne_e4m3(clamp(float(x) / kv_scale[b], -448, 448)), NaN to a NaN code - written behind the lengths, then seen.
     """
-    return _mla("flash_attention_n_mla_fp8", query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_new, softmax_n_param, is_causal,
-                return_lse, fp8=True)
+    return _mla(_MLA_FP8, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_new, softmax_n_param, is_causal, return_lse)
 
 
 def flash_attention_n_mla_sparse(
@@ -122,8 +121,7 @@ def flash_attention_n_mla_sparse(
                   serves every step.
     :return: [B, H, Sq, 512] in query's dtype (and lse). Rows without a key give exactly 0 and lse = log n.
     """
-    return _mla("flash_attention_n_mla_sparse", query, kv_cache, cache_seqlens, scale, None, block_table, kv_new, softmax_n_param, is_causal,
-                return_lse, indices=indices, sparse=True)
+    return _mla(_MLA_SPARSE, query, kv_cache, cache_seqlens, scale, indices, block_table, kv_new, softmax_n_param, is_causal, return_lse)
 
 
 def flash_attention_n_mla_sparse_fp8(
@@ -154,8 +152,7 @@ def flash_attention_n_mla_sparse_fp8(
                   cache_seqlens[b] .. + Sq - 1 (positions at or beyond the capacity are dropped in the kernel), then nameable.
     :return: [B, H, Sq, 512] in query's dtype (and lse). Rows without a key give exactly 0 and lse = log n.
     """
-    return _mla("flash_attention_n_mla_sparse_fp8", query, kv_cache, cache_seqlens, scale, None, block_table, kv_new, softmax_n_param,
-                is_causal, return_lse, indices=indices, sparse=True, rows8=True)
+    return _mla(_MLA_SPARSE_FP8, query, kv_cache, cache_seqlens, scale, indices, block_table, kv_new, softmax_n_param, is_causal, return_lse)
 
 
 def _fp8_group_exponent(amax: Tensor) -> Tensor:
@@ -199,35 +196,117 @@ def mla_fp8_rows_unpack(rows656: Tensor, dtype: torch.dtype) -> Tensor:
     return torch.cat([(codes * s[..., None]).to(dtype).reshape(*lead, MLA_VALUE_DIM), rope], -1)
 
 
-def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_new, softmax_n_param, is_causal, return_lse, fp8=False,
-         indices=None, sparse=False, rows8=False):
-    """the one call path of the four functions; fp8: the cache holds e4m3fn codes and `kv_scale` is their scale; sparse: `indices` is the
-    top-k list of logical positions; rows8 (with sparse): the cache holds 656-byte FP8 rows, which carry their scales"""
-    row = MLA_FP8_ROW_BYTES if rows8 else MLA_HEAD_DIM   # elements of a cache row
+def _scale_operand(fn, kv_scale, query):
+    if isinstance(kv_scale, Tensor) and kv_scale.dim() == 1:   # the one K/V head has no axis here: a 1-D scale is [B]
+        kv_scale = kv_scale[:, None]
+    ks = _scale_tensor(fn, "kv_scale", kv_scale, query, 1)   # [1 or B, 1] fp32
+    f8 = MlaFp8()
+    f8.kv_scale, f8.sb, f8.reserved = ks.data_ptr(), ks.stride(0) if ks.shape[0] > 1 else 0, 0
+    return f8, ks
+
+
+def _list_operand(fn, indices, query):
+    sp, (B, Sq, topk) = MlaSparse(), indices.shape
+    sp.indices, sp.topk, sp.reserved = indices.data_ptr(), topk, 0
+    sp.stride_b, sp.stride_q = indices.stride(0) if B > 1 else 0, indices.stride(1) if Sq > 1 else 0
+    return sp, indices
+
+
+class _Variant(NamedTuple):
+    """one public function of the decode (csrc/fasn_mla.hip: MlaVariant): what its cache holds and which operand stands behind the block"""
+    fn: str                 # the public name, for messages
+    row: int                # elements of a cache row
+    cache_dtypes: Optional[tuple]   # the dtypes the cache may have; None: the query's
+    refusals: tuple         # (cache dtypes or None for every other, the refusal's text in front of the dtype, behind it), in the order tried
+    indices: bool           # the operand is the top-k list, checked beside the queries
+    operand: Optional[Callable]   # (fn, kv_scale or indices, query) -> (the ctypes operand, the tensor it points into); None: no operand
+    forward: str            # the entry points: the forward, its workspace size ...
+    workspace: str
+    append: str             # ... and the append ...
+    append_operand: bool    # ... which takes the operand too
+
+
+_MLA = _Variant("flash_attention_n_mla", MLA_HEAD_DIM, None,
+                ((_FP8_DTYPES, "an FP8 latent cache (", ") is flash_attention_n_mla_fp8's (e4m3fn codes with kv_scale); " + _SERVED),),
+                False, None, "fasn_fwd_mla", "fasn_mla_workspace_bytes", "fasn_mla_append", False)
+_MLA_FP8 = _Variant("flash_attention_n_mla_fp8", MLA_HEAD_DIM, (torch.float8_e4m3fn,),
+                    ((_FP8_DTYPES, "the cache must hold torch.float8_e4m3fn codes; ", " has no kernel; " + _SERVED),
+                     (None, "the cache must hold torch.float8_e4m3fn codes; a ", " cache is flash_attention_n_mla's")),
+                    False, _scale_operand, "fasn_fwd_mla_fp8", "fasn_mla_fp8_workspace_bytes", "fasn_mla_fp8_append", True)
+_MLA_SPARSE = _Variant("flash_attention_n_mla_sparse", MLA_HEAD_DIM, None,
+                       (((torch.uint8,) + _FP8_DTYPES, "an FP8 latent cache (",
+                         f") behind indices is flash_attention_n_mla_sparse_fp8's ({MLA_FP8_ROW_BYTES}-byte rows); " + _SERVED),),
+                       True, _list_operand, "fasn_fwd_mla_sparse", "fasn_mla_sparse_workspace_bytes", "fasn_mla_append", False)   # (the 16-bit cache's append)
+_MLA_SPARSE_FP8 = _Variant("flash_attention_n_mla_sparse_fp8", MLA_FP8_ROW_BYTES, _BYTE_DTYPES,
+                           ((None, f"the cache must hold {MLA_FP8_ROW_BYTES}-byte rows as torch.uint8 or torch.float8_e4m3fn; a ",
+                             " cache behind indices is flash_attention_n_mla_sparse's; " + _SERVED),),
+                           True, _list_operand, "fasn_fwd_mla_sparse_fp8", "fasn_mla_sparse_fp8_workspace_bytes", "fasn_mla_sparse_fp8_append", False)
+
+
+# how the shared checks call a caller's operands: the queries, the cache, the new rows and their width, the device rule's text
+_Names = NamedTuple("_Names", [("query", str), ("cache", str), ("new", str), ("new_dim", int), ("where", str)])
+_MLA_NAMES = _Names("query", "kv_cache", "kv_new", MLA_HEAD_DIM, "every operand must live on the query's device (the lengths, the block table "
+                    "and the index list are read by the kernels, never on the host); " + _SERVED)
+_NO_CPU = "flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor (there is deliberately no CPU fallback)"
+
+
+def _cache_operands(a, stride, fn, names, query, B, Sq, dev, operands, no_grad, cache, row, cache_seqlens, block_table, new):
+    """What the decode and the indexer share behind their own checks: every operand on the queries' device, forward only, the rules of
+    `cache_seqlens`, `block_table`, the page size and the dense batch, the cache's layout, the new rows; then the cache, table and length
+    members of the argument block `a` (stride: its array of the cache's page and row strides). operands: (name, tensor) of all but the
+    queries, in the order the device rule names them; no_grad: what must not require grad. Returns (the new rows as the kernels read
+    them, page_size)."""
+    for name, t in operands:
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{name} is on {t.device}, {names.query} on {dev}: {names.where}")
+    if torch.is_grad_enabled() and any(isinstance(t, Tensor) and t.requires_grad for t in no_grad):
+        raise RuntimeError(f"{fn} is forward only (inference): an input requires grad. Call it under torch.no_grad()")
+    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B or not cache_seqlens.is_contiguous():
+        raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
+    page_size = cache.shape[1]
+    paged = block_table is not None
+    if paged:
+        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.stride(1) != 1 or block_table.shape[0] != B or block_table.shape[1] < 1:
+            raise ValueError(f"block_table must be an int32 tensor [B, max_pages] = [{B}, >= 1] with unit column stride; got {block_table.dtype} {tuple(block_table.shape)}")
+        if page_size % 64 != 0:
+            raise ValueError(f"page_size {page_size} is not supported: a paged cache needs page_size % 64 == 0 (a 64-key tile never straddles a page)")
+    elif cache.shape[0] != B:
+        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, 1, {row}] with B = {B}; got {tuple(cache.shape)}")
+    _check_cache(names.cache, cache, paged, row)
+    if new is not None:
+        if new.dtype != query.dtype or tuple(new.shape) != (B, Sq, 1, names.new_dim):
+            raise ValueError(f"{names.new} must be [B, Sq, 1, {names.new_dim}] = [{B}, {Sq}, 1, {names.new_dim}] in {query.dtype}; got {tuple(new.shape)} {new.dtype}")
+        new = _rows(new)
+    stride[0] = cache.stride(0) if cache.size(0) > 1 else 0
+    stride[1] = cache.stride(1) if cache.size(1) > 1 else row
+    if paged:
+        a.block_table, a.block_table_stride, a.max_pages = block_table.data_ptr(), block_table.stride(0) if B > 1 else block_table.shape[1], block_table.shape[1]
+    else:
+        a.block_table, a.block_table_stride, a.max_pages = None, 0, 1
+    a.seqlens, a.seqlen_add, a.page_size = cache_seqlens.data_ptr(), Sq if new is not None else 0, page_size
+    return new, page_size
+
+
+def _mla(v, query, kv_cache, cache_seqlens, scale, operand, block_table, kv_new, softmax_n_param, is_causal, return_lse):
+    """the one call path of the four functions; v: the function's variant record; operand: kv_scale or indices, where v takes one"""
+    fn, row, cache_dtypes, refusals, takes_list, build_operand, fwd, ws_name, append, append_operand = v
     if not isinstance(query, Tensor) or query.dim() != 4 or not isinstance(kv_cache, Tensor) or kv_cache.dim() not in (3, 4):
         raise ValueError(f"{fn}: query must be [B, H, Sq, {MLA_HEAD_DIM}] and kv_cache [num_pages, page_size, 1, {row}] (paged) or "
                          f"[B, capacity, 1, {row}] (dense); {_SERVED}")
     if kv_cache.dim() == 3:
         kv_cache = kv_cache.unsqueeze(2)
-    if rows8 and kv_cache.dtype not in _BYTE_DTYPES:
-        raise TypeError(f"{fn}: the cache must hold {MLA_FP8_ROW_BYTES}-byte rows as torch.uint8 or torch.float8_e4m3fn; a {kv_cache.dtype} "
-                        f"cache behind indices is flash_attention_n_mla_sparse's; {_SERVED}")
-    if sparse and not rows8 and kv_cache.dtype in (torch.uint8,) + _FP8_DTYPES:
-        raise TypeError(f"{fn}: an FP8 latent cache ({kv_cache.dtype}) behind indices is flash_attention_n_mla_sparse_fp8's "
-                        f"({MLA_FP8_ROW_BYTES}-byte rows); {_SERVED}")
-    if not fp8 and not rows8 and kv_cache.dtype in _FP8_DTYPES:
-        raise TypeError(f"{fn}: an FP8 latent cache ({kv_cache.dtype}) is flash_attention_n_mla_fp8's (e4m3fn codes with kv_scale); {_SERVED}")
-    if fp8 and kv_cache.dtype != torch.float8_e4m3fn:
-        if kv_cache.dtype in _FP8_DTYPES:
-            raise TypeError(f"{fn}: the cache must hold torch.float8_e4m3fn codes; {kv_cache.dtype} has no kernel; {_SERVED}")
-        raise TypeError(f"{fn}: the cache must hold torch.float8_e4m3fn codes; a {kv_cache.dtype} cache is flash_attention_n_mla's")
+    cache_dtype = kv_cache.dtype
+    if cache_dtypes is None or cache_dtype not in cache_dtypes:
+        for dtypes, before, behind in refusals:
+            if dtypes is None or cache_dtype in dtypes:
+                raise TypeError(f"{fn}: {before}{cache_dtype}{behind}")
     B, H, Sq, D = query.shape
     if D != MLA_HEAD_DIM or kv_cache.shape[3] != row or kv_cache.shape[2] != 1:
         raise ValueError(f"{fn}: query is {tuple(query.shape)} and kv_cache {tuple(kv_cache.shape)}: not a latent cache; {_SERVED}. "
                          "Separate K and V of one head dim are flash_attention_n_kvcache's")
     if query.dtype not in _KV_DTYPES:
         raise ValueError(f"{fn}: dtype {query.dtype} is not supported; {_SERVED}")
-    if not fp8 and not rows8 and kv_cache.dtype != query.dtype:
+    if cache_dtypes is None and cache_dtype != query.dtype:
         raise TypeError(f"{fn}: query and kv_cache must share one dtype; got {query.dtype} and {kv_cache.dtype}")
     if H * Sq > MLA_MAX_ROWS:
         raise ValueError(f"{fn}: H * Sq = {H} x {Sq} = {H * Sq} rows exceed {MLA_MAX_ROWS}; {_SERVED}")
@@ -239,7 +318,8 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
         raise ValueError(f"{fn}: float16 serves |scale| * log2(e) <= {_F16_MAX_PRESCALE:g} (the queries are prescaled in float16); got scale "
                          f"{scale}. Use bfloat16, or fold the factor into the queries")
     dev = query.device
-    if sparse:
+    indices = operand if takes_list else None
+    if takes_list:
         if not isinstance(indices, Tensor) or indices.dtype != torch.int32 or tuple(indices.shape[:2]) != (B, Sq) or indices.dim() != 3 \
                 or indices.stride(2) != 1:
             got = f"{indices.dtype} {tuple(indices.shape)}" if isinstance(indices, Tensor) else type(indices).__name__
@@ -248,58 +328,25 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
         if indices.shape[2] < 64 or indices.shape[2] % 64 != 0:
             raise ValueError(f"{fn}: topk = {indices.shape[2]} is not supported: topk % 64 == 0 and topk >= 64 (pad the list with -1 where "
                              f"it is built: the call does not copy it); {_SERVED}")
-    for name, t in (("kv_cache", kv_cache), ("indices", indices), ("cache_seqlens", cache_seqlens), ("block_table", block_table), ("kv_new", kv_new)):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"{name} is on {t.device}, query on {dev}: every operand must live on the query's device "
-                               f"(the lengths, the block table and the index list are read by the kernels, never on the host); {_SERVED}")
-    if torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in (query, kv_cache, kv_new))
-                                    or (isinstance(softmax_n_param, Tensor) and softmax_n_param.requires_grad)):
-        raise RuntimeError(f"{fn} is forward only (inference): an input requires grad. Call it under torch.no_grad()")
-    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B or not cache_seqlens.is_contiguous():
-        raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
-    page_size = kv_cache.shape[1]
-    paged = block_table is not None
-    if paged:
-        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.stride(1) != 1 or block_table.shape[0] != B or block_table.shape[1] < 1:
-            raise ValueError(f"block_table must be an int32 tensor [B, max_pages] = [{B}, >= 1] with unit column stride; got {block_table.dtype} {tuple(block_table.shape)}")
-        if page_size % 64 != 0:
-            raise ValueError(f"page_size {page_size} is not supported: a paged cache needs page_size % 64 == 0 (a 64-key tile never straddles a page)")
-    elif kv_cache.shape[0] != B:
-        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, 1, {row}] with B = {B}; got {tuple(kv_cache.shape)}")
-    _check_cache("kv_cache", kv_cache, paged, row)
-    if kv_new is not None:
-        if kv_new.dtype != query.dtype or tuple(kv_new.shape) != (B, Sq, 1, MLA_HEAD_DIM):
-            raise ValueError(f"kv_new must be [B, Sq, 1, {MLA_HEAD_DIM}] = [{B}, {Sq}, 1, {MLA_HEAD_DIM}] in {query.dtype}; got {tuple(kv_new.shape)} {kv_new.dtype}")
-        kv_new = _rows(kv_new)
+    a = MlaArgs()
+    operands = (("kv_cache", kv_cache), ("indices", indices), ("cache_seqlens", cache_seqlens), ("block_table", block_table), ("kv_new", kv_new))
+    kv_new, _ = _cache_operands(a, a.kv_stride, fn, _MLA_NAMES, query, B, Sq, dev, operands, (query, kv_cache, kv_new, softmax_n_param),
+                                kv_cache, row, cache_seqlens, block_table, kv_new)
     query = _rows(query)
-    if fp8 and isinstance(kv_scale, Tensor) and kv_scale.dim() == 1:   # the one K/V head has no axis here: a 1-D scale is [B]
-        kv_scale = kv_scale[:, None]
-    ks = _scale_tensor(fn, "kv_scale", kv_scale, query, 1) if fp8 else None   # [1 or B, 1] fp32
+    held = build_operand(fn, operand, query) if build_operand else None   # (the ctypes operand, the tensor it points into: alive until the launches)
     if isinstance(softmax_n_param, Tensor):
         nt, n = _n_tensor(softmax_n_param.detach(), query).contiguous(), 0.0
     else:
         nt, n = None, 0.0 if softmax_n_param is None else float(softmax_n_param)
         if n < 0:
             raise ValueError("softmax_n_param must be >= 0")
-    # (the argument checks above need no device; everything below does)
-    if not query.is_cuda:
-        raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
-                           "(there is deliberately no CPU fallback)")
+    if not query.is_cuda:   # (the argument checks above need no device; everything below does)
+        raise RuntimeError(_NO_CPU)
     out = torch.empty((B, H, Sq, MLA_VALUE_DIM), dtype=query.dtype, device=dev)
     lse = torch.empty((B, H, Sq), dtype=torch.float32, device=dev) if return_lse else None
-    a = MlaArgs()
     a.q, a.o = _view4(query), _view4(out)
     a.lse = None if lse is None else lse.data_ptr()
     a.kv_cache = kv_cache.data_ptr()
-    a.kv_stride[0] = kv_cache.stride(0) if kv_cache.size(0) > 1 else 0
-    a.kv_stride[1] = kv_cache.stride(1) if kv_cache.size(1) > 1 else row
-    if paged:
-        a.block_table, a.block_table_stride, a.max_pages = block_table.data_ptr(), block_table.stride(0) if B > 1 else block_table.shape[1], block_table.shape[1]
-    else:
-        a.block_table, a.block_table_stride, a.max_pages = None, 0, 1
-    a.seqlens = cache_seqlens.data_ptr()
-    a.seqlen_add = Sq if kv_new is not None else 0
-    a.page_size = page_size
     a.B, a.H, a.Sq, a.D, a.Dv = B, H, Sq, MLA_HEAD_DIM, MLA_VALUE_DIM
     a.dtype = _KV_DTYPES[query.dtype]
     a.scale, a.softmax_n, a.causal, a.reserved = scale, n, 1 if is_causal else 0, 0
@@ -307,28 +354,15 @@ def _mla(fn, query, kv_cache, cache_seqlens, scale, kv_scale, block_table, kv_ne
         a.n = nt.data_ptr()
         a.n_stride_b, a.n_stride_h = _n_strides(nt)
     lib = _lib.load()
-    # the entry points and the operands behind the block: the four of the 16-bit cache, their _fp8 siblings with the scale, or the
-    # _sparse ones with the index list (whose append is the 16-bit cache's), or the _sparse_fp8 ones with the list and an append of their own
-    ops, suffix, app = (), "", ()
-    if fp8:
-        f8 = MlaFp8()
-        f8.kv_scale, f8.sb, f8.reserved = ks.data_ptr(), ks.stride(0) if ks.shape[0] > 1 else 0, 0
-        ops, suffix = (f8,), "_fp8"
-        app = ops
-    if sparse:
-        sp = MlaSparse()
-        sp.indices, sp.topk, sp.reserved = indices.data_ptr(), indices.shape[2], 0
-        sp.stride_b, sp.stride_q = indices.stride(0) if B > 1 else 0, indices.stride(1) if Sq > 1 else 0
-        ops, suffix = (sp,), "_sparse_fp8" if rows8 else "_sparse"
-    app_name = "fasn_mla_sparse_fp8_append" if rows8 else "fasn_mla_fp8_append" if fp8 else "fasn_mla_append"
+    ops = () if held is None else (held[0],)
 
     def launch():
         stream = _stream_ptr(dev)
         if kv_new is not None:
-            _lib.check(getattr(lib, app_name)(a, *app, _view4(kv_new), stream), app_name)
-        ws_bytes = getattr(lib, f"fasn_mla{suffix}_workspace_bytes")(a, *ops)
+            _lib.check(getattr(lib, append)(a, *(ops if append_operand else ()), _view4(kv_new), stream), append)
+        ws_bytes = getattr(lib, ws_name)(a, *ops)
         ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=dev)   # torch's caching allocator: capturable
-        _lib.check(getattr(lib, f"fasn_fwd_mla{suffix}")(a, *ops, ws.data_ptr(), ws_bytes, stream), f"fasn_fwd_mla{suffix}")
+        _lib.check(getattr(lib, fwd)(a, *ops, ws.data_ptr(), ws_bytes, stream), fwd)
 
     _on_device(dev, launch)
     return out if lse is None else (out, lse)
@@ -338,6 +372,10 @@ MLA_INDEX_DIM, MLA_INDEX_HEADS = 128, (32, 64)
 _INDEX_SERVED = (f"served: index queries [B, Hi, Sq, {MLA_INDEX_DIM}] with Hi = 32 or 64 and a cache of {MLA_INDEX_DIM}-feature index keys, both fp16 or "
                  "both bf16, fp32 weights [B, Hi, Sq], causal or not, topk a multiple of 64, a paged cache with page_size % 64 == 0 or a dense "
                  f"one; not served: FP8 index keys or queries, other head counts, feature sizes other than {MLA_INDEX_DIM}, packed queries, gradients")
+
+
+_INDEX_NAMES = _Names("q_index", "k_cache", "k_new", MLA_INDEX_DIM, "every operand must live on the queries' device (the lengths and the block "
+                      "table are read by the kernels, never on the host); " + _INDEX_SERVED)
 
 
 def flash_attention_n_mla_index(
@@ -404,49 +442,19 @@ def flash_attention_n_mla_index(
     if q_index.stride(3) != 1 or q_index.data_ptr() % 16 != 0 or any(q_index.stride(i) % 8 != 0 for i in range(3) if q_index.size(i) > 1):
         raise ValueError(f"{fn}: q_index needs feature stride 1 and 16-byte aligned rows (it is never copied); got strides {tuple(q_index.stride())}")
     dev = q_index.device
-    for name, t in (("weights", weights), ("k_cache", k_cache), ("cache_seqlens", cache_seqlens), ("block_table", block_table), ("k_new", k_new)):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"{name} is on {t.device}, q_index on {dev}: every operand must live on the queries' device "
-                               f"(the lengths and the block table are read by the kernels, never on the host); {_INDEX_SERVED}")
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q_index, weights, k_cache, k_new)):
-        raise RuntimeError(f"{fn} is forward only (inference): an input requires grad. Call it under torch.no_grad()")
-    if cache_seqlens.dtype != torch.int32 or cache_seqlens.dim() != 1 or cache_seqlens.shape[0] != B or not cache_seqlens.is_contiguous():
-        raise ValueError(f"cache_seqlens must be a contiguous int32 tensor of shape [{B}] on the device; got {cache_seqlens.dtype} {tuple(cache_seqlens.shape)}")
-    page_size = k_cache.shape[1]
-    paged = block_table is not None
-    if paged:
-        if block_table.dtype != torch.int32 or block_table.dim() != 2 or block_table.stride(1) != 1 or block_table.shape[0] != B or block_table.shape[1] < 1:
-            raise ValueError(f"block_table must be an int32 tensor [B, max_pages] = [{B}, >= 1] with unit column stride; got {block_table.dtype} {tuple(block_table.shape)}")
-        if page_size % 64 != 0:
-            raise ValueError(f"page_size {page_size} is not supported: a paged cache needs page_size % 64 == 0 (a 64-key tile never straddles a page)")
-    elif k_cache.shape[0] != B:
-        raise ValueError(f"dense cache (block_table=None) must be [B, capacity, 1, {MLA_INDEX_DIM}] with B = {B}; got {tuple(k_cache.shape)}")
-    _check_cache("k_cache", k_cache, paged, MLA_INDEX_DIM)
-    if k_new is not None:
-        if k_new.dtype != q_index.dtype or tuple(k_new.shape) != (B, Sq, 1, MLA_INDEX_DIM):
-            raise ValueError(f"k_new must be [B, Sq, 1, {MLA_INDEX_DIM}] = [{B}, {Sq}, 1, {MLA_INDEX_DIM}] in {q_index.dtype}; got {tuple(k_new.shape)} {k_new.dtype}")
-        k_new = _rows(k_new)
-    # (the argument checks above need no device; everything below does)
-    if not q_index.is_cuda:
-        raise RuntimeError("flash_attention_softmax_n_amd runs on MI355X device tensors only; got a CPU tensor "
-                           "(there is deliberately no CPU fallback)")
-    capacity = block_table.shape[1] * page_size if paged else page_size
-    weights = weights.detach()
     a = MlaIndexArgs()
+    operands = (("weights", weights), ("k_cache", k_cache), ("cache_seqlens", cache_seqlens), ("block_table", block_table), ("k_new", k_new))
+    k_new, page_size = _cache_operands(a, a.k_stride, fn, _INDEX_NAMES, q_index, B, Sq, dev, operands, (q_index, weights, k_cache, k_new),
+                                       k_cache, MLA_INDEX_DIM, cache_seqlens, block_table, k_new)
+    if not q_index.is_cuda:   # (the argument checks above need no device; everything below does)
+        raise RuntimeError(_NO_CPU)
+    capacity = block_table.shape[1] * page_size if block_table is not None else page_size
+    weights = weights.detach()
     a.q = _view4(q_index)
     a.w = weights.data_ptr()
     for i in range(3):
         a.w_stride[i] = weights.stride(i) if weights.size(i) > 1 else 0
     a.k_cache = k_cache.data_ptr()
-    a.k_stride[0] = k_cache.stride(0) if k_cache.size(0) > 1 else 0
-    a.k_stride[1] = k_cache.stride(1) if k_cache.size(1) > 1 else MLA_INDEX_DIM
-    if paged:
-        a.block_table, a.block_table_stride, a.max_pages = block_table.data_ptr(), block_table.stride(0) if B > 1 else block_table.shape[1], block_table.shape[1]
-    else:
-        a.block_table, a.block_table_stride, a.max_pages = None, 0, 1
-    a.seqlens = cache_seqlens.data_ptr()
-    a.seqlen_add = Sq if k_new is not None else 0
-    a.page_size = page_size
     a.B, a.Hi, a.Sq, a.D = B, Hi, Sq, MLA_INDEX_DIM
     a.dtype, a.causal, a.topk, a.reserved = _KV_DTYPES[q_index.dtype], 1 if is_causal else 0, topk, 0
     a.indices_stride[0], a.indices_stride[1] = Sq * topk, topk

@@ -1,53 +1,15 @@
 """flash_attention_n_mla on the GPU: decode over a compressed latent K/V cache (576-feature rows, the first 512 the value) against plain
 fp32 torch - the visible rows gathered through the table, x = scale q row^T, the mask, the explicit sink column of weight n,
 out = p row[:, :512] - under the K/V-cache suites' own gates (tests/kv_support.py)."""
-import functools
-
 import pytest
 import torch
 
-from kv_support import _bh, _bits, _capture, _check, _check_lse, _gather, _n_values, _Paged, _rand, _visibility
+from kv_support import _bits, _capture, _check, _check_lse, _gather, _Paged, _rand, _visibility
+from mla_support import E, EV, LENS, SCALE, _cache, _n, _nsplit, _ref
 
 pytestmark = pytest.mark.gpu
 
-E, EV = 576, 512
-SCALE = (128 + 64) ** -0.5
-LENS = [0, 1, 63, 64, 65, 129, 1100]   # empty, shorter than Sq, a tile edge from both sides, a page edge, a length that is split
 SHAPES = [(5, 1), (16, 2), (33, 2), (128, 2)]   # a partial wave, one 32-row half, a 64-row block + 2 rows, the 256-row limit
-
-
-def _ref(q, rows, lens, n, causal, scale=SCALE):
-    """rows: [B, S, 576] with the rows at or beyond len_b zeroed. Returns (out [B, H, Sq, 512], lse [B, H, Sq]) in fp32."""
-    B, H, Sq, _ = q.shape
-    x = scale * torch.einsum("bhqd,bsd->bhqs", q.float(), rows.float())
-    x = x.masked_fill(~_visibility(lens, Sq, rows.shape[1], causal, q.device), float("-inf"))
-    sink = _bh(torch.as_tensor(n, dtype=torch.float32, device=q.device), B, H).log()[..., None, None].expand(B, H, Sq, 1)   # (log 0 = -inf)
-    xs = torch.cat([sink, x], -1)
-    lse = torch.logsumexp(xs, -1)
-    p = torch.exp(xs - torch.where(torch.isfinite(lse), lse, torch.zeros_like(lse))[..., None])[..., 1:]
-    return torch.einsum("bhqs,bsd->bhqd", p, rows[..., :EV].float()), lse
-
-
-@functools.lru_cache(maxsize=None)
-def _cache(dtype, page, lens=tuple(LENS), alloc_all=False, seed=3):
-    """one paged latent cache per (dtype, page): stale rows and unnamed pages are NaN (_Paged). Returns (pool, its gathered rows)."""
-    dev = torch.device("cuda")
-    max_pages = max(1, max((ln + page - 1) // page for ln in lens)) + 1
-    rows = _rand((len(lens), 1, page * max_pages, E), dtype, dev, seed)
-    pc = _Paged(rows, rows, list(lens), page, max_pages, seed, alloc_all=alloc_all)
-    return pc, _gather(pc.k, pc.table, list(lens), page)[:, 0]
-
-
-def _nsplit(pkg, B, H, Sq, page, max_pages, paged=True):
-    a = pkg._lib.MlaArgs()
-    a.q.ptr = a.o.ptr = a.kv_cache = a.seqlens = 1 << 20
-    a.block_table = (1 << 20) if paged else None
-    for v, d in ((a.q, E), (a.o, EV)):
-        v.stride[0], v.stride[1], v.stride[2], v.stride[3] = H * Sq * d, Sq * d, d, 1
-    a.kv_stride[0], a.kv_stride[1], a.block_table_stride, a.max_pages, a.page_size = page * E, E, max_pages, max_pages, page
-    a.B, a.H, a.Sq, a.D, a.Dv, a.dtype, a.scale = B, H, Sq, E, EV, 1, SCALE
-    fwd = pkg._lib.mla_plan(a)[0]
-    return fwd[1] // (B * ((H * Sq + 63) // 64))
 
 
 def _check_case(pkg, q, pool, table, lens, rows, n, causal, dtype, what):
@@ -61,10 +23,6 @@ def _check_case(pkg, q, pool, table, lens, rows, n, causal, dtype, what):
     if not isinstance(n, torch.Tensor):   # log n exactly: 0 for n = 1, -inf for n = 0
         assert (lse[blind] == (0.0 if n == 1 else float("-inf"))).all(), f"{what}: lse of rows without a visible key"
     return out, lse
-
-
-def _n(kind, B, H, dev):
-    return _n_values((B, H), dev, 11) if kind == "tensor" else kind
 
 
 @pytest.mark.parametrize("n", [0, 1, "tensor"])

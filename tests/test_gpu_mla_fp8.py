@@ -9,7 +9,7 @@ import torch
 
 from kv_fp8 import F8, NAN_CODE, PagedCodes, finite_codes, is_nan_code, quantise, rand_codes, up, visible
 from kv_support import _bits, _capture, _check, _check_lse, _n_values, _rand
-from test_gpu_mla import E, EV, LENS, SCALE, _nsplit, _ref
+from mla_support import E, EV, LENS, SCALE, _nsplit, _ref
 
 pytestmark = pytest.mark.gpu
 DTYPES = [torch.float16, torch.bfloat16]

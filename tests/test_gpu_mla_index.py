@@ -146,7 +146,7 @@ def test_one_graph(pkg):
 
 def test_end_to_end_with_the_sparse_decode(pkg):
     """topk >= L: the list is every visible position, and flash_attention_n_mla_sparse behind it is flash_attention_n_mla"""
-    from test_gpu_mla import SCALE, _cache
+    from mla_support import SCALE, _cache
     dtype, Sq, lens = torch.bfloat16, 2, (0, 1, 65, 1100)
     latent, _ = _cache(dtype, 64, lens, False, 13)
     dev, nb = latent.k.device, len(lens)

@@ -5,54 +5,15 @@ import pytest
 import torch
 
 import kv_layout as kl
-from kv_support import _bh, _bits, _capture, _check, _check_lse, _gather, _Paged, _rand
-from test_gpu_mla import E, EV, LENS, SCALE, _cache, _n
-from test_gpu_mla import _nsplit as _dense_nsplit
-from test_mla_cpu import _args
+from kv_support import _bits, _capture, _check, _check_lse, _gather, _Paged, _rand
+from mla_support import E, LENS, SCALE, _cache, _entry_vis, _lists, _n
+from mla_support import _nsplit as _dense_nsplit
+from mla_support import _nsplit_sparse as _nsplit
+from mla_support import _ref_sparse as _ref
 
 pytestmark = pytest.mark.gpu
 DTYPES = [torch.float16, torch.bfloat16]
 SHAPES = [(5, 1), (16, 2), (64, 1), (128, 2)]   # a partial wave, one 32-row half, one full head block, two head blocks x two positions
-
-
-def _entry_vis(idx, lens, Sq, causal):
-    """[B, Sq, topk] bool: entry j is a key of position i iff 0 <= j < len_b and (causal) j <= i + len_b - Sq"""
-    ln = torch.as_tensor(lens, device=idx.device).view(-1, 1, 1)
-    vis = (idx >= 0) & (idx < ln)
-    return vis & (idx <= torch.arange(Sq, device=idx.device).view(1, -1, 1) + ln - Sq) if causal else vis
-
-
-def _ref(q, rows, idx, lens, n, causal):
-    """rows: [B, S, 576], the cache read through the table. Returns (out [B, H, Sq, 512], lse [B, H, Sq], vis) in fp32."""
-    B, H, Sq, _ = q.shape
-    vis = _entry_vis(idx, lens, Sq, causal)
-    g = rows.float()[torch.arange(B, device=q.device).view(-1, 1, 1), idx.clamp(0, rows.shape[1] - 1).long()]   # [B, Sq, topk, 576]
-    x = (SCALE * torch.einsum("bhqd,bqtd->bhqt", q.float(), g)).masked_fill(~vis[:, None], float("-inf"))
-    sink = _bh(torch.as_tensor(n, dtype=torch.float32, device=q.device), B, H).log()[..., None, None].expand(B, H, Sq, 1)
-    xs = torch.cat([sink, x], -1)
-    lse = torch.logsumexp(xs, -1)
-    p = torch.exp(xs - torch.where(torch.isfinite(lse), lse, torch.zeros_like(lse))[..., None])[..., 1:]
-    return torch.einsum("bhqt,bqtd->bhqd", p, g[..., :EV]), lse, vis
-
-
-def _lists(B, Sq, topk, capacity, seed, longest=None):
-    """seeded CPU lists from [-1, capacity): -1, beyond-length, causally hidden and duplicate entries all occur. topk = 2048: the second
-    half is -1, tile 2 (between live tiles) is -1, and tile 0 of element `longest` = (b, len) is 64 distinct positions every row sees"""
-    gen = torch.Generator().manual_seed(seed)
-    idx = torch.randint(-1, capacity, (B, Sq, topk), generator=gen, dtype=torch.int32)
-    if topk == 2048:
-        idx[..., 1024:] = -1
-        idx[..., 128:192] = -1
-        if longest is not None:
-            idx[longest[0], :, :64] = torch.randperm(longest[1] - Sq + 1, generator=gen)[:64].to(torch.int32)
-    return idx
-
-
-def _nsplit(pkg, B, H, Sq, topk, max_pages, page=64):
-    a = _args(pkg, B=B, H=H, Sq=Sq, max_pages=max_pages, block_table_stride=max_pages, page_size=page, block_table=(1 << 20) if max_pages > 1 else None)
-    s = pkg._lib.MlaSparse()
-    s.indices, s.stride_b, s.stride_q, s.topk = 1 << 20, Sq * topk, topk, topk
-    return pkg._lib.mla_sparse_plan(a, s)[0][1] // (B * Sq * ((H + 63) // 64))
 
 
 def _check_case(pkg, q, pool, table, idx, lens, rows, n, causal, dtype, what):

@@ -1,15 +1,12 @@
 """flash_attention_n_mla_sparse_fp8 on the GPU: the 656-byte rows against flash_attention_n_mla_sparse on their unpacked 16-bit rows (bit
-for bit) and against plain fp32 torch on those rows (test_gpu_mla_sparse._ref under the family's gates, tests/kv_support.py)."""
+for bit) and against plain fp32 torch on those rows (mla_support._ref_sparse under the family's gates, tests/kv_support.py)."""
 import pytest
 import torch
 
 import kv_layout as kl
 from kv_support import _bits, _capture, _check, _check_lse, _gather, _Paged, _rand
-from test_gpu_mla import E, EV, LENS, SCALE, _n
-from test_gpu_mla_sparse import _entry_vis, _lists, _ref
-from test_mla_cpu import _args
-from test_mla_sparse_cpu import _sparse
-from test_mla_sparse_fp8_cpu import _block
+from mla_support import E, EV, LENS, SCALE, _args, _block, _entry_vis, _lists, _n, _sparse
+from mla_support import _ref_sparse as _ref
 
 pytestmark = pytest.mark.gpu
 DTYPES = pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])

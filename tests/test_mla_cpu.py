@@ -5,28 +5,7 @@ import ctypes
 import pytest
 import torch
 
-EINVAL, EDTYPE, EHEADDIM, EALIGN, ESTRIDE, EUNSUPPORTED = -1, -2, -3, -4, -5, -7
-
-
-def _args(pkg, **over):
-    """a block every check accepts: B = 2, H = 16, Sq = 2, page 64 x 4 pages, bf16 (pointers are never dereferenced)"""
-    a = pkg._lib.MlaArgs()
-    base = 1 << 20
-    a.q.ptr = a.o.ptr = a.kv_cache = a.seqlens = a.block_table = base
-    for v, d in ((a.q, 576), (a.o, 512)):
-        v.stride[0], v.stride[1], v.stride[2], v.stride[3] = 16 * 2 * d, 2 * d, d, 1
-    a.kv_stride[0], a.kv_stride[1] = 64 * 576, 576
-    a.block_table_stride, a.max_pages, a.page_size = 4, 4, 64
-    a.B, a.H, a.Sq, a.D, a.Dv, a.dtype = 2, 16, 2, 576, 512, 1
-    a.scale, a.softmax_n, a.causal = 192 ** -0.5, 1.0, 1
-    for k, v in over.items():
-        obj, _, leaf = k.rpartition(".")
-        tgt = getattr(a, obj) if obj else a
-        if leaf.startswith("stride"):
-            tgt.stride[int(leaf[6:])] = v
-        else:
-            setattr(tgt, leaf, v)
-    return a
+from mla_support import EALIGN, EDTYPE, EHEADDIM, EINVAL, ESTRIDE, EUNSUPPORTED, _args
 
 
 def _codes(pkg, a):

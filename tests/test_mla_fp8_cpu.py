@@ -6,17 +6,7 @@ import ctypes
 import pytest
 import torch
 
-from test_mla_cpu import EALIGN, EDTYPE, EHEADDIM, EINVAL, EUNSUPPORTED, _args
-
-BASE = 1 << 20
-
-
-def _fp8(pkg, **over):
-    f = pkg._lib.MlaFp8()
-    f.kv_scale, f.sb, f.reserved = BASE, 1, 0
-    for k, v in over.items():
-        setattr(f, k, v)
-    return f
+from mla_support import BASE, EALIGN, EDTYPE, EHEADDIM, EINVAL, EUNSUPPORTED, _args, _fp8
 
 
 def _codes(pkg, a, f):

@@ -5,30 +5,8 @@ import ctypes
 import pytest
 import torch
 
-from test_mla_cpu import EALIGN, EDTYPE, EHEADDIM, EINVAL, ESTRIDE, EUNSUPPORTED
-
-BASE = 1 << 20
-
-
-def _args(pkg, **over):
-    """a block every check accepts: B = 3, Hi = 64, Sq = 2, page 64 x 96 pages, bf16, topk 2048 (pointers are never dereferenced)"""
-    a = pkg._lib.MlaIndexArgs()
-    a.q.ptr = a.w = a.k_cache = a.seqlens = a.block_table = a.indices = BASE
-    a.q.stride[0], a.q.stride[1], a.q.stride[2], a.q.stride[3] = 64 * 2 * 128, 2 * 128, 128, 1
-    a.w_stride[0], a.w_stride[1], a.w_stride[2] = 128, 2, 1
-    a.k_stride[0], a.k_stride[1] = 64 * 128, 128
-    a.block_table_stride, a.max_pages, a.page_size = 96, 96, 64
-    a.B, a.Hi, a.Sq, a.D, a.dtype, a.causal, a.topk = 3, 64, 2, 128, 1, 1, 2048
-    a.indices_stride[0], a.indices_stride[1] = 2 * 2048, 2048
-    a.logits_stride[0], a.logits_stride[1] = 2 * 6144, 6144
-    for k, v in over.items():
-        name, _, i = k.partition("#")
-        tgt = a.q if name == "q.stride" else a
-        if i:
-            getattr(tgt, name.rpartition(".")[2])[int(i)] = v
-        else:
-            setattr(a, name, v)
-    return a
+from mla_support import BASE, EALIGN, EDTYPE, EHEADDIM, EINVAL, ESTRIDE, EUNSUPPORTED
+from mla_support import _index_args as _args
 
 
 def _codes(pkg, a):

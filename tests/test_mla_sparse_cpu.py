@@ -5,17 +5,7 @@ import ctypes
 import pytest
 import torch
 
-from test_mla_cpu import EALIGN, EINVAL, EUNSUPPORTED, _args
-
-BASE = 1 << 20
-
-
-def _sparse(pkg, **over):
-    s = pkg._lib.MlaSparse()
-    s.indices, s.stride_b, s.stride_q, s.topk, s.reserved = BASE, 2 * 2048, 2048, 2048, 0
-    for k, v in over.items():
-        setattr(s, k, v)
-    return s
+from mla_support import BASE, EALIGN, EINVAL, EUNSUPPORTED, _args, _sparse
 
 
 def _codes(pkg, a, s):

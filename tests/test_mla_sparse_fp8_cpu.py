@@ -5,8 +5,7 @@ import ctypes
 import pytest
 import torch
 
-from test_mla_cpu import EALIGN, EINVAL, EUNSUPPORTED, _args
-from test_mla_sparse_cpu import BASE, _sparse
+from mla_support import BASE, EALIGN, EINVAL, EUNSUPPORTED, _args, _block, _sparse
 
 
 @pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16], ids=["f16", "bf16"])
@@ -30,12 +29,6 @@ def test_pack_unpack_and_the_scale_rule(pkg, dtype):
     assert torch.equal(s[0], torch.full((4,), 2.0 ** -30)) and not r[0, :512].any()
     assert s[1].tolist() == [2.0 ** -5, 2.0 ** -4, 2.0 ** -7, 2.0 ** -30] and r[1, 5] == 0x7E and r[1, 128 + 9] == 0x76   # 448; 224 under twice the scale
     assert s[2, 0] == 2.0 ** -8 and r[2, :4].tolist() == [0x7F, 0x7E, 0xFE, 0x78]
-
-
-def _block(pkg, stride=(64 * 656, 656), **over):
-    a = _args(pkg, **over)   # test_mla_cpu's block over 656-byte rows: kv_stride counts bytes
-    a.kv_stride[0], a.kv_stride[1] = stride
-    return a
 
 
 REFUSALS = [   # (what, block, list, code)

@@ -8,7 +8,9 @@ the library's attention families that no plan named: an instantiation no call ca
 The token-packed sliding-window and rotary K/V-cache calls (fasn_kvvarlen_window_plan, fasn_kvvarlen_rope_append_plan) are swept too, where the
 library has them: every head dim and dtype, one split and several, with and without new rows; their kernels count as families that must be reached.
 So is the shared-prefix decode (fasn_shared_prefix_plan) and its three kernels, and the prefix-groups decode (fasn_prefix_groups_plan)
-and its four."""
+and its four. So are the MLA calls (fasn_mla_plan, fasn_mla_fp8_plan, fasn_mla_sparse_plan, fasn_mla_sparse_fp8_plan, fasn_mla_index_plan): both
+dtypes, paged and dense, H x Sq from a partial wave to the 256-row limit, topk 64 and 2048, capacities of one split and of many, Hi 32 and 64; the
+fasn_mla_ forward, combine, logits and select kernels must be reached (the append kernels have no plan entry point and are not counted)."""
 import ctypes, hashlib, itertools, os, re, sys
 
 ARGV = [a for a in sys.argv[1:] if not a.startswith("--")]
@@ -156,10 +158,46 @@ def prefix_groups_calls():
                                       max_prefix_pages=sp.max_prefix_pages, reserved=0)))
 
 
+def mla_calls():
+    """(header, plan function, its operands) of the four MLA decode calls - a fasn_mla_args over dummy addresses, its cache strides in
+    elements of the call's row (576, or 656 bytes), with the FP8 scale or the index list - and of the indexer"""
+    if not hasattr(lib, "fasn_mla_plan"):   # (a tree from before these calls)
+        return
+    caches = ((True, 64, 4), (True, 256, 128), (False, 200, 1), (False, 32768, 1))   # (paged, page_size, max_pages): one split and many, each way
+    for dt, (H, Sq), B, (paged, page, pages) in itertools.product((0, 1), ((5, 1), (16, 2), (33, 2), (64, 1), (128, 2)), (1, 64), caches):
+        def block(row):
+            a = L.MlaArgs()
+            view(a.q, (H * Sq * 576, Sq * 576, 576, 1))
+            view(a.o, (H * Sq * 512, Sq * 512, 512, 1))
+            a.lse = a.kv_cache = a.seqlens = DUMMY
+            a.kv_stride[0], a.kv_stride[1] = page * row, row
+            a.block_table, a.block_table_stride, a.max_pages, a.page_size = (DUMMY if paged else None), pages, pages, page
+            a.B, a.H, a.Sq, a.D, a.Dv, a.dtype = B, H, Sq, 576, 512, dt
+            a.scale, a.softmax_n, a.causal = 192 ** -0.5, 1.0, 1
+            return a
+        hdr = f"dt={dt} H={H} Sq={Sq} B={B} {'paged' if paged else 'dense'} page={page} pages={pages}"
+        yield f"mla {hdr}", lib.fasn_mla_plan, (block(576),)
+        yield f"mla_fp8 {hdr}", lib.fasn_mla_fp8_plan, (block(576), L.MlaFp8(kv_scale=DUMMY, sb=1, reserved=0))
+        for topk in (64, 2048):
+            sp = L.MlaSparse(indices=DUMMY, stride_b=Sq * topk, stride_q=topk, topk=topk, reserved=0)
+            yield f"mla_sparse {hdr} topk={topk}", lib.fasn_mla_sparse_plan, (block(576), sp)
+            yield f"mla_sparse_fp8 {hdr} topk={topk}", lib.fasn_mla_sparse_fp8_plan, (block(656), sp)
+    for dt, Hi, (B, Sq), (paged, page, pages), topk in itertools.product((0, 1), (32, 64), ((1, 1), (3, 2), (64, 1)), caches, (64, 2048)):
+        a = L.MlaIndexArgs()
+        view(a.q, (Hi * Sq * 128, Sq * 128, 128, 1))
+        a.w = a.k_cache = a.seqlens = a.indices = DUMMY
+        a.w_stride[0], a.w_stride[1], a.w_stride[2] = Hi * Sq, Sq, 1
+        a.k_stride[0], a.k_stride[1] = page * 128, 128
+        a.block_table, a.block_table_stride, a.max_pages, a.page_size = (DUMMY if paged else None), pages, pages, page
+        a.B, a.Hi, a.Sq, a.D, a.dtype, a.causal, a.topk = B, Hi, Sq, 128, dt, 1, topk
+        a.indices_stride[0], a.indices_stride[1] = Sq * topk, topk
+        yield f"mla_index dt={dt} Hi={Hi} B={B} Sq={Sq} {'paged' if paged else 'dense'} page={page} pages={pages} topk={topk}", lib.fasn_mla_index_plan, (a,)
+
+
 def library_attention_kernels():
     table = spill_map.kernel_table(os.path.join(ROOT, "flash-attention-softmax-n_amd", "libfasn.so"))
     names = {re.sub(r"\(fasn::\w+(, fasn::\w+)*\)$", "", d).replace("void fasn::", "") for d in spill_map.demangle(list(table)).values()}
-    return names, {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel|fasn_kvshared_|fasn_kvgroups_", n)}
+    return names, {n for n in names if re.match(r"fasn_(fwd|bwd|f32)_|fasn_kvvarlen_(fwd_window|rope)_kernel|fasn_kvshared_|fasn_kvgroups_|fasn_mla_(?!\w*append)", n)}
 
 
 def witness_main():
@@ -187,7 +225,7 @@ def main():
         return witness_main()
     out, named, ncalls = [], set(), 0
     buf = ctypes.create_string_buffer(1 << 15)
-    for hdr, plan, operands in itertools.chain(kv_packed_calls(), shared_prefix_calls(), prefix_groups_calls()):
+    for hdr, plan, operands in itertools.chain(kv_packed_calls(), shared_prefix_calls(), prefix_groups_calls(), mla_calls()):
         ncalls += 1
         rc = plan(*operands, buf, len(buf))
         out.append(f"{hdr} rc={rc}")
